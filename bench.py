@@ -12,7 +12,11 @@ and the MAX over ranks is taken.  For N > 1 trajectories are sharded over ranks 
 data-path collective) and the decoded shards are all-gathered over RCCL in step blocks, overlapped with the remaining
 rollout.  Rank 0 prints ONE JSON line.
 
-What the line carries besides the contract fields: `roofline` (the dominant KERNEL -- the nine-tap f16x2 3x3 convolution --
+A plain run sets up, warms up, times the steps, writes the last timed step's decoded rollout if `--dump-outputs DIR` is
+given, and prints the line.  Everything else is measured or checked only with `--full` (each record can still be switched
+off there by its `--no-...` option).
+
+What a `--full` line carries besides the contract fields: `roofline` (the dominant KERNEL -- the nine-tap f16x2 3x3 convolution --
 HIP-event timed on the launch stream, with the other kernel forms of its class, the executed matrix-pipe FLOP and the
 whole-path floors beside it; formulas in DESIGN.md section 6e), `kernel_classes`, `check` (the first two trajectories are
 the golden fixture's inputs: their decoded fields are compared with the REAL reference's outputs), `check_stable` (the same
@@ -54,6 +58,22 @@ WORKLOADS = {
     "ns2d_64": ("NS2d 64^2 1-ch", "NS2d 64x64 1-channel", {}),
     "ns2d_mini": ("NS2d-mini 32^2 2-ch", "NS2d-mini 32x32 2-channel (plumbing)", {}),
 }
+DUMP_BYTES = 48 << 20       # --dump-outputs: at most this much per run
+
+
+def dump_outputs(d, y):
+    """--dump-outputs: y is the decoded rollout [B, T, C, H, W] (float32) the timed path returned in its last step.  It is
+    written whole to d/rollout.npy when it fits DUMP_BYTES; otherwise as [K, C, H, W]: the K frames that fit, drawn with a
+    fixed seed from the B*T frames and kept in (b, t) order, so that two builds are compared frame for frame."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    if y.numel() * 4 > DUMP_BYTES:
+        frames = y.reshape((-1,) + tuple(y.shape[2:]))
+        k = max(1, DUMP_BYTES // (frames[0].numel() * 4))
+        idx = np.sort(np.random.default_rng(0).choice(frames.shape[0], size=k, replace=False))
+        y = frames[torch.from_numpy(idx).to(y.device)]
+    np.save(os.path.join(d, "rollout.npy"), y.cpu().numpy())
 
 
 def build_model(preset, device, variant=None):
@@ -392,8 +412,16 @@ def main():
                          "the gathered buffer must equal the shard bit for bit).  Not a scaling measurement")
     ap.add_argument("--no-rccl-world1", action="store_true", help="skip the rccl_world1 sub-record (child process, --force-dist on the config-5 shard)")
     ap.add_argument("--no-check-stable", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side records: check, roofline + kernel_classes, check_stable, "
+                         "strict_fp32, rccl_world1, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the decoded rollout of the last timed step to DIR/rollout.npy (float32): the whole "
+                         "[B, T, C, H, W] array, or above %d MB a fixed seeded sample of its frames" % (DUMP_BYTES >> 20))
     ap.add_argument("--strict-fp32-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if not a.full:
+        a.no_roofline = a.no_check_stable = a.no_strict_fp32 = a.no_rccl_world1 = a.no_cpu_baseline = True
     if a.batch is None:
         a.batch = 32 if a.preset == "twophase_cond" else 64
     if a.rollout is None:
@@ -505,6 +533,8 @@ def main():
         dt = float(tt.item())
     traj_steps = float(n_gpus) * B * T * a.steps
     value = traj_steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out if chunked is None else chunked.assemble())
 
     if a.strict_fp32_child:      # child of the strict-fp32 sub-record: value and check only
         rec = {"value": value, "ms_per_step": dt / a.steps * 1e3}
@@ -561,7 +591,7 @@ def main():
         return
 
     # what was timed is what is checked: the first two trajectories of rank 0 against the real reference's outputs
-    if rank == 0 and fixture and B >= 2:
+    if rank == 0 and a.full and fixture and B >= 2:
         src = out if chunked is None else torch.cat(chunked.bufs, dim=1)
         result["check"] = golden_check(a.preset, T, src[:2].cpu().numpy(), fixture)
 

@@ -196,6 +196,33 @@ def test_bench_force_dist_runs_the_collective_with_one_rank():
     assert mg["bytes_contributed_per_rank"] == 4 * 3 * 5 * 2 * 8 * 8 and mg["bytes_received_per_rank"] == 0
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`--dump-outputs DIR` writes the last timed step's decoded rollout: whole when it fits the budget, else the same
+    seeded sample of whole frames on every run."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist-backend", "gloo",
+                        "--plumbing-only", "--steps", "3", "--warmup", "1", "--batch", "3", "--rollout", "5",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    rec = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+    y = np.load(str(tmp_path / "rollout.npy"))
+    assert y.dtype == np.float32 and y.shape == (3, 5, 2, 8, 8)
+    assert all((y[:, t] == t + 1).all() for t in range(5))       # plumbing stand-in: frame t of rank 0 holds t + 1
+    sys.path.insert(0, ROOT)
+    import bench
+    full = torch.arange(4 * 6 * 2 * 3 * 3, dtype=torch.float32).reshape(4, 6, 2, 3, 3)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 5 * 2 * 3 * 3 * 4)
+    bench.dump_outputs(str(tmp_path / "a"), full)
+    bench.dump_outputs(str(tmp_path / "b"), full)
+    a, b = np.load(str(tmp_path / "a" / "rollout.npy")), np.load(str(tmp_path / "b" / "rollout.npy"))
+    assert a.shape == (5, 2, 3, 3) and (a == b).all()
+    idx = a[:, 0, 0, 0].astype(int) // (2 * 3 * 3)
+    assert (np.diff(idx) > 0).all() and all((a[i] == full.reshape(24, 2, 3, 3)[j].numpy()).all() for i, j in enumerate(idx))
+
+
 def test_bench_workload_labels_follow_the_preset():
     """metric / workload strings are derived from the preset (they were hard-coded to NS2d in round 1)."""
     sys.path.insert(0, ROOT)

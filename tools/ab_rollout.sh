@@ -11,7 +11,7 @@ for rep in 1 2; do
   for lib in "$@"; do
     i=$((i+1))
     if [ "$lib" = main ]; then unset LNS_HIP_LIB; else export LNS_HIP_LIB=$R/$lib; fi
-    timeout -k 10 300 python bench.py $FLAGS > $O/b${i}_$rep.log 2>$O/b${i}_$rep.err || { echo FAIL $lib; tail -5 $O/b${i}_$rep.err; exit 1; }
+    timeout -k 10 300 python bench.py --full $FLAGS > $O/b${i}_$rep.log 2>$O/b${i}_$rep.err || { echo FAIL $lib; tail -5 $O/b${i}_$rep.err; exit 1; }
     python3 - "$lib" $O/b${i}_$rep.log <<'PY' | tee -a $O/summary.txt
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -15,7 +15,7 @@ QUIET="--no-cpu-baseline --no-strict-fp32 --no-check --no-check-stable --no-rccl
 # 2. kernel stats of the single-stream pass, every configuration (steps 4 + warmup 1 + the roofline pass = 6 rollouts)
 stats() {   # name, bench args...
   local n=$1; shift
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/st_$n -- python3 $R/bench.py --serial --steps 4 --warmup 1 $QUIET "$@" > $O/st_$n.log 2>&1 || fail "stats $n" $O/st_$n.log
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/st_$n -- python3 $R/bench.py --full --serial --steps 4 --warmup 1 $QUIET "$@" > $O/st_$n.log 2>&1 || fail "stats $n" $O/st_$n.log
   local f=$(find $O/st_$n -name "*kernel_stats.csv" | head -1); cp $f $O/${TAG}_serial_kernel_stats$n.csv
   grep '^{"metric"' $O/st_$n.log | tail -1 > $O/st_$n.json
 }
@@ -39,13 +39,13 @@ python3 tools/make_traffic_json.py $F $W $O/${TAG}_traffic.json > $O/traffic.txt
 # the bench lines quote the counter passes of THIS box and build: put them where bench.py looks (profiles/ of this copy)
 cp $O/${TAG}_pmc.json $O/${TAG}_traffic.json $R/profiles/
 # 3b. bench lines
-timeout -k 10 900 python bench.py > $O/bench_main.log 2>$O/bench_main.err || fail "bench main" $O/bench_main.err
+timeout -k 10 900 python bench.py --full > $O/bench_main.log 2>$O/bench_main.err || fail "bench main" $O/bench_main.err
 line $O/bench_main.log $O/${TAG}_bench_line.json headline
-timeout -k 10 400 python bench.py --rollout 256 --no-strict-fp32 --no-cpu-baseline --no-rccl-world1 > $O/b256.log 2>$O/b256.err || fail "bench T256" $O/b256.err
+timeout -k 10 400 python bench.py --full --rollout 256 --no-strict-fp32 --no-cpu-baseline --no-rccl-world1 > $O/b256.log 2>$O/b256.err || fail "bench T256" $O/b256.err
 line $O/b256.log $O/${TAG}_bench_line_ns2d_T256.json T256
-timeout -k 10 400 python bench.py --preset sw_96x192x5 --no-strict-fp32 --no-cpu-baseline --no-rccl-world1 > $O/bsw.log 2>$O/bsw.err || fail "bench sw" $O/bsw.err
+timeout -k 10 400 python bench.py --full --preset sw_96x192x5 --no-strict-fp32 --no-cpu-baseline --no-rccl-world1 > $O/bsw.log 2>$O/bsw.err || fail "bench sw" $O/bsw.err
 line $O/bsw.log $O/${TAG}_bench_line_sw_96x192x5.json sw
-timeout -k 10 400 python bench.py --preset twophase_cond --batch 32 --rollout 128 --no-strict-fp32 --no-cpu-baseline --no-rccl-world1 > $O/btp.log 2>$O/btp.err || fail "bench twophase" $O/btp.err
+timeout -k 10 400 python bench.py --full --preset twophase_cond --batch 32 --rollout 128 --no-strict-fp32 --no-cpu-baseline --no-rccl-world1 > $O/btp.log 2>$O/btp.err || fail "bench twophase" $O/btp.err
 line $O/btp.log $O/${TAG}_bench_line_twophase_cond.json twophase_cond
 echo "bench done"
 

@@ -3,7 +3,7 @@
 
     python tools/roofline_from_stats.py <kernel_stats.csv> <bench_line.json> [rollouts in the profile]
 
-The CSV comes from `rocprofv3 --kernel-trace --stats -- python3 bench.py --serial --steps K --warmup W --no-check ...`
+The CSV comes from `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --serial --steps K --warmup W --no-check ...`
 (single stream: no co-running kernels); `rollouts` = K + W + 1 (the roofline pass), default: inferred from the call count of
 the FABlock sandwich kernel (two launches per decode step... i.e. from the bench line's launch counts).  For every kernel FORM
 of the bench line (`roofline.entries`) the kernels of that form are summed in the CSV and
