@@ -142,6 +142,7 @@ int lns_finalize_weights(lns_engine* e, int device);
  *                     most this many MB (it then stays in the 256 MB Infinity Cache between the three kernels instead of going
  *                     to HBM three times); 0 = whole batch per launch.  Cached plans are rebuilt.  Default: LNS_FA_CHUNK_MB
  *   "fa_fused_gpb"    plane groups (of 16) one block of the fused FABlock kernel walks; 0 = automatic.  Cached plans are rebuilt.
+ *   "eval_max_steps"  longest horizon of lns_rollout_eval / lns_rollout_latent_eval (it sizes their partial sums; default 1024)
  *   "track_nonfinite" 1: lns_check_finite also remembers the plan runs whose amax record has been reused since (the
  *                     earlier steps / decode groups of a rollout): one extra one-block launch per plan run (default 0)
  * One option selects an ARITHMETIC FORM (results differ at rounding level, ~2e-7 relative on the decoded field):
@@ -189,6 +190,62 @@ int lns_rollout(lns_engine* e, const float* x, const float* param, int B, int T,
  * out [B,T,...]; z_last (nullable) receives the latent after step T. */
 int lns_rollout_latent(lns_engine* e, const float* z_in, const float* param, int B, int T, int to_x,
                        float* out, float* z_last, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- streaming validation rollout: predict and score without the [B,T] field ---------------------------------
+ * Reference: the body of the validation loop, train_stage2_ns2d.py:249-263 (same text in train_stage2_SW.py and
+ * train_stage2_twophase*.py, where denormalize is the per-channel / closed-wall / clamp form):
+ *     y_hat = model.predict(x, T, to_x=True); y_hat, y = denormalize(y_hat), denormalize(y)
+ *     frame_wise = relative_lp_loss(y_hat, y, reduce_dim=(3, 4)); seq_wise = relative_lp_loss(y_hat, y, reduce_dim=(1, 3, 4))
+ * i.e. lns_rollout followed by lns_metric_rel_l2{,_ch}, without the decoded rollout [B,T,C,Ly,Lx] between them: the
+ * decode of every group of steps writes a per-decode-stream frame buffer, a scoring kernel on the same stream reduces
+ * it against the truth planes of those steps to the metric's per-plane sums, and the metric's finish kernel runs once
+ * on the caller's stream after the streams have joined.  The per-plane arithmetic and reduction order are those of
+ * lns_metric_rel_l2{,_ch} (one device function shared by the kernels), so frame_out / seq_out hold the bits the two
+ * calls produce (for y_hat and y_true of equal 16-byte alignment, as any allocator gives), whatever the scheduling options.
+ *
+ * lns_eval_spec: the denormalisation, i.e. the arguments of lns_metric_rel_l2 (per_channel = 0: mean, std) or of
+ * lns_metric_rel_l2_ch (per_channel = 1: mean_c / std_c / flags_c (LNS_METRIC_*) per channel, clamp_lo / clamp_hi;
+ * in_channels <= 8), and eps for both.  size = sizeof(lns_eval_spec): another value is LNS_EINVAL. */
+typedef struct lns_eval_spec {
+    uint32_t size;
+    int32_t per_channel;
+    float mean, std, eps;
+    float mean_c[8], std_c[8];
+    int32_t flags_c[8];
+    float clamp_lo, clamp_hi;
+} lns_eval_spec;
+
+/* Workspace of the two calls below for batch B: the lns_prepare(B) layout, byte for byte (lns_prepare and the sizes
+ * the other run calls need do not change), followed by
+ *     "decode_streams" frame buffers of decode_group * B * in_channels * Ly * Lx * 4 bytes   (decode_group as resolved
+ *                                                                                             for B when the option is 0)
+ *     the partial sums [B]["eval_max_steps"][in_channels][2] floats,
+ * each rounded up to 256 bytes.  The horizon is bounded by the option "eval_max_steps" (lns_set_option; default 1024,
+ * 1 .. 65536): T (T_total) above it is LNS_EINVAL.  NS2d 128 x 128 x 3, B = 64, three decode streams: 37.7 MB + 1.6 MB,
+ * against the 805 MB (T = 64) / 3.22 GB (T = 256) of the rollout tensor.  Changing a scheduling option changes the size. */
+int lns_rollout_eval_workspace_bytes(lns_engine* e, int B, size_t* bytes);
+
+/* x [B,Cin,Ly,Lx], y_true [B,T,Cin,Ly,Lx] (normalised, like the decoded rollout) -> frame_out [B,T,Cin], seq_out [B,Cin]
+ * (either may be NULL, not both).  keep_steps_host: n_keep ascending 0-based steps (HOST array, read during the call)
+ * whose decoded frames are copied to frames_out [B,n_keep,Cin,Ly,Lx] -- the reference plots y_hat[:10, ::5, 0]
+ * (train_stage2_ns2d.py:259-263); n_keep = 0: keep_steps_host / frames_out are ignored.
+ * param, batch limits, trace / timing modes (single stream) and lns_check_finite: as for lns_rollout.
+ * LNS_EINVAL (bad argument, named by lns_last_error; decided before any device work), LNS_ENOMEM (workspace smaller
+ * than lns_rollout_eval_workspace_bytes), LNS_ESTATE (no autoencoder / propagator). */
+int lns_rollout_eval(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                     const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
+                     float* frames_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same from a latent state (lns_rollout_latent; chunked evaluations): scores steps t0 .. t0+T-1 of
+ * y_true [B,T_total,Cin,Ly,Lx].  The per-plane sums of a chunk stay in `workspace` at their [B][T_total][Cin][2] slots;
+ * the call that completes the horizon (t0 + T == T_total) runs the finish kernel and writes frame_out [B,T_total,Cin] and
+ * seq_out [B,Cin]; earlier chunks leave them untouched.  The chunks of one evaluation must therefore use the same
+ * workspace, and nothing else may write its evaluation part in between (lns_rollout & co. do not: they stay inside the
+ * lns_prepare bytes).  keep_steps_host: steps of THIS chunk, 0 .. T-1.  z_last (nullable): the latent after step t0+T. */
+int lns_rollout_latent_eval(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                            int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                            const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* Post-run health check.  Every kernel of a plan records, per sample, the running maximum of |y| of the tensor it
  * produces (the side channel from which the split-operand convolutions derive their activation scale); a NaN or inf

@@ -57,11 +57,26 @@ class LnsConfig(ctypes.Structure):
     ]
 
 
+LNS_METRIC_MAX_CH = 8
+_F32x8 = ctypes.c_float * LNS_METRIC_MAX_CH
+
+
+class LnsEvalSpec(ctypes.Structure):
+    """Mirror of `struct lns_eval_spec` (include/lns.h): the denormalisation of the streaming evaluation."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("per_channel", _I32),
+        ("mean", ctypes.c_float), ("std", ctypes.c_float), ("eps", ctypes.c_float),
+        ("mean_c", _F32x8), ("std_c", _F32x8), ("flags_c", ctypes.c_int32 * LNS_METRIC_MAX_CH),
+        ("clamp_lo", ctypes.c_float), ("clamp_hi", ctypes.c_float),
+    ]
+
+
 # every symbol include/lns.h declares (tests check the library exports them all)
 SYMBOLS = [
     "lns_create_error", "lns_create", "lns_destroy", "lns_last_error", "lns_num_params",
     "lns_param_info", "lns_set_weight", "lns_finalize_weights", "lns_latent_shape", "lns_prepare",
     "lns_encode", "lns_encode_cond", "lns_encode_affine", "lns_decode", "lns_propagate", "lns_rollout", "lns_rollout_latent", "lns_check_finite", "lns_set_option",
+    "lns_rollout_eval_workspace_bytes", "lns_rollout_eval", "lns_rollout_latent_eval",
     "lns_train_workspace_bytes", "lns_train_forward", "lns_train_backward",
     "lns_trace_enable", "lns_trace_count", "lns_trace_info", "lns_trace_copy",
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
@@ -75,7 +90,7 @@ _lib = None
 def build(force=False):
     """Compile liblns_hip.so in-tree (hipcc --offload-arch=gfx950)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)
-            if f.endswith((".hip", ".cpp", ".h"))] + [os.path.join(_HERE, "..", "include", "lns.h")]
+            if f.endswith((".hip", ".cpp", ".h", ".inc"))] + [os.path.join(_HERE, "..", "include", "lns.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -125,6 +140,11 @@ def lib():
     L.lns_propagate.argtypes = [vp, vp, vp, i, i, i, vp, vp, c.c_size_t, vp]
     L.lns_rollout.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, c.c_size_t, vp]
     L.lns_rollout_latent.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, c.c_size_t, vp]
+    if hasattr(L, "lns_rollout_eval"):
+        sp, ip = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int)
+        L.lns_rollout_eval_workspace_bytes.argtypes = [vp, i, c.POINTER(c.c_size_t)]
+        L.lns_rollout_eval.argtypes = [vp, vp, vp, vp, i, i, sp, vp, vp, ip, i, vp, vp, c.c_size_t, vp]
+        L.lns_rollout_latent_eval.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, vp, c.c_size_t, vp]
     if hasattr(L, "lns_check_finite"):      # (absent from older builds loaded through LNS_HIP_LIB for A/B runs)
         L.lns_check_finite.argtypes = [vp, i, vp, c.c_size_t, vp]
     if hasattr(L, "lns_set_option"):

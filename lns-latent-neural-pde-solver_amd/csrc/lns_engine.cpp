@@ -1866,6 +1866,25 @@ static int ws_layout(lns_engine* e, int B, WsLayout* L) {
     return LNS_OK;
 }
 
+// Streaming evaluation (lns_rollout_eval): the rollout layout above, untouched, then one frame buffer per decode stream
+// (the decode output of a group, [kdec][B][C][Ly][Lx]) and the metric's per-plane sums [B][eval_max_steps][C][2].
+struct EvalLayout { size_t fbuf_off, fbuf_stride, part_off, total; };
+static void eval_layout(const lns_engine* e, int B, const WsLayout& L, EvalLayout* E) {
+    const size_t xper = (size_t)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx;
+    E->fbuf_off = round_up_sz(L.total, 256);
+    E->fbuf_stride = round_up_sz((size_t)L.kdec * B * xper * 4, 256);
+    E->part_off = E->fbuf_off + (size_t)L.ndec * E->fbuf_stride;
+    E->total = E->part_off + round_up_sz((size_t)B * e->opt_eval_max_steps * e->cfg.in_channels * 2 * 4, 256);
+}
+
+// what rollout_loop does with a decoded group in evaluation mode (instead of writing it to `out`)
+struct EvalRun {
+    MetricGroupArgs m;             // y, part, shapes, denormalisation; frames / kk / y_t / p_t are set per group
+    int t0;                        // step of y / part that the loop's step 0 is
+    char* fbuf; size_t fbuf_stride;
+    const int* keep; int n_keep; float* frames_out;
+};
+
 // second stream + events for the propagate / decode overlap (created once, owned by the engine)
 static int ensure_overlap_objects(lns_engine* e) {
     if (e->side_stream) return LNS_OK;
@@ -1993,6 +2012,7 @@ int lns_set_option(lns_engine* e, const char* name, long value) {
     if (n == "decode_group") { if (value < 0 || value > 8) return LNS_EINVAL; e->opt_decode_group = (int)value; }
     else if (n == "decode_streams") { if (value < 1 || value > NDEC) return LNS_EINVAL; e->opt_decode_streams = (int)value; }
     else if (n == "overlap") e->opt_overlap = value != 0;
+    else if (n == "eval_max_steps") { if (value < 1 || value > 65536) return LNS_EINVAL; e->opt_eval_max_steps = (int)value; }
     else if (n == "track_nonfinite") e->opt_track_nonfinite = value != 0;
     else if (n == "fa_fused" || n == "fa_fused_gpb") {
         if (n == "fa_fused_gpb" && (value < 0 || value > 64)) return LNS_EINVAL;
@@ -2160,8 +2180,11 @@ int lns_propagate(lns_engine* e, const float* z_in, const float* param, int B, i
 // ring, and every finished group is decoded by one launch set at batch B * kdec on one of the decode streams
 // (round-robin, one arena each), ordered by events, so the small latent-resolution kernels of later steps overlap
 // the large decode kernels of earlier ones.
+// Evaluation mode (ev != null; to_x): the decode of a group writes that decode stream's frame buffer instead of `out`,
+// the scoring kernel and the copies of the kept steps follow on the same decode stream -- in stream order before the
+// next decode that reuses the buffer, so the event scheme is the rollout's own.
 static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param, int B, int T, int to_x, float* out,
-                        float* latents_out, float* z_last, const WsLayout& L, char* base) {
+                        float* latents_out, float* z_last, const WsLayout& L, char* base, const EvalRun* ev = nullptr) {
     Plan* pp;
     int rc;
     if ((rc = get_plan(e, PK_PROP, B, e->lat_H, e->lat_W, &pp))) return rc;
@@ -2219,7 +2242,7 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
     }
     char* ring = base + L.ring_off;
     std::vector<char> used(ngroup, 0);
-    int g = 0, gi = 0;
+    int g = 0, gi = 0, ki = 0;                       // ki: next entry of ev->keep
     for (int t = 0; t < T;) {
         const int kk = std::min(kdec, T - t);
         char* gbase = ring + (size_t)g * L.group_bytes;
@@ -2246,8 +2269,19 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
             HIPCHK(e, hipStreamWaitEvent(dstream[d], ev_z[g], 0));
         }
         ext[EX_IN] = {gbase, zper};
-        ext[EX_OUT] = {out + (long)t * xper, (long)T * xper, xper, B};
+        float* fb = ev ? reinterpret_cast<float*>(ev->fbuf + (size_t)d * ev->fbuf_stride) : nullptr;
+        if (ev) ext[EX_OUT] = {fb, xper};            // [kk][B][xper]: launch sample s = j * B + b
+        else ext[EX_OUT] = {out + (long)t * xper, (long)T * xper, xper, B};
         if ((rc = (overlap ? rd[d] : r).run(*pd, ext, darena[d]))) return rc;
+        if (ev) {
+            MetricGroupArgs m = ev->m;
+            m.frames = fb; m.kk = kk; m.y_t = ev->t0 + t; m.p_t = ev->t0 + t;
+            HIPCHK(e, launch_metric_group(m, dstream[d]));
+            for (; ki < ev->n_keep && ev->keep[ki] < t + kk; ++ki)       // ascending: each kept step lies in one group
+                HIPCHK(e, hipMemcpy2DAsync(ev->frames_out + (long)ki * xper, (size_t)ev->n_keep * xper * 4,
+                                           fb + (long)(ev->keep[ki] - t) * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
+                                           hipMemcpyDeviceToDevice, dstream[d]));
+        }
         if (overlap) { HIPCHK(e, hipEventRecord(ev_free[g], dstream[d])); used[g] = 1; }
         t += kk;
         g = (g + 1) % ngroup;
@@ -2309,6 +2343,138 @@ int lns_rollout_latent(lns_engine* e, const float* z_in, const float* param, int
     if ((rc = arm_sticky(e, r.stream))) return rc;
     ExtT z0 = {z_in, (long)e->lat_C * e->lat_H * e->lat_W};
     if ((rc = rollout_loop(e, r, z0, param, B, T, to_x, out, nullptr, z_last, L, static_cast<char*>(ws)))) return rc;
+    return r.finish();
+}
+
+// ---- streaming validation rollout (include/lns.h) --------------------------------------------------------------
+static int einval(lns_engine* e, const char* what) { e->err = what; return LNS_EINVAL; }
+
+// argument checks shared by the two evaluation calls; nothing here touches the device
+static int eval_check_args(lns_engine* e, const void* first, const char* first_name, const float* y_true, int B, int T, int t0,
+                           int T_total, const lns_eval_spec* spec, const float* frame_out, const float* seq_out,
+                           const int* keep, int n_keep, const float* frames_out) {
+    if (!first) { e->err = fmt("%s is null", first_name); return LNS_EINVAL; }
+    if (!y_true) return einval(e, "y_true is null");
+    if (B <= 0) return einval(e, "B must be positive");
+    if (T <= 0) return einval(e, "T must be positive");
+    if (t0 < 0 || (long)t0 + T > T_total) { e->err = fmt("t0 + T = %d + %d exceeds T_total = %d (or t0 < 0)", t0, T, T_total); return LNS_EINVAL; }
+    if (!frame_out && !seq_out) return einval(e, "frame_out and seq_out are both null");
+    if (!spec || spec->size != sizeof(lns_eval_spec)) return einval(e, "spec is null or its size field is not sizeof(lns_eval_spec)");
+    if (spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "spec: the per-channel form needs in_channels <= 8");
+    if (n_keep < 0) return einval(e, "n_keep is negative");
+    if (n_keep > 0) {
+        if (!keep) return einval(e, "keep_steps is null but n_keep > 0");
+        if (!frames_out) return einval(e, "frames_out is null but n_keep > 0");
+        for (int i = 0; i < n_keep; ++i)
+            if (keep[i] < 0 || keep[i] >= T || (i > 0 && keep[i] <= keep[i - 1])) {
+                e->err = fmt("keep_steps must be ascending steps in [0, %d): entry %d is %d", T, i, keep[i]);
+                return LNS_EINVAL;
+            }
+    }
+    if (int brc = check_batch(e, B)) return brc;
+    if (T_total > e->opt_eval_max_steps) {
+        e->err = fmt("%d steps exceed the option eval_max_steps = %d (it sizes the evaluation workspace)", T_total, e->opt_eval_max_steps);
+        return LNS_EINVAL;
+    }
+    return LNS_OK;
+}
+
+static void eval_fill(const lns_engine* e, EvalRun* ev, const float* y_true, int B, int t0, int T_total, const lns_eval_spec* spec,
+                      const int* keep, int n_keep, float* frames_out, char* base, const EvalLayout& E) {
+    MetricGroupArgs& m = ev->m;
+    m.frames = nullptr; m.y = y_true; m.part = reinterpret_cast<float*>(base + E.part_off);
+    m.B = B; m.C = e->cfg.in_channels; m.H = e->cfg.Ly; m.W = e->cfg.Lx; m.kk = 0;
+    m.y_T = T_total; m.y_t = 0; m.p_T = T_total; m.p_t = 0;
+    m.per_channel = spec->per_channel != 0;
+    m.mean = spec->mean; m.sd = spec->std;
+    for (int c = 0; c < LNS_METRIC_MAX_CH; ++c) {       // as lns_metric_rel_l2_ch fills it
+        const bool in = c < m.C;
+        m.spec.mean[c] = in ? spec->mean_c[c] : 0.0f;
+        m.spec.std[c] = in ? spec->std_c[c] : 1.0f;
+        m.spec.flags[c] = in ? spec->flags_c[c] : 0;
+    }
+    m.spec.lo = spec->clamp_lo; m.spec.hi = spec->clamp_hi;
+    ev->t0 = t0;
+    ev->fbuf = base + E.fbuf_off; ev->fbuf_stride = E.fbuf_stride;
+    ev->keep = keep; ev->n_keep = n_keep; ev->frames_out = frames_out;
+}
+
+int lns_rollout_eval_workspace_bytes(lns_engine* e, int B, size_t* bytes) {
+    if (!e) return LNS_EINVAL;
+    if (B <= 0) return einval(e, "B must be positive");
+    if (int brc = check_batch(e, B)) return brc;
+    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
+    DeviceGuard dg(e);
+    WsLayout L; EvalLayout E;
+    if (int rc = ws_layout(e, B, &L)) return rc;
+    eval_layout(e, B, L, &E);
+    if (bytes) *bytes = E.total;
+    return LNS_OK;
+}
+
+static int check_eval_ws(lns_engine* e, const EvalLayout& E, void* ws, size_t bytes) {
+    if (!ws || bytes < E.total) { e->err = fmt("evaluation workspace too small: need %zu bytes, got %zu", E.total, bytes); return LNS_ENOMEM; }
+    return LNS_OK;
+}
+
+int lns_rollout_eval(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                     const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
+                     float* frames_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!e) return LNS_EINVAL;
+    if (int arc = eval_check_args(e, x, "x", y_true, B, T, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out)) return arc;
+    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
+    if ((e->cfg.prop_kind == LNS_PROP_CONDITIONAL || e->cfg.cond_encoder) && !param) { e->err = "conditional model needs param"; return LNS_EINVAL; }
+    DeviceGuard dg(e);
+    WsLayout L; EvalLayout E; int rc;
+    if ((rc = ws_layout(e, B, &L))) return rc;
+    eval_layout(e, B, L, &E);
+    if ((rc = check_eval_ws(e, E, ws, ws_bytes))) return rc;
+    Plan* pe;
+    if ((rc = get_plan(e, PK_ENC, B, 0, 0, &pe))) return rc;
+    const lns_config& c = e->cfg;
+    const long zper = (long)e->lat_C * e->lat_H * e->lat_W;
+    char* base = static_cast<char*>(ws);
+    EvalRun ev;
+    eval_fill(e, &ev, y_true, B, 0, T, spec, keep_steps_host, n_keep, frames_out, base, E);
+    Runner r(e, static_cast<hipStream_t>(stream));
+    ExtT ext[EX_COUNT];
+    ext[EX_PARAM] = {param, 1};
+    begin_run(e, ws, B);
+    if ((rc = arm_sticky(e, r.stream))) return rc;
+    // encode once: x -> z0                                    (train_stage2_ns2d.py:144)
+    ext[EX_IN] = {x, (long)c.in_channels * c.Ly * c.Lx};
+    ext[EX_OUT] = {base, zper};
+    if ((rc = r.run(*pe, ext, base + L.arena_off))) return rc;
+    ExtT z0 = {base, zper};
+    if ((rc = rollout_loop(e, r, z0, param, B, T, 1, nullptr, nullptr, nullptr, L, base, &ev))) return rc;
+    // every plane's pair is in place once the decode streams have joined: frame- and sequence-wise ratios
+    HIPCHK(e, launch_metric_finish(ev.m.part, B, T, c.in_channels, spec->eps, frame_out, seq_out, r.stream));
+    return r.finish();
+}
+
+int lns_rollout_latent_eval(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                            int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                            const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* ws,
+                            size_t ws_bytes, void* stream) {
+    if (!e) return LNS_EINVAL;
+    if (int arc = eval_check_args(e, z_in, "z_in", y_true, B, T, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out)) return arc;
+    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
+    if (e->cfg.prop_kind == LNS_PROP_CONDITIONAL && !param) { e->err = "conditional propagator needs param"; return LNS_EINVAL; }
+    DeviceGuard dg(e);
+    WsLayout L; EvalLayout E; int rc;
+    if ((rc = ws_layout(e, B, &L))) return rc;
+    eval_layout(e, B, L, &E);
+    if ((rc = check_eval_ws(e, E, ws, ws_bytes))) return rc;
+    char* base = static_cast<char*>(ws);
+    EvalRun ev;
+    eval_fill(e, &ev, y_true, B, t0, T_total, spec, keep_steps_host, n_keep, frames_out, base, E);
+    Runner r(e, static_cast<hipStream_t>(stream));
+    begin_run(e, ws, B);
+    if ((rc = arm_sticky(e, r.stream))) return rc;
+    ExtT z0 = {z_in, (long)e->lat_C * e->lat_H * e->lat_W};
+    if ((rc = rollout_loop(e, r, z0, param, B, T, 1, nullptr, nullptr, z_last, L, base, &ev))) return rc;
+    if (t0 + T == T_total)   // the horizon is complete: the pairs of the earlier chunks are in the workspace
+        HIPCHK(e, launch_metric_finish(ev.m.part, B, T_total, e->cfg.in_channels, spec->eps, frame_out, seq_out, r.stream));
     return r.finish();
 }
 

@@ -161,6 +161,7 @@ struct lns_engine {
     // scheduling options (lns_set_option; defaults from the LNS_* environment variables of the same meaning)
     int opt_decode_group = 1;      // steps decoded per launch set; 0 = automatic (about 256 samples per launch set)
     int opt_decode_streams = 3;
+    int opt_eval_max_steps = 1024; // longest horizon of lns_rollout_eval (sizes the [B][steps][C][2] partial sums of its workspace)
     int opt_overlap = 1;           // propagator / decode streams; 0 = everything on the caller's stream
     int opt_prop_priority = 0;     // 1: the propagator's side stream is created with the highest priority
     // FABlock2D: in_proj -> sandwich -> to_out run per group of samples whose 512-plane tensor is at most this many MB, so

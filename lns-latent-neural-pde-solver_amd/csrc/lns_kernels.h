@@ -323,6 +323,18 @@ hipError_t launch_metric_rel_l2_ch(const float* yhat, const float* y, int B, int
                                    const MetricChannelSpec& spec, float eps, float* frame_out, float* seq_out,
                                    float* scratch, hipStream_t s);
 
+// Streaming evaluation (lns_rollout_eval): per-plane sums of one decoded group of steps, frames [kk][B][C][H*W], against
+// y [B][y_T][C][H*W] at steps y_t .. y_t+kk-1 into part [B][p_T][C][2] at steps p_t .. p_t+kk-1 -- the scalar form
+// (mean, sd) or the per-channel one (spec), with the per-plane body of the kernels above; then the same finish kernel.
+struct MetricGroupArgs {
+    const float* frames; const float* y; float* part;
+    int B, C, H, W, kk, y_T, y_t, p_T, p_t, per_channel;
+    float mean, sd;
+    MetricChannelSpec spec;
+};
+hipError_t launch_metric_group(const MetricGroupArgs& a, hipStream_t s);
+hipError_t launch_metric_finish(const float* part, int B, int T, int C, float eps, float* frame_out, float* seq_out, hipStream_t s);
+
 // per-sample max |x| (bit patterns) of a [B, n] tensor with batch stride x_bs into amax [B][LNS_AMAX_SUB] (atomic max)
 hipError_t launch_amax(const float* x, long x_bs, long n, int B, unsigned* amax, hipStream_t s);
 hipError_t launch_amax_sticky(const unsigned* amax, int n, unsigned* flag, hipStream_t s);

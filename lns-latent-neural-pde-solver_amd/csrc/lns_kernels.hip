@@ -4910,16 +4910,18 @@ hipError_t launch_vec_linear(const VecLinearArgs& a, hipStream_t s) {
 // rollouts.  One block per (b, t, c) plane -> (sum of squared denormalised error, sum of squared denormalised
 // truth); a second tiny kernel forms the frame-wise and sequence-wise ratios.  Fixed reduction order.
 // ===========================================================================
-__global__ __launch_bounds__(256) void metric_plane_kernel(const float* yhat, const float* y, int HW, float mean, float sd,
-                                                           float* part) {
-    __shared__ float red[8];
-    const long plane = blockIdx.x;
-    const float* a = yhat + plane * HW;
-    const float* g = y + plane * HW;
-    float d2 = 0.0f, g2 = 0.0f;
-    const int n4 = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(g)) & 15) == 0 ? HW / 4 : 0;
+// The per-plane body, shared by the whole-rollout kernels and the group-scoring kernel of the streaming evaluation
+// (one definition: the latter must produce the former's bits).  kVecA: the prediction plane is 16-byte aligned (float4
+// loads); without it the same four elements are loaded one by one and summed in the same order.  n4: float4 groups of
+// the plane that are summed in the vector order (0 when the truth plane is not 16-byte aligned), the rest in element order.
+template <bool kVecA>
+__device__ __forceinline__ void metric_plane_sums(const float* a, const float* g, int HW, int n4, float mean, float sd,
+                                                  float& d2, float& g2) {
     for (int i = threadIdx.x; i < n4; i += 256) {
-        const float4 p = reinterpret_cast<const float4*>(a)[i], q = reinterpret_cast<const float4*>(g)[i];
+        float4 p;
+        if (kVecA) p = reinterpret_cast<const float4*>(a)[i];
+        else p = make_float4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]);
+        const float4 q = reinterpret_cast<const float4*>(g)[i];
         const float e0 = (p.x - q.x) * sd, e1 = (p.y - q.y) * sd, e2 = (p.z - q.z) * sd, e3 = (p.w - q.w) * sd;
         const float t0 = q.x * sd + mean, t1 = q.y * sd + mean, t2 = q.z * sd + mean, t3 = q.w * sd + mean;
         d2 += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
@@ -4929,29 +4931,16 @@ __global__ __launch_bounds__(256) void metric_plane_kernel(const float* yhat, co
         const float e = (a[i] - g[i]) * sd, t = g[i] * sd + mean;
         d2 += e * e; g2 += t * t;
     }
-    d2 = wave_sum(d2); g2 = wave_sum(g2);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = d2; red[4 + (threadIdx.x >> 6)] = g2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[plane * 2] = (red[0] + red[1]) + (red[2] + red[3]);
-        part[plane * 2 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
-    }
 }
 
 // Per-channel statistics and the two-phase dataset's boundary handling (dataset/twophase_flow_stage2.py:370-390,
 // dataset/Stage2_SW.py:60-72): v = x*std[c] + mean[c]; flag 1: the four wall rows/columns are set to zero;
 // flag 2: v is clamped to [lo, hi].  Both tensors go through the same map, as the reference denormalises both.
-__global__ __launch_bounds__(256) void metric_plane_ch_kernel(const float* yhat, const float* y, int C, int H, int W,
-                                                              MetricChannelSpec spec, float* part) {
-    __shared__ float red[8];
-    const long plane = blockIdx.x;
-    const int c = (int)(plane % C);
+__device__ __forceinline__ void metric_plane_ch_sums(const float* a, const float* g, int c, int H, int W,
+                                                     const MetricChannelSpec& spec, float& d2, float& g2) {
     const float sd = spec.std[c], mean = spec.mean[c];
     const bool walls = spec.flags[c] & 1, clampv = spec.flags[c] & 2;
     const int HW = H * W;
-    const float* a = yhat + plane * HW;
-    const float* g = y + plane * HW;
-    float d2 = 0.0f, g2 = 0.0f;
     for (int i = threadIdx.x; i < HW; i += 256) {
         const int r = i / W, col = i - r * W;
         float p = a[i] * sd + mean, q = g[i] * sd + mean;
@@ -4960,13 +4949,64 @@ __global__ __launch_bounds__(256) void metric_plane_ch_kernel(const float* yhat,
         const float e = p - q;
         d2 += e * e; g2 += q * q;
     }
+}
+
+// thread sums -> the plane's pair: wave sums, then the fixed four-wave sum (red: 8 floats of LDS)
+__device__ __forceinline__ void metric_plane_store(float d2, float g2, float* red, float* out2) {
     d2 = wave_sum(d2); g2 = wave_sum(g2);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = d2; red[4 + (threadIdx.x >> 6)] = g2; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        part[plane * 2] = (red[0] + red[1]) + (red[2] + red[3]);
-        part[plane * 2 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+        out2[0] = (red[0] + red[1]) + (red[2] + red[3]);
+        out2[1] = (red[4] + red[5]) + (red[6] + red[7]);
     }
+}
+
+__global__ __launch_bounds__(256) void metric_plane_kernel(const float* yhat, const float* y, int HW, float mean, float sd,
+                                                           float* part) {
+    __shared__ float red[8];
+    const long plane = blockIdx.x;
+    const float* a = yhat + plane * HW;
+    const float* g = y + plane * HW;
+    float d2 = 0.0f, g2 = 0.0f;
+    const int n4 = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(g)) & 15) == 0 ? HW / 4 : 0;
+    metric_plane_sums<true>(a, g, HW, n4, mean, sd, d2, g2);
+    metric_plane_store(d2, g2, red, part + plane * 2);
+}
+
+__global__ __launch_bounds__(256) void metric_plane_ch_kernel(const float* yhat, const float* y, int C, int H, int W,
+                                                              MetricChannelSpec spec, float* part) {
+    __shared__ float red[8];
+    const long plane = blockIdx.x;
+    const int c = (int)(plane % C);
+    const int HW = H * W;
+    float d2 = 0.0f, g2 = 0.0f;
+    metric_plane_ch_sums(yhat + plane * HW, y + plane * HW, c, H, W, spec, d2, g2);
+    metric_plane_store(d2, g2, red, part + plane * 2);
+}
+
+// Streaming evaluation: the decode output of one group of steps, frames [kk][B][C][H*W] (a per-decode-stream buffer),
+// against the truth planes y[b][y_t + j][c] of y [B][y_T][C][H*W]; the pair of plane (b, p_t + j, c) goes to its slot of
+// part [B][p_T][C][2].  One block per plane, the bodies above: what metric_plane{,_ch}_kernel would write for the
+// same plane of a stored rollout.  Every slot is written by exactly one block: no atomics, no dependence on the grouping.
+__global__ __launch_bounds__(256) void metric_group_kernel(MetricGroupArgs a) {
+    __shared__ float red[8];
+    const int q = blockIdx.x;                          // (j * B + b) * C + c
+    const int c = q % a.C, s = q / a.C, b = s % a.B, j = s / a.B;
+    const int HW = a.H * a.W;
+    const float* f = a.frames + (long)q * HW;
+    const float* g = a.y + (((long)b * a.y_T + a.y_t + j) * a.C + c) * HW;
+    float* out2 = a.part + (((long)b * a.p_T + a.p_t + j) * a.C + c) * 2;
+    float d2 = 0.0f, g2 = 0.0f;
+    if (a.per_channel) {
+        metric_plane_ch_sums(f, g, c, a.H, a.W, a.spec, d2, g2);
+    } else {
+        // the stored rollout's plane (b, t, c) has the truth plane's offset, hence (equal base alignment) its alignment
+        const int n4 = (reinterpret_cast<uintptr_t>(g) & 15) == 0 ? HW / 4 : 0;
+        if ((reinterpret_cast<uintptr_t>(f) & 15) == 0) metric_plane_sums<true>(f, g, HW, n4, a.mean, a.sd, d2, g2);
+        else metric_plane_sums<false>(f, g, HW, n4, a.mean, a.sd, d2, g2);
+    }
+    metric_plane_store(d2, g2, red, out2);
 }
 
 __global__ void metric_finish_kernel(const float* part, int B, int T, int C, float eps, float* frame_out, float* seq_out) {
@@ -4995,6 +5035,16 @@ hipError_t launch_metric_rel_l2_ch(const float* yhat, const float* y, int B, int
                                    float* scratch, hipStream_t s) {
     hipLaunchKernelGGL(metric_plane_ch_kernel, dim3((unsigned)((long)B * T * C)), dim3(256), 0, s, yhat, y, C, H, W, spec, scratch);
     hipLaunchKernelGGL(metric_finish_kernel, dim3((B * C + 63) / 64), dim3(64), 0, s, scratch, B, T, C, eps, frame_out, seq_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_metric_group(const MetricGroupArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(metric_group_kernel, dim3((unsigned)((long)a.kk * a.B * a.C)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_metric_finish(const float* part, int B, int T, int C, float eps, float* frame_out, float* seq_out, hipStream_t s) {
+    hipLaunchKernelGGL(metric_finish_kernel, dim3((B * C + 63) / 64), dim3(64), 0, s, part, B, T, C, eps, frame_out, seq_out);
     return hipGetLastError();
 }
 

@@ -446,6 +446,26 @@ class LatentDynamics(_Hosted):
         x = self._fields(x)
         return self._engine(x).rollout(x, steps, param=param, to_x=to_x, return_latents=return_latents)
 
+    @torch.no_grad()
+    def validate(self, x, y, *rest, keep_steps=(), **norm):
+        """validate(x, y, **norm) -- conditional: validate(x, y, param, **norm): the body of the reference's validation
+        loop (train_stage2_ns2d.py:249-263) in one call,
+            y_hat = denormalize(predict(x, T, to_x=True)); y = denormalize(y)
+            frame_wise = relative_lp_loss(y_hat, y, reduce_dim=(3, 4)); seq_wise = relative_lp_loss(y_hat, y, reduce_dim=(1, 3, 4))
+        with T = y.shape[1] and the decoded rollout scored group by group as it is decoded: y_hat [B,T,C,Ly,Lx] is never
+        stored.  `norm` restates the dataset's denormalize as in `metrics.relative_l2` (mean, std, eps,
+        zero_wall_channels, clamp_channels, clamp; e.g. `**metrics.twophase_spec(...)`).  Returns (frame_wise [B,T,C],
+        seq_wise [B,C], decoded frames [B,len(keep_steps),C,Ly,Lx] or None -- the few the reference plots)."""
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("validate() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if rest:
+            raise TypeError("validate() takes (x, y, param, **norm)" if self._conditional else "validate() takes (x, y, **norm)")
+        x = self._fields(x)
+        return self._engine(x).rollout_eval(x, y, param=param, keep_steps=keep_steps, **norm)
+
 
 class LatentDynamicsSW(LatentDynamics):                 # train_stage2_SW.py:90-159
     _family = "sw_half_periodic"

@@ -106,6 +106,37 @@ def make_config(args, ae_kind=None, prop_kind=None, ae_prefix="", prop_prefix=""
     return c
 
 
+def eval_spec(C, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
+    """`lns_eval_spec` from the arguments of `metrics.relative_l2`, with its rule for the choice between the scalar and
+    the per-channel kernel: per-channel as soon as a statistic is a sequence or a channel is zeroed / clamped."""
+    spec = _lib.LnsEvalSpec()
+    spec.size = ctypes.sizeof(_lib.LnsEvalSpec)
+    spec.eps = float(eps)
+    spec.clamp_lo, spec.clamp_hi = float(clamp[0]), float(clamp[1])
+    per_channel = (not isinstance(mean, (int, float))) or (not isinstance(std, (int, float))) or \
+        len(zero_wall_channels) > 0 or len(clamp_channels) > 0
+    spec.per_channel = int(per_channel)
+    if not per_channel:
+        spec.mean, spec.std = float(mean), float(std)
+        return spec
+    if C > _lib.LNS_METRIC_MAX_CH:
+        raise ValueError("per-channel statistics: at most %d channels" % _lib.LNS_METRIC_MAX_CH)
+
+    def per_c(v):
+        v = [float(v)] * C if isinstance(v, (int, float)) else [float(e) for e in v]
+        if len(v) != C:
+            raise ValueError("per-channel statistics need %d entries" % C)
+        return v
+    m, sd = per_c(mean), per_c(std)
+    for c in range(_lib.LNS_METRIC_MAX_CH):
+        spec.mean_c[c], spec.std_c[c], spec.flags_c[c] = (m[c], sd[c], 0) if c < C else (0.0, 1.0, 0)
+    for c in zero_wall_channels:
+        spec.flags_c[c] |= 1
+    for c in clamp_channels:
+        spec.flags_c[c] |= 2
+    return spec
+
+
 class Engine:
     """One lns_engine handle (one per GPU; not thread-safe)."""
 
@@ -167,7 +198,8 @@ class Engine:
 
     def set_option(self, name, value):
         """Scheduling options of the rollout (include/lns.h lns_set_option): decode_group, decode_streams, overlap,
-        prop_priority, track_nonfinite, fa_chunk_mb, fa_fused_gpb.  Results never depend on them.  "fa_fused" (default 2; 1 = single-buffered kernel, same bits; 0 = off) selects
+        prop_priority, track_nonfinite, fa_chunk_mb, fa_fused_gpb, eval_max_steps (longest horizon of rollout_eval; it sizes
+        the evaluation workspace).  Results never depend on them.  "fa_fused" (default 2; 1 = single-buffered kernel, same bits; 0 = off) selects
         the arithmetic form of FABlock2D at 64 x 64 planes (in_proj inside the sandwich kernel): ~2e-7 relative on the fields."""
         self._check(self._L.lns_set_option(self._h, name.encode(), int(value)), "lns_set_option")
         self._ws.clear()                      # the workspace size depends on the options
@@ -314,6 +346,84 @@ class Engine:
                                                int(steps), int(bool(to_x)), out.data_ptr(), z_last.data_ptr(),
                                                ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent")
         return out, z_last
+
+    # -- streaming validation rollout (include/lns.h "streaming validation rollout") --------------------------------
+    def _eval_common(self, first, y, steps, t0, keep_steps, norm):
+        """Shared argument handling of rollout_eval / rollout_latent_eval -> (y, B, T, T_total, spec, keep array, frames)."""
+        import torch
+        y = self._dev(y)
+        c = self.cfg
+        if y.dim() != 5 or y.shape[0] != first.shape[0] or tuple(y.shape[2:]) != (c.in_channels, c.Ly, c.Lx):
+            raise LnsError("ground truth must be [B, T, %d, %d, %d] with the input's batch, got %s"
+                           % (c.in_channels, c.Ly, c.Lx, tuple(y.shape)))
+        if y.device != first.device:
+            raise LnsError("ground truth is on %s but the input is on %s" % (y.device, first.device))
+        B, T_total = int(y.shape[0]), int(y.shape[1])
+        T = T_total - t0 if steps is None else int(steps)
+        if t0 < 0 or T <= 0 or t0 + T > T_total:
+            raise LnsError("steps %d from step %d do not fit the %d steps of the ground truth" % (T, t0, T_total))
+        spec = eval_spec(c.in_channels, **norm)
+        keep = [int(s) for s in keep_steps]
+        arr = (ctypes.c_int * len(keep))(*keep) if keep else None
+        frames = torch.empty((B, len(keep), c.in_channels, c.Ly, c.Lx), dtype=torch.float32, device=y.device) if keep else None
+        return y, B, T, T_total, spec, arr, len(keep), frames
+
+    def _eval_workspace(self, B, device):
+        n = ctypes.c_size_t(0)
+        self._check(self._L.lns_rollout_eval_workspace_bytes(self._h, int(B), ctypes.byref(n)), "lns_rollout_eval_workspace_bytes")
+        return self._workspace(B, device, min_bytes=int(n.value))
+
+    def rollout_eval(self, x, y, steps=None, param=None, keep_steps=(), **norm):
+        """The validation loop's predict -> denormalize -> relative_lp_loss pair (train_stage2_ns2d.py:249-263) without the
+        [B,T,C,Ly,Lx] rollout: every decoded group of steps is scored against the normalised ground truth y [B,T,C,Ly,Lx]
+        right after its decode.  `norm`: mean / std / eps / zero_wall_channels / clamp_channels / clamp as in
+        `metrics.relative_l2` (so `**metrics.twophase_spec(...)` works).  steps < T scores the first `steps` of y.
+        Returns (frame_wise [B,T,C], seq_wise [B,C], frames [B,len(keep_steps),C,Ly,Lx] or None): the same bits as
+        `metrics.relative_l2(rollout(x, T), y, ...)` and `rollout(x, T)[:, keep_steps]`."""
+        import torch
+        x = self._dev(x)
+        if steps is not None and int(steps) < y.shape[1]:
+            y = y[:, :int(steps)]
+        y, B, T, _, spec, keep, n_keep, frames = self._eval_common(x, y, steps, 0, keep_steps, norm)
+        frame = torch.empty((B, T, self.cfg.in_channels), dtype=torch.float32, device=x.device)
+        seq = torch.empty((B, self.cfg.in_channels), dtype=torch.float32, device=x.device)
+        p = self._param(param, x)
+        with torch.cuda.device(x.device):
+            ws = self._eval_workspace(B, x.device)
+            self._check(self._L.lns_rollout_eval(self._h, x.data_ptr(), p.data_ptr() if p is not None else None, y.data_ptr(),
+                                                 B, T, ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(), keep, n_keep,
+                                                 frames.data_ptr() if frames is not None else None, ws.data_ptr(),
+                                                 ws.numel(), self._stream(x)), "lns_rollout_eval")
+        return frame, seq, frames
+
+    def rollout_latent_eval(self, z, y, steps=None, t0=0, param=None, keep_steps=(), frame=None, seq=None, **norm):
+        """rollout_eval continued from a latent: scores steps t0 .. t0+steps-1 of y [B,T_total,C,Ly,Lx] (steps=None: to
+        the end).  Chunks of one evaluation must follow each other on the same engine and batch: their per-plane sums
+        stay in the engine's workspace, and the call that completes the horizon (t0 + steps == T_total) writes `frame`
+        [B,T_total,C] and `seq` [B,C] (pass the tensors along, or take them from the last chunk's return value).
+        keep_steps are relative to the chunk.  Returns (frame, seq, frames or None, z after the last step)."""
+        import torch
+        z = self._dev(z)
+        t0 = int(t0)
+        y, B, T, T_total, spec, keep, n_keep, frames = self._eval_common(z, y, steps, t0, keep_steps, norm)
+        C = self.cfg.in_channels
+        if frame is None:
+            frame = torch.empty((B, T_total, C), dtype=torch.float32, device=z.device)
+        if seq is None:
+            seq = torch.empty((B, C), dtype=torch.float32, device=z.device)
+        for t, shape in ((frame, (B, T_total, C)), (seq, (B, C))):
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != z.device:
+                raise LnsError("preallocated result must be a contiguous fp32 tensor of shape %s on the input's device" % (shape,))
+        z_last = torch.empty_like(z)
+        p = self._param(param, z)
+        with torch.cuda.device(z.device):
+            ws = self._eval_workspace(B, z.device)
+            self._check(self._L.lns_rollout_latent_eval(self._h, z.data_ptr(), p.data_ptr() if p is not None else None,
+                                                        y.data_ptr(), B, T, t0, T_total, ctypes.byref(spec), frame.data_ptr(),
+                                                        seq.data_ptr(), keep, n_keep,
+                                                        frames.data_ptr() if frames is not None else None, z_last.data_ptr(),
+                                                        ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_eval")
+        return frame, seq, frames, z_last
 
     # -- training rollout of the propagator (include/lns.h "training rollout") ------------------------------------
     def _ptr_array(self, tensors):

@@ -144,3 +144,35 @@ def gather_metrics(frame, seq, group=None):
     dist.all_gather_into_tensor(f_all, frame.contiguous(), group=group)
     dist.all_gather_into_tensor(s_all, seq.contiguous(), group=group)
     return f_all, s_all
+
+
+class ShardedEval:
+    """Evaluation counterpart of EndGatherRollout: every rank runs the streaming validation rollout on its own slice of
+    the global batch (`shard_bounds`) and ONLY the reductions -- frame-wise [b,T,C] and sequence-wise [b,C] errors --
+    are all-gathered (`gather_metrics`); the decoded fields never leave the rank, and with `Engine.rollout_eval` /
+    `LatentDynamics.validate` as the callable they are never stored either.
+
+    evaluate(*shards) -> (frame [b,T,C], seq [b,C], ...): called with the rank's slice of every tensor given to run()
+    (x, y[, param]); anything it returns after the first two entries stays local (`self.local`).
+    All ranks must hold the same local batch size (all_gather_into_tensor)."""
+
+    def __init__(self, evaluate, global_batch, group=None):
+        self.evaluate, self.group = evaluate, group
+        on = dist.is_initialized()
+        self.world = dist.get_world_size(group) if on else 1
+        self.rank = dist.get_rank(group) if on else 0
+        self.lo, self.hi = shard_bounds(int(global_batch), self.rank, self.world)
+        self.bytes_contributed_per_rank = 0
+        self.bytes_received_per_rank = 0        # what the last run() received from the OTHER ranks
+        self.local = ()
+
+    def run(self, *tensors):
+        """(frame [world*b,T,C], seq [world*b,C]) in rank order, i.e. the rows of the global batch."""
+        out = self.evaluate(*[None if t is None else t[self.lo:self.hi] for t in tensors])
+        frame, seq = out[0], out[1]
+        self.local = tuple(out[2:])
+        own = frame.numel() * frame.element_size() + seq.numel() * seq.element_size()
+        self.bytes_contributed_per_rank = own
+        f_all, s_all = gather_metrics(frame, seq, group=self.group)
+        self.bytes_received_per_rank = (f_all.numel() * f_all.element_size() + s_all.numel() * s_all.element_size()) - own
+        return f_all, s_all
