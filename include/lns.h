@@ -271,13 +271,73 @@ int lns_check_finite(lns_engine* e, int B, void* workspace, size_t workspace_byt
  * (an optimiser updates them in place between calls) -- lns_set_weight / lns_finalize_weights are not involved.
  * All contractions run on the exact-fp32 matrix instruction.  Plain propagators (NS2d, SW, two-phase) and the
  * conditional one (train_stage2_twophase_conditional.py:25-121; `param` [B], no gradient w.r.t. it).  The same
- * workspace and parameter values must be used for the backward call. */
+ * workspace and parameter values must be used for the backward call.
+ * lns_train_workspace_bytes needs no device for the size; when the process has one it also builds the shape's plan (device
+ * index maps) on the caller's current device, so that the first run call does not. */
 int lns_train_workspace_bytes(lns_engine* e, int B, int h, int w, int T, size_t* bytes);
 int lns_train_forward(lns_engine* e, const float* const* params, const float* z_in, const float* param_or_null,
                       int B, int h, int w, int T, float* z_pred, void* workspace, size_t workspace_bytes, void* stream);
 int lns_train_backward(lns_engine* e, const float* const* params, const float* z_in, const float* z_pred,
                        const float* grad_z_pred, int B, int h, int w, int T, float* const* grads, float* grad_z_in,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- device-resident training step: loss, backward through time and Adam ---------------------------------------
+ * Reference: the body of the stage-2 training loop, train_stage2_ns2d.py:210-216 (same text in train_stage2_SW.py and
+ * train_stage2_twophase*.py):
+ *     optim.zero_grad(); loss = model(z_in, z_out[, param], F.smooth_l1_loss); loss.backward(); optim.step()
+ * with optim = torch.optim.Adam(propagator parameters) (:179).  The calls below only enqueue kernels on `stream`: no
+ * host synchronisation, no device allocation and no copy from host memory (the first call for a shape builds the
+ * training plan, as lns_train_forward does).  Their argument errors (LNS_EINVAL / LNS_ESTATE / LNS_ENOMEM, named by the
+ * error message) are decided before any device work.
+ *
+ * F.smooth_l1_loss(pred, target, reduction='mean', beta) (train_stage2_ns2d.py:213) and its gradient in one pass:
+ *     d = pred - target;  l = 0.5 d^2 / beta if |d| < beta else |d| - 0.5 beta;  *loss_out = mean(l)   (device float)
+ *     grad_out (nullable, n floats) = dL/dpred = (d / beta if |d| < beta else sign(d)) / n
+ * scratch: device, scratch_floats >= ceil(n / LNS_SL1_CHUNK) floats of block partial sums.  The sums are combined in a
+ * fixed order that does not depend on the launch: the loss is bit-reproducible.  beta > 0 (torch's beta = 0 is L1: use
+ * another kernel), 1 <= n <= LNS_SL1_CHUNK * 2^30 (LNS_EINVAL otherwise).  No engine: the message of a refused call is lns_create_error()'s (this thread). */
+#define LNS_SL1_CHUNK 4096
+int lns_loss_smooth_l1(const float* pred, const float* target, int64_t n, float beta, float* loss_out, float* grad_out,
+                       float* scratch, size_t scratch_floats, void* stream);
+
+/* torch.optim.Adam.step() (train_stage2_ns2d.py:216; no amsgrad, not maximize; L2 weight_decay added to the gradient):
+ *     g' = g + weight_decay p;  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2
+ *     p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * of many tensors in one launch (the pointer table travels in the kernel-argument block: 96 tensors per launch).
+ * `step` is the 1-based count of THIS update; it lives on the host, the bias corrections are computed there in double.
+ * size = sizeof(lns_adam_spec): another value is LNS_EINVAL, as are lr < 0, betas outside [0, 1), eps <= 0,
+ * weight_decay < 0 and step < 1. */
+typedef struct lns_adam_spec {
+    uint32_t size;
+    uint32_t reserved;                          /* 0 */
+    double lr, beta1, beta2, eps, weight_decay; /* doubles, as torch keeps them: 1 - beta2 formed from a float beta2 is off by 1e-5 */
+    int64_t step;
+} lns_adam_spec;
+/* params / grads / exp_avg / exp_avg_sq: arrays of lns_num_params() DEVICE pointers indexed like lns_param_info (any
+ * tensor of the table, not only the propagator's); an entry is updated when all four are non-null and left untouched
+ * otherwise.  Runs on the caller's current device. */
+int lns_adam_step(lns_engine* e, float* const* params, const float* const* grads, float* const* exp_avg,
+                  float* const* exp_avg_sq, const lns_adam_spec* spec, void* stream);
+/* The same for any n fp32 tensors of numel[i] elements (0 < numel < 2^31): the optimiser of lns_amd/optim.py.  No engine:
+ * the message of a refused call is lns_create_error()'s. */
+int lns_adam_step_tensors(int n, float* const* params, const float* const* grads, float* const* exp_avg,
+                          float* const* exp_avg_sq, const int64_t* numel, const lns_adam_spec* spec, void* stream);
+
+/* The whole step: lns_train_forward -> smooth-L1 loss and dL/dz_pred -> lns_train_backward -> Adam, enqueued on `stream`
+ * in that order.  z_in [B,1,c,h,w] (= [B,c,h,w]), z_out [B,T,c,h,w]: the pre-encoded targets as the reference's loader
+ * yields them; params / grads / exp_avg / exp_avg_sq as above.  `grads` are the caller's buffers and hold this step's
+ * gradients afterwards (to clip or log); *loss_out (device float) is the loss BEFORE the update, like `loss` in the
+ * reference loop.  adam_spec == NULL: loss and gradients only (exp_avg / exp_avg_sq are ignored).  With adam_spec every
+ * propagator parameter needs all four pointers (LNS_EINVAL otherwise).  LNS_ESTATE: the engine has no propagator;
+ * (both calls);
+ * LNS_ENOMEM: workspace smaller than lns_train_step_workspace_bytes, which is lns_train_workspace_bytes followed by
+ * z_pred, dL/dz_pred (B*T*c*h*w floats each) and the loss partials, each rounded up to 256 bytes.  Noise injection
+ * (z_in + randn * noise_level, train_stage2_ns2d.py:211-212) stays the caller's. */
+int lns_train_step_workspace_bytes(lns_engine* e, int B, int h, int w, int T, size_t* bytes);
+int lns_train_step(lns_engine* e, float* const* params, const float* z_in, const float* z_out, const float* param_or_null,
+                   int B, int h, int w, int T, float beta, float* const* grads, float* const* exp_avg,
+                   float* const* exp_avg_sq, const lns_adam_spec* adam_spec, float* loss_out, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* ---- diagnostics -------------------------------------------------------- */
 /* Layer trace: when enabled the run calls synchronise after every reference

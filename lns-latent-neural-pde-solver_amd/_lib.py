@@ -71,6 +71,17 @@ class LnsEvalSpec(ctypes.Structure):
     ]
 
 
+LNS_SL1_CHUNK = 4096
+
+
+class LnsAdamSpec(ctypes.Structure):
+    """Mirror of `struct lns_adam_spec` (include/lns.h): torch.optim.Adam's hyper-parameters and the 1-based step count."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("step", ctypes.c_int64),
+    ]
+
+
 # every symbol include/lns.h declares (tests check the library exports them all)
 SYMBOLS = [
     "lns_create_error", "lns_create", "lns_destroy", "lns_last_error", "lns_num_params",
@@ -78,6 +89,7 @@ SYMBOLS = [
     "lns_encode", "lns_encode_cond", "lns_encode_affine", "lns_decode", "lns_propagate", "lns_rollout", "lns_rollout_latent", "lns_check_finite", "lns_set_option",
     "lns_rollout_eval_workspace_bytes", "lns_rollout_eval", "lns_rollout_latent_eval",
     "lns_train_workspace_bytes", "lns_train_forward", "lns_train_backward",
+    "lns_loss_smooth_l1", "lns_adam_step", "lns_adam_step_tensors", "lns_train_step_workspace_bytes", "lns_train_step",
     "lns_trace_enable", "lns_trace_count", "lns_trace_info", "lns_trace_copy",
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
     "lns_op_conv2d", "lns_op_conv_pair_stress", "lns_op_groupnorm_stats", "lns_op_attention", "lns_op_fa_sandwich", "lns_op_fourier_block",
@@ -153,6 +165,13 @@ def lib():
         L.lns_train_workspace_bytes.argtypes = [vp, i, i, i, i, c.POINTER(c.c_size_t)]
         L.lns_train_forward.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp, c.c_size_t, vp]
         L.lns_train_backward.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, c.c_size_t, vp]
+    if hasattr(L, "lns_train_step"):
+        ap = c.POINTER(LnsAdamSpec)
+        L.lns_loss_smooth_l1.argtypes = [vp, vp, c.c_int64, c.c_float, vp, vp, vp, c.c_size_t, vp]
+        L.lns_adam_step.argtypes = [vp, vp, vp, vp, vp, ap, vp]
+        L.lns_adam_step_tensors.argtypes = [i, vp, vp, vp, vp, i64p, ap, vp]
+        L.lns_train_step_workspace_bytes.argtypes = [vp, i, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_train_step.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, c.c_float, vp, vp, vp, ap, vp, vp, c.c_size_t, vp]
     L.lns_build_has.argtypes = [c.c_char_p]
     L.lns_trace_enable.argtypes = [vp, i]
     L.lns_trace_count.argtypes = [vp]

@@ -75,11 +75,17 @@ int train_same_device(lns_engine* e, int device, const void* p, const char* what
     return LNS_OK;
 }
 
-int tconv_setup(lns_engine* e, TConv& t, int B, int Cin, int Cout, int H, int W, int k, int dil, int my, int mx) {
+// channel counts and pads of a convolution: all the workspace layout needs (no device, no tiling)
+int tconv_dims(TConv& t, int Cin, int Cout, int k, int dil) {
     t.Cin = Cin; t.Cout = Cout; t.k = k; t.dil = dil;
     const int kc_log2 = k == 3 ? 3 : 5;
     t.Cin_pad = (Cin + (1 << kc_log2) - 1) / (1 << kc_log2) * (1 << kc_log2);
     t.Cout_pad = Cout <= 32 ? 32 : (Cout <= 64 ? 64 : (Cout + 127) / 128 * 128);
+    return kc_log2;
+}
+
+int tconv_setup(lns_engine* e, TConv& t, int B, int Cin, int Cout, int H, int W, int k, int dil, int my, int mx) {
+    const int kc_log2 = tconv_dims(t, Cin, Cout, k, dil);
     const int p = dil * (k - 1) / 2;
     const int pad[4] = {p, p, p, p};
     ConvGeom g;
@@ -114,19 +120,29 @@ int tconv_setup(lns_engine* e, TConv& t, int B, int Cin, int Cout, int H, int W,
     return LNS_OK;
 }
 
+// sizes of a plan without its device maps: what train_layout reads (the workspace size is known without a GPU)
+int train_plan_dims(lns_engine* e, int B, int H, int W, TrainPlan& p) {
+    const lns_config& c = e->cfg;
+    if (c.prop_kind != LNS_PROP_PLAIN && c.prop_kind != LNS_PROP_CONDITIONAL) { e->err = "training rollout: engine has no propagator"; return LNS_EINVAL; }
+    if (H <= 0 || W <= 0 || H > 4096 || W > 4096) { e->err = "training rollout: bad latent size"; return LNS_EINVAL; }
+    p.B = B; p.D = c.prop_n_embd; p.c = c.latent_dim; p.nb = c.prop_n_block; p.dil = c.prop_dilation;
+    p.H = H; p.W = W;
+    p.cond = c.prop_kind == LNS_PROP_CONDITIONAL; p.E = c.cond_emb_dim;
+    tconv_dims(p.in_proj, p.c, p.D, 1, 1); tconv_dims(p.in_proj_T, p.D, p.c, 1, 1);
+    tconv_dims(p.c_d1, p.D, p.D, 3, 1); tconv_dims(p.c_dd, p.D, p.D, 3, p.dil); tconv_dims(p.c_1, p.D, p.D, 1, 1);
+    tconv_dims(p.out_proj, p.D, p.c, 1, 1); tconv_dims(p.out_proj_T, p.c, p.D, 1, 1);
+    return LNS_OK;
+}
+
 int get_train_plan(lns_engine* e, int device, int B, int H, int W, TrainPlan** out) {
     const TrainKey key{e, device, ((long)B << 32) | ((long)H << 16) | (long)W};
     std::lock_guard<std::mutex> lock(g_train_mutex);
     auto it = g_train_plans.find(key);
     if (it != g_train_plans.end()) { *out = &it->second; return LNS_OK; }
     const lns_config& c = e->cfg;
-    if (c.prop_kind != LNS_PROP_PLAIN && c.prop_kind != LNS_PROP_CONDITIONAL) { e->err = "training rollout: engine has no propagator"; return LNS_EINVAL; }
-    if (H <= 0 || W <= 0 || H > 4096 || W > 4096) { e->err = "training rollout: bad latent size"; return LNS_EINVAL; }
     TrainPlan p;
-    p.B = B; p.D = c.prop_n_embd; p.c = c.latent_dim; p.nb = c.prop_n_block; p.dil = c.prop_dilation;
-    p.H = H; p.W = W;
-    p.cond = c.prop_kind == LNS_PROP_CONDITIONAL; p.E = c.cond_emb_dim;
     int rc;
+    if ((rc = train_plan_dims(e, B, H, W, p))) return rc;
     const int my = c.prop_pad_y, mx = c.prop_pad_x;
     if ((rc = tconv_setup(e, p.in_proj, B, p.c, p.D, p.H, p.W, 1, 1, my, mx)) ||
         (rc = tconv_setup(e, p.in_proj_T, B, p.D, p.c, p.H, p.W, 1, 1, my, mx)) ||
@@ -154,7 +170,7 @@ int find_param(const lns_engine* e, const std::string& key) {
     auto it = e->pindex.find(key);
     return it == e->pindex.end() ? -1 : it->second;
 }
-int prop_params(lns_engine* e, PropParams& pp) {
+int build_prop_params(lns_engine* e, PropParams& pp) {
     const std::string p = e->cfg.prop_prefix;
     const bool cond = e->cfg.prop_kind == LNS_PROP_CONDITIONAL;
     bool ok = true;
@@ -190,6 +206,19 @@ int prop_params(lns_engine* e, PropParams& pp) {
         pp.blk.push_back(b);
     }
     if (!ok) { e->err = "training rollout: propagator parameter missing from the table"; return LNS_EINVAL; }
+    return LNS_OK;
+}
+// The table never changes after lns_create: the indices are looked up once per engine (every training call needs them).
+std::map<const lns_engine*, PropParams> g_prop_params;
+int prop_params(lns_engine* e, const PropParams** out) {
+    std::lock_guard<std::mutex> lock(g_train_mutex);
+    auto it = g_prop_params.find(e);
+    if (it == g_prop_params.end()) {
+        PropParams pp;
+        if (int rc = build_prop_params(e, pp)) return rc;
+        it = g_prop_params.emplace(e, std::move(pp)).first;
+    }
+    *out = &it->second;
     return LNS_OK;
 }
 
@@ -306,6 +335,7 @@ GnTrainArgs gn_args(const TrainPlan& p, int groups, float eps, const float* x, f
 
 void lns_train_release(const lns_engine* e) {
     std::lock_guard<std::mutex> lock(g_train_mutex);
+    g_prop_params.erase(e);
     for (auto it = g_train_plans.begin(); it != g_train_plans.end();) {
         if (it->first.e == e) {
             DeviceGuard dg(it->first.device);
@@ -318,14 +348,17 @@ void lns_train_release(const lns_engine* e) {
 int lns_train_workspace_bytes(lns_engine* e, int B, int H, int W, int T, size_t* bytes) {
     if (!e || B <= 0 || T <= 0 || !bytes) return LNS_EINVAL;
     if (int brc = check_batch(e, B)) return brc;
-    int device = 0;                       // (no tensor in this call: the caller's current device, as torch sets it)
-    HIPCHK(e, hipGetDevice(&device));
-    TrainPlan* p; int rc;
-    if ((rc = get_train_plan(e, device, B, H, W, &p))) return rc;
+    TrainPlan dims; int rc;
+    if ((rc = train_plan_dims(e, B, H, W, dims))) return rc;
     TrainLayout L;
-    train_layout(*p, T, L);
+    train_layout(dims, T, L);
     *bytes = L.total * 4;
-    return LNS_OK;
+    // the plan itself (device maps) is built here when a device is there -- the caller's current one, as torch sets it (no
+    // tensor in this call) -- so that the first run call does not; the size does not need one
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) { (void)hipGetLastError(); return LNS_OK; }
+    TrainPlan* p;
+    return get_train_plan(e, device, B, H, W, &p);
 }
 
 // the per-sample vector network of the conditional propagator (step-invariant): ce, and per block emb and m
@@ -378,8 +411,9 @@ int lns_train_forward(lns_engine* e, const float* const* params, const float* z_
     TrainLayout L;
     train_layout(p, T, L);
     if (!ws || ws_bytes < L.total * 4) { e->err = fmt("training workspace too small: need %zu bytes", L.total * 4); return LNS_ENOMEM; }
-    PropParams pp;
-    if ((rc = prop_params(e, pp)) || (rc = check_params(e, pp, params, "parameter"))) return rc;
+    const PropParams* ppp;
+    if ((rc = prop_params(e, &ppp)) || (rc = check_params(e, *ppp, params, "parameter"))) return rc;
+    const PropParams& pp = *ppp;
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* W = static_cast<float*>(ws);
     if ((rc = pack_all(e, p, L, pp, params, W, false, s))) return rc;
@@ -454,9 +488,10 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
     TrainLayout L;
     train_layout(p, T, L);
     if (!ws || ws_bytes < L.total * 4) { e->err = fmt("training workspace too small: need %zu bytes", L.total * 4); return LNS_ENOMEM; }
-    PropParams pp;
-    if ((rc = prop_params(e, pp)) || (rc = check_params(e, pp, params, "parameter")) ||
-        (rc = check_params(e, pp, const_cast<const float* const*>(grads), "gradient"))) return rc;
+    const PropParams* ppp;
+    if ((rc = prop_params(e, &ppp)) || (rc = check_params(e, *ppp, params, "parameter")) ||
+        (rc = check_params(e, *ppp, const_cast<const float* const*>(grads), "gradient"))) return rc;
+    const PropParams& pp = *ppp;
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* W = static_cast<float*>(ws);
     if ((rc = pack_all(e, p, L, pp, params, W, true, s))) return rc;
@@ -587,5 +622,182 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
         HIPCHK(e, launch_vec_gelu(vv.l0, vv.t1, vv.t2, Bn * E, s));
         HIPCHK(e, launch_vec_linear_bwd(vv.t2, vv.fe, params[pp.m0w], nullptr, 0, grads[pp.m0w], grads[pp.m0b], 0, Bn, E, E, s));
     }
+    return LNS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The device-resident training step (include/lns.h): loss + gradient, multi-tensor Adam, and the whole step.
+// Reference: train_stage2_ns2d.py:210-216.  Every argument check below is host-only and precedes the first HIP call.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// lns_adam_spec -> the kernel's scalars; the bias corrections in double from the host-side step count
+int adam_scalars(const lns_adam_spec* sp, AdamScalars& sc, std::string& err) {
+    if (!sp || sp->size != sizeof(lns_adam_spec)) { err = "adam spec is null or its size field is not sizeof(lns_adam_spec)"; return LNS_EINVAL; }
+    if (!(sp->lr >= 0.0) || !std::isfinite(sp->lr)) { err = "adam spec: lr must be >= 0"; return LNS_EINVAL; }
+    if (!(sp->beta1 >= 0.0 && sp->beta1 < 1.0)) { err = "adam spec: beta1 must be in [0, 1)"; return LNS_EINVAL; }
+    if (!(sp->beta2 >= 0.0 && sp->beta2 < 1.0)) { err = "adam spec: beta2 must be in [0, 1)"; return LNS_EINVAL; }
+    if (!(sp->eps > 0.0) || !std::isfinite(sp->eps) || (float)sp->eps <= 0.0f) { err = "adam spec: eps must be > 0"; return LNS_EINVAL; }
+    if (!(sp->weight_decay >= 0.0) || !std::isfinite(sp->weight_decay)) { err = "adam spec: weight_decay must be >= 0"; return LNS_EINVAL; }
+    if (sp->step < 1) { err = "adam spec: step is the 1-based count of this update (>= 1)"; return LNS_EINVAL; }
+    const double b1 = sp->beta1, b2 = sp->beta2, t = (double)sp->step;
+    const double bc1 = 1.0 - std::pow(b1, t), bc2 = 1.0 - std::pow(b2, t);
+    sc.step_size = (float)(sp->lr / bc1);
+    sc.beta1 = (float)b1; sc.one_minus_beta1 = (float)(1.0 - b1);      // each rounded once from the caller's double
+    sc.beta2 = (float)b2; sc.one_minus_beta2 = (float)(1.0 - b2);
+    sc.bc2_sqrt = (float)std::sqrt(bc2);
+    sc.eps = (float)sp->eps; sc.weight_decay = (float)sp->weight_decay;
+    return LNS_OK;
+}
+
+static_assert(LNS_SL1_CHUNK == SL1_CHUNK, "include/lns.h and lns_train_kernels.h name the same chunk");
+constexpr int64_t SL1_MAX_N = (int64_t)SL1_CHUNK << 30;       // 2^30 blocks: grid and partial count stay 32-bit
+int loss_check(int64_t n, float beta, const void* loss_out, std::string& err) {
+    if (n < 1 || n > SL1_MAX_N) { err = fmt("smooth_l1: n must be in 1 .. %lld", (long long)SL1_MAX_N); return LNS_EINVAL; }
+    if (!(beta > 0.0f) || !std::isfinite(beta)) { err = "smooth_l1: beta must be > 0 (beta = 0 is the L1 loss, which this kernel does not compute)"; return LNS_EINVAL; }
+    if (!loss_out) { err = "smooth_l1: loss_out is null"; return LNS_EINVAL; }
+    return LNS_OK;
+}
+
+// workspace of the whole step (bytes): training workspace | z_pred | dL/dz_pred | loss partials
+struct StepLayout { size_t train = 0, z_pred = 0, dz = 0, part = 0, total = 0, n = 0; };
+int step_layout(lns_engine* e, int B, int H, int W, int T, StepLayout& S) {
+    TrainPlan dims; int rc;
+    if ((rc = train_plan_dims(e, B, H, W, dims))) return rc;
+    TrainLayout L;
+    train_layout(dims, T, L);
+    S.n = (size_t)B * T * dims.c * H * W;
+    S.train = L.total * 4;
+    S.z_pred = round256(S.train);
+    S.dz = S.z_pred + round256(S.n * 4);
+    S.part = S.dz + round256(S.n * 4);
+    S.total = S.part + round256((size_t)smooth_l1_partials((long)S.n) * 4);
+    return LNS_OK;
+}
+
+}  // namespace
+
+int lns_loss_smooth_l1(const float* pred, const float* target, int64_t n, float beta, float* loss_out, float* grad_out,
+                       float* scratch, size_t scratch_floats, void* stream) {
+    std::string& err = g_create_error;
+    if (!pred || !target) { err = "smooth_l1: pred / target is null"; return LNS_EINVAL; }
+    if (int rc = loss_check(n, beta, loss_out, err)) return rc;
+    if (!scratch || scratch_floats < (size_t)smooth_l1_partials((long)n)) {
+        err = fmt("smooth_l1: scratch must hold %ld floats", smooth_l1_partials((long)n));
+        return LNS_ENOMEM;
+    }
+    const hipError_t rc = launch_smooth_l1(pred, target, (long)n, beta, loss_out, grad_out, scratch, static_cast<hipStream_t>(stream));
+    if (rc != hipSuccess) { err = std::string("smooth_l1: ") + hipGetErrorString(rc); return LNS_EHIP; }
+    return LNS_OK;
+}
+
+int lns_adam_step_tensors(int n, float* const* params, const float* const* grads, float* const* exp_avg,
+                          float* const* exp_avg_sq, const int64_t* numel, const lns_adam_spec* spec, void* stream) {
+    std::string& err = g_create_error;
+    if (n < 0 || (n > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel))) { err = "adam: null pointer array"; return LNS_EINVAL; }
+    AdamScalars sc;
+    if (int rc = adam_scalars(spec, sc, err)) return rc;
+    std::vector<AdamTensor> tt;
+    tt.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]) continue;
+        if (numel[i] < 1 || numel[i] >= (int64_t)1 << 31) { err = fmt("adam: tensor %d has %lld elements (1 .. 2^31 - 1)", i, (long long)numel[i]); return LNS_EINVAL; }
+        tt.push_back(AdamTensor{params[i], grads[i], exp_avg[i], exp_avg_sq[i], (unsigned)numel[i], 0u});
+    }
+    if (tt.empty()) return LNS_OK;
+    const hipError_t rc = launch_adam_multi(tt.data(), (int)tt.size(), sc, static_cast<hipStream_t>(stream));
+    if (rc != hipSuccess) { err = std::string("adam: ") + hipGetErrorString(rc); return LNS_EHIP; }
+    return LNS_OK;
+}
+
+// the engine's tensors: lengths from the parameter table
+static int adam_engine(lns_engine* e, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                       const AdamScalars& sc, hipStream_t s) {
+    std::vector<AdamTensor> tt;
+    tt.reserve(e->params.size());
+    for (size_t i = 0; i < e->params.size(); ++i) {
+        if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]) continue;
+        const size_t n = e->params[i].numel();
+        if (n < 1 || n >= (size_t)1 << 31) continue;
+        tt.push_back(AdamTensor{params[i], grads[i], exp_avg[i], exp_avg_sq[i], (unsigned)n, 0u});
+    }
+    if (tt.empty()) return LNS_OK;
+    HIPCHK(e, launch_adam_multi(tt.data(), (int)tt.size(), sc, s));
+    return LNS_OK;
+}
+
+int lns_adam_step(lns_engine* e, float* const* params, const float* const* grads, float* const* exp_avg,
+                  float* const* exp_avg_sq, const lns_adam_spec* spec, void* stream) {
+    if (!e) return LNS_EINVAL;
+    if (!params || !grads || !exp_avg || !exp_avg_sq) { e->err = "adam: null pointer array"; return LNS_EINVAL; }
+    AdamScalars sc;
+    if (int rc = adam_scalars(spec, sc, e->err)) return rc;
+    return adam_engine(e, params, grads, exp_avg, exp_avg_sq, sc, static_cast<hipStream_t>(stream));
+}
+
+int lns_train_step_workspace_bytes(lns_engine* e, int B, int H, int W, int T, size_t* bytes) {
+    if (!e) return LNS_EINVAL;
+    if (B < 1) { e->err = "training step: B must be >= 1"; return LNS_EINVAL; }
+    if (T < 1) { e->err = "training step: T must be >= 1"; return LNS_EINVAL; }
+    if (!bytes) { e->err = "training step: bytes is null"; return LNS_EINVAL; }
+    if (e->cfg.prop_kind != LNS_PROP_PLAIN && e->cfg.prop_kind != LNS_PROP_CONDITIONAL) { e->err = "training step: engine has no propagator"; return LNS_ESTATE; }
+    if (int brc = check_batch(e, B)) return brc;
+    StepLayout S; int rc;
+    if ((rc = step_layout(e, B, H, W, T, S))) return rc;
+    *bytes = S.total;
+    // build the plan now when a device is there, as lns_train_workspace_bytes does
+    size_t tb = 0;
+    return lns_train_workspace_bytes(e, B, H, W, T, &tb);
+}
+
+int lns_train_step(lns_engine* e, float* const* params, const float* z_in, const float* z_out, const float* param,
+                   int B, int H, int W, int T, float beta, float* const* grads, float* const* exp_avg,
+                   float* const* exp_avg_sq, const lns_adam_spec* adam_spec, float* loss_out, void* ws,
+                   size_t ws_bytes, void* stream) {
+    if (!e) return LNS_EINVAL;
+    // ---- host-only checks ----
+    if (e->cfg.prop_kind != LNS_PROP_PLAIN && e->cfg.prop_kind != LNS_PROP_CONDITIONAL) { e->err = "training step: engine has no propagator"; return LNS_ESTATE; }
+    if (B < 1) { e->err = "training step: B must be >= 1"; return LNS_EINVAL; }
+    if (T < 1) { e->err = "training step: T must be >= 1"; return LNS_EINVAL; }
+    if (int brc = check_batch(e, B)) return brc;
+    if (!params || !grads) { e->err = "training step: params / grads array is null"; return LNS_EINVAL; }
+    if (!z_in || !z_out) { e->err = "training step: z_in / z_out is null"; return LNS_EINVAL; }
+    if (e->cfg.prop_kind == LNS_PROP_CONDITIONAL && !param) { e->err = "training step: conditional propagator needs param"; return LNS_EINVAL; }
+    int rc;
+    AdamScalars sc;
+    if (adam_spec && (rc = adam_scalars(adam_spec, sc, e->err))) return rc;
+    const PropParams* pp;
+    if ((rc = prop_params(e, &pp)) || (rc = check_params(e, *pp, params, "parameter")) ||
+        (rc = check_params(e, *pp, const_cast<const float* const*>(grads), "gradient"))) return rc;
+    if (adam_spec) {
+        if (!exp_avg || !exp_avg_sq) { e->err = "training step: exp_avg / exp_avg_sq array is null (adam_spec is given)"; return LNS_EINVAL; }
+        if ((rc = check_params(e, *pp, const_cast<const float* const*>(exp_avg), "exp_avg")) ||
+            (rc = check_params(e, *pp, const_cast<const float* const*>(exp_avg_sq), "exp_avg_sq"))) return rc;
+    }
+    StepLayout S;
+    if ((rc = step_layout(e, B, H, W, T, S)) || (rc = loss_check((int64_t)S.n, beta, loss_out, e->err))) return rc;
+    if (!ws || ws_bytes < S.total) { e->err = fmt("training step workspace too small: need %zu bytes", S.total); return LNS_ENOMEM; }
+    // ---- where the tensors live (pointer attributes: the first HIP calls), still before anything is enqueued ----
+    int device = -1;
+    if ((rc = train_device_of(e, z_in, &device)) || (rc = train_same_device(e, device, z_out, "z_out")) ||
+        (rc = train_same_device(e, device, loss_out, "loss_out")) || (rc = train_same_device(e, device, ws, "the workspace"))) return rc;
+    // ---- device work, in stream order ----
+    char* base = static_cast<char*>(ws);
+    float* z_pred = reinterpret_cast<float*>(base + S.z_pred);
+    float* dz = reinterpret_cast<float*>(base + S.dz);
+    float* part = reinterpret_cast<float*>(base + S.part);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if ((rc = lns_train_forward(e, params, z_in, param, B, H, W, T, z_pred, ws, S.train, stream))) return rc;
+    DeviceGuard dg(device);
+    HIPCHK(e, launch_smooth_l1(z_pred, z_out, (long)S.n, beta, loss_out, dz, part, s));
+    if ((rc = lns_train_backward(e, params, z_in, z_pred, dz, B, H, W, T, grads, nullptr, ws, S.train, stream))) return rc;
+    if (!adam_spec) return LNS_OK;
+    // only the propagator's tensors: other entries of the arrays are not this step's business
+    std::vector<AdamTensor> tt;
+    tt.reserve(pp->all.size());
+    for (int v : pp->all) tt.push_back(AdamTensor{params[v], grads[v], exp_avg[v], exp_avg_sq[v], (unsigned)e->params[v].numel(), 0u});
+    HIPCHK(e, launch_adam_multi(tt.data(), (int)tt.size(), sc, s));
     return LNS_OK;
 }

@@ -48,4 +48,18 @@ hipError_t launch_vec_gelu(const float* u, const float* dy, float* out, int n, h
 hipError_t launch_vec_gn(const float* x, const float* gamma, const float* beta, float* y, float* stats, const float* dy, float* dx,
                          float* dgamma, float* dbeta, int p_acc, int B, int D, float eps, hipStream_t s);
 
+// ---- loss and optimiser of the training step (lns_optim.inc) ----------------------------------------------------------
+// F.smooth_l1_loss(pred, target, 'mean', beta) -> *loss_out (device float) and, if grad != null, dL/dpred, in one pass.
+// partial: device scratch of smooth_l1_partials(n) floats (one per SL1_CHUNK elements).  n >= 1, beta > 0.
+constexpr int SL1_CHUNK = 4096;
+long smooth_l1_partials(long n);
+hipError_t launch_smooth_l1(const float* pred, const float* target, long n, float beta, float* loss_out, float* grad, float* partial,
+                            hipStream_t s);
+
+// torch.optim.Adam's update of `count` tensors, ADAM_MAX_TENSORS per launch (the table is a kernel argument).
+constexpr int ADAM_MAX_TENSORS = 96;
+struct AdamTensor { float* p; const float* g; float* m; float* v; unsigned n; unsigned first; };
+struct AdamScalars { float step_size, beta1, one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt, eps, weight_decay; };
+hipError_t launch_adam_multi(AdamTensor* tensors, int count, const AdamScalars& sc, hipStream_t s);
+
 }  // namespace lns

@@ -432,4 +432,6 @@ hipError_t launch_vec_gn(const float* x, const float* gamma, const float* beta, 
     return hipGetLastError();
 }
 
+#include "lns_optim.inc"
+
 }  // namespace lns

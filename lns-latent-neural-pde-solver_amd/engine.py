@@ -106,6 +106,38 @@ def make_config(args, ae_kind=None, prop_kind=None, ae_prefix="", prop_prefix=""
     return c
 
 
+def adam_spec(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1):
+    """`lns_adam_spec` from torch.optim.Adam's hyper-parameters; `step` is the 1-based count of the update."""
+    spec = _lib.LnsAdamSpec()
+    spec.size = ctypes.sizeof(_lib.LnsAdamSpec)
+    spec.lr, spec.beta1, spec.beta2 = float(lr), float(betas[0]), float(betas[1])
+    spec.eps, spec.weight_decay, spec.step = float(eps), float(weight_decay), int(step)
+    return spec
+
+
+def smooth_l1(pred, target, beta=1.0, need_grad=True, loss_out=None, grad_out=None):
+    """F.smooth_l1_loss(pred, target, beta=beta) (train_stage2_ns2d.py:213) and dL/dpred in one pass on the HIP kernel
+    (lns_loss_smooth_l1): returns (0-dim device tensor, gradient like pred or None).  Bit-reproducible; never
+    synchronises.  Module-level because the op needs no engine; `Engine.smooth_l1` is the same call."""
+    import torch
+    pred, target = Engine._dev(pred), Engine._dev(target)
+    if pred.shape != target.shape or pred.device != target.device:
+        raise LnsError("smooth_l1: pred %s on %s and target %s on %s must match"
+                       % (tuple(pred.shape), pred.device, tuple(target.shape), target.device))
+    L = _lib.lib()
+    n = pred.numel()
+    with torch.cuda.device(pred.device):
+        loss = torch.empty((), dtype=torch.float32, device=pred.device) if loss_out is None else loss_out
+        grad = (torch.empty_like(pred) if grad_out is None else grad_out) if need_grad else None
+        scratch = torch.empty(max(1, -(-n // _lib.LNS_SL1_CHUNK)), dtype=torch.float32, device=pred.device)
+        rc = L.lns_loss_smooth_l1(pred.data_ptr(), target.data_ptr(), n, float(beta), loss.data_ptr(),
+                                  grad.data_ptr() if grad is not None else None, scratch.data_ptr(), scratch.numel(),
+                                  Engine._stream(pred))
+    if rc != 0:
+        raise LnsError("lns_loss_smooth_l1 failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    return loss, grad
+
+
 def eval_spec(C, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
     """`lns_eval_spec` from the arguments of `metrics.relative_l2`, with its rule for the choice between the scalar and
     the per-channel kernel: per-channel as soon as a statistic is a sequence or a channel is zeroed / clamped."""
@@ -469,6 +501,59 @@ class Engine:
                                                B, h, w, T, self._ptr_array(grads), gz.data_ptr() if gz is not None else None,
                                                ws.data_ptr(), ws.numel(), self._stream(z_in)), "lns_train_backward")
         return grads, gz
+
+    # -- device-resident training step (include/lns.h "device-resident training step") -------------------------------
+    smooth_l1 = staticmethod(smooth_l1)
+
+    def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1):
+        """torch.optim.Adam's update of every tensor present in all four {key: device tensor} dicts, in one launch
+        (lns_adam_step).  step: 1-based count of this update.  In place; the caller bumps the tensors' versions."""
+        import torch
+        spec = adam_spec(lr, betas, eps, weight_decay, step)
+        any_t = next(iter(params.values()))
+        with torch.cuda.device(any_t.device):
+            self._check(self._L.lns_adam_step(self._h, self._ptr_array(params), self._ptr_array(grads), self._ptr_array(exp_avg),
+                                              self._ptr_array(exp_avg_sq), ctypes.byref(spec), self._stream(any_t)), "lns_adam_step")
+
+    def train_step_workspace_bytes(self, B, h, w, T):
+        n = ctypes.c_size_t(0)
+        self._check(self._L.lns_train_step_workspace_bytes(self._h, int(B), int(h), int(w), int(T), ctypes.byref(n)),
+                    "lns_train_step_workspace_bytes")
+        return int(n.value)
+
+    def train_step(self, params, z_in, z_out, grads, param=None, beta=1.0, exp_avg=None, exp_avg_sq=None, spec=None,
+                   loss_out=None, workspace=None):
+        """One stage-2 training step on the device (lns_train_step): training forward from z_in [B,1,c,h,w] (or [B,c,h,w]),
+        smooth-L1 loss against z_out [B,T,c,h,w], backward through time into `grads`, and -- with `spec` (adam_spec(...)) --
+        Adam on params / exp_avg / exp_avg_sq.  params & co.: {key: tensor} dicts, or ctypes pointer arrays in table order
+        (what `_ptr_array` returns; `lns_amd.train.Stage2Trainer` resolves them once).  Returns the 0-dim device loss
+        (before the update).  Nothing here synchronises; with `loss_out` and `workspace` given nothing allocates."""
+        import torch
+        z_in, z_out = self._dev(z_in), self._dev(z_out)
+        if z_in.dim() == 5:
+            if z_in.shape[1] != 1:
+                raise LnsError("z_in must be [B,1,c,h,w] (t_in == 1)")
+            z_in = z_in[:, 0]
+        B, c, h, w = z_in.shape
+        if z_out.dim() != 5 or z_out.shape[0] != B or tuple(z_out.shape[2:]) != (c, h, w) or z_out.device != z_in.device:
+            raise LnsError("z_out must be [B,T,%d,%d,%d] on z_in's device, got %s on %s" % (c, h, w, tuple(z_out.shape), z_out.device))
+        T = int(z_out.shape[1])
+        pc = self._param(param, z_in)
+
+        def arr(t):
+            return self._ptr_array(t) if isinstance(t, dict) else t
+        with torch.cuda.device(z_in.device):
+            if workspace is None:
+                workspace = torch.empty(self.train_step_workspace_bytes(B, h, w, T), dtype=torch.uint8, device=z_in.device)
+            if loss_out is None:
+                loss_out = torch.empty((), dtype=torch.float32, device=z_in.device)
+            self._check(self._L.lns_train_step(self._h, arr(params), z_in.data_ptr(), z_out.data_ptr(),
+                                               pc.data_ptr() if pc is not None else None, B, h, w, T, float(beta), arr(grads),
+                                               arr(exp_avg) if exp_avg is not None else None,
+                                               arr(exp_avg_sq) if exp_avg_sq is not None else None,
+                                               ctypes.byref(spec) if spec is not None else None, loss_out.data_ptr(),
+                                               workspace.data_ptr(), workspace.numel(), self._stream(z_in)), "lns_train_step")
+        return loss_out
 
     def check_finite(self, B, device=None):
         """Raises LnsError naming the first layer / sample whose output held inf or NaN in the LAST call (encode /
