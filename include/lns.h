@@ -145,6 +145,13 @@ int lns_finalize_weights(lns_engine* e, int device);
  *   "eval_max_steps"  longest horizon of lns_rollout_eval / lns_rollout_latent_eval (it sizes their partial sums; default 1024)
  *   "track_nonfinite" 1: lns_check_finite also remembers the plan runs whose amax record has been reused since (the
  *                     earlier steps / decode groups of a rollout): one extra one-block launch per plan run (default 0)
+ *   "train_wgrad"     weight-gradient kernel of lns_train_backward (and through it of lns_train_step and the drop-in's autograd
+ *                     path).  0 (default): one block per 64 x 64 output tile (and tap) walks the whole K = batch x pixels;
+ *                     1: batch-parallel -- K is cut into S slices of whole (sample, 64-pixel chunk)s, one block per (tile, slice),
+ *                     3x3: all nine taps per block; the S partial tiles are summed in ascending slice order by a second kernel
+ *                     (no atomics: bit-reproducible for a shape; the gradient differs from form 0 by the summation order only).
+ *                     With 1 the training workspaces grow by one partial-sum area (see lns_train_workspace_bytes); any other
+ *                     value: LNS_EINVAL.
  * One option selects an ARITHMETIC FORM (results differ at rounding level, ~2e-7 relative on the decoded field):
  *   "fa_fused"        2 (default; LNS_FA_FUSED): FABlock2D on 64 x 64 planes with 64 channels and on 32 x 32 planes with 128
  *                     channels computes in_proj inside the sandwich kernel (csrc/fa_fused.inc) -- the heads * dim_head plane tensor
@@ -273,7 +280,12 @@ int lns_check_finite(lns_engine* e, int B, void* workspace, size_t workspace_byt
  * conditional one (train_stage2_twophase_conditional.py:25-121; `param` [B], no gradient w.r.t. it).  The same
  * workspace and parameter values must be used for the backward call.
  * lns_train_workspace_bytes needs no device for the size; when the process has one it also builds the shape's plan (device
- * index maps) on the caller's current device, so that the first run call does not. */
+ * index maps) on the caller's current device, so that the first run call does not.
+ * Option "train_wgrad" = 1 appends one area to the layout (everything before it keeps its offset): the partial sums of the
+ * plan's largest weight-gradient launch, S * Cout * Cin * k * k floats rounded up to 64 floats, where S is
+ * lns_op_conv_wgrad_scratch_bytes' slice count for (B, Cin, Cout, h, w, k).  With the option at 0 the sizes are what they
+ * were without it.  A workspace sized under 0 and used under 1 is refused with LNS_ENOMEM (the message names the needed
+ * size) before anything is enqueued. */
 int lns_train_workspace_bytes(lns_engine* e, int B, int h, int w, int T, size_t* bytes);
 int lns_train_forward(lns_engine* e, const float* const* params, const float* z_in, const float* param_or_null,
                       int B, int h, int w, int T, float* z_pred, void* workspace, size_t workspace_bytes, void* stream);
@@ -364,7 +376,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  *  (event, launch, event) timing around empty launches and subtracted from every timed launch; -1000 before the first timed run) */
 
 /* Build-time features of this library: "experimental" = compiled with -DLNS_EXPERIMENTAL (the measured-slower kernel
- * forms behind op-level variants 15 / 16 / 18 / 19 exist; the shipped library does not carry them).  1 / 0; -1: unknown name.
+ * forms behind op-level variants 15 / 16 / 18 / 19 exist; the shipped library does not carry them); "train_wgrad_split" = the
+ * batch-parallel weight gradient (option "train_wgrad", lns_op_conv_wgrad) is there.  1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
 
@@ -391,6 +404,20 @@ int lns_op_conv2d(const float* x, int B, int Cin, int Hin, int Win, int Hv, int 
 int lns_op_conv_pair_stress(int B, int H, int W, int cin_a, int cout_a, int ksize_a, int variant_a, int cin_b, int cout_b,
                             int ksize_b, int variant_b, int rounds, int launches, long long* mismatches_a,
                             long long* mismatches_b);
+
+/* Weight gradient of a stride-1 "same" convolution (ksize 1 or 3, dilation d, padding d * (ksize - 1) / 2 per side):
+ *   dw[co][ci][ty][tx] (+)= sum_b sum_{y,x} dy[b][co][y][x] * xpad[b][ci][y + ty*d][x + tx*d]
+ * dy [B,Cout,H,W], x [B,Cin,H,W], dw [Cout,Cin,ksize,ksize]: device fp32; pad_y / pad_x: LNS_PAD_ZEROS / LNS_PAD_CIRCULAR per
+ * axis; accumulate 1: added to the value already in dw.  form 0: one block per output tile; form 1: batch-parallel (the
+ * two kernels of option "train_wgrad"), which needs `scratch` (device) of lns_op_conv_wgrad_scratch_bytes(...) bytes =
+ * S * Cout * Cin * ksize^2 floats rounded up to 64 floats, S a function of (B, Cin, Cout, H, W, ksize) only; form 0: 0 bytes,
+ * scratch may be NULL.  Exact-fp32 matrix instruction in both forms.  Every argument check precedes the first launch
+ * (LNS_EINVAL; LNS_ENOMEM for a short scratch; message: lns_create_error()); the call synchronises `stream`.
+ * lns_op_conv_wgrad_scratch_bytes needs no device. */
+int lns_op_conv_wgrad_scratch_bytes(int B, int Cin, int Cout, int H, int W, int ksize, int form, size_t* bytes);
+int lns_op_conv_wgrad(const float* dy, const float* x, int B, int Cin, int Cout, int H, int W, int ksize, int dilation,
+                      int pad_y, int pad_x, int form, int accumulate, float* dw, void* scratch, size_t scratch_bytes,
+                      void* stream);
 
 /* GroupNorm statistics -> per-(b,c) (scale,shift) such that norm(x) = x*scale+shift. */
 int lns_op_groupnorm_stats(const float* x, int B, int C, int HW, int groups, float eps,

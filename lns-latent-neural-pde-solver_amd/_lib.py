@@ -92,6 +92,7 @@ SYMBOLS = [
     "lns_loss_smooth_l1", "lns_adam_step", "lns_adam_step_tensors", "lns_train_step_workspace_bytes", "lns_train_step",
     "lns_trace_enable", "lns_trace_count", "lns_trace_info", "lns_trace_copy",
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
+    "lns_op_conv_wgrad_scratch_bytes", "lns_op_conv_wgrad",
     "lns_op_conv2d", "lns_op_conv_pair_stress", "lns_op_groupnorm_stats", "lns_op_attention", "lns_op_fa_sandwich", "lns_op_fourier_block",
     "lns_fourier_block_create", "lns_fourier_block_forward", "lns_fourier_block_destroy", "lns_metric_rel_l2", "lns_metric_rel_l2_ch",
 ]
@@ -184,6 +185,9 @@ def lib():
     L.lns_timing_mfma_flops.argtypes = [vp, i, c.POINTER(c.c_double)]
     L.lns_op_conv2d.argtypes = [vp, i, i, i, i, i, i, vp, vp, i, i, i, i, i, i, i, i, i, i,
                                 vp, i, i, vp, vp, vp, i, vp, vp]
+    if hasattr(L, "lns_op_conv_wgrad"):
+        L.lns_op_conv_wgrad_scratch_bytes.argtypes = [i, i, i, i, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_op_conv_wgrad.argtypes = [vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, vp, c.c_size_t, vp]
     L.lns_op_groupnorm_stats.argtypes = [vp, i, i, i, i, c.c_float, vp, vp, vp, vp, vp]
     L.lns_op_attention.argtypes = [vp, i, i, i, i, c.c_float, vp, vp]
     L.lns_op_fa_sandwich.argtypes = [vp, vp, vp, i, i, i, i, i, c.c_float, i, vp, vp]

@@ -2014,6 +2014,10 @@ int lns_set_option(lns_engine* e, const char* name, long value) {
     else if (n == "overlap") e->opt_overlap = value != 0;
     else if (n == "eval_max_steps") { if (value < 1 || value > 65536) return LNS_EINVAL; e->opt_eval_max_steps = (int)value; }
     else if (n == "track_nonfinite") e->opt_track_nonfinite = value != 0;
+    else if (n == "train_wgrad") {
+        if (value != 0 && value != 1) { e->err = "train_wgrad: 0 (one block per output tile) or 1 (batch-parallel)"; return LNS_EINVAL; }
+        e->opt_train_wgrad = (int)value;
+    }
     else if (n == "fa_fused" || n == "fa_fused_gpb") {
         if (n == "fa_fused_gpb" && (value < 0 || value > 64)) return LNS_EINVAL;
         if (n == "fa_fused" && (value < 0 || value > 3)) return LNS_EINVAL;
@@ -2566,6 +2570,7 @@ int lns_timing_mfma_flops(const lns_engine* e, int i, double* mfma_flops) {
 int lns_build_has(const char* feature) {
     if (!feature) return -1;
     if (!strcmp(feature, "experimental")) return build_has_experimental() ? 1 : 0;
+    if (!strcmp(feature, "train_wgrad_split")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else

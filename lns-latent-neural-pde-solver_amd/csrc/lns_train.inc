@@ -26,6 +26,7 @@ namespace {
 
 struct TConv {                       // one convolution geometry with its gather maps on the device
     int Cin = 0, Cout = 0, k = 1, dil = 1, Cin_pad = 0, Cout_pad = 0, variant = 0;
+    int wg_S = 1;                    // slices of the batch-parallel weight gradient (wgrad_split_slices of the plan's shape)
     ConvArgs base;                   // everything but x / y / w / bias / res
     int* d_maps = nullptr;           // forward kernel's tile maps (rowmap | colmap)
     int* d_full = nullptr;           // whole-image maps of the weight-gradient kernel (rowmap | colmap)
@@ -131,6 +132,7 @@ int train_plan_dims(lns_engine* e, int B, int H, int W, TrainPlan& p) {
     tconv_dims(p.in_proj, p.c, p.D, 1, 1); tconv_dims(p.in_proj_T, p.D, p.c, 1, 1);
     tconv_dims(p.c_d1, p.D, p.D, 3, 1); tconv_dims(p.c_dd, p.D, p.D, 3, p.dil); tconv_dims(p.c_1, p.D, p.D, 1, 1);
     tconv_dims(p.out_proj, p.D, p.c, 1, 1); tconv_dims(p.out_proj_T, p.c, p.D, 1, 1);
+    for (TConv* t : {&p.in_proj, &p.c_d1, &p.c_dd, &p.c_1, &p.out_proj}) t->wg_S = wgrad_split_slices(B, H, W, t->Cin, t->Cout, t->k);
     return LNS_OK;
 }
 
@@ -143,6 +145,7 @@ int get_train_plan(lns_engine* e, int device, int B, int H, int W, TrainPlan** o
     TrainPlan p;
     int rc;
     if ((rc = train_plan_dims(e, B, H, W, p))) return rc;
+    HIPCHK(e, init_train_kernels());      // dynamic-LDS attributes of the batch-parallel weight gradient: per device, at plan build
     const int my = c.prop_pad_y, mx = c.prop_pad_x;
     if ((rc = tconv_setup(e, p.in_proj, B, p.c, p.D, p.H, p.W, 1, 1, my, mx)) ||
         (rc = tconv_setup(e, p.in_proj_T, B, p.D, p.c, p.H, p.W, 1, 1, my, mx)) ||
@@ -222,13 +225,14 @@ int prop_params(lns_engine* e, const PropParams** out) {
     return LNS_OK;
 }
 
-// workspace layout (floats): weight packs | tape[T] | backward scratch
+// workspace layout (floats): weight packs | tape[T] | backward scratch [| partial sums of the batch-parallel weight gradient]
 struct TrainLayout {
     size_t n = 0, nl = 0;                          // B*D*HW, B*c*HW
     size_t pk_in = 0, pk_inT = 0, pk_out = 0, pk_outT = 0;
     std::vector<size_t> pk_c1, pk_c3, pk_c5, pk_f1, pk_f3, pk_c1T, pk_c3T, pk_c5T, pk_f1T, pk_f3T;
     size_t tape0 = 0, tape_step = 0, st_blk = 0;   // per step: x0 | blocks | nO | stats
     size_t scratch = 0, total = 0;
+    size_t wg_part = 0, wg_floats = 0;             // option "train_wgrad" = 1: [S][Cout][Cin][k*k] of the plan's largest launch
     size_t vec0 = 0, vec_blk = 0, vec_glob = 0, vstat = 0;     // conditional: per-block vectors | fe, l0, l0g, ce, d_ce | GN stats
     // tape offsets inside a step
     size_t off_x0 = 0, off_blk = 0, blk_stride = 0, off_nO = 0, off_stats = 0;
@@ -237,7 +241,7 @@ enum { TB_N1 = 0, TB_U1, TB_A1, TB_U2, TB_A2, TB_X1, TB_N2, TB_V, TB_G, TB_X2, T
 // (conditional block: TB_U2 = h = conv1.3(a1) + emb, TB_NC = GN(h), TB_A2 = GELU(TB_NC), TB_XM = x1 (1 + m))
 enum { TV_EMB = 0, TV_VG, TV_C1, TV_C1G, TV_M, TV_DEMB, TV_DM, TV_COUNT };     // per-block [B][D] vectors
 
-void train_layout(const TrainPlan& p, int T, TrainLayout& L) {
+void train_layout(const TrainPlan& p, int T, TrainLayout& L, int wgrad_form) {
     const size_t HW = (size_t)p.H * p.W;
     L.n = (size_t)p.B * p.D * HW; L.nl = (size_t)p.B * p.c * HW;
     size_t off = 0;
@@ -271,6 +275,11 @@ void train_layout(const TrainPlan& p, int T, TrainLayout& L) {
         L.vec_glob = off; off += 8 * ve;                          // fe, l0, l0g, ce, d_ce, 3 scratch vectors
         L.vstat = off; off += (size_t)p.nb * (((size_t)p.B * 2 + 63) / 64 * 64);
     }
+    if (wgrad_form == 1) {                                           // appended: everything above keeps its offset
+        for (const TConv* t : {&p.in_proj, &p.c_d1, &p.c_dd, &p.c_1, &p.out_proj})
+            L.wg_floats = std::max(L.wg_floats, (size_t)t->wg_S * t->Cout * t->Cin * t->k * t->k);
+        L.wg_part = take(L.wg_floats);
+    }
     L.total = off;
 }
 
@@ -281,11 +290,17 @@ int run_tconv(lns_engine* e, const TConv& t, const float* x, const float* wpack,
     HIPCHK(e, launch_conv(t.variant, a, s));
     return LNS_OK;
 }
-int run_wgrad(lns_engine* e, const TConv& t, const TrainPlan& p, const float* dy, const float* x, float* dw, int accumulate, hipStream_t s) {
+// part: the layout's partial-sum area (batch-parallel form) or null (one block per output tile); x_bs: floats between two
+// samples of x, which only the batch-parallel form takes other than Cin*H*W
+int run_wgrad(lns_engine* e, const TConv& t, const TrainPlan& p, const float* dy, const float* x, long x_bs, float* dw, int accumulate,
+              float* part, hipStream_t s) {
     WgradArgs a;
+    memset(&a, 0, sizeof a);
     a.dy = dy; a.x = x; a.rowmap = t.d_full; a.colmap = t.d_full + t.full_rows; a.dw = dw;
     a.B = p.B; a.Cin = t.Cin; a.Cout = t.Cout; a.H = p.H; a.W = p.W; a.k = t.k; a.dil = t.dil; a.accumulate = accumulate;
-    HIPCHK(e, launch_conv_wgrad(a, s));
+    a.x_bs = x_bs; a.part = part; a.S = t.wg_S;
+    if (part) HIPCHK(e, launch_conv_wgrad_split(a, s));
+    else HIPCHK(e, launch_conv_wgrad(a, s));
     return LNS_OK;
 }
 
@@ -351,7 +366,7 @@ int lns_train_workspace_bytes(lns_engine* e, int B, int H, int W, int T, size_t*
     TrainPlan dims; int rc;
     if ((rc = train_plan_dims(e, B, H, W, dims))) return rc;
     TrainLayout L;
-    train_layout(dims, T, L);
+    train_layout(dims, T, L, e->opt_train_wgrad);
     *bytes = L.total * 4;
     // the plan itself (device maps) is built here when a device is there -- the caller's current one, as torch sets it (no
     // tensor in this call) -- so that the first run call does not; the size does not need one
@@ -409,7 +424,7 @@ int lns_train_forward(lns_engine* e, const float* const* params, const float* z_
     const TrainPlan& p = *pl;
     if (p.cond && !param) { e->err = "conditional propagator needs param"; return LNS_EINVAL; }
     TrainLayout L;
-    train_layout(p, T, L);
+    train_layout(p, T, L, e->opt_train_wgrad);
     if (!ws || ws_bytes < L.total * 4) { e->err = fmt("training workspace too small: need %zu bytes", L.total * 4); return LNS_ENOMEM; }
     const PropParams* ppp;
     if ((rc = prop_params(e, &ppp)) || (rc = check_params(e, *ppp, params, "parameter"))) return rc;
@@ -486,7 +501,7 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
     if ((rc = get_train_plan(e, device, B, H, Wd, &pl))) return rc;
     const TrainPlan& p = *pl;
     TrainLayout L;
-    train_layout(p, T, L);
+    train_layout(p, T, L, e->opt_train_wgrad);
     if (!ws || ws_bytes < L.total * 4) { e->err = fmt("training workspace too small: need %zu bytes", L.total * 4); return LNS_ENOMEM; }
     const PropParams* ppp;
     if ((rc = prop_params(e, &ppp)) || (rc = check_params(e, *ppp, params, "parameter")) ||
@@ -502,6 +517,8 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
     float* dz = dD + np;                 // [B][c][HW] gradient w.r.t. the step's output (contiguous)
     float* dz2 = dz + nlp;
     float* part = dz2 + nlp;             // [B][D][2]
+    float* wgp = e->opt_train_wgrad == 1 ? W + L.wg_part : nullptr;      // batch-parallel weight gradient: its partial sums
+    const long nbs = (long)p.D * HW;     // sample stride of the D-channel tensors
     const int Bn = p.B, BD = p.B * p.D;
     for (int t = T - 1; t >= 0; --t) {
         const int acc = t == T - 1 ? 0 : 1;          // parameter gradients: written at the first processed step, accumulated after
@@ -514,7 +531,7 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
         float* stO = tp + L.off_stats + (size_t)p.nb * L.st_blk;
         const float* xL = p.nb ? tp + L.off_blk + (size_t)(p.nb - 1) * L.blk_stride + TB_X2 * (L.blk_stride / TB_COUNT) : tp + L.off_x0;
         HIPCHK(e, launch_bias_grad(dz, Bn, p.c, (int)HW, grads[pp.out_b], acc, s));
-        if ((rc = run_wgrad(e, p.out_proj, p, dz, tp + L.off_nO, grads[pp.out_w], acc, s))) return rc;
+        if ((rc = run_wgrad(e, p.out_proj, p, dz, tp + L.off_nO, nbs, grads[pp.out_w], acc, wgp, s))) return rc;
         if ((rc = run_tconv(e, p.out_proj_T, dz, W + L.pk_outT, nullptr, dA, nullptr, s))) return rc;        // d nO
         {
             GnTrainArgs g = gn_args(p, 32, 1e-6f, xL, nullptr, stO, params[pp.out_g], params[pp.out_be]);
@@ -531,10 +548,10 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
             float* st = tp + L.off_stats + (size_t)i * L.st_blk;
             const float* xin = i == 0 ? tp + L.off_x0 : tp + L.off_blk + (size_t)(i - 1) * L.blk_stride + TB_X2 * ts;
             // x2 = x1 + ffn.3(g): d w(f3), d g
-            if ((rc = run_wgrad(e, p.c_1, p, dx, tb + TB_G * ts, grads[b.f3w], acc, s))) return rc;
+            if ((rc = run_wgrad(e, p.c_1, p, dx, tb + TB_G * ts, nbs, grads[b.f3w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_1, dx, W + L.pk_f3T[i], nullptr, f1, nullptr, s))) return rc;           // d g
             HIPCHK(e, launch_gelu_bwd(f1, tb + TB_V * ts, f2, n, s));                                            // d v
-            if ((rc = run_wgrad(e, p.c_1, p, f2, tb + TB_N2 * ts, grads[b.f1w], acc, s))) return rc;
+            if ((rc = run_wgrad(e, p.c_1, p, f2, tb + TB_N2 * ts, nbs, grads[b.f1w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_1, f2, W + L.pk_f1T[i], nullptr, f1, nullptr, s))) return rc;           // d n2
             float* dx1;                                                                                          // gradient w.r.t. x1
             if (!p.cond) {
@@ -557,7 +574,7 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
             float* g2 = f2;
             // x1 = x + conv.5 / cond_conv1.2 (a2)
             HIPCHK(e, launch_bias_grad(dx1, Bn, p.D, (int)HW, grads[b.c5b], acc, s));
-            if ((rc = run_wgrad(e, p.c_d1, p, dx1, tb + TB_A2 * ts, grads[b.c5w], acc, s))) return rc;
+            if ((rc = run_wgrad(e, p.c_d1, p, dx1, tb + TB_A2 * ts, nbs, grads[b.c5w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_d1, dx1, W + L.pk_c5T[i], nullptr, g1, nullptr, s))) return rc;         // d a2
             if (!p.cond) {
                 HIPCHK(e, launch_gelu_bwd(g1, tb + TB_U2 * ts, g2, n, s));                                        // d u2
@@ -571,11 +588,11 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
                 std::swap(g1, g2);                                                                               // d h is in g2 now
             }
             HIPCHK(e, launch_bias_grad(g2, Bn, p.D, (int)HW, grads[b.c3b], acc, s));
-            if ((rc = run_wgrad(e, p.c_dd, p, g2, tb + TB_A1 * ts, grads[b.c3w], acc, s))) return rc;
+            if ((rc = run_wgrad(e, p.c_dd, p, g2, tb + TB_A1 * ts, nbs, grads[b.c3w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_dd, g2, W + L.pk_c3T[i], nullptr, g1, nullptr, s))) return rc;          // d a1
             HIPCHK(e, launch_gelu_bwd(g1, tb + TB_U1 * ts, g2, n, s));                                            // d u1
             HIPCHK(e, launch_bias_grad(g2, Bn, p.D, (int)HW, grads[b.c1b], acc, s));
-            if ((rc = run_wgrad(e, p.c_d1, p, g2, tb + TB_N1 * ts, grads[b.c1w], acc, s))) return rc;
+            if ((rc = run_wgrad(e, p.c_d1, p, g2, tb + TB_N1 * ts, nbs, grads[b.c1w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_d1, g2, W + L.pk_c1T[i], nullptr, g1, nullptr, s))) return rc;          // d n1
             {
                 GnTrainArgs g = gn_args(p, 1, 1e-5f, xin, nullptr, st, params[b.g1], params[b.b1]);
@@ -590,12 +607,14 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
         {
             // the weight-gradient kernel reads x with a plain [B][Cin][HW] layout: step t > 0 reads z_pred through its
             // T-strided batch axis, so it is copied to a contiguous buffer first (small: B x c x HW)
+            // (the batch-parallel form takes a batch stride and reads z_pred in place)
             const float* zc = zin;
-            if (t > 0) {
+            long zbs = t == 0 ? (long)p.c * HW : (long)T * p.c * HW;
+            if (t > 0 && !wgp) {
                 HIPCHK(e, launch_add_rows(zin, (long)T * p.c * HW, nullptr, 0, dz, (long)p.c * HW, Bn, (long)(p.c * HW), s));
-                zc = dz;
+                zc = dz; zbs = (long)p.c * HW;
             }
-            if ((rc = run_wgrad(e, p.in_proj, p, dx, zc, grads[pp.in_w], acc, s))) return rc;
+            if ((rc = run_wgrad(e, p.in_proj, p, dx, zc, zbs, grads[pp.in_w], acc, wgp, s))) return rc;
         }
         float* dzin = t == 0 ? (grad_z_in ? grad_z_in : dz2) : dz2;
         if ((rc = run_tconv(e, p.in_proj_T, dx, W + L.pk_inT, nullptr, dzin, nullptr, s))) return rc;            // d z_{t-1}
@@ -667,7 +686,7 @@ int step_layout(lns_engine* e, int B, int H, int W, int T, StepLayout& S) {
     TrainPlan dims; int rc;
     if ((rc = train_plan_dims(e, B, H, W, dims))) return rc;
     TrainLayout L;
-    train_layout(dims, T, L);
+    train_layout(dims, T, L, e->opt_train_wgrad);
     S.n = (size_t)B * T * dims.c * H * W;
     S.train = L.total * 4;
     S.z_pred = round256(S.train);
@@ -799,5 +818,57 @@ int lns_train_step(lns_engine* e, float* const* params, const float* z_in, const
     tt.reserve(pp->all.size());
     for (int v : pp->all) tt.push_back(AdamTensor{params[v], grads[v], exp_avg[v], exp_avg_sq[v], (unsigned)e->params[v].numel(), 0u});
     HIPCHK(e, launch_adam_multi(tt.data(), (int)tt.size(), sc, s));
+    return LNS_OK;
+}
+
+// ---- weight gradient of a stride-1 "same" convolution, both forms (csrc/lns_train_kernels.hip, csrc/wgrad_split.inc) ----
+static int wgrad_op_check(int B, int Cin, int Cout, int H, int W, int ksize, int form) {
+    if (B < 1 || B > LNS_MAX_BATCH || Cin < 1 || Cout < 1 || Cin > 65536 || Cout > 65536 || H < 1 || W < 1 || H > 4096 || W > 4096) {
+        g_create_error = "conv_wgrad: B in 1..65535, Cin / Cout in 1..65536, H / W in 1..4096"; return LNS_EINVAL;
+    }
+    if (ksize != 1 && ksize != 3) { g_create_error = "conv_wgrad: ksize must be 1 or 3"; return LNS_EINVAL; }
+    if (form != 0 && form != 1) { g_create_error = "conv_wgrad: form must be 0 (one block per output tile) or 1 (batch-parallel)"; return LNS_EINVAL; }
+    return LNS_OK;
+}
+int lns_op_conv_wgrad_scratch_bytes(int B, int Cin, int Cout, int H, int W, int ksize, int form, size_t* bytes) {
+    if (!bytes) { g_create_error = "conv_wgrad: bytes is null"; return LNS_EINVAL; }
+    if (int rc = wgrad_op_check(B, Cin, Cout, H, W, ksize, form)) return rc;
+    *bytes = form == 1 ? (wgrad_split_scratch_floats(B, H, W, Cin, Cout, ksize) + 63) / 64 * 64 * 4 : 0;
+    return LNS_OK;
+}
+int lns_op_conv_wgrad(const float* dy, const float* x, int B, int Cin, int Cout, int H, int W, int ksize, int dilation, int pad_y,
+                      int pad_x, int form, int accumulate, float* dw, void* scratch, size_t scratch_bytes, void* stream) {
+    // every check precedes the first HIP call
+    if (!dy || !x || !dw) { g_create_error = "conv_wgrad: dy / x / dw is null"; return LNS_EINVAL; }
+    if (int rc = wgrad_op_check(B, Cin, Cout, H, W, ksize, form)) return rc;
+    if (dilation < 1 || dilation > 64) { g_create_error = "conv_wgrad: dilation must be in 1..64"; return LNS_EINVAL; }
+    if ((pad_y != LNS_PAD_ZEROS && pad_y != LNS_PAD_CIRCULAR) || (pad_x != LNS_PAD_ZEROS && pad_x != LNS_PAD_CIRCULAR)) {
+        g_create_error = "conv_wgrad: pad_y / pad_x must be LNS_PAD_ZEROS or LNS_PAD_CIRCULAR"; return LNS_EINVAL;
+    }
+    if (accumulate != 0 && accumulate != 1) { g_create_error = "conv_wgrad: accumulate must be 0 or 1"; return LNS_EINVAL; }
+    size_t need = 0;
+    (void)lns_op_conv_wgrad_scratch_bytes(B, Cin, Cout, H, W, ksize, form, &need);
+    if (form == 1 && (!scratch || scratch_bytes < need)) { g_create_error = fmt("conv_wgrad: scratch too small: need %zu bytes", need); return LNS_ENOMEM; }
+    const int p = dilation * (ksize - 1) / 2;
+    std::vector<int> fr, fc;                                     // the whole-image maps, as tconv_setup builds them
+    build_axis_map(fr, H + 2 * p, H, H, 0.0f, p, p, pad_y);
+    build_axis_map(fc, W + 2 * p, W, W, 0.0f, p, p, pad_x);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (form == 1) OPCHK(init_train_kernels());
+    int* dmap = nullptr;
+    OPCHK(hipMalloc(reinterpret_cast<void**>(&dmap), (fr.size() + fc.size()) * 4));
+    hipError_t he = hipMemcpy(dmap, fr.data(), fr.size() * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(dmap + fr.size(), fc.data(), fc.size() * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess) {
+        WgradArgs a;
+        memset(&a, 0, sizeof a);
+        a.dy = dy; a.x = x; a.rowmap = dmap; a.colmap = dmap + fr.size(); a.dw = dw;
+        a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.k = ksize; a.dil = dilation; a.accumulate = accumulate;
+        a.x_bs = (long)Cin * H * W; a.part = static_cast<float*>(scratch); a.S = wgrad_split_slices(B, H, W, Cin, Cout, ksize);
+        he = form == 1 ? launch_conv_wgrad_split(a, s) : launch_conv_wgrad(a, s);
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    (void)hipFree(dmap);
+    OPCHK(he);
     return LNS_OK;
 }

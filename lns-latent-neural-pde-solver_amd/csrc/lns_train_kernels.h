@@ -34,8 +34,19 @@ struct WgradArgs {
     const int* rowmap; const int* colmap;   // padded coordinate -> source row / column or -1 (H + (k-1) dil entries)
     float* dw;                         // [Cout][Cin][k][k] (OIHW, the parameter's own layout)
     int B, Cin, Cout, H, W, k, dil, accumulate;
+    // batch-parallel form only (wgrad_split.inc); launch_conv_wgrad reads none of these
+    long x_bs;                         // floats between two samples of x (Cin*H*W, or T*c*H*W for a view of z_pred)
+    float* part;                       // [S][Cout][Cin][k*k] partial sums
+    int S;                             // slices = wgrad_split_slices(B, H, W, Cin, Cout, k)
+    int cps, nchunk, patch_pos;        // filled by the launcher
 };
 hipError_t launch_conv_wgrad(const WgradArgs& a, hipStream_t s);
+// Batch-parallel form: K = (sample, 64-pixel chunk) cut into S slices, one block per (co tile, ci tile, slice) writes a
+// partial tile, wgrad_reduce_kernel sums them in ascending slice order (and adds dw when a.accumulate).  Host helpers need no device.
+int wgrad_split_slices(int B, int H, int W, int Cin, int Cout, int k);
+size_t wgrad_split_scratch_floats(int B, int H, int W, int Cin, int Cout, int k);
+hipError_t init_train_kernels();       // dynamic-LDS attributes of the batch-parallel kernels; needs a GPU
+hipError_t launch_conv_wgrad_split(const WgradArgs& a, hipStream_t s);
 
 // conditional propagator: per-channel reductions / modulation of fields, per-sample vector network (one block each)
 hipError_t launch_chan_dot(const float* a, const float* b2, float* out, int BC, int HW, int accumulate, hipStream_t s);

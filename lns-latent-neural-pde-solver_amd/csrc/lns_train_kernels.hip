@@ -7,6 +7,8 @@
 //   * GroupNorm forward that keeps (mean, rstd) and GroupNorm backward; exact-erf GELU forward / backward;
 //   * bias gradient and the reduction of per-sample partials.
 // Hand-written HIP for gfx950; no CPU fallback.
+#include <cstdlib>
+
 #include "lns_train_kernels.h"
 
 namespace lns {
@@ -283,6 +285,8 @@ hipError_t launch_conv_wgrad(const WgradArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(conv_wgrad_kernel, dim3((a.Cout + 63) / 64, (a.Cin + 63) / 64, a.k * a.k), dim3(256), 0, s, a);
     return hipGetLastError();
 }
+
+#include "wgrad_split.inc"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Conditional propagator (train_stage2_twophase_conditional.py:25-121): per-channel reductions / modulation of the

@@ -182,6 +182,7 @@ class Engine:
             raise LnsError("lns_create failed: %s" % L.lns_create_error().decode())
         self._h = h
         self._ws = {}
+        self.options = {}                     # what set_option was given (options never set are at the library's defaults)
         self.device_index = None
         self.params = self._param_table()
 
@@ -231,9 +232,12 @@ class Engine:
     def set_option(self, name, value):
         """Scheduling options of the rollout (include/lns.h lns_set_option): decode_group, decode_streams, overlap,
         prop_priority, track_nonfinite, fa_chunk_mb, fa_fused_gpb, eval_max_steps (longest horizon of rollout_eval; it sizes
-        the evaluation workspace).  Results never depend on them.  "fa_fused" (default 2; 1 = single-buffered kernel, same bits; 0 = off) selects
+        the evaluation workspace), train_wgrad (0: one block per output tile, 1: batch-parallel weight gradient of the
+        training step; it sizes the training workspaces, and the gradients differ by the summation order only).
+        Results never depend on the others.  "fa_fused" (default 2; 1 = single-buffered kernel, same bits; 0 = off) selects
         the arithmetic form of FABlock2D at 64 x 64 planes (in_proj inside the sandwich kernel): ~2e-7 relative on the fields."""
         self._check(self._L.lns_set_option(self._h, name.encode(), int(value)), "lns_set_option")
+        self.options[name] = int(value)
         self._ws.clear()                      # the workspace size depends on the options
 
     def latent_shape(self):
@@ -515,7 +519,36 @@ class Engine:
             self._check(self._L.lns_adam_step(self._h, self._ptr_array(params), self._ptr_array(grads), self._ptr_array(exp_avg),
                                               self._ptr_array(exp_avg_sq), ctypes.byref(spec), self._stream(any_t)), "lns_adam_step")
 
+    def conv_wgrad(self, dy, x, ksize, dilation=1, pad_y=LNS_PAD_CIRCULAR, pad_x=LNS_PAD_CIRCULAR, form=1, accumulate=False, dw=None):
+        """Weight gradient of a stride-1 "same" convolution (lns_op_conv_wgrad): dy [B,Cout,H,W], x [B,Cin,H,W] ->
+        dw [Cout,Cin,ksize,ksize].  form 0: one block per output tile; 1: batch-parallel (option "train_wgrad").
+        accumulate: added to the given dw.  Synchronises."""
+        import torch
+        dy, x = self._dev(dy), self._dev(x)
+        B, Cout, H, W = dy.shape
+        Cin = x.shape[1]
+        if x.dim() != 4 or (x.shape[0], x.shape[2], x.shape[3]) != (B, H, W) or x.device != dy.device:
+            raise LnsError("conv_wgrad: x must be [B,Cin,%d,%d] on dy's device, got %s on %s" % (H, W, tuple(x.shape), x.device))
+        if dw is None:
+            if accumulate:
+                raise LnsError("conv_wgrad: accumulate needs dw")
+            dw = torch.empty((Cout, Cin, ksize, ksize), dtype=torch.float32, device=dy.device)
+        elif tuple(dw.shape) != (Cout, Cin, ksize, ksize) or dw.dtype != torch.float32 or not dw.is_contiguous() or dw.device != dy.device:
+            raise LnsError("conv_wgrad: dw must be a contiguous fp32 [%d,%d,%d,%d] tensor on dy's device" % (Cout, Cin, ksize, ksize))
+        n = ctypes.c_size_t(0)
+        rc = self._L.lns_op_conv_wgrad_scratch_bytes(B, Cin, Cout, H, W, int(ksize), int(form), ctypes.byref(n))
+        with torch.cuda.device(dy.device):
+            scratch = torch.empty(max(int(n.value), 4), dtype=torch.uint8, device=dy.device) if rc == 0 else None
+            if rc == 0:
+                rc = self._L.lns_op_conv_wgrad(dy.data_ptr(), x.data_ptr(), B, Cin, Cout, H, W, int(ksize), int(dilation), int(pad_y),
+                                               int(pad_x), int(form), int(bool(accumulate)), dw.data_ptr(), scratch.data_ptr(),
+                                               int(n.value), self._stream(dy))
+        if rc != 0:
+            raise LnsError("lns_op_conv_wgrad failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return dw
+
     def train_step_workspace_bytes(self, B, h, w, T):
+        """Bytes of the workspace of train_step; follows the "train_wgrad" option (set_option)."""
         n = ctypes.c_size_t(0)
         self._check(self._L.lns_train_step_workspace_bytes(self._h, int(B), int(h), int(w), int(T), ctypes.byref(n)),
                     "lns_train_step_workspace_bytes")

@@ -31,11 +31,12 @@ from . import optim as _optim
 from ._lib import LnsError
 
 LOSS_RING = 4096
+WGRAD_FORMS = {"tile": 0, "split": 1}
 
 
 class Stage2Trainer:
     def __init__(self, model, optimizer=None, lr=1e-3, beta=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 loss_ring=LOSS_RING):
+                 loss_ring=LOSS_RING, wgrad=None):
         if not isinstance(model, _dropin.LatentDynamics):
             raise LnsError("Stage2Trainer needs a LatentDynamics drop-in (lns_amd.dropin), got %s" % type(model).__name__)
         if not beta > 0:
@@ -51,7 +52,9 @@ class Stage2Trainer:
                            "(a torch.optim.Adam state_dict loads into it), got %s" % type(optimizer).__name__)
         self.optimizer = optimizer
         self._key = None               # what the resolved pointers were taken from
-        self._ws = {}                  # (device, B, T, h, w) -> workspace
+        self._ws = {}                  # (device, B, T, h, w, bytes the engine asks for under its current options) -> workspace
+        if wgrad is not None:          # None: the engine's option stays as it is
+            self.set_wgrad(wgrad)
         self._loss = None
         self._loss_i = 0
         self._loss_ring = int(loss_ring)           # steps a returned loss keeps its value: size it to the logging interval
@@ -132,12 +135,22 @@ class Stage2Trainer:
             if p.grad is not g:
                 p.grad = g
 
+    def set_wgrad(self, wgrad):
+        """Weight-gradient kernel of the step: "tile" (one block per output tile) or "split" (batch-parallel); the engine's
+        "train_wgrad" option.  Workspaces are kept per form, so switching on a live trainer allocates once per form."""
+        if wgrad not in WGRAD_FORMS:
+            raise LnsError("wgrad must be None, 'tile' or 'split', got %r" % (wgrad,))
+        self._eng.set_option("train_wgrad", WGRAD_FORMS[wgrad])
+
     def _workspace(self, B, T, h, w):
-        key = (self._device, B, T, h, w)
+        # the size follows the engine's options ("train_wgrad"), however they were set: the library is asked (host-only) and
+        # a workspace is only ever handed to the C call at the size it was allocated for
+        need = self._eng.train_step_workspace_bytes(B, h, w, T)
+        key = (self._device, B, T, h, w, need)
         ws = self._ws.get(key)
         if ws is None:
             with torch.cuda.device(self._device):
-                ws = torch.empty(self._eng.train_step_workspace_bytes(B, h, w, T), dtype=torch.uint8, device=self._device)
+                ws = torch.empty(need, dtype=torch.uint8, device=self._device)
             self._ws[key] = ws
         return ws
 

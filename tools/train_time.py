@@ -1,16 +1,20 @@
-"""Stage-2 training step, three ways, on one box and in one process (synthetic latents, B = 32):
-  (a) autograd   : model(z_in, z_out[, param], F.smooth_l1_loss); loss.backward(); torch.optim.Adam.step()
-  (b) lns Adam   : the same with lns_amd.optim.Adam (one-launch multi-tensor kernel)
-  (c) trainer    : lns_amd.train.Stage2Trainer.step (lns_train_step: forward, loss, backward and Adam in one C call)
+"""Stage-2 training step, four ways, on one box and in one process (synthetic latents, B = 32):
+  (a) autograd      : model(z_in, z_out[, param], F.smooth_l1_loss); loss.backward(); torch.optim.Adam.step()
+  (b) lns Adam      : the same with lns_amd.optim.Adam (one-launch multi-tensor kernel)
+  (c) trainer       : lns_amd.train.Stage2Trainer.step (lns_train_step: forward, loss, backward and Adam in one C call)
+  (d) trainer_split : the same with wgrad="split" (engine option "train_wgrad" = 1: the batch-parallel weight gradient)
 for the reference's shipped training shapes: ns2d_64 (T = 2), sw_half_periodic (T = 5), twophase_cond (T = 5), and
 ns2d_128 (T = 2).  Warm-up, then blocks of 10 steps with one synchronisation before and after each block, the arms
 interleaved block by block; per arm the median block time, its min / max, steps/s and trajectory-steps/s (B * T / time).
 
-    python tools/train_time.py [--blocks 5] [--block 10] [--warmup 5] [--out profiles/train_step_time.json]
-    python tools/train_time.py --only-trainer --preset ns2d_64 --blocks 3      # the run to put under rocprofv3 --kernel-trace --stats
-    python tools/train_time.py --merge-stats ns2d_64:25=out/..._kernel_stats.csv [...] --out profiles/train_step_time.json
-The last form (PRESET:STEPS=CSV, STEPS = warm-up + timed steps of the profiled run) adds, per preset, the GPU kernel time of
-one trainer step (sum of the kernel-stats totals / steps run) and its share of the measured step time to an existing record.
+    python tools/train_time.py [--blocks 5] [--block 10] [--warmup 5] [--out profiles/train_step_time_wgrad.json]
+    python tools/train_time.py --only-trainer --preset ns2d_64 --blocks 3      # the runs to put under rocprofv3 --kernel-trace --stats,
+    python tools/train_time.py --only-trainer-split --preset ns2d_64 --blocks 3  # one per arm
+    python tools/train_time.py --merge-stats ns2d_64:25=out/..._kernel_stats.csv trainer_split/ns2d_64:25=... --out profiles/train_step_time_wgrad.json
+The last form ([ARM/]PRESET:STEPS=CSV, ARM = trainer by default, STEPS = warm-up + timed steps of the profiled run) adds, per
+preset and arm, the GPU kernel time of one step (sum of the kernel-stats totals / steps run), its share of the measured step
+time, the share of the weight-gradient kernels in it and the per-kernel totals (largest first) to an existing record.
+(profiles/train_step_time.json is the record of the three-arm form of this tool, before the split arm existed.)
 """
 import argparse
 import csv
@@ -45,7 +49,7 @@ def build(preset, dev):
     return args, model
 
 
-def arms_for(preset, T, dev, only_trainer=False):
+def arms_for(preset, T, dev, only=None):
     args, probe = build(preset, dev)
     c, h, w = probe._eng.latent_shape()
     del probe
@@ -65,14 +69,13 @@ def arms_for(preset, T, dev, only_trainer=False):
             return loss
         return step
 
-    def trainer_arm():
-        _, model = build(preset, dev)
-        tr = train.Stage2Trainer(model, lr=LR)
+    def trainer_arm(wgrad):
+        _, model = build(preset, dev)            # (its own model, hence its own engine: the option is per engine)
+        tr = train.Stage2Trainer(model, lr=LR, wgrad=wgrad)
         return lambda: tr.step(z_in, z_out, *prm)
-    arms = {"trainer": trainer_arm()}
-    if not only_trainer:
-        arms = {"autograd": autograd_arm(torch.optim.Adam), "lns_adam": autograd_arm(optim.Adam), **arms}
-    return arms, (c, h, w)
+    makers = {"autograd": lambda: autograd_arm(torch.optim.Adam), "lns_adam": lambda: autograd_arm(optim.Adam),
+              "trainer": lambda: trainer_arm("tile"), "trainer_split": lambda: trainer_arm("split")}
+    return {k: mk() for k, mk in makers.items() if only is None or k in only}, (c, h, w)
 
 
 def block_ms(step, n):
@@ -86,7 +89,8 @@ def block_ms(step, n):
 
 
 def measure(preset, T, a, dev):
-    arms, latent = arms_for(preset, T, dev, a.only_trainer)
+    only = ("trainer",) if a.only_trainer else ("trainer_split",) if a.only_trainer_split else None
+    arms, latent = arms_for(preset, T, dev, only)
     for step in arms.values():
         for _ in range(a.warmup):
             step()
@@ -107,6 +111,13 @@ def measure(preset, T, a, dev):
         rec["speedup_lns_adam_over_autograd"] = round(base["step_ms_median"] / rec["lns_adam"]["step_ms_median"], 4)
         rec["autograd_spread_max_over_min"] = round(base["step_ms_max"] / base["step_ms_min"], 4)
         rec["trainer_within_autograd_spread"] = bool(base["step_ms_min"] <= rec["trainer"]["step_ms_median"] <= base["step_ms_max"])
+    if "trainer" in rec and "trainer_split" in rec:
+        # the yardstick of the split arm is the trainer arm of the same run (option 0): a gain only counts when the split
+        # arm's median is below the FASTEST block of that arm
+        tile, split = rec["trainer"], rec["trainer_split"]
+        rec["speedup_split_over_trainer"] = round(tile["step_ms_median"] / split["step_ms_median"], 4)
+        rec["trainer_spread_max_over_min"] = round(tile["step_ms_max"] / tile["step_ms_min"], 4)
+        rec["split_median_below_trainer_min"] = bool(split["step_ms_median"] < tile["step_ms_min"])
     return rec
 
 
@@ -116,6 +127,8 @@ def merge_stats(a):
     for item in a.merge_stats:
         spec, path = item.split("=", 1)
         preset, _, steps = spec.partition(":")
+        arm, _, preset = preset.rpartition("/")
+        arm = arm or "trainer"
         with open(path) as f:
             rows = list(csv.DictReader(f))
         total_ns = sum(float(r["TotalDurationNs"]) for r in rows)
@@ -123,10 +136,17 @@ def merge_stats(a):
         rec = next(r for r in doc["shapes"] if r["preset"] == preset)
         n = int(steps)
         gpu_ms = total_ns / 1e6 / n
-        rec["trainer"]["gpu_kernel_ms_per_step"] = round(gpu_ms, 4)
-        rec["trainer"]["kernel_launches_per_step"] = round(calls / n, 1)
-        rec["trainer"]["gpu_kernel_share_of_step"] = round(gpu_ms / rec["trainer"]["step_ms_median"], 4)
-        rec["trainer"]["gpu_kernel_time_source"] = "rocprofv3 --kernel-trace --stats over %d steps (warm-up included), a run of its own" % n
+        out = rec[arm]
+        out["gpu_kernel_ms_per_step"] = round(gpu_ms, 4)
+        out["kernel_launches_per_step"] = round(calls / n, 1)
+        out["gpu_kernel_share_of_step"] = round(gpu_ms / out["step_ms_median"], 4)
+        out["gpu_kernel_time_source"] = "rocprofv3 --kernel-trace --stats over %d steps (warm-up included), a run of its own" % n
+        wgrad_ns = sum(float(r["TotalDurationNs"]) for r in rows if "wgrad" in r["Name"])
+        out["wgrad_share_of_kernel_time"] = round(wgrad_ns / total_ns, 4)
+        top = sorted(rows, key=lambda r: -float(r["TotalDurationNs"]))[:8]
+        out["kernels_ms_per_step"] = [dict(name=r["Name"].split("(")[0][:96], ms=round(float(r["TotalDurationNs"]) / 1e6 / n, 4),
+                                           calls_per_step=round(int(r["Calls"]) / n, 1),
+                                           share=round(float(r["TotalDurationNs"]) / total_ns, 4)) for r in top]
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
 
@@ -138,6 +158,7 @@ def main():
     ap.add_argument("--block", type=int, default=10, help="steps per synchronised block")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only-trainer", action="store_true")
+    ap.add_argument("--only-trainer-split", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--merge-stats", nargs="*", default=None, metavar="PRESET:STEPS=CSV")
     a = ap.parse_args()
