@@ -351,6 +351,66 @@ int lns_train_step(lns_engine* e, float* const* params, const float* z_in, const
                    float* const* exp_avg_sq, const lns_adam_spec* adam_spec, float* loss_out, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- gradient-norm clipping and AdamW in the training step ----------------------------------------------------------
+ * No reference counterpart: the reference's loop (train_stage2_ns2d.py:210-216) neither clips nor decays.  What is
+ * reproduced is torch's own text: torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type = 2)
+ *     norm = || all gradients ||_2;  coef = min(1, max_norm / (norm + 1e-6));  g *= coef
+ * and torch.optim.AdamW (p *= 1 - lr weight_decay, then Adam on the gradient alone).  Everything is enqueued on `stream`:
+ * no host read-back, no allocation, no copy from host memory; argument errors are decided before any device work.
+ *
+ * The norm: a block squares and sums LNS_NORM_CHUNK consecutive elements of one tensor in double (the square of an fp32
+ * value is exact there) and stores one double partial; one finishing block adds the partials in ascending order.  No
+ * atomics; the order depends on the tensors' lengths alone, so the norm is bit-reproducible.  *norm_out = (float)sqrt(sum);
+ * *coef_out as above in fp32 (max_norm <= 0: the norm is computed and coef = 1; a NaN norm gives a NaN coef, as torch).
+ * flags: an lns_update_spec's (unknown bits: LNS_EINVAL; LNS_UPDATE_DECOUPLED_WD means nothing here).  With
+ * LNS_UPDATE_SKIP_NONFINITE a norm that is inf or NaN writes coef = -1 -- the one negative value, which the
+ * update and scale calls below read as "change nothing" -- and adds 1 to *skipped_counter (device uint32, nullable; the
+ * caller zeroes it once).  scratch: device, lns_grad_norm_scratch_bytes = 8 * sum(ceil(numel[i] / LNS_NORM_CHUNK)) rounded
+ * up to 256 (host only; over all n entries).  0 < numel[i] < 2^31; entries whose gradient pointer is null are left out.
+ * norm_out / coef_out: device floats, either may be null.  LNS_ENOMEM: scratch null or short.  No engine: the message of a
+ * refused call is lns_create_error()'s. */
+#define LNS_NORM_CHUNK 2048
+#define LNS_UPDATE_DECOUPLED_WD 1u     /* weight_decay is AdamW's: p *= 1 - lr weight_decay, nothing added to the gradient */
+#define LNS_UPDATE_SKIP_NONFINITE 2u   /* a non-finite gradient norm skips the update (see above) */
+int lns_grad_norm_scratch_bytes(int n, const int64_t* numel, size_t* bytes);
+int lns_grad_norm_tensors(int n, const float* const* grads, const int64_t* numel, double max_norm, float* norm_out,
+                          float* coef_out, uint32_t* skipped_counter, uint32_t flags, void* scratch, size_t scratch_bytes,
+                          void* stream);
+/* g *= *coef for every tensor (the second half of clip_grad_norm_ when no update follows); coef == -1: nothing. */
+int lns_grad_scale_tensors(int n, float* const* grads, const int64_t* numel, const float* coef, void* stream);
+
+/* lns_adam_spec plus what the clipped step needs.  size = sizeof(lns_update_spec); unknown flag bits and a NaN max_norm
+ * are LNS_EINVAL like a wrong size (the message names the field); lr .. step are checked as in lns_adam_spec.
+ * max_norm <= 0: the norm is computed, nothing is clipped.  (lns_update_step_tensors takes its coefficient from the caller
+ * and does not read max_norm.) */
+typedef struct lns_update_spec {
+    uint32_t size;
+    uint32_t flags;                             /* LNS_UPDATE_* */
+    double lr, beta1, beta2, eps, weight_decay;
+    int64_t step;
+    double max_norm;
+} lns_update_spec;
+/* Adam / AdamW of n tensors on g * *coef, in one launch per 96 tensors.  coef (device float, nullable): with it the
+ * gradient buffers hold g * coef afterwards, as .grad does after clip_grad_norm_; null: gradients are used and left as
+ * they are.  *coef == -1 (a skipped step): params, exp_avg, exp_avg_sq and grads keep their bits.  `step` lives on the host
+ * and cannot know about a skip: the caller advances it all the same, so a skipped step still moves the bias corrections on. */
+int lns_update_step_tensors(int n, float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                            const int64_t* numel, const lns_update_spec* spec, const float* coef, void* stream);
+
+/* lns_train_step with the clipped update: forward -> loss -> backward -> norm of the propagator's gradients -> update, in
+ * that order on `stream`; honours "train_wgrad" like lns_train_step.  `spec` is required (gradients alone: lns_train_step
+ * with adam_spec == NULL).  *norm_out (device float, nullable) = the norm before clipping; `grads` hold the clipped
+ * gradients afterwards.  The workspace is lns_train_step's followed by the norm partials (8 bytes per LNS_NORM_CHUNK of
+ * every propagator tensor), the coefficient (float), the norm (float; used when norm_out is null) and the counter of
+ * skipped steps (uint32), each rounded up to 256 bytes: the coefficient sits 768 bytes, the counter 256 bytes before the
+ * end of lns_train_step_clip_workspace_bytes.  The caller zeroes the counter once after allocating.  Errors as
+ * lns_train_step. */
+int lns_train_step_clip_workspace_bytes(lns_engine* e, int B, int h, int w, int T, size_t* bytes);
+int lns_train_step_clip(lns_engine* e, float* const* params, const float* z_in, const float* z_out, const float* param_or_null,
+                        int B, int h, int w, int T, float beta, float* const* grads, float* const* exp_avg,
+                        float* const* exp_avg_sq, const lns_update_spec* spec, float* loss_out, float* norm_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- diagnostics -------------------------------------------------------- */
 /* Layer trace: when enabled the run calls synchronise after every reference
  * module boundary and keep a host copy of its output (tests compare them with
@@ -377,7 +437,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
 
 /* Build-time features of this library: "experimental" = compiled with -DLNS_EXPERIMENTAL (the measured-slower kernel
  * forms behind op-level variants 15 / 16 / 18 / 19 exist; the shipped library does not carry them); "train_wgrad_split" = the
- * batch-parallel weight gradient (option "train_wgrad", lns_op_conv_wgrad) is there.  1 / 0; -1: unknown name.
+ * batch-parallel weight gradient (option "train_wgrad", lns_op_conv_wgrad) is there; "train_clip" = lns_train_step_clip and
+ * the gradient-norm / update calls are there.  1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
 

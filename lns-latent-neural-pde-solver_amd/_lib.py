@@ -82,6 +82,19 @@ class LnsAdamSpec(ctypes.Structure):
     ]
 
 
+LNS_NORM_CHUNK = 2048
+LNS_UPDATE_DECOUPLED_WD, LNS_UPDATE_SKIP_NONFINITE = 1, 2
+
+
+class LnsUpdateSpec(ctypes.Structure):
+    """Mirror of `struct lns_update_spec` (include/lns.h): lns_adam_spec's fields, flags (LNS_UPDATE_*) and max_norm."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("step", ctypes.c_int64),
+        ("max_norm", ctypes.c_double),
+    ]
+
+
 # every symbol include/lns.h declares (tests check the library exports them all)
 SYMBOLS = [
     "lns_create_error", "lns_create", "lns_destroy", "lns_last_error", "lns_num_params",
@@ -90,6 +103,8 @@ SYMBOLS = [
     "lns_rollout_eval_workspace_bytes", "lns_rollout_eval", "lns_rollout_latent_eval",
     "lns_train_workspace_bytes", "lns_train_forward", "lns_train_backward",
     "lns_loss_smooth_l1", "lns_adam_step", "lns_adam_step_tensors", "lns_train_step_workspace_bytes", "lns_train_step",
+    "lns_grad_norm_scratch_bytes", "lns_grad_norm_tensors", "lns_grad_scale_tensors", "lns_update_step_tensors",
+    "lns_train_step_clip_workspace_bytes", "lns_train_step_clip",
     "lns_trace_enable", "lns_trace_count", "lns_trace_info", "lns_trace_copy",
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
     "lns_op_conv_wgrad_scratch_bytes", "lns_op_conv_wgrad",
@@ -173,6 +188,14 @@ def lib():
         L.lns_adam_step_tensors.argtypes = [i, vp, vp, vp, vp, i64p, ap, vp]
         L.lns_train_step_workspace_bytes.argtypes = [vp, i, i, i, i, c.POINTER(c.c_size_t)]
         L.lns_train_step.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, c.c_float, vp, vp, vp, ap, vp, vp, c.c_size_t, vp]
+    if hasattr(L, "lns_train_step_clip"):
+        up = c.POINTER(LnsUpdateSpec)
+        L.lns_grad_norm_scratch_bytes.argtypes = [i, i64p, c.POINTER(c.c_size_t)]
+        L.lns_grad_norm_tensors.argtypes = [i, vp, i64p, c.c_double, vp, vp, vp, c.c_uint32, vp, c.c_size_t, vp]
+        L.lns_grad_scale_tensors.argtypes = [i, vp, i64p, vp, vp]
+        L.lns_update_step_tensors.argtypes = [i, vp, vp, vp, vp, i64p, up, vp, vp]
+        L.lns_train_step_clip_workspace_bytes.argtypes = [vp, i, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_train_step_clip.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, c.c_float, vp, vp, vp, up, vp, vp, vp, c.c_size_t, vp]
     L.lns_build_has.argtypes = [c.c_char_p]
     L.lns_trace_enable.argtypes = [vp, i]
     L.lns_trace_count.argtypes = [vp]

@@ -2571,6 +2571,7 @@ int lns_build_has(const char* feature) {
     if (!feature) return -1;
     if (!strcmp(feature, "experimental")) return build_has_experimental() ? 1 : 0;
     if (!strcmp(feature, "train_wgrad_split")) return 1;
+    if (!strcmp(feature, "train_clip")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else

@@ -671,6 +671,49 @@ int adam_scalars(const lns_adam_spec* sp, AdamScalars& sc, std::string& err) {
     return LNS_OK;
 }
 
+// max_norm as the norm kernel takes it: 0 = no clipping.  A positive double below fp32's smallest denormal stays positive
+// (it clips to ~0, as torch would) instead of rounding to "no clipping"; beyond fp32's range it is inf, which clips nothing.
+float clip_threshold(double max_norm) {
+    if (!(max_norm > 0.0)) return 0.0f;
+    const float f = (float)max_norm;
+    return f > 0.0f ? f : 1.401298464e-45f;                  // FLT_TRUE_MIN
+}
+
+// lns_update_spec -> the scalars of the clipped / decoupled update; what lns_adam_spec shares is checked by adam_scalars
+struct UpdatePlan { AdamScalars sc; int decoupled = 0; float decay = 1.0f; float max_norm = 0.0f; int skip = 0; };
+int update_scalars(const lns_update_spec* sp, UpdatePlan& u, std::string& err) {
+    if (!sp || sp->size != sizeof(lns_update_spec)) { err = "update spec is null or its size field is not sizeof(lns_update_spec)"; return LNS_EINVAL; }
+    if (sp->flags & ~(LNS_UPDATE_DECOUPLED_WD | LNS_UPDATE_SKIP_NONFINITE)) { err = fmt("update spec: unknown flags 0x%x", sp->flags); return LNS_EINVAL; }
+    if (std::isnan(sp->max_norm)) { err = "update spec: max_norm is NaN (<= 0 means: no clipping)"; return LNS_EINVAL; }
+    lns_adam_spec as;
+    as.size = sizeof(lns_adam_spec); as.reserved = 0;
+    as.lr = sp->lr; as.beta1 = sp->beta1; as.beta2 = sp->beta2; as.eps = sp->eps; as.weight_decay = sp->weight_decay; as.step = sp->step;
+    if (int rc = adam_scalars(&as, u.sc, err)) return rc;
+    u.decoupled = (sp->flags & LNS_UPDATE_DECOUPLED_WD) ? 1 : 0;
+    u.skip = (sp->flags & LNS_UPDATE_SKIP_NONFINITE) ? 1 : 0;
+    if (u.decoupled) {                                                // torch.optim.AdamW: param.mul_(1 - lr * weight_decay)
+        u.decay = (float)(1.0 - sp->lr * sp->weight_decay);
+        u.sc.weight_decay = 0.0f;
+    }
+    u.max_norm = clip_threshold(sp->max_norm);
+    return LNS_OK;
+}
+
+static_assert(LNS_NORM_CHUNK == 2048, "include/lns.h names the chunk of grad_sumsq_multi_kernel (lns_optim.inc: ADAM_CHUNK)");
+// n gradient tensors -> the norm kernel's table (null gradients left out) and the scratch the whole list needs
+int norm_tensors(int n, const float* const* grads, const int64_t* numel, std::vector<NormTensor>* tt, size_t& bytes, std::string& err) {
+    if (n < 0 || (n > 0 && !numel)) { err = "grad norm: numel is null"; return LNS_EINVAL; }
+    int64_t chunks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] < 1 || numel[i] >= (int64_t)1 << 31) { err = fmt("grad norm: tensor %d has %lld elements (1 .. 2^31 - 1)", i, (long long)numel[i]); return LNS_EINVAL; }
+        chunks += (numel[i] + LNS_NORM_CHUNK - 1) / LNS_NORM_CHUNK;
+        if (tt && grads[i]) tt->push_back(NormTensor{grads[i], (unsigned)numel[i], 0u});
+    }
+    if (chunks >= (int64_t)1 << 31) { err = "grad norm: more than 2^31 - 1 chunks in one call"; return LNS_EINVAL; }
+    bytes = round256((size_t)chunks * 8);
+    return LNS_OK;
+}
+
 static_assert(LNS_SL1_CHUNK == SL1_CHUNK, "include/lns.h and lns_train_kernels.h name the same chunk");
 constexpr int64_t SL1_MAX_N = (int64_t)SL1_CHUNK << 30;       // 2^30 blocks: grid and partial count stay 32-bit
 int loss_check(int64_t n, float beta, const void* loss_out, std::string& err) {
@@ -694,6 +737,18 @@ int step_layout(lns_engine* e, int B, int H, int W, int T, StepLayout& S) {
     S.part = S.dz + round256(S.n * 4);
     S.total = S.part + round256((size_t)smooth_l1_partials((long)S.n) * 4);
     return LNS_OK;
+}
+
+// tail of the clipped step's workspace (bytes from its start): norm partials | coefficient | norm | counter of skipped steps
+struct ClipLayout { size_t part = 0, coef = 0, norm = 0, counter = 0, total = 0; };
+void clip_layout(const lns_engine* e, const PropParams& pp, const StepLayout& S, ClipLayout& C) {
+    size_t chunks = 0;
+    for (int v : pp.all) chunks += (e->params[v].numel() + LNS_NORM_CHUNK - 1) / LNS_NORM_CHUNK;
+    C.part = S.total;
+    C.coef = C.part + round256(chunks * 8);
+    C.norm = C.coef + 256;
+    C.counter = C.norm + 256;
+    C.total = C.counter + 256;
 }
 
 }  // namespace
@@ -771,10 +826,11 @@ int lns_train_step_workspace_bytes(lns_engine* e, int B, int H, int W, int T, si
     return lns_train_workspace_bytes(e, B, H, W, T, &tb);
 }
 
-int lns_train_step(lns_engine* e, float* const* params, const float* z_in, const float* z_out, const float* param,
-                   int B, int H, int W, int T, float beta, float* const* grads, float* const* exp_avg,
-                   float* const* exp_avg_sq, const lns_adam_spec* adam_spec, float* loss_out, void* ws,
-                   size_t ws_bytes, void* stream) {
+// lns_train_step (adam_spec or neither) and lns_train_step_clip (update_spec): one body, so the two cannot drift apart
+static int train_step_impl(lns_engine* e, float* const* params, const float* z_in, const float* z_out, const float* param,
+                           int B, int H, int W, int T, float beta, float* const* grads, float* const* exp_avg,
+                           float* const* exp_avg_sq, const lns_adam_spec* adam_spec, const lns_update_spec* update_spec, bool clip,
+                           float* loss_out, float* norm_out, void* ws, size_t ws_bytes, void* stream) {
     if (!e) return LNS_EINVAL;
     // ---- host-only checks ----
     if (e->cfg.prop_kind != LNS_PROP_PLAIN && e->cfg.prop_kind != LNS_PROP_CONDITIONAL) { e->err = "training step: engine has no propagator"; return LNS_ESTATE; }
@@ -786,22 +842,28 @@ int lns_train_step(lns_engine* e, float* const* params, const float* z_in, const
     if (e->cfg.prop_kind == LNS_PROP_CONDITIONAL && !param) { e->err = "training step: conditional propagator needs param"; return LNS_EINVAL; }
     int rc;
     AdamScalars sc;
+    UpdatePlan up;
     if (adam_spec && (rc = adam_scalars(adam_spec, sc, e->err))) return rc;
+    if (clip && (rc = update_scalars(update_spec, up, e->err))) return rc;
     const PropParams* pp;
     if ((rc = prop_params(e, &pp)) || (rc = check_params(e, *pp, params, "parameter")) ||
         (rc = check_params(e, *pp, const_cast<const float* const*>(grads), "gradient"))) return rc;
-    if (adam_spec) {
+    if (adam_spec || clip) {
         if (!exp_avg || !exp_avg_sq) { e->err = "training step: exp_avg / exp_avg_sq array is null (adam_spec is given)"; return LNS_EINVAL; }
         if ((rc = check_params(e, *pp, const_cast<const float* const*>(exp_avg), "exp_avg")) ||
             (rc = check_params(e, *pp, const_cast<const float* const*>(exp_avg_sq), "exp_avg_sq"))) return rc;
     }
     StepLayout S;
     if ((rc = step_layout(e, B, H, W, T, S)) || (rc = loss_check((int64_t)S.n, beta, loss_out, e->err))) return rc;
-    if (!ws || ws_bytes < S.total) { e->err = fmt("training step workspace too small: need %zu bytes", S.total); return LNS_ENOMEM; }
+    ClipLayout C;
+    if (clip) clip_layout(e, *pp, S, C);
+    const size_t need = clip ? C.total : S.total;
+    if (!ws || ws_bytes < need) { e->err = fmt("training step workspace too small: need %zu bytes", need); return LNS_ENOMEM; }
     // ---- where the tensors live (pointer attributes: the first HIP calls), still before anything is enqueued ----
     int device = -1;
     if ((rc = train_device_of(e, z_in, &device)) || (rc = train_same_device(e, device, z_out, "z_out")) ||
         (rc = train_same_device(e, device, loss_out, "loss_out")) || (rc = train_same_device(e, device, ws, "the workspace"))) return rc;
+    if (clip && norm_out && (rc = train_same_device(e, device, norm_out, "norm_out"))) return rc;
     // ---- device work, in stream order ----
     char* base = static_cast<char*>(ws);
     float* z_pred = reinterpret_cast<float*>(base + S.z_pred);
@@ -812,12 +874,106 @@ int lns_train_step(lns_engine* e, float* const* params, const float* z_in, const
     DeviceGuard dg(device);
     HIPCHK(e, launch_smooth_l1(z_pred, z_out, (long)S.n, beta, loss_out, dz, part, s));
     if ((rc = lns_train_backward(e, params, z_in, z_pred, dz, B, H, W, T, grads, nullptr, ws, S.train, stream))) return rc;
-    if (!adam_spec) return LNS_OK;
+    if (!adam_spec && !clip) return LNS_OK;
     // only the propagator's tensors: other entries of the arrays are not this step's business
     std::vector<AdamTensor> tt;
     tt.reserve(pp->all.size());
     for (int v : pp->all) tt.push_back(AdamTensor{params[v], grads[v], exp_avg[v], exp_avg_sq[v], (unsigned)e->params[v].numel(), 0u});
-    HIPCHK(e, launch_adam_multi(tt.data(), (int)tt.size(), sc, s));
+    if (!clip) {
+        HIPCHK(e, launch_adam_multi(tt.data(), (int)tt.size(), sc, s));
+        return LNS_OK;
+    }
+    std::vector<NormTensor> nt;
+    nt.reserve(tt.size());
+    for (const AdamTensor& t : tt) nt.push_back(NormTensor{t.g, t.n, 0u});
+    float* coef = reinterpret_cast<float*>(base + C.coef);
+    HIPCHK(e, launch_grad_norm(nt.data(), (int)nt.size(), up.max_norm, up.skip, norm_out ? norm_out : reinterpret_cast<float*>(base + C.norm),
+                               coef, reinterpret_cast<unsigned*>(base + C.counter), reinterpret_cast<double*>(base + C.part), s));
+    HIPCHK(e, launch_update_multi(tt.data(), (int)tt.size(), up.sc, coef, up.decoupled, up.decay, s));
+    return LNS_OK;
+}
+
+int lns_train_step(lns_engine* e, float* const* params, const float* z_in, const float* z_out, const float* param,
+                   int B, int H, int W, int T, float beta, float* const* grads, float* const* exp_avg,
+                   float* const* exp_avg_sq, const lns_adam_spec* adam_spec, float* loss_out, void* ws,
+                   size_t ws_bytes, void* stream) {
+    return train_step_impl(e, params, z_in, z_out, param, B, H, W, T, beta, grads, exp_avg, exp_avg_sq, adam_spec, nullptr, false,
+                           loss_out, nullptr, ws, ws_bytes, stream);
+}
+
+int lns_train_step_clip(lns_engine* e, float* const* params, const float* z_in, const float* z_out, const float* param,
+                        int B, int H, int W, int T, float beta, float* const* grads, float* const* exp_avg,
+                        float* const* exp_avg_sq, const lns_update_spec* spec, float* loss_out, float* norm_out, void* ws,
+                        size_t ws_bytes, void* stream) {
+    return train_step_impl(e, params, z_in, z_out, param, B, H, W, T, beta, grads, exp_avg, exp_avg_sq, nullptr, spec, true,
+                           loss_out, norm_out, ws, ws_bytes, stream);
+}
+
+int lns_train_step_clip_workspace_bytes(lns_engine* e, int B, int H, int W, int T, size_t* bytes) {
+    size_t step = 0;
+    if (e && !bytes) { e->err = "training step: bytes is null"; return LNS_EINVAL; }
+    if (int rc = lns_train_step_workspace_bytes(e, B, H, W, T, &step)) return rc;
+    const PropParams* pp;
+    if (int rc = prop_params(e, &pp)) return rc;
+    StepLayout S; ClipLayout C;
+    S.total = step;
+    clip_layout(e, *pp, S, C);
+    *bytes = C.total;
+    return LNS_OK;
+}
+
+// ---- the norm and the update on their own: any n fp32 tensors (lns_amd/optim.py) ----
+int lns_grad_norm_scratch_bytes(int n, const int64_t* numel, size_t* bytes) {
+    std::string& err = g_create_error;
+    if (!bytes) { err = "grad norm: bytes is null"; return LNS_EINVAL; }
+    return norm_tensors(n, nullptr, numel, nullptr, *bytes, err);
+}
+
+int lns_grad_norm_tensors(int n, const float* const* grads, const int64_t* numel, double max_norm, float* norm_out, float* coef_out,
+                          uint32_t* skipped, uint32_t flags, void* scratch, size_t scratch_bytes, void* stream) {
+    std::string& err = g_create_error;
+    if (n < 0 || (n > 0 && !grads)) { err = "grad norm: grads is null"; return LNS_EINVAL; }
+    if (flags & ~(LNS_UPDATE_DECOUPLED_WD | LNS_UPDATE_SKIP_NONFINITE)) { err = fmt("grad norm: unknown flags 0x%x", flags); return LNS_EINVAL; }
+    if (std::isnan(max_norm)) { err = "grad norm: max_norm is NaN (<= 0 means: no clipping)"; return LNS_EINVAL; }
+    std::vector<NormTensor> tt;
+    size_t need = 0;
+    if (int rc = norm_tensors(n, grads, numel, &tt, need, err)) return rc;
+    if (need > 0 && (!scratch || scratch_bytes < need)) { err = fmt("grad norm: scratch must hold %zu bytes", need); return LNS_ENOMEM; }
+    const hipError_t rc = launch_grad_norm(tt.data(), (int)tt.size(), clip_threshold(max_norm), (flags & LNS_UPDATE_SKIP_NONFINITE) ? 1 : 0, norm_out, coef_out,
+                                           skipped, static_cast<double*>(scratch), static_cast<hipStream_t>(stream));
+    if (rc != hipSuccess) { err = std::string("grad norm: ") + hipGetErrorString(rc); return LNS_EHIP; }
+    return LNS_OK;
+}
+
+int lns_grad_scale_tensors(int n, float* const* grads, const int64_t* numel, const float* coef, void* stream) {
+    std::string& err = g_create_error;
+    if (n < 0 || (n > 0 && !grads)) { err = "grad scale: grads is null"; return LNS_EINVAL; }
+    if (!coef) { err = "grad scale: coef is null"; return LNS_EINVAL; }
+    std::vector<NormTensor> tt;
+    size_t unused = 0;
+    if (int rc = norm_tensors(n, grads, numel, &tt, unused, err)) return rc;
+    if (tt.empty()) return LNS_OK;
+    const hipError_t rc = launch_grad_scale(tt.data(), (int)tt.size(), coef, static_cast<hipStream_t>(stream));
+    if (rc != hipSuccess) { err = std::string("grad scale: ") + hipGetErrorString(rc); return LNS_EHIP; }
+    return LNS_OK;
+}
+
+int lns_update_step_tensors(int n, float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                            const int64_t* numel, const lns_update_spec* spec, const float* coef, void* stream) {
+    std::string& err = g_create_error;
+    if (n < 0 || (n > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel))) { err = "update: null pointer array"; return LNS_EINVAL; }
+    UpdatePlan up;
+    if (int rc = update_scalars(spec, up, err)) return rc;
+    std::vector<AdamTensor> tt;
+    tt.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]) continue;
+        if (numel[i] < 1 || numel[i] >= (int64_t)1 << 31) { err = fmt("update: tensor %d has %lld elements (1 .. 2^31 - 1)", i, (long long)numel[i]); return LNS_EINVAL; }
+        tt.push_back(AdamTensor{params[i], grads[i], exp_avg[i], exp_avg_sq[i], (unsigned)numel[i], 0u});
+    }
+    if (tt.empty()) return LNS_OK;
+    const hipError_t rc = launch_update_multi(tt.data(), (int)tt.size(), up.sc, coef, up.decoupled, up.decay, static_cast<hipStream_t>(stream));
+    if (rc != hipSuccess) { err = std::string("update: ") + hipGetErrorString(rc); return LNS_EHIP; }
     return LNS_OK;
 }
 

@@ -73,4 +73,14 @@ struct AdamTensor { float* p; const float* g; float* m; float* v; unsigned n; un
 struct AdamScalars { float step_size, beta1, one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt, eps, weight_decay; };
 hipError_t launch_adam_multi(AdamTensor* tensors, int count, const AdamScalars& sc, hipStream_t s);
 
+// clip_grad_norm_'s global L2 norm (double partials, one per 2048-element chunk of a tensor, fixed summation order) and
+// clip coefficient of `count` gradient tensors as device floats; the update on the clipped gradient (Adam or AdamW).
+struct NormTensor { const float* g; unsigned n; unsigned first; };
+long grad_norm_partials(const NormTensor* tensors, int count);
+hipError_t launch_grad_norm(const NormTensor* tensors, int count, float max_norm, int skip_nonfinite, float* norm_out, float* coef_out,
+                            unsigned* skipped, double* partial, hipStream_t s);
+hipError_t launch_grad_scale(const NormTensor* tensors, int count, const float* coef, hipStream_t s);
+hipError_t launch_update_multi(AdamTensor* tensors, int count, const AdamScalars& sc, const float* coef, int decoupled, float decay,
+                               hipStream_t s);
+
 }  // namespace lns

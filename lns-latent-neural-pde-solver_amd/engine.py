@@ -115,6 +115,18 @@ def adam_spec(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1):
     return spec
 
 
+def update_spec(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, max_norm=0.0, decoupled=False, skip_nonfinite=False):
+    """`lns_update_spec`: adam_spec's fields, the clip threshold (`max_norm` <= 0 or None: the norm is computed, nothing is
+    clipped) and the LNS_UPDATE_* flags (decoupled: AdamW's weight decay; skip_nonfinite: no update on an inf / NaN norm)."""
+    spec = _lib.LnsUpdateSpec()
+    spec.size = ctypes.sizeof(_lib.LnsUpdateSpec)
+    spec.flags = (_lib.LNS_UPDATE_DECOUPLED_WD if decoupled else 0) | (_lib.LNS_UPDATE_SKIP_NONFINITE if skip_nonfinite else 0)
+    spec.lr, spec.beta1, spec.beta2 = float(lr), float(betas[0]), float(betas[1])
+    spec.eps, spec.weight_decay, spec.step = float(eps), float(weight_decay), int(step)
+    spec.max_norm = 0.0 if max_norm is None else float(max_norm)
+    return spec
+
+
 def smooth_l1(pred, target, beta=1.0, need_grad=True, loss_out=None, grad_out=None):
     """F.smooth_l1_loss(pred, target, beta=beta) (train_stage2_ns2d.py:213) and dL/dpred in one pass on the HIP kernel
     (lns_loss_smooth_l1): returns (0-dim device tensor, gradient like pred or None).  Bit-reproducible; never
@@ -587,6 +599,49 @@ class Engine:
                                                ctypes.byref(spec) if spec is not None else None, loss_out.data_ptr(),
                                                workspace.data_ptr(), workspace.numel(), self._stream(z_in)), "lns_train_step")
         return loss_out
+
+    def train_step_clip_workspace_bytes(self, B, h, w, T):
+        """Bytes of the workspace of train_step_clip: train_step's, then the norm partials, the clip coefficient (768 bytes
+        before the end), the norm and the counter of skipped steps (256 bytes before the end; the caller zeroes it once)."""
+        n = ctypes.c_size_t(0)
+        self._check(self._L.lns_train_step_clip_workspace_bytes(self._h, int(B), int(h), int(w), int(T), ctypes.byref(n)),
+                    "lns_train_step_clip_workspace_bytes")
+        return int(n.value)
+
+    def train_step_clip(self, params, z_in, z_out, grads, exp_avg, exp_avg_sq, spec, param=None, beta=1.0, loss_out=None,
+                        norm_out=None, workspace=None):
+        """train_step with gradient-norm clipping and / or AdamW (lns_train_step_clip): forward, loss, backward, the global
+        L2 norm of the propagator's gradients, then the update on the clipped gradients, which `grads` hold afterwards.
+        spec: update_spec(...).  Returns (loss, norm before clipping) as 0-dim device tensors; never synchronises.  A
+        workspace allocated here has its counter of skipped steps zeroed; a caller's own workspace is the caller's to zero."""
+        import torch
+        z_in, z_out = self._dev(z_in), self._dev(z_out)
+        if z_in.dim() == 5:
+            if z_in.shape[1] != 1:
+                raise LnsError("z_in must be [B,1,c,h,w] (t_in == 1)")
+            z_in = z_in[:, 0]
+        B, c, h, w = z_in.shape
+        if z_out.dim() != 5 or z_out.shape[0] != B or tuple(z_out.shape[2:]) != (c, h, w) or z_out.device != z_in.device:
+            raise LnsError("z_out must be [B,T,%d,%d,%d] on z_in's device, got %s on %s" % (c, h, w, tuple(z_out.shape), z_out.device))
+        T = int(z_out.shape[1])
+        pc = self._param(param, z_in)
+
+        def arr(t):
+            return self._ptr_array(t) if isinstance(t, dict) else t
+        with torch.cuda.device(z_in.device):
+            if workspace is None:
+                workspace = torch.empty(self.train_step_clip_workspace_bytes(B, h, w, T), dtype=torch.uint8, device=z_in.device)
+                workspace[-256:].zero_()
+            if loss_out is None:
+                loss_out = torch.empty((), dtype=torch.float32, device=z_in.device)
+            if norm_out is None:
+                norm_out = torch.empty((), dtype=torch.float32, device=z_in.device)
+            self._check(self._L.lns_train_step_clip(self._h, arr(params), z_in.data_ptr(), z_out.data_ptr(),
+                                                    pc.data_ptr() if pc is not None else None, B, h, w, T, float(beta), arr(grads),
+                                                    arr(exp_avg), arr(exp_avg_sq), ctypes.byref(spec), loss_out.data_ptr(),
+                                                    norm_out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                                    self._stream(z_in)), "lns_train_step_clip")
+        return loss_out, norm_out
 
     def check_finite(self, B, device=None):
         """Raises LnsError naming the first layer / sample whose output held inf or NaN in the LAST call (encode /

@@ -20,6 +20,16 @@ resolved once (and again only when the drop-in's tree epoch moves or a tensor's 
   * the returned loss is a 0-dim view into a ring of `loss_ring` (default 4096) device floats: it keeps its value for that
     many further steps (read it, or `.clone()` it, before; a loop that reduces an epoch's losses at its end passes
     `loss_ring=len(train_loader)`).
+
+Not in the reference's loop, but what a BPTT rollout at a higher learning rate asks for: `max_grad_norm` clips the global L2
+norm of the propagator's gradients (torch.nn.utils.clip_grad_norm_'s formula) inside the same enqueue, an
+`lns_amd.optim.AdamW` makes the weight decay decoupled, `skip_nonfinite` leaves parameters and Adam state alone when the
+norm is inf / NaN.  Any of the three routes the step through lns_train_step_clip; without them the step is what it was.
+  * `.grad` then holds the CLIPPED gradients, as after clip_grad_norm_; `trainer.grad_norm` is the norm before clipping of
+    the last such step (a 0-dim view into a ring like the loss's), `trainer.skipped_steps` the device count of skipped steps;
+  * the optimiser's `step` counts advance on a skipped step too (they live on the host, which does not look): the bias
+    corrections move on, as they do under torch.amp's GradScaler only when it is told to -- documented, not hidden;
+  * `step(update=False)` is the plain call: unclipped gradients, no norm.
 """
 import ctypes
 
@@ -36,7 +46,7 @@ WGRAD_FORMS = {"tile": 0, "split": 1}
 
 class Stage2Trainer:
     def __init__(self, model, optimizer=None, lr=1e-3, beta=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 loss_ring=LOSS_RING, wgrad=None):
+                 loss_ring=LOSS_RING, wgrad=None, max_grad_norm=None, skip_nonfinite=False):
         if not isinstance(model, _dropin.LatentDynamics):
             raise LnsError("Stage2Trainer needs a LatentDynamics drop-in (lns_amd.dropin), got %s" % type(model).__name__)
         if not beta > 0:
@@ -51,8 +61,14 @@ class Stage2Trainer:
             raise LnsError("Stage2Trainer runs Adam on the device: pass an lns_amd.optim.Adam over the propagator's parameters "
                            "(a torch.optim.Adam state_dict loads into it), got %s" % type(optimizer).__name__)
         self.optimizer = optimizer
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise LnsError("max_grad_norm must be > 0 (None: no clipping), got %r" % (max_grad_norm,))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._norm = None              # ring of norms, parallel to the loss ring (clipped path only)
+        self._norm_last = None
         self._key = None               # what the resolved pointers were taken from
-        self._ws = {}                  # (device, B, T, h, w, bytes the engine asks for under its current options) -> workspace
+        self._ws = {}                  # (device, B, T, h, w, bytes the engine asks for under its current options, clipped) -> workspace
         if wgrad is not None:          # None: the engine's option stays as it is
             self.set_wgrad(wgrad)
         self._loss = None
@@ -142,23 +158,45 @@ class Stage2Trainer:
             raise LnsError("wgrad must be None, 'tile' or 'split', got %r" % (wgrad,))
         self._eng.set_option("train_wgrad", WGRAD_FORMS[wgrad])
 
-    def _workspace(self, B, T, h, w):
+    def _workspace(self, B, T, h, w, clip=False):
         # the size follows the engine's options ("train_wgrad"), however they were set: the library is asked (host-only) and
         # a workspace is only ever handed to the C call at the size it was allocated for
-        need = self._eng.train_step_workspace_bytes(B, h, w, T)
-        key = (self._device, B, T, h, w, need)
+        need = (self._eng.train_step_clip_workspace_bytes if clip else self._eng.train_step_workspace_bytes)(B, h, w, T)
+        key = (self._device, B, T, h, w, need, clip)
         ws = self._ws.get(key)
         if ws is None:
             with torch.cuda.device(self._device):
                 ws = torch.empty(need, dtype=torch.uint8, device=self._device)
+                if clip:
+                    ws[-256:].zero_()          # the counter of skipped steps (include/lns.h: 256 bytes before the end)
             self._ws[key] = ws
         return ws
+
+    @property
+    def clipped(self):
+        """Whether `step` goes through lns_train_step_clip (max_grad_norm, skip_nonfinite or an AdamW optimiser)."""
+        return self.max_grad_norm is not None or self.skip_nonfinite or isinstance(self.optimizer, _optim.AdamW)
+
+    @property
+    def grad_norm(self):
+        """Global L2 norm of the gradients before clipping, of the last clipped step: 0-dim view into a ring of `loss_ring`
+        device floats (None before the first such step)."""
+        return self._norm_last
+
+    @property
+    def skipped_steps(self):
+        """Steps `skip_nonfinite` left out, as a 0-dim int32 device tensor (reading it synchronises; the step never does).
+        One workspace (one batch shape): a view of its counter; several: their sum."""
+        cs = [ws[-256:-252].view(torch.int32)[0] for key, ws in self._ws.items() if key[-1]]
+        if not cs:
+            return torch.zeros((), dtype=torch.int32, device=getattr(self, "_device", None))
+        return cs[0] if len(cs) == 1 else torch.stack(cs).sum().to(torch.int32)
 
     # -- the step ------------------------------------------------------------------------------------------------------
     def step(self, z_in, z_out, param=None, update=True):
         """z_in [B,1,c,h,w], z_out [B,T,c,h,w] (fp32, on the parameters' device), param [B] for the conditional model.
         Returns the loss before the update as a 0-dim device tensor; never synchronises.  update=False: loss and
-        gradients only (`.grad` is filled, parameters and Adam state stay)."""
+        gradients only (`.grad` is filled, unclipped; parameters and Adam state stay)."""
         self._current()
         if self.model._conditional != (param is not None):
             raise LnsError("param must be given exactly for the conditional model")
@@ -169,18 +207,31 @@ class Stage2Trainer:
         B, _, _, h, w = z_in.shape
         T = int(z_out.shape[1])
         spec = None
+        clip = update and self.clipped
         if update:
             t = {_optim._step_of(st) for st in self._states}
             if len(t) != 1:
                 raise LnsError("Stage2Trainer: the propagator's parameters have different Adam step counts %s" % sorted(t))
             g = self.optimizer.param_groups[0]
-            spec = _engine.adam_spec(g["lr"], g["betas"], g["eps"], g["weight_decay"], t.pop() + 1)
+            if clip:
+                spec = _engine.update_spec(g["lr"], g["betas"], g["eps"], g["weight_decay"], t.pop() + 1, max_norm=self.max_grad_norm,
+                                           decoupled=isinstance(self.optimizer, _optim.AdamW), skip_nonfinite=self.skip_nonfinite)
+            else:
+                spec = _engine.adam_spec(g["lr"], g["betas"], g["eps"], g["weight_decay"], t.pop() + 1)
         loss = self._loss[self._loss_i]
+        if clip:
+            if self._norm is None or self._norm.device != self._device:
+                self._norm = torch.zeros(self._loss_ring, dtype=torch.float32, device=self._device)
+            self._norm_last = self._norm[self._loss_i]
         self._loss_i = (self._loss_i + 1) % self._loss_ring
         a = self._arrs
         with torch.no_grad():
-            self._eng.train_step(a[0], z_in, z_out, a[1], param=param, beta=self.beta, exp_avg=a[2], exp_avg_sq=a[3], spec=spec,
-                                 loss_out=loss, workspace=self._workspace(int(B), T, int(h), int(w)))
+            if clip:
+                self._eng.train_step_clip(a[0], z_in, z_out, a[1], a[2], a[3], spec, param=param, beta=self.beta, loss_out=loss,
+                                          norm_out=self._norm_last, workspace=self._workspace(int(B), T, int(h), int(w), clip=True))
+            else:
+                self._eng.train_step(a[0], z_in, z_out, a[1], param=param, beta=self.beta, exp_avg=a[2], exp_avg_sq=a[3], spec=spec,
+                                     loss_out=loss, workspace=self._workspace(int(B), T, int(h), int(w)))
             if update:
                 torch._foreach_add_(self._steps, 1.0)
                 # the kernel wrote the parameters through raw pointers: bump their versions, which is what

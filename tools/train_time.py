@@ -1,13 +1,18 @@
-"""Stage-2 training step, four ways, on one box and in one process (synthetic latents, B = 32):
+"""Stage-2 training step, four ways (six with --clip), on one box and in one process (synthetic latents, B = 32):
   (a) autograd      : model(z_in, z_out[, param], F.smooth_l1_loss); loss.backward(); torch.optim.Adam.step()
   (b) lns Adam      : the same with lns_amd.optim.Adam (one-launch multi-tensor kernel)
   (c) trainer       : lns_amd.train.Stage2Trainer.step (lns_train_step: forward, loss, backward and Adam in one C call)
   (d) trainer_split : the same with wgrad="split" (engine option "train_wgrad" = 1: the batch-parallel weight gradient)
+  (e) trainer_clip  : --clip only: Stage2Trainer(max_grad_norm=1.0) (lns_train_step_clip: + norm and clipped update), in the
+                      weight-gradient form --clip-wgrad names (default split); its yardstick is (c) / (d) of the same form
+  (f) unfused_clip  : --clip only: what a user wrote before: step(update=False); torch.nn.utils.clip_grad_norm_(params, 1.0);
+                      lns_amd.optim.Adam.step(), same form
 for the reference's shipped training shapes: ns2d_64 (T = 2), sw_half_periodic (T = 5), twophase_cond (T = 5), and
 ns2d_128 (T = 2).  Warm-up, then blocks of 10 steps with one synchronisation before and after each block, the arms
 interleaved block by block; per arm the median block time, its min / max, steps/s and trajectory-steps/s (B * T / time).
 
     python tools/train_time.py [--blocks 5] [--block 10] [--warmup 5] [--out profiles/train_step_time_wgrad.json]
+    python tools/train_time.py --clip --out profiles/train_step_time_clip.json
     python tools/train_time.py --only-trainer --preset ns2d_64 --blocks 3      # the runs to put under rocprofv3 --kernel-trace --stats,
     python tools/train_time.py --only-trainer-split --preset ns2d_64 --blocks 3  # one per arm
     python tools/train_time.py --merge-stats ns2d_64:25=out/..._kernel_stats.csv trainer_split/ns2d_64:25=... --out profiles/train_step_time_wgrad.json
@@ -49,7 +54,7 @@ def build(preset, dev):
     return args, model
 
 
-def arms_for(preset, T, dev, only=None):
+def arms_for(preset, T, dev, only=None, clip_wgrad=None):
     args, probe = build(preset, dev)
     c, h, w = probe._eng.latent_shape()
     del probe
@@ -73,8 +78,26 @@ def arms_for(preset, T, dev, only=None):
         _, model = build(preset, dev)            # (its own model, hence its own engine: the option is per engine)
         tr = train.Stage2Trainer(model, lr=LR, wgrad=wgrad)
         return lambda: tr.step(z_in, z_out, *prm)
+    def clip_arm():
+        _, model = build(preset, dev)
+        tr = train.Stage2Trainer(model, lr=LR, wgrad=clip_wgrad, max_grad_norm=1.0)
+        return lambda: tr.step(z_in, z_out, *prm)
+
+    def unfused_clip_arm():
+        _, model = build(preset, dev)
+        tr = train.Stage2Trainer(model, lr=LR, wgrad=clip_wgrad)
+        params = list(model.propagator.parameters())
+
+        def step():
+            loss = tr.step(z_in, z_out, *prm, update=False)
+            torch.nn.utils.clip_grad_norm_(params, 1.0)
+            tr.optimizer.step()
+            return loss
+        return step
     makers = {"autograd": lambda: autograd_arm(torch.optim.Adam), "lns_adam": lambda: autograd_arm(optim.Adam),
               "trainer": lambda: trainer_arm("tile"), "trainer_split": lambda: trainer_arm("split")}
+    if clip_wgrad:
+        makers.update(trainer_clip=clip_arm, unfused_clip=unfused_clip_arm)
     return {k: mk() for k, mk in makers.items() if only is None or k in only}, (c, h, w)
 
 
@@ -90,7 +113,7 @@ def block_ms(step, n):
 
 def measure(preset, T, a, dev):
     only = ("trainer",) if a.only_trainer else ("trainer_split",) if a.only_trainer_split else None
-    arms, latent = arms_for(preset, T, dev, only)
+    arms, latent = arms_for(preset, T, dev, only, a.clip_wgrad if a.clip else None)
     for step in arms.values():
         for _ in range(a.warmup):
             step()
@@ -118,6 +141,18 @@ def measure(preset, T, a, dev):
         rec["speedup_split_over_trainer"] = round(tile["step_ms_median"] / split["step_ms_median"], 4)
         rec["trainer_spread_max_over_min"] = round(tile["step_ms_max"] / tile["step_ms_min"], 4)
         rec["split_median_below_trainer_min"] = bool(split["step_ms_median"] < tile["step_ms_min"])
+    if "trainer_clip" in rec:
+        # the yardstick of the clipped arm is the unclipped trainer of the same form in the same run; a cost only counts when
+        # the clipped arm's median lies outside that arm's block spread
+        yard_name = "trainer_split" if a.clip_wgrad == "split" else "trainer"
+        yard, clip, unf = rec[yard_name], rec["trainer_clip"], rec["unfused_clip"]
+        rec["clip_wgrad"] = a.clip_wgrad
+        rec["clip_yardstick_arm"] = yard_name
+        rec["clip_median_within_yardstick_spread"] = bool(yard["step_ms_min"] <= clip["step_ms_median"] <= yard["step_ms_max"])
+        rec["clip_over_yardstick"] = round(clip["step_ms_median"] / yard["step_ms_median"], 4)
+        rec["yardstick_spread_max_over_min"] = round(yard["step_ms_max"] / yard["step_ms_min"], 4)
+        rec["speedup_clip_over_unfused"] = round(unf["step_ms_median"] / clip["step_ms_median"], 4)
+        rec["clip_median_below_unfused_min"] = bool(clip["step_ms_median"] < unf["step_ms_min"])
     return rec
 
 
@@ -159,6 +194,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only-trainer", action="store_true")
     ap.add_argument("--only-trainer-split", action="store_true")
+    ap.add_argument("--clip", action="store_true", help="add the clipped trainer and the unfused clip sequence (arms e, f)")
+    ap.add_argument("--clip-wgrad", choices=("tile", "split"), default="split")
     ap.add_argument("--out", default=None)
     ap.add_argument("--merge-stats", nargs="*", default=None, metavar="PRESET:STEPS=CSV")
     a = ap.parse_args()
