@@ -438,7 +438,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
 /* Build-time features of this library: "experimental" = compiled with -DLNS_EXPERIMENTAL (the measured-slower kernel
  * forms behind op-level variants 15 / 16 / 18 / 19 exist; the shipped library does not carry them); "train_wgrad_split" = the
  * batch-parallel weight gradient (option "train_wgrad", lns_op_conv_wgrad) is there; "train_clip" = lns_train_step_clip and
- * the gradient-norm / update calls are there.  1 / 0; -1: unknown name.
+ * the gradient-norm / update calls are there; "train_ops" = lns_op_groupnorm_train, lns_op_gelu_grad and lns_op_bias_grad
+ * are there.  1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
 
@@ -479,6 +480,25 @@ int lns_op_conv_wgrad_scratch_bytes(int B, int Cin, int Cout, int H, int W, int 
 int lns_op_conv_wgrad(const float* dy, const float* x, int B, int Cin, int Cout, int H, int W, int ksize, int dilation,
                       int pad_y, int pad_x, int form, int accumulate, float* dw, void* scratch, size_t scratch_bytes,
                       void* stream);
+
+/* The elementwise and reduction kernels of the training rollout's backward pass on their own (unit tests of their input
+ * domain): the launchers lns_train_forward / lns_train_backward use, nothing added.  All pointers DEVICE fp32; argument
+ * checks precede the first launch (LNS_EINVAL; message: lns_create_error()); each call synchronises `stream`.
+ *
+ * Training-form GroupNorm (nn.GroupNorm, biased variance, two-pass statistics).  Forward, always:
+ *   y [B,C,HW] = (x - mean) rstd gamma + beta,  stats [B,groups,2] = (mean, rstd) per (sample, group).
+ * Backward, when dy [B,C,HW] is given, from the stats just written:
+ *   dx [B,C,HW] = (add ? add : 0) + rstd (gamma dy - mean_g(gamma dy) - xhat mean_g(gamma dy xhat))
+ *   dgamma[c] (+)= sum_b sum_p dy xhat,  dbeta[c] (+)= sum_b sum_p dy      (accumulate 1: added to what dgamma / dbeta hold)
+ * through the per-sample partials `part` [B,C,2] (scratch) and their reduction over the batch in ascending order.
+ * add: the gradient arriving over a skip connection, or NULL.  dy NULL: forward only (dx .. part are not read). */
+int lns_op_groupnorm_train(const float* x, int B, int C, int HW, int groups, float eps, const float* gamma, const float* beta,
+                           float* y, float* stats, const float* dy, const float* add, float* dx, float* dgamma, float* dbeta,
+                           int accumulate, float* part, void* stream);
+/* du[i] = dy[i] * d/du GELU(u[i]), exact-erf GELU (nn.GELU default): Phi(u) + u phi(u).  1 <= n <= 2^40. */
+int lns_op_gelu_grad(const float* dy, const float* u, float* du, int64_t n, void* stream);
+/* db[c] (+)= sum_b sum_p dy[b][c][p], dy [B,C,HW]; one fixed summation order: bit-reproducible. */
+int lns_op_bias_grad(const float* dy, int B, int C, int HW, float* db, int accumulate, void* stream);
 
 /* GroupNorm statistics -> per-(b,c) (scale,shift) such that norm(x) = x*scale+shift. */
 int lns_op_groupnorm_stats(const float* x, int B, int C, int HW, int groups, float eps,

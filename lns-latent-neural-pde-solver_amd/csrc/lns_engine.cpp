@@ -2572,6 +2572,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "experimental")) return build_has_experimental() ? 1 : 0;
     if (!strcmp(feature, "train_wgrad_split")) return 1;
     if (!strcmp(feature, "train_clip")) return 1;
+    if (!strcmp(feature, "train_ops")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else

@@ -1028,3 +1028,52 @@ int lns_op_conv_wgrad(const float* dy, const float* x, int B, int Cin, int Cout,
     OPCHK(he);
     return LNS_OK;
 }
+
+// ---- elementwise / reduction kernels of the backward pass on their own (csrc/lns_train_kernels.hip): the launchers the
+// training rollout calls, nothing else.  Every check precedes the first HIP call; each call synchronises `stream`. ----
+int lns_op_groupnorm_train(const float* x, int B, int C, int HW, int groups, float eps, const float* gamma, const float* beta,
+                           float* y, float* stats, const float* dy, const float* add, float* dx, float* dgamma, float* dbeta,
+                           int accumulate, float* part, void* stream) {
+    if (!x || !gamma || !beta || !y || !stats) { g_create_error = "groupnorm_train: x / gamma / beta / y / stats is null"; return LNS_EINVAL; }
+    if (B < 1 || B > LNS_MAX_BATCH || C < 1 || C > 65536 || HW < 1 || HW > 4096 * 4096 || groups < 1 || groups > C || C % groups != 0) {
+        g_create_error = "groupnorm_train: B in 1..65535, C in 1..65536, HW in 1..4096*4096, groups a divisor of C"; return LNS_EINVAL;
+    }
+    if (!(eps > 0.0f) || !std::isfinite(eps)) { g_create_error = "groupnorm_train: eps must be positive and finite"; return LNS_EINVAL; }
+    if (dy && (!dx || !dgamma || !dbeta || !part)) { g_create_error = "groupnorm_train: the backward (dy given) needs dx, dgamma, dbeta and part"; return LNS_EINVAL; }
+    if (!dy && add) { g_create_error = "groupnorm_train: add belongs to the backward (dy is null)"; return LNS_EINVAL; }
+    if (accumulate != 0 && accumulate != 1) { g_create_error = "groupnorm_train: accumulate must be 0 or 1"; return LNS_EINVAL; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GnTrainArgs a;
+    memset(&a, 0, sizeof a);
+    a.x = x; a.y = y; a.stats = stats; a.gamma = gamma; a.beta = beta;
+    a.B = B; a.C = C; a.HW = HW; a.groups = groups; a.eps = eps;
+    OPCHK(launch_gn_train_fwd(a, s));
+    if (dy) {
+        a.dy = dy; a.dx = dx; a.add = add; a.part = part;
+        OPCHK(launch_gn_train_bwd(a, s));
+        OPCHK(launch_colsum2(part, B, C, dgamma, dbeta, accumulate, s));
+    }
+    OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+int lns_op_gelu_grad(const float* dy, const float* u, float* du, int64_t n, void* stream) {
+    if (!dy || !u || !du) { g_create_error = "gelu_grad: dy / u / du is null"; return LNS_EINVAL; }
+    if (n < 1 || n > ((int64_t)1 << 40)) { g_create_error = "gelu_grad: n in 1..2^40"; return LNS_EINVAL; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    OPCHK(launch_gelu_bwd(dy, u, du, (long)n, s));
+    OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+int lns_op_bias_grad(const float* dy, int B, int C, int HW, float* db, int accumulate, void* stream) {
+    if (!dy || !db) { g_create_error = "bias_grad: dy / db is null"; return LNS_EINVAL; }
+    if (B < 1 || B > LNS_MAX_BATCH || C < 1 || C > 65536 || HW < 1 || HW > 4096 * 4096) {
+        g_create_error = "bias_grad: B in 1..65535, C in 1..65536, HW in 1..4096*4096"; return LNS_EINVAL;
+    }
+    if (accumulate != 0 && accumulate != 1) { g_create_error = "bias_grad: accumulate must be 0 or 1"; return LNS_EINVAL; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    OPCHK(launch_bias_grad(dy, B, C, HW, db, accumulate, s));
+    OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}

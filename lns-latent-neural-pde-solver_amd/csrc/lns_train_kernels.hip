@@ -70,7 +70,7 @@ hipError_t launch_pack_conv_w(const float* w, float* dst, int Cout, int Cin, int
 
 // ---------------------------------------------------------------------------------------------------------------------
 // GroupNorm forward, training form: y = (x - mean) rstd gamma + beta and (mean, rstd) per (sample, group).
-// One block per (group, sample); two-pass statistics (biased variance), reference: nn.GroupNorm.
+// One block per (group, sample); corrected two-pass statistics (biased variance), reference: nn.GroupNorm.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gn_train_fwd_kernel(GnTrainArgs a) {
     __shared__ float red[4];
@@ -81,9 +81,13 @@ __global__ __launch_bounds__(256) void gn_train_fwd_kernel(GnTrainArgs a) {
     float s = 0.0f;
     for (long i = threadIdx.x; i < n; i += 256) s += x[i];
     const float mean = t_block_sum(s, red) / (float)n;
-    float q = 0.0f;
-    for (long i = threadIdx.x; i < n; i += 256) { const float d = x[i] - mean; q += d * d; }
-    const float var = t_block_sum(q, red) / (float)n;
+    // corrected two-pass variance: `mean` is the float32 rounding of the group's mean, off by up to half an ulp; with a mean
+    // of 1e3 over a spread of 1e-2 that offset squared is 1e-5 of the variance.  sum(d)^2 / n takes it out again.
+    float q = 0.0f, sd = 0.0f;
+    for (long i = threadIdx.x; i < n; i += 256) { const float d = x[i] - mean; q += d * d; sd += d; }
+    const float qs = t_block_sum(q, red);
+    const float ds = t_block_sum(sd, red);
+    const float var = fmaxf(qs - ds * (ds / (float)n), 0.0f) / (float)n;
     const float rstd = 1.0f / sqrtf(var + a.eps);
     if (threadIdx.x == 0) { a.stats[((long)b * a.groups + g) * 2] = mean; a.stats[((long)b * a.groups + g) * 2 + 1] = rstd; }
     float* y = a.y + base;
@@ -99,7 +103,11 @@ hipError_t launch_gn_train_fwd(const GnTrainArgs& a, hipStream_t s) {
 
 // GroupNorm backward.  dx = rstd (g dy - mean_g(g dy) - xhat mean_g(g dy xhat)) [+ add]; per-sample partials of
 // dgamma[c] = sum dy xhat, dbeta[c] = sum dy go to part [B][C][2] (reduced over the batch by colsum2_kernel).
+// g dy is a ROUNDED product in both loops (fp contract off: no fusing into the sum or into g dy - mean): the mean that is
+// subtracted is then the mean of the very values it is subtracted from, and where a group holds a single value (HW = 1, one
+// channel per group) g dy - mean_g(g dy) is exactly 0 instead of rstd times the product's rounding residue.
 __global__ __launch_bounds__(256) void gn_train_bwd_kernel(GnTrainArgs a) {
+#pragma clang fp contract(off)
     __shared__ float red[4];
     const int g = blockIdx.x, b = blockIdx.y, cg = a.C / a.groups;
     const long n = (long)cg * a.HW;
