@@ -198,6 +198,32 @@ int lns_rollout(lns_engine* e, const float* x, const float* param, int B, int T,
 int lns_rollout_latent(lns_engine* e, const float* z_in, const float* param, int B, int T, int to_x,
                        float* out, float* z_last, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- selected-step rollout: decode only the steps the caller keeps ---------------------------------------------
+ * lns_rollout(..., to_x = 1) for a caller that looks at a few of the T steps (the reference's validation loop plots
+ * y_hat[:10, ::5, 0], train_stage2_ns2d.py:259-263): the latent chain runs all T steps, the decoder runs for the kept
+ * steps only.  keep_steps_host: n_keep >= 1 strictly ascending 0-based steps in [0, T) (HOST array, read during the
+ * call).  out is [B,n_keep,Cin,Ly,Lx] and out[:, i] holds the bits lns_rollout writes to out[:, keep_steps[i]], whatever
+ * the scheduling options: a decode group is the next up to "decode_group" KEPT steps, decoded by the launch set of the
+ * full rollout at batch B * (steps in the group).  latents_out (nullable) is the full [B,T,latent_dim,h,w]: every latent
+ * is computed anyway.  Decoded fields only (no to_x): for latents, slice lns_rollout(..., to_x = 0).
+ * param, batch limits, trace / timing modes (single stream) and lns_check_finite: as for lns_rollout.
+ * LNS_EINVAL (bad argument, named by lns_last_error; decided before any device work), LNS_ENOMEM (workspace smaller
+ * than lns_rollout_select_workspace_bytes; nothing is enqueued), LNS_ESTATE (no autoencoder / propagator).
+ *
+ * Workspace for batch B: the lns_prepare(B) layout, byte for byte (lns_prepare and the sizes the other run calls need
+ * do not change), rounded up to 256 bytes, followed by two latent buffers of B * latent_dim * h * w floats, each rounded
+ * up to 256 bytes: the chain writes the latent of a skipped step into them alternately (it cannot write a step into
+ * the buffer it reads), the latent of a kept step into the ring of the rollout layout. */
+int lns_rollout_select_workspace_bytes(lns_engine* e, int B, size_t* bytes);
+int lns_rollout_select(lns_engine* e, const float* x, const float* param, int B, int T,
+                       const int* keep_steps_host, int n_keep, float* out, float* latents_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* The same from a latent state (lns_rollout_latent; chunked rollouts): keep_steps_host are steps of THIS chunk,
+ * 0 .. T-1; z_last (nullable) receives the latent after step T. */
+int lns_rollout_latent_select(lns_engine* e, const float* z_in, const float* param, int B, int T,
+                              const int* keep_steps_host, int n_keep, float* out, float* z_last,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- streaming validation rollout: predict and score without the [B,T] field ---------------------------------
  * Reference: the body of the validation loop, train_stage2_ns2d.py:249-263 (same text in train_stage2_SW.py and
  * train_stage2_twophase*.py, where denormalize is the per-channel / closed-wall / clamp form):
@@ -439,7 +465,7 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * forms behind op-level variants 15 / 16 / 18 / 19 exist; the shipped library does not carry them); "train_wgrad_split" = the
  * batch-parallel weight gradient (option "train_wgrad", lns_op_conv_wgrad) is there; "train_clip" = lns_train_step_clip and
  * the gradient-norm / update calls are there; "train_ops" = lns_op_groupnorm_train, lns_op_gelu_grad and lns_op_bias_grad
- * are there.  1 / 0; -1: unknown name.
+ * are there; "rollout_select" = lns_rollout_select & co. are there.  1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
 

@@ -1885,6 +1885,18 @@ struct EvalRun {
     const int* keep; int n_keep; float* frames_out;
 };
 
+// Selected-step rollout (lns_rollout_select): the rollout layout above, untouched, then two latent buffers [B][zper]
+// that take the latents of the steps nobody decodes.
+struct SelectLayout { size_t pp_off[2], total; };
+static void select_layout(const WsLayout& L, SelectLayout* S) {
+    S->pp_off[0] = round_up_sz(L.total, 256);
+    S->pp_off[1] = S->pp_off[0] + L.z_bytes;                          // (z_bytes is a multiple of 256)
+    S->total = S->pp_off[1] + L.z_bytes;
+}
+
+// which steps rollout_loop decodes (null: all of them); out is then [B][n_keep] instead of [B][T]
+struct SelectRun { const int* keep; int n_keep; char* pp[2]; };
+
 // second stream + events for the propagate / decode overlap (created once, owned by the engine)
 static int ensure_overlap_objects(lns_engine* e) {
     if (e->side_stream) return LNS_OK;
@@ -2187,8 +2199,10 @@ int lns_propagate(lns_engine* e, const float* z_in, const float* param, int B, i
 // Evaluation mode (ev != null; to_x): the decode of a group writes that decode stream's frame buffer instead of `out`,
 // the scoring kernel and the copies of the kept steps follow on the same decode stream -- in stream order before the
 // next decode that reuses the buffer, so the event scheme is the rollout's own.
+// Selection (sel != null; to_x, no ev): the chain still runs all T steps, the decoder runs for sel->keep only.
 static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param, int B, int T, int to_x, float* out,
-                        float* latents_out, float* z_last, const WsLayout& L, char* base, const EvalRun* ev = nullptr) {
+                        float* latents_out, float* z_last, const WsLayout& L, char* base, const EvalRun* ev = nullptr,
+                        const SelectRun* sel = nullptr) {
     Plan* pp;
     int rc;
     if ((rc = get_plan(e, PK_PROP, B, e->lat_H, e->lat_W, &pp))) return rc;
@@ -2246,25 +2260,44 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
     }
     char* ring = base + L.ring_off;
     std::vector<char> used(ngroup, 0);
-    int g = 0, gi = 0, ki = 0;                       // ki: next entry of ev->keep
-    for (int t = 0; t < T;) {
-        const int kk = std::min(kdec, T - t);
+    // A decode group is the next up to kdec DECODED steps: all steps, or the kept ones (sel).  The chain writes the
+    // latent of a decoded step into the group's next ring slot and the latent of a skipped step into the two
+    // ping-pong buffers in turn, so a step never writes the buffer it reads.
+    const int n_dec = sel ? sel->n_keep : T;         // decoded steps; `out` is [B][n_dec]
+    auto dec_step = [&](int i) { return sel ? sel->keep[i] : i; };
+    int npp = 0;                                     // the ping-pong buffer the next skipped step writes
+    auto chain_step = [&](int t, const ExtT& znext) -> int {   // strictly sequential in t, independent in b
+        ext[EX_IN] = zcur;
+        ext[EX_OUT] = znext;
+        rp.skip_step_invariant = t > 0 && !e->trace_on;
+        const int src = rp.run(*pp, ext, parena);
+        rp.skip_step_invariant = false;
+        if (src) return src;
+        if (latents_out)
+            HIPCHK(e, hipMemcpy2DAsync(latents_out + (long)t * zper, (size_t)T * zper * 4, znext.ptr, (size_t)zper * 4,
+                                       (size_t)zper * 4, B, hipMemcpyDeviceToDevice, pstream));
+        zcur = znext;
+        return LNS_OK;
+    };
+    auto skipped_step = [&](int t) -> int {
+        const ExtT znext = {sel->pp[npp], zper};
+        npp ^= 1;
+        return chain_step(t, znext);
+    };
+    int g = 0, gi = 0, ki = 0, t = 0;                // ki: next entry of ev->keep; t: next step of the chain
+    for (int i0 = 0; i0 < n_dec;) {                  // i0: index in `out` of the group's first step
+        const int kk = std::min(kdec, n_dec - i0);
+        const int t0g = dec_step(i0);                // the group's first step
         char* gbase = ring + (size_t)g * L.group_bytes;
-        if (overlap && used[g]) HIPCHK(e, hipStreamWaitEvent(pstream, ev_free[g], 0));   // WAR: the decode of the group that lived here
-        for (int j = 0; j < kk; ++j) {               // strictly sequential in t, independent in b
-            ExtT znext = {gbase + (size_t)j * B * zper * 4, zper};
-            ext[EX_IN] = zcur;
-            ext[EX_OUT] = znext;
-            rp.skip_step_invariant = (t + j) > 0 && !e->trace_on;
-            rc = rp.run(*pp, ext, parena);
-            rp.skip_step_invariant = false;
-            if (rc) return rc;
-            if (latents_out)
-                HIPCHK(e, hipMemcpy2DAsync(latents_out + (long)(t + j) * zper, (size_t)T * zper * 4, znext.ptr, (size_t)zper * 4,
-                                           (size_t)zper * 4, B, hipMemcpyDeviceToDevice, pstream));
-            zcur = znext;
+        // WAR: the decode of the group that lived here (under selection it may have been filled many chain steps ago)
+        if (overlap && used[g]) HIPCHK(e, hipStreamWaitEvent(pstream, ev_free[g], 0));
+        for (int j = 0; j < kk; ++t) {
+            if (t != dec_step(i0 + j)) { if ((rc = skipped_step(t))) return rc; continue; }
+            const ExtT znext = {gbase + (size_t)j * B * zper * 4, zper};
+            if ((rc = chain_step(t, znext))) return rc;
+            ++j;
         }
-        // decode the group: launch sample s = j * B + b reads latent [j][b] and writes out[b][t + j]
+        // decode the group: launch sample s = j * B + b reads latent [j][b] and writes out[b][i0 + j]
         Plan* pd;
         if ((rc = get_plan(e, PK_DEC, B * kk, 0, 0, &pd))) return rc;
         const int d = gi % ndec;
@@ -2275,22 +2308,24 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
         ext[EX_IN] = {gbase, zper};
         float* fb = ev ? reinterpret_cast<float*>(ev->fbuf + (size_t)d * ev->fbuf_stride) : nullptr;
         if (ev) ext[EX_OUT] = {fb, xper};            // [kk][B][xper]: launch sample s = j * B + b
-        else ext[EX_OUT] = {out + (long)t * xper, (long)T * xper, xper, B};
+        else ext[EX_OUT] = {out + (long)i0 * xper, (long)n_dec * xper, xper, B};
         if ((rc = (overlap ? rd[d] : r).run(*pd, ext, darena[d]))) return rc;
-        if (ev) {
+        if (ev) {                                    // (evaluation decodes every step: t0g == i0)
             MetricGroupArgs m = ev->m;
-            m.frames = fb; m.kk = kk; m.y_t = ev->t0 + t; m.p_t = ev->t0 + t;
+            m.frames = fb; m.kk = kk; m.y_t = ev->t0 + t0g; m.p_t = ev->t0 + t0g;
             HIPCHK(e, launch_metric_group(m, dstream[d]));
-            for (; ki < ev->n_keep && ev->keep[ki] < t + kk; ++ki)       // ascending: each kept step lies in one group
+            for (; ki < ev->n_keep && ev->keep[ki] < t0g + kk; ++ki)     // ascending: each kept step lies in one group
                 HIPCHK(e, hipMemcpy2DAsync(ev->frames_out + (long)ki * xper, (size_t)ev->n_keep * xper * 4,
-                                           fb + (long)(ev->keep[ki] - t) * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
+                                           fb + (long)(ev->keep[ki] - t0g) * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
                                            hipMemcpyDeviceToDevice, dstream[d]));
         }
         if (overlap) { HIPCHK(e, hipEventRecord(ev_free[g], dstream[d])); used[g] = 1; }
-        t += kk;
+        i0 += kk;
         g = (g + 1) % ngroup;
         ++gi;
     }
+    for (; t < T; ++t)                               // skipped steps behind the last decoded one: latents_out / z_last
+        if ((rc = skipped_step(t))) return rc;
     if (z_last)   // the last latent is complete once the propagator stream has passed its step
         HIPCHK(e, hipMemcpy2DAsync(z_last, (size_t)zper * 4, zcur.ptr, (size_t)zcur.bs * 4, (size_t)zper * 4, B,
                                    hipMemcpyDeviceToDevice, pstream));
@@ -2353,6 +2388,16 @@ int lns_rollout_latent(lns_engine* e, const float* z_in, const float* param, int
 // ---- streaming validation rollout (include/lns.h) --------------------------------------------------------------
 static int einval(lns_engine* e, const char* what) { e->err = what; return LNS_EINVAL; }
 
+// kept steps (evaluation: frames to copy out; selection: steps to decode): strictly ascending, in [0, T)
+static int check_keep_steps(lns_engine* e, const int* keep, int n_keep, int T) {
+    for (int i = 0; i < n_keep; ++i)
+        if (keep[i] < 0 || keep[i] >= T || (i > 0 && keep[i] <= keep[i - 1])) {
+            e->err = fmt("keep_steps must be ascending steps in [0, %d): entry %d is %d", T, i, keep[i]);
+            return LNS_EINVAL;
+        }
+    return LNS_OK;
+}
+
 // argument checks shared by the two evaluation calls; nothing here touches the device
 static int eval_check_args(lns_engine* e, const void* first, const char* first_name, const float* y_true, int B, int T, int t0,
                            int T_total, const lns_eval_spec* spec, const float* frame_out, const float* seq_out,
@@ -2369,11 +2414,7 @@ static int eval_check_args(lns_engine* e, const void* first, const char* first_n
     if (n_keep > 0) {
         if (!keep) return einval(e, "keep_steps is null but n_keep > 0");
         if (!frames_out) return einval(e, "frames_out is null but n_keep > 0");
-        for (int i = 0; i < n_keep; ++i)
-            if (keep[i] < 0 || keep[i] >= T || (i > 0 && keep[i] <= keep[i - 1])) {
-                e->err = fmt("keep_steps must be ascending steps in [0, %d): entry %d is %d", T, i, keep[i]);
-                return LNS_EINVAL;
-            }
+        if (int krc = check_keep_steps(e, keep, n_keep, T)) return krc;
     }
     if (int brc = check_batch(e, B)) return brc;
     if (T_total > e->opt_eval_max_steps) {
@@ -2482,6 +2523,91 @@ int lns_rollout_latent_eval(lns_engine* e, const float* z_in, const float* param
     return r.finish();
 }
 
+// ---- selected-step rollout (include/lns.h) ----------------------------------------------------------------------
+// argument checks shared by the two selection calls; nothing here touches the device
+static int select_check_args(lns_engine* e, const void* first, const char* first_name, const float* out, int B, int T,
+                             const int* keep, int n_keep) {
+    if (!first) { e->err = fmt("%s is null", first_name); return LNS_EINVAL; }
+    if (!out) return einval(e, "out is null");
+    if (B <= 0) return einval(e, "B must be positive");
+    if (T <= 0) return einval(e, "T must be positive");
+    if (n_keep < 1) return einval(e, "n_keep must be at least 1 (for no decoded step: lns_rollout with to_x = 0)");
+    if (!keep) return einval(e, "keep_steps is null");
+    if (int krc = check_keep_steps(e, keep, n_keep, T)) return krc;
+    return check_batch(e, B);
+}
+
+int lns_rollout_select_workspace_bytes(lns_engine* e, int B, size_t* bytes) {
+    if (!e) return LNS_EINVAL;
+    if (B <= 0) return einval(e, "B must be positive");
+    if (int brc = check_batch(e, B)) return brc;
+    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
+    DeviceGuard dg(e);
+    WsLayout L; SelectLayout S;
+    if (int rc = ws_layout(e, B, &L)) return rc;
+    select_layout(L, &S);
+    if (bytes) *bytes = S.total;
+    return LNS_OK;
+}
+
+static int check_select_ws(lns_engine* e, const SelectLayout& S, void* ws, size_t bytes) {
+    if (!ws || bytes < S.total) { e->err = fmt("selection workspace too small: need %zu bytes, got %zu", S.total, bytes); return LNS_ENOMEM; }
+    return LNS_OK;
+}
+
+int lns_rollout_select(lns_engine* e, const float* x, const float* param, int B, int T, const int* keep_steps_host,
+                       int n_keep, float* out, float* latents_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!e) return LNS_EINVAL;
+    if (int arc = select_check_args(e, x, "x", out, B, T, keep_steps_host, n_keep)) return arc;
+    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
+    if ((e->cfg.prop_kind == LNS_PROP_CONDITIONAL || e->cfg.cond_encoder) && !param) { e->err = "conditional model needs param"; return LNS_EINVAL; }
+    DeviceGuard dg(e);
+    WsLayout L; SelectLayout S; int rc;
+    if ((rc = ws_layout(e, B, &L))) return rc;
+    select_layout(L, &S);
+    if ((rc = check_select_ws(e, S, ws, ws_bytes))) return rc;
+    Plan* pe;
+    if ((rc = get_plan(e, PK_ENC, B, 0, 0, &pe))) return rc;
+    const lns_config& c = e->cfg;
+    const long zper = (long)e->lat_C * e->lat_H * e->lat_W;
+    char* base = static_cast<char*>(ws);
+    const SelectRun sel = {keep_steps_host, n_keep, {base + S.pp_off[0], base + S.pp_off[1]}};
+    Runner r(e, static_cast<hipStream_t>(stream));
+    ExtT ext[EX_COUNT];
+    ext[EX_PARAM] = {param, 1};
+    begin_run(e, ws, B);
+    if ((rc = arm_sticky(e, r.stream))) return rc;
+    // encode once: x -> z0                                    (train_stage2_ns2d.py:144)
+    ext[EX_IN] = {x, (long)c.in_channels * c.Ly * c.Lx};
+    ext[EX_OUT] = {base, zper};
+    if ((rc = r.run(*pe, ext, base + L.arena_off))) return rc;
+    ExtT z0 = {base, zper};
+    if ((rc = rollout_loop(e, r, z0, param, B, T, 1, out, latents_out, nullptr, L, base, nullptr, &sel))) return rc;
+    return r.finish();
+}
+
+int lns_rollout_latent_select(lns_engine* e, const float* z_in, const float* param, int B, int T,
+                              const int* keep_steps_host, int n_keep, float* out, float* z_last, void* ws, size_t ws_bytes,
+                              void* stream) {
+    if (!e) return LNS_EINVAL;
+    if (int arc = select_check_args(e, z_in, "z_in", out, B, T, keep_steps_host, n_keep)) return arc;
+    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
+    if (e->cfg.prop_kind == LNS_PROP_CONDITIONAL && !param) { e->err = "conditional propagator needs param"; return LNS_EINVAL; }
+    DeviceGuard dg(e);
+    WsLayout L; SelectLayout S; int rc;
+    if ((rc = ws_layout(e, B, &L))) return rc;
+    select_layout(L, &S);
+    if ((rc = check_select_ws(e, S, ws, ws_bytes))) return rc;
+    char* base = static_cast<char*>(ws);
+    const SelectRun sel = {keep_steps_host, n_keep, {base + S.pp_off[0], base + S.pp_off[1]}};
+    Runner r(e, static_cast<hipStream_t>(stream));
+    begin_run(e, ws, B);
+    if ((rc = arm_sticky(e, r.stream))) return rc;
+    ExtT z0 = {z_in, (long)e->lat_C * e->lat_H * e->lat_W};
+    if ((rc = rollout_loop(e, r, z0, param, B, T, 1, out, nullptr, z_last, L, base, nullptr, &sel))) return rc;
+    return r.finish();
+}
+
 int lns_check_finite(lns_engine* e, int B, void* ws, size_t ws_bytes, void* stream) {
     if (!e || B <= 0 || !ws) return LNS_EINVAL;
     // The amax vectors live in the CALLER's workspace: they are read through the `ws` handed in here, which must be
@@ -2573,6 +2699,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "train_wgrad_split")) return 1;
     if (!strcmp(feature, "train_clip")) return 1;
     if (!strcmp(feature, "train_ops")) return 1;
+    if (!strcmp(feature, "rollout_select")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else

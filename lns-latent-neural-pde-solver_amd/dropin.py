@@ -434,8 +434,10 @@ class LatentDynamics(_Hosted):
         return x
 
     @torch.no_grad()
-    def predict(self, x, steps, *rest, to_x=False, return_latents=False):
-        """predict(x, steps, to_x=False) -- conditional: predict(x, steps, param, to_x=False)."""
+    def predict(self, x, steps, *rest, to_x=False, return_latents=False, keep_steps=None):
+        """predict(x, steps, to_x=False) -- conditional: predict(x, steps, param, to_x=False).
+        keep_steps (with to_x=True; ints, a range, or a slice such as slice(None, None, 5) for the `::5` the reference
+        plots): only these steps are decoded -> [B, n_keep, C, Ly, Lx], the bits of predict(...)[:, keep_steps]."""
         param = None
         if self._conditional:
             if not rest:
@@ -444,7 +446,7 @@ class LatentDynamics(_Hosted):
         if rest:
             to_x = rest[0]
         x = self._fields(x)
-        return self._engine(x).rollout(x, steps, param=param, to_x=to_x, return_latents=return_latents)
+        return self._engine(x).rollout(x, steps, param=param, to_x=to_x, return_latents=return_latents, keep_steps=keep_steps)
 
     @torch.no_grad()
     def validate(self, x, y, *rest, keep_steps=(), **norm):

@@ -181,6 +181,29 @@ def eval_spec(C, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_chann
     return spec
 
 
+def normalize_keep_steps(keep_steps, steps):
+    """The `keep_steps` argument of the selected-step rollout -> list of ints, strictly ascending, in [0, steps).
+    A slice is resolved against `steps` as indexing a [.., steps, ..] tensor would (slice(None, None, 5) is `::5`); a
+    range or any sequence of integers is taken as it is.  Pure host code; LnsError names what is wrong."""
+    import operator
+    steps = int(steps)
+    if steps <= 0:
+        raise LnsError("steps must be positive, got %d" % steps)
+    if isinstance(keep_steps, slice):
+        keep = list(range(*keep_steps.indices(steps)))
+    else:
+        try:
+            keep = [operator.index(s) for s in keep_steps]
+        except TypeError:
+            raise LnsError("keep_steps must be a sequence of ints, a range or a slice, got %r" % (keep_steps,))
+    if not keep:
+        raise LnsError("keep_steps selects no step of the %d (for latents only: to_x=False)" % steps)
+    for i, s in enumerate(keep):
+        if s < 0 or s >= steps or (i > 0 and s <= keep[i - 1]):
+            raise LnsError("keep_steps must be ascending steps in [0, %d): entry %d is %d" % (steps, i, s))
+    return keep
+
+
 class Engine:
     """One lns_engine handle (one per GPU; not thread-safe)."""
 
@@ -355,12 +378,46 @@ class Engine:
                                           self._stream(z)), "lns_propagate")
         return out
 
-    def rollout(self, x, steps, param=None, to_x=True, return_latents=False, out=None):
+    def _select_workspace(self, B, device):
+        n = ctypes.c_size_t(0)
+        self._check(self._L.lns_rollout_select_workspace_bytes(self._h, int(B), ctypes.byref(n)), "lns_rollout_select_workspace_bytes")
+        return self._workspace(B, device, min_bytes=int(n.value))
+
+    def _select_common(self, first, steps, to_x, out, keep_steps):
+        """Shared argument handling of the keep_steps path of rollout / rollout_latent -> (keep array, n_keep, out)."""
+        import torch
+        if not to_x:
+            raise LnsError("keep_steps selects the steps to DECODE; for latents slice the latent rollout "
+                           "(rollout(..., to_x=False)[:, keep_steps]): every latent is computed anyway")
+        keep = normalize_keep_steps(keep_steps, steps)
+        c = self.cfg
+        shape = (first.shape[0], len(keep), c.in_channels, c.Ly, c.Lx)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=first.device)
+        elif tuple(out.shape) != shape or not out.is_contiguous():
+            raise LnsError("preallocated output must be contiguous with shape %s" % (shape,))
+        return (ctypes.c_int * len(keep))(*keep), len(keep), out
+
+    def rollout(self, x, steps, param=None, to_x=True, return_latents=False, out=None, keep_steps=None):
+        """keep_steps (a sequence of ints, a range, or a slice resolved against `steps`: slice(None, None, 5) is the
+        reference's y_hat[:, ::5]): decode these steps only -> [B, n_keep, C, Ly, Lx], the bits of rollout(x, steps)[:, keep_steps]
+        without the decodes, or the memory, of the other steps.  return_latents still gives all `steps` latents."""
         import torch
         x = self._dev(x)
         B = x.shape[0]
         c = self.cfg
         C, H, W = self.latent_shape()
+        if keep_steps is not None:
+            keep, n_keep, out = self._select_common(x, steps, to_x, out, keep_steps)
+            lat = torch.empty((B, steps, C, H, W), dtype=torch.float32, device=x.device) if return_latents else None
+            p = self._param(param, x)
+            with torch.cuda.device(x.device):
+                ws = self._select_workspace(B, x.device)
+                self._check(self._L.lns_rollout_select(self._h, x.data_ptr(), p.data_ptr() if p is not None else None, B,
+                                                       int(steps), keep, n_keep, out.data_ptr(),
+                                                       lat.data_ptr() if lat is not None else None, ws.data_ptr(),
+                                                       ws.numel(), self._stream(x)), "lns_rollout_select")
+            return (out, lat) if return_latents else out
         shape = (B, steps, c.in_channels, c.Ly, c.Lx) if to_x else (B, steps, C, H, W)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=x.device)
@@ -375,13 +432,25 @@ class Engine:
                                         ws.numel(), self._stream(x)), "lns_rollout")
         return (out, lat) if return_latents else out
 
-    def rollout_latent(self, z, steps, param=None, to_x=True, out=None):
-        """Continue from latent z: returns (out [B,steps,...], z after the last step)."""
+    def rollout_latent(self, z, steps, param=None, to_x=True, out=None, keep_steps=None):
+        """Continue from latent z: returns (out [B,steps,...], z after the last step).  keep_steps (steps of this chunk,
+        as for `rollout`): out is [B, n_keep, C, Ly, Lx]."""
         import torch
         z = self._dev(z)
         B = z.shape[0]
         c = self.cfg
         C, H, W = self.latent_shape()
+        if keep_steps is not None:
+            keep, n_keep, out = self._select_common(z, steps, to_x, out, keep_steps)
+            z_last = torch.empty_like(z)
+            p = self._param(param, z)
+            with torch.cuda.device(z.device):
+                ws = self._select_workspace(B, z.device)
+                self._check(self._L.lns_rollout_latent_select(self._h, z.data_ptr(), p.data_ptr() if p is not None else None,
+                                                              B, int(steps), keep, n_keep, out.data_ptr(), z_last.data_ptr(),
+                                                              ws.data_ptr(), ws.numel(), self._stream(z)),
+                            "lns_rollout_latent_select")
+            return out, z_last
         shape = (B, steps, c.in_channels, c.Ly, c.Lx) if to_x else (B, steps, C, H, W)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=z.device)
