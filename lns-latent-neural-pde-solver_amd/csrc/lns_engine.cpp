@@ -1818,6 +1818,14 @@ struct Runner {
     }
 };
 
+// What a rollout call does with the latent chain: exactly one of
+//   SINK_LATENTS  every latent into `out` [B][T][zper]; nothing is decoded
+//   SINK_STEPS    every step decoded into `out` [B][T][xper]
+//   SINK_KEPT     the steps keep[0 .. n_keep) decoded into `out` [B][n_keep][xper]; the chain still runs all T steps
+//   SINK_SCORED   every step decoded into a frame buffer of the workspace and scored against y_true right there; the frames
+//                 of the steps keep[0 .. n_keep) are copied to frames_out
+enum SinkKind { SINK_LATENTS, SINK_STEPS, SINK_KEPT, SINK_SCORED };
+
 // workspace layout: [ z0 | latent ring: NGROUP groups x kdec steps x [B][zper] | NDEC decode arenas | propagator arena ]
 // The propagator gets its own arena because it runs on a second stream, concurrently with decode.
 // Step-batched decode: the decodes of different steps are independent given z_t, so the latent chain runs ahead and
@@ -1825,8 +1833,16 @@ struct Runner {
 // 32x32 decoder layers, a quarter of the launches, weight slabs amortised).  A trajectory-step's arithmetic does not
 // depend on the batch it rides in (kernel accumulation order is a function of the layer only), so the result is
 // bit-identical for every kdec.
+// Behind it, from round_up(that layout's total, 256) on, the one region the sink needs (never both):
+//   SINK_SCORED  one frame buffer per decode stream (the decode output of a group, [kdec][B][C][Ly][Lx]), then the
+//                metric's per-plane sums [B][eval_max_steps][C][2]
+//   SINK_KEPT    two latent buffers [B][zper] that take the latents of the steps nobody decodes
 enum { NDEC = 4, NGROUP_MAX = NDEC + 2 };   // max decode streams; latent groups in flight
-struct WsLayout { size_t z_bytes, ring_off, group_bytes, arena_off, arena_stride, prop_off, total; int ndec, kdec, ngroup; };
+struct WsLayout {
+    size_t z_bytes, ring_off, group_bytes, arena_off, arena_stride, prop_off, total; int ndec, kdec, ngroup;
+    size_t fbuf_off, fbuf_stride, part_off;   // SINK_SCORED
+    size_t pp_off[2];                         // SINK_KEPT
+};
 
 static int decode_group(const lns_engine* e, int B) {
     // trajectories x steps per decode launch set: about 256 samples ("decode_group" option; 1 = one step per launch)
@@ -1836,7 +1852,9 @@ static int decode_group(const lns_engine* e, int B) {
     return k;
 }
 
-static int ws_layout(lns_engine* e, int B, WsLayout* L) {
+// `total` is what a call with this sink needs.  encode / decode / lns_prepare use the layout of SINK_STEPS; the arena offsets
+// lns_check_finite reads back are the same for every sink
+static int ws_layout(lns_engine* e, int B, SinkKind sink, WsLayout* L) {
     size_t arena = 0, parena = 0;
     Plan* p;
     int rc;
@@ -1863,39 +1881,37 @@ static int ws_layout(lns_engine* e, int B, WsLayout* L) {
     L->arena_stride = round_up_sz(arena, 256);                        // one decode arena per decode stream
     L->prop_off = L->arena_off + (size_t)L->ndec * L->arena_stride;
     L->total = L->prop_off + round_up_sz(parena, 256) + 256;
+    L->fbuf_off = L->fbuf_stride = L->part_off = L->pp_off[0] = L->pp_off[1] = 0;
+    if (sink == SINK_SCORED) {
+        const size_t xper = (size_t)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx;
+        L->fbuf_off = round_up_sz(L->total, 256);
+        L->fbuf_stride = round_up_sz((size_t)L->kdec * B * xper * 4, 256);
+        L->part_off = L->fbuf_off + (size_t)L->ndec * L->fbuf_stride;
+        L->total = L->part_off + round_up_sz((size_t)B * e->opt_eval_max_steps * e->cfg.in_channels * 2 * 4, 256);
+    } else if (sink == SINK_KEPT) {
+        L->pp_off[0] = round_up_sz(L->total, 256);
+        L->pp_off[1] = L->pp_off[0] + L->z_bytes;                     // (z_bytes is a multiple of 256)
+        L->total = L->pp_off[1] + L->z_bytes;
+    }
     return LNS_OK;
 }
 
-// Streaming evaluation (lns_rollout_eval): the rollout layout above, untouched, then one frame buffer per decode stream
-// (the decode output of a group, [kdec][B][C][Ly][Lx]) and the metric's per-plane sums [B][eval_max_steps][C][2].
-struct EvalLayout { size_t fbuf_off, fbuf_stride, part_off, total; };
-static void eval_layout(const lns_engine* e, int B, const WsLayout& L, EvalLayout* E) {
-    const size_t xper = (size_t)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx;
-    E->fbuf_off = round_up_sz(L.total, 256);
-    E->fbuf_stride = round_up_sz((size_t)L.kdec * B * xper * 4, 256);
-    E->part_off = E->fbuf_off + (size_t)L.ndec * E->fbuf_stride;
-    E->total = E->part_off + round_up_sz((size_t)B * e->opt_eval_max_steps * e->cfg.in_channels * 2 * 4, 256);
-}
-
-// what rollout_loop does with a decoded group in evaluation mode (instead of writing it to `out`)
-struct EvalRun {
-    MetricGroupArgs m;             // y, part, shapes, denormalisation; frames / kk / y_t / p_t are set per group
-    int t0;                        // step of y / part that the loop's step 0 is
-    char* fbuf; size_t fbuf_stride;
-    const int* keep; int n_keep; float* frames_out;
+// One rollout call, as the six entry points (lns_rollout, lns_rollout_latent and their _eval / _select forms) describe it
+struct RolloutCall {
+    RolloutCall(const float* start_, bool encode_, const float* param_, int B_, int T_, void* ws_, size_t ws_bytes_, void* stream_)
+        : start(start_), encode(encode_), param(param_), B(B_), T(T_), ws(ws_), ws_bytes(ws_bytes_), stream(stream_) {}
+    const float* start = nullptr; bool encode = false;   // x [B][xper], encoded into z0 first, or the latent z_in [B][zper]
+    const float* param = nullptr; int B = 0, T = 0;
+    SinkKind sink = SINK_STEPS;
+    float* out = nullptr;                                // every sink but SINK_SCORED
+    const int* keep = nullptr; int n_keep = 0;           // SINK_KEPT (n_keep >= 1), SINK_SCORED (n_keep >= 0); host, ascending
+    // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
+    const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
+    float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
+    float* latents_out = nullptr;                        // optional side outputs: all T latents [B][T][zper],
+    float* z_last = nullptr;                             // the latent after the last step [B][zper]
+    void* ws = nullptr; size_t ws_bytes = 0; void* stream = nullptr;
 };
-
-// Selected-step rollout (lns_rollout_select): the rollout layout above, untouched, then two latent buffers [B][zper]
-// that take the latents of the steps nobody decodes.
-struct SelectLayout { size_t pp_off[2], total; };
-static void select_layout(const WsLayout& L, SelectLayout* S) {
-    S->pp_off[0] = round_up_sz(L.total, 256);
-    S->pp_off[1] = S->pp_off[0] + L.z_bytes;                          // (z_bytes is a multiple of 256)
-    S->total = S->pp_off[1] + L.z_bytes;
-}
-
-// which steps rollout_loop decodes (null: all of them); out is then [B][n_keep] instead of [B][T]
-struct SelectRun { const int* keep; int n_keep; char* pp[2]; };
 
 // second stream + events for the propagate / decode overlap (created once, owned by the engine)
 static int ensure_overlap_objects(lns_engine* e) {
@@ -2077,24 +2093,44 @@ static int check_batch(lns_engine* e, int B) {
     return LNS_OK;
 }
 
-int lns_prepare(lns_engine* e, int B, size_t* workspace_bytes) {
-    if (!e || B <= 0) return LNS_EINVAL;
+static int einval(lns_engine* e, const char* what) { e->err = what; return LNS_EINVAL; }
+
+static int need_model(lns_engine* e) {
+    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
+    return LNS_OK;
+}
+
+// a conditional propagator (and, where the call encodes, a conditional encoder) reads one parameter per trajectory
+static int need_param(lns_engine* e, bool encodes, const float* param) {
+    if (param) return LNS_OK;
+    if (e->cfg.prop_kind == LNS_PROP_CONDITIONAL || (encodes && e->cfg.cond_encoder))
+        return einval(e, encodes ? "conditional model needs param" : "conditional propagator needs param");
+    return LNS_OK;
+}
+
+// the three size queries: the layout's total for the sink (lns_prepare also serves engines that only encode / decode)
+static int workspace_bytes(lns_engine* e, int B, SinkKind sink, size_t* bytes) {
+    if (!e) return LNS_EINVAL;
+    if (B <= 0) return einval(e, "B must be positive");
     if (int brc = check_batch(e, B)) return brc;
+    if (sink != SINK_STEPS)
+        if (int mrc = need_model(e)) return mrc;
     DeviceGuard dg(e);
     WsLayout L;
-    int rc = ws_layout(e, B, &L);
-    if (rc) return rc;
-    if (workspace_bytes) *workspace_bytes = L.total;
+    if (int rc = ws_layout(e, B, sink, &L)) return rc;
+    if (bytes) *bytes = L.total;
     return LNS_OK;
 }
 
-static int check_ws(lns_engine* e, const WsLayout& L, void* ws, size_t bytes) {
-    if (!ws || bytes < L.total) { e->err = fmt("workspace too small: need %zu bytes, got %zu", L.total, bytes); return LNS_ENOMEM; }
+int lns_prepare(lns_engine* e, int B, size_t* bytes) { return workspace_bytes(e, B, SINK_STEPS, bytes); }
+int lns_rollout_eval_workspace_bytes(lns_engine* e, int B, size_t* bytes) { return workspace_bytes(e, B, SINK_SCORED, bytes); }
+int lns_rollout_select_workspace_bytes(lns_engine* e, int B, size_t* bytes) { return workspace_bytes(e, B, SINK_KEPT, bytes); }
+
+// label: "" / "evaluation " / "selection " (what the workspace was sized for)
+static int check_ws(lns_engine* e, const WsLayout& L, const char* label, void* ws, size_t bytes) {
+    if (!ws || bytes < L.total) { e->err = fmt("%sworkspace too small: need %zu bytes, got %zu", label, L.total, bytes); return LNS_ENOMEM; }
     return LNS_OK;
 }
-
-static int encode_impl(lns_engine* e, const float* x, const float* param, int B, float* z, void* ws, size_t ws_bytes, void* stream,
-                       const float* ss = nullptr);
 
 // every top-level entry point: forget what the previous call ran (lns_check_finite looks at the LAST call only)
 static void begin_run(lns_engine* e, const void* ws, int B) {
@@ -2110,6 +2146,39 @@ static int arm_sticky(lns_engine* e, hipStream_t s) {
     return LNS_OK;
 }
 
+// encode / decode / propagate: one run of one plan (key B, H, W) on the caller's stream.  The autoencoder's plans run in
+// the decode arena of the rollout layout; the propagator on its own needs its plan's arena only, at offset 0 (an engine
+// without autoencoder has no layout).
+static int run_single(lns_engine* e, PlanKind kind, int B, int H, int W, const ExtT* ext, void* ws, size_t ws_bytes, void* stream) {
+    DeviceGuard dg(e);
+    Plan* p; int rc; size_t arena_off = 0;
+    if (kind == PK_PROP) {
+        if ((rc = get_plan(e, kind, B, H, W, &p))) return rc;
+        if (!ws || ws_bytes < p->arena_bytes) { e->err = fmt("workspace too small: need %zu bytes", p->arena_bytes); return LNS_ENOMEM; }
+    } else {
+        WsLayout L;
+        if ((rc = ws_layout(e, B, SINK_STEPS, &L)) || (rc = check_ws(e, L, "", ws, ws_bytes)) || (rc = get_plan(e, kind, B, H, W, &p))) return rc;
+        arena_off = L.arena_off;
+    }
+    Runner r(e, static_cast<hipStream_t>(stream));
+    begin_run(e, ws, B);
+    if ((rc = arm_sticky(e, r.stream)) || (rc = r.run(*p, ext, static_cast<char*>(ws) + arena_off))) return rc;
+    return r.finish();
+}
+
+static int encode_impl(lns_engine* e, const float* x, const float* param, int B, float* z, void* ws, size_t ws_bytes, void* stream,
+                       const float* ss = nullptr) {
+    if (!e || !x || !z || B <= 0) return LNS_EINVAL;
+    if (int brc = check_batch(e, B)) return brc;
+    const lns_config& c = e->cfg;
+    ExtT ext[EX_COUNT];
+    ext[EX_IN] = {x, (long)c.in_channels * c.Ly * c.Lx};
+    ext[EX_OUT] = {z, (long)e->lat_C * e->lat_H * e->lat_W};
+    ext[EX_PARAM] = {param, 1};
+    ext[EX_SS] = {ss, (long)c.in_channels * 2};
+    return run_single(e, PK_ENC, B, ss ? 1 : 0, 0, ext, ws, ws_bytes, stream);
+}
+
 int lns_encode(lns_engine* e, const float* x, int B, float* z, void* ws, size_t ws_bytes, void* stream) {
     if (e && e->cfg.cond_encoder) { e->err = "this autoencoder's encoder is conditional: use lns_encode_cond(x, param)"; return LNS_EINVAL; }
     return encode_impl(e, x, nullptr, B, z, ws, ws_bytes, stream);
@@ -2119,28 +2188,6 @@ int lns_encode_cond(lns_engine* e, const float* x, const float* param, int B, fl
     if (e && !e->cfg.cond_encoder) { e->err = "lns_encode_cond needs cfg.cond_encoder"; return LNS_EINVAL; }
     if (!param) { if (e) e->err = "conditional encoder needs param"; return LNS_EINVAL; }
     return encode_impl(e, x, param, B, z, ws, ws_bytes, stream);
-}
-
-static int encode_impl(lns_engine* e, const float* x, const float* param, int B, float* z, void* ws, size_t ws_bytes, void* stream,
-                       const float* ss) {
-    if (!e || !x || !z || B <= 0) return LNS_EINVAL;
-    if (int brc = check_batch(e, B)) return brc;
-    DeviceGuard dg(e);
-    WsLayout L; int rc;
-    if ((rc = ws_layout(e, B, &L)) || (rc = check_ws(e, L, ws, ws_bytes))) return rc;
-    Plan* p;
-    if ((rc = get_plan(e, PK_ENC, B, ss ? 1 : 0, 0, &p))) return rc;
-    const lns_config& c = e->cfg;
-    ExtT ext[EX_COUNT];
-    ext[EX_IN] = {x, (long)c.in_channels * c.Ly * c.Lx};
-    ext[EX_OUT] = {z, (long)e->lat_C * e->lat_H * e->lat_W};
-    ext[EX_PARAM] = {param, 1};
-    ext[EX_SS] = {ss, (long)c.in_channels * 2};
-    Runner r(e, static_cast<hipStream_t>(stream));
-    begin_run(e, ws, B);
-    if ((rc = arm_sticky(e, r.stream))) return rc;
-    if ((rc = r.run(*p, ext, static_cast<char*>(ws) + L.arena_off))) return rc;
-    return r.finish();
 }
 
 int lns_encode_affine(lns_engine* e, const float* x, const float* scale_shift, const float* param, int B, float* z, void* ws,
@@ -2153,88 +2200,71 @@ int lns_encode_affine(lns_engine* e, const float* x, const float* scale_shift, c
 int lns_decode(lns_engine* e, const float* z, int B, float* y, void* ws, size_t ws_bytes, void* stream) {
     if (!e || !z || !y || B <= 0) return LNS_EINVAL;
     if (int brc = check_batch(e, B)) return brc;
-    DeviceGuard dg(e);
-    WsLayout L; int rc;
-    if ((rc = ws_layout(e, B, &L)) || (rc = check_ws(e, L, ws, ws_bytes))) return rc;
-    Plan* p;
-    if ((rc = get_plan(e, PK_DEC, B, 0, 0, &p))) return rc;
     const lns_config& c = e->cfg;
     ExtT ext[EX_COUNT];
     ext[EX_IN] = {z, (long)e->lat_C * e->lat_H * e->lat_W};
     ext[EX_OUT] = {y, (long)c.in_channels * c.Ly * c.Lx};
-    Runner r(e, static_cast<hipStream_t>(stream));
-    begin_run(e, ws, B);
-    if ((rc = arm_sticky(e, r.stream))) return rc;
-    if ((rc = r.run(*p, ext, static_cast<char*>(ws) + L.arena_off))) return rc;
-    return r.finish();
+    return run_single(e, PK_DEC, B, 0, 0, ext, ws, ws_bytes, stream);
 }
 
 int lns_propagate(lns_engine* e, const float* z_in, const float* param, int B, int H, int W, float* z_out, void* ws,
                   size_t ws_bytes, void* stream) {
     if (!e || !z_in || !z_out || B <= 0 || H <= 0 || W <= 0) return LNS_EINVAL;
     if (int brc = check_batch(e, B)) return brc;
-    if (e->cfg.prop_kind == LNS_PROP_CONDITIONAL && !param) { e->err = "conditional propagator needs param"; return LNS_EINVAL; }
-    DeviceGuard dg(e);
-    Plan* p; int rc;
-    if ((rc = get_plan(e, PK_PROP, B, H, W, &p))) return rc;
-    if (!ws || ws_bytes < p->arena_bytes) { e->err = fmt("workspace too small: need %zu bytes", p->arena_bytes); return LNS_ENOMEM; }
+    if (int prc = need_param(e, false, param)) return prc;
     ExtT ext[EX_COUNT];
     const long per = (long)e->cfg.latent_dim * H * W;
     ext[EX_IN] = {z_in, per};
     ext[EX_OUT] = {z_out, per};
     ext[EX_PARAM] = {param, 1};
-    Runner r(e, static_cast<hipStream_t>(stream));
-    begin_run(e, ws, B);
-    if ((rc = arm_sticky(e, r.stream))) return rc;
-    if ((rc = r.run(*p, ext, static_cast<char*>(ws)))) return rc;
-    return r.finish();
+    return run_single(e, PK_PROP, B, H, W, ext, ws, ws_bytes, stream);
 }
 
-// shared autoregressive loop: zcur -> T x (propagate ; decode)   (train_stage2_ns2d.py:147-156)
+// the scoring kernel's arguments for a SINK_SCORED call; frames / kk / y_t / p_t are set per decoded group
+static void metric_args(const lns_engine* e, const RolloutCall& c, const WsLayout& L, MetricGroupArgs* mp) {
+    MetricGroupArgs& m = *mp;
+    const lns_eval_spec* spec = c.spec;
+    m.frames = nullptr; m.y = c.y_true; m.part = reinterpret_cast<float*>(static_cast<char*>(c.ws) + L.part_off);
+    m.B = c.B; m.C = e->cfg.in_channels; m.H = e->cfg.Ly; m.W = e->cfg.Lx; m.kk = 0;
+    m.y_T = c.T_total; m.y_t = 0; m.p_T = c.T_total; m.p_t = 0;
+    m.per_channel = spec->per_channel != 0;
+    m.mean = spec->mean; m.sd = spec->std;
+    for (int ch = 0; ch < LNS_METRIC_MAX_CH; ++ch) {       // as lns_metric_rel_l2_ch fills it
+        const bool in = ch < m.C;
+        m.spec.mean[ch] = in ? spec->mean_c[ch] : 0.0f;
+        m.spec.std[ch] = in ? spec->std_c[ch] : 1.0f;
+        m.spec.flags[ch] = in ? spec->flags_c[ch] : 0;
+    }
+    m.spec.lo = spec->clamp_lo; m.spec.hi = spec->clamp_hi;
+}
+
+// the autoregressive loop of every rollout call: zcur -> T x (propagate ; what the sink does)   (train_stage2_ns2d.py:147-156)
 // The latent chain z_t -> z_{t+1} is strictly sequential, but decode(z_t) depends on z_t only: the chain runs ahead
-// (on the engine's side stream when overlapping; own arena) writing groups of `kdec` consecutive latents into the
-// ring, and every finished group is decoded by one launch set at batch B * kdec on one of the decode streams
+// (on the engine's side stream when overlapping; own arena) writing groups of `kdec` consecutive decoded latents into
+// the ring, and every finished group is decoded by one launch set at batch B * kdec on one of the decode streams
 // (round-robin, one arena each), ordered by events, so the small latent-resolution kernels of later steps overlap
 // the large decode kernels of earlier ones.
-// Evaluation mode (ev != null; to_x): the decode of a group writes that decode stream's frame buffer instead of `out`,
-// the scoring kernel and the copies of the kept steps follow on the same decode stream -- in stream order before the
-// next decode that reuses the buffer, so the event scheme is the rollout's own.
-// Selection (sel != null; to_x, no ev): the chain still runs all T steps, the decoder runs for sel->keep only.
-static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param, int B, int T, int to_x, float* out,
-                        float* latents_out, float* z_last, const WsLayout& L, char* base, const EvalRun* ev = nullptr,
-                        const SelectRun* sel = nullptr) {
+// SINK_SCORED: the decode of a group writes that decode stream's frame buffer instead of `out`, the scoring kernel and
+// the copies of the kept steps follow on the same decode stream -- in stream order before the next decode that reuses
+// the buffer, so the event scheme is the rollout's own.
+// SINK_KEPT: the chain still runs all T steps, the decoder runs for the kept ones only.
+// SINK_LATENTS: no step is decoded, so there is no group, no side stream and no event: every step is "a step nobody
+// decodes", whose latent goes straight into `out` on the caller's stream.
+static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& c, const WsLayout& L) {
     Plan* pp;
     int rc;
+    const int B = c.B, T = c.T;
     if ((rc = get_plan(e, PK_PROP, B, e->lat_H, e->lat_W, &pp))) return rc;
-    const lns_config& c = e->cfg;
     const long zper = (long)e->lat_C * e->lat_H * e->lat_W;
-    const long xper = (long)c.in_channels * c.Ly * c.Lx;
+    const long xper = (long)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx;
+    const bool scored = c.sink == SINK_SCORED, kept = c.sink == SINK_KEPT, latents = c.sink == SINK_LATENTS;
+    char* base = static_cast<char*>(c.ws);
     char* arena = base + L.arena_off;
     char* parena = base + L.prop_off;
     hipStream_t stream = r.stream;
     ExtT ext[EX_COUNT];
-    ext[EX_PARAM] = {param, 1};
-    if (!to_x) {
-        // latent-only rollout: single stream, latents written straight into the output
-        for (int t = 0; t < T; ++t) {   // strictly sequential in t, independent in b
-            ExtT znext = {out + (long)t * zper, (long)T * zper};
-            ext[EX_IN] = zcur;
-            ext[EX_OUT] = znext;
-            r.skip_step_invariant = t > 0 && !e->trace_on;
-            rc = r.run(*pp, ext, parena);
-            r.skip_step_invariant = false;
-            if (rc) return rc;
-            if (latents_out)
-                HIPCHK(e, hipMemcpy2DAsync(latents_out + (long)t * zper, (size_t)T * zper * 4, znext.ptr, (size_t)T * zper * 4,
-                                           (size_t)zper * 4, B, hipMemcpyDeviceToDevice, stream));
-            zcur = znext;
-        }
-        if (z_last)
-            HIPCHK(e, hipMemcpy2DAsync(z_last, (size_t)zper * 4, zcur.ptr, (size_t)zcur.bs * 4, (size_t)zper * 4, B,
-                                       hipMemcpyDeviceToDevice, stream));
-        return LNS_OK;
-    }
-    const bool overlap = !e->trace_on && !e->timing_on && e->opt_overlap;
+    ext[EX_PARAM] = {c.param, 1};
+    const bool overlap = !latents && !e->trace_on && !e->timing_on && e->opt_overlap;
     const int kdec = e->trace_on ? 1 : L.kdec, ngroup = L.ngroup, ndec = overlap ? L.ndec : 1;
     if (overlap && (rc = ensure_overlap_objects(e))) return rc;
     hipStream_t pstream = overlap ? static_cast<hipStream_t>(e->side_stream) : stream;
@@ -2260,11 +2290,13 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
     }
     char* ring = base + L.ring_off;
     std::vector<char> used(ngroup, 0);
-    // A decode group is the next up to kdec DECODED steps: all steps, or the kept ones (sel).  The chain writes the
-    // latent of a decoded step into the group's next ring slot and the latent of a skipped step into the two
-    // ping-pong buffers in turn, so a step never writes the buffer it reads.
-    const int n_dec = sel ? sel->n_keep : T;         // decoded steps; `out` is [B][n_dec]
-    auto dec_step = [&](int i) { return sel ? sel->keep[i] : i; };
+    MetricGroupArgs m;
+    if (scored) metric_args(e, c, L, &m);
+    // A decode group is the next up to kdec DECODED steps: all steps, the kept ones, or none.  The chain writes the
+    // latent of a decoded step into the group's next ring slot; the latent of a step nobody decodes goes into `out`
+    // (SINK_LATENTS) or into the two ping-pong buffers in turn (SINK_KEPT), so a step never writes the buffer it reads.
+    const int n_dec = latents ? 0 : (kept ? c.n_keep : T);   // decoded steps; a decoded `out` is [B][n_dec]
+    auto dec_step = [&](int i) { return kept ? c.keep[i] : i; };
     int npp = 0;                                     // the ping-pong buffer the next skipped step writes
     auto chain_step = [&](int t, const ExtT& znext) -> int {   // strictly sequential in t, independent in b
         ext[EX_IN] = zcur;
@@ -2273,18 +2305,19 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
         const int src = rp.run(*pp, ext, parena);
         rp.skip_step_invariant = false;
         if (src) return src;
-        if (latents_out)
-            HIPCHK(e, hipMemcpy2DAsync(latents_out + (long)t * zper, (size_t)T * zper * 4, znext.ptr, (size_t)zper * 4,
+        if (c.latents_out)
+            HIPCHK(e, hipMemcpy2DAsync(c.latents_out + (long)t * zper, (size_t)T * zper * 4, znext.ptr, (size_t)znext.bs * 4,
                                        (size_t)zper * 4, B, hipMemcpyDeviceToDevice, pstream));
         zcur = znext;
         return LNS_OK;
     };
-    auto skipped_step = [&](int t) -> int {
-        const ExtT znext = {sel->pp[npp], zper};
+    auto undecoded_step = [&](int t) -> int {
+        if (latents) return chain_step(t, ExtT{c.out + (long)t * zper, (long)T * zper});
+        const ExtT znext = {base + L.pp_off[npp], zper};
         npp ^= 1;
         return chain_step(t, znext);
     };
-    int g = 0, gi = 0, ki = 0, t = 0;                // ki: next entry of ev->keep; t: next step of the chain
+    int g = 0, gi = 0, ki = 0, t = 0;                // ki: next entry of c.keep (SINK_SCORED); t: next step of the chain
     for (int i0 = 0; i0 < n_dec;) {                  // i0: index in `out` of the group's first step
         const int kk = std::min(kdec, n_dec - i0);
         const int t0g = dec_step(i0);                // the group's first step
@@ -2292,7 +2325,7 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
         // WAR: the decode of the group that lived here (under selection it may have been filled many chain steps ago)
         if (overlap && used[g]) HIPCHK(e, hipStreamWaitEvent(pstream, ev_free[g], 0));
         for (int j = 0; j < kk; ++t) {
-            if (t != dec_step(i0 + j)) { if ((rc = skipped_step(t))) return rc; continue; }
+            if (t != dec_step(i0 + j)) { if ((rc = undecoded_step(t))) return rc; continue; }
             const ExtT znext = {gbase + (size_t)j * B * zper * 4, zper};
             if ((rc = chain_step(t, znext))) return rc;
             ++j;
@@ -2306,17 +2339,16 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
             HIPCHK(e, hipStreamWaitEvent(dstream[d], ev_z[g], 0));
         }
         ext[EX_IN] = {gbase, zper};
-        float* fb = ev ? reinterpret_cast<float*>(ev->fbuf + (size_t)d * ev->fbuf_stride) : nullptr;
-        if (ev) ext[EX_OUT] = {fb, xper};            // [kk][B][xper]: launch sample s = j * B + b
-        else ext[EX_OUT] = {out + (long)i0 * xper, (long)n_dec * xper, xper, B};
+        float* fb = scored ? reinterpret_cast<float*>(base + L.fbuf_off + (size_t)d * L.fbuf_stride) : nullptr;
+        if (scored) ext[EX_OUT] = {fb, xper};        // [kk][B][xper]: launch sample s = j * B + b
+        else ext[EX_OUT] = {c.out + (long)i0 * xper, (long)n_dec * xper, xper, B};
         if ((rc = (overlap ? rd[d] : r).run(*pd, ext, darena[d]))) return rc;
-        if (ev) {                                    // (evaluation decodes every step: t0g == i0)
-            MetricGroupArgs m = ev->m;
-            m.frames = fb; m.kk = kk; m.y_t = ev->t0 + t0g; m.p_t = ev->t0 + t0g;
+        if (scored) {                                // (every step is decoded: t0g == i0)
+            m.frames = fb; m.kk = kk; m.y_t = c.t0 + t0g; m.p_t = c.t0 + t0g;
             HIPCHK(e, launch_metric_group(m, dstream[d]));
-            for (; ki < ev->n_keep && ev->keep[ki] < t0g + kk; ++ki)     // ascending: each kept step lies in one group
-                HIPCHK(e, hipMemcpy2DAsync(ev->frames_out + (long)ki * xper, (size_t)ev->n_keep * xper * 4,
-                                           fb + (long)(ev->keep[ki] - t0g) * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
+            for (; ki < c.n_keep && c.keep[ki] < t0g + kk; ++ki)     // ascending: each kept step lies in one group
+                HIPCHK(e, hipMemcpy2DAsync(c.frames_out + (long)ki * xper, (size_t)c.n_keep * xper * 4,
+                                           fb + (long)(c.keep[ki] - t0g) * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
                                            hipMemcpyDeviceToDevice, dstream[d]));
         }
         if (overlap) { HIPCHK(e, hipEventRecord(ev_free[g], dstream[d])); used[g] = 1; }
@@ -2324,10 +2356,10 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
         g = (g + 1) % ngroup;
         ++gi;
     }
-    for (; t < T; ++t)                               // skipped steps behind the last decoded one: latents_out / z_last
-        if ((rc = skipped_step(t))) return rc;
-    if (z_last)   // the last latent is complete once the propagator stream has passed its step
-        HIPCHK(e, hipMemcpy2DAsync(z_last, (size_t)zper * 4, zcur.ptr, (size_t)zcur.bs * 4, (size_t)zper * 4, B,
+    for (; t < T; ++t)                               // the steps behind the last decoded one
+        if ((rc = undecoded_step(t))) return rc;
+    if (c.z_last)   // the last latent is complete once the propagator stream has passed its step
+        HIPCHK(e, hipMemcpy2DAsync(c.z_last, (size_t)zper * 4, zcur.ptr, (size_t)zcur.bs * 4, (size_t)zper * 4, B,
                                    hipMemcpyDeviceToDevice, pstream));
     if (overlap) {   // join: everything the side streams did is ordered before whatever the caller enqueues next
         HIPCHK(e, hipEventRecord(ev_end[0], pstream));
@@ -2340,55 +2372,7 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const float* param,
     return LNS_OK;
 }
 
-int lns_rollout(lns_engine* e, const float* x, const float* param, int B, int T, int to_x, float* out,
-                float* latents_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!e || !x || !out || B <= 0 || T <= 0) return LNS_EINVAL;
-    if (int brc = check_batch(e, B)) return brc;
-    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
-    if ((e->cfg.prop_kind == LNS_PROP_CONDITIONAL || e->cfg.cond_encoder) && !param) { e->err = "conditional model needs param"; return LNS_EINVAL; }
-    DeviceGuard dg(e);
-    WsLayout L; int rc;
-    if ((rc = ws_layout(e, B, &L)) || (rc = check_ws(e, L, ws, ws_bytes))) return rc;
-    Plan* pe;
-    if ((rc = get_plan(e, PK_ENC, B, 0, 0, &pe))) return rc;
-    const lns_config& c = e->cfg;
-    const long zper = (long)e->lat_C * e->lat_H * e->lat_W;
-    char* base = static_cast<char*>(ws);
-    Runner r(e, static_cast<hipStream_t>(stream));
-    ExtT ext[EX_COUNT];
-    ext[EX_PARAM] = {param, 1};
-    begin_run(e, ws, B);
-    if ((rc = arm_sticky(e, r.stream))) return rc;
-    // encode once: x -> z0                                    (train_stage2_ns2d.py:144)
-    ext[EX_IN] = {x, (long)c.in_channels * c.Ly * c.Lx};
-    ext[EX_OUT] = {base, zper};
-    if ((rc = r.run(*pe, ext, base + L.arena_off))) return rc;
-    ExtT z0 = {base, zper};
-    if ((rc = rollout_loop(e, r, z0, param, B, T, to_x, out, latents_out, nullptr, L, base))) return rc;
-    return r.finish();
-}
-
-int lns_rollout_latent(lns_engine* e, const float* z_in, const float* param, int B, int T, int to_x, float* out,
-                       float* z_last, void* ws, size_t ws_bytes, void* stream) {
-    if (!e || !z_in || !out || B <= 0 || T <= 0) return LNS_EINVAL;
-    if (int brc = check_batch(e, B)) return brc;
-    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
-    if (e->cfg.prop_kind == LNS_PROP_CONDITIONAL && !param) { e->err = "conditional propagator needs param"; return LNS_EINVAL; }
-    DeviceGuard dg(e);
-    WsLayout L; int rc;
-    if ((rc = ws_layout(e, B, &L)) || (rc = check_ws(e, L, ws, ws_bytes))) return rc;
-    Runner r(e, static_cast<hipStream_t>(stream));
-    begin_run(e, ws, B);
-    if ((rc = arm_sticky(e, r.stream))) return rc;
-    ExtT z0 = {z_in, (long)e->lat_C * e->lat_H * e->lat_W};
-    if ((rc = rollout_loop(e, r, z0, param, B, T, to_x, out, nullptr, z_last, L, static_cast<char*>(ws)))) return rc;
-    return r.finish();
-}
-
-// ---- streaming validation rollout (include/lns.h) --------------------------------------------------------------
-static int einval(lns_engine* e, const char* what) { e->err = what; return LNS_EINVAL; }
-
-// kept steps (evaluation: frames to copy out; selection: steps to decode): strictly ascending, in [0, T)
+// kept steps (SINK_SCORED: frames to copy out; SINK_KEPT: steps to decode): strictly ascending, in [0, T)
 static int check_keep_steps(lns_engine* e, const int* keep, int n_keep, int T) {
     for (int i = 0; i < n_keep; ++i)
         if (keep[i] < 0 || keep[i] >= T || (i > 0 && keep[i] <= keep[i - 1])) {
@@ -2398,214 +2382,130 @@ static int check_keep_steps(lns_engine* e, const int* keep, int n_keep, int T) {
     return LNS_OK;
 }
 
-// argument checks shared by the two evaluation calls; nothing here touches the device
-static int eval_check_args(lns_engine* e, const void* first, const char* first_name, const float* y_true, int B, int T, int t0,
-                           int T_total, const lns_eval_spec* spec, const float* frame_out, const float* seq_out,
-                           const int* keep, int n_keep, const float* frames_out) {
-    if (!first) { e->err = fmt("%s is null", first_name); return LNS_EINVAL; }
-    if (!y_true) return einval(e, "y_true is null");
-    if (B <= 0) return einval(e, "B must be positive");
-    if (T <= 0) return einval(e, "T must be positive");
-    if (t0 < 0 || (long)t0 + T > T_total) { e->err = fmt("t0 + T = %d + %d exceeds T_total = %d (or t0 < 0)", t0, T, T_total); return LNS_EINVAL; }
-    if (!frame_out && !seq_out) return einval(e, "frame_out and seq_out are both null");
-    if (!spec || spec->size != sizeof(lns_eval_spec)) return einval(e, "spec is null or its size field is not sizeof(lns_eval_spec)");
-    if (spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "spec: the per-channel form needs in_channels <= 8");
-    if (n_keep < 0) return einval(e, "n_keep is negative");
-    if (n_keep > 0) {
-        if (!keep) return einval(e, "keep_steps is null but n_keep > 0");
-        if (!frames_out) return einval(e, "frames_out is null but n_keep > 0");
-        if (int krc = check_keep_steps(e, keep, n_keep, T)) return krc;
+// every refusal of a rollout call that needs no plan: nothing here touches the device.  The order is part of the
+// interface (which of two failing checks answers): arguments, batch, eval_max_steps, the model, param.
+static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
+    const bool scored = c.sink == SINK_SCORED, kept = c.sink == SINK_KEPT;
+    if (!c.start) return einval(e, c.encode ? "x is null" : "z_in is null");
+    if (scored && !c.y_true) return einval(e, "y_true is null");
+    if (!scored && !c.out) return einval(e, "out is null");
+    if (c.B <= 0) return einval(e, "B must be positive");
+    if (c.T <= 0) return einval(e, "T must be positive");
+    if (scored) {
+        if (c.t0 < 0 || (long)c.t0 + c.T > c.T_total) {
+            e->err = fmt("t0 + T = %d + %d exceeds T_total = %d (or t0 < 0)", c.t0, c.T, c.T_total);
+            return LNS_EINVAL;
+        }
+        if (!c.frame_out && !c.seq_out) return einval(e, "frame_out and seq_out are both null");
+        if (!c.spec || c.spec->size != sizeof(lns_eval_spec)) return einval(e, "spec is null or its size field is not sizeof(lns_eval_spec)");
+        if (c.spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "spec: the per-channel form needs in_channels <= 8");
+        if (c.n_keep < 0) return einval(e, "n_keep is negative");
     }
-    if (int brc = check_batch(e, B)) return brc;
-    if (T_total > e->opt_eval_max_steps) {
-        e->err = fmt("%d steps exceed the option eval_max_steps = %d (it sizes the evaluation workspace)", T_total, e->opt_eval_max_steps);
+    if (kept && c.n_keep < 1) return einval(e, "n_keep must be at least 1 (for no decoded step: lns_rollout with to_x = 0)");
+    if ((scored || kept) && c.n_keep > 0) {
+        if (!c.keep) return einval(e, scored ? "keep_steps is null but n_keep > 0" : "keep_steps is null");
+        if (scored && !c.frames_out) return einval(e, "frames_out is null but n_keep > 0");
+        if (int krc = check_keep_steps(e, c.keep, c.n_keep, c.T)) return krc;
+    }
+    if (int brc = check_batch(e, c.B)) return brc;
+    if (scored && c.T_total > e->opt_eval_max_steps) {
+        e->err = fmt("%d steps exceed the option eval_max_steps = %d (it sizes the evaluation workspace)", c.T_total, e->opt_eval_max_steps);
         return LNS_EINVAL;
     }
-    return LNS_OK;
+    if (int mrc = need_model(e)) return mrc;
+    return need_param(e, c.encode, c.param);
 }
 
-static void eval_fill(const lns_engine* e, EvalRun* ev, const float* y_true, int B, int t0, int T_total, const lns_eval_spec* spec,
-                      const int* keep, int n_keep, float* frames_out, char* base, const EvalLayout& E) {
-    MetricGroupArgs& m = ev->m;
-    m.frames = nullptr; m.y = y_true; m.part = reinterpret_cast<float*>(base + E.part_off);
-    m.B = B; m.C = e->cfg.in_channels; m.H = e->cfg.Ly; m.W = e->cfg.Lx; m.kk = 0;
-    m.y_T = T_total; m.y_t = 0; m.p_T = T_total; m.p_t = 0;
-    m.per_channel = spec->per_channel != 0;
-    m.mean = spec->mean; m.sd = spec->std;
-    for (int c = 0; c < LNS_METRIC_MAX_CH; ++c) {       // as lns_metric_rel_l2_ch fills it
-        const bool in = c < m.C;
-        m.spec.mean[c] = in ? spec->mean_c[c] : 0.0f;
-        m.spec.std[c] = in ? spec->std_c[c] : 1.0f;
-        m.spec.flags[c] = in ? spec->flags_c[c] : 0;
-    }
-    m.spec.lo = spec->clamp_lo; m.spec.hi = spec->clamp_hi;
-    ev->t0 = t0;
-    ev->fbuf = base + E.fbuf_off; ev->fbuf_stride = E.fbuf_stride;
-    ev->keep = keep; ev->n_keep = n_keep; ev->frames_out = frames_out;
-}
-
-int lns_rollout_eval_workspace_bytes(lns_engine* e, int B, size_t* bytes) {
+// the one call path behind the six rollout entry points
+static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if (!e) return LNS_EINVAL;
-    if (B <= 0) return einval(e, "B must be positive");
-    if (int brc = check_batch(e, B)) return brc;
-    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
+    int rc;
+    if ((rc = rollout_refusal(e, c))) return rc;
+    const bool scored = c.sink == SINK_SCORED;
     DeviceGuard dg(e);
-    WsLayout L; EvalLayout E;
-    if (int rc = ws_layout(e, B, &L)) return rc;
-    eval_layout(e, B, L, &E);
-    if (bytes) *bytes = E.total;
-    return LNS_OK;
+    WsLayout L;
+    if ((rc = ws_layout(e, c.B, c.sink, &L)) ||
+        (rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : ""), c.ws, c.ws_bytes))) return rc;
+    Plan* pe = nullptr;
+    if (c.encode && (rc = get_plan(e, PK_ENC, c.B, 0, 0, &pe))) return rc;
+    const lns_config& cfg = e->cfg;
+    const long zper = (long)e->lat_C * e->lat_H * e->lat_W;
+    char* base = static_cast<char*>(c.ws);
+    Runner r(e, static_cast<hipStream_t>(c.stream));
+    begin_run(e, c.ws, c.B);
+    if ((rc = arm_sticky(e, r.stream))) return rc;
+    ExtT z0 = {c.start, zper};
+    if (c.encode) {   // encode once: x -> z0                  (train_stage2_ns2d.py:144)
+        ExtT ext[EX_COUNT];
+        ext[EX_PARAM] = {c.param, 1};
+        ext[EX_IN] = {c.start, (long)cfg.in_channels * cfg.Ly * cfg.Lx};
+        ext[EX_OUT] = {base, zper};
+        if ((rc = r.run(*pe, ext, base + L.arena_off))) return rc;
+        z0.ptr = base;
+    }
+    if ((rc = rollout_loop(e, r, z0, c, L))) return rc;
+    // every plane's pair is in place once the decode streams have joined: frame- and sequence-wise ratios, once the
+    // horizon is complete (the pairs of the earlier chunks are in the workspace)
+    if (scored && c.t0 + c.T == c.T_total)
+        HIPCHK(e, launch_metric_finish(reinterpret_cast<float*>(base + L.part_off), c.B, c.T_total, cfg.in_channels, c.spec->eps,
+                                       c.frame_out, c.seq_out, r.stream));
+    return r.finish();
 }
 
-static int check_eval_ws(lns_engine* e, const EvalLayout& E, void* ws, size_t bytes) {
-    if (!ws || bytes < E.total) { e->err = fmt("evaluation workspace too small: need %zu bytes, got %zu", E.total, bytes); return LNS_ENOMEM; }
-    return LNS_OK;
+static void score_into(RolloutCall& c, const float* y_true, int t0, int T_total, const lns_eval_spec* spec, float* frame_out,
+                       float* seq_out, const int* keep, int n_keep, float* frames_out) {
+    c.sink = SINK_SCORED;
+    c.y_true = y_true; c.t0 = t0; c.T_total = T_total; c.spec = spec; c.frame_out = frame_out; c.seq_out = seq_out;
+    c.keep = keep; c.n_keep = n_keep; c.frames_out = frames_out;
 }
 
+int lns_rollout(lns_engine* e, const float* x, const float* param, int B, int T, int to_x, float* out,
+                float* latents_out, void* ws, size_t ws_bytes, void* stream) {
+    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
+    c.sink = to_x ? SINK_STEPS : SINK_LATENTS; c.out = out; c.latents_out = latents_out;
+    return rollout_call(e, c);
+}
+
+int lns_rollout_latent(lns_engine* e, const float* z_in, const float* param, int B, int T, int to_x, float* out,
+                       float* z_last, void* ws, size_t ws_bytes, void* stream) {
+    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
+    c.sink = to_x ? SINK_STEPS : SINK_LATENTS; c.out = out; c.z_last = z_last;
+    return rollout_call(e, c);
+}
+
+// ---- streaming validation rollout (include/lns.h) --------------------------------------------------------------
 int lns_rollout_eval(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
                      const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
                      float* frames_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!e) return LNS_EINVAL;
-    if (int arc = eval_check_args(e, x, "x", y_true, B, T, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out)) return arc;
-    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
-    if ((e->cfg.prop_kind == LNS_PROP_CONDITIONAL || e->cfg.cond_encoder) && !param) { e->err = "conditional model needs param"; return LNS_EINVAL; }
-    DeviceGuard dg(e);
-    WsLayout L; EvalLayout E; int rc;
-    if ((rc = ws_layout(e, B, &L))) return rc;
-    eval_layout(e, B, L, &E);
-    if ((rc = check_eval_ws(e, E, ws, ws_bytes))) return rc;
-    Plan* pe;
-    if ((rc = get_plan(e, PK_ENC, B, 0, 0, &pe))) return rc;
-    const lns_config& c = e->cfg;
-    const long zper = (long)e->lat_C * e->lat_H * e->lat_W;
-    char* base = static_cast<char*>(ws);
-    EvalRun ev;
-    eval_fill(e, &ev, y_true, B, 0, T, spec, keep_steps_host, n_keep, frames_out, base, E);
-    Runner r(e, static_cast<hipStream_t>(stream));
-    ExtT ext[EX_COUNT];
-    ext[EX_PARAM] = {param, 1};
-    begin_run(e, ws, B);
-    if ((rc = arm_sticky(e, r.stream))) return rc;
-    // encode once: x -> z0                                    (train_stage2_ns2d.py:144)
-    ext[EX_IN] = {x, (long)c.in_channels * c.Ly * c.Lx};
-    ext[EX_OUT] = {base, zper};
-    if ((rc = r.run(*pe, ext, base + L.arena_off))) return rc;
-    ExtT z0 = {base, zper};
-    if ((rc = rollout_loop(e, r, z0, param, B, T, 1, nullptr, nullptr, nullptr, L, base, &ev))) return rc;
-    // every plane's pair is in place once the decode streams have joined: frame- and sequence-wise ratios
-    HIPCHK(e, launch_metric_finish(ev.m.part, B, T, c.in_channels, spec->eps, frame_out, seq_out, r.stream));
-    return r.finish();
+    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
+    score_into(c, y_true, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
+    return rollout_call(e, c);
 }
 
 int lns_rollout_latent_eval(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
                             int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
                             const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* ws,
                             size_t ws_bytes, void* stream) {
-    if (!e) return LNS_EINVAL;
-    if (int arc = eval_check_args(e, z_in, "z_in", y_true, B, T, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out)) return arc;
-    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
-    if (e->cfg.prop_kind == LNS_PROP_CONDITIONAL && !param) { e->err = "conditional propagator needs param"; return LNS_EINVAL; }
-    DeviceGuard dg(e);
-    WsLayout L; EvalLayout E; int rc;
-    if ((rc = ws_layout(e, B, &L))) return rc;
-    eval_layout(e, B, L, &E);
-    if ((rc = check_eval_ws(e, E, ws, ws_bytes))) return rc;
-    char* base = static_cast<char*>(ws);
-    EvalRun ev;
-    eval_fill(e, &ev, y_true, B, t0, T_total, spec, keep_steps_host, n_keep, frames_out, base, E);
-    Runner r(e, static_cast<hipStream_t>(stream));
-    begin_run(e, ws, B);
-    if ((rc = arm_sticky(e, r.stream))) return rc;
-    ExtT z0 = {z_in, (long)e->lat_C * e->lat_H * e->lat_W};
-    if ((rc = rollout_loop(e, r, z0, param, B, T, 1, nullptr, nullptr, z_last, L, base, &ev))) return rc;
-    if (t0 + T == T_total)   // the horizon is complete: the pairs of the earlier chunks are in the workspace
-        HIPCHK(e, launch_metric_finish(ev.m.part, B, T_total, e->cfg.in_channels, spec->eps, frame_out, seq_out, r.stream));
-    return r.finish();
+    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
+    score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
+    c.z_last = z_last;
+    return rollout_call(e, c);
 }
 
 // ---- selected-step rollout (include/lns.h) ----------------------------------------------------------------------
-// argument checks shared by the two selection calls; nothing here touches the device
-static int select_check_args(lns_engine* e, const void* first, const char* first_name, const float* out, int B, int T,
-                             const int* keep, int n_keep) {
-    if (!first) { e->err = fmt("%s is null", first_name); return LNS_EINVAL; }
-    if (!out) return einval(e, "out is null");
-    if (B <= 0) return einval(e, "B must be positive");
-    if (T <= 0) return einval(e, "T must be positive");
-    if (n_keep < 1) return einval(e, "n_keep must be at least 1 (for no decoded step: lns_rollout with to_x = 0)");
-    if (!keep) return einval(e, "keep_steps is null");
-    if (int krc = check_keep_steps(e, keep, n_keep, T)) return krc;
-    return check_batch(e, B);
-}
-
-int lns_rollout_select_workspace_bytes(lns_engine* e, int B, size_t* bytes) {
-    if (!e) return LNS_EINVAL;
-    if (B <= 0) return einval(e, "B must be positive");
-    if (int brc = check_batch(e, B)) return brc;
-    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
-    DeviceGuard dg(e);
-    WsLayout L; SelectLayout S;
-    if (int rc = ws_layout(e, B, &L)) return rc;
-    select_layout(L, &S);
-    if (bytes) *bytes = S.total;
-    return LNS_OK;
-}
-
-static int check_select_ws(lns_engine* e, const SelectLayout& S, void* ws, size_t bytes) {
-    if (!ws || bytes < S.total) { e->err = fmt("selection workspace too small: need %zu bytes, got %zu", S.total, bytes); return LNS_ENOMEM; }
-    return LNS_OK;
-}
-
 int lns_rollout_select(lns_engine* e, const float* x, const float* param, int B, int T, const int* keep_steps_host,
                        int n_keep, float* out, float* latents_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!e) return LNS_EINVAL;
-    if (int arc = select_check_args(e, x, "x", out, B, T, keep_steps_host, n_keep)) return arc;
-    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
-    if ((e->cfg.prop_kind == LNS_PROP_CONDITIONAL || e->cfg.cond_encoder) && !param) { e->err = "conditional model needs param"; return LNS_EINVAL; }
-    DeviceGuard dg(e);
-    WsLayout L; SelectLayout S; int rc;
-    if ((rc = ws_layout(e, B, &L))) return rc;
-    select_layout(L, &S);
-    if ((rc = check_select_ws(e, S, ws, ws_bytes))) return rc;
-    Plan* pe;
-    if ((rc = get_plan(e, PK_ENC, B, 0, 0, &pe))) return rc;
-    const lns_config& c = e->cfg;
-    const long zper = (long)e->lat_C * e->lat_H * e->lat_W;
-    char* base = static_cast<char*>(ws);
-    const SelectRun sel = {keep_steps_host, n_keep, {base + S.pp_off[0], base + S.pp_off[1]}};
-    Runner r(e, static_cast<hipStream_t>(stream));
-    ExtT ext[EX_COUNT];
-    ext[EX_PARAM] = {param, 1};
-    begin_run(e, ws, B);
-    if ((rc = arm_sticky(e, r.stream))) return rc;
-    // encode once: x -> z0                                    (train_stage2_ns2d.py:144)
-    ext[EX_IN] = {x, (long)c.in_channels * c.Ly * c.Lx};
-    ext[EX_OUT] = {base, zper};
-    if ((rc = r.run(*pe, ext, base + L.arena_off))) return rc;
-    ExtT z0 = {base, zper};
-    if ((rc = rollout_loop(e, r, z0, param, B, T, 1, out, latents_out, nullptr, L, base, nullptr, &sel))) return rc;
-    return r.finish();
+    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
+    c.sink = SINK_KEPT; c.keep = keep_steps_host; c.n_keep = n_keep; c.out = out; c.latents_out = latents_out;
+    return rollout_call(e, c);
 }
 
 int lns_rollout_latent_select(lns_engine* e, const float* z_in, const float* param, int B, int T,
                               const int* keep_steps_host, int n_keep, float* out, float* z_last, void* ws, size_t ws_bytes,
                               void* stream) {
-    if (!e) return LNS_EINVAL;
-    if (int arc = select_check_args(e, z_in, "z_in", out, B, T, keep_steps_host, n_keep)) return arc;
-    if (e->enc.empty() || e->prop.empty()) { e->err = "rollout needs autoencoder and propagator"; return LNS_ESTATE; }
-    if (e->cfg.prop_kind == LNS_PROP_CONDITIONAL && !param) { e->err = "conditional propagator needs param"; return LNS_EINVAL; }
-    DeviceGuard dg(e);
-    WsLayout L; SelectLayout S; int rc;
-    if ((rc = ws_layout(e, B, &L))) return rc;
-    select_layout(L, &S);
-    if ((rc = check_select_ws(e, S, ws, ws_bytes))) return rc;
-    char* base = static_cast<char*>(ws);
-    const SelectRun sel = {keep_steps_host, n_keep, {base + S.pp_off[0], base + S.pp_off[1]}};
-    Runner r(e, static_cast<hipStream_t>(stream));
-    begin_run(e, ws, B);
-    if ((rc = arm_sticky(e, r.stream))) return rc;
-    ExtT z0 = {z_in, (long)e->lat_C * e->lat_H * e->lat_W};
-    if ((rc = rollout_loop(e, r, z0, param, B, T, 1, out, nullptr, z_last, L, base, nullptr, &sel))) return rc;
-    return r.finish();
+    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
+    c.sink = SINK_KEPT; c.keep = keep_steps_host; c.n_keep = n_keep; c.out = out; c.z_last = z_last;
+    return rollout_call(e, c);
 }
 
 int lns_check_finite(lns_engine* e, int B, void* ws, size_t ws_bytes, void* stream) {

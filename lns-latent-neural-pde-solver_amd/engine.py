@@ -339,7 +339,7 @@ class Engine:
             if bool(self.cfg.cond_encoder) != (param is not None):
                 raise LnsError("param must be given exactly for a conditional encoder")
             p = self._param(param, x) if param is not None else None
-            self._check(self._L.lns_encode_affine(self._h, x.data_ptr(), ss.data_ptr(), p.data_ptr() if p is not None else None,
+            self._check(self._L.lns_encode_affine(self._h, x.data_ptr(), ss.data_ptr(), self._ptr(p),
                                                   B, z.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(x)),
                         "lns_encode_affine")
             return z
@@ -373,96 +373,80 @@ class Engine:
         p = self._param(param, z)
         # propagator-only engines have no lns_prepare(): size generously from the activations
         ws = self._workspace(B, z.device, min_bytes=64 * B * max(C, self.cfg.prop_n_embd) * H * W * 4 + (1 << 22))
-        self._check(self._L.lns_propagate(self._h, z.data_ptr(), p.data_ptr() if p is not None else None,
+        self._check(self._L.lns_propagate(self._h, z.data_ptr(), self._ptr(p),
                                           B, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                           self._stream(z)), "lns_propagate")
         return out
 
-    def _select_workspace(self, B, device):
+    def _sized_workspace(self, query, B, device):
+        """The engine's workspace for batch B, at least as large as the size query `query` (lns_*_workspace_bytes) asks."""
         n = ctypes.c_size_t(0)
-        self._check(self._L.lns_rollout_select_workspace_bytes(self._h, int(B), ctypes.byref(n)), "lns_rollout_select_workspace_bytes")
+        self._check(getattr(self._L, query)(self._h, int(B), ctypes.byref(n)), query)
         return self._workspace(B, device, min_bytes=int(n.value))
 
-    def _select_common(self, first, steps, to_x, out, keep_steps):
-        """Shared argument handling of the keep_steps path of rollout / rollout_latent -> (keep array, n_keep, out)."""
+    @staticmethod
+    def _ptr(t):
+        return t.data_ptr() if t is not None else None
+
+    @staticmethod
+    def _out(out, shape, device):
+        """A new fp32 tensor of `shape`, or the caller's preallocated one once it is seen to fit."""
         import torch
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=device)
+        if tuple(out.shape) != shape or not out.is_contiguous():
+            raise LnsError("preallocated output must be contiguous with shape %s" % (shape,))
+        return out
+
+    @staticmethod
+    def _keep_array(steps, to_x, keep_steps):
+        """keep_steps of rollout / rollout_latent -> ctypes int array (pure host code: decided before any device use)."""
         if not to_x:
             raise LnsError("keep_steps selects the steps to DECODE; for latents slice the latent rollout "
                            "(rollout(..., to_x=False)[:, keep_steps]): every latent is computed anyway")
         keep = normalize_keep_steps(keep_steps, steps)
+        return (ctypes.c_int * len(keep))(*keep)
+
+    def _rollout_call(self, first, from_x, steps, param, to_x, out, keep_steps, want_side):
+        """The one call behind rollout (from_x: `first` is x) and rollout_latent (`first` is z), with every step or with
+        keep_steps -> (out, side output): all latents [B, steps, C, H, W] from x, the latent after the last step from z."""
+        import contextlib
+        import torch
+        B = first.shape[0]
         c = self.cfg
-        shape = (first.shape[0], len(keep), c.in_channels, c.Ly, c.Lx)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=first.device)
-        elif tuple(out.shape) != shape or not out.is_contiguous():
-            raise LnsError("preallocated output must be contiguous with shape %s" % (shape,))
-        return (ctypes.c_int * len(keep))(*keep), len(keep), out
+        C, H, W = self.latent_shape()
+        keep = self._keep_array(steps, to_x, keep_steps) if keep_steps is not None else None
+        if not to_x:
+            shape = (B, steps, C, H, W)
+        else:
+            shape = (B, steps if keep is None else len(keep), c.in_channels, c.Ly, c.Lx)
+        out = self._out(out, shape, first.device)
+        side = torch.empty((B, steps, C, H, W) if from_x else tuple(first.shape), dtype=torch.float32,
+                           device=first.device) if want_side else None
+        p = self._param(param, first)
+        name = "lns_rollout" + ("" if from_x else "_latent") + ("" if keep is None else "_select")
+        sink = (int(bool(to_x)), out.data_ptr()) if keep is None else (keep, len(keep), out.data_ptr())
+        # the selected-step calls run with the input's device current, the others with whatever device the caller has
+        with torch.cuda.device(first.device) if keep is not None else contextlib.nullcontext():
+            if keep is None:
+                ws = self._workspace(B, first.device)
+            else:
+                ws = self._sized_workspace("lns_rollout_select_workspace_bytes", B, first.device)
+            self._check(getattr(self._L, name)(self._h, first.data_ptr(), self._ptr(p), B, int(steps), *sink, self._ptr(side),
+                                               ws.data_ptr(), ws.numel(), self._stream(first)), name)
+        return out, side
 
     def rollout(self, x, steps, param=None, to_x=True, return_latents=False, out=None, keep_steps=None):
         """keep_steps (a sequence of ints, a range, or a slice resolved against `steps`: slice(None, None, 5) is the
         reference's y_hat[:, ::5]): decode these steps only -> [B, n_keep, C, Ly, Lx], the bits of rollout(x, steps)[:, keep_steps]
         without the decodes, or the memory, of the other steps.  return_latents still gives all `steps` latents."""
-        import torch
-        x = self._dev(x)
-        B = x.shape[0]
-        c = self.cfg
-        C, H, W = self.latent_shape()
-        if keep_steps is not None:
-            keep, n_keep, out = self._select_common(x, steps, to_x, out, keep_steps)
-            lat = torch.empty((B, steps, C, H, W), dtype=torch.float32, device=x.device) if return_latents else None
-            p = self._param(param, x)
-            with torch.cuda.device(x.device):
-                ws = self._select_workspace(B, x.device)
-                self._check(self._L.lns_rollout_select(self._h, x.data_ptr(), p.data_ptr() if p is not None else None, B,
-                                                       int(steps), keep, n_keep, out.data_ptr(),
-                                                       lat.data_ptr() if lat is not None else None, ws.data_ptr(),
-                                                       ws.numel(), self._stream(x)), "lns_rollout_select")
-            return (out, lat) if return_latents else out
-        shape = (B, steps, c.in_channels, c.Ly, c.Lx) if to_x else (B, steps, C, H, W)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        elif tuple(out.shape) != shape or not out.is_contiguous():
-            raise LnsError("preallocated output must be contiguous with shape %s" % (shape,))
-        lat = torch.empty((B, steps, C, H, W), dtype=torch.float32, device=x.device) if return_latents else None
-        p = self._param(param, x)
-        ws = self._workspace(B, x.device)
-        self._check(self._L.lns_rollout(self._h, x.data_ptr(), p.data_ptr() if p is not None else None, B,
-                                        int(steps), int(bool(to_x)), out.data_ptr(),
-                                        lat.data_ptr() if lat is not None else None, ws.data_ptr(),
-                                        ws.numel(), self._stream(x)), "lns_rollout")
+        out, lat = self._rollout_call(self._dev(x), True, steps, param, to_x, out, keep_steps, return_latents)
         return (out, lat) if return_latents else out
 
     def rollout_latent(self, z, steps, param=None, to_x=True, out=None, keep_steps=None):
         """Continue from latent z: returns (out [B,steps,...], z after the last step).  keep_steps (steps of this chunk,
         as for `rollout`): out is [B, n_keep, C, Ly, Lx]."""
-        import torch
-        z = self._dev(z)
-        B = z.shape[0]
-        c = self.cfg
-        C, H, W = self.latent_shape()
-        if keep_steps is not None:
-            keep, n_keep, out = self._select_common(z, steps, to_x, out, keep_steps)
-            z_last = torch.empty_like(z)
-            p = self._param(param, z)
-            with torch.cuda.device(z.device):
-                ws = self._select_workspace(B, z.device)
-                self._check(self._L.lns_rollout_latent_select(self._h, z.data_ptr(), p.data_ptr() if p is not None else None,
-                                                              B, int(steps), keep, n_keep, out.data_ptr(), z_last.data_ptr(),
-                                                              ws.data_ptr(), ws.numel(), self._stream(z)),
-                            "lns_rollout_latent_select")
-            return out, z_last
-        shape = (B, steps, c.in_channels, c.Ly, c.Lx) if to_x else (B, steps, C, H, W)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=z.device)
-        elif tuple(out.shape) != shape or not out.is_contiguous():
-            raise LnsError("preallocated output must be contiguous with shape %s" % (shape,))
-        z_last = torch.empty_like(z)
-        p = self._param(param, z)
-        ws = self._workspace(B, z.device)
-        self._check(self._L.lns_rollout_latent(self._h, z.data_ptr(), p.data_ptr() if p is not None else None, B,
-                                               int(steps), int(bool(to_x)), out.data_ptr(), z_last.data_ptr(),
-                                               ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent")
-        return out, z_last
+        return self._rollout_call(self._dev(z), False, steps, param, to_x, out, keep_steps, True)
 
     # -- streaming validation rollout (include/lns.h "streaming validation rollout") --------------------------------
     def _eval_common(self, first, y, steps, t0, keep_steps, norm):
@@ -485,11 +469,6 @@ class Engine:
         frames = torch.empty((B, len(keep), c.in_channels, c.Ly, c.Lx), dtype=torch.float32, device=y.device) if keep else None
         return y, B, T, T_total, spec, arr, len(keep), frames
 
-    def _eval_workspace(self, B, device):
-        n = ctypes.c_size_t(0)
-        self._check(self._L.lns_rollout_eval_workspace_bytes(self._h, int(B), ctypes.byref(n)), "lns_rollout_eval_workspace_bytes")
-        return self._workspace(B, device, min_bytes=int(n.value))
-
     def rollout_eval(self, x, y, steps=None, param=None, keep_steps=(), **norm):
         """The validation loop's predict -> denormalize -> relative_lp_loss pair (train_stage2_ns2d.py:249-263) without the
         [B,T,C,Ly,Lx] rollout: every decoded group of steps is scored against the normalised ground truth y [B,T,C,Ly,Lx]
@@ -506,10 +485,10 @@ class Engine:
         seq = torch.empty((B, self.cfg.in_channels), dtype=torch.float32, device=x.device)
         p = self._param(param, x)
         with torch.cuda.device(x.device):
-            ws = self._eval_workspace(B, x.device)
-            self._check(self._L.lns_rollout_eval(self._h, x.data_ptr(), p.data_ptr() if p is not None else None, y.data_ptr(),
+            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, x.device)
+            self._check(self._L.lns_rollout_eval(self._h, x.data_ptr(), self._ptr(p), y.data_ptr(),
                                                  B, T, ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(), keep, n_keep,
-                                                 frames.data_ptr() if frames is not None else None, ws.data_ptr(),
+                                                 self._ptr(frames), ws.data_ptr(),
                                                  ws.numel(), self._stream(x)), "lns_rollout_eval")
         return frame, seq, frames
 
@@ -534,11 +513,11 @@ class Engine:
         z_last = torch.empty_like(z)
         p = self._param(param, z)
         with torch.cuda.device(z.device):
-            ws = self._eval_workspace(B, z.device)
-            self._check(self._L.lns_rollout_latent_eval(self._h, z.data_ptr(), p.data_ptr() if p is not None else None,
+            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, z.device)
+            self._check(self._L.lns_rollout_latent_eval(self._h, z.data_ptr(), self._ptr(p),
                                                         y.data_ptr(), B, T, t0, T_total, ctypes.byref(spec), frame.data_ptr(),
                                                         seq.data_ptr(), keep, n_keep,
-                                                        frames.data_ptr() if frames is not None else None, z_last.data_ptr(),
+                                                        self._ptr(frames), z_last.data_ptr(),
                                                         ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_eval")
         return frame, seq, frames, z_last
 

@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""What do the rollout entry points enqueue?  One JSON object: "case/entry/options" -> {output tensor: sha256 of its
+bytes} for every rollout entry point of `Engine` (rollout, rollout with to_x=False, rollout with keep_steps,
+rollout_latent, rollout_latent with keep_steps, rollout_eval, rollout_latent_eval in one chunk and in two, 4 + 3) under
+decode_group {default, 1, 2, automatic} x decode_streams {1, 2} x overlap {0, 1}, at B = 2, T = 7 (decode_group = 2: a ragged last
+group), keep_steps = [1, 4, 6], on the shapes of the ns2d_mini, twophase_cond and sw_half_periodic fixtures with inputs
+from `filler`; plus "launches/<call>" -> {kernel class: launches} of one rollout, one rollout(keep_steps=...) and one
+rollout_eval of ns2d_mini under timing_enable(True).  Two builds that enqueue the same work print the same object.
+
+    python tools/rollout_bits.py [--out FILE]
+"""
+import argparse
+import hashlib
+import itertools
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from lns_amd import config, dropin, filler  # noqa: E402
+
+CASES = ("ns2d_mini", "twophase_cond", "sw_half_periodic")
+B, T = 2, 7
+KEEP = [1, 4, 6]
+CHUNKS = ((0, 4, [1]), (4, 3, [0, 2]))              # (t0, steps, keep_steps of the chunk): KEEP again
+NORM = dict(mean=0.37, std=1.9)
+DECODE_GROUPS = (None, 1, 2, 0)                     # None: never set (it comes first); 0: automatic, here one group of all T steps
+
+
+def sha(t):
+    return hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def setup(name):
+    d = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
+    meta = json.loads(bytes(d["meta"]).decode())
+    args = config.preset(meta["preset"], **meta["overrides"])
+    model = dropin.build_dynamics(args)
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in filler.synthetic_state_dict(shapes, meta["weight_seed"]).items()})
+    model = model.to("cuda:0")
+    seed = meta["input_seed"]
+    x = torch.from_numpy(filler.normal("x", (B, args.in_channels, args.Ly, args.Lx), seed)).cuda()
+    y = torch.from_numpy(filler.normal("y", (B, T, args.in_channels, args.Ly, args.Lx), seed)).cuda()
+    p = torch.from_numpy(filler.uniform01("param", B, seed).astype(np.float32)).cuda() if args.family == "twophase_cond" else None
+    return model._engine(x), x, y, p
+
+
+def entries(eng, x, y, p):
+    z0 = eng.encode(x, p) if eng.cfg.cond_encoder else eng.encode(x)
+    out, lat = eng.rollout(x, T, param=p, return_latents=True)
+    yield "rollout", dict(out=out, latents=lat)
+    yield "rollout_latents_only", dict(out=eng.rollout(x, T, param=p, to_x=False))
+    out, lat = eng.rollout(x, T, param=p, keep_steps=KEEP, return_latents=True)
+    yield "rollout_keep", dict(out=out, latents=lat)
+    out, z = eng.rollout_latent(z0, T, param=p)
+    yield "rollout_latent", dict(out=out, z_last=z)
+    out, z = eng.rollout_latent(z0, T, param=p, keep_steps=KEEP)
+    yield "rollout_latent_keep", dict(out=out, z_last=z)
+    frame, seq, frames = eng.rollout_eval(x, y, param=p, keep_steps=KEEP, **NORM)
+    yield "rollout_eval", dict(frame=frame, seq=seq, frames=frames)
+    frame, seq, frames, z = eng.rollout_latent_eval(z0, y, param=p, keep_steps=KEEP, **NORM)
+    yield "rollout_latent_eval", dict(frame=frame, seq=seq, frames=frames, z_last=z)
+    z, frame, seq, kept = z0, None, None, []
+    for t0, steps, keep in CHUNKS:
+        frame, seq, frames, z = eng.rollout_latent_eval(z, y, steps=steps, t0=t0, param=p, keep_steps=keep, frame=frame, seq=seq, **NORM)
+        kept.append(frames)
+    yield "rollout_latent_eval_4+3", dict(frame=frame, seq=seq, frames=torch.cat(kept, 1), z_last=z)
+
+
+def launches(eng, x, y):
+    calls = (("rollout", lambda: eng.rollout(x, T)), ("rollout_keep", lambda: eng.rollout(x, T, keep_steps=KEEP)),
+             ("rollout_eval", lambda: eng.rollout_eval(x, y, keep_steps=KEEP, **NORM)))
+    rec = {}
+    for name, fn in calls:
+        eng.timing_enable(True)
+        fn()
+        torch.cuda.synchronize()
+        rec["launches/" + name] = {k: v["launches"] for k, v in sorted(eng.timing().items())}
+        eng.timing_enable(False)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rec = {}
+    for case in CASES:
+        eng, x, y, p = setup(case)
+        for dg, ds, ov in itertools.product(DECODE_GROUPS, (1, 2), (0, 1)):
+            for k, v in (("decode_group", dg), ("decode_streams", ds), ("overlap", ov)):
+                if v is not None:
+                    eng.set_option(k, v)
+            for name, tensors in entries(eng, x, y, p):
+                torch.cuda.synchronize()
+                rec["%s/%s/dg%s_ds%d_ov%d" % (case, name, "default" if dg is None else dg, ds, ov)] = {k: sha(t) for k, t in tensors.items()}
+        if case == "ns2d_mini":
+            for k, v in (("decode_group", 1), ("decode_streams", 3), ("overlap", 1)):      # the library's defaults
+                eng.set_option(k, v)
+            rec.update(launches(eng, x, y))
+    text = json.dumps(rec, indent=1, sort_keys=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
