@@ -224,6 +224,37 @@ int lns_rollout_latent_select(lns_engine* e, const float* z_in, const float* par
                               const int* keep_steps_host, int n_keep, float* out, float* z_last,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ensemble rollout: per-step mean and variance over perturbed members ---------------------------------------
+ * The reference trains the propagator with noise on the latent (z_in + randn_like(z_in) * noise_level,
+ * train_stage2_ns2d.py:211-212) so that LatentDynamics.predict (train_stage2_ns2d.py:143-158) tolerates a perturbed
+ * latent; the inference-side use is an ensemble forecast: encode once, perturb the latent M times (the caller's one
+ * torch op, as for training), roll every member out and keep the mean and the spread per step -- without the
+ * [B*M,T,Cin,Ly,Lx] tensor of lns_rollout_latent at batch B*M and without a second pass over it.
+ * The chain runs at batch N = B*M (launch sample b*M + m is member m of trajectory b); the kept steps have the semantics
+ * of lns_rollout_latent_select (a decode group is the next up to "decode_group" kept steps, resolved for N); the decode
+ * of a group writes a per-decode-stream frame buffer [steps][B][M][Cin*Ly*Lx], and a reduction kernel on the same
+ * stream writes mean_out[b][i] and var_out[b][i] before the buffer is reused.  Per element, in fp32, nothing fused:
+ *     s = f[0]; for m = 1 .. M-1: s = s + f[m];   mean = s / (float)M
+ *     d_m = f[m] - mean;  sd = sum_m d_m;  q = sum_m d_m * d_m            (ascending m)
+ *     var = (q - sd * sd / (float)M) / (float)(M - 1)                     (unbiased; corrected two-pass form)
+ * so a result depends on its M member values only, never on the scheduling options; f[m] are the bits lns_rollout_latent
+ * at batch B*M writes for sample b*M + m.  M = 1: mean is the rollout itself, var_out must be NULL.
+ * There is no from-x form and no device random numbers: encoding is one lns_encode call, the noise the caller's.
+ * param, batch limits (on B*M), trace / timing modes (single stream) and lns_check_finite (with B*M): as for lns_rollout.
+ * LNS_EINVAL (bad argument, named by lns_last_error; decided before any device work), LNS_ENOMEM (workspace smaller than
+ * lns_rollout_ensemble_workspace_bytes; nothing is enqueued), LNS_ESTATE (no autoencoder / propagator).
+ *
+ * Workspace for (B, M), N = B*M: the lns_prepare(N) layout, byte for byte (lns_prepare and the sizes the other run calls
+ * need do not change), followed by two regions, each rounded up to 256 bytes: the two latent buffers of
+ * lns_rollout_select_workspace_bytes(N), then "decode_streams" frame buffers of decode_group * N * Cin * Ly * Lx * 4
+ * bytes (decode_group as resolved for N when the option is 0). */
+int lns_rollout_ensemble_workspace_bytes(lns_engine* e, int B, int M, size_t* bytes);
+/* z_in [B][M][zper]; param [B][M] (one value per MEMBER: a parameter ensemble is the same call) or NULL;
+ * mean_out, var_out (nullable) [B][n_keep][Cin][Ly][Lx]; z_last (nullable) [B][M][zper]; keep_steps_host as lns_rollout_latent_select */
+int lns_rollout_latent_ensemble(lns_engine* e, const float* z_in, const float* param, int B, int M, int T,
+                                const int* keep_steps_host, int n_keep, float* mean_out, float* var_out, float* z_last,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- streaming validation rollout: predict and score without the [B,T] field ---------------------------------
  * Reference: the body of the validation loop, train_stage2_ns2d.py:249-263 (same text in train_stage2_SW.py and
  * train_stage2_twophase*.py, where denormalize is the per-channel / closed-wall / clamp form):
@@ -465,7 +496,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * forms behind op-level variants 15 / 16 / 18 / 19 exist; the shipped library does not carry them); "train_wgrad_split" = the
  * batch-parallel weight gradient (option "train_wgrad", lns_op_conv_wgrad) is there; "train_clip" = lns_train_step_clip and
  * the gradient-norm / update calls are there; "train_ops" = lns_op_groupnorm_train, lns_op_gelu_grad and lns_op_bias_grad
- * are there; "rollout_select" = lns_rollout_select & co. are there.  1 / 0; -1: unknown name.
+ * are there; "rollout_select" = lns_rollout_select & co. are there; "rollout_ensemble" = lns_rollout_latent_ensemble,
+ * its size query and lns_op_ensemble_stats are there.  1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
 
@@ -525,6 +557,13 @@ int lns_op_groupnorm_train(const float* x, int B, int C, int HW, int groups, flo
 int lns_op_gelu_grad(const float* dy, const float* u, float* du, int64_t n, void* stream);
 /* db[c] (+)= sum_b sum_p dy[b][c][p], dy [B,C,HW]; one fixed summation order: bit-reproducible. */
 int lns_op_bias_grad(const float* dy, int B, int C, int HW, float* db, int accumulate, void* stream);
+
+/* The reduction kernel of lns_rollout_latent_ensemble on its own: frames [B][M][per] -> mean [B][per] and var [B][per]
+ * (nullable; var != NULL with M < 2 is LNS_EINVAL) by the statement written there.  16-byte accesses when the three
+ * pointers are 16-byte aligned and per is a multiple of 4, one element at a time otherwise: the bits do not depend on it.
+ * B in 1..65535, M in 1..65536, per in 1..2^40.  Checks precede the launch (message: lns_create_error()); the call
+ * synchronises `stream`. */
+int lns_op_ensemble_stats(const float* frames, int B, int M, int64_t per, float* mean, float* var /* nullable */, void* stream);
 
 /* GroupNorm statistics -> per-(b,c) (scale,shift) such that norm(x) = x*scale+shift. */
 int lns_op_groupnorm_stats(const float* x, int B, int C, int HW, int groups, float eps,

@@ -1824,7 +1824,10 @@ struct Runner {
 //   SINK_KEPT     the steps keep[0 .. n_keep) decoded into `out` [B][n_keep][xper]; the chain still runs all T steps
 //   SINK_SCORED   every step decoded into a frame buffer of the workspace and scored against y_true right there; the frames
 //                 of the steps keep[0 .. n_keep) are copied to frames_out
-enum SinkKind { SINK_LATENTS, SINK_STEPS, SINK_KEPT, SINK_SCORED };
+//   SINK_ENSEMBLE the chain runs at batch N = B * M (launch sample b * M + m is member m of trajectory b); the steps
+//                 keep[0 .. n_keep) are decoded into a frame buffer of the workspace and reduced over the members right there
+//                 into `out` (mean) and `var_out` [B][n_keep][xper]
+enum SinkKind { SINK_LATENTS, SINK_STEPS, SINK_KEPT, SINK_SCORED, SINK_ENSEMBLE };
 
 // workspace layout: [ z0 | latent ring: NGROUP groups x kdec steps x [B][zper] | NDEC decode arenas | propagator arena ]
 // The propagator gets its own arena because it runs on a second stream, concurrently with decode.
@@ -1833,15 +1836,16 @@ enum SinkKind { SINK_LATENTS, SINK_STEPS, SINK_KEPT, SINK_SCORED };
 // 32x32 decoder layers, a quarter of the launches, weight slabs amortised).  A trajectory-step's arithmetic does not
 // depend on the batch it rides in (kernel accumulation order is a function of the layer only), so the result is
 // bit-identical for every kdec.
-// Behind it, from round_up(that layout's total, 256) on, the one region the sink needs (never both):
+// Behind it, from round_up(that layout's total, 256) on, the region the sink needs (kept and frame regions for the ensemble sink):
 //   SINK_SCORED  one frame buffer per decode stream (the decode output of a group, [kdec][B][C][Ly][Lx]), then the
 //                metric's per-plane sums [B][eval_max_steps][C][2]
 //   SINK_KEPT    two latent buffers [B][zper] that take the latents of the steps nobody decodes
+//   SINK_ENSEMBLE  (B = N) the two latent buffers of SINK_KEPT, then the frame buffers of SINK_SCORED
 enum { NDEC = 4, NGROUP_MAX = NDEC + 2 };   // max decode streams; latent groups in flight
 struct WsLayout {
     size_t z_bytes, ring_off, group_bytes, arena_off, arena_stride, prop_off, total; int ndec, kdec, ngroup;
-    size_t fbuf_off, fbuf_stride, part_off;   // SINK_SCORED
-    size_t pp_off[2];                         // SINK_KEPT
+    size_t fbuf_off, fbuf_stride, part_off;   // SINK_SCORED; SINK_ENSEMBLE (no part)
+    size_t pp_off[2];                         // SINK_KEPT, SINK_ENSEMBLE
 };
 
 static int decode_group(const lns_engine* e, int B) {
@@ -1882,29 +1886,36 @@ static int ws_layout(lns_engine* e, int B, SinkKind sink, WsLayout* L) {
     L->prop_off = L->arena_off + (size_t)L->ndec * L->arena_stride;
     L->total = L->prop_off + round_up_sz(parena, 256) + 256;
     L->fbuf_off = L->fbuf_stride = L->part_off = L->pp_off[0] = L->pp_off[1] = 0;
-    if (sink == SINK_SCORED) {
-        const size_t xper = (size_t)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx;
-        L->fbuf_off = round_up_sz(L->total, 256);
-        L->fbuf_stride = round_up_sz((size_t)L->kdec * B * xper * 4, 256);
-        L->part_off = L->fbuf_off + (size_t)L->ndec * L->fbuf_stride;
-        L->total = L->part_off + round_up_sz((size_t)B * e->opt_eval_max_steps * e->cfg.in_channels * 2 * 4, 256);
-    } else if (sink == SINK_KEPT) {
+    if (sink == SINK_KEPT || sink == SINK_ENSEMBLE) {
         L->pp_off[0] = round_up_sz(L->total, 256);
         L->pp_off[1] = L->pp_off[0] + L->z_bytes;                     // (z_bytes is a multiple of 256)
         L->total = L->pp_off[1] + L->z_bytes;
     }
+    if (sink == SINK_SCORED || sink == SINK_ENSEMBLE) {
+        const size_t xper = (size_t)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx;
+        L->fbuf_off = round_up_sz(L->total, 256);
+        L->fbuf_stride = round_up_sz((size_t)L->kdec * B * xper * 4, 256);
+        L->total = L->fbuf_off + (size_t)L->ndec * L->fbuf_stride;
+    }
+    if (sink == SINK_SCORED) {
+        L->part_off = L->total;
+        L->total = L->part_off + round_up_sz((size_t)B * e->opt_eval_max_steps * e->cfg.in_channels * 2 * 4, 256);
+    }
     return LNS_OK;
 }
 
-// One rollout call, as the six entry points (lns_rollout, lns_rollout_latent and their _eval / _select forms) describe it
+// One rollout call, as the entry points (lns_rollout, lns_rollout_latent, their _eval / _select forms and
+// lns_rollout_latent_ensemble) describe it
 struct RolloutCall {
     RolloutCall(const float* start_, bool encode_, const float* param_, int B_, int T_, void* ws_, size_t ws_bytes_, void* stream_)
         : start(start_), encode(encode_), param(param_), B(B_), T(T_), ws(ws_), ws_bytes(ws_bytes_), stream(stream_) {}
     const float* start = nullptr; bool encode = false;   // x [B][xper], encoded into z0 first, or the latent z_in [B][zper]
     const float* param = nullptr; int B = 0, T = 0;
     SinkKind sink = SINK_STEPS;
-    float* out = nullptr;                                // every sink but SINK_SCORED
-    const int* keep = nullptr; int n_keep = 0;           // SINK_KEPT (n_keep >= 1), SINK_SCORED (n_keep >= 0); host, ascending
+    float* out = nullptr;                                // every sink but SINK_SCORED (SINK_ENSEMBLE: the mean)
+    const int* keep = nullptr; int n_keep = 0;           // SINK_KEPT, SINK_ENSEMBLE (n_keep >= 1), SINK_SCORED (n_keep >= 0); host, ascending
+    // SINK_ENSEMBLE: B above is the chain's batch N = traj * M (clipped to int; 0 when either factor is not positive)
+    int traj = 0, M = 0; float* var_out = nullptr;
     // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
     const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
     float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
@@ -2126,7 +2137,19 @@ int lns_prepare(lns_engine* e, int B, size_t* bytes) { return workspace_bytes(e,
 int lns_rollout_eval_workspace_bytes(lns_engine* e, int B, size_t* bytes) { return workspace_bytes(e, B, SINK_SCORED, bytes); }
 int lns_rollout_select_workspace_bytes(lns_engine* e, int B, size_t* bytes) { return workspace_bytes(e, B, SINK_KEPT, bytes); }
 
-// label: "" / "evaluation " / "selection " (what the workspace was sized for)
+// the chain's batch of an ensemble call: B * M, clipped so that check_batch names the product
+static int ensemble_batch(int B, int M) {
+    if (B <= 0 || M <= 0) return 0;
+    return (int)std::min<long long>((long long)B * M, 0x7fffffffLL);
+}
+int lns_rollout_ensemble_workspace_bytes(lns_engine* e, int B, int M, size_t* bytes) {
+    if (!e) return LNS_EINVAL;
+    if (B <= 0) return einval(e, "B must be positive");
+    if (M <= 0) return einval(e, "M must be positive");
+    return workspace_bytes(e, ensemble_batch(B, M), SINK_ENSEMBLE, bytes);
+}
+
+// label: "" / "evaluation " / "selection " / "ensemble " (what the workspace was sized for)
 static int check_ws(lns_engine* e, const WsLayout& L, const char* label, void* ws, size_t bytes) {
     if (!ws || bytes < L.total) { e->err = fmt("%sworkspace too small: need %zu bytes, got %zu", label, L.total, bytes); return LNS_ENOMEM; }
     return LNS_OK;
@@ -2248,6 +2271,8 @@ static void metric_args(const lns_engine* e, const RolloutCall& c, const WsLayou
 // the copies of the kept steps follow on the same decode stream -- in stream order before the next decode that reuses
 // the buffer, so the event scheme is the rollout's own.
 // SINK_KEPT: the chain still runs all T steps, the decoder runs for the kept ones only.
+// SINK_ENSEMBLE: SINK_KEPT at batch N = B * M whose decode writes the decode stream's frame buffer as SINK_SCORED's does;
+// the reduction over the members follows on the same decode stream and writes mean / var of out[b][i0 + j].
 // SINK_LATENTS: no step is decoded, so there is no group, no side stream and no event: every step is "a step nobody
 // decodes", whose latent goes straight into `out` on the caller's stream.
 static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& c, const WsLayout& L) {
@@ -2257,7 +2282,8 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     if ((rc = get_plan(e, PK_PROP, B, e->lat_H, e->lat_W, &pp))) return rc;
     const long zper = (long)e->lat_C * e->lat_H * e->lat_W;
     const long xper = (long)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx;
-    const bool scored = c.sink == SINK_SCORED, kept = c.sink == SINK_KEPT, latents = c.sink == SINK_LATENTS;
+    const bool scored = c.sink == SINK_SCORED, ens = c.sink == SINK_ENSEMBLE, kept = c.sink == SINK_KEPT || ens;
+    const bool latents = c.sink == SINK_LATENTS;
     char* base = static_cast<char*>(c.ws);
     char* arena = base + L.arena_off;
     char* parena = base + L.prop_off;
@@ -2294,7 +2320,7 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     if (scored) metric_args(e, c, L, &m);
     // A decode group is the next up to kdec DECODED steps: all steps, the kept ones, or none.  The chain writes the
     // latent of a decoded step into the group's next ring slot; the latent of a step nobody decodes goes into `out`
-    // (SINK_LATENTS) or into the two ping-pong buffers in turn (SINK_KEPT), so a step never writes the buffer it reads.
+    // (SINK_LATENTS) or into the two ping-pong buffers in turn (SINK_KEPT, SINK_ENSEMBLE), so a step never writes the buffer it reads.
     const int n_dec = latents ? 0 : (kept ? c.n_keep : T);   // decoded steps; a decoded `out` is [B][n_dec]
     auto dec_step = [&](int i) { return kept ? c.keep[i] : i; };
     int npp = 0;                                     // the ping-pong buffer the next skipped step writes
@@ -2339,8 +2365,8 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
             HIPCHK(e, hipStreamWaitEvent(dstream[d], ev_z[g], 0));
         }
         ext[EX_IN] = {gbase, zper};
-        float* fb = scored ? reinterpret_cast<float*>(base + L.fbuf_off + (size_t)d * L.fbuf_stride) : nullptr;
-        if (scored) ext[EX_OUT] = {fb, xper};        // [kk][B][xper]: launch sample s = j * B + b
+        float* fb = scored || ens ? reinterpret_cast<float*>(base + L.fbuf_off + (size_t)d * L.fbuf_stride) : nullptr;
+        if (fb) ext[EX_OUT] = {fb, xper};            // [kk][B][xper]: launch sample s = j * B + b
         else ext[EX_OUT] = {c.out + (long)i0 * xper, (long)n_dec * xper, xper, B};
         if ((rc = (overlap ? rd[d] : r).run(*pd, ext, darena[d]))) return rc;
         if (scored) {                                // (every step is decoded: t0g == i0)
@@ -2350,6 +2376,12 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
                 HIPCHK(e, hipMemcpy2DAsync(c.frames_out + (long)ki * xper, (size_t)c.n_keep * xper * 4,
                                            fb + (long)(c.keep[ki] - t0g) * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
                                            hipMemcpyDeviceToDevice, dstream[d]));
+        }
+        if (ens) {                                   // fb is [kk][traj][M][xper] -> mean / var of out[b][i0 .. i0 + kk)
+            EnsembleStatsArgs es;
+            es.frames = fb; es.mean = c.out + (long)i0 * xper; es.var = c.var_out ? c.var_out + (long)i0 * xper : nullptr;
+            es.per = xper; es.out_bs = (long)n_dec * xper; es.B = c.traj; es.M = c.M; es.kk = kk;
+            HIPCHK(e, launch_ensemble_stats(es, dstream[d]));
         }
         if (overlap) { HIPCHK(e, hipEventRecord(ev_free[g], dstream[d])); used[g] = 1; }
         i0 += kk;
@@ -2385,12 +2417,14 @@ static int check_keep_steps(lns_engine* e, const int* keep, int n_keep, int T) {
 // every refusal of a rollout call that needs no plan: nothing here touches the device.  The order is part of the
 // interface (which of two failing checks answers): arguments, batch, eval_max_steps, the model, param.
 static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
-    const bool scored = c.sink == SINK_SCORED, kept = c.sink == SINK_KEPT;
+    const bool scored = c.sink == SINK_SCORED, ens = c.sink == SINK_ENSEMBLE, kept = c.sink == SINK_KEPT || ens;
     if (!c.start) return einval(e, c.encode ? "x is null" : "z_in is null");
     if (scored && !c.y_true) return einval(e, "y_true is null");
-    if (!scored && !c.out) return einval(e, "out is null");
-    if (c.B <= 0) return einval(e, "B must be positive");
+    if (!scored && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
+    if ((ens ? c.traj : c.B) <= 0) return einval(e, "B must be positive");
+    if (ens && c.M <= 0) return einval(e, "M must be positive");
     if (c.T <= 0) return einval(e, "T must be positive");
+    if (ens && c.var_out && c.M < 2) return einval(e, "var_out needs M >= 2");
     if (scored) {
         if (c.t0 < 0 || (long)c.t0 + c.T > c.T_total) {
             e->err = fmt("t0 + T = %d + %d exceeds T_total = %d (or t0 < 0)", c.t0, c.T, c.T_total);
@@ -2416,7 +2450,7 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
     return need_param(e, c.encode, c.param);
 }
 
-// the one call path behind the six rollout entry points
+// the one call path behind the rollout entry points
 static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if (!e) return LNS_EINVAL;
     int rc;
@@ -2425,7 +2459,8 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     DeviceGuard dg(e);
     WsLayout L;
     if ((rc = ws_layout(e, c.B, c.sink, &L)) ||
-        (rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : ""), c.ws, c.ws_bytes))) return rc;
+        (rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : (c.sink == SINK_ENSEMBLE ? "ensemble " : "")),
+                       c.ws, c.ws_bytes))) return rc;
     Plan* pe = nullptr;
     if (c.encode && (rc = get_plan(e, PK_ENC, c.B, 0, 0, &pe))) return rc;
     const lns_config& cfg = e->cfg;
@@ -2505,6 +2540,16 @@ int lns_rollout_latent_select(lns_engine* e, const float* z_in, const float* par
                               void* stream) {
     RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
     c.sink = SINK_KEPT; c.keep = keep_steps_host; c.n_keep = n_keep; c.out = out; c.z_last = z_last;
+    return rollout_call(e, c);
+}
+
+// ---- ensemble rollout (include/lns.h) --------------------------------------------------------------------------
+int lns_rollout_latent_ensemble(lns_engine* e, const float* z_in, const float* param, int B, int M, int T,
+                                const int* keep_steps_host, int n_keep, float* mean_out, float* var_out, float* z_last,
+                                void* ws, size_t ws_bytes, void* stream) {
+    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
+    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
+    c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
     return rollout_call(e, c);
 }
 
@@ -2600,6 +2645,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "train_clip")) return 1;
     if (!strcmp(feature, "train_ops")) return 1;
     if (!strcmp(feature, "rollout_select")) return 1;
+    if (!strcmp(feature, "rollout_ensemble")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else
@@ -2865,6 +2911,21 @@ int lns_op_conv_pair_stress(int B, int H, int W, int cin_a, int cout_a, int ksiz
     }
     if (mismatches_a) *mismatches_a = bad[0];
     if (mismatches_b) *mismatches_b = bad[1];
+    return LNS_OK;
+}
+
+// ensemble_stats_kernel on its own: frames [B][M][per] -> mean [B][per], var [B][per] (nullable)
+int lns_op_ensemble_stats(const float* frames, int B, int M, int64_t per, float* mean, float* var, void* stream) {
+    if (!frames || !mean) { g_create_error = "ensemble_stats: frames / mean is null"; return LNS_EINVAL; }
+    if (B < 1 || B > LNS_MAX_BATCH || M < 1 || M > 65536 || per < 1 || per > ((int64_t)1 << 40)) {
+        g_create_error = "ensemble_stats: B in 1..65535, M in 1..65536, per in 1..2^40"; return LNS_EINVAL;
+    }
+    if (var && M < 2) { g_create_error = "ensemble_stats: var needs M >= 2"; return LNS_EINVAL; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EnsembleStatsArgs a;
+    a.frames = frames; a.mean = mean; a.var = var; a.per = (long)per; a.out_bs = (long)per; a.B = B; a.M = M; a.kk = 1;
+    OPCHK(launch_ensemble_stats(a, s));
+    OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
 }
 

@@ -335,6 +335,14 @@ struct MetricGroupArgs {
 hipError_t launch_metric_group(const MetricGroupArgs& a, hipStream_t s);
 hipError_t launch_metric_finish(const float* part, int B, int T, int C, float eps, float* frame_out, float* seq_out, hipStream_t s);
 
+// Ensemble rollout (lns_rollout_latent_ensemble): member frames [kk][B][M][per] (the decode output of one group of kept
+// steps) -> mean, var (nullable) over the M members; row (b, j) of either goes to out + b * out_bs + j * per, so the engine
+// writes out[b][i0 + j] of a [B][n_keep][per] tensor directly.  Per element, fp32, nothing fused, ascending m:
+//   s = f[0] + f[1] + ...;  mean = s / M;  d_m = f[m] - mean;  sd = sum d_m;  q = sum d_m * d_m;
+//   var = (q - sd * sd / M) / (M - 1)        (unbiased; the corrected two-pass form of gn_train_fwd_kernel)
+struct EnsembleStatsArgs { const float* frames; float* mean; float* var; long per, out_bs; int B, M, kk; };
+hipError_t launch_ensemble_stats(const EnsembleStatsArgs& a, hipStream_t s);
+
 // per-sample max |x| (bit patterns) of a [B, n] tensor with batch stride x_bs into amax [B][LNS_AMAX_SUB] (atomic max)
 hipError_t launch_amax(const float* x, long x_bs, long n, int B, unsigned* amax, hipStream_t s);
 hipError_t launch_amax_sticky(const unsigned* amax, int n, unsigned* flag, hipStream_t s);

@@ -5048,6 +5048,81 @@ hipError_t launch_metric_finish(const float* part, int B, int T, int C, float ep
     return hipGetLastError();
 }
 
+// ---- ensemble statistics (lns_kernels.h EnsembleStatsArgs) ------------------------------------------------------------
+// A thread owns four consecutive elements of one (step j, trajectory b) row and walks the M member rows twice (the
+// second pass hits the cache: a block's 4 KB of every member row).  float4 accesses when every row starts on a 16-byte
+// boundary (pointers, per and out_bs multiples of four floats: `vec`); otherwise, and for a tail, the same elements one
+// by one.  An element's result depends on its M inputs only, in the order written in lns_kernels.h.
+template <bool VEC>
+__device__ __forceinline__ float4 ens_load(const float* p, int nv) {
+    if (VEC) return *reinterpret_cast<const float4*>(p);
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    v.x = p[0];
+    if (nv > 1) v.y = p[1];
+    if (nv > 2) v.z = p[2];
+    if (nv > 3) v.w = p[3];
+    return v;
+}
+template <bool VEC>
+__device__ __forceinline__ void ens_store(float* p, const float4& v, int nv) {
+    if (VEC) { *reinterpret_cast<float4*>(p) = v; return; }
+    p[0] = v.x;
+    if (nv > 1) p[1] = v.y;
+    if (nv > 2) p[2] = v.z;
+    if (nv > 3) p[3] = v.w;
+}
+
+// products and sums are rounded one by one (hipcc contracts device code by default and honours this pragma): d * d must
+// not be fused into the sum of squares, nor sd * sd / M into the subtraction
+template <bool VEC>
+__device__ __forceinline__ void ensemble_stats_body(const float* f, long per, int M, float* mean, float* var, int nv) {
+#pragma clang fp contract(off)
+    const float fm = (float)M;
+    float4 s = ens_load<VEC>(f, nv);
+#pragma unroll 4
+    for (int m = 1; m < M; ++m) {
+        const float4 v = ens_load<VEC>(f + (long)m * per, nv);
+        s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
+    }
+    const float4 mu = make_float4(s.x / fm, s.y / fm, s.z / fm, s.w / fm);
+    ens_store<VEC>(mean, mu, nv);
+    if (!var) return;
+    float4 sd = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q = sd;
+#pragma unroll 4
+    for (int m = 0; m < M; ++m) {
+        const float4 v = ens_load<VEC>(f + (long)m * per, nv);
+        const float dx = v.x - mu.x, dy = v.y - mu.y, dz = v.z - mu.z, dw = v.w - mu.w;
+        const float px = dx * dx, py = dy * dy, pz = dz * dz, pw = dw * dw;
+        sd.x = sd.x + dx; sd.y = sd.y + dy; sd.z = sd.z + dz; sd.w = sd.w + dw;
+        q.x = q.x + px; q.y = q.y + py; q.z = q.z + pz; q.w = q.w + pw;
+    }
+    const float fm1 = (float)(M - 1);
+    float4 r;
+    { const float c = sd.x * sd.x; const float k = c / fm; const float n = q.x - k; r.x = n / fm1; }
+    { const float c = sd.y * sd.y; const float k = c / fm; const float n = q.y - k; r.y = n / fm1; }
+    { const float c = sd.z * sd.z; const float k = c / fm; const float n = q.z - k; r.z = n / fm1; }
+    { const float c = sd.w * sd.w; const float k = c / fm; const float n = q.w - k; r.w = n / fm1; }
+    ens_store<VEC>(var, r, nv);
+}
+
+__global__ __launch_bounds__(256) void ensemble_stats_kernel(EnsembleStatsArgs a, int vec) {
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= a.per) return;
+    const int b = blockIdx.y, j = blockIdx.z;
+    const float* f = a.frames + ((long)j * a.B + b) * a.M * a.per + i;
+    const long o = (long)b * a.out_bs + (long)j * a.per + i;
+    const int nv = a.per - i < 4 ? (int)(a.per - i) : 4;
+    if (vec && nv == 4) ensemble_stats_body<true>(f, a.per, a.M, a.mean + o, a.var ? a.var + o : nullptr, nv);
+    else ensemble_stats_body<false>(f, a.per, a.M, a.mean + o, a.var ? a.var + o : nullptr, nv);
+}
+
+hipError_t launch_ensemble_stats(const EnsembleStatsArgs& a, hipStream_t s) {
+    const int vec = ((reinterpret_cast<uintptr_t>(a.frames) | reinterpret_cast<uintptr_t>(a.mean) | reinterpret_cast<uintptr_t>(a.var)) & 15) == 0 &&
+                    a.per % 4 == 0 && a.out_bs % 4 == 0;
+    hipLaunchKernelGGL(ensemble_stats_kernel, dim3((unsigned)((a.per + 1023) / 1024), a.B, a.kk), dim3(256), 0, s, a, vec);
+    return hipGetLastError();
+}
+
 // per-sample max |x| of a [B, n] tensor: grid (chunks, B); one atomic per wave
 __global__ __launch_bounds__(256) void amax_kernel(const float* x, long x_bs, long n, unsigned* amax) {
     const int b = blockIdx.y;

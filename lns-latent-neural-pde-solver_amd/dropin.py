@@ -449,6 +449,35 @@ class LatentDynamics(_Hosted):
         return self._engine(x).rollout(x, steps, param=param, to_x=to_x, return_latents=return_latents, keep_steps=keep_steps)
 
     @torch.no_grad()
+    def predict_ensemble(self, x, steps, *rest, generator=None, control=True, keep_steps=None, return_var=True):
+        """predict_ensemble(x, steps, members, noise_level) -- conditional: predict_ensemble(x, steps, param, members,
+        noise_level): an ensemble forecast from the robustness the stage-2 training buys with its latent noise
+        (z_in + randn_like(z_in) * noise_level, train_stage2_ns2d.py:211-212).  Encodes x once, perturbs the latent
+        `members` times -- z[b, m] = z0[b] + randn * noise_level, member 0 left as z0 under control=True -- rolls every
+        member out and returns the per-step mean, or (mean, var) with the unbiased variance over the members, of the
+        decoded fields [B, n_keep, C, Ly, Lx]; the members' own fields are never stored.  generator: a torch.Generator on
+        x's device for the noise.  param: [B] (shared by a trajectory's members) or [B, members].  keep_steps as for predict."""
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("predict_ensemble() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if len(rest) != 2:
+            raise TypeError("predict_ensemble() takes (x, steps, param, members, noise_level)" if self._conditional
+                            else "predict_ensemble() takes (x, steps, members, noise_level)")
+        members, noise_level = int(rest[0]), float(rest[1])
+        if members < 1:
+            raise LnsError("members must be at least 1, got %d" % members)
+        x = self._fields(x)
+        z0 = self.x_to_z(x)
+        B, c, h, w = z0.shape
+        eps = torch.randn((B, members, c, h, w), device=z0.device, dtype=z0.dtype, generator=generator) * noise_level
+        z = z0[:, None] + eps
+        if control:
+            z[:, 0] = z0
+        return self._engine(z).rollout_latent_ensemble(z, steps, param=param, keep_steps=keep_steps, return_var=return_var)
+
+    @torch.no_grad()
     def validate(self, x, y, *rest, keep_steps=(), **norm):
         """validate(x, y, **norm) -- conditional: validate(x, y, param, **norm): the body of the reference's validation
         loop (train_stage2_ns2d.py:249-263) in one call,

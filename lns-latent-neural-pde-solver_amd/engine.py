@@ -448,6 +448,71 @@ class Engine:
         as for `rollout`): out is [B, n_keep, C, Ly, Lx]."""
         return self._rollout_call(self._dev(z), False, steps, param, to_x, out, keep_steps, True)
 
+    # -- ensemble rollout (include/lns.h "ensemble rollout") -------------------------------------------------------
+    def rollout_latent_ensemble(self, z, steps, param=None, keep_steps=None, return_var=True, return_last=False, out=None):
+        """z [B, M, c, h, w]: M perturbed members of each of B trajectories (the noise is the caller's, as in training).
+        Rolls every member out and returns, per kept step, the mean and the unbiased variance over the members
+        [B, n_keep, C, Ly, Lx] without storing the members' fields: `mean`, or `(mean, var)`, with `z_last` [B, M, c, h, w]
+        appended under return_last.  keep_steps as for `rollout` (None: every step).  param: one value per trajectory
+        [B] (broadcast over the members) or per member [B, M].  M = 1 has no variance: return_var=False.  out: a
+        preallocated mean.  The workspace is the one of batch B * M: `check_finite(B * M)` covers the call."""
+        import torch
+        z = self._dev(z)
+        C, H, W = self.latent_shape()
+        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
+            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
+        B, M = int(z.shape[0]), int(z.shape[1])
+        if return_var and M < 2:
+            raise LnsError("the variance needs at least 2 members, got M = %d (return_var=False for the mean alone)" % M)
+        steps = int(steps)
+        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
+        arr = (ctypes.c_int * len(keep))(*keep)
+        c = self.cfg
+        shape = (B, len(keep), c.in_channels, c.Ly, c.Lx)
+        mean = self._out(out, shape, z.device)
+        var = torch.empty(shape, dtype=torch.float32, device=z.device) if return_var else None
+        z_last = torch.empty_like(z) if return_last else None
+        p = None
+        if param is not None:
+            p = torch.as_tensor(param)
+            if p.device != z.device:
+                raise LnsError("param is on %s but the latents are on %s" % (p.device, z.device))
+            if p.numel() == B:
+                p = p.reshape(B, 1).expand(B, M)
+            elif p.numel() != B * M:
+                raise LnsError("param must hold one value per trajectory or per member: got %d values for B = %d, M = %d"
+                               % (p.numel(), B, M))
+            p = p.reshape(B, M).to(torch.float32).contiguous()
+        with torch.cuda.device(z.device):
+            n = ctypes.c_size_t(0)
+            self._check(self._L.lns_rollout_ensemble_workspace_bytes(self._h, B, M, ctypes.byref(n)),
+                        "lns_rollout_ensemble_workspace_bytes")
+            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+            self._check(self._L.lns_rollout_latent_ensemble(self._h, z.data_ptr(), self._ptr(p), B, M, steps, arr, len(keep),
+                                                            mean.data_ptr(), self._ptr(var), self._ptr(z_last), ws.data_ptr(),
+                                                            ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble")
+        res = (mean,) + ((var,) if return_var else ()) + ((z_last,) if return_last else ())
+        return res[0] if len(res) == 1 else res
+
+    def ensemble_stats(self, frames, return_var=True):
+        """The reduction kernel of the ensemble rollout on its own: frames [B, M, ...] -> mean [B, ...] or (mean, var)
+        (unbiased, over dim 1) in the fixed order documented in include/lns.h (lns_op_ensemble_stats)."""
+        import torch
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.float32 or frames.dim() < 2:
+            raise LnsError("ensemble_stats takes an fp32 HIP tensor [B, M, ...]")
+        if not frames.is_contiguous():
+            frames = frames.contiguous()
+        B, M = int(frames.shape[0]), int(frames.shape[1])
+        per = frames[0, 0].numel() if frames.dim() > 2 else 1
+        shape = (B,) + tuple(frames.shape[2:])
+        mean = torch.empty(shape, dtype=torch.float32, device=frames.device)
+        var = torch.empty(shape, dtype=torch.float32, device=frames.device) if return_var else None
+        with torch.cuda.device(frames.device):
+            rc = self._L.lns_op_ensemble_stats(frames.data_ptr(), B, M, per, mean.data_ptr(), self._ptr(var), self._stream(frames))
+        if rc != 0:
+            raise LnsError("lns_op_ensemble_stats failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return (mean, var) if return_var else mean
+
     # -- streaming validation rollout (include/lns.h "streaming validation rollout") --------------------------------
     def _eval_common(self, first, y, steps, t0, keep_steps, norm):
         """Shared argument handling of rollout_eval / rollout_latent_eval -> (y, B, T, T_total, spec, keep array, frames)."""

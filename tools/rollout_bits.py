@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """What do the rollout entry points enqueue?  One JSON object: "case/entry/options" -> {output tensor: sha256 of its
 bytes} for every rollout entry point of `Engine` (rollout, rollout with to_x=False, rollout with keep_steps,
-rollout_latent, rollout_latent with keep_steps, rollout_eval, rollout_latent_eval in one chunk and in two, 4 + 3) under
+rollout_latent, rollout_latent with keep_steps, rollout_eval, rollout_latent_eval in one chunk and in two, 4 + 3,
+rollout_latent_ensemble with M = 3 members where the library has it) under
 decode_group {default, 1, 2, automatic} x decode_streams {1, 2} x overlap {0, 1}, at B = 2, T = 7 (decode_group = 2: a ragged last
 group), keep_steps = [1, 4, 6], on the shapes of the ns2d_mini, twophase_cond and sw_half_periodic fixtures with inputs
 from `filler`; plus "launches/<call>" -> {kernel class: launches} of one rollout, one rollout(keep_steps=...) and one
@@ -29,6 +30,7 @@ B, T = 2, 7
 KEEP = [1, 4, 6]
 CHUNKS = ((0, 4, [1]), (4, 3, [0, 2]))              # (t0, steps, keep_steps of the chunk): KEEP again
 NORM = dict(mean=0.37, std=1.9)
+MEMBERS, NOISE = 3, 0.05                            # rollout_latent_ensemble: z0 + NOISE * filler.normal per member
 DECODE_GROUPS = (None, 1, 2, 0)                     # None: never set (it comes first); 0: automatic, here one group of all T steps
 
 
@@ -71,6 +73,11 @@ def entries(eng, x, y, p):
         frame, seq, frames, z = eng.rollout_latent_eval(z, y, steps=steps, t0=t0, param=p, keep_steps=keep, frame=frame, seq=seq, **NORM)
         kept.append(frames)
     yield "rollout_latent_eval_4+3", dict(frame=frame, seq=seq, frames=torch.cat(kept, 1), z_last=z)
+    if eng._L.lns_build_has(b"rollout_ensemble") == 1:           # (absent from a build that predates the entry point)
+        noise = torch.from_numpy(filler.normal("ens", (B, MEMBERS) + tuple(z0.shape[1:]), 3)).cuda()
+        ze = (z0[:, None] + NOISE * noise).contiguous()
+        mean, var, z = eng.rollout_latent_ensemble(ze, T, param=p, keep_steps=KEEP, return_last=True)
+        yield "rollout_latent_ensemble", dict(mean=mean, var=var, z_last=z)
 
 
 def launches(eng, x, y):
