@@ -152,11 +152,18 @@ int lns_finalize_weights(lns_engine* e, int device);
  *                     (no atomics: bit-reproducible for a shape; the gradient differs from form 0 by the summation order only).
  *                     With 1 the training workspaces grow by one partial-sum area (see lns_train_workspace_bytes); any other
  *                     value: LNS_EINVAL.
- * One option selects an ARITHMETIC FORM (results differ at rounding level, ~2e-7 relative on the decoded field):
+ * Two options select an ARITHMETIC FORM (results differ at rounding level, ~2e-7 relative on the decoded field):
  *   "fa_fused"        2 (default; LNS_FA_FUSED): FABlock2D on 64 x 64 planes with 64 channels and on 32 x 32 planes with 128
  *                     channels computes in_proj inside the sandwich kernel (csrc/fa_fused.inc) -- the heads * dim_head plane tensor
  *                     is never stored; 1 / 3: other forms of the 64 x 64 kernel (single-buffered band image / the generic kernel:
  *                     same bits as 2, slower); 0: in_proj as its own 1x1 convolution, then the sandwich.  Cached plans are rebuilt.
+ *   "fold_linear"     1 (default; LNS_NO_FOLD_LINEAR=1 in the environment makes it 0): a convolution directly followed by a 1x1
+ *                     convolution -- no norm, activation or residual between them -- runs as ONE convolution on weights composed
+ *                     when the weights are finalized (W' = W2 W1, b' = W2 b1 + b2; csrc/lns_fold.h): the decoder's output layer
+ *                     3x3 -> 1x1 and post_quant_conv -> decoder.model.0 of the square autoencoder, the encoder's last
+ *                     1x1 -> quant_conv.  The parameter table is unchanged; the layer trace shows the pair under the 1x1's name.
+ *                     0: the pair as two launches, or as the 64 -> 64 1x1 in the first convolution's epilogue.  Any other
+ *                     value: LNS_EINVAL.  Cached plans are rebuilt.
  * Defaults come from LNS_DECODE_GROUP / LNS_DECODE_STREAMS / LNS_NO_OVERLAP / LNS_PROP_PRIORITY at lns_create().
  * Changing an option changes the workspace size: call lns_prepare() again. */
 int lns_set_option(lns_engine* e, const char* name, long value);

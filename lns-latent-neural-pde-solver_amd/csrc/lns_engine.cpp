@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "lns_engine.h"
+#include "lns_fold.h"
 
 // the batch is a grid dimension (gridDim.y / .z) of every kernel
 #define LNS_MAX_BATCH 65535
@@ -1252,18 +1253,24 @@ struct Planner {
                     int act_out = ACT_NONE;
                     size_t skip = 0;
                     int fuse = -1;
+                    int pack = l.pack;
+                    // conv -> 1x1 conv with nothing in between: ONE conv on the weights composed at pack time (lns_fold.h),
+                    // under the 1x1's layer name like the fused-epilogue form below (the intermediate is not traced there either)
+                    const bool folded = e->opt_fold_linear && l.fold >= 0 && !last;
+                    if (folded) { pack = l.fold; skip = 1; }
+                    const size_t j = i + 1 + skip;                 // the layer behind this conv (or behind the pair)
                     // conv -> Swish with no norm in between: fuse the activation into the epilogue
-                    if (!last && L[i + 1].type == LT_SWISH) { act_out = ACT_SWISH; skip = 1; }
+                    if (j < L.size() && L[j].type == LT_SWISH) { act_out = ACT_SWISH; ++skip; }
                     // conv -> 1x1 conv (64 -> 64): the second conv runs in the first one's epilogue
-                    else if (!last && L[i + 1].type == LT_CONV && L[i + 1].k == 1 && L[i + 1].stride == 1 &&
+                    else if (!folded && !last && L[i + 1].type == LT_CONV && L[i + 1].k == 1 && L[i + 1].stride == 1 &&
                              can_fuse_1x1(e->packs[l.pack], e->packs[L[i + 1].pack])) { fuse = L[i + 1].pack; skip = 1; }
                     const bool is_last = (i + 1 + skip == L.size());
-                    nxt = emit_conv(cur, l.pack, l.k, l.stride, l.dil, l.pad, l.mode_y, l.mode_x, act_out, nullptr, 0,
-                                    is_last ? &out_ext : nullptr, fuse >= 0 ? L[i + 1].name : l.name, fuse,
-                                    reads_raw(L, i + 1 + skip));
+                    const std::string& nm = (folded || fuse >= 0) ? L[i + 1].name : l.name;
+                    nxt = emit_conv(cur, pack, l.k, l.stride, l.dil, l.pad, l.mode_y, l.mode_x, act_out, nullptr, 0,
+                                    is_last ? &out_ext : nullptr, nm, fuse, reads_raw(L, i + 1 + skip));
                     free_t(cur);
                     i += skip;
-                    if (!is_last) trace(fuse >= 0 ? L[i].name : l.name, nxt);   // i already points at the fused 1x1
+                    if (!is_last) trace(nm, nxt);
                     break;
                 }
                 case LT_SWISH:
@@ -1349,6 +1356,20 @@ static int finalize_weights(lns_engine* e, int device) {
     }
     for (VecPack& v : e->vecs) { v.off = off; off += round_up_sz(v.count, 64); }
     std::vector<float> host(off, 0.0f);
+    // composed packs (lns_fold.h): W' and b' from the two source packs' current host parameters, once per weight load; from
+    // here on the array is packed like any other conv's
+    std::vector<std::vector<float>> fold_w(e->packs.size()), fold_b(e->packs.size());
+    for (size_t i = 0; i < e->packs.size(); ++i) {
+        const ConvPack& p = e->packs[i];
+        if (p.fold_a < 0) continue;
+        const ConvPack& pa = e->packs[p.fold_a];
+        const ConvPack& pb = e->packs[p.fold_b];
+        auto host_of = [&](const std::string& key) { return key.empty() ? nullptr : e->params[e->pindex.at(key)].host.data(); };
+        fold_w[i].resize((size_t)p.cout * p.cin * p.k * p.k);
+        fold_b[i].resize((size_t)p.cout);
+        fold_conv_1x1(host_of(pa.wkeys[0]), host_of(pa.bkeys[0]), host_of(pb.wkeys[0]), host_of(pb.bkeys[0]), p.k, p.cin, pa.cout,
+                      p.cout, fold_w[i].data(), fold_b[i].data());
+    }
     // 3x3 convs: two-term fp16 split (f16x2) unless LNS_CONV3_SPLIT=bf16x3; the weight scale is the power of two
     // that brings the largest |w| of the layer just below 2^14
     static const bool conv3_f16 = !(getenv("LNS_CONV3_SPLIT") && strcmp(getenv("LNS_CONV3_SPLIT"), "bf16x3") == 0);
@@ -1359,6 +1380,7 @@ static int finalize_weights(lns_engine* e, int device) {
         float mx = 0.0f;
         for (const std::string& key : p.wkeys)
             for (float v : e->params[e->pindex.at(key)].host) mx = std::max(mx, fabsf(v));
+        if (p.fold_a >= 0) for (float v : fold_w[&p - e->packs.data()]) mx = std::max(mx, fabsf(v));
         if (!(mx > 0.0f) || !std::isfinite(mx)) { if (p.k == 1) p.wscale = 1.0f; continue; }   // all-zero weights: scale 1 (3x3: bf16x3)
         p.f16 = p.k == 3;
         p.wscale = exp2f(floorf(log2f(16000.0f / mx)));
@@ -1366,14 +1388,17 @@ static int finalize_weights(lns_engine* e, int device) {
     }
     for (const ConvPack& p : e->packs) {
         int co = 0;
-        for (size_t i = 0; i < p.wkeys.size(); ++i) {
-            const Param& w = e->params[e->pindex.at(p.wkeys[i])];
-            pack_conv_weight(host.data() + p.w_off, w.host.data(), co, p.couts[i], p.cin, p.k, p.Cin_pad, p.Cout_pad);
-            if (p.has_wb && p.k == 3 && !p.f16) convb_pack_weight(host.data() + p.wb_off, w.host.data(), co, p.couts[i], p.cin, p.Cin_pad);
-            if (p.has_wb && p.k == 3 && p.f16) convf_pack_weight(host.data() + p.wb_off, w.host.data(), co, p.couts[i], p.cin, p.Cin_pad, p.wscale);
-            if (p.has_wu && p.f16) convu_pack_weight(host.data() + p.wu_off, w.host.data(), co, p.couts[i], p.cin, p.Cin_pad, p.wscale_up);
-            if (p.has_wb && p.k == 1) convb1_pack_weight(host.data() + p.wb_off, w.host.data(), co, p.couts[i], p.cin, p.Cin_pad, p.wscale);
-            if (!p.bkeys[i].empty()) {
+        const size_t pi = &p - e->packs.data();
+        for (size_t i = 0; i < p.couts.size(); ++i) {      // (a composed pack: one slice, its weights in fold_w / fold_b)
+            const float* w = p.fold_a >= 0 ? fold_w[pi].data() : e->params[e->pindex.at(p.wkeys[i])].host.data();
+            pack_conv_weight(host.data() + p.w_off, w, co, p.couts[i], p.cin, p.k, p.Cin_pad, p.Cout_pad);
+            if (p.has_wb && p.k == 3 && !p.f16) convb_pack_weight(host.data() + p.wb_off, w, co, p.couts[i], p.cin, p.Cin_pad);
+            if (p.has_wb && p.k == 3 && p.f16) convf_pack_weight(host.data() + p.wb_off, w, co, p.couts[i], p.cin, p.Cin_pad, p.wscale);
+            if (p.has_wu && p.f16) convu_pack_weight(host.data() + p.wu_off, w, co, p.couts[i], p.cin, p.Cin_pad, p.wscale_up);
+            if (p.has_wb && p.k == 1) convb1_pack_weight(host.data() + p.wb_off, w, co, p.couts[i], p.cin, p.Cin_pad, p.wscale);
+            if (p.fold_a >= 0) {
+                if (p.has_bias) memcpy(host.data() + p.b_off, fold_b[pi].data(), (size_t)p.cout * 4);
+            } else if (!p.bkeys[i].empty()) {
                 const Param& b = e->params[e->pindex.at(p.bkeys[i])];
                 memcpy(host.data() + p.b_off + co, b.host.data(), (size_t)p.couts[i] * 4);
             }
@@ -1983,6 +2008,7 @@ int lns_create(const lns_config* cfg, lns_engine** out) {
     if (const char* v = getenv("LNS_FA_CHUNK_MB")) e->opt_fa_chunk_mb = atoi(v);
     if (const char* v = getenv("LNS_FA_FUSED")) e->opt_fa_fused = std::min(3, std::max(0, atoi(v)));
     if (const char* v = getenv("LNS_FA_FUSED_GPB")) e->opt_fa_fused_gpb = std::max(0, atoi(v));
+    if (getenv("LNS_NO_FOLD_LINEAR")) e->opt_fold_linear = 0;
     e->cfg.ae_prefix[sizeof(e->cfg.ae_prefix) - 1] = 0;
     e->cfg.prop_prefix[sizeof(e->cfg.prop_prefix) - 1] = 0;
     try {
@@ -2070,6 +2096,17 @@ int lns_set_option(lns_engine* e, const char* name, long value) {
         }
         if (n == "fa_fused") e->opt_fa_fused = (int)value;
         else e->opt_fa_fused_gpb = (int)value;
+    }
+    else if (n == "fold_linear") {
+        if (value != 0 && value != 1) { e->err = "fold_linear: 0 (the pair as it stands) or 1 (one conv on the composed weights)"; return LNS_EINVAL; }
+        if (e->opt_fold_linear != (int)value) {         // a planning rule of the decoder / encoder: cached plans are rebuilt
+            DeviceGuard dg(e);
+            for (auto* m : {&e->enc_plans, &e->dec_plans}) {
+                for (auto& kv : *m) if (kv.second.d_consts) (void)hipFree(kv.second.d_consts);
+                m->clear();
+            }
+        }
+        e->opt_fold_linear = (int)value;
     }
     else if (n == "fa_chunk_mb") {
         if (value < 0 || value > 4096) return LNS_EINVAL;

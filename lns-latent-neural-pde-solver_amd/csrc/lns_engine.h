@@ -32,6 +32,9 @@ struct ConvPack {
     bool f16 = false; float wscale = 1.0f;    // 3x3: slabs hold the two-term fp16 split of w * wscale
     // the conv follows a 2x nearest upsample (UpSampleBlock, final nn.Upsample): phase slabs of the four-tap form too
     bool up2 = false; size_t wu_off = 0; bool has_wu = false; float wscale_up = 1.0f;
+    // composed pack (lns_fold.h): the conv of pack fold_a directly followed by the 1x1 conv of pack fold_b as ONE conv.  It has
+    // no keys of its own: finalize_weights composes its weights from the two packs' current host parameters
+    int fold_a = -1, fold_b = -1;
 };
 
 enum VecXform { VX_NONE = 0, VX_TRANSPOSE2D = 1, VX_PE_T = 2 };
@@ -47,6 +50,7 @@ struct Layer {
     int pack = -1, k = 1, stride = 1, dil = 1;
     int pad[4] = {0, 0, 0, 0};   // top, bottom, left, right
     int mode_y = 0, mode_x = 0;
+    int fold = -1;               // composed pack of this conv and the 1x1 conv that directly follows it ("fold_linear"); -1: none
     // group norm
     int groups = 0; float eps = 0; int vg = -1, vb = -1; int C = 0;
     // residual block
@@ -173,6 +177,9 @@ struct lns_engine {
     int opt_fa_fused = 2;          // 0: off, 1: single-buffered kernel, 2: double-buffered kernel (default), 3: the generic kernel
                                    // for the 64 x 64 block as well (tests); the 32 x 32 block (128 channels) uses the generic one for 1..3
     int opt_fa_fused_gpb = 0;      // plane groups (of 16) per block of the fused kernel; 0 = automatic (scheduling only)
+    // conv -> 1x1 conv with nothing in between runs as one conv on the composed weights (Layer::fold).  A planning rule
+    // ("fold_linear" option / LNS_NO_FOLD_LINEAR); 0: the pair runs as two launches or as the fused 64 -> 64 epilogue
+    int opt_fold_linear = 1;
     // what the last top-level call ran, for lns_check_finite: (plan kind, plan key, arena offset inside the caller's
     // workspace) -- no pointers into the plan caches or the workspace, which the caller may drop at any time -- plus
     // the workspace and batch of that call.  Cleared whenever plans are dropped.

@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "lns_engine.h"
+#include "lns_fold.h"
 
 namespace lns {
 
@@ -471,6 +472,33 @@ static int conv_out(int in, int pad_lo, int pad_hi, int k, int stride, int dil) 
     return (in + pad_lo + pad_hi - dil * (k - 1) - 1) / stride + 1;
 }
 
+// Composed packs (lns_fold.h; DESIGN.md "Folded linear pairs"): a conv directly followed by a 1x1 conv -- no norm, activation
+// or residual between the two layers of the sequence -- gets a third pack that computes both.  The two source packs stay
+// registered (parameter table, state_dict and the fold-off plan are unchanged); the planner picks the composed pack through
+// Layer::fold.  Sites in the reference: decoder tail Conv2d(C, C, 3) -> Conv2d(C, C, 1) (autoencoder2d.py:134-151),
+// post_quant_conv -> decoder.model.0 (:179-181, :97), both in the square autoencoder only, and every encoder's last
+// 1x1 -> quant_conv (:66, :175-177).
+static void add_folded_packs(lns_engine* e, std::vector<Layer>& L) {
+    for (size_t i = 0; i + 1 < L.size(); ++i) {
+        Layer& a = L[i];
+        const Layer& b = L[i + 1];
+        if (a.type != LT_CONV || b.type != LT_CONV) continue;
+        if (b.k != 1 || b.stride != 1 || b.pad[0] || b.pad[1] || b.pad[2] || b.pad[3]) continue;
+        const ConvPack& pa = e->packs[a.pack];
+        const ConvPack& pb = e->packs[b.pack];
+        if (pa.wkeys.size() != 1 || pb.wkeys.size() != 1) continue;
+        if (pb.k != 1 || pb.cin != pa.cout || !fold_pays(pa.k, pa.cin, pa.cout, pb.cout)) continue;
+        ConvPack p;
+        p.cin = pa.cin; p.k = pa.k; p.up2 = pa.up2;
+        p.cout = pb.cout; p.couts.push_back(pb.cout);
+        p.has_bias = pa.has_bias || pb.has_bias;
+        p.fold_a = a.pack; p.fold_b = b.pack;
+        Builder::size_pack(p);
+        e->packs.push_back(p);
+        a.fold = (int)e->packs.size() - 1;
+    }
+}
+
 void build_model(lns_engine* e) {
     const lns_config& c = e->cfg;
     Builder b(e);
@@ -496,6 +524,8 @@ void build_model(lns_engine* e) {
         e->lat_C = c.latent_dim; e->lat_H = H; e->lat_W = W;
     }
     if (c.prop_kind != LNS_PROP_NONE) build_propagator(b, c, e->prop);
+    add_folded_packs(e, e->enc);
+    add_folded_packs(e, e->dec);
 }
 
 }  // namespace lns

@@ -270,7 +270,9 @@ class Engine:
         the evaluation workspace), train_wgrad (0: one block per output tile, 1: batch-parallel weight gradient of the
         training step; it sizes the training workspaces, and the gradients differ by the summation order only).
         Results never depend on the others.  "fa_fused" (default 2; 1 = single-buffered kernel, same bits; 0 = off) selects
-        the arithmetic form of FABlock2D at 64 x 64 planes (in_proj inside the sandwich kernel): ~2e-7 relative on the fields."""
+        the arithmetic form of FABlock2D at 64 x 64 planes (in_proj inside the sandwich kernel): ~2e-7 relative on the fields.
+        "fold_linear" (default 1; 0 = off) runs a convolution directly followed by a 1x1 convolution as one convolution on
+        weights composed at load_weights: the same order of difference."""
         self._check(self._L.lns_set_option(self._h, name.encode(), int(value)), "lns_set_option")
         self.options[name] = int(value)
         self._ws.clear()                      # the workspace size depends on the options
