@@ -583,6 +583,12 @@ int lns_op_attention(const float* qkv, int B, int heads, int dim_head, int n, fl
  *   P <- instance_norm( Kx[b,h] . P . Ky[b,h]^T ), kx [B,heads,H,H], ky [B,heads,W,W] */
 int lns_op_fa_sandwich(const float* u, const float* kx, const float* ky, int B, int heads, int C,
                        int H, int W, float eps, int apply_instance_norm, float* out, void* stream);
+/* FABlock2D axis pooling of the normalised input: x [B,C,H,W] device, sample b at x + b * x_bs floats (x_bs >= C*H*W);
+ * ss [B][C][2] device = per (sample, channel) (scale, shift), or null = identity:
+ *   mx [B,H,C] = scale * mean_W(x) + shift,  my [B,W,C] = scale * mean_H(x) + shift.
+ * The order of every sum is a function of (H, W) only: a sample's result does not depend on B. */
+int lns_op_fa_pool(const float* x, int64_t x_bs, const float* ss, int B, int C, int H, int W,
+                   float* mx, float* my, void* stream);
 
 /* FourierBasicBlock (modules/basics.py:531-583) and CondFourierBasicBlock
  * (modules/fourier_cond.py:84-117) as standalone ops (not reached by any shipped config):

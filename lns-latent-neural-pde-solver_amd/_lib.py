@@ -111,7 +111,7 @@ SYMBOLS = [
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
     "lns_op_conv_wgrad_scratch_bytes", "lns_op_conv_wgrad",
     "lns_op_groupnorm_train", "lns_op_gelu_grad", "lns_op_bias_grad",
-    "lns_op_conv2d", "lns_op_conv_pair_stress", "lns_op_groupnorm_stats", "lns_op_attention", "lns_op_fa_sandwich", "lns_op_fourier_block",
+    "lns_op_conv2d", "lns_op_conv_pair_stress", "lns_op_groupnorm_stats", "lns_op_attention", "lns_op_fa_sandwich", "lns_op_fa_pool", "lns_op_fourier_block",
     "lns_fourier_block_create", "lns_fourier_block_forward", "lns_fourier_block_destroy", "lns_metric_rel_l2", "lns_metric_rel_l2_ch",
 ]
 
@@ -231,6 +231,7 @@ def lib():
     L.lns_op_groupnorm_stats.argtypes = [vp, i, i, i, i, c.c_float, vp, vp, vp, vp, vp]
     L.lns_op_attention.argtypes = [vp, i, i, i, i, c.c_float, vp, vp]
     L.lns_op_fa_sandwich.argtypes = [vp, vp, vp, i, i, i, i, i, c.c_float, i, vp, vp]
+    L.lns_op_fa_pool.argtypes = [vp, c.c_int64, vp, i, i, i, i, vp, vp, vp]
     L.lns_op_fourier_block.argtypes = [vp, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp]
     L.lns_fourier_block_create.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, c.POINTER(vp)]
     L.lns_fourier_block_forward.argtypes = [vp, vp, vp, i, i, i, vp, vp]

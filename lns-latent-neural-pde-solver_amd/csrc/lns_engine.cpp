@@ -776,7 +776,7 @@ struct Planner {
     // FABlock2D's three passes over the 512-plane tensor (in_proj writes it, the sandwich rewrites it in place, to_out reads
     // it: 537 MB at 64 x 64, B = 64 -- twice the Infinity Cache, so every pass goes to HBM) are re-issued per GROUP OF SAMPLES
     // small enough for the group's slice to stay in the cache from one kernel to the next: [in_proj, sandwich, to_out](chunk 0),
-    // [...](chunk 1), ...  The ops in between (to_in, pooling, reducers, low-rank kernels) do not depend on in_proj and keep
+    // [...](chunk 1), ...  The ops in between (pooling, reducers, low-rank kernels) do not depend on in_proj and keep
     // their place; per-sample arithmetic is untouched (ConvArgs::b0), so the bits do not change.
     int next_chunk_group = 1;
     int fa_chunk_samples(size_t bytes_per_sample) const {          // 0: no chunking
@@ -812,8 +812,7 @@ struct Planner {
         const int C = x.C, H = x.H, W = x.W, heads = l.heads, dh = l.dim_head, lat = l.fa_lat, DK = l.fa_dk;
         TRef xin = x; xin.owned = false;
         emit_gn(xin, 1, 1e-5f, l.fa_g, l.fa_b, 0, l.name + ".in_norm");
-        // in_proj records max |u| per sample: the sandwich's f16x2 form scales its planes by it (to_in's consumer, the
-        // pooling, needs none)
+        // in_proj records max |u| per sample: the sandwich's f16x2 form scales its planes by it
         // round 4: in_proj inside the sandwich kernel (fa_fused.inc) -- the plane tensor is only ever the sandwich's OUTPUT
         static const bool fused_off = getenv("LNS_FA_SANDWICH_FP32") != nullptr || getenv("LNS_CONV_FP32_MFMA") != nullptr ||
                                       getenv("LNS_CONV1_FP32_MFMA") != nullptr || getenv("LNS_FA_SANDWICH_BF16X3") != nullptr;
@@ -840,23 +839,26 @@ struct Planner {
             uphi = conv_same1(xin, l.inproj, ACT_NONE, nullptr, nullptr, l.name + ".in_proj", -1, true);
             inproj_at = plan->ops.size() - 1;
         }
-        TRef v = conv_same1(xin, l.toin, ACT_NONE, nullptr, nullptr, l.name + ".to_in", -1, false);
+        // axis pooling of the NORMALISED INPUT: to_in (1x1, no bias) and the reducers' first Linear commute with the mean over
+        // an axis, so the pool reads xin through its (scale, shift) table and the reducers apply W_x W_toin / W_y W_toin
+        // (VecPack::key2) -- the full-resolution to_in conv and its output tensor do not exist.  in_proj may have merged the
+        // GroupNorm partials in its own prologue; the pool needs the finished table.
+        flush_gn(xin);
+        const size_t mx_off = arena.alloc((size_t)B * H * C * 4), my_off = arena.alloc((size_t)B * W * C * 4);
+        {
+            Op op;
+            op.type = OP_FAPOOL; op.name = l.name + ".pool"; op.cls = CLS_FAPOOL;
+            op.fp.x = as_ptr<const float>(xin.ptr); op.fp.x_bs = xin.bs; op.fp.ss = as_ptr<const float>(xin.ss);
+            op.fp.B = B; op.fp.C = C; op.fp.H = H; op.fp.W = W;
+            op.fp.mx = as_ptr<float>(tag(SP_WS, mx_off)); op.fp.my = as_ptr<float>(tag(SP_WS, my_off));
+            op.bytes = 4.0 * B * C * H * W;
+            plan->ops.push_back(op);
+        }
         // (chunked: in_proj is re-issued AFTER the pooling / reducer / low-rank ops, so the GroupNorm table it reads must
         //  outlive their allocations)
         const bool fused_out = getenv("LNS_FA_NO_FUSE_TO_OUT") == nullptr && can_fuse_1x1(e->packs[l.out1], e->packs[l.out3]);
         const bool will_chunk = !fused_in && fused_out && fa_chunk_samples((size_t)heads * dh * H * W * 4) > 0;
         if (!will_chunk) free_t(xin);
-        // axis pooling
-        const size_t mx_off = arena.alloc((size_t)B * H * C * 4), my_off = arena.alloc((size_t)B * W * C * 4);
-        {
-            Op op;
-            op.type = OP_FAPOOL; op.name = l.name + ".pool"; op.cls = CLS_FAPOOL;
-            op.fp.v = as_ptr<const float>(v.ptr); op.fp.B = B; op.fp.C = C; op.fp.H = H; op.fp.W = W;
-            op.fp.mx = as_ptr<float>(tag(SP_WS, mx_off)); op.fp.my = as_ptr<float>(tag(SP_WS, my_off));
-            op.bytes = 4.0 * B * C * H * W;
-            plan->ops.push_back(op);
-        }
-        free_t(v);
         // PoolingReducer of both axes in ONE launch, rotary + q k^T of both axes in one more
         // (LNS_FA_NO_MERGE restores one launch per axis)
         static const bool no_merge = getenv("LNS_FA_NO_MERGE") != nullptr;
@@ -1405,18 +1407,28 @@ static int finalize_weights(lns_engine* e, int device) {
             co += p.couts[i];
         }
     }
+    std::vector<float> composed;
     for (const VecPack& v : e->vecs) {
         const Param& p = e->params[e->pindex.at(v.key)];
+        const float* src = p.host.data();
+        if (!v.key2.empty()) {
+            // composed vector (VecPack::key2): `key` [n][n] applied after `key2` [n][n] is the k = 1, bias-free case of
+            // lns_fold.h (compensated double, one rounding) -- from the current host parameters, so a reload recomposes
+            const int n = (int)p.shape[0];
+            composed.resize(v.count);
+            fold_conv_1x1(e->params[e->pindex.at(v.key2)].host.data(), nullptr, p.host.data(), nullptr, 1, n, n, n, composed.data(), nullptr);
+            src = composed.data();
+        }
         float* dst = host.data() + v.off;
-        if (v.xform == VX_NONE) memcpy(dst, p.host.data(), v.count * 4);
+        if (v.xform == VX_NONE) memcpy(dst, src, v.count * 4);
         else if (v.xform == VX_TRANSPOSE2D) {   // [out][in] -> [in][out]
             const size_t rows = (size_t)p.shape[0], cols = v.count / rows;
             for (size_t r = 0; r < rows; ++r)
-                for (size_t c = 0; c < cols; ++c) dst[c * rows + r] = p.host[r * cols + c];
+                for (size_t c = 0; c < cols; ++c) dst[c * rows + r] = src[r * cols + c];
         } else if (v.xform == VX_PE_T) {        // [1][L][C] -> [C][L]
             const size_t L = (size_t)p.shape[1], C = (size_t)p.shape[2];
             for (size_t i = 0; i < L; ++i)
-                for (size_t c = 0; c < C; ++c) dst[c * L + i] = p.host[i * C + c];
+                for (size_t c = 0; c < C; ++c) dst[c * L + i] = src[i * C + c];
         }
     }
     HIPCHK(e, hipSetDevice(device));
@@ -1635,7 +1647,7 @@ struct Runner {
                     break;
                 }
                 case OP_ATTN: { AttnArgs a = op.at; fix(a.qkv, B); fix(a.o, B); fix(a.amax_in, B); rc = launch_attention(a, stream); break; }
-                case OP_FAPOOL: { FaPoolArgs a = op.fp; fix(a.v, B); fix(a.mx, B); fix(a.my, B); rc = launch_fa_pool(a, stream); break; }
+                case OP_FAPOOL: { FaPoolArgs a = op.fp; fix(a.x, B); fix(a.ss, B); fix(a.mx, B); fix(a.my, B); fixbs(a.x_bs, B); rc = launch_fa_pool(a, stream); break; }
                 case OP_FARED: {
                     FaReducerArgs a = op.fr;
                     fix(a.m, B); fix(a.win_t, B); fix(a.ln_g, B); fix(a.ln_b, B); fix(a.w1_t, B); fix(a.w2_t, B);
@@ -3043,6 +3055,16 @@ int lns_op_fa_sandwich(const float* u, const float* kx, const float* ky, int B, 
     if (he == hipSuccess) he = hipStreamSynchronize(s);
     (void)hipFree(damax);
     OPCHK(he);
+    return LNS_OK;
+}
+
+int lns_op_fa_pool(const float* x, int64_t x_bs, const float* ss, int B, int C, int H, int W, float* mx, float* my, void* stream) {
+    if (!x || !mx || !my || B <= 0 || C <= 0 || H <= 0 || W <= 0 || x_bs < (int64_t)C * H * W) return LNS_EINVAL;
+    OPCHK(init_kernels());
+    FaPoolArgs a = {x, (long)x_bs, ss, B, C, H, W, mx, my};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    OPCHK(launch_fa_pool(a, s));
+    OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
 }
 

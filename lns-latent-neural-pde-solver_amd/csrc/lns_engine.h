@@ -38,7 +38,12 @@ struct ConvPack {
 };
 
 enum VecXform { VX_NONE = 0, VX_TRANSPOSE2D = 1, VX_PE_T = 2 };
-struct VecPack { std::string key; int xform = VX_NONE; size_t off = 0; size_t count = 0; };
+struct VecPack {
+    std::string key; int xform = VX_NONE; size_t off = 0; size_t count = 0;
+    // composed vector (lns_fold.h): the [out][mid] matrix `key` applied after the [mid][in] matrix `key2` as ONE [out][in] matrix,
+    // which then takes `xform`.  It has no key of its own: finalize_weights composes it from the two current host parameters
+    std::string key2;
+};
 
 // ---- layer IR (mirrors the reference nn.Sequential entries) ------------------
 enum LType { LT_CONV, LT_SWISH, LT_GN, LT_RES, LT_UP2, LT_RESIZE, LT_SA, LT_FA, LT_FOURIER, LT_PROPBLOCK, LT_CONDBLOCK, LT_CONDRES };
@@ -60,7 +65,7 @@ struct Layer {
     // self attention
     int heads = 0, dim_head = 0, ln_g = -1, ln_b = -1, pe = -1, pe_len = 0, qkv = -1, proj = -1;
     // factorized attention
-    int fa_g = -1, fa_b = -1, inproj = -1, toin = -1, qkx = -1, qky = -1, out1 = -1, out3 = -1;
+    int fa_g = -1, fa_b = -1, inproj = -1, qkx = -1, qky = -1, out1 = -1, out3 = -1;
     int rx[6] = {-1, -1, -1, -1, -1, -1}, ry[6] = {-1, -1, -1, -1, -1, -1};
     std::string invf_x, invf_y;
     int fa_lat = 0, fa_dk = 0;

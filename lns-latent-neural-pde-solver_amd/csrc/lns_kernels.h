@@ -199,7 +199,9 @@ struct AttnArgs { const float* qkv; int B, heads, D, n; float scale; float* o;
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 
 // FABlock2D pieces ----------------------------------------------------------
-struct FaPoolArgs { const float* v; int B, C, H, W; float* mx; float* my; };   // mx [B,H,C], my [B,W,C]
+// x [B,C,H,W] (batch stride x_bs floats), ss [B][C][2] (scale, shift) or null = identity:
+// mx [B,H,C] = scale * mean over W + shift, my [B,W,C] = scale * mean over H + shift
+struct FaPoolArgs { const float* x; long x_bs; const float* ss; int B, C, H, W; float* mx; float* my; };
 hipError_t launch_fa_pool(const FaPoolArgs& a, hipStream_t s);
 
 struct FaReducerArgs {                 // PoolingReducer on pooled rows [rows, C]

@@ -79,6 +79,14 @@ struct Builder {
         add_param(key, std::move(shape));
         return vec(key, xform);
     }
+    // the square matrix `key` (a new parameter) applied after the square matrix `key2` (an existing one), packed as one
+    int vec_param_composed(const std::string& key, const std::string& key2, std::vector<int64_t> shape, int xform) {
+        if (e->params[e->pindex.at(key2)].numel() != (size_t)(shape[0] * shape[1]) || shape[0] != shape[1])
+            throw std::runtime_error("composed vector: shapes of " + key + " and " + key2);
+        const int id = vec_param(key, std::move(shape), xform);
+        e->vecs[id].key2 = key2;
+        return id;
+    }
 };
 
 static bool in_list(const int32_t* lst, int n, int v) {
@@ -163,8 +171,10 @@ static Layer sa_layer(Builder& b, const std::string& p, int dim, int heads, int 
 }
 
 // PoolingReducer(in=dim, hidden=dim, out=latent): modules/factorized_attention.py:72-94
-static void reducer_params(Builder& b, const std::string& p, int dim, int lat, int* ids) {
-    ids[0] = b.vec_param(p + ".to_in.weight", {dim, dim}, VX_TRANSPOSE2D);
+// Its first matrix is packed as to_in.weight x `toin_key` (FABlock2D's 1x1 to_in conv): the engine pools the block's
+// normalised input and never runs that conv (DESIGN.md "FABlock2D: pooling in front of to_in")
+static void reducer_params(Builder& b, const std::string& p, const std::string& toin_key, int dim, int lat, int* ids) {
+    ids[0] = b.vec_param_composed(p + ".to_in.weight", toin_key, {dim, dim}, VX_TRANSPOSE2D);
     ids[1] = b.vec_param(p + ".out_ffn.0.weight", {dim});
     ids[2] = b.vec_param(p + ".out_ffn.0.bias", {dim});
     ids[3] = b.vec_param(p + ".out_ffn.1.weight", {2 * dim, dim}, VX_TRANSPOSE2D);
@@ -180,9 +190,9 @@ static Layer fa_layer(Builder& b, const std::string& p, int dim, int dim_head, i
     l.fa_g = b.vec_param(p + ".in_norm.weight", {dim});
     l.fa_b = b.vec_param(p + ".in_norm.bias", {dim});
     l.inproj = b.conv(p + ".in_proj", dim, heads * dim_head, 1, false);
-    l.toin = b.conv(p + ".to_in.0", dim, dim, 1, false);
-    reducer_params(b, p + ".to_x.0", dim, lat, l.rx);
-    reducer_params(b, p + ".to_y.1", dim, lat, l.ry);
+    b.add_param(p + ".to_in.0.weight", {dim, dim, 1, 1});      // no pack of its own: composed into the reducers' first matrix
+    reducer_params(b, p + ".to_x.0", p + ".to_in.0.weight", dim, lat, l.rx);
+    reducer_params(b, p + ".to_y.1", p + ".to_in.0.weight", dim, lat, l.ry);
     b.linear_params(p + ".low_rank_kernel_x.to_qk", lat, l.fa_dk * heads * 2, false);
     l.qkx = b.linear_pack({p + ".low_rank_kernel_x.to_qk"}, {false}, lat, l.fa_dk * heads * 2);
     l.invf_x = p + ".low_rank_kernel_x.pos_emb.inv_freq";
