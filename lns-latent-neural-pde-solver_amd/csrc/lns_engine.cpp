@@ -13,10 +13,10 @@
 #include <mutex>
 #include <tuple>
 #include <stdexcept>
-#include <type_traits>
 
 #include "lns_engine.h"
 #include "lns_fold.h"
+#include "lns_resolve.h"
 
 // the batch is a grid dimension (gridDim.y / .z) of every kernel
 #define LNS_MAX_BATCH 65535
@@ -45,30 +45,6 @@ static std::string fmt(const char* f, ...) {
     } while (0)
 
 static size_t round_up_sz(size_t v, size_t m) { return (v + m - 1) / m * m; }
-
-// ---------------------------------------------------------------------------
-// tagged pointers: (space+0) << 56 | byte offset ; resolved at launch time
-// ---------------------------------------------------------------------------
-static inline uint64_t tag(int space, size_t byte_off) { return ((uint64_t)space << 56) | (uint64_t)byte_off; }
-template <class T> static inline T* as_ptr(uint64_t t) { return reinterpret_cast<T*>(t); }
-
-struct Bases { char* b[16]; long bs[16]; long bs2[16]; int bdiv[16]; mutable bool bad = false; };
-template <class T> static inline void fix(T*& p, const Bases& B) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    if (!v) return;
-    const int sp = (int)(v >> 56);
-    if (sp == SP_NULL) return;                                                       // already a device address
-    if (sp >= 16 || !B.b[sp]) { B.bad = true; p = nullptr; return; }                 // tag without a base: never launch on it
-    if (sp == SP_CT && ((v >> 54) & 1)) { B.bad = true; p = nullptr; return; }       // float-segment constant Planner::finish() did not rebase
-    p = reinterpret_cast<T*>(B.b[sp] + (v & 0x00FFFFFFFFFFFFFFull));
-}
-// A planner-tagged pointer (space id in bits 56+) that reached a launch without fix() would be a wild device address
-// (the GPU abort of round 1, DESIGN.md "FUSE2 abort"): every pointer argument of an op is checked after resolution.
-static inline bool untagged(const void* p) { return (reinterpret_cast<uint64_t>(p) >> 56) == 0; }
-template <class... P> static inline bool all_untagged(P... ps) { return (untagged(ps) && ...); }
-static inline void fixbs(long& bs, const Bases& B) {
-    if (bs < 0) bs = B.bs[SP_EXT0 + (int)(-bs - 1)];
-}
 
 // ---------------------------------------------------------------------------
 // host helpers shared by the planner and the op-level test entry points
@@ -1309,21 +1285,7 @@ struct Planner {
     void finish() {
         // int constants first, then float constants, in one device blob
         const size_t ibytes = plan->consts_i.size() * 4;
-        for (Op& op : plan->ops) {
-            auto rebase = [&](auto*& p) {
-                uint64_t v = reinterpret_cast<uint64_t>(p);
-                if ((v >> 56) != SP_CT) return;
-                const bool is_f = (v >> 54) & 1;
-                uint64_t off = v & 0x003FFFFFFFFFFFFFull;
-                if (is_f) off += ibytes;
-                p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(tag(SP_CT, off));
-            };
-            if (op.type == OP_CONV) { rebase(op.conv.rowmap); rebase(op.conv.colmap); }
-            if (op.type == OP_FALRK || op.type == OP_FALRK2) rebase(op.fl.cs);
-            if (op.type == OP_FALRK2) rebase(op.fl2.cs);
-            if (op.type == OP_CONDBASE) rebase(op.cb.freqs);
-            if (op.type == OP_FAFUSED) rebase(op.ff.wp);
-        }
+        for (Op& op : plan->ops) for_each_ptr(op, [&](auto*& p) { rebase_const(p, ibytes); });
         plan->arena_bytes = arena.high;
         plan->amax_bytes = (size_t)amax_used * B * LNS_AMAX_SUB * 4;
     }
@@ -1520,6 +1482,34 @@ static int get_plan(lns_engine* e, PlanKind kind, int B, int H, int W, Plan** ou
 // ---------------------------------------------------------------------------
 // execution
 // ---------------------------------------------------------------------------
+#if defined(LNS_TS) || defined(FAF_TS)
+// diagnostic builds: launch(stamps) with a zeroed [blocks][words] stamp buffer, wait for it, and append the header line and one
+// "<block> <words ...>" line per block to $LNS_TS_FILE (tools/ts_analyze.py, faf_ts_analyze.py, clock_analyze.py read that).
+// false: no file named or no buffer, and nothing was launched
+template <class L> static bool ts_capture(long blocks, int words, const std::string& header, hipStream_t s, hipError_t& rc, L&& launch) {
+    const char* path = getenv("LNS_TS_FILE");
+    const size_t n = (size_t)blocks * words;
+    long long* dts = nullptr;
+    if (!path || hipMalloc(reinterpret_cast<void**>(&dts), n * 8) != hipSuccess) return false;
+    (void)hipMemsetAsync(dts, 0, n * 8, s);
+    rc = launch(dts);
+    (void)hipStreamSynchronize(s);
+    std::vector<long long> h(n);
+    (void)hipMemcpy(h.data(), dts, n * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(dts);
+    if (FILE* f = fopen(path, "a")) {
+        fprintf(f, "%s\n", header.c_str());
+        for (long i = 0; i < blocks; ++i) {
+            fprintf(f, "%ld", i);
+            for (int k = 0; k < words; ++k) fprintf(f, " %lld", h[(size_t)i * words + k]);
+            fprintf(f, "\n");
+        }
+        fclose(f);
+    }
+    return true;
+}
+#endif
+
 struct EvPair { hipEvent_t a, b; int cls; const Op* op; };
 
 struct Runner {
@@ -1532,8 +1522,7 @@ struct Runner {
     bool skip_step_invariant = false;
 
     int run(const Plan& plan, const ExtT* ext, char* arena_base) {
-        Bases B;
-        memset(&B, 0, sizeof B);
+        Bases B = {};
         B.b[SP_WS] = arena_base;
         B.b[SP_WT] = reinterpret_cast<char*>(e->d_weights);
         B.b[SP_CT] = static_cast<char*>(plan.d_consts);
@@ -1577,183 +1566,72 @@ struct Runner {
                 if ((is_gn && strstr(skip, "gn")) || (is_fas && strstr(skip, "fasmall"))) continue;
             }
 #endif
+            // resolve a copy of the op's block(s), launch only if every pointer resolved (B.bad is reported below)
+            auto go = [&](auto a, auto launch) { if (resolve(a, B)) rc = launch(a, stream); };
+            auto go2 = [&](auto a, auto b, auto launch) { if (resolve(a, B) && resolve(b, B)) rc = launch(a, b, stream); };   // both axes
             switch (op.type) {
                 case OP_CONV: {
                     ConvArgs a = op.conv;
-                    fix(a.x, B); fix(a.w, B); fix(a.bias, B); fix(a.ss, B); fix(a.rowmap, B); fix(a.colmap, B);
-                    fix(a.y, B); fix(a.res, B); fix(a.badd, B); fix(a.w2, B); fix(a.bias2, B); fix(a.wb, B); fix(a.stat_part, B);
-                    fix(a.amax_in, B); fix(a.amax_out, B); fix(a.gn_part, B); fix(a.gn_gamma, B); fix(a.gn_beta, B); fix(a.gn_premul, B);
-                    if (a.y_bs < 0) {          // output handed in by the caller: may be addressed in two levels (step-batched decode)
-                        const int sl = SP_EXT0 + (int)(-a.y_bs - 1);
-                        a.y_bs2 = B.bs2[sl]; a.y_bdiv = B.bdiv[sl];
-                    }
-                    if (a.x_bs < 0 && B.bdiv[SP_EXT0 + (int)(-a.x_bs - 1)]) B.bad = true;   // inputs are always plain
-                    fixbs(a.x_bs, B); fixbs(a.y_bs, B); fixbs(a.res_bs, B);
-                    if (!all_untagged(a.x, a.w, a.bias, a.ss, a.rowmap, a.colmap, a.y, a.res, a.badd, a.w2, a.bias2, a.wb, a.stat_part,
-                                      a.amax_in, a.amax_out, a.gn_part, a.gn_gamma, a.gn_beta, a.gn_premul)) B.bad = true;
-                    if (B.bad) break;
+                    if (!resolve_conv(a, B)) break;
 #ifdef LNS_TS
                     // diagnostic build: per-block phase timestamps of the layer named by $LNS_TS_LAYER, appended to $LNS_TS_FILE
                     // ($LNS_TS_SKIP: leave the first N launches of the layer alone -- a stamp taken after seconds of sustained load)
                     static long ts_seen = 0;
-                    const bool ts_match = getenv("LNS_TS_FILE") && getenv("LNS_TS_LAYER") && op.name.find(getenv("LNS_TS_LAYER")) != std::string::npos &&
+                    const bool ts_match = getenv("LNS_TS_LAYER") && op.name.find(getenv("LNS_TS_LAYER")) != std::string::npos &&
                                           (cv_is_split_3x3(op.variant) || op.variant == CV_B1);
                     const long ts_skip = getenv("LNS_TS_SKIP") ? atol(getenv("LNS_TS_SKIP")) : 0, ts_max = getenv("LNS_TS_MAX") ? atol(getenv("LNS_TS_MAX")) : (1L << 40);
-                    if (ts_match && ts_seen++ >= ts_skip && ts_seen - 1 - ts_skip < ts_max) {
-                        const long nblk = (long)a.tiles_x * a.tiles_y * a.cout_tiles * a.B;
-                        long long* dts = nullptr;
-                        if (hipMalloc(reinterpret_cast<void**>(&dts), nblk * 64) == hipSuccess) {
-                            (void)hipMemsetAsync(dts, 0, nblk * 64, stream);
-                            a.dbg_ts = dts;
-                            rc = launch_conv(op.variant, a, stream);
-                            (void)hipStreamSynchronize(stream);
-                            std::vector<long long> h(nblk * 8);
-                            (void)hipMemcpy(h.data(), dts, nblk * 64, hipMemcpyDeviceToHost);
-                            (void)hipFree(dts);
-                            if (FILE* f = fopen(getenv("LNS_TS_FILE"), "a")) {
-                                fprintf(f, "# launch %s B=%d Cin=%d Cout=%d H=%d W=%d blocks=%ld\n", op.name.c_str(), a.B, a.Cin, a.Cout, a.Hout, a.Wout, nblk);
-                                for (long i = 0; i < nblk; ++i) {
-                                    fprintf(f, "%ld", i);
-                                    for (int k = 0; k < 8; ++k) fprintf(f, " %lld", h[i * 8 + k]);
-                                    fprintf(f, "\n");
-                                }
-                                fclose(f);
-                            }
-                            break;
-                        }
-                    }
-                    a.dbg_ts = nullptr;
+                    const long nblk = (long)a.tiles_x * a.tiles_y * a.cout_tiles * a.B;
+                    if (ts_match && ts_seen++ >= ts_skip && ts_seen - 1 - ts_skip < ts_max &&
+                        ts_capture(nblk, 8, fmt("# launch %s B=%d Cin=%d Cout=%d H=%d W=%d blocks=%ld", op.name.c_str(), a.B, a.Cin, a.Cout, a.Hout, a.Wout, nblk),
+                                   stream, rc, [&](long long* ts) { a.dbg_ts = ts; return launch_conv(op.variant, a, stream); })) break;
 #endif
                     rc = launch_conv(op.variant, a, stream);
                     break;
                 }
                 case OP_GNSTATS: {
                     GnStatsArgs a = op.gn;
-                    fix(a.x, B); fix(a.gamma, B); fix(a.beta, B); fix(a.premul, B); fix(a.ss, B); fixbs(a.x_bs, B);
-                    if (op.gn_tiles) {
-                        const float* tp = op.gn_tile_part;
-                        fix(tp, B);
+                    const float* tp = op.gn_tile_part;
+                    if (!resolve(a, B) || !fix(tp, B)) break;
+                    if (op.gn_tiles)
                         rc = launch_gn_tile_finalize(a, tp, op.gn_tiles, op.gn_count < 0 ? 0 : (op.gn_count ? op.gn_count : GN_TILE_PIXELS),
                                                      op.gn_geom, stream);
-                        break;
-                    }
-                    rc = launch_gn_stats(a, a.ss + (size_t)a.B * a.C * 2, stream);
+                    else rc = launch_gn_stats(a, a.ss + (size_t)a.B * a.C * 2, stream);
                     break;
                 }
-                case OP_LNPE: {
-                    LnPeArgs a = op.ln;
-                    fix(a.x, B); fix(a.gamma, B); fix(a.beta, B); fix(a.pe_t, B); fix(a.h, B); fixbs(a.x_bs, B);
-                    rc = launch_ln_pe(a, stream);
-                    break;
-                }
-                case OP_ATTN: { AttnArgs a = op.at; fix(a.qkv, B); fix(a.o, B); fix(a.amax_in, B); rc = launch_attention(a, stream); break; }
-                case OP_FAPOOL: { FaPoolArgs a = op.fp; fix(a.x, B); fix(a.ss, B); fix(a.mx, B); fix(a.my, B); fixbs(a.x_bs, B); rc = launch_fa_pool(a, stream); break; }
-                case OP_FARED: {
-                    FaReducerArgs a = op.fr;
-                    fix(a.m, B); fix(a.win_t, B); fix(a.ln_g, B); fix(a.ln_b, B); fix(a.w1_t, B); fix(a.w2_t, B);
-                    fix(a.b2, B); fix(a.u, B); fix(a.amax_out, B);
-                    rc = launch_fa_reducer(a, stream);
-                    break;
-                }
-                case OP_FARED2: {
-                    FaReducerArgs a[2] = {op.fr, op.fr2};
-                    for (int i = 0; i < 2; ++i) {
-                        fix(a[i].m, B); fix(a[i].win_t, B); fix(a[i].ln_g, B); fix(a[i].ln_b, B); fix(a[i].w1_t, B); fix(a[i].w2_t, B);
-                        fix(a[i].b2, B); fix(a[i].u, B); fix(a[i].wqk_t, B); fix(a[i].bqk, B); fix(a[i].qk, B); fix(a[i].amax_out, B);
-                    }
-                    rc = launch_fa_reducer2(a[0], a[1], stream);
-                    break;
-                }
-                case OP_FALRK: { FaLrkArgs a = op.fl; fix(a.qk, B); fix(a.cs, B); fix(a.kmat, B); rc = launch_fa_lrk(a, stream); break; }
-                case OP_FALRK2: {
-                    FaLrkArgs a[2] = {op.fl, op.fl2};
-                    for (int i = 0; i < 2; ++i) { fix(a[i].qk, B); fix(a[i].cs, B); fix(a[i].kmat, B); }
-                    rc = launch_fa_lrk2(a[0], a[1], stream);
-                    break;
-                }
-                case OP_FASAND: {
-                    FaSandwichArgs a = op.fs;
-                    fix(a.u, B); fix(a.kx, B); fix(a.ky, B); fix(a.out, B); fix(a.amax_u, B);
-                    rc = launch_fa_sandwich(a, stream);
-                    break;
-                }
-                case OP_FAGSPLIT: {
-                    FaGsplitArgs a = op.fg;
-                    fix(a.x, B); fix(a.ss, B); fix(a.gs, B); fix(a.amax_out, B); fixbs(a.x_bs, B);
-                    rc = launch_fa_gsplit(a, stream);
-                    break;
-                }
+                case OP_LNPE: go(op.ln, launch_ln_pe); break;
+                case OP_ATTN: go(op.at, launch_attention); break;
+                case OP_FAPOOL: go(op.fp, launch_fa_pool); break;
+                case OP_FARED: go(op.fr, launch_fa_reducer); break;
+                case OP_FARED2: go2(op.fr, op.fr2, launch_fa_reducer2); break;
+                case OP_FALRK: go(op.fl, launch_fa_lrk); break;
+                case OP_FALRK2: go2(op.fl, op.fl2, launch_fa_lrk2); break;
+                case OP_FASAND: go(op.fs, launch_fa_sandwich); break;
+                case OP_FAGSPLIT: go(op.fg, launch_fa_gsplit); break;
                 case OP_FAFUSED: {
                     FaFusedArgs a = op.ff;
-                    fix(a.gs, B); fix(a.amax_g, B); fix(a.wp, B); fix(a.kx, B); fix(a.ky, B); fix(a.out, B);
+                    if (!resolve(a, B)) break;
                     a.dbg_ts = nullptr;
 #ifdef FAF_TS
                     // diagnostic build: wave 0's phase timestamps of every block, appended to $LNS_TS_FILE
-                    if (getenv("LNS_TS_FILE")) {
-                        const long nblk = (long)a.B * a.heads * (a.C / 16 / a.gpb);
-                        long long* dts = nullptr;
-                        if (hipMalloc(reinterpret_cast<void**>(&dts), nblk * 24 * 8) == hipSuccess) {
-                            (void)hipMemsetAsync(dts, 0, nblk * 24 * 8, stream);
-                            a.dbg_ts = dts;
-                            rc = launch_fa_fused(a, stream);
-                            (void)hipStreamSynchronize(stream);
-                            std::vector<long long> hts(nblk * 24);
-                            (void)hipMemcpy(hts.data(), dts, nblk * 24 * 8, hipMemcpyDeviceToHost);
-                            (void)hipFree(dts);
-                            if (FILE* f = fopen(getenv("LNS_TS_FILE"), "a")) {
-                                fprintf(f, "# launch %s blocks=%ld\n", op.name.c_str(), nblk);
-                                for (long i = 0; i < nblk; ++i) {
-                                    fprintf(f, "%ld", i);
-                                    for (int k = 0; k < 24; ++k) fprintf(f, " %lld", hts[i * 24 + k]);
-                                    fprintf(f, "\n");
-                                }
-                                fclose(f);
-                            }
-                            break;
-                        }
-                    }
+                    const long nblk = (long)a.B * a.heads * (a.C / 16 / a.gpb);
+                    if (ts_capture(nblk, 24, fmt("# launch %s blocks=%ld", op.name.c_str(), nblk), stream, rc,
+                                   [&](long long* ts) { a.dbg_ts = ts; return launch_fa_fused(a, stream); })) break;
 #endif
                     rc = launch_fa_fused(a, stream);
                     break;
                 }
-                case OP_CONDBASE: {
-                    CondBaseArgs a = op.cb;
-                    fix(a.param, B); fix(a.freqs, B); fix(a.w0_t, B); fix(a.b0, B); fix(a.w2_t, B); fix(a.b2, B); fix(a.ce, B);
-                    rc = launch_cond_base(a, stream);
-                    break;
-                }
-                case OP_CONDBLK: {
-                    CondBlockArgs a = op.ck;
-                    fix(a.ce, B); fix(a.wce_t, B); fix(a.bce, B); fix(a.gn_g, B); fix(a.gn_b, B); fix(a.c1_t, B);
-                    fix(a.c1_b, B); fix(a.c3_t, B); fix(a.c3_b, B); fix(a.emb, B); fix(a.mul, B);
-                    rc = launch_cond_block(a, stream);
-                    break;
-                }
-                case OP_APPLY: { ApplyArgs a = op.ap; fix(a.x, B); fix(a.ss, B); fix(a.y, B); fix(a.amax_out, B); fixbs(a.x_bs, B); rc = launch_apply(a, stream); break; }
-                case OP_SPECTRAL: {
-                    SpectralArgs a = op.sp;
-                    fix(a.x, B); fix(a.w1, B); fix(a.w2, B); fix(a.emb, B); fix(a.t1, B); fix(a.xf, B); fix(a.of, B); fix(a.y, B);
-                    fixbs(a.x_bs, B);
-                    rc = launch_spectral(a, stream);
-                    break;
-                }
-                case OP_FCOMBINE: {
-                    FourierCombineArgs a = op.fc;
-                    fix(a.a, B); fix(a.b, B); fix(a.e, B); fix(a.skip, B); fix(a.y, B); fix(a.amax_out, B); fixbs(a.skip_bs, B); fixbs(a.y_bs, B);
-                    rc = launch_fourier_combine(a, stream);
-                    break;
-                }
-                case OP_VECLIN: {
-                    VecLinearArgs a = op.vl;
-                    fix(a.in, B); fix(a.w, B); fix(a.bias, B); fix(a.out, B);
-                    rc = launch_vec_linear(a, stream);
-                    break;
-                }
+                case OP_CONDBASE: go(op.cb, launch_cond_base); break;
+                case OP_CONDBLK: go(op.ck, launch_cond_block); break;
+                case OP_APPLY: go(op.ap, launch_apply); break;
+                case OP_SPECTRAL: go(op.sp, launch_spectral); break;
+                case OP_FCOMBINE: go(op.fc, launch_fourier_combine); break;
+                case OP_VECLIN: go(op.vl, launch_vec_linear); break;
                 case OP_TRACE: {
                     if (!e->trace_on) break;
                     const float* p = as_ptr<const float>(op.t_ptr);
                     long bs = op.t_bs;
-                    fix(p, B); fixbs(bs, B);
+                    if (!fix(p, B)) break;
+                    fixbs(bs, B);
                     HIPCHK(e, hipStreamSynchronize(stream));
                     TraceRec r;
                     r.name = op.name; r.B = plan.B; r.C = op.tC; r.H = op.tH; r.W = op.tW;
@@ -2849,33 +2727,19 @@ int lns_op_conv2d(const float* x, int B, int Cin, int Hin, int Win, int Hv, int 
     oc.a.amax_out = amax_out;
     hipStream_t s = static_cast<hipStream_t>(stream);
 #ifdef LNS_TS
-    // diagnostic build: per-block phase timestamps of the split-operand 3x3 kernel, appended to $LNS_TS_FILE
+    // diagnostic build: per-block phase timestamps of the split-operand kernels, appended to $LNS_TS_FILE
     const long nblk = (long)oc.a.tiles_x * oc.a.tiles_y * oc.a.cout_tiles * oc.a.B;     // an upper bound for the input-stationary 1x1 form
-    long long* dts = nullptr;
-    if (getenv("LNS_TS_FILE") && (cv_is_split_3x3(oc.variant) || oc.variant == CV_B1)) {
-        OPCHK(hipMalloc(reinterpret_cast<void**>(&dts), nblk * 64));
-        OPCHK(hipMemset(dts, 0, nblk * 64));
+    hipError_t lrc = hipSuccess;
+    if ((cv_is_split_3x3(oc.variant) || oc.variant == CV_B1) &&
+        ts_capture(nblk, 8, fmt("# launch B=%d Cin=%d Cout=%d H=%d W=%d blocks=%ld", B, Cin, Cout, Hv, Wv, nblk), s, lrc,
+                   [&](long long* ts) { oc.a.dbg_ts = ts; return launch_conv(oc.variant, oc.a, s); })) {
+        oc.release();
+        OPCHK(lrc);
+        return LNS_OK;
     }
-    oc.a.dbg_ts = dts;
 #endif
     OPCHK(launch_conv(oc.variant, oc.a, s));
     OPCHK(hipStreamSynchronize(s));
-#ifdef LNS_TS
-    if (dts) {
-        std::vector<long long> h(nblk * 8);
-        OPCHK(hipMemcpy(h.data(), dts, nblk * 64, hipMemcpyDeviceToHost));
-        (void)hipFree(dts);
-        if (FILE* f = fopen(getenv("LNS_TS_FILE"), "a")) {
-            fprintf(f, "# launch B=%d Cin=%d Cout=%d H=%d W=%d blocks=%ld\n", B, Cin, Cout, Hv, Wv, nblk);
-            for (long i = 0; i < nblk; ++i) {
-                fprintf(f, "%ld", i);
-                for (int k = 0; k < 8; ++k) fprintf(f, " %lld", h[i * 8 + k]);
-                fprintf(f, "\n");
-            }
-            fclose(f);
-        }
-    }
-#endif
     oc.release();
     return LNS_OK;
 }

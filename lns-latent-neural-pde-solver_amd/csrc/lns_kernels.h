@@ -8,6 +8,12 @@ namespace lns {
 
 enum Act { ACT_NONE = 0, ACT_SWISH = 1, ACT_GELU = 2, ACT_RELU = 3, ACT_TANH = 4, ACT_SIGMOID = 5 };
 
+// Under every argument block a launch plan can hold, for_each_ptr names each pointer member once and for_each_stride each batch
+// stride that may hold an external-slot sentinel (< 0): the planner's rebase and the runner's resolution (lns_resolve.h) walk these
+// lists and nothing else.  The size assert sends whoever adds a member past the list; dbg_ts is set at the launch site, not listed.
+template <class A, class F> void for_each_stride(A&, F&&) {}     // blocks without a batch stride of that kind
+#define LNS_ARGS_SIZE(T, n) static_assert(sizeof(T) == (n), "member added to " #T ": list it in for_each_ptr if it is a pointer, in for_each_stride if it is a tagged batch stride")
+
 // ---------------------------------------------------------------------------
 // fused implicit-GEMM convolution on fp32 MFMA (v_mfma_f32_32x32x2_f32)
 //   y = act_out(conv(act_in(x*scale+shift)) + bias + badd) + residual
@@ -104,6 +110,16 @@ struct ConvArgs {
     long long* dbg_ts;     // diagnostic build only: [blocks][8] phase timestamps (100 MHz wall clock) + hardware ids
 #endif
 };
+template <class F> void for_each_ptr(ConvArgs& a, F&& f) {
+    f(a.x); f(a.w); f(a.bias); f(a.ss); f(a.rowmap); f(a.colmap); f(a.y); f(a.res); f(a.badd); f(a.w2); f(a.bias2); f(a.wb);
+    f(a.gn_part); f(a.gn_gamma); f(a.gn_beta); f(a.gn_premul); f(a.stat_part); f(a.amax_in); f(a.amax_out);
+}
+template <class F> void for_each_stride(ConvArgs& a, F&& f) { f(a.x_bs); f(a.y_bs); f(a.res_bs); }
+#ifdef LNS_TS
+LNS_ARGS_SIZE(ConvArgs, 408);
+#else
+LNS_ARGS_SIZE(ConvArgs, 400);
+#endif
 // power-of-two activation scale from a bound on |x| (host mirror of the device rule; tests)
 float convf_scale_for_bound(float bound);
 
@@ -172,6 +188,9 @@ struct GnStatsArgs {
     float* ss;                               // [B][C][2]
     int B;
 };
+template <class F> void for_each_ptr(GnStatsArgs& a, F&& f) { f(a.x); f(a.gamma); f(a.beta); f(a.premul); f(a.ss); }
+template <class F> void for_each_stride(GnStatsArgs& a, F&& f) { f(a.x_bs); }
+LNS_ARGS_SIZE(GnStatsArgs, 72);
 // part: [B][C][2] scratch enabling the two-stage path (may be null)
 bool gn_stats_two_stage(const GnStatsArgs& a);
 hipError_t launch_gn_stats(const GnStatsArgs& a, float* part, hipStream_t s);
@@ -191,17 +210,25 @@ struct LnPeArgs {
     float* h;                                // [B][C][n]
     int B;
 };
+template <class F> void for_each_ptr(LnPeArgs& a, F&& f) { f(a.x); f(a.gamma); f(a.beta); f(a.pe_t); f(a.h); }
+template <class F> void for_each_stride(LnPeArgs& a, F&& f) { f(a.x_bs); }
+LNS_ARGS_SIZE(LnPeArgs, 80);
 hipError_t launch_ln_pe(const LnPeArgs& a, hipStream_t s);
 
 // softmax attention, channel-major qkv [B, 3*heads*D, n] -> o [B, heads*D, n]
 struct AttnArgs { const float* qkv; int B, heads, D, n; float scale; float* o;
                   const unsigned* amax_in; };   // [B][LNS_AMAX_SUB] max |qkv| per sample or null: enables the f16x2 form
+template <class F> void for_each_ptr(AttnArgs& a, F&& f) { f(a.qkv); f(a.o); f(a.amax_in); }
+LNS_ARGS_SIZE(AttnArgs, 48);
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 
 // FABlock2D pieces ----------------------------------------------------------
 // x [B,C,H,W] (batch stride x_bs floats), ss [B][C][2] (scale, shift) or null = identity:
 // mx [B,H,C] = scale * mean over W + shift, my [B,W,C] = scale * mean over H + shift
 struct FaPoolArgs { const float* x; long x_bs; const float* ss; int B, C, H, W; float* mx; float* my; };
+template <class F> void for_each_ptr(FaPoolArgs& a, F&& f) { f(a.x); f(a.ss); f(a.mx); f(a.my); }
+template <class F> void for_each_stride(FaPoolArgs& a, F&& f) { f(a.x_bs); }
+LNS_ARGS_SIZE(FaPoolArgs, 56);
 hipError_t launch_fa_pool(const FaPoolArgs& a, hipStream_t s);
 
 struct FaReducerArgs {                 // PoolingReducer on pooled rows [rows, C]
@@ -219,6 +246,11 @@ struct FaReducerArgs {                 // PoolingReducer on pooled rows [rows, C
     const float* bqk;                  // [Mqk] or null
     int Mqk; float* qk;
 };
+// (the fused to_qk members are listed for both launch forms; the planner leaves them null: fill_reducer)
+template <class F> void for_each_ptr(FaReducerArgs& a, F&& f) {
+    f(a.m); f(a.win_t); f(a.ln_g); f(a.ln_b); f(a.w1_t); f(a.w2_t); f(a.b2); f(a.u); f(a.amax_out); f(a.wqk_t); f(a.bqk); f(a.qk);
+}
+LNS_ARGS_SIZE(FaReducerArgs, 136);
 hipError_t launch_fa_reducer(const FaReducerArgs& a, hipStream_t s);
 // both axes (x: rows = B*H, y: rows = B*W) of one FABlock in ONE launch
 hipError_t launch_fa_reducer2(const FaReducerArgs& ax, const FaReducerArgs& ay, hipStream_t s);
@@ -229,6 +261,8 @@ struct FaLrkArgs {                     // rotary + q k^T
     const float* cs;                   // [DK/2][n][2] (cos, sin), frequency-major
     float* kmat;                       // [B, heads, n, n]
 };
+template <class F> void for_each_ptr(FaLrkArgs& a, F&& f) { f(a.qk); f(a.cs); f(a.kmat); }
+LNS_ARGS_SIZE(FaLrkArgs, 40);
 hipError_t launch_fa_lrk(const FaLrkArgs& a, hipStream_t s);
 hipError_t launch_fa_lrk2(const FaLrkArgs& ax, const FaLrkArgs& ay, hipStream_t s);   // both axes in one launch
 
@@ -239,6 +273,8 @@ struct FaSandwichArgs {
     int b_rev;                         // f16x2 form: walk the samples in reverse launch order (scheduling only)
     int b0;                            // batch-chunked launch: samples b0 .. b0 + B - 1 (ConvArgs::b0)
 };
+template <class F> void for_each_ptr(FaSandwichArgs& a, F&& f) { f(a.u); f(a.kx); f(a.ky); f(a.out); f(a.amax_u); }
+LNS_ARGS_SIZE(FaSandwichArgs, 80);
 hipError_t launch_fa_sandwich(const FaSandwichArgs& a, hipStream_t s);
 size_t fa_sandwich_lds_bytes(int H, int W);
 
@@ -259,6 +295,11 @@ struct FaFusedArgs {
     int gpb;               // plane groups (of 16) one block walks: Kx / Ky of the (sample, head) are staged once for them
     long long* dbg_ts;     // -DFAF_TS builds: [blocks][24] phase timestamps of wave 0 (null otherwise)
 };
+template <class F> void for_each_ptr(FaGsplitArgs& a, F&& f) { f(a.x); f(a.ss); f(a.gs); f(a.amax_out); }
+template <class F> void for_each_stride(FaGsplitArgs& a, F&& f) { f(a.x_bs); }
+LNS_ARGS_SIZE(FaGsplitArgs, 64);
+template <class F> void for_each_ptr(FaFusedArgs& a, F&& f) { f(a.gs); f(a.amax_g); f(a.wp); f(a.kx); f(a.ky); f(a.out); }
+LNS_ARGS_SIZE(FaFusedArgs, 120);
 bool fa_fused_fits(int H, int W, int Cin, int dim_head);
 size_t fa_fused_gs_bytes(int B, int H, int W, int Cin);
 size_t fa_fused_weight_bytes(int planes, int Cin);
@@ -275,6 +316,8 @@ struct CondBaseArgs {            // ce = W2 act(W0 fourier_embedding(param) + b0
     int Hd;                      // hidden width (0: E)
     int act;                     // ACT_GELU (conditional propagator) / ACT_SWISH (CondEncoder.embed)
 };
+template <class F> void for_each_ptr(CondBaseArgs& a, F&& f) { f(a.param); f(a.freqs); f(a.w0_t); f(a.b0); f(a.w2_t); f(a.b2); f(a.ce); }
+LNS_ARGS_SIZE(CondBaseArgs, 72);
 hipError_t launch_cond_base(const CondBaseArgs& a, hipStream_t s);
 struct CondBlockArgs {           // emb = Wce ce + bce ; mul = 1 + conv1(gelu(conv1(GN1(emb))))
     const float* ce; int B, E, D;
@@ -284,10 +327,17 @@ struct CondBlockArgs {           // emb = Wce ce + bce ; mul = 1 + conv1(gelu(co
     const float* c3_t; const float* c3_b;
     float* emb; float* mul;                        // [B][D]
 };
+template <class F> void for_each_ptr(CondBlockArgs& a, F&& f) {
+    f(a.ce); f(a.wce_t); f(a.bce); f(a.gn_g); f(a.gn_b); f(a.c1_t); f(a.c1_b); f(a.c3_t); f(a.c3_b); f(a.emb); f(a.mul);
+}
+LNS_ARGS_SIZE(CondBlockArgs, 104);
 hipError_t launch_cond_block(const CondBlockArgs& a, hipStream_t s);
 
 // y = act(x * scale[b,c] + shift[b,c])  (materialises a pending GroupNorm + activation)
 struct ApplyArgs { const float* x; long x_bs; const float* ss; int act; float* y; int B, C, HW; unsigned* amax_out; };
+template <class F> void for_each_ptr(ApplyArgs& a, F&& f) { f(a.x); f(a.ss); f(a.y); f(a.amax_out); }
+template <class F> void for_each_stride(ApplyArgs& a, F&& f) { f(a.x_bs); }
+LNS_ARGS_SIZE(ApplyArgs, 64);
 hipError_t launch_apply(const ApplyArgs& a, hipStream_t s);
 
 // Fourier blocks (opt-in): truncated DFT as dense contractions --------------------
@@ -302,14 +352,22 @@ struct SpectralArgs {
     float* of;                            // [B][Cout][2*m1][m2][2]
     float* y;                             // [B][Cout][H][W]
 };
+template <class F> void for_each_ptr(SpectralArgs& a, F&& f) { f(a.x); f(a.w1); f(a.w2); f(a.emb); f(a.t1); f(a.xf); f(a.of); f(a.y); }
+template <class F> void for_each_stride(SpectralArgs& a, F&& f) { f(a.x_bs); }
+LNS_ARGS_SIZE(SpectralArgs, 104);
 hipError_t launch_spectral(const SpectralArgs& a, hipStream_t s);
 
 // y = [skip +] act(a + b + e[b,c])     (skip null: residual=False; act 0: GELU)
 struct FourierCombineArgs { const float* a; const float* b; const float* e; const float* skip; long skip_bs; float* y; long y_bs; int B, C, HW; unsigned* amax_out; int act; };
+template <class F> void for_each_ptr(FourierCombineArgs& a, F&& f) { f(a.a); f(a.b); f(a.e); f(a.skip); f(a.y); f(a.amax_out); }
+template <class F> void for_each_stride(FourierCombineArgs& a, F&& f) { f(a.skip_bs); f(a.y_bs); }
+LNS_ARGS_SIZE(FourierCombineArgs, 88);
 hipError_t launch_fourier_combine(const FourierCombineArgs& a, hipStream_t s);
 
 // out[b,o] = bias[o] + sum_i in[b,i] * w[i*ldo + o*ldi]   (tiny dense layer on per-sample vectors)
 struct VecLinearArgs { const float* in; const float* w; const float* bias; float* out; int B, In, Out, ldi, ldo; };
+template <class F> void for_each_ptr(VecLinearArgs& a, F&& f) { f(a.in); f(a.w); f(a.bias); f(a.out); }
+LNS_ARGS_SIZE(VecLinearArgs, 56);
 hipError_t launch_vec_linear(const VecLinearArgs& a, hipStream_t s);
 
 // fused denormalise + relative-L2 metric of a rollout (scratch: B*T*C*2 floats)

@@ -13,14 +13,15 @@ B = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 64
 args, model, sd = bench.build_model(preset, torch.device("cuda", 0))
 x = torch.from_numpy(filler.normal("x", (B, args.in_channels, args.Ly, args.Lx), 5)).cuda()
+param = torch.from_numpy(filler.uniform01("param", B, 5).astype("float32")).cuda() if args.family == "twophase_cond" else None
 eng = model._engine(x)
 out = torch.empty((B, T, args.in_channels, args.Ly, args.Lx), device="cuda")
 for _ in range(2):
-    eng.rollout(x, T, to_x=True, out=out)
+    eng.rollout(x, T, param=param, to_x=True, out=out)
 torch.cuda.synchronize()
 for it in range(5):
     t0 = time.perf_counter()
-    eng.rollout(x, T, to_x=True, out=out)
+    eng.rollout(x, T, param=param, to_x=True, out=out)
     t1 = time.perf_counter()
     torch.cuda.synchronize()
     t2 = time.perf_counter()

@@ -6,7 +6,13 @@ rollout_latent_ensemble with M = 3 members where the library has it) under
 decode_group {default, 1, 2, automatic} x decode_streams {1, 2} x overlap {0, 1}, at B = 2, T = 7 (decode_group = 2: a ragged last
 group), keep_steps = [1, 4, 6], on the shapes of the ns2d_mini, twophase_cond and sw_half_periodic fixtures with inputs
 from `filler`; plus "launches/<call>" -> {kernel class: launches} of one rollout, one rollout(keep_steps=...) and one
-rollout_eval of ns2d_mini under timing_enable(True).  Two builds that enqueue the same work print the same object.
+rollout_eval of ns2d_mini under timing_enable(True).  Then, so that every kind of launch a plan can hold is reached, with the
+library's default options only: the ns2d_mini variants with self-attention, an attention encoder, Fourier blocks and two
+residual blocks per level and the unconditional two-phase model (EXTRA), and ns2d_64 (the smallest preset whose FABlock fits
+the fused kernel: 32 x 32 planes, 128 channels) under fa_fused 0 (plain sandwich), fa_fused 2 (input split + fused kernel) and
+fa_fused 0 with fa_chunk_mb 1 (the in_proj -> sandwich -> to_out chain re-issued per sample); "classes/<case>[/<options>]" ->
+{kernel class or class/form: launches} of one rollout of each case.  The tool fails if a kernel class of the library is
+launched by none of them.  Two builds that enqueue the same work print the same object.
 
     python tools/rollout_bits.py [--out FILE]
 """
@@ -15,6 +21,7 @@ import hashlib
 import itertools
 import json
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,6 +33,9 @@ import torch  # noqa: E402
 from lns_amd import config, dropin, filler  # noqa: E402
 
 CASES = ("ns2d_mini", "twophase_cond", "sw_half_periodic")
+EXTRA = ("ns2d_mini_sa", "ns2d_mini_attn_enc", "ns2d_mini_attn_enc_sa", "ns2d_mini_fourier", "ns2d_mini_res2", "twophase")
+FA_CASE = "ns2d_64"
+FA_OPTIONS = (dict(fa_fused=0, fa_chunk_mb=0), dict(fa_fused=2, fa_chunk_mb=0), dict(fa_fused=0, fa_chunk_mb=1))
 B, T = 2, 7
 KEEP = [1, 4, 6]
 CHUNKS = ((0, 4, [1]), (4, 3, [0, 2]))              # (t0, steps, keep_steps of the chunk): KEEP again
@@ -39,6 +49,7 @@ def sha(t):
 
 
 def setup(name):
+    print("case", name, file=sys.stderr, flush=True)
     d = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
     meta = json.loads(bytes(d["meta"]).decode())
     args = config.preset(meta["preset"], **meta["overrides"])
@@ -93,6 +104,16 @@ def launches(eng, x, y):
     return rec
 
 
+def classes(eng, x, p):
+    """{kernel class or class/form: launches} of one rollout (timing mode: everything on the caller's stream)."""
+    eng.timing_enable(True)
+    eng.rollout(x, T, param=p)
+    torch.cuda.synchronize()
+    rec = {k: v["launches"] for k, v in sorted(eng.timing().items())}
+    eng.timing_enable(False)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -111,11 +132,26 @@ def main():
             for k, v in (("decode_group", 1), ("decode_streams", 3), ("overlap", 1)):      # the library's defaults
                 eng.set_option(k, v)
             rec.update(launches(eng, x, y))
+        rec["classes/" + case] = classes(eng, x, p)
+    for case in EXTRA + (FA_CASE,):
+        eng, x, y, p = setup(case)
+        for opts in (FA_OPTIONS if case == FA_CASE else ({},)):
+            for k, v in opts.items():
+                eng.set_option(k, v)
+            suffix = "".join("/%s%d" % kv for kv in sorted(opts.items()))
+            for name, tensors in entries(eng, x, y, p):
+                torch.cuda.synchronize()
+                rec["%s/%s/default%s" % (case, name, suffix)] = {k: sha(t) for k, t in tensors.items()}
+            rec["classes/" + case + suffix] = classes(eng, x, p)
+    reached = {k for key, c in rec.items() if key.startswith("classes/") for k, n in c.items() if "/" not in k and n > 0}
+    src = open(os.path.join(ROOT, "lns-latent-neural-pde-solver_amd", "csrc", "lns_engine.cpp")).read()
+    every = set(re.findall(r'"([^"]+)"', re.search(r"kClsName\[CLS_COUNT\] = \{([^}]*)\}", src).group(1)))
     text = json.dumps(rec, indent=1, sort_keys=True)
     if a.out:
         with open(a.out, "w") as f:
             f.write(text + "\n")
     print(text)
+    assert reached == every, "kernel classes no case launches: %s" % sorted(every - reached)
 
 
 if __name__ == "__main__":
