@@ -318,6 +318,49 @@ int lns_rollout_latent_eval(lns_engine* e, const float* z_in, const float* param
                             const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- ensemble validation: streaming CRPS, spread / skill and rank histograms -------------------------------------
+ * lns_rollout_latent_ensemble with the members scored against the truth where they are decoded: is the spread calibrated
+ * (spread against rmse), is the ensemble mean better than one forecast (rmse, rel_l2), does the truth fall inside the
+ * members (rank histogram), and the fair CRPS -- all of which need the M member values and the truth of a pixel at the
+ * same time, i.e. the [B*M, n_keep, Cin, Ly, Lx] tensor the ensemble call exists to avoid.  The chain, the kept steps, the
+ * frame buffers and the workspace are those of lns_rollout_latent_ensemble; a scoring kernel follows the decode of a group
+ * on its decode stream (one block per plane), and a finish kernel runs once on the caller's stream after the join.
+ *
+ * Every frame is denormalised as lns_eval_spec says, members and truth by the same map D_c of channel c:
+ *     per_channel = 0:  D_c(x) = x * std + mean
+ *     per_channel = 1:  x * std_c + mean_c, then 0 on the four wall rows / columns under flag 1, then
+ *                       fminf(fmaxf(., clamp_lo), clamp_hi) under flag 2
+ * For one pixel, v_m = D_c(f_m), q = D_c(y); fp32, nothing fused (the product and the sum of D_c included), m ascending:
+ *     s = v_0; s = s + v_m (m = 1 .. M-1);  mu = s / (float)M
+ *     d_m = v_m - mu;  sd = sum d_m;  qq = sum d_m * d_m;  var = (qq - sd * sd / (float)M) / (float)(M - 1)
+ *     e = mu - q;  se = e * e;  g = q * q
+ *     a = sum_m |v_m - q|
+ *     w = 0; for m = 0 .. M-2: for n = m+1 .. M-1: w = w + |v_m - v_n|          (one running sum, in this order)
+ *     crps = a / (float)M - w / (float)(M * (M - 1))                            (the fair CRPS)
+ *     rank = #{ m : v_m < q }                                                   (0 .. M; a NaN compares false)
+ * (sd, qq, a and w start from 0.)  Per plane (b, kept step i, c) four fp32 sums over its H * W pixels, SE = sum se, G = sum g,
+ * V = sum var, CR = sum crps, in the order of the metric kernels: thread t of 256 adds pixels t, t + 256, ... in ascending
+ * order, then the wave sum, then (w0 + w1) + (w2 + w3) over the four waves.  One block owns one plane, so every slot has one
+ * writer: no float atomics, nothing depends on the grouping or the scheduling options.  The rank histogram of a plane is M + 1
+ * int32 counts (integer LDS atomics: order-independent).  The finish kernel turns the sums, in place, into
+ *     rel_l2 = sqrtf(SE / (G < eps ? eps : G)),  rmse = sqrtf(SE / HW),  spread = sqrtf(V / HW),  crps = CR / HW
+ * (HW = (float)(H * W)) and, per (b, c), over the kept steps in ascending order, into seq_out:
+ *     sqrtf(sum SE / (sum G < eps ? eps : sum G)),  sqrtf(sum SE / N),  sqrtf(sum V / N),  sum CR / N,   N = (float)(n_keep * H * W)
+ * A calibrated ensemble has spread * sqrt((M + 1) / M) / rmse near 1.
+ *
+ * z_in, param, keep_steps_host, z_last, B, M, T: as lns_rollout_latent_ensemble, with 2 <= M <= 128.
+ * y_true [B][n_keep][Cin][Ly][Lx]: the normalised truth of the KEPT steps.  mean_out / var_out (both nullable; var_out
+ * needs mean_out): lns_rollout_latent_ensemble's outputs, same bits; the reduction kernel runs only when mean_out is given.
+ * workspace: lns_rollout_ensemble_workspace_bytes(B, M), no more (the plane sums live in scores_out until the finish kernel).
+ * Trace / timing modes, lns_check_finite (with B*M) and the status codes: as lns_rollout_latent_ensemble. */
+int lns_rollout_latent_ensemble_eval(lns_engine* e, const float* z_in, const float* param, const float* y_true,
+                                     int B, int M, int T, const int* keep_steps_host, int n_keep, const lns_eval_spec* spec,
+                                     float* scores_out,   /* [B][n_keep][Cin][4]: rel_l2, rmse, spread, crps */
+                                     float* seq_out,      /* nullable [B][Cin][4] */
+                                     int32_t* rank_out,   /* nullable [B][n_keep][Cin][M+1] */
+                                     float* mean_out, float* var_out, float* z_last,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* Post-run health check.  Every kernel of a plan records, per sample, the running maximum of |y| of the tensor it
  * produces (the side channel from which the split-operand convolutions derive their activation scale); a NaN or inf
  * anywhere in a tensor survives in it.  This call synchronises `stream`, reads those few KB back from `workspace`
@@ -504,7 +547,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * batch-parallel weight gradient (option "train_wgrad", lns_op_conv_wgrad) is there; "train_clip" = lns_train_step_clip and
  * the gradient-norm / update calls are there; "train_ops" = lns_op_groupnorm_train, lns_op_gelu_grad and lns_op_bias_grad
  * are there; "rollout_select" = lns_rollout_select & co. are there; "rollout_ensemble" = lns_rollout_latent_ensemble,
- * its size query and lns_op_ensemble_stats are there.  1 / 0; -1: unknown name.
+ * its size query and lns_op_ensemble_stats are there; "ensemble_score" = lns_rollout_latent_ensemble_eval and
+ * lns_op_ensemble_score are there.  1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
 
@@ -571,6 +615,15 @@ int lns_op_bias_grad(const float* dy, int B, int C, int HW, float* db, int accum
  * B in 1..65535, M in 1..65536, per in 1..2^40.  Checks precede the launch (message: lns_create_error()); the call
  * synchronises `stream`. */
 int lns_op_ensemble_stats(const float* frames, int B, int M, int64_t per, float* mean, float* var /* nullable */, void* stream);
+
+/* The two kernels of lns_rollout_latent_ensemble_eval on stored member fields, without an engine: frames
+ * [n][B][M][C][H][W] (the layout of a frame buffer), y [B][n][C][H][W] -> scores_out [B][n][C][4], seq_out (nullable)
+ * [B][C][4], rank_out (nullable) [B][n][C][M+1] by the statement written there.  pixel_out (nullable, for tests)
+ * [n][B][C][H*W][4]: mu, var, crps and (float)rank of every pixel.  2 <= M <= 128, B in 1..65535, n * B * C < 2^31; the
+ * per-channel form needs C <= 8.  Checks precede the launch (message: lns_create_error()); the call synchronises `stream`. */
+int lns_op_ensemble_score(const float* frames, const float* y, int n, int B, int M, int C, int H, int W,
+                          const lns_eval_spec* spec, float* scores_out, float* seq_out, int32_t* rank_out,
+                          float* pixel_out, void* stream);
 
 /* GroupNorm statistics -> per-(b,c) (scale,shift) such that norm(x) = x*scale+shift. */
 int lns_op_groupnorm_stats(const float* x, int B, int C, int HW, int groups, float eps,

@@ -1741,7 +1741,8 @@ struct Runner {
 //                 of the steps keep[0 .. n_keep) are copied to frames_out
 //   SINK_ENSEMBLE the chain runs at batch N = B * M (launch sample b * M + m is member m of trajectory b); the steps
 //                 keep[0 .. n_keep) are decoded into a frame buffer of the workspace and reduced over the members right there
-//                 into `out` (mean) and `var_out` [B][n_keep][xper]
+//                 into `out` (mean) and `var_out` [B][n_keep][xper]; with `scores_out` (lns_rollout_latent_ensemble_eval) also
+//                 scored there against y_true, and `out` may be null
 enum SinkKind { SINK_LATENTS, SINK_STEPS, SINK_KEPT, SINK_SCORED, SINK_ENSEMBLE };
 
 // workspace layout: [ z0 | latent ring: NGROUP groups x kdec steps x [B][zper] | NDEC decode arenas | propagator arena ]
@@ -1831,6 +1832,8 @@ struct RolloutCall {
     const int* keep = nullptr; int n_keep = 0;           // SINK_KEPT, SINK_ENSEMBLE (n_keep >= 1), SINK_SCORED (n_keep >= 0); host, ascending
     // SINK_ENSEMBLE: B above is the chain's batch N = traj * M (clipped to int; 0 when either factor is not positive)
     int traj = 0, M = 0; float* var_out = nullptr;
+    // SINK_ENSEMBLE with ens_scored: y_true [traj][n_keep], spec and seq_out below; the plane sums go straight into scores_out
+    bool ens_scored = false; float* scores_out = nullptr; int32_t* rank_out = nullptr;
     // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
     const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
     float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
@@ -2170,6 +2173,17 @@ int lns_propagate(lns_engine* e, const float* z_in, const float* param, int B, i
     return run_single(e, PK_PROP, B, H, W, ext, ws, ws_bytes, stream);
 }
 
+// the per-channel part of an lns_eval_spec as the kernels take it (as lns_metric_rel_l2_ch fills it)
+static void channel_spec(const lns_eval_spec* spec, int C, MetricChannelSpec* out) {
+    for (int ch = 0; ch < LNS_METRIC_MAX_CH; ++ch) {
+        const bool in = ch < C;
+        out->mean[ch] = in ? spec->mean_c[ch] : 0.0f;
+        out->std[ch] = in ? spec->std_c[ch] : 1.0f;
+        out->flags[ch] = in ? spec->flags_c[ch] : 0;
+    }
+    out->lo = spec->clamp_lo; out->hi = spec->clamp_hi;
+}
+
 // the scoring kernel's arguments for a SINK_SCORED call; frames / kk / y_t / p_t are set per decoded group
 static void metric_args(const lns_engine* e, const RolloutCall& c, const WsLayout& L, MetricGroupArgs* mp) {
     MetricGroupArgs& m = *mp;
@@ -2179,13 +2193,17 @@ static void metric_args(const lns_engine* e, const RolloutCall& c, const WsLayou
     m.y_T = c.T_total; m.y_t = 0; m.p_T = c.T_total; m.p_t = 0;
     m.per_channel = spec->per_channel != 0;
     m.mean = spec->mean; m.sd = spec->std;
-    for (int ch = 0; ch < LNS_METRIC_MAX_CH; ++ch) {       // as lns_metric_rel_l2_ch fills it
-        const bool in = ch < m.C;
-        m.spec.mean[ch] = in ? spec->mean_c[ch] : 0.0f;
-        m.spec.std[ch] = in ? spec->std_c[ch] : 1.0f;
-        m.spec.flags[ch] = in ? spec->flags_c[ch] : 0;
-    }
-    m.spec.lo = spec->clamp_lo; m.spec.hi = spec->clamp_hi;
+    channel_spec(spec, m.C, &m.spec);
+}
+
+// the same for the scoring kernel of a scored SINK_ENSEMBLE call; frames / kk / y_t are set per decoded group
+static void score_args(const lns_engine* e, const RolloutCall& c, EnsembleScoreArgs* sp) {
+    EnsembleScoreArgs& s = *sp;
+    s.frames = nullptr; s.y = c.y_true; s.scores = c.scores_out; s.rank = c.rank_out; s.pixel = nullptr;
+    s.B = c.traj; s.M = c.M; s.C = e->cfg.in_channels; s.H = e->cfg.Ly; s.W = e->cfg.Lx; s.kk = 0; s.y_T = c.n_keep; s.y_t = 0;
+    s.per_channel = c.spec->per_channel != 0;
+    s.mean = c.spec->mean; s.sd = c.spec->std;
+    channel_spec(c.spec, s.C, &s.spec);
 }
 
 // the autoregressive loop of every rollout call: zcur -> T x (propagate ; what the sink does)   (train_stage2_ns2d.py:147-156)
@@ -2245,6 +2263,8 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     std::vector<char> used(ngroup, 0);
     MetricGroupArgs m;
     if (scored) metric_args(e, c, L, &m);
+    EnsembleScoreArgs sc;
+    if (ens && c.ens_scored) score_args(e, c, &sc);
     // A decode group is the next up to kdec DECODED steps: all steps, the kept ones, or none.  The chain writes the
     // latent of a decoded step into the group's next ring slot; the latent of a step nobody decodes goes into `out`
     // (SINK_LATENTS) or into the two ping-pong buffers in turn (SINK_KEPT, SINK_ENSEMBLE), so a step never writes the buffer it reads.
@@ -2304,7 +2324,11 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
                                            fb + (long)(c.keep[ki] - t0g) * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
                                            hipMemcpyDeviceToDevice, dstream[d]));
         }
-        if (ens) {                                   // fb is [kk][traj][M][xper] -> mean / var of out[b][i0 .. i0 + kk)
+        if (ens && c.ens_scored) {                   // fb is [kk][traj][M][xper] against y_true[b][i0 .. i0 + kk)
+            sc.frames = fb; sc.kk = kk; sc.y_t = i0;
+            HIPCHK(e, launch_ensemble_score(sc, dstream[d]));
+        }
+        if (ens && c.out) {                          // fb is [kk][traj][M][xper] -> mean / var of out[b][i0 .. i0 + kk)
             EnsembleStatsArgs es;
             es.frames = fb; es.mean = c.out + (long)i0 * xper; es.var = c.var_out ? c.var_out + (long)i0 * xper : nullptr;
             es.per = xper; es.out_bs = (long)n_dec * xper; es.B = c.traj; es.M = c.M; es.kk = kk;
@@ -2345,23 +2369,31 @@ static int check_keep_steps(lns_engine* e, const int* keep, int n_keep, int T) {
 // interface (which of two failing checks answers): arguments, batch, eval_max_steps, the model, param.
 static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
     const bool scored = c.sink == SINK_SCORED, ens = c.sink == SINK_ENSEMBLE, kept = c.sink == SINK_KEPT || ens;
+    const bool ens_scored = ens && c.ens_scored;     // lns_rollout_latent_ensemble_eval: every output but scores_out is optional
     if (!c.start) return einval(e, c.encode ? "x is null" : "z_in is null");
-    if (scored && !c.y_true) return einval(e, "y_true is null");
-    if (!scored && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
+    if ((scored || ens_scored) && !c.y_true) return einval(e, "y_true is null");
+    if (ens_scored && !c.scores_out) return einval(e, "scores_out is null");
+    if (!scored && !ens_scored && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
     if ((ens ? c.traj : c.B) <= 0) return einval(e, "B must be positive");
     if (ens && c.M <= 0) return einval(e, "M must be positive");
     if (c.T <= 0) return einval(e, "T must be positive");
     if (ens && c.var_out && c.M < 2) return einval(e, "var_out needs M >= 2");
+    if (ens_scored) {
+        if (c.M < 2 || c.M > LNS_SCORE_MAX_MEMBERS) return einval(e, "ensemble scoring needs M in 2 .. 128");
+        if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
+    }
     if (scored) {
         if (c.t0 < 0 || (long)c.t0 + c.T > c.T_total) {
             e->err = fmt("t0 + T = %d + %d exceeds T_total = %d (or t0 < 0)", c.t0, c.T, c.T_total);
             return LNS_EINVAL;
         }
         if (!c.frame_out && !c.seq_out) return einval(e, "frame_out and seq_out are both null");
+    }
+    if (scored || ens_scored) {
         if (!c.spec || c.spec->size != sizeof(lns_eval_spec)) return einval(e, "spec is null or its size field is not sizeof(lns_eval_spec)");
         if (c.spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "spec: the per-channel form needs in_channels <= 8");
-        if (c.n_keep < 0) return einval(e, "n_keep is negative");
     }
+    if (scored && c.n_keep < 0) return einval(e, "n_keep is negative");
     if (kept && c.n_keep < 1) return einval(e, "n_keep must be at least 1 (for no decoded step: lns_rollout with to_x = 0)");
     if ((scored || kept) && c.n_keep > 0) {
         if (!c.keep) return einval(e, scored ? "keep_steps is null but n_keep > 0" : "keep_steps is null");
@@ -2411,6 +2443,9 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if (scored && c.t0 + c.T == c.T_total)
         HIPCHK(e, launch_metric_finish(reinterpret_cast<float*>(base + L.part_off), c.B, c.T_total, cfg.in_channels, c.spec->eps,
                                        c.frame_out, c.seq_out, r.stream));
+    if (c.sink == SINK_ENSEMBLE && c.ens_scored)     // likewise: the plane sums in scores_out -> the scores, in place
+        HIPCHK(e, launch_ensemble_score_finish(c.scores_out, c.traj, c.n_keep, cfg.in_channels, cfg.Ly * cfg.Lx, c.spec->eps,
+                                               c.seq_out, r.stream));
     return r.finish();
 }
 
@@ -2476,6 +2511,18 @@ int lns_rollout_latent_ensemble(lns_engine* e, const float* z_in, const float* p
                                 void* ws, size_t ws_bytes, void* stream) {
     RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
     c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
+    c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
+    return rollout_call(e, c);
+}
+
+// ---- ensemble validation (include/lns.h) ------------------------------------------------------------------------
+int lns_rollout_latent_ensemble_eval(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int M, int T,
+                                     const int* keep_steps_host, int n_keep, const lns_eval_spec* spec, float* scores_out,
+                                     float* seq_out, int32_t* rank_out, float* mean_out, float* var_out, float* z_last,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
+    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
+    c.ens_scored = true; c.y_true = y_true; c.spec = spec; c.scores_out = scores_out; c.seq_out = seq_out; c.rank_out = rank_out;
     c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
     return rollout_call(e, c);
 }
@@ -2573,6 +2620,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "train_ops")) return 1;
     if (!strcmp(feature, "rollout_select")) return 1;
     if (!strcmp(feature, "rollout_ensemble")) return 1;
+    if (!strcmp(feature, "ensemble_score")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else
@@ -2838,6 +2886,32 @@ int lns_op_ensemble_stats(const float* frames, int B, int M, int64_t per, float*
     EnsembleStatsArgs a;
     a.frames = frames; a.mean = mean; a.var = var; a.per = (long)per; a.out_bs = (long)per; a.B = B; a.M = M; a.kk = 1;
     OPCHK(launch_ensemble_stats(a, s));
+    OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+// ensemble_score_kernel and its finish kernel on stored member fields: frames [n][B][M][C][H][W], y [B][n][C][H][W]
+int lns_op_ensemble_score(const float* frames, const float* y, int n, int B, int M, int C, int H, int W, const lns_eval_spec* spec,
+                          float* scores_out, float* seq_out, int32_t* rank_out, float* pixel_out, void* stream) {
+    if (!frames || !y || !scores_out) { g_create_error = "ensemble_score: frames / y / scores_out is null"; return LNS_EINVAL; }
+    if (!spec || spec->size != sizeof(lns_eval_spec)) {
+        g_create_error = "ensemble_score: spec is null or its size field is not sizeof(lns_eval_spec)"; return LNS_EINVAL;
+    }
+    if (M < 2 || M > LNS_SCORE_MAX_MEMBERS) { g_create_error = "ensemble_score: M in 2 .. 128"; return LNS_EINVAL; }
+    if (n < 1 || B < 1 || B > LNS_MAX_BATCH || C < 1 || H < 1 || W < 1 || (int64_t)H * W > (1 << 30) ||
+        (int64_t)n * B * C > 0x7fffffffLL) {
+        g_create_error = "ensemble_score: n >= 1, B in 1..65535, C, H, W >= 1, H * W <= 2^30, n * B * C < 2^31"; return LNS_EINVAL;
+    }
+    if (spec->per_channel && C > LNS_METRIC_MAX_CH) { g_create_error = "ensemble_score: the per-channel form needs C <= 8"; return LNS_EINVAL; }
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EnsembleScoreArgs a;
+    a.frames = frames; a.y = y; a.scores = scores_out; a.rank = rank_out; a.pixel = pixel_out;
+    a.B = B; a.M = M; a.C = C; a.H = H; a.W = W; a.kk = n; a.y_T = n; a.y_t = 0;
+    a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std;
+    channel_spec(spec, C, &a.spec);
+    OPCHK(launch_ensemble_score(a, s));
+    OPCHK(launch_ensemble_score_finish(scores_out, B, n, C, H * W, spec->eps, seq_out, s));
     OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
 }

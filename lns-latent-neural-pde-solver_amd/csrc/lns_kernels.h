@@ -403,6 +403,22 @@ hipError_t launch_metric_finish(const float* part, int B, int T, int C, float ep
 struct EnsembleStatsArgs { const float* frames; float* mean; float* var; long per, out_bs; int B, M, kk; };
 hipError_t launch_ensemble_stats(const EnsembleStatsArgs& a, hipStream_t s);
 
+// Ensemble validation (lns_rollout_latent_ensemble_eval): member frames [kk][B][M][C][H*W] against the truth planes
+// y[b][y_t + j][c] of y [B][y_T][C][H*W]; one block per plane (j, b, c) writes the plane's four sums (SE, G, V, CR of
+// include/lns.h) to scores[b][y_t + j][c][0..3] and, when rank is given, its M + 1 rank counts to rank[b][y_t + j][c][0..M].
+// pixel (nullable, tests): [kk][B][C][H*W][4] = mu, var, crps, (float)rank of every pixel.  Dynamic LDS: M * 1 KB of columns and 4 M + 68 bytes.
+// The denormalisation is the scalar form (mean, sd) or the per-channel one (spec), as MetricGroupArgs; 2 <= M <= 128.
+struct EnsembleScoreArgs {
+    const float* frames; const float* y; float* scores; int* rank; float* pixel;
+    int B, M, C, H, W, kk, y_T, y_t, per_channel;
+    float mean, sd;
+    MetricChannelSpec spec;
+};
+#define LNS_SCORE_MAX_MEMBERS 128
+hipError_t launch_ensemble_score(const EnsembleScoreArgs& a, hipStream_t s);
+// scores [B][T][C][4] plane sums -> rel_l2, rmse, spread, crps in place; seq (nullable) [B][C][4] over the T steps
+hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int HW, float eps, float* seq, hipStream_t s);
+
 // per-sample max |x| (bit patterns) of a [B, n] tensor with batch stride x_bs into amax [B][LNS_AMAX_SUB] (atomic max)
 hipError_t launch_amax(const float* x, long x_bs, long n, int B, unsigned* amax, hipStream_t s);
 hipError_t launch_amax_sticky(const unsigned* amax, int n, unsigned* flag, hipStream_t s);

@@ -5130,6 +5130,138 @@ hipError_t launch_ensemble_stats(const EnsembleStatsArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- ensemble validation (lns_kernels.h EnsembleScoreArgs; the statement: include/lns.h) -----------------------------
+// One block per plane.  A pixel needs its M denormalised member values three times (the mean, the deviations, the pair
+// sum), and M is a run-time value: a thread keeps them in its own LDS column col[m * 256 + tid] (lane-strided dwords:
+// no bank conflict; nobody else reads or writes the column, so the pixel loop has no barrier).  The pair sum is
+// M (M - 1) / 2 LDS reads per pixel.  Every product and sum is rounded on its own (fp contract off, as ensemble_stats_body).
+__device__ __forceinline__ float score_denorm(float x, float sd, float mean, bool zero, bool clampv, float lo, float hi) {
+#pragma clang fp contract(off)
+    const float p = x * sd;
+    float v = p + mean;
+    if (zero) v = 0.0f;
+    if (clampv) v = fminf(fmaxf(v, lo), hi);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void ensemble_score_kernel(EnsembleScoreArgs a) {
+#pragma clang fp contract(off)
+    // all LDS is dynamic (a kernel with static LDS cannot be granted the full 160 KB of dynamic LDS init_kernels asks for):
+    // [M][256] columns | red[16] | hist[M + 1]
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* red = reinterpret_cast<float*>(smem) + a.M * 256;
+    int* hist = reinterpret_cast<int*>(red + 16);
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x;                          // (j * B + b) * C + c
+    const int c = q % a.C, s = q / a.C, b = s % a.B, j = s / a.B;
+    const int HW = a.H * a.W, M = a.M;
+    const long mstride = (long)a.C * HW;               // member to member inside frames [kk][B][M][C][HW]
+    const float* f = a.frames + ((long)s * M * a.C + c) * HW;
+    const long plane = ((long)b * a.y_T + a.y_t + j) * a.C + c;
+    const float* g = a.y + plane * HW;
+    const float sd = a.per_channel ? a.spec.std[c] : a.sd, mean = a.per_channel ? a.spec.mean[c] : a.mean;
+    const bool walls = a.per_channel && (a.spec.flags[c] & 1), clampv = a.per_channel && (a.spec.flags[c] & 2);
+    const float lo = a.spec.lo, hi = a.spec.hi;
+    const float fm = (float)M, fm1 = (float)(M - 1), fpairs = (float)(M * (M - 1));
+    float* col = reinterpret_cast<float*>(smem) + tid;
+    for (int k = tid; k <= M; k += 256) hist[k] = 0;
+    __syncthreads();
+    float se_sum = 0.0f, g_sum = 0.0f, v_sum = 0.0f, cr_sum = 0.0f;
+    for (int i = tid; i < HW; i += 256) {
+        bool zero = false;
+        if (walls) { const int r = i / a.W, cx = i - r * a.W; zero = r == 0 || r == a.H - 1 || cx == 0 || cx == a.W - 1; }
+        const float qv = score_denorm(g[i], sd, mean, zero, clampv, lo, hi);
+        float v = score_denorm(f[i], sd, mean, zero, clampv, lo, hi);
+        col[0] = v;
+        float sum = v;
+#pragma unroll 4
+        for (int m = 1; m < M; ++m) {
+            v = score_denorm(f[m * mstride + i], sd, mean, zero, clampv, lo, hi);
+            col[m * 256] = v;
+            sum = sum + v;
+        }
+        const float mu = sum / fm;
+        float dsum = 0.0f, qq = 0.0f, ab = 0.0f;
+        int rank = 0;
+#pragma unroll 4
+        for (int m = 0; m < M; ++m) {
+            v = col[m * 256];
+            const float d = v - mu;
+            const float p = d * d;
+            dsum = dsum + d;
+            qq = qq + p;
+            ab = ab + fabsf(v - qv);
+            rank += v < qv ? 1 : 0;
+        }
+        float var;
+        { const float cc = dsum * dsum; const float k = cc / fm; const float n = qq - k; var = n / fm1; }
+        float w = 0.0f;
+        for (int m = 0; m < M - 1; ++m) {
+            const float vm = col[m * 256];
+#pragma unroll 4
+            for (int n = m + 1; n < M; ++n) w = w + fabsf(vm - col[n * 256]);
+        }
+        const float t0 = ab / fm, t1 = w / fpairs;
+        const float crps = t0 - t1;
+        const float e = mu - qv;
+        const float se = e * e, gg = qv * qv;
+        se_sum = se_sum + se; g_sum = g_sum + gg; v_sum = v_sum + var; cr_sum = cr_sum + crps;
+        if (a.rank) atomicAdd(&hist[rank], 1);
+        if (a.pixel) {
+            float* px = a.pixel + ((long)q * HW + i) * 4;
+            px[0] = mu; px[1] = var; px[2] = crps; px[3] = (float)rank;
+        }
+    }
+    se_sum = wave_sum(se_sum); g_sum = wave_sum(g_sum); v_sum = wave_sum(v_sum); cr_sum = wave_sum(cr_sum);
+    if ((tid & 63) == 0) {
+        const int wv = tid >> 6;
+        red[wv] = se_sum; red[4 + wv] = g_sum; red[8 + wv] = v_sum; red[12 + wv] = cr_sum;
+    }
+    __syncthreads();
+    if (tid < 4) a.scores[plane * 4 + tid] = (red[4 * tid] + red[4 * tid + 1]) + (red[4 * tid + 2] + red[4 * tid + 3]);
+    if (a.rank)
+        for (int k = tid; k <= M; k += 256) a.rank[plane * (M + 1) + k] = hist[k];
+}
+
+// (b, c) per thread: the four plane sums of every step -> the four scores in place; the sequence-wise forms from the
+// running sums over the steps in ascending order
+__global__ void ensemble_score_finish_kernel(float* scores, int B, int T, int C, int HW, float eps, float* seq) {
+#pragma clang fp contract(off)
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= B * C) return;
+    const int b = idx / C, c = idx - b * C;
+    const float fhw = (float)HW, fall = (float)((long)T * HW);
+    float sse = 0.0f, sg = 0.0f, sv = 0.0f, scr = 0.0f;
+    for (int t = 0; t < T; ++t) {
+        float* p = scores + (((long)b * T + t) * C + c) * 4;
+        const float se = p[0], g2 = p[1], v = p[2], cr = p[3];
+        p[0] = sqrtf(se / (g2 < eps ? eps : g2));
+        p[1] = sqrtf(se / fhw);
+        p[2] = sqrtf(v / fhw);
+        p[3] = cr / fhw;
+        sse = sse + se; sg = sg + g2; sv = sv + v; scr = scr + cr;
+    }
+    if (seq) {
+        float* p = seq + (long)idx * 4;
+        p[0] = sqrtf(sse / (sg < eps ? eps : sg));
+        p[1] = sqrtf(sse / fall);
+        p[2] = sqrtf(sv / fall);
+        p[3] = scr / fall;
+    }
+}
+
+hipError_t launch_ensemble_score(const EnsembleScoreArgs& a, hipStream_t s) {
+    if (a.M < 2 || a.M > LNS_SCORE_MAX_MEMBERS) return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.M * 1024 + (16 + a.M + 1) * 4;            // columns, red, hist: at most 128.6 KB
+    hipLaunchKernelGGL(ensemble_score_kernel, dim3((unsigned)((long)a.kk * a.B * a.C)), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int HW, float eps, float* seq, hipStream_t s) {
+    hipLaunchKernelGGL(ensemble_score_finish_kernel, dim3((B * C + 63) / 64), dim3(64), 0, s, scores, B, T, C, HW, eps, seq);
+    return hipGetLastError();
+}
+
 // per-sample max |x| of a [B, n] tensor: grid (chunks, B); one atomic per wave
 __global__ __launch_bounds__(256) void amax_kernel(const float* x, long x_bs, long n, unsigned* amax) {
     const int b = blockIdx.y;
@@ -5289,6 +5421,7 @@ hipError_t init_kernels() {
     LNS_SET_LDS(fa_lrk2_kernel)
     LNS_SET_LDS(fa_pool_kernel)
     LNS_SET_LDS(fa_reducer_kernel)
+    LNS_SET_LDS(ensemble_score_kernel)                                   // 128 members: 128 KB of columns
 #undef LNS_SET_LDS
     return hipSuccess;
 }

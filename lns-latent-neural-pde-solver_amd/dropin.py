@@ -448,6 +448,16 @@ class LatentDynamics(_Hosted):
         x = self._fields(x)
         return self._engine(x).rollout(x, steps, param=param, to_x=to_x, return_latents=return_latents, keep_steps=keep_steps)
 
+    def _ensemble_latents(self, x, members, noise_level, generator, control):
+        """x -> z [B, members, c, h, w]: z0 + randn * noise_level per member, member 0 left as z0 under control."""
+        z0 = self.x_to_z(self._fields(x))
+        B, c, h, w = z0.shape
+        eps = torch.randn((B, members, c, h, w), device=z0.device, dtype=z0.dtype, generator=generator) * noise_level
+        z = z0[:, None] + eps
+        if control:
+            z[:, 0] = z0
+        return z
+
     @torch.no_grad()
     def predict_ensemble(self, x, steps, *rest, generator=None, control=True, keep_steps=None, return_var=True):
         """predict_ensemble(x, steps, members, noise_level) -- conditional: predict_ensemble(x, steps, param, members,
@@ -468,14 +478,30 @@ class LatentDynamics(_Hosted):
         members, noise_level = int(rest[0]), float(rest[1])
         if members < 1:
             raise LnsError("members must be at least 1, got %d" % members)
-        x = self._fields(x)
-        z0 = self.x_to_z(x)
-        B, c, h, w = z0.shape
-        eps = torch.randn((B, members, c, h, w), device=z0.device, dtype=z0.dtype, generator=generator) * noise_level
-        z = z0[:, None] + eps
-        if control:
-            z[:, 0] = z0
+        z = self._ensemble_latents(x, members, noise_level, generator, control)
         return self._engine(z).rollout_latent_ensemble(z, steps, param=param, keep_steps=keep_steps, return_var=return_var)
+
+    @torch.no_grad()
+    def validate_ensemble(self, x, y, *rest, generator=None, control=True, keep_steps=None, **norm):
+        """validate_ensemble(x, y, members, noise_level, **norm) -- conditional: validate_ensemble(x, y, param, members,
+        noise_level, **norm): the ensemble forecast of `predict_ensemble` over T = y.shape[1] steps (same encode, same noise
+        from the same generator state, same `control`), scored against the normalised truth y [B,T,C,Ly,Lx] as it is
+        decoded: relative L2 and RMSE of the ensemble mean, spread, fair CRPS and the rank histogram per kept step and
+        channel (engine.EnsembleScores; `metrics.spread_skill_ratio`).  Neither the members' fields nor their mean are
+        stored.  `norm` as in `validate`; keep_steps as for predict (None: every step)."""
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("validate_ensemble() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if len(rest) != 2:
+            raise TypeError("validate_ensemble() takes (x, y, param, members, noise_level)" if self._conditional
+                            else "validate_ensemble() takes (x, y, members, noise_level)")
+        members, noise_level = int(rest[0]), float(rest[1])
+        if members < 2:
+            raise LnsError("scoring an ensemble needs at least 2 members, got %d" % members)
+        z = self._ensemble_latents(x, members, noise_level, generator, control)
+        return self._engine(z).rollout_latent_ensemble_eval(z, y, param=param, keep_steps=keep_steps, **norm)
 
     @torch.no_grad()
     def validate(self, x, y, *rest, keep_steps=(), **norm):

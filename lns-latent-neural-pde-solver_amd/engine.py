@@ -4,6 +4,7 @@ Translates the reference's `args` namespace into `lns_config`, exposes the
 engine's parameter table (= the reference state_dict keys/shapes) and runs the
 hot path on CUDA/HIP tensors.  torch is used for device memory and streams only.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -179,6 +180,12 @@ def eval_spec(C, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_chann
     for c in clamp_channels:
         spec.flags_c[c] |= 2
     return spec
+
+
+EnsembleScores = collections.namedtuple("EnsembleScores", "rel_l2 rmse spread crps seq rank mean var z_last")
+EnsembleScores.__doc__ = """Result of Engine.rollout_latent_ensemble_eval / ensemble_score: rel_l2, rmse, spread, crps
+[B, n_keep, C] (views of one [B, n_keep, C, 4] tensor), seq [B, C, 4] (the same four over all kept steps), rank
+[B, n_keep, C, M + 1] int32 or None, and mean, var, z_last where asked for (None otherwise)."""
 
 
 def normalize_keep_steps(keep_steps, steps):
@@ -451,6 +458,22 @@ class Engine:
         return self._rollout_call(self._dev(z), False, steps, param, to_x, out, keep_steps, True)
 
     # -- ensemble rollout (include/lns.h "ensemble rollout") -------------------------------------------------------
+    @staticmethod
+    def _member_param(param, z, B, M):
+        """param of an ensemble call: one value per trajectory [B] (broadcast over the members) or per member -> fp32 [B, M]."""
+        import torch
+        if param is None:
+            return None
+        p = torch.as_tensor(param)
+        if p.device != z.device:
+            raise LnsError("param is on %s but the latents are on %s" % (p.device, z.device))
+        if p.numel() == B:
+            p = p.reshape(B, 1).expand(B, M)
+        elif p.numel() != B * M:
+            raise LnsError("param must hold one value per trajectory or per member: got %d values for B = %d, M = %d"
+                           % (p.numel(), B, M))
+        return p.reshape(B, M).to(torch.float32).contiguous()
+
     def rollout_latent_ensemble(self, z, steps, param=None, keep_steps=None, return_var=True, return_last=False, out=None):
         """z [B, M, c, h, w]: M perturbed members of each of B trajectories (the noise is the caller's, as in training).
         Rolls every member out and returns, per kept step, the mean and the unbiased variance over the members
@@ -474,17 +497,7 @@ class Engine:
         mean = self._out(out, shape, z.device)
         var = torch.empty(shape, dtype=torch.float32, device=z.device) if return_var else None
         z_last = torch.empty_like(z) if return_last else None
-        p = None
-        if param is not None:
-            p = torch.as_tensor(param)
-            if p.device != z.device:
-                raise LnsError("param is on %s but the latents are on %s" % (p.device, z.device))
-            if p.numel() == B:
-                p = p.reshape(B, 1).expand(B, M)
-            elif p.numel() != B * M:
-                raise LnsError("param must hold one value per trajectory or per member: got %d values for B = %d, M = %d"
-                               % (p.numel(), B, M))
-            p = p.reshape(B, M).to(torch.float32).contiguous()
+        p = self._member_param(param, z, B, M)
         with torch.cuda.device(z.device):
             n = ctypes.c_size_t(0)
             self._check(self._L.lns_rollout_ensemble_workspace_bytes(self._h, B, M, ctypes.byref(n)),
@@ -514,6 +527,87 @@ class Engine:
         if rc != 0:
             raise LnsError("lns_op_ensemble_stats failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
         return (mean, var) if return_var else mean
+
+    # -- ensemble validation (include/lns.h "ensemble validation") ---------------------------------------------------
+    @staticmethod
+    def _scores_result(scores, seq, rank, mean=None, var=None, z_last=None):
+        return EnsembleScores(scores[..., 0], scores[..., 1], scores[..., 2], scores[..., 3], seq, rank, mean, var, z_last)
+
+    def ensemble_score(self, frames, y, return_rank=True, **norm):
+        """The scoring kernels of the ensemble validation on stored member fields (lns_op_ensemble_score): frames
+        [n, B, M, C, H, W] (a frame buffer's layout), y [B, n, C, H, W], both normalised; `norm` as in `rollout_eval`.
+        Returns EnsembleScores (mean, var, z_last None)."""
+        import torch
+        for t in (frames, y):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+                raise LnsError("ensemble_score takes fp32 HIP tensors")
+        if frames.dim() != 6 or y.dim() != 5 or y.device != frames.device:
+            raise LnsError("ensemble_score takes frames [n, B, M, C, H, W] and y [B, n, C, H, W] on one device")
+        n, B, M, C, H, W = (int(v) for v in frames.shape)
+        if tuple(y.shape) != (B, n, C, H, W):
+            raise LnsError("y must be %s for frames %s, got %s" % ((B, n, C, H, W), tuple(frames.shape), tuple(y.shape)))
+        frames, y = frames.contiguous(), y.contiguous()
+        spec = eval_spec(C, **norm)
+        scores = torch.empty((B, n, C, 4), dtype=torch.float32, device=y.device)
+        seq = torch.empty((B, C, 4), dtype=torch.float32, device=y.device)
+        rank = torch.empty((B, n, C, M + 1), dtype=torch.int32, device=y.device) if return_rank else None
+        with torch.cuda.device(y.device):
+            rc = self._L.lns_op_ensemble_score(frames.data_ptr(), y.data_ptr(), n, B, M, C, H, W, ctypes.byref(spec),
+                                               scores.data_ptr(), seq.data_ptr(), self._ptr(rank), None, self._stream(y))
+        if rc != 0:
+            raise LnsError("lns_op_ensemble_score failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return self._scores_result(scores, seq, rank)
+
+    def rollout_latent_ensemble_eval(self, z, y, steps=None, param=None, keep_steps=None, return_rank=True, return_mean=False,
+                                     return_var=False, return_last=False, **norm):
+        """rollout_latent_ensemble with the members scored against the truth as they are decoded: z [B, M, c, h, w] as there
+        (2 <= M <= 128), y [B, T, C, Ly, Lx] the normalised truth of all `steps` = T steps (the kept ones, y[:, keep_steps],
+        are what is scored; keep_steps None: every step), `norm` as in `rollout_eval`.  Returns EnsembleScores: per kept
+        step and channel the relative L2 error and the RMSE of the ensemble mean, the spread (root of the mean unbiased
+        member variance) and the fair CRPS, their sequence-wise forms, the rank histogram of the truth among the members,
+        and (return_mean / return_var / return_last) rollout_latent_ensemble's outputs.  The member fields are never stored;
+        the workspace is rollout_latent_ensemble's."""
+        import torch
+        z = self._dev(z)
+        y = self._dev(y)
+        C, H, W = self.latent_shape()
+        c = self.cfg
+        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
+            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
+        B, M = int(z.shape[0]), int(z.shape[1])
+        if y.dim() != 5 or y.shape[0] != B or tuple(y.shape[2:]) != (c.in_channels, c.Ly, c.Lx) or y.dtype != torch.float32:
+            raise LnsError("ground truth must be fp32 [B, T, %d, %d, %d] with the latents' batch, got %s"
+                           % (c.in_channels, c.Ly, c.Lx, tuple(y.shape)))
+        if y.device != z.device:
+            raise LnsError("ground truth is on %s but the latents are on %s" % (y.device, z.device))
+        if return_var and not return_mean:
+            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
+        steps = int(y.shape[1]) if steps is None else int(steps)
+        if steps > y.shape[1]:
+            raise LnsError("%d steps do not fit the %d steps of the ground truth" % (steps, y.shape[1]))
+        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
+        arr = (ctypes.c_int * len(keep))(*keep)
+        yk = y[:, keep].contiguous()
+        spec = eval_spec(c.in_channels, **norm)
+        nk = len(keep)
+        scores = torch.empty((B, nk, c.in_channels, 4), dtype=torch.float32, device=z.device)
+        seq = torch.empty((B, c.in_channels, 4), dtype=torch.float32, device=z.device)
+        rank = torch.empty((B, nk, c.in_channels, M + 1), dtype=torch.int32, device=z.device) if return_rank else None
+        shape = (B, nk, c.in_channels, c.Ly, c.Lx)
+        mean = torch.empty(shape, dtype=torch.float32, device=z.device) if return_mean else None
+        var = torch.empty(shape, dtype=torch.float32, device=z.device) if return_var else None
+        z_last = torch.empty_like(z) if return_last else None
+        p = self._member_param(param, z, B, M)
+        with torch.cuda.device(z.device):
+            n = ctypes.c_size_t(0)
+            self._check(self._L.lns_rollout_ensemble_workspace_bytes(self._h, B, M, ctypes.byref(n)),
+                        "lns_rollout_ensemble_workspace_bytes")
+            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+            self._check(self._L.lns_rollout_latent_ensemble_eval(
+                self._h, z.data_ptr(), self._ptr(p), yk.data_ptr(), B, M, steps, arr, nk, ctypes.byref(spec), scores.data_ptr(),
+                seq.data_ptr(), self._ptr(rank), self._ptr(mean), self._ptr(var), self._ptr(z_last), ws.data_ptr(), ws.numel(),
+                self._stream(z)), "lns_rollout_latent_ensemble_eval")
+        return self._scores_result(scores, seq, rank, mean, var, z_last)
 
     # -- streaming validation rollout (include/lns.h "streaming validation rollout") --------------------------------
     def _eval_common(self, first, y, steps, t0, keep_steps, norm):

@@ -77,6 +77,16 @@ def _launch_metric(L, per_channel, y_hat, y, B, T, C, H, W, mean, std, eps, zero
     return rc
 
 
+def spread_skill_ratio(scores, members):
+    """spread * sqrt((M + 1) / M) / rmse of an `engine.EnsembleScores` (Engine.rollout_latent_ensemble_eval,
+    LatentDynamics.validate_ensemble) with M = `members`: near 1 for a calibrated ensemble, below it for an
+    under-dispersive one (the finite-ensemble correction of the spread-skill relation)."""
+    members = int(members)
+    if members < 2:
+        raise ValueError("spread_skill_ratio needs at least 2 members")
+    return scores.spread * float((members + 1) / members) ** 0.5 / scores.rmse
+
+
 def sw_norm(u_mean, u_std, v_mean, v_std, pres_mean, pres_std):
     """Keyword arguments for encode_dataset restating Stage2_SW.normalize (dataset/Stage2_SW.py:74-78): channels
     (u, v, pres), each by its own statistics, no epsilon."""
