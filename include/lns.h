@@ -361,6 +361,62 @@ int lns_rollout_latent_ensemble_eval(lns_engine* e, const float* z_in, const flo
                                      float* mean_out, float* var_out, float* z_last,
                                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- streaming validation: energy spectra of forecast, truth and error ---------------------------------------------
+ * lns_rollout_eval / lns_rollout_latent_eval with, for selected steps, the shell-summed energy spectra of the forecast,
+ * of the truth and of their difference, taken where the step is decoded: a spectrum needs the whole plane of a step, i.e.
+ * the [B,T,Cin,Ly,Lx] tensor the streaming calls exist to avoid.  A spectrum kernel follows the scoring kernel of a decoded
+ * group on its decode stream, one launch per group for the group's selected steps (none selected: no launch), one block
+ * per plane.  (No reference counterpart; the ground truth of the tests is numpy.fft in float64.)
+ *
+ * The statement, for a plane u[y][x] of H x W pixels after the denormalisation D_c of lns_eval_spec (the map written above
+ * for lns_rollout_latent_ensemble_eval, product and sum rounded one by one, wall-zero and clamp flags included; eps unused):
+ *     F[ky][kx] = sum_y sum_x u[y][x] exp(-2 pi i (ky y / H + kx x / W)),    kx = 0 .. Wh-1, Wh = W/2 + 1  (u is real)
+ *     ky' = ky <= H/2 ? ky : ky - H,  kx' = kx,  r2 = ky'*ky' + kx'*kx'
+ *     shell(r2) = the integer s with s*(s-1) < r2 <= s*(s+1), 0 for r2 = 0     (round(sqrt(r2)) in integers: no floating tie)
+ *     S(H, W) = shell((H/2)^2 + (W/2)^2) + 1 bins (integer division): 24 for 32x32, 92 for 128x128, 108 for 96x192, 68 for 61x121
+ *     inv = 1 / (float)(H*W);  a = re * inv;  b = im * inv;  p = w * (a*a + b*b)          (fp32, nothing fused)
+ *     w = 1 for kx = 0 and, when W is even, for kx = W/2; else 2 (the conjugate partner, which lies in the same shell)
+ *     E[s] = sum of p over the modes of shell s;  by Parseval sum_s E[s] = mean(u^2)
+ * Three spectra per plane (b, step, c): row 0 of the forecast P = D_c(yhat), row 1 of the truth Q = D_c(y), row 2 of the
+ * error d = P - Q, differenced per pixel in fp32 BEFORE the transform (F_P - F_Q would put the error spectrum's floor at the
+ * field's rounding level).  Each of the three fields is transformed directly: the truth is not taken as F_P - F_d.
+ *
+ * Order of the sums (a function of the plane only; fp32; the contractions are exact-fp32 matrix instructions, i.e. fmaf
+ * chains in ascending k starting from +0).  c_N[r] = cospi(2r/N), m_N[r] = -sinpi(2r/N) in fp32 (sincospif), r = (k n) mod N:
+ *     row pass     Rre[y][kx] = chain over x = 0 .. W-1 of u[y][x] * c_W[(kx x) mod W];  Rim likewise with m_W
+ *     column pass  re[ky][kx] = one chain: y = 0 .. H-1 of c_H[(ky y) mod H] * Rre[y][kx], then y = 0 .. H-1 of (-m_H[.]) * Rim[y][kx]
+ *                  im[ky][kx] = one chain: y = 0 .. H-1 of c_H[.] * Rim[y][kx], then y = 0 .. H-1 of m_H[.] * Rre[y][kx]
+ *     shell sums   the columns kx are taken in tiles of 32 (kx0 = 0, 32, ...).  In a tile, row ky is cut into runs of
+ *                  consecutive kx of equal shell (along a row the shell does not decrease with kx); a run's sum starts
+ *                  from 0 and adds its p in ascending kx.  E[s] starts from 0 and adds, tile after tile, within a tile
+ *                  in ascending ky = 0 .. H-1 (storage order, not the signed one), the run of shell s of that row, if any.
+ * One block owns one plane and stores its 3 x S (1 x S) floats itself: no float atomics, nothing depends on the grouping or
+ * the scheduling options, so the streaming calls and lns_op_energy_spectrum (one device function) produce the same bits.
+ * A NaN pixel makes every bin of its own plane's spectra that read it NaN and touches no other plane.
+ * Bins are index wavenumbers (no physical lengths; on a non-square plane ky and kx count cycles per side).  On the
+ * non-periodic families the DFT sees the jump across the walls: those spectra carry its leakage (a k^-2 tail).
+ *
+ * Supported planes: 1 <= H, W <= 192 and H * W <= 18432 (96 x 192); lns_spectrum_bins is host-only and returns S, or
+ * LNS_EINVAL for an unsupported plane. */
+int lns_spectrum_bins(int H, int W);
+
+/* lns_rollout_eval / lns_rollout_latent_eval (same arguments, same frame_out / seq_out / frames_out bits, same workspace:
+ * lns_rollout_eval_workspace_bytes(B) and nothing more) followed by the spectrum selection: spectrum_steps_host, n_spec >= 1
+ * ascending 0-based steps of this call's T (HOST array, read during the call; independent of keep_steps_host), and
+ * spectra_out [B][n_spec][Cin][3][S], S = lns_spectrum_bins(Ly, Lx), which every block writes with final values.
+ * Refusals: those of lns_rollout_eval, then (host only, ahead of the batch check) LNS_EINVAL for spectra_out null,
+ * n_spec < 1, spectrum_steps_host null / out of range / not ascending, and an unsupported plane.  Trace / timing modes
+ * (single stream) and lns_check_finite: as lns_rollout_eval. */
+int lns_rollout_eval_spectrum(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                              const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host,
+                              int n_keep, float* frames_out, void* workspace, size_t workspace_bytes, void* stream,
+                              const int* spectrum_steps_host, int n_spec, float* spectra_out);
+int lns_rollout_latent_eval_spectrum(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                     int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                     const int* keep_steps_host, int n_keep, float* frames_out, float* z_last,
+                                     void* workspace, size_t workspace_bytes, void* stream,
+                                     const int* spectrum_steps_host, int n_spec, float* spectra_out);
+
 /* Post-run health check.  Every kernel of a plan records, per sample, the running maximum of |y| of the tensor it
  * produces (the side channel from which the split-operand convolutions derive their activation scale); a NaN or inf
  * anywhere in a tensor survives in it.  This call synchronises `stream`, reads those few KB back from `workspace`
@@ -548,7 +604,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * the gradient-norm / update calls are there; "train_ops" = lns_op_groupnorm_train, lns_op_gelu_grad and lns_op_bias_grad
  * are there; "rollout_select" = lns_rollout_select & co. are there; "rollout_ensemble" = lns_rollout_latent_ensemble,
  * its size query and lns_op_ensemble_stats are there; "ensemble_score" = lns_rollout_latent_ensemble_eval and
- * lns_op_ensemble_score are there.  1 / 0; -1: unknown name.
+ * lns_op_ensemble_score are there; "eval_spectrum" = lns_rollout_eval_spectrum, lns_rollout_latent_eval_spectrum,
+ * lns_op_energy_spectrum and lns_spectrum_bins are there.  1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
 
@@ -624,6 +681,13 @@ int lns_op_ensemble_stats(const float* frames, int B, int M, int64_t per, float*
 int lns_op_ensemble_score(const float* frames, const float* y, int n, int B, int M, int C, int H, int W,
                           const lns_eval_spec* spec, float* scores_out, float* seq_out, int32_t* rank_out,
                           float* pixel_out, void* stream);
+
+/* The spectrum kernel of lns_rollout_eval_spectrum on stored fields, without an engine: yhat and y (nullable) [B][T][C][H][W],
+ * normalised -> out [B][T][C][K][S], K = 3 (forecast, truth, error) when y is given, K = 1 (the forecast's row, same bits) when
+ * it is NULL; S = lns_spectrum_bins(H, W).  The per-plane body is the streaming call's (one device function).  B * T * C < 2^31;
+ * the per-channel form needs C <= 8.  Checks precede the launch (message: lns_create_error()); the call synchronises `stream`. */
+int lns_op_energy_spectrum(const float* yhat, const float* y /* nullable */, int B, int T, int C, int H, int W,
+                           const lns_eval_spec* spec, float* out, void* stream);
 
 /* GroupNorm statistics -> per-(b,c) (scale,shift) such that norm(x) = x*scale+shift. */
 int lns_op_groupnorm_stats(const float* x, int B, int C, int HW, int groups, float eps,

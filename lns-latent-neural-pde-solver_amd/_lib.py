@@ -104,6 +104,7 @@ SYMBOLS = [
     "lns_rollout_select_workspace_bytes", "lns_rollout_select", "lns_rollout_latent_select",
     "lns_rollout_ensemble_workspace_bytes", "lns_rollout_latent_ensemble", "lns_op_ensemble_stats",
     "lns_rollout_latent_ensemble_eval", "lns_op_ensemble_score",
+    "lns_spectrum_bins", "lns_rollout_eval_spectrum", "lns_rollout_latent_eval_spectrum", "lns_op_energy_spectrum",
     "lns_train_workspace_bytes", "lns_train_forward", "lns_train_backward",
     "lns_loss_smooth_l1", "lns_adam_step", "lns_adam_step_tensors", "lns_train_step_workspace_bytes", "lns_train_step",
     "lns_grad_norm_scratch_bytes", "lns_grad_norm_tensors", "lns_grad_scale_tensors", "lns_update_step_tensors",
@@ -191,6 +192,13 @@ def lib():
         sp, ip = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int)
         L.lns_rollout_latent_ensemble_eval.argtypes = [vp, vp, vp, vp, i, i, i, ip, i, sp, vp, vp, vp, vp, vp, vp, vp, c.c_size_t, vp]
         L.lns_op_ensemble_score.argtypes = [vp, vp, i, i, i, i, i, i, sp, vp, vp, vp, vp, vp]
+    if hasattr(L, "lns_rollout_eval_spectrum"):
+        sp, ip = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int)
+        L.lns_spectrum_bins.argtypes = [i, i]
+        L.lns_rollout_eval_spectrum.argtypes = [vp, vp, vp, vp, i, i, sp, vp, vp, ip, i, vp, vp, c.c_size_t, vp, ip, i, vp]
+        L.lns_rollout_latent_eval_spectrum.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, vp, c.c_size_t, vp,
+                                                       ip, i, vp]
+        L.lns_op_energy_spectrum.argtypes = [vp, vp, i, i, i, i, i, sp, vp, vp]
     if hasattr(L, "lns_check_finite"):      # (absent from older builds loaded through LNS_HIP_LIB for A/B runs)
         L.lns_check_finite.argtypes = [vp, i, vp, c.c_size_t, vp]
     if hasattr(L, "lns_set_option"):

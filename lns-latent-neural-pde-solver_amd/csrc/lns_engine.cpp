@@ -17,6 +17,7 @@
 #include "lns_engine.h"
 #include "lns_fold.h"
 #include "lns_resolve.h"
+#include "lns_spectrum.h"
 
 // the batch is a grid dimension (gridDim.y / .z) of every kernel
 #define LNS_MAX_BATCH 65535
@@ -1837,6 +1838,8 @@ struct RolloutCall {
     // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
     const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
     float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
+    // SINK_SCORED with spectra (lns_rollout_eval_spectrum): spectra_out [B][n_spec][C][3][S] of the steps spec_steps[0 .. n_spec) (host, ascending)
+    bool spectra = false; const int* spec_steps = nullptr; int n_spec = 0; float* spectra_out = nullptr;
     float* latents_out = nullptr;                        // optional side outputs: all T latents [B][T][zper],
     float* z_last = nullptr;                             // the latent after the last step [B][zper]
     void* ws = nullptr; size_t ws_bytes = 0; void* stream = nullptr;
@@ -2196,6 +2199,17 @@ static void metric_args(const lns_engine* e, const RolloutCall& c, const WsLayou
     channel_spec(spec, m.C, &m.spec);
 }
 
+// the spectrum kernel's arguments for a SINK_SCORED call with spectra; frames / n / sel / y_t / o_t are set per decoded group
+static void spectrum_args(const lns_engine* e, const RolloutCall& c, SpectrumArgs* sp) {
+    SpectrumArgs& s = *sp;
+    s.frames = nullptr; s.y = c.y_true; s.out = c.spectra_out;
+    s.B = c.B; s.C = e->cfg.in_channels; s.H = e->cfg.Ly; s.W = e->cfg.Lx; s.S = lns_spectrum::bins(s.H, s.W); s.K = 3;
+    s.n = 0; s.y_T = c.T_total; s.y_t = 0; s.o_T = c.n_spec; s.o_t = 0;
+    s.per_channel = c.spec->per_channel != 0; s.mean = c.spec->mean; s.sd = c.spec->std;
+    channel_spec(c.spec, s.C, &s.spec);
+    memset(s.sel, 0, sizeof s.sel);
+}
+
 // the same for the scoring kernel of a scored SINK_ENSEMBLE call; frames / kk / y_t are set per decoded group
 static void score_args(const lns_engine* e, const RolloutCall& c, EnsembleScoreArgs* sp) {
     EnsembleScoreArgs& s = *sp;
@@ -2265,6 +2279,8 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     if (scored) metric_args(e, c, L, &m);
     EnsembleScoreArgs sc;
     if (ens && c.ens_scored) score_args(e, c, &sc);
+    SpectrumArgs sx;
+    if (scored && c.spectra) spectrum_args(e, c, &sx);
     // A decode group is the next up to kdec DECODED steps: all steps, the kept ones, or none.  The chain writes the
     // latent of a decoded step into the group's next ring slot; the latent of a step nobody decodes goes into `out`
     // (SINK_LATENTS) or into the two ping-pong buffers in turn (SINK_KEPT, SINK_ENSEMBLE), so a step never writes the buffer it reads.
@@ -2290,7 +2306,7 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
         npp ^= 1;
         return chain_step(t, znext);
     };
-    int g = 0, gi = 0, ki = 0, t = 0;                // ki: next entry of c.keep (SINK_SCORED); t: next step of the chain
+    int g = 0, gi = 0, ki = 0, si = 0, t = 0;        // ki / si: next entry of c.keep / c.spec_steps (SINK_SCORED); t: next step of the chain
     for (int i0 = 0; i0 < n_dec;) {                  // i0: index in `out` of the group's first step
         const int kk = std::min(kdec, n_dec - i0);
         const int t0g = dec_step(i0);                // the group's first step
@@ -2323,6 +2339,11 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
                 HIPCHK(e, hipMemcpy2DAsync(c.frames_out + (long)ki * xper, (size_t)c.n_keep * xper * 4,
                                            fb + (long)(c.keep[ki] - t0g) * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
                                            hipMemcpyDeviceToDevice, dstream[d]));
+            if (c.spectra) {                         // the group's selected steps (kk <= 8), one launch; none: no launch
+                sx.frames = fb; sx.y_t = c.t0 + t0g; sx.o_t = si; sx.n = 0;
+                for (; si < c.n_spec && c.spec_steps[si] < t0g + kk; ++si) sx.sel[sx.n++] = (unsigned char)(c.spec_steps[si] - t0g);
+                if (sx.n) HIPCHK(e, launch_spectrum_group(sx, dstream[d]));
+            }
         }
         if (ens && c.ens_scored) {                   // fb is [kk][traj][M][xper] against y_true[b][i0 .. i0 + kk)
             sc.frames = fb; sc.kk = kk; sc.y_t = i0;
@@ -2399,6 +2420,20 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
         if (!c.keep) return einval(e, scored ? "keep_steps is null but n_keep > 0" : "keep_steps is null");
         if (scored && !c.frames_out) return einval(e, "frames_out is null but n_keep > 0");
         if (int krc = check_keep_steps(e, c.keep, c.n_keep, c.T)) return krc;
+    }
+    if (scored && c.spectra) {
+        if (!c.spectra_out) return einval(e, "spectra_out is null");
+        if (c.n_spec < 1) return einval(e, "n_spec must be at least 1");
+        if (!c.spec_steps) return einval(e, "spectrum_steps is null");
+        for (int i = 0; i < c.n_spec; ++i)
+            if (c.spec_steps[i] < 0 || c.spec_steps[i] >= c.T || (i > 0 && c.spec_steps[i] <= c.spec_steps[i - 1])) {
+                e->err = fmt("spectrum_steps must be ascending steps in [0, %d): entry %d is %d", c.T, i, c.spec_steps[i]);
+                return LNS_EINVAL;
+            }
+        if (!lns_spectrum::supported(e->cfg.Ly, e->cfg.Lx)) {
+            e->err = fmt("energy spectrum: a %d x %d plane is not supported (H, W <= 192 and H * W <= 18432)", e->cfg.Ly, e->cfg.Lx);
+            return LNS_EINVAL;
+        }
     }
     if (int brc = check_batch(e, c.B)) return brc;
     if (scored && c.T_total > e->opt_eval_max_steps) {
@@ -2486,6 +2521,29 @@ int lns_rollout_latent_eval(lns_engine* e, const float* z_in, const float* param
     RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
     score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
     c.z_last = z_last;
+    return rollout_call(e, c);
+}
+
+// ---- streaming validation with energy spectra (include/lns.h) ----------------------------------------------------
+int lns_rollout_eval_spectrum(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                              const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
+                              float* frames_out, void* ws, size_t ws_bytes, void* stream, const int* spectrum_steps_host,
+                              int n_spec, float* spectra_out) {
+    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
+    score_into(c, y_true, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
+    c.spectra = true; c.spec_steps = spectrum_steps_host; c.n_spec = n_spec; c.spectra_out = spectra_out;
+    return rollout_call(e, c);
+}
+
+int lns_rollout_latent_eval_spectrum(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                     int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                     const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* ws,
+                                     size_t ws_bytes, void* stream, const int* spectrum_steps_host, int n_spec,
+                                     float* spectra_out) {
+    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
+    score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
+    c.z_last = z_last;
+    c.spectra = true; c.spec_steps = spectrum_steps_host; c.n_spec = n_spec; c.spectra_out = spectra_out;
     return rollout_call(e, c);
 }
 
@@ -2621,6 +2679,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "rollout_select")) return 1;
     if (!strcmp(feature, "rollout_ensemble")) return 1;
     if (!strcmp(feature, "ensemble_score")) return 1;
+    if (!strcmp(feature, "eval_spectrum")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else
@@ -2912,6 +2971,36 @@ int lns_op_ensemble_score(const float* frames, const float* y, int n, int B, int
     channel_spec(spec, C, &a.spec);
     OPCHK(launch_ensemble_score(a, s));
     OPCHK(launch_ensemble_score_finish(scores_out, B, n, C, H * W, spec->eps, seq_out, s));
+    OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+int lns_spectrum_bins(int H, int W) {
+    const int S = lns_spectrum::bins(H, W);
+    return S < 0 ? LNS_EINVAL : S;
+}
+
+// spectrum_stored_kernel on stored fields: the per-plane body of the streaming call (spectrum_plane)
+int lns_op_energy_spectrum(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
+                           float* out, void* stream) {
+    if (!yhat || !out) { g_create_error = "energy_spectrum: yhat / out is null"; return LNS_EINVAL; }
+    if (!spec || spec->size != sizeof(lns_eval_spec)) {
+        g_create_error = "energy_spectrum: spec is null or its size field is not sizeof(lns_eval_spec)"; return LNS_EINVAL;
+    }
+    if (B < 1 || T < 1 || C < 1 || (int64_t)B * T * C > 0x7fffffffLL) {
+        g_create_error = "energy_spectrum: B, T, C >= 1 and B * T * C < 2^31"; return LNS_EINVAL;
+    }
+    if (!lns_spectrum::supported(H, W)) { g_create_error = "energy_spectrum: the plane needs 1 <= H, W <= 192 and H * W <= 18432"; return LNS_EINVAL; }
+    if (spec->per_channel && C > LNS_METRIC_MAX_CH) { g_create_error = "energy_spectrum: the per-channel form needs C <= 8"; return LNS_EINVAL; }
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SpectrumArgs a;
+    memset(&a, 0, sizeof a);
+    a.frames = yhat; a.y = y; a.out = out;
+    a.B = B; a.C = C; a.H = H; a.W = W; a.S = lns_spectrum::bins(H, W); a.K = y ? 3 : 1; a.n = T;
+    a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std;
+    channel_spec(spec, C, &a.spec);
+    OPCHK(launch_spectrum_stored(a, s));
     OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
 }

@@ -419,6 +419,22 @@ hipError_t launch_ensemble_score(const EnsembleScoreArgs& a, hipStream_t s);
 // scores [B][T][C][4] plane sums -> rel_l2, rmse, spread, crps in place; seq (nullable) [B][C][4] over the T steps
 hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int HW, float eps, float* seq, hipStream_t s);
 
+// Energy spectra (lns_rollout_eval_spectrum, lns_op_energy_spectrum; the statement: include/lns.h): one block per plane
+// writes its K x S shell energies, K = 3 (forecast, truth, error) with y, K = 1 (forecast) without; S = lns_spectrum::bins(H, W).
+// Group form: frames [kk][B][C][H*W] (a decode stream's frame buffer); the n <= 8 selected steps sel[0 .. n) of the group
+// against the truth planes y[b][y_t + sel[i]][c] of y [B][y_T][C][H*W] into out[b][o_t + i][c] of out [B][o_T][C][K][S].
+// Stored form: frames and y are [B][n][C][H*W], out [B][n][C][K][S] (sel, y_T, y_t, o_T, o_t unused).
+// Dynamic LDS: lns_spectrum::lds_bytes(H, W), at most 154368 bytes (192 x 96).  The denormalisation: as MetricGroupArgs.
+struct SpectrumArgs {
+    const float* frames; const float* y; float* out;
+    int B, C, H, W, S, K, n, y_T, y_t, o_T, o_t, per_channel;
+    float mean, sd;
+    MetricChannelSpec spec;
+    unsigned char sel[8];
+};
+hipError_t launch_spectrum_group(const SpectrumArgs& a, hipStream_t s);
+hipError_t launch_spectrum_stored(const SpectrumArgs& a, hipStream_t s);
+
 // per-sample max |x| (bit patterns) of a [B, n] tensor with batch stride x_bs into amax [B][LNS_AMAX_SUB] (atomic max)
 hipError_t launch_amax(const float* x, long x_bs, long n, int B, unsigned* amax, hipStream_t s);
 hipError_t launch_amax_sticky(const unsigned* amax, int n, unsigned* flag, hipStream_t s);

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "lns_kernels.h"
+#include "lns_spectrum.h"
 
 namespace lns {
 
@@ -5262,6 +5263,8 @@ hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int 
     return hipGetLastError();
 }
 
+#include "spectrum.inc"
+
 // per-sample max |x| of a [B, n] tensor: grid (chunks, B); one atomic per wave
 __global__ __launch_bounds__(256) void amax_kernel(const float* x, long x_bs, long n, unsigned* amax) {
     const int b = blockIdx.y;
@@ -5347,6 +5350,8 @@ hipError_t init_kernels() {
     LNS_SET_LDS((conv_mfma_kernel<1, 1, 1, 4, 3, false, 8>))
     LNS_SET_LDS((conv_mfma_kernel<1, 1, 1, 4, 1, true, 16>))
     LNS_SET_LDS((conv_mfma_kernel<1, 1, 1, 4, 1, false, 16>))
+    LNS_SET_LDS(spectrum_group_kernel)
+    LNS_SET_LDS(spectrum_stored_kernel)
 #define LNS_SET_SWB(HT, WT)                                                                                              \
     {                                                                                                                    \
         constexpr int NWV = fa_sandwich_b_lds_const(HT, WT, 4) <= 160 * 1024 ? 4 : 3;                                    \

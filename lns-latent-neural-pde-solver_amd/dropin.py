@@ -523,6 +523,24 @@ class LatentDynamics(_Hosted):
         x = self._fields(x)
         return self._engine(x).rollout_eval(x, y, param=param, keep_steps=keep_steps, **norm)
 
+    @torch.no_grad()
+    def validate_spectrum(self, x, y, *rest, spectrum_steps=None, keep_steps=(), **norm):
+        """validate_spectrum(x, y, **norm) -- conditional: validate_spectrum(x, y, param, **norm): `validate` with the
+        shell-summed energy spectra of forecast, truth and error of the steps `spectrum_steps` (a sequence, range or slice;
+        None: every step), taken as the steps are decoded.  Returns engine.EvalSpectra: frame, seq, frames as `validate`
+        returns them, spectra [B,n,C,3,S] (S = metrics.spectrum_bins(Ly, Lx); rows forecast, truth, error) and the steps.
+        Bins are index wavenumbers; on the non-periodic families a spectrum carries the leakage of the walls."""
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("validate_spectrum() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if rest:
+            raise TypeError("validate_spectrum() takes (x, y, param, **norm)" if self._conditional
+                            else "validate_spectrum() takes (x, y, **norm)")
+        x = self._fields(x)
+        return self._engine(x).rollout_eval_spectrum(x, y, param=param, keep_steps=keep_steps, spectrum_steps=spectrum_steps, **norm)
+
 
 class LatentDynamicsSW(LatentDynamics):                 # train_stage2_SW.py:90-159
     _family = "sw_half_periodic"

@@ -188,6 +188,15 @@ EnsembleScores.__doc__ = """Result of Engine.rollout_latent_ensemble_eval / ense
 [B, n_keep, C, M + 1] int32 or None, and mean, var, z_last where asked for (None otherwise)."""
 
 
+EvalSpectra = collections.namedtuple("EvalSpectra", "frame seq frames spectra spectrum_steps")
+EvalSpectra.__doc__ = """Result of Engine.rollout_eval_spectrum: frame [B, T, C], seq [B, C] and frames (or None) as rollout_eval
+returns them, spectra [B, len(spectrum_steps), C, 3, S] (rows: forecast, truth, error; S = metrics.spectrum_bins(Ly, Lx)) and
+spectrum_steps (the list of steps the spectra belong to)."""
+EvalSpectraChunk = collections.namedtuple("EvalSpectraChunk", EvalSpectra._fields + ("z_last",))
+EvalSpectraChunk.__doc__ = """Result of Engine.rollout_latent_eval_spectrum: EvalSpectra's five fields for the chunk, then z_last, the
+latent after the chunk's last step -- appended as rollout_latent_eval appends it to rollout_eval's result."""
+
+
 def normalize_keep_steps(keep_steps, steps):
     """The `keep_steps` argument of the selected-step rollout -> list of ints, strictly ascending, in [0, steps).
     A slice is resolved against `steps` as indexing a [.., steps, ..] tensor would (slice(None, None, 5) is `::5`); a
@@ -681,6 +690,77 @@ class Engine:
                                                         self._ptr(frames), z_last.data_ptr(),
                                                         ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_eval")
         return frame, seq, frames, z_last
+
+    # -- streaming validation with energy spectra (include/lns.h "energy spectra") ----------------------------------
+    def spectrum_bins(self, H=None, W=None):
+        """Number of shells S of an H x W plane (default: the model's Ly x Lx); host only."""
+        H, W = (self.cfg.Ly if H is None else int(H)), (self.cfg.Lx if W is None else int(W))
+        from . import metrics
+        return metrics.spectrum_bins(H, W)
+
+    def _spectrum_select(self, spectrum_steps, T, B, device):
+        import torch
+        sel = normalize_keep_steps(range(T) if spectrum_steps is None else spectrum_steps, T)
+        arr = (ctypes.c_int * len(sel))(*sel)
+        spectra = torch.empty((B, len(sel), self.cfg.in_channels, 3, self.spectrum_bins()), dtype=torch.float32, device=device)
+        return sel, arr, spectra
+
+    def energy_spectrum(self, y_hat, y=None, **norm):
+        """Shell-summed energy spectra of stored fields (lns_op_energy_spectrum): y_hat and y (optional) [B, T, C, H, W],
+        normalised; `norm` as in `rollout_eval` (eps is not used).  Returns [B, T, C, 3, S] (forecast, truth, error = forecast -
+        truth differenced before the transform) or, without y, [B, T, C, 1, S]: the kernel body of rollout_eval_spectrum."""
+        from . import metrics
+        return metrics.energy_spectrum(y_hat, y, **norm)
+
+    def rollout_eval_spectrum(self, x, y, steps=None, param=None, keep_steps=(), spectrum_steps=None, **norm):
+        """rollout_eval with the energy spectra of forecast, truth and error of the steps `spectrum_steps` (what
+        `normalize_keep_steps` takes; None: every step), taken where the step is decoded.  Returns EvalSpectra: frame, seq
+        and frames hold rollout_eval's bits, spectra [B, n, C, 3, S] those of
+        `energy_spectrum(rollout(x, T)[:, spectrum_steps], y[:, spectrum_steps], ...)`.  Bins are index wavenumbers; on the
+        non-periodic families a spectrum carries the leakage of the walls.  The workspace is rollout_eval's."""
+        import torch
+        x = self._dev(x)
+        if steps is not None and int(steps) < y.shape[1]:
+            y = y[:, :int(steps)]
+        y, B, T, _, spec, keep, n_keep, frames = self._eval_common(x, y, steps, 0, keep_steps, norm)
+        sel, sel_arr, spectra = self._spectrum_select(spectrum_steps, T, B, x.device)
+        frame = torch.empty((B, T, self.cfg.in_channels), dtype=torch.float32, device=x.device)
+        seq = torch.empty((B, self.cfg.in_channels), dtype=torch.float32, device=x.device)
+        p = self._param(param, x)
+        with torch.cuda.device(x.device):
+            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, x.device)
+            self._check(self._L.lns_rollout_eval_spectrum(
+                self._h, x.data_ptr(), self._ptr(p), y.data_ptr(), B, T, ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(),
+                keep, n_keep, self._ptr(frames), ws.data_ptr(), ws.numel(), self._stream(x), sel_arr, len(sel),
+                spectra.data_ptr()), "lns_rollout_eval_spectrum")
+        return EvalSpectra(frame, seq, frames, spectra, sel)
+
+    def rollout_latent_eval_spectrum(self, z, y, steps=None, t0=0, param=None, keep_steps=(), spectrum_steps=None, frame=None,
+                                     seq=None, **norm):
+        """rollout_latent_eval with energy spectra: keep_steps and spectrum_steps are relative to the chunk, spectra
+        [B, n, C, 3, S] belong to this chunk's steps.  Returns EvalSpectraChunk (see rollout_latent_eval for frame / seq)."""
+        import torch
+        z = self._dev(z)
+        t0 = int(t0)
+        y, B, T, T_total, spec, keep, n_keep, frames = self._eval_common(z, y, steps, t0, keep_steps, norm)
+        sel, sel_arr, spectra = self._spectrum_select(spectrum_steps, T, B, z.device)
+        C = self.cfg.in_channels
+        if frame is None:
+            frame = torch.empty((B, T_total, C), dtype=torch.float32, device=z.device)
+        if seq is None:
+            seq = torch.empty((B, C), dtype=torch.float32, device=z.device)
+        for t, shape in ((frame, (B, T_total, C)), (seq, (B, C))):
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != z.device:
+                raise LnsError("preallocated result must be a contiguous fp32 tensor of shape %s on the input's device" % (shape,))
+        z_last = torch.empty_like(z)
+        p = self._param(param, z)
+        with torch.cuda.device(z.device):
+            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, z.device)
+            self._check(self._L.lns_rollout_latent_eval_spectrum(
+                self._h, z.data_ptr(), self._ptr(p), y.data_ptr(), B, T, t0, T_total, ctypes.byref(spec), frame.data_ptr(),
+                seq.data_ptr(), keep, n_keep, self._ptr(frames), z_last.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(z),
+                sel_arr, len(sel), spectra.data_ptr()), "lns_rollout_latent_eval_spectrum")
+        return EvalSpectraChunk(frame, seq, frames, spectra, sel, z_last)
 
     # -- training rollout of the propagator (include/lns.h "training rollout") ------------------------------------
     def _ptr_array(self, tensors):

@@ -77,6 +77,44 @@ def _launch_metric(L, per_channel, y_hat, y, B, T, C, H, W, mean, std, eps, zero
     return rc
 
 
+def spectrum_bins(H, W):
+    """Number of shells S of the energy spectrum of an H x W plane (include/lns.h "energy spectra"): the shell of the
+    corner mode (H/2, W/2) plus one.  Host only; an unsupported plane (H, W <= 192 and H * W <= 18432) raises."""
+    S = _lib.lib().lns_spectrum_bins(int(H), int(W))
+    if S < 0:
+        raise _lib.LnsError("energy spectrum: a %d x %d plane is not supported (H, W <= 192 and H * W <= 18432)" % (H, W))
+    return int(S)
+
+
+def energy_spectrum(y_hat, y=None, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
+    """Shell-summed energy spectra of stored fields (lns_op_energy_spectrum): y_hat and y (optional) [B,T,C,H,W],
+    normalised, denormalised as in `relative_l2` (eps is not used).  Returns [B,T,C,3,S] -- forecast, truth and error
+    (forecast - truth, differenced before the transform) -- or, without y, [B,T,C,1,S]; S = spectrum_bins(H, W), bin s
+    holds the energy of the modes whose index wavenumber rounds to s, and the bins of a row sum to mean(u^2).  On the
+    non-periodic families a spectrum carries the leakage of the walls.  The kernel body of Engine.rollout_eval_spectrum."""
+    from .engine import eval_spec
+    for t in (y_hat, y):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 5):
+            raise _lib.LnsError("energy_spectrum takes fp32 HIP tensors [B,T,C,H,W] (no CPU fallback)")
+    if y is not None and (y.shape != y_hat.shape or y.device != y_hat.device):
+        raise _lib.LnsError("y must have y_hat's shape %s and device, got %s" % (tuple(y_hat.shape), tuple(y.shape)))
+    B, T, C, H, W = (int(v) for v in y_hat.shape)
+    S = spectrum_bins(H, W)
+    y_hat = y_hat.contiguous()
+    y = y.contiguous() if y is not None else None
+    spec = eval_spec(C, mean=mean, std=std, eps=eps, zero_wall_channels=zero_wall_channels, clamp_channels=clamp_channels,
+                     clamp=clamp)
+    out = torch.empty((B, T, C, 3 if y is not None else 1, S), dtype=torch.float32, device=y_hat.device)
+    L = _lib.lib()
+    with torch.cuda.device(y_hat.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(y_hat.device).cuda_stream)
+        rc = L.lns_op_energy_spectrum(y_hat.data_ptr(), y.data_ptr() if y is not None else None, B, T, C, H, W,
+                                      ctypes.byref(spec), out.data_ptr(), stream)
+    if rc != 0:
+        raise _lib.LnsError("lns_op_energy_spectrum failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    return out
+
+
 def spread_skill_ratio(scores, members):
     """spread * sqrt((M + 1) / M) / rmse of an `engine.EnsembleScores` (Engine.rollout_latent_ensemble_eval,
     LatentDynamics.validate_ensemble) with M = `members`: near 1 for a calibrated ensemble, below it for an
