@@ -417,6 +417,76 @@ int lns_rollout_latent_eval_spectrum(lns_engine* e, const float* z_in, const flo
                                      void* workspace, size_t workspace_bytes, void* stream,
                                      const int* spectrum_steps_host, int n_spec, float* spectra_out);
 
+/* ---- streaming validation: correlation, gradient error, value statistics and histograms ------------------------------
+ * lns_rollout_eval / lns_rollout_latent_eval (and, optionally, the spectra above) with, for selected steps, twelve per-plane
+ * statistics of the decoded frame against the truth plane and, optionally, the value histograms of both -- taken where the
+ * step is decoded, so the [B,T,Cin,Ly,Lx] rollout is never stored.  A statistics kernel follows the scoring kernel of a decoded
+ * group on its decode stream, beside the spectrum launch: one launch per group for the group's selected steps (none
+ * selected: no launch), one block of 256 threads per plane.  Reference: training_utils.py:26-32 (pointwise_correlation) and
+ * training_utils.py:51-58 (GradientDomainLoss.spatial_fd) followed by relative_lp_loss over (-1, -2); the centred
+ * correlation, the moments, the extrema and the histograms have no reference counterpart.
+ *
+ * The statement, for a plane (b, step, c) of H x W pixels, N = (float)(H*W).  P = D_c(yhat) and Q = D_c(y) are the denormalised
+ * forecast and truth, D_c the map of lns_eval_spec as written above for lns_rollout_latent_ensemble_eval (product and sum
+ * rounded one by one, wall-zero and clamp flags included).  Everything is fp32, nothing is fused.  Every plane sum is taken
+ * in the order of the metric kernels: thread t of 256 adds its terms t, t + 256, ... in ascending order, starting from 0;
+ * then the wave sum; then (w0 + w1) + (w2 + w3) over the four waves.  The term index is the row-major pixel index or, for
+ * the gradient sums, the row-major index of the difference grid.
+ *     pass 1   SP = sum P, SQ = sum Q, PP = sum P*P, QQ = sum Q*Q, PQ = sum P*Q
+ *              mP = SP / N, mQ = SQ / N
+ *              cos = PQ / ((sqrtf(PP) + eps) * (sqrtf(QQ) + eps))       (pointwise_correlation; eps = spec.eps)
+ *              min / max of P and of Q with fminf / fmaxf (a NaN pixel is skipped by them and poisons the sums)
+ *     pass 2   a = P - mP, b = Q - mQ;  SA = sum a, SB = sum b, AA = sum a*a, BB = sum b*b, AB = sum a*b
+ *              vP = fmaxf((AA - SA*SA/N) / N, 0), vQ likewise, cov = (AB - SA*SB/N) / N     (corrected two-pass, biased)
+ *              den = sqrtf(vP) * sqrtf(vQ);  corr = den == 0 ? 0 : cov / den
+ *     gradient gyP[y][x] = P[y+2][x] - P[y][x] on (H-2) x W, gxP[y][x] = P[y][x+2] - P[y][x] on H x (W-2); Q likewise
+ *              (spatial_fd: no wrap-around, also on the periodic families)
+ *              GDy = sum (gyP - gyQ)^2, GGy = sum gyQ^2;  grad_y = sqrtf(GDy / (GGy < eps ? eps : GGy));  x likewise
+ *              (H < 3 or W < 3: no terms in either direction, both values are 0)
+ * stats_out holds LNS_FIELD_STATS = 12 floats per plane, in this order:
+ *     mean_P, mean_Q, var_P, var_Q, corr, cos, grad_y, grad_x, min_P, max_P, min_Q, max_Q
+ * (a plane without a non-NaN pixel has min = +inf, max = -inf; in a plane with a NaN pixel the means, cos and the gradient
+ * errors of the fields that hold it are NaN, while fmaxf(NaN, 0) = 0 makes its variance 0 and hence corr 0).
+ *
+ * Histograms are optional and described by lns_stats_spec: nbins in 1 .. 256 and per-channel edges lo_c < hi_c (finite).
+ *     scale_c = (float)nbins / (hi_c - lo_c), formed in fp32 on the host (the difference rounded, then the quotient)
+ *     v < lo_c: bin 0;  v >= hi_c: bin nbins + 1;  else bin 1 + min(nbins - 1, (int)((v - lo_c) * scale_c))  (two rounded ops)
+ *     a NaN is counted nowhere; -inf goes to bin 0, +inf to bin nbins + 1
+ * hist_out is int32 [B][n][Cin][2][nbins + 2], row 0 of the forecast, row 1 of the truth.  Counts are taken with integer
+ * LDS atomics (order-independent) and stored with ordinary stores.
+ * One block owns one plane and stores its 12 floats and its counts itself: no float atomics, no finish kernel, no workspace
+ * region; nothing depends on the grouping or the scheduling options, so the streaming calls and lns_op_field_stats (one
+ * device function) produce the same bits.  Planes of any size work (the planes are re-read, not staged). */
+#define LNS_FIELD_STATS 12
+typedef struct lns_stats_spec {
+    uint32_t size;      /* sizeof(lns_stats_spec) */
+    int32_t nbins;      /* 1 .. 256 */
+    float lo[8], hi[8]; /* per channel, in denormalised units */
+} lns_stats_spec;
+
+/* lns_rollout_eval_spectrum / lns_rollout_latent_eval_spectrum (same leading arguments; n_spec = 0: no spectra, the three
+ * spectrum arguments are ignored) followed by the statistics selection: stats_steps_host, n_stats >= 1 ascending 0-based
+ * steps of this call's T (HOST array, read during the call; independent of keep_steps_host and spectrum_steps_host),
+ * hspec (nullable), stats_out [B][n_stats][Cin][12] and hist_out (nullable) [B][n_stats][Cin][2][nbins + 2].
+ * frame_out / seq_out / frames_out / spectra_out keep the bits of the existing calls; the workspace is
+ * lns_rollout_eval_workspace_bytes(B) and nothing more.  Refusals (host only): those of lns_rollout_eval, then those of the
+ * spectrum selection when n_spec != 0, then LNS_EINVAL for stats_out null, n_stats < 1, stats_steps_host null / out of
+ * range / not ascending, hist_out without hspec, a wrong hspec->size, nbins outside 1 .. 256, a non-finite edge or hi <= lo
+ * for a channel below in_channels, and histograms with in_channels > 8.  hspec without hist_out is checked and unused. */
+int lns_rollout_eval_stats(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                           const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host,
+                           int n_keep, float* frames_out, void* workspace, size_t workspace_bytes, void* stream,
+                           const int* spectrum_steps_host, int n_spec, float* spectra_out,
+                           const int* stats_steps_host, int n_stats, const lns_stats_spec* hspec, float* stats_out,
+                           int32_t* hist_out);
+int lns_rollout_latent_eval_stats(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                  int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                  const int* keep_steps_host, int n_keep, float* frames_out, float* z_last,
+                                  void* workspace, size_t workspace_bytes, void* stream,
+                                  const int* spectrum_steps_host, int n_spec, float* spectra_out,
+                                  const int* stats_steps_host, int n_stats, const lns_stats_spec* hspec, float* stats_out,
+                                  int32_t* hist_out);
+
 /* Post-run health check.  Every kernel of a plan records, per sample, the running maximum of |y| of the tensor it
  * produces (the side channel from which the split-operand convolutions derive their activation scale); a NaN or inf
  * anywhere in a tensor survives in it.  This call synchronises `stream`, reads those few KB back from `workspace`
@@ -605,7 +675,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * are there; "rollout_select" = lns_rollout_select & co. are there; "rollout_ensemble" = lns_rollout_latent_ensemble,
  * its size query and lns_op_ensemble_stats are there; "ensemble_score" = lns_rollout_latent_ensemble_eval and
  * lns_op_ensemble_score are there; "eval_spectrum" = lns_rollout_eval_spectrum, lns_rollout_latent_eval_spectrum,
- * lns_op_energy_spectrum and lns_spectrum_bins are there.  1 / 0; -1: unknown name.
+ * lns_op_energy_spectrum and lns_spectrum_bins are there; "eval_stats" = lns_rollout_eval_stats,
+ * lns_rollout_latent_eval_stats and lns_op_field_stats are there.  1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
 
@@ -688,6 +759,14 @@ int lns_op_ensemble_score(const float* frames, const float* y, int n, int B, int
  * the per-channel form needs C <= 8.  Checks precede the launch (message: lns_create_error()); the call synchronises `stream`. */
 int lns_op_energy_spectrum(const float* yhat, const float* y /* nullable */, int B, int T, int C, int H, int W,
                            const lns_eval_spec* spec, float* out, void* stream);
+
+/* The statistics kernel of lns_rollout_eval_stats on stored fields, without an engine: yhat and y [B][T][C][H][W],
+ * normalised -> stats_out [B][T][C][12] and, with hspec and hist_out, hist_out [B][T][C][2][nbins + 2].  The per-plane body
+ * is the streaming call's (one device function).  H * W <= 2^30, B * T * C < 2^31; the per-channel form and histograms need
+ * C <= 8.  Checks precede the launch (message: lns_create_error()); the call synchronises `stream`. */
+int lns_op_field_stats(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
+                       const lns_stats_spec* hspec /* nullable */, float* stats_out, int32_t* hist_out /* nullable */,
+                       void* stream);
 
 /* GroupNorm statistics -> per-(b,c) (scale,shift) such that norm(x) = x*scale+shift. */
 int lns_op_groupnorm_stats(const float* x, int B, int C, int HW, int groups, float eps,

@@ -71,6 +71,14 @@ class LnsEvalSpec(ctypes.Structure):
     ]
 
 
+LNS_FIELD_STATS = 12
+
+
+class LnsStatsSpec(ctypes.Structure):
+    """Mirror of `struct lns_stats_spec` (include/lns.h): the value histograms of the field statistics."""
+    _fields_ = [("size", ctypes.c_uint32), ("nbins", _I32), ("lo", _F32x8), ("hi", _F32x8)]
+
+
 LNS_SL1_CHUNK = 4096
 
 
@@ -105,6 +113,7 @@ SYMBOLS = [
     "lns_rollout_ensemble_workspace_bytes", "lns_rollout_latent_ensemble", "lns_op_ensemble_stats",
     "lns_rollout_latent_ensemble_eval", "lns_op_ensemble_score",
     "lns_spectrum_bins", "lns_rollout_eval_spectrum", "lns_rollout_latent_eval_spectrum", "lns_op_energy_spectrum",
+    "lns_rollout_eval_stats", "lns_rollout_latent_eval_stats", "lns_op_field_stats",
     "lns_train_workspace_bytes", "lns_train_forward", "lns_train_backward",
     "lns_loss_smooth_l1", "lns_adam_step", "lns_adam_step_tensors", "lns_train_step_workspace_bytes", "lns_train_step",
     "lns_grad_norm_scratch_bytes", "lns_grad_norm_tensors", "lns_grad_scale_tensors", "lns_update_step_tensors",
@@ -199,6 +208,13 @@ def lib():
         L.lns_rollout_latent_eval_spectrum.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, vp, c.c_size_t, vp,
                                                        ip, i, vp]
         L.lns_op_energy_spectrum.argtypes = [vp, vp, i, i, i, i, i, sp, vp, vp]
+    if hasattr(L, "lns_rollout_eval_stats"):
+        sp, ip, hp = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.POINTER(LnsStatsSpec)
+        L.lns_rollout_eval_stats.argtypes = [vp, vp, vp, vp, i, i, sp, vp, vp, ip, i, vp, vp, c.c_size_t, vp, ip, i, vp,
+                                             ip, i, hp, vp, vp]
+        L.lns_rollout_latent_eval_stats.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, vp, c.c_size_t, vp,
+                                                    ip, i, vp, ip, i, hp, vp, vp]
+        L.lns_op_field_stats.argtypes = [vp, vp, i, i, i, i, i, sp, hp, vp, vp, vp]
     if hasattr(L, "lns_check_finite"):      # (absent from older builds loaded through LNS_HIP_LIB for A/B runs)
         L.lns_check_finite.argtypes = [vp, i, vp, c.c_size_t, vp]
     if hasattr(L, "lns_set_option"):

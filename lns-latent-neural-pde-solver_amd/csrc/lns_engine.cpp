@@ -1840,6 +1840,10 @@ struct RolloutCall {
     float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
     // SINK_SCORED with spectra (lns_rollout_eval_spectrum): spectra_out [B][n_spec][C][3][S] of the steps spec_steps[0 .. n_spec) (host, ascending)
     bool spectra = false; const int* spec_steps = nullptr; int n_spec = 0; float* spectra_out = nullptr;
+    // SINK_SCORED with field statistics (lns_rollout_eval_stats): stats_out [B][n_stats][C][12] and, with hspec, hist_out
+    // [B][n_stats][C][2][nbins + 2] of the steps stats_steps[0 .. n_stats) (host, ascending)
+    bool stats = false; const int* stats_steps = nullptr; int n_stats = 0; const lns_stats_spec* hspec = nullptr;
+    float* stats_out = nullptr; int32_t* hist_out = nullptr;
     float* latents_out = nullptr;                        // optional side outputs: all T latents [B][T][zper],
     float* z_last = nullptr;                             // the latent after the last step [B][zper]
     void* ws = nullptr; size_t ws_bytes = 0; void* stream = nullptr;
@@ -2210,6 +2214,41 @@ static void spectrum_args(const lns_engine* e, const RolloutCall& c, SpectrumArg
     memset(s.sel, 0, sizeof s.sel);
 }
 
+// The histogram part of FieldStatsArgs from an lns_stats_spec (nullable: no histograms), for C channels.  Returns the
+// refusal's text, or null when the description is usable (or absent).  Host only.
+static const char* stats_hist_args(const lns_stats_spec* hs, const int32_t* hist_out, int C, FieldStatsArgs* a) {
+    a->hist = nullptr; a->nbins = 0;
+    for (int ch = 0; ch < LNS_METRIC_MAX_CH; ++ch) { a->hlo[ch] = 0.0f; a->hhi[ch] = 1.0f; a->hscale[ch] = 1.0f; }
+    if (hist_out && !hs) return "hist_out needs a histogram description (hspec is null)";
+    if (!hs) return nullptr;
+    if (hs->size != sizeof(lns_stats_spec)) return "hspec: the size field is not sizeof(lns_stats_spec)";
+    if (hs->nbins < 1 || hs->nbins > 256) return "hspec: nbins must be in 1 .. 256";
+    for (int ch = 0; ch < C && ch < LNS_METRIC_MAX_CH; ++ch)
+        if (!std::isfinite(hs->lo[ch]) || !std::isfinite(hs->hi[ch]) || !(hs->hi[ch] > hs->lo[ch]))
+            return "hspec: the edges of every channel must be finite with hi > lo";
+    if (C > LNS_METRIC_MAX_CH) return "histograms need in_channels <= 8";
+    if (!hist_out) return nullptr;                   // a description without a destination: no histograms
+    a->hist = const_cast<int32_t*>(hist_out); a->nbins = hs->nbins;
+    for (int ch = 0; ch < C; ++ch) {
+        a->hlo[ch] = hs->lo[ch]; a->hhi[ch] = hs->hi[ch];
+        const float width = hs->hi[ch] - hs->lo[ch];
+        a->hscale[ch] = (float)hs->nbins / width;
+    }
+    return nullptr;
+}
+
+// the statistics kernel's arguments for a SINK_SCORED call with statistics; frames / n / sel / y_t / o_t are set per decoded group
+static void field_stats_args(const lns_engine* e, const RolloutCall& c, FieldStatsArgs* fp) {
+    FieldStatsArgs& f = *fp;
+    memset(&f, 0, sizeof f);
+    f.y = c.y_true; f.stats = c.stats_out;
+    f.B = c.B; f.C = e->cfg.in_channels; f.H = e->cfg.Ly; f.W = e->cfg.Lx;
+    f.y_T = c.T_total; f.o_T = c.n_stats;
+    f.per_channel = c.spec->per_channel != 0; f.mean = c.spec->mean; f.sd = c.spec->std; f.eps = c.spec->eps;
+    channel_spec(c.spec, f.C, &f.spec);
+    stats_hist_args(c.hspec, c.hist_out, f.C, &f);   // (accepted by rollout_refusal)
+}
+
 // the same for the scoring kernel of a scored SINK_ENSEMBLE call; frames / kk / y_t are set per decoded group
 static void score_args(const lns_engine* e, const RolloutCall& c, EnsembleScoreArgs* sp) {
     EnsembleScoreArgs& s = *sp;
@@ -2281,6 +2320,8 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     if (ens && c.ens_scored) score_args(e, c, &sc);
     SpectrumArgs sx;
     if (scored && c.spectra) spectrum_args(e, c, &sx);
+    FieldStatsArgs fs;
+    if (scored && c.stats) field_stats_args(e, c, &fs);
     // A decode group is the next up to kdec DECODED steps: all steps, the kept ones, or none.  The chain writes the
     // latent of a decoded step into the group's next ring slot; the latent of a step nobody decodes goes into `out`
     // (SINK_LATENTS) or into the two ping-pong buffers in turn (SINK_KEPT, SINK_ENSEMBLE), so a step never writes the buffer it reads.
@@ -2306,7 +2347,7 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
         npp ^= 1;
         return chain_step(t, znext);
     };
-    int g = 0, gi = 0, ki = 0, si = 0, t = 0;        // ki / si: next entry of c.keep / c.spec_steps (SINK_SCORED); t: next step of the chain
+    int g = 0, gi = 0, ki = 0, si = 0, fi = 0, t = 0; // ki / si / fi: next entry of c.keep / c.spec_steps / c.stats_steps (SINK_SCORED); t: next step of the chain
     for (int i0 = 0; i0 < n_dec;) {                  // i0: index in `out` of the group's first step
         const int kk = std::min(kdec, n_dec - i0);
         const int t0g = dec_step(i0);                // the group's first step
@@ -2343,6 +2384,11 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
                 sx.frames = fb; sx.y_t = c.t0 + t0g; sx.o_t = si; sx.n = 0;
                 for (; si < c.n_spec && c.spec_steps[si] < t0g + kk; ++si) sx.sel[sx.n++] = (unsigned char)(c.spec_steps[si] - t0g);
                 if (sx.n) HIPCHK(e, launch_spectrum_group(sx, dstream[d]));
+            }
+            if (c.stats) {                           // likewise, beside the spectrum launch
+                fs.frames = fb; fs.y_t = c.t0 + t0g; fs.o_t = fi; fs.n = 0;
+                for (; fi < c.n_stats && c.stats_steps[fi] < t0g + kk; ++fi) fs.sel[fs.n++] = (unsigned char)(c.stats_steps[fi] - t0g);
+                if (fs.n) HIPCHK(e, launch_field_stats_group(fs, dstream[d]));
             }
         }
         if (ens && c.ens_scored) {                   // fb is [kk][traj][M][xper] against y_true[b][i0 .. i0 + kk)
@@ -2434,6 +2480,18 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
             e->err = fmt("energy spectrum: a %d x %d plane is not supported (H, W <= 192 and H * W <= 18432)", e->cfg.Ly, e->cfg.Lx);
             return LNS_EINVAL;
         }
+    }
+    if (scored && c.stats) {
+        if (!c.stats_out) return einval(e, "stats_out is null");
+        if (c.n_stats < 1) return einval(e, "n_stats must be at least 1");
+        if (!c.stats_steps) return einval(e, "stats_steps is null");
+        for (int i = 0; i < c.n_stats; ++i)
+            if (c.stats_steps[i] < 0 || c.stats_steps[i] >= c.T || (i > 0 && c.stats_steps[i] <= c.stats_steps[i - 1])) {
+                e->err = fmt("stats_steps must be ascending steps in [0, %d): entry %d is %d", c.T, i, c.stats_steps[i]);
+                return LNS_EINVAL;
+            }
+        FieldStatsArgs probe;
+        if (const char* why = stats_hist_args(c.hspec, c.hist_out, e->cfg.in_channels, &probe)) return einval(e, why);
     }
     if (int brc = check_batch(e, c.B)) return brc;
     if (scored && c.T_total > e->opt_eval_max_steps) {
@@ -2544,6 +2602,38 @@ int lns_rollout_latent_eval_spectrum(lns_engine* e, const float* z_in, const flo
     score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
     c.z_last = z_last;
     c.spectra = true; c.spec_steps = spectrum_steps_host; c.n_spec = n_spec; c.spectra_out = spectra_out;
+    return rollout_call(e, c);
+}
+
+// ---- streaming validation with field statistics (include/lns.h) ---------------------------------------------------
+static void stats_into(RolloutCall& c, const int* spectrum_steps_host, int n_spec, float* spectra_out, const int* stats_steps_host,
+                       int n_stats, const lns_stats_spec* hspec, float* stats_out, int32_t* hist_out) {
+    c.spectra = n_spec != 0; c.spec_steps = spectrum_steps_host; c.n_spec = n_spec; c.spectra_out = spectra_out;
+    c.stats = true; c.stats_steps = stats_steps_host; c.n_stats = n_stats; c.hspec = hspec; c.stats_out = stats_out;
+    c.hist_out = hist_out;
+}
+
+int lns_rollout_eval_stats(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                           const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
+                           float* frames_out, void* ws, size_t ws_bytes, void* stream, const int* spectrum_steps_host, int n_spec,
+                           float* spectra_out, const int* stats_steps_host, int n_stats, const lns_stats_spec* hspec,
+                           float* stats_out, int32_t* hist_out) {
+    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
+    score_into(c, y_true, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
+    stats_into(c, spectrum_steps_host, n_spec, spectra_out, stats_steps_host, n_stats, hspec, stats_out, hist_out);
+    return rollout_call(e, c);
+}
+
+int lns_rollout_latent_eval_stats(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                  int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                  const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* ws,
+                                  size_t ws_bytes, void* stream, const int* spectrum_steps_host, int n_spec, float* spectra_out,
+                                  const int* stats_steps_host, int n_stats, const lns_stats_spec* hspec, float* stats_out,
+                                  int32_t* hist_out) {
+    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
+    score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
+    c.z_last = z_last;
+    stats_into(c, spectrum_steps_host, n_spec, spectra_out, stats_steps_host, n_stats, hspec, stats_out, hist_out);
     return rollout_call(e, c);
 }
 
@@ -2680,6 +2770,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "rollout_ensemble")) return 1;
     if (!strcmp(feature, "ensemble_score")) return 1;
     if (!strcmp(feature, "eval_spectrum")) return 1;
+    if (!strcmp(feature, "eval_stats")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else
@@ -3001,6 +3092,33 @@ int lns_op_energy_spectrum(const float* yhat, const float* y, int B, int T, int 
     a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std;
     channel_spec(spec, C, &a.spec);
     OPCHK(launch_spectrum_stored(a, s));
+    OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+static_assert(LNS_FIELD_STATS_N == LNS_FIELD_STATS, "the kernels' and the header's number of statistics differ");
+
+// field_stats_stored_kernel on stored fields: the per-plane body of the streaming call (field_stats_plane)
+int lns_op_field_stats(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
+                       const lns_stats_spec* hspec, float* stats_out, int32_t* hist_out, void* stream) {
+    if (!yhat || !y || !stats_out) { g_create_error = "field_stats: yhat / y / stats_out is null"; return LNS_EINVAL; }
+    if (!spec || spec->size != sizeof(lns_eval_spec)) {
+        g_create_error = "field_stats: spec is null or its size field is not sizeof(lns_eval_spec)"; return LNS_EINVAL;
+    }
+    if (B < 1 || T < 1 || C < 1 || H < 1 || W < 1 || (int64_t)H * W > (1LL << 30) || (int64_t)B * T * C > 0x7fffffffLL) {
+        g_create_error = "field_stats: B, T, C, H, W >= 1, H * W <= 2^30 and B * T * C < 2^31"; return LNS_EINVAL;
+    }
+    if (spec->per_channel && C > LNS_METRIC_MAX_CH) { g_create_error = "field_stats: the per-channel form needs C <= 8"; return LNS_EINVAL; }
+    FieldStatsArgs a;
+    memset(&a, 0, sizeof a);
+    if (const char* why = stats_hist_args(hspec, hist_out, C, &a)) { g_create_error = std::string("field_stats: ") + why; return LNS_EINVAL; }
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    a.frames = yhat; a.y = y; a.stats = stats_out;
+    a.B = B; a.C = C; a.H = H; a.W = W; a.n = T;
+    a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std; a.eps = spec->eps;
+    channel_spec(spec, C, &a.spec);
+    OPCHK(launch_field_stats_stored(a, s));
     OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
 }

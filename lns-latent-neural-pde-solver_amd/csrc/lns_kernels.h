@@ -435,6 +435,25 @@ struct SpectrumArgs {
 hipError_t launch_spectrum_group(const SpectrumArgs& a, hipStream_t s);
 hipError_t launch_spectrum_stored(const SpectrumArgs& a, hipStream_t s);
 
+// Field statistics (lns_rollout_eval_stats, lns_op_field_stats; the statement: include/lns.h): one block per plane writes its
+// LNS_FIELD_STATS_N floats to stats and, when hist is given, its 2 x (nbins + 2) int32 counts (forecast row, truth row).
+// Group form: frames [kk][B][C][H*W]; the n <= 8 selected steps sel[0 .. n) of the group against the truth planes
+// y[b][y_t + sel[i]][c] of y [B][y_T][C][H*W] into plane (b, o_t + i, c) of stats [B][o_T][C][12] / hist [B][o_T][C][2][nbins + 2].
+// Stored form: frames and y are [B][n][C][H*W], the outputs [B][n][C][..] (sel, y_T, y_t, o_T, o_t unused).
+// hlo / hhi / hscale: the per-channel edges and (float)nbins / (hi - lo) (C <= 8 with hist).  Static LDS only (2.2 KB).
+// The denormalisation: as MetricGroupArgs.
+#define LNS_FIELD_STATS_N 12
+struct FieldStatsArgs {
+    const float* frames; const float* y; float* stats; int* hist;
+    int B, C, H, W, n, y_T, y_t, o_T, o_t, per_channel, nbins;
+    float mean, sd, eps;
+    MetricChannelSpec spec;
+    float hlo[LNS_METRIC_MAX_CH], hhi[LNS_METRIC_MAX_CH], hscale[LNS_METRIC_MAX_CH];
+    unsigned char sel[8];
+};
+hipError_t launch_field_stats_group(const FieldStatsArgs& a, hipStream_t s);
+hipError_t launch_field_stats_stored(const FieldStatsArgs& a, hipStream_t s);
+
 // per-sample max |x| (bit patterns) of a [B, n] tensor with batch stride x_bs into amax [B][LNS_AMAX_SUB] (atomic max)
 hipError_t launch_amax(const float* x, long x_bs, long n, int B, unsigned* amax, hipStream_t s);
 hipError_t launch_amax_sticky(const unsigned* amax, int n, unsigned* flag, hipStream_t s);

@@ -541,6 +541,25 @@ class LatentDynamics(_Hosted):
         x = self._fields(x)
         return self._engine(x).rollout_eval_spectrum(x, y, param=param, keep_steps=keep_steps, spectrum_steps=spectrum_steps, **norm)
 
+    @torch.no_grad()
+    def validate_stats(self, x, y, *rest, stats_steps=None, hist=None, spectrum_steps=(), keep_steps=(), **norm):
+        """validate_stats(x, y, **norm) -- conditional: validate_stats(x, y, param, **norm): `validate` with the per-plane
+        field statistics (metrics.FIELD_STATS: means, variances, correlation, gradient-domain error, extrema) of the steps
+        `stats_steps` (a sequence, range or slice; None: every step) and, with hist = (nbins, lo, hi), the value histograms
+        of forecast and truth, taken as the steps are decoded; `spectrum_steps` adds validate_spectrum's spectra in the
+        same pass.  Returns engine.EvalStats.  metrics.correlation_time turns the corr column into a decorrelation step."""
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("validate_stats() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if rest:
+            raise TypeError("validate_stats() takes (x, y, param, **norm)" if self._conditional
+                            else "validate_stats() takes (x, y, **norm)")
+        x = self._fields(x)
+        return self._engine(x).rollout_eval_stats(x, y, param=param, keep_steps=keep_steps, stats_steps=stats_steps, hist=hist,
+                                                  spectrum_steps=spectrum_steps, **norm)
+
 
 class LatentDynamicsSW(LatentDynamics):                 # train_stage2_SW.py:90-159
     _family = "sw_half_periodic"

@@ -6,6 +6,7 @@ hot path on CUDA/HIP tensors.  torch is used for device memory and streams only.
 """
 import collections
 import ctypes
+import numbers
 
 import numpy as np
 
@@ -195,6 +196,37 @@ spectrum_steps (the list of steps the spectra belong to)."""
 EvalSpectraChunk = collections.namedtuple("EvalSpectraChunk", EvalSpectra._fields + ("z_last",))
 EvalSpectraChunk.__doc__ = """Result of Engine.rollout_latent_eval_spectrum: EvalSpectra's five fields for the chunk, then z_last, the
 latent after the chunk's last step -- appended as rollout_latent_eval appends it to rollout_eval's result."""
+
+
+EvalStats = collections.namedtuple("EvalStats", "frame seq frames stats hist stats_steps spectra spectrum_steps")
+EvalStats.__doc__ = """Result of Engine.rollout_eval_stats: frame [B, T, C], seq [B, C] and frames (or None) as rollout_eval returns
+them, stats [B, len(stats_steps), C, 12] (columns: metrics.FIELD_STATS), hist [B, len(stats_steps), C, 2, nbins + 2] int32 (rows
+forecast, truth; bins: metrics.histogram_edges) or None, stats_steps, and spectra [B, len(spectrum_steps), C, 3, S] or None with
+spectrum_steps (empty: no spectra were asked for)."""
+EvalStatsChunk = collections.namedtuple("EvalStatsChunk", EvalStats._fields + ("z_last",))
+EvalStatsChunk.__doc__ = """Result of Engine.rollout_latent_eval_stats: EvalStats' fields for the chunk, then z_last, the latent after
+the chunk's last step."""
+
+
+def stats_spec(C, hist):
+    """`lns_stats_spec` from hist = (nbins, lo, hi) with scalar or per-channel edges (denormalised units); None -> None."""
+    if hist is None:
+        return None
+    nbins, lo, hi = hist
+    hs = _lib.LnsStatsSpec()
+    hs.size = ctypes.sizeof(_lib.LnsStatsSpec)
+    hs.nbins = int(nbins)
+    for name, v in (("lo", lo), ("hi", hi)):
+        try:                                                            # a number, a numpy scalar or a 0-d array / tensor
+            scalar = isinstance(v, numbers.Real) or getattr(v, "ndim", None) == 0
+            vals = [float(v)] * min(C, 8) if scalar else [float(e) for e in v]
+        except (TypeError, ValueError):
+            raise LnsError("hist: %s must be a number or one value per channel (%d), got %r" % (name, C, v))
+        if len(vals) != min(C, 8) and len(vals) != C:
+            raise LnsError("hist: %s must be a number or one value per channel (%d), got %d" % (name, C, len(vals)))
+        for ch, e in enumerate(vals[:8]):
+            getattr(hs, name)[ch] = e
+    return hs
 
 
 def normalize_keep_steps(keep_steps, steps):
@@ -761,6 +793,85 @@ class Engine:
                 seq.data_ptr(), keep, n_keep, self._ptr(frames), z_last.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(z),
                 sel_arr, len(sel), spectra.data_ptr()), "lns_rollout_latent_eval_spectrum")
         return EvalSpectraChunk(frame, seq, frames, spectra, sel, z_last)
+
+    # -- streaming validation with field statistics (include/lns.h "field statistics") ----------------------------
+    def field_stats(self, y_hat, y, hist=None, **norm):
+        """Per-plane statistics of stored fields (lns_op_field_stats): see metrics.field_stats.  The kernel body of
+        rollout_eval_stats."""
+        from . import metrics
+        return metrics.field_stats(y_hat, y, hist=hist, **norm)
+
+    def _stats_select(self, stats_steps, spectrum_steps, hist, T, B, device):
+        """-> (stats steps, their array, stats, lns_stats_spec or None, hist or None, spectrum steps, their array or None, spectra or None)"""
+        import torch
+        C = self.cfg.in_channels
+        sel = normalize_keep_steps(range(T) if stats_steps is None else stats_steps, T)
+        arr = (ctypes.c_int * len(sel))(*sel)
+        stats = torch.empty((B, len(sel), C, _lib.LNS_FIELD_STATS), dtype=torch.float32, device=device)
+        hs = stats_spec(C, hist)
+        counts = None
+        if hs is not None:
+            if not 1 <= hs.nbins <= 256:
+                raise LnsError("hist: nbins must be in 1 .. 256, got %d" % hs.nbins)
+            counts = torch.empty((B, len(sel), C, 2, hs.nbins + 2), dtype=torch.int32, device=device)
+        no_spectra = spectrum_steps is not None and not isinstance(spectrum_steps, slice) and len(spectrum_steps) == 0
+        ssel, sarr, spectra = ([], None, None) if no_spectra else self._spectrum_select(spectrum_steps, T, B, device)
+        return sel, arr, stats, hs, counts, ssel, sarr, spectra
+
+    def rollout_eval_stats(self, x, y, steps=None, param=None, keep_steps=(), stats_steps=None, hist=None, spectrum_steps=(),
+                           **norm):
+        """rollout_eval with, for the steps `stats_steps` (what `normalize_keep_steps` takes; None: every step), the twelve
+        per-plane statistics metrics.FIELD_STATS of the decoded frame against the truth -- means, variances, centred
+        correlation, the reference's pointwise_correlation, the gradient-domain relative L2 in y and x, and the extrema -- and,
+        with hist = (nbins, lo, hi) (scalar or per-channel edges, denormalised units), the value histograms of both.
+        `spectrum_steps` (default: none; None: every step) adds rollout_eval_spectrum's spectra in the same pass.  Returns
+        EvalStats: frame, seq, frames and spectra hold the bits of the existing calls, stats / hist those of
+        `field_stats(rollout(x, T)[:, stats_steps], y[:, stats_steps], hist, ...)`.  The workspace is rollout_eval's."""
+        import torch
+        x = self._dev(x)
+        if steps is not None and int(steps) < y.shape[1]:
+            y = y[:, :int(steps)]
+        y, B, T, _, spec, keep, n_keep, frames = self._eval_common(x, y, steps, 0, keep_steps, norm)
+        sel, arr, stats, hs, counts, ssel, sarr, spectra = self._stats_select(stats_steps, spectrum_steps, hist, T, B, x.device)
+        frame = torch.empty((B, T, self.cfg.in_channels), dtype=torch.float32, device=x.device)
+        seq = torch.empty((B, self.cfg.in_channels), dtype=torch.float32, device=x.device)
+        p = self._param(param, x)
+        with torch.cuda.device(x.device):
+            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, x.device)
+            self._check(self._L.lns_rollout_eval_stats(
+                self._h, x.data_ptr(), self._ptr(p), y.data_ptr(), B, T, ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(),
+                keep, n_keep, self._ptr(frames), ws.data_ptr(), ws.numel(), self._stream(x), sarr, len(ssel), self._ptr(spectra),
+                arr, len(sel), ctypes.byref(hs) if hs is not None else None, stats.data_ptr(), self._ptr(counts)),
+                "lns_rollout_eval_stats")
+        return EvalStats(frame, seq, frames, stats, counts, sel, spectra, ssel)
+
+    def rollout_latent_eval_stats(self, z, y, steps=None, t0=0, param=None, keep_steps=(), stats_steps=None, hist=None,
+                                  spectrum_steps=(), frame=None, seq=None, **norm):
+        """rollout_latent_eval with field statistics: keep_steps, stats_steps and spectrum_steps are relative to the chunk,
+        stats / hist / spectra belong to this chunk's steps.  Returns EvalStatsChunk (see rollout_latent_eval for frame / seq)."""
+        import torch
+        z = self._dev(z)
+        t0 = int(t0)
+        y, B, T, T_total, spec, keep, n_keep, frames = self._eval_common(z, y, steps, t0, keep_steps, norm)
+        sel, arr, stats, hs, counts, ssel, sarr, spectra = self._stats_select(stats_steps, spectrum_steps, hist, T, B, z.device)
+        C = self.cfg.in_channels
+        if frame is None:
+            frame = torch.empty((B, T_total, C), dtype=torch.float32, device=z.device)
+        if seq is None:
+            seq = torch.empty((B, C), dtype=torch.float32, device=z.device)
+        for t, shape in ((frame, (B, T_total, C)), (seq, (B, C))):
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != z.device:
+                raise LnsError("preallocated result must be a contiguous fp32 tensor of shape %s on the input's device" % (shape,))
+        z_last = torch.empty_like(z)
+        p = self._param(param, z)
+        with torch.cuda.device(z.device):
+            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, z.device)
+            self._check(self._L.lns_rollout_latent_eval_stats(
+                self._h, z.data_ptr(), self._ptr(p), y.data_ptr(), B, T, t0, T_total, ctypes.byref(spec), frame.data_ptr(),
+                seq.data_ptr(), keep, n_keep, self._ptr(frames), z_last.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(z),
+                sarr, len(ssel), self._ptr(spectra), arr, len(sel), ctypes.byref(hs) if hs is not None else None,
+                stats.data_ptr(), self._ptr(counts)), "lns_rollout_latent_eval_stats")
+        return EvalStatsChunk(frame, seq, frames, stats, counts, sel, spectra, ssel, z_last)
 
     # -- training rollout of the propagator (include/lns.h "training rollout") ------------------------------------
     def _ptr_array(self, tensors):

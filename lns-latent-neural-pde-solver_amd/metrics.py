@@ -115,6 +115,67 @@ def energy_spectrum(y_hat, y=None, mean=0.0, std=1.0, eps=1e-8, zero_wall_channe
     return out
 
 
+FIELD_STATS = ("mean_P", "mean_Q", "var_P", "var_Q", "corr", "cos", "grad_y", "grad_x", "min_P", "max_P", "min_Q", "max_Q")
+
+
+def field_stats(y_hat, y, hist=None, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
+    """Per-plane statistics of stored fields (lns_op_field_stats; include/lns.h "field statistics"): y_hat and y [B,T,C,H,W],
+    normalised, denormalised as in `relative_l2` into forecast P and truth Q.  Returns (stats [B,T,C,12], hist): the columns
+    are FIELD_STATS -- the means and biased variances of P and Q, their centred correlation `corr`, the reference's
+    pointwise_correlation `cos`, the relative L2 of the central differences in y and x (GradientDomainLoss.spatial_fd, no
+    wrap-around), and the extrema.  hist = (nbins, lo, hi) with scalar or per-channel edges adds int32 counts
+    [B,T,C,2,nbins+2] (rows forecast, truth; bin 0 below lo, bin nbins+1 from hi on; see histogram_edges), else None.
+    The kernel body of Engine.rollout_eval_stats."""
+    from .engine import eval_spec, stats_spec
+    for t in (y_hat, y):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 5:
+            raise _lib.LnsError("field_stats takes fp32 HIP tensors [B,T,C,H,W] (no CPU fallback)")
+    if y.shape != y_hat.shape or y.device != y_hat.device:
+        raise _lib.LnsError("y must have y_hat's shape %s and device, got %s" % (tuple(y_hat.shape), tuple(y.shape)))
+    B, T, C, H, W = (int(v) for v in y_hat.shape)
+    y_hat, y = y_hat.contiguous(), y.contiguous()
+    spec = eval_spec(C, mean=mean, std=std, eps=eps, zero_wall_channels=zero_wall_channels, clamp_channels=clamp_channels,
+                     clamp=clamp)
+    hs = stats_spec(C, hist)
+    stats = torch.empty((B, T, C, _lib.LNS_FIELD_STATS), dtype=torch.float32, device=y_hat.device)
+    counts = None
+    if hs is not None:
+        if not 1 <= hs.nbins <= 256:
+            raise _lib.LnsError("hist: nbins must be in 1 .. 256, got %d" % hs.nbins)
+        counts = torch.empty((B, T, C, 2, hs.nbins + 2), dtype=torch.int32, device=y_hat.device)
+    L = _lib.lib()
+    with torch.cuda.device(y_hat.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(y_hat.device).cuda_stream)
+        rc = L.lns_op_field_stats(y_hat.data_ptr(), y.data_ptr(), B, T, C, H, W, ctypes.byref(spec),
+                                  ctypes.byref(hs) if hs is not None else None, stats.data_ptr(),
+                                  counts.data_ptr() if counts is not None else None, stream)
+    if rc != 0:
+        raise _lib.LnsError("lns_op_field_stats failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    return stats, counts
+
+
+def histogram_edges(nbins, lo, hi):
+    """The nbins + 1 edges lo + k (hi - lo) / nbins of the interior bins of a field_stats histogram, float64 [nbins + 1]
+    (lo, hi scalars) or [C, nbins + 1] (per channel).  Bin 0 of the counts lies below edges[0], bin k in 1 .. nbins between
+    edges[k - 1] and edges[k], bin nbins + 1 from edges[-1] on.  (The kernel places a value by (v - lo) * (nbins / (hi - lo))
+    in fp32: a value within rounding of an interior edge may fall on either side.)"""
+    lo_t = torch.as_tensor(lo, dtype=torch.float64)
+    hi_t = torch.as_tensor(hi, dtype=torch.float64)
+    k = torch.arange(int(nbins) + 1, dtype=torch.float64) / int(nbins)
+    return lo_t.unsqueeze(-1) + (hi_t - lo_t).unsqueeze(-1) * k
+
+
+def correlation_time(corr, steps, threshold=0.8):
+    """corr [B, n, C] (column `corr` or `cos` of field statistics taken at `steps`, n ascending steps) -> int64 [B, C]: the
+    first of `steps` at which the correlation is below `threshold`, -1 where it never is (a NaN is not below)."""
+    steps_t = torch.as_tensor(list(steps), dtype=torch.int64, device=corr.device)
+    if corr.dim() != 3 or corr.shape[1] != steps_t.numel():
+        raise _lib.LnsError("correlation_time takes corr [B, n, C] and n steps, got %s and %d" % (tuple(corr.shape), steps_t.numel()))
+    below = corr < threshold
+    first = below.to(torch.int64).argmax(dim=1)
+    return torch.where(below.any(dim=1), steps_t[first], torch.full_like(first, -1))
+
+
 def spread_skill_ratio(scores, members):
     """spread * sqrt((M + 1) / M) / rmse of an `engine.EnsembleScores` (Engine.rollout_latent_ensemble_eval,
     LatentDynamics.validate_ensemble) with M = `members`: near 1 for a calibrated ensemble, below it for an
