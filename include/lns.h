@@ -487,6 +487,78 @@ int lns_rollout_latent_eval_stats(lns_engine* e, const float* z_in, const float*
                                   const int* stats_steps_host, int n_stats, const lns_stats_spec* hspec, float* stats_out,
                                   int32_t* hist_out);
 
+/* ---- streaming validation: per-pixel time-mean, variance, covariance and error maps ---------------------------------
+ * Everything above reduces over space, per step.  These maps reduce over time, per pixel: where the error lives, whether
+ * the forecast keeps the time-mean state and whether it keeps the temporal variance -- again without storing the
+ * [B,T,Cin,Ly,Lx] rollout.  An accumulation kernel follows the statistics launch of a decoded group on its decode stream
+ * (one launch per group for the group's selected steps; none selected: no launch) and adds the group's steps to a state of
+ * 52 bytes per (b, c, pixel) in the workspace; a finish kernel turns the state into the maps once the horizon is complete.
+ * (No reference counterpart: the reference has no per-pixel time statistics.)
+ *
+ * The statement, for a trajectory b, channel c and pixel p.  P_t = D_c(yhat) and Q_t = D_c(y) are the denormalised fp32
+ * forecast and truth of step t, D_c the map of lns_eval_spec as written above for lns_rollout_latent_ensemble_eval (product
+ * and sum rounded one by one, wall-zero and clamp flags included).  K = D_c(y_true[b][0][c][p]) is the truth's first frame of
+ * the horizon (step 0 of T_total): a per-pixel shift that costs no state and keeps the sums small beside an offset.
+ * The selected steps are t >= map_from with (t - map_from) % map_every == 0, in steps of the horizon: a rule, not a list,
+ * so a chunked call derives everything from t0, T and T_total and carries no count between calls.  n is their number.
+ * In ascending t, all in float64, every operation rounded on its own (no contraction):
+ *     a = (double)P_t - (double)K      b = (double)Q_t - (double)K      e = (double)P_t - (double)Q_t
+ *     Sa += a   Sb += b   Saa += a*a   Sbb += b*b   Sab += a*b   See += e*e
+ *     mx = fmaxf(mx, (float)fabs(e))         (fp32 state, from 0; a NaN is skipped by fmaxf and poisons the sums of that pixel only)
+ * The finish, in float64, each result then rounded once to fp32; N = (double)n, d = (double)max(n - 1, 1):
+ *     mean_P = K + Sa/N        mean_Q = K + Sb/N
+ *     var_P  = v > 0 ? v : 0 with v = (Saa - Sa*Sa/N)/d  (so 0 for a NaN), var_Q likewise     (unbiased; n = 1: exactly 0)
+ *     cov    = (Sab - Sa*Sb/N)/d
+ *     mse    = See/N           max_err = mx
+ * maps_out holds LNS_TIME_MAPS = 7 planes per (b, c), in this order: mean_P, mean_Q, var_P, var_Q, cov, mse, max_err;
+ * it is fp32 [B][Cin][7][Ly][Lx].  bias = mean_P - mean_Q, rmse = sqrt(mse) and the temporal correlation
+ * cov / sqrt(var_P var_Q) are left to the caller.
+ * Why float64 sums and a shift: a sequential fp32 Welford recurrence misses the project's rule max(2e-7, 3 x torch's own fp32
+ * error) against float64 (1.4 x the bound at n = 64, 7 to 12 x at n = 1024, orders of magnitude on 1e3 + 1e-2 x); this
+ * statement stays near 1e-7 relative for n up to 1024 on unit, 1e-12, 1e12, offset and drifting fields.
+ * A thread owns its pixels and is the only writer of their state: no float atomics, no reduction across threads.  The order
+ * of a pixel's steps is the only order there is, and it is kept across the decode streams by chaining the accumulation
+ * launches with events, so the maps have the same bits for every decode_group / decode_streams / overlap setting, for every
+ * chunking of the horizon, and as lns_op_time_maps computes them on the stored rollout (one device function). */
+#define LNS_TIME_MAPS 7
+
+/* The optional selections and outputs of a streaming validation call, in one sized struct (the argument lists above do not
+ * grow again).  n_spec == 0 / n_stats == 0: none, and the pointers of that part are ignored; otherwise the part is what
+ * lns_rollout_eval_spectrum / lns_rollout_eval_stats take, steps relative to this call's T.  map_from / map_every are steps
+ * of the horizon (T_total), the same in every chunk. */
+typedef struct lns_eval_select {
+    uint32_t size;                    /* sizeof(lns_eval_select) */
+    int32_t n_spec, n_stats;
+    int32_t map_from, map_every;
+    int32_t reserved;                 /* 0 */
+    const int* spectrum_steps_host;
+    float* spectra_out;
+    const int* stats_steps_host;
+    const lns_stats_spec* hspec;      /* nullable */
+    float* stats_out;
+    int32_t* hist_out;                /* nullable */
+    float* maps_out;                  /* [B][Cin][7][Ly][Lx]; written by the call that completes the horizon */
+} lns_eval_select;
+
+/* lns_rollout_eval_workspace_bytes(B), byte for byte, followed by the state region (52 B * Cin * Ly * Lx bytes), rounded to 256. */
+int lns_rollout_eval_maps_workspace_bytes(lns_engine* e, int B, size_t* bytes);
+
+/* lns_rollout_eval / lns_rollout_latent_eval (same leading arguments) with the selections of `sel`.  frame_out / seq_out /
+ * frames_out / spectra_out / stats_out / hist_out keep the bits of the existing calls.  The call with t0 == 0 clears the state
+ * (in stream order), every call adds its selected steps, the call with t0 + T == T_total writes maps_out; until then maps_out
+ * is untouched.  The chunks of one horizon share one workspace, which nothing else may use in between.
+ * Refusals (host only): those of lns_rollout_eval, of the spectrum selection when n_spec != 0 and of the statistics selection
+ * when n_stats != 0; then LNS_EINVAL for sel null or sel->size wrong (the two selections then count as absent), maps_out null,
+ * map_every < 1, map_from outside [0, T_total); LNS_ENOMEM for a workspace below lns_rollout_eval_maps_workspace_bytes(B). */
+int lns_rollout_eval_maps(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                          const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host,
+                          int n_keep, float* frames_out, void* workspace, size_t workspace_bytes, void* stream,
+                          const lns_eval_select* sel);
+int lns_rollout_latent_eval_maps(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                 int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                 const int* keep_steps_host, int n_keep, float* frames_out, float* z_last,
+                                 void* workspace, size_t workspace_bytes, void* stream, const lns_eval_select* sel);
+
 /* Post-run health check.  Every kernel of a plan records, per sample, the running maximum of |y| of the tensor it
  * produces (the side channel from which the split-operand convolutions derive their activation scale); a NaN or inf
  * anywhere in a tensor survives in it.  This call synchronises `stream`, reads those few KB back from `workspace`
@@ -676,7 +748,9 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * its size query and lns_op_ensemble_stats are there; "ensemble_score" = lns_rollout_latent_ensemble_eval and
  * lns_op_ensemble_score are there; "eval_spectrum" = lns_rollout_eval_spectrum, lns_rollout_latent_eval_spectrum,
  * lns_op_energy_spectrum and lns_spectrum_bins are there; "eval_stats" = lns_rollout_eval_stats,
- * lns_rollout_latent_eval_stats and lns_op_field_stats are there.  1 / 0; -1: unknown name.
+ * lns_rollout_latent_eval_stats and lns_op_field_stats are there; "eval_maps" = lns_rollout_eval_maps,
+ * lns_rollout_latent_eval_maps, their size query, lns_op_time_maps and lns_time_maps_state_bytes are there.
+ * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
 
@@ -767,6 +841,16 @@ int lns_op_energy_spectrum(const float* yhat, const float* y /* nullable */, int
 int lns_op_field_stats(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
                        const lns_stats_spec* hspec /* nullable */, float* stats_out, int32_t* hist_out /* nullable */,
                        void* stream);
+
+/* The time maps of lns_rollout_eval_maps on stored fields, without an engine: yhat and y [B][T][C][H][W], normalised ->
+ * maps_out [B][C][7][H][W] over the steps map_from, map_from + map_every, ... below T (the horizon is T, K is y[b][0]).
+ * `state` is device memory of at least lns_time_maps_state_bytes(B, C, H, W) = 52 B C H W rounded up to 256 bytes, 8-byte
+ * aligned; the call clears it, accumulates (the streaming call's device function) and finishes.  H * W <= 2^30, B <= 65535;
+ * the per-channel form needs C <= 8.  Checks precede the launches (message: lns_create_error()): LNS_EINVAL, or LNS_ENOMEM
+ * for a state_bytes below the need; the call synchronises `stream`. */
+int lns_time_maps_state_bytes(int B, int C, int H, int W, size_t* bytes);
+int lns_op_time_maps(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
+                     int map_from, int map_every, float* maps_out, void* state, size_t state_bytes, void* stream);
 
 /* GroupNorm statistics -> per-(b,c) (scale,shift) such that norm(x) = x*scale+shift. */
 int lns_op_groupnorm_stats(const float* x, int B, int C, int HW, int groups, float eps,

@@ -79,6 +79,20 @@ class LnsStatsSpec(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("nbins", _I32), ("lo", _F32x8), ("hi", _F32x8)]
 
 
+LNS_TIME_MAPS = 7
+
+
+class LnsEvalSelect(ctypes.Structure):
+    """Mirror of `struct lns_eval_select` (include/lns.h): the optional selections and outputs of lns_rollout_eval_maps."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("n_spec", _I32), ("n_stats", _I32), ("map_from", _I32), ("map_every", _I32),
+        ("reserved", _I32),
+        ("spectrum_steps_host", ctypes.POINTER(ctypes.c_int)), ("spectra_out", ctypes.c_void_p),
+        ("stats_steps_host", ctypes.POINTER(ctypes.c_int)), ("hspec", ctypes.POINTER(LnsStatsSpec)),
+        ("stats_out", ctypes.c_void_p), ("hist_out", ctypes.c_void_p), ("maps_out", ctypes.c_void_p),
+    ]
+
+
 LNS_SL1_CHUNK = 4096
 
 
@@ -114,6 +128,8 @@ SYMBOLS = [
     "lns_rollout_latent_ensemble_eval", "lns_op_ensemble_score",
     "lns_spectrum_bins", "lns_rollout_eval_spectrum", "lns_rollout_latent_eval_spectrum", "lns_op_energy_spectrum",
     "lns_rollout_eval_stats", "lns_rollout_latent_eval_stats", "lns_op_field_stats",
+    "lns_rollout_eval_maps_workspace_bytes", "lns_rollout_eval_maps", "lns_rollout_latent_eval_maps",
+    "lns_time_maps_state_bytes", "lns_op_time_maps",
     "lns_train_workspace_bytes", "lns_train_forward", "lns_train_backward",
     "lns_loss_smooth_l1", "lns_adam_step", "lns_adam_step_tensors", "lns_train_step_workspace_bytes", "lns_train_step",
     "lns_grad_norm_scratch_bytes", "lns_grad_norm_tensors", "lns_grad_scale_tensors", "lns_update_step_tensors",
@@ -215,6 +231,13 @@ def lib():
         L.lns_rollout_latent_eval_stats.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, vp, c.c_size_t, vp,
                                                     ip, i, vp, ip, i, hp, vp, vp]
         L.lns_op_field_stats.argtypes = [vp, vp, i, i, i, i, i, sp, hp, vp, vp, vp]
+    if hasattr(L, "lns_rollout_eval_maps"):
+        sp, ip, qp = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.POINTER(LnsEvalSelect)
+        L.lns_rollout_eval_maps_workspace_bytes.argtypes = [vp, i, c.POINTER(c.c_size_t)]
+        L.lns_rollout_eval_maps.argtypes = [vp, vp, vp, vp, i, i, sp, vp, vp, ip, i, vp, vp, c.c_size_t, vp, qp]
+        L.lns_rollout_latent_eval_maps.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, vp, c.c_size_t, vp, qp]
+        L.lns_time_maps_state_bytes.argtypes = [i, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_op_time_maps.argtypes = [vp, vp, i, i, i, i, i, sp, i, i, vp, vp, c.c_size_t, vp]
     if hasattr(L, "lns_check_finite"):      # (absent from older builds loaded through LNS_HIP_LIB for A/B runs)
         L.lns_check_finite.argtypes = [vp, i, vp, c.c_size_t, vp]
     if hasattr(L, "lns_set_option"):

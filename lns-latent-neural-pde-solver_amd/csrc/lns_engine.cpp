@@ -1755,7 +1755,7 @@ enum SinkKind { SINK_LATENTS, SINK_STEPS, SINK_KEPT, SINK_SCORED, SINK_ENSEMBLE 
 // bit-identical for every kdec.
 // Behind it, from round_up(that layout's total, 256) on, the region the sink needs (kept and frame regions for the ensemble sink):
 //   SINK_SCORED  one frame buffer per decode stream (the decode output of a group, [kdec][B][C][Ly][Lx]), then the
-//                metric's per-plane sums [B][eval_max_steps][C][2]
+//                metric's per-plane sums [B][eval_max_steps][C][2]; a call with time maps appends their state (add_maps_region)
 //   SINK_KEPT    two latent buffers [B][zper] that take the latents of the steps nobody decodes
 //   SINK_ENSEMBLE  (B = N) the two latent buffers of SINK_KEPT, then the frame buffers of SINK_SCORED
 enum { NDEC = 4, NGROUP_MAX = NDEC + 2 };   // max decode streams; latent groups in flight
@@ -1763,6 +1763,7 @@ struct WsLayout {
     size_t z_bytes, ring_off, group_bytes, arena_off, arena_stride, prop_off, total; int ndec, kdec, ngroup;
     size_t fbuf_off, fbuf_stride, part_off;   // SINK_SCORED; SINK_ENSEMBLE (no part)
     size_t pp_off[2];                         // SINK_KEPT, SINK_ENSEMBLE
+    size_t maps_off = 0, maps_bytes = 0;      // SINK_SCORED with time maps (add_maps_region)
 };
 
 static int decode_group(const lns_engine* e, int B) {
@@ -1821,6 +1822,17 @@ static int ws_layout(lns_engine* e, int B, SinkKind sink, WsLayout* L) {
     return LNS_OK;
 }
 
+// The state of the time maps (lns_rollout_eval_maps): 52 bytes per (b, c, pixel), behind the SINK_SCORED layout, which it leaves
+// byte for byte as it is.
+static size_t time_maps_state_bytes(size_t B, size_t C, size_t H, size_t W) {
+    return round_up_sz(B * C * H * W * LNS_TIME_MAPS_STATE_PER_PIXEL, 256);
+}
+static void add_maps_region(const lns_engine* e, int B, WsLayout* L) {
+    L->maps_off = round_up_sz(L->total, 256);
+    L->maps_bytes = time_maps_state_bytes((size_t)B, (size_t)e->cfg.in_channels, (size_t)e->cfg.Ly, (size_t)e->cfg.Lx);
+    L->total = L->maps_off + L->maps_bytes;
+}
+
 // One rollout call, as the entry points (lns_rollout, lns_rollout_latent, their _eval / _select forms and
 // lns_rollout_latent_ensemble) describe it
 struct RolloutCall {
@@ -1844,6 +1856,9 @@ struct RolloutCall {
     // [B][n_stats][C][2][nbins + 2] of the steps stats_steps[0 .. n_stats) (host, ascending)
     bool stats = false; const int* stats_steps = nullptr; int n_stats = 0; const lns_stats_spec* hspec = nullptr;
     float* stats_out = nullptr; int32_t* hist_out = nullptr;
+    // SINK_SCORED with time maps (lns_rollout_eval_maps): maps_out [B][C][7][Ly][Lx] over the steps t >= map_from of the horizon
+    // with (t - map_from) % map_every == 0; sel_bad: the call's lns_eval_select was null or of the wrong size
+    bool maps = false, sel_bad = false; int map_from = 0, map_every = 1; float* maps_out = nullptr;
     float* latents_out = nullptr;                        // optional side outputs: all T latents [B][T][zper],
     float* z_last = nullptr;                             // the latent after the last step [B][zper]
     void* ws = nullptr; size_t ws_bytes = 0; void* stream = nullptr;
@@ -1864,7 +1879,7 @@ static int ensure_overlap_objects(lns_engine* e) {
         HIPCHK(e, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         e->dec_streams.push_back(st);
     }
-    for (int i = 0; i < 2 * NGROUP_MAX + 1 + NDEC; ++i) {
+    for (int i = 0; i < 2 * NGROUP_MAX + 1 + 2 * NDEC; ++i) {   // ev_z, ev_free, ev_start, ev_end, ev_maps (rollout_loop)
         hipEvent_t ev;
         HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         e->events.push_back(ev);
@@ -2249,6 +2264,18 @@ static void field_stats_args(const lns_engine* e, const RolloutCall& c, FieldSta
     stats_hist_args(c.hspec, c.hist_out, f.C, &f);   // (accepted by rollout_refusal)
 }
 
+// the accumulation kernel's arguments for a SINK_SCORED call with time maps; frames / n / sel / y_t are set per decoded group
+static void time_maps_args(const lns_engine* e, const RolloutCall& c, const WsLayout& L, TimeMapsArgs* tp) {
+    TimeMapsArgs& t = *tp;
+    memset(&t, 0, sizeof t);
+    t.y = c.y_true; t.state = static_cast<char*>(c.ws) + L.maps_off; t.maps = c.maps_out;
+    t.B = c.B; t.C = e->cfg.in_channels; t.H = e->cfg.Ly; t.W = e->cfg.Lx;
+    t.y_T = c.T_total; t.first = c.map_from; t.every = c.map_every;
+    t.count = (c.T_total - 1 - c.map_from) / c.map_every + 1;
+    t.per_channel = c.spec->per_channel != 0; t.mean = c.spec->mean; t.sd = c.spec->std;
+    channel_spec(c.spec, t.C, &t.spec);
+}
+
 // the same for the scoring kernel of a scored SINK_ENSEMBLE call; frames / kk / y_t are set per decoded group
 static void score_args(const lns_engine* e, const RolloutCall& c, EnsembleScoreArgs* sp) {
     EnsembleScoreArgs& s = *sp;
@@ -2302,12 +2329,13 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     }
     Runner rp_side(e, pstream);
     Runner& rp = overlap ? rp_side : r;              // single-stream: everything through the caller's runner (timing events)
-    hipEvent_t *ev_z = nullptr, *ev_free = nullptr, *ev_end = nullptr;
+    hipEvent_t *ev_z = nullptr, *ev_free = nullptr, *ev_end = nullptr, *ev_maps = nullptr;
     if (overlap) {
         ev_z = e->events.data();                     // ev_z[g]: the latents of ring group g are complete
         ev_free = e->events.data() + NGROUP_MAX;     // ev_free[g]: the decode that read ring group g has finished
         hipEvent_t ev_start = e->events[2 * NGROUP_MAX];
         ev_end = e->events.data() + 2 * NGROUP_MAX + 1;   // [0]: propagator stream, [d]: decode stream d
+        ev_maps = ev_end + NDEC;                     // [d]: the last time-map accumulation launched on decode stream d
         HIPCHK(e, hipEventRecord(ev_start, stream));
         HIPCHK(e, hipStreamWaitEvent(pstream, ev_start, 0));
         for (int d = 1; d < ndec; ++d) HIPCHK(e, hipStreamWaitEvent(dstream[d], ev_start, 0));
@@ -2322,6 +2350,9 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     if (scored && c.spectra) spectrum_args(e, c, &sx);
     FieldStatsArgs fs;
     if (scored && c.stats) field_stats_args(e, c, &fs);
+    TimeMapsArgs tm;
+    if (scored && c.maps) time_maps_args(e, c, L, &tm);
+    int maps_d = -1;                                 // the decode stream of the latest time-map accumulation of this call
     // A decode group is the next up to kdec DECODED steps: all steps, the kept ones, or none.  The chain writes the
     // latent of a decoded step into the group's next ring slot; the latent of a step nobody decodes goes into `out`
     // (SINK_LATENTS) or into the two ping-pong buffers in turn (SINK_KEPT, SINK_ENSEMBLE), so a step never writes the buffer it reads.
@@ -2389,6 +2420,23 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
                 fs.frames = fb; fs.y_t = c.t0 + t0g; fs.o_t = fi; fs.n = 0;
                 for (; fi < c.n_stats && c.stats_steps[fi] < t0g + kk; ++fi) fs.sel[fs.n++] = (unsigned char)(c.stats_steps[fi] - t0g);
                 if (fs.n) HIPCHK(e, launch_field_stats_group(fs, dstream[d]));
+            }
+            if (c.maps) {
+                // The one result of the scored path that is reduced across groups: a pixel's sums take its steps in ascending
+                // order, so the accumulations form a chain across the decode streams -- this one waits for the previous
+                // group's, which ran on another stream.  Only the accumulation is chained; decode and scoring stay unordered
+                // against other groups.  Last in the group's launches: stream order still covers the frame buffer's reuse.
+                tm.frames = fb; tm.y_t = c.t0 + t0g; tm.n = 0;
+                for (int j = 0; j < kk; ++j) {
+                    const int ta = c.t0 + t0g + j;   // the step of the horizon
+                    if (ta >= c.map_from && (ta - c.map_from) % c.map_every == 0) tm.sel[tm.n++] = (unsigned char)j;
+                }
+                if (tm.n) {
+                    if (overlap && maps_d >= 0 && maps_d != d) HIPCHK(e, hipStreamWaitEvent(dstream[d], ev_maps[maps_d], 0));
+                    HIPCHK(e, launch_time_maps_group(tm, dstream[d]));
+                    if (overlap && ndec > 1) HIPCHK(e, hipEventRecord(ev_maps[d], dstream[d]));
+                    maps_d = d;
+                }
             }
         }
         if (ens && c.ens_scored) {                   // fb is [kk][traj][M][xper] against y_true[b][i0 .. i0 + kk)
@@ -2493,6 +2541,15 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
         FieldStatsArgs probe;
         if (const char* why = stats_hist_args(c.hspec, c.hist_out, e->cfg.in_channels, &probe)) return einval(e, why);
     }
+    if (scored && c.maps) {
+        if (c.sel_bad) return einval(e, "sel is null or its size field is not sizeof(lns_eval_select)");
+        if (!c.maps_out) return einval(e, "maps_out is null");
+        if (c.map_every < 1) return einval(e, "map_every must be at least 1");
+        if (c.map_from < 0 || c.map_from >= c.T_total) {
+            e->err = fmt("map_from must be a step in [0, %d), got %d", c.T_total, c.map_from);
+            return LNS_EINVAL;
+        }
+    }
     if (int brc = check_batch(e, c.B)) return brc;
     if (scored && c.T_total > e->opt_eval_max_steps) {
         e->err = fmt("%d steps exceed the option eval_max_steps = %d (it sizes the evaluation workspace)", c.T_total, e->opt_eval_max_steps);
@@ -2510,8 +2567,9 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     const bool scored = c.sink == SINK_SCORED;
     DeviceGuard dg(e);
     WsLayout L;
-    if ((rc = ws_layout(e, c.B, c.sink, &L)) ||
-        (rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : (c.sink == SINK_ENSEMBLE ? "ensemble " : "")),
+    if ((rc = ws_layout(e, c.B, c.sink, &L))) return rc;
+    if (scored && c.maps) add_maps_region(e, c.B, &L);
+    if ((rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : (c.sink == SINK_ENSEMBLE ? "ensemble " : "")),
                        c.ws, c.ws_bytes))) return rc;
     Plan* pe = nullptr;
     if (c.encode && (rc = get_plan(e, PK_ENC, c.B, 0, 0, &pe))) return rc;
@@ -2530,12 +2588,19 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
         if ((rc = r.run(*pe, ext, base + L.arena_off))) return rc;
         z0.ptr = base;
     }
+    // time maps: the horizon's first call clears the state on the caller's stream, which every stream of the loop starts behind
+    if (scored && c.maps && c.t0 == 0) HIPCHK(e, hipMemsetAsync(base + L.maps_off, 0, L.maps_bytes, r.stream));
     if ((rc = rollout_loop(e, r, z0, c, L))) return rc;
     // every plane's pair is in place once the decode streams have joined: frame- and sequence-wise ratios, once the
     // horizon is complete (the pairs of the earlier chunks are in the workspace)
     if (scored && c.t0 + c.T == c.T_total)
         HIPCHK(e, launch_metric_finish(reinterpret_cast<float*>(base + L.part_off), c.B, c.T_total, cfg.in_channels, c.spec->eps,
                                        c.frame_out, c.seq_out, r.stream));
+    if (scored && c.maps && c.t0 + c.T == c.T_total) {   // likewise: the state of all chunks -> the seven maps
+        TimeMapsArgs tm;
+        time_maps_args(e, c, L, &tm);
+        HIPCHK(e, launch_time_maps_finish(tm, r.stream));
+    }
     if (c.sink == SINK_ENSEMBLE && c.ens_scored)     // likewise: the plane sums in scores_out -> the scores, in place
         HIPCHK(e, launch_ensemble_score_finish(c.scores_out, c.traj, c.n_keep, cfg.in_channels, cfg.Ly * cfg.Lx, c.spec->eps,
                                                c.seq_out, r.stream));
@@ -2634,6 +2699,47 @@ int lns_rollout_latent_eval_stats(lns_engine* e, const float* z_in, const float*
     score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
     c.z_last = z_last;
     stats_into(c, spectrum_steps_host, n_spec, spectra_out, stats_steps_host, n_stats, hspec, stats_out, hist_out);
+    return rollout_call(e, c);
+}
+
+// ---- streaming validation with time maps (include/lns.h) ----------------------------------------------------------
+static void maps_into(RolloutCall& c, const lns_eval_select* sel) {
+    c.maps = true;
+    c.sel_bad = !sel || sel->size != sizeof(lns_eval_select);
+    if (c.sel_bad) return;
+    c.spectra = sel->n_spec != 0; c.spec_steps = sel->spectrum_steps_host; c.n_spec = sel->n_spec; c.spectra_out = sel->spectra_out;
+    c.stats = sel->n_stats != 0; c.stats_steps = sel->stats_steps_host; c.n_stats = sel->n_stats; c.hspec = sel->hspec;
+    c.stats_out = sel->stats_out; c.hist_out = sel->hist_out;
+    c.map_from = sel->map_from; c.map_every = sel->map_every; c.maps_out = sel->maps_out;
+}
+
+int lns_rollout_eval_maps_workspace_bytes(lns_engine* e, int B, size_t* bytes) {
+    size_t base = 0;
+    if (int rc = workspace_bytes(e, B, SINK_SCORED, &base)) return rc;
+    WsLayout L;
+    L.total = base;
+    add_maps_region(e, B, &L);
+    if (bytes) *bytes = L.total;
+    return LNS_OK;
+}
+
+int lns_rollout_eval_maps(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                          const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
+                          float* frames_out, void* ws, size_t ws_bytes, void* stream, const lns_eval_select* sel) {
+    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
+    score_into(c, y_true, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
+    maps_into(c, sel);
+    return rollout_call(e, c);
+}
+
+int lns_rollout_latent_eval_maps(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                 int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                 const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* ws,
+                                 size_t ws_bytes, void* stream, const lns_eval_select* sel) {
+    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
+    score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
+    c.z_last = z_last;
+    maps_into(c, sel);
     return rollout_call(e, c);
 }
 
@@ -2771,6 +2877,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "ensemble_score")) return 1;
     if (!strcmp(feature, "eval_spectrum")) return 1;
     if (!strcmp(feature, "eval_stats")) return 1;
+    if (!strcmp(feature, "eval_maps")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else
@@ -3119,6 +3226,47 @@ int lns_op_field_stats(const float* yhat, const float* y, int B, int T, int C, i
     a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std; a.eps = spec->eps;
     channel_spec(spec, C, &a.spec);
     OPCHK(launch_field_stats_stored(a, s));
+    OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+static_assert(LNS_TIME_MAPS_N == LNS_TIME_MAPS, "the kernels' and the header's number of time maps differ");
+
+int lns_time_maps_state_bytes(int B, int C, int H, int W, size_t* bytes) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || (int64_t)H * W > (1LL << 30) || (int64_t)C * H * W > (1LL << 38)) {
+        g_create_error = "time_maps: B, C, H, W >= 1, H * W <= 2^30 and C * H * W <= 2^38"; return LNS_EINVAL;
+    }
+    if (bytes) *bytes = time_maps_state_bytes((size_t)B, (size_t)C, (size_t)H, (size_t)W);
+    return LNS_OK;
+}
+
+// the accumulation and finish kernels of lns_rollout_eval_maps on stored fields (one device function with the streaming call)
+int lns_op_time_maps(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec, int map_from,
+                     int map_every, float* maps_out, void* state, size_t state_bytes, void* stream) {
+    if (!yhat || !y || !maps_out) { g_create_error = "time_maps: yhat / y / maps_out is null"; return LNS_EINVAL; }
+    if (!spec || spec->size != sizeof(lns_eval_spec)) {
+        g_create_error = "time_maps: spec is null or its size field is not sizeof(lns_eval_spec)"; return LNS_EINVAL;
+    }
+    if (T < 1 || B > LNS_MAX_BATCH) { g_create_error = "time_maps: T >= 1 and B <= 65535"; return LNS_EINVAL; }
+    size_t need = 0;
+    if (int rc = lns_time_maps_state_bytes(B, C, H, W, &need)) return rc;
+    if (spec->per_channel && C > LNS_METRIC_MAX_CH) { g_create_error = "time_maps: the per-channel form needs C <= 8"; return LNS_EINVAL; }
+    if (map_every < 1) { g_create_error = "time_maps: map_every must be at least 1"; return LNS_EINVAL; }
+    if (map_from < 0 || map_from >= T) { g_create_error = fmt("time_maps: map_from must be a step in [0, %d), got %d", T, map_from); return LNS_EINVAL; }
+    if (!state || (reinterpret_cast<uintptr_t>(state) & 7)) { g_create_error = "time_maps: state is null or not 8-byte aligned"; return LNS_EINVAL; }
+    if (state_bytes < need) { g_create_error = fmt("time_maps: state too small: need %zu bytes, got %zu", need, state_bytes); return LNS_ENOMEM; }
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TimeMapsArgs a;
+    memset(&a, 0, sizeof a);
+    a.frames = yhat; a.y = y; a.state = state; a.maps = maps_out;
+    a.B = B; a.C = C; a.H = H; a.W = W; a.y_T = T; a.first = map_from; a.every = map_every;
+    a.n = a.count = (T - 1 - map_from) / map_every + 1;
+    a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std;
+    channel_spec(spec, C, &a.spec);
+    OPCHK(hipMemsetAsync(state, 0, (size_t)B * C * H * W * LNS_TIME_MAPS_STATE_PER_PIXEL, s));
+    OPCHK(launch_time_maps_stored(a, s));
+    OPCHK(launch_time_maps_finish(a, s));
     OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
 }

@@ -454,6 +454,26 @@ struct FieldStatsArgs {
 hipError_t launch_field_stats_group(const FieldStatsArgs& a, hipStream_t s);
 hipError_t launch_field_stats_stored(const FieldStatsArgs& a, hipStream_t s);
 
+// Time maps (lns_rollout_eval_maps, lns_op_time_maps; the statement: include/lns.h): per (b, c, pixel) six float64 sums and
+// an fp32 running maximum over the selected steps, in `state`: [6][N] doubles (Sa, Sb, Saa, Sbb, Sab, See) followed by [N]
+// floats, N = B * C * H * W, 52 N bytes; 8-byte aligned, zeroed before the first step of a horizon.
+// Group form: frames [kk][B][C][H*W]; the n <= 8 steps sel[0 .. n) (ascending) of the group against y[b][y_t + sel[i]][c] of
+// y [B][y_T][C][H*W]; the shift K is D_c(y[b][0][c]).  Stored form: frames and y are [B][y_T][C][H*W], the steps are first,
+// first + every, ... (n of them, the last below y_T).  Finish: state and y[b][0] -> maps [B][C][7][H*W] for `count` selected
+// steps in all.  A thread owns its pixels: no LDS, no atomics.  The denormalisation: as MetricGroupArgs.
+#define LNS_TIME_MAPS_N 7
+#define LNS_TIME_MAPS_STATE_PER_PIXEL 52
+struct TimeMapsArgs {
+    const float* frames; const float* y; void* state; float* maps;
+    int B, C, H, W, n, y_T, y_t, first, every, count, per_channel;
+    float mean, sd;
+    MetricChannelSpec spec;
+    unsigned char sel[8];
+};
+hipError_t launch_time_maps_group(const TimeMapsArgs& a, hipStream_t s);
+hipError_t launch_time_maps_stored(const TimeMapsArgs& a, hipStream_t s);
+hipError_t launch_time_maps_finish(const TimeMapsArgs& a, hipStream_t s);
+
 // per-sample max |x| (bit patterns) of a [B, n] tensor with batch stride x_bs into amax [B][LNS_AMAX_SUB] (atomic max)
 hipError_t launch_amax(const float* x, long x_bs, long n, int B, unsigned* amax, hipStream_t s);
 hipError_t launch_amax_sticky(const unsigned* amax, int n, unsigned* flag, hipStream_t s);

@@ -560,8 +560,30 @@ class LatentDynamics(_Hosted):
         return self._engine(x).rollout_eval_stats(x, y, param=param, keep_steps=keep_steps, stats_steps=stats_steps, hist=hist,
                                                   spectrum_steps=spectrum_steps, **norm)
 
+    @torch.no_grad()
+    def validate_maps(self, x, y, *rest, map_steps=None, stats_steps=(), hist=None, spectrum_steps=(), keep_steps=(), **norm):
+        """validate_maps(x, y, **norm) -- conditional: validate_maps(x, y, param, **norm): `validate` with the per-pixel time
+        maps (metrics.TIME_MAPS: time-mean of forecast and truth, temporal variances and covariance, mean squared and largest
+        error) over the steps `map_steps` (None: every step; slice(from, None, every) or (from, every) for burn-in and
+        thinning), accumulated as the steps are decoded; `stats_steps` / `hist` and `spectrum_steps` add validate_stats'
+        statistics and validate_spectrum's spectra in the same pass.  Returns engine.EvalMaps.  metrics.rmse_map and
+        metrics.temporal_correlation derive the usual maps from it."""
+        from .engine import normalize_map_steps
+        normalize_map_steps(map_steps)                  # a ValueError before anything touches the device
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("validate_maps() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if rest:
+            raise TypeError("validate_maps() takes (x, y, param, **norm)" if self._conditional
+                            else "validate_maps() takes (x, y, **norm)")
+        x = self._fields(x)
+        return self._engine(x).rollout_eval_maps(x, y, param=param, keep_steps=keep_steps, map_steps=map_steps,
+                                                 stats_steps=stats_steps, hist=hist, spectrum_steps=spectrum_steps, **norm)
 
-class LatentDynamicsSW(LatentDynamics):                 # train_stage2_SW.py:90-159
+
+class LatentDynamicsSW(LatentDynamics):                # train_stage2_SW.py:90-159
     _family = "sw_half_periodic"
     _ae_cls = SimpleAutoencoderHalfPeriodic
     _prop_cls = SimpleCNNHalfPeriodic

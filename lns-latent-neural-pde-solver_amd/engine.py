@@ -208,6 +208,39 @@ EvalStatsChunk.__doc__ = """Result of Engine.rollout_latent_eval_stats: EvalStat
 the chunk's last step."""
 
 
+EvalMaps = collections.namedtuple("EvalMaps", EvalStats._fields + ("maps", "map_steps"))
+EvalMaps.__doc__ = """Result of Engine.rollout_eval_maps: EvalStats' fields (stats / hist / spectra are None and their step lists empty
+where they were not asked for), then maps [B, C, 7, Ly, Lx] (planes: metrics.TIME_MAPS) and map_steps = (from, every), the rule
+of the steps the maps were taken over."""
+EvalMapsChunk = collections.namedtuple("EvalMapsChunk", EvalMaps._fields + ("z_last",))
+EvalMapsChunk.__doc__ = """Result of Engine.rollout_latent_eval_maps: EvalMaps' fields for the chunk, then z_last, the latent after
+the chunk's last step.  maps is written by the chunk that completes the horizon."""
+
+
+def normalize_map_steps(map_steps):
+    """The `map_steps` argument of the time maps -> (from, every): None is every step, (0, 1); slice(from, None, every) and a
+    (from, every) pair name the steps from, from + every, ... of the horizon (burn-in and thinning).  Anything else -- a stop,
+    a negative start, a step below 1, a list of steps -- is a ValueError.  Pure host code."""
+    def whole(v, what):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError("map_steps: %s must be an integer, got %r" % (what, v))
+        return int(v)
+    if map_steps is None:
+        return 0, 1
+    if isinstance(map_steps, slice):
+        if map_steps.stop is not None:
+            raise ValueError("map_steps: a slice must be slice(from, None, every): the maps run to the end of the horizon")
+        first = 0 if map_steps.start is None else whole(map_steps.start, "from")
+        every = 1 if map_steps.step is None else whole(map_steps.step, "every")
+    elif isinstance(map_steps, (tuple, list)) and len(map_steps) == 2:
+        first, every = whole(map_steps[0], "from"), whole(map_steps[1], "every")
+    else:
+        raise ValueError("map_steps must be None, slice(from, None, every) or a (from, every) pair, got %r" % (map_steps,))
+    if first < 0 or every < 1:
+        raise ValueError("map_steps: from must be >= 0 and every >= 1, got (%d, %d)" % (first, every))
+    return first, every
+
+
 def stats_spec(C, hist):
     """`lns_stats_spec` from hist = (nbins, lo, hi) with scalar or per-channel edges (denormalised units); None -> None."""
     if hist is None:
@@ -872,6 +905,103 @@ class Engine:
                 sarr, len(ssel), self._ptr(spectra), arr, len(sel), ctypes.byref(hs) if hs is not None else None,
                 stats.data_ptr(), self._ptr(counts)), "lns_rollout_latent_eval_stats")
         return EvalStatsChunk(frame, seq, frames, stats, counts, sel, spectra, ssel, z_last)
+
+    # -- streaming validation with time maps (include/lns.h "time maps") -------------------------------------------
+    def time_maps(self, y_hat, y, map_steps=None, **norm):
+        """Per-pixel time maps of stored fields (lns_op_time_maps): see metrics.time_maps.  The kernel body of
+        rollout_eval_maps."""
+        from . import metrics
+        return metrics.time_maps(y_hat, y, map_steps=map_steps, **norm)
+
+    def _maps_select(self, map_steps, stats_steps, hist, spectrum_steps, T, B, device):
+        """-> (lns_eval_select, what it points to (kept alive by the caller), EvalMaps' fields from `stats` on)"""
+        import torch
+        C = self.cfg.in_channels
+        first, every = map_steps
+        none = lambda s: s is not None and not isinstance(s, slice) and len(s) == 0
+        if none(stats_steps):
+            if hist is not None:
+                raise LnsError("hist needs stats_steps")
+            sel, arr, stats, hs, counts = [], None, None, None, None
+        else:
+            sel, arr, stats, hs, counts, _, _, _ = self._stats_select(stats_steps, (), hist, T, B, device)
+        ssel, sarr, spectra = ([], None, None) if none(spectrum_steps) else self._spectrum_select(spectrum_steps, T, B, device)
+        maps = torch.empty((B, C, _lib.LNS_TIME_MAPS, self.cfg.Ly, self.cfg.Lx), dtype=torch.float32, device=device)
+        q = _lib.LnsEvalSelect()
+        q.size = ctypes.sizeof(_lib.LnsEvalSelect)
+        q.n_spec, q.n_stats, q.map_from, q.map_every = len(ssel), len(sel), first, every
+        if ssel:
+            q.spectrum_steps_host, q.spectra_out = sarr, spectra.data_ptr()
+        if sel:
+            q.stats_steps_host, q.stats_out = arr, stats.data_ptr()
+            if hs is not None:
+                q.hspec, q.hist_out = ctypes.pointer(hs), counts.data_ptr()
+        q.maps_out = maps.data_ptr()
+        return q, (arr, sarr, hs), (stats, counts, sel, spectra, ssel, maps, (first, every))
+
+    def rollout_eval_maps(self, x, y, steps=None, param=None, keep_steps=(), map_steps=None, stats_steps=(), hist=None,
+                          spectrum_steps=(), **norm):
+        """rollout_eval with the seven per-pixel time maps metrics.TIME_MAPS -- time-mean of forecast and truth, their unbiased
+        temporal variances and covariance, the mean squared error and the largest absolute error -- over the steps `map_steps`
+        (None: every step; slice(from, None, every) or (from, every): burn-in and thinning), accumulated as the steps are decoded:
+        the [B,T,C,Ly,Lx] rollout is never stored.  `stats_steps` / `hist` and `spectrum_steps` (default: none) add
+        rollout_eval_stats' statistics and rollout_eval_spectrum's spectra in the same pass.  Returns EvalMaps: every field but
+        maps holds the bits of the existing calls, maps those of `time_maps(rollout(x, T), y, map_steps, ...)`.  The workspace is
+        rollout_eval's plus 52 bytes per (trajectory, channel, pixel)."""
+        import torch
+        ms = normalize_map_steps(map_steps)
+        x = self._dev(x)
+        if steps is not None and int(steps) < y.shape[1]:
+            y = y[:, :int(steps)]
+        y, B, T, _, spec, keep, n_keep, frames = self._eval_common(x, y, steps, 0, keep_steps, norm)
+        q, alive, tail = self._maps_select(ms, stats_steps, hist, spectrum_steps, T, B, x.device)
+        frame = torch.empty((B, T, self.cfg.in_channels), dtype=torch.float32, device=x.device)
+        seq = torch.empty((B, self.cfg.in_channels), dtype=torch.float32, device=x.device)
+        p = self._param(param, x)
+        with torch.cuda.device(x.device):
+            ws = self._sized_workspace("lns_rollout_eval_maps_workspace_bytes", B, x.device)
+            self._check(self._L.lns_rollout_eval_maps(
+                self._h, x.data_ptr(), self._ptr(p), y.data_ptr(), B, T, ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(),
+                keep, n_keep, self._ptr(frames), ws.data_ptr(), ws.numel(), self._stream(x), ctypes.byref(q)),
+                "lns_rollout_eval_maps")
+        del alive
+        return EvalMaps(frame, seq, frames, *tail)
+
+    def rollout_latent_eval_maps(self, z, y, steps=None, t0=0, param=None, keep_steps=(), map_steps=None, stats_steps=(),
+                                 hist=None, spectrum_steps=(), frame=None, seq=None, maps=None, **norm):
+        """rollout_latent_eval with time maps: `map_steps` names steps of the horizon (the same in every chunk); keep_steps,
+        stats_steps and spectrum_steps are relative to the chunk.  The chunks of one horizon must follow each other on the same
+        engine and batch, with nothing else run on it in between: the maps' state stays in the engine's workspace, and the chunk
+        that completes the horizon writes `maps` (pass the tensor along like frame / seq, or take it from the last chunk's
+        result; it is untouched until then).  Returns EvalMapsChunk."""
+        import torch
+        ms = normalize_map_steps(map_steps)
+        z = self._dev(z)
+        t0 = int(t0)
+        y, B, T, T_total, spec, keep, n_keep, frames = self._eval_common(z, y, steps, t0, keep_steps, norm)
+        q, alive, tail = self._maps_select(ms, stats_steps, hist, spectrum_steps, T, B, z.device)
+        C = self.cfg.in_channels
+        if frame is None:
+            frame = torch.empty((B, T_total, C), dtype=torch.float32, device=z.device)
+        if seq is None:
+            seq = torch.empty((B, C), dtype=torch.float32, device=z.device)
+        if maps is None:
+            maps = tail[5]
+        for t, shape in ((frame, (B, T_total, C)), (seq, (B, C)), (maps, (B, C, _lib.LNS_TIME_MAPS, self.cfg.Ly, self.cfg.Lx))):
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != z.device:
+                raise LnsError("preallocated result must be a contiguous fp32 tensor of shape %s on the input's device" % (shape,))
+        q.maps_out = maps.data_ptr()
+        tail = tail[:5] + (maps,) + tail[6:]
+        z_last = torch.empty_like(z)
+        p = self._param(param, z)
+        with torch.cuda.device(z.device):
+            ws = self._sized_workspace("lns_rollout_eval_maps_workspace_bytes", B, z.device)
+            self._check(self._L.lns_rollout_latent_eval_maps(
+                self._h, z.data_ptr(), self._ptr(p), y.data_ptr(), B, T, t0, T_total, ctypes.byref(spec), frame.data_ptr(),
+                seq.data_ptr(), keep, n_keep, self._ptr(frames), z_last.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(z),
+                ctypes.byref(q)), "lns_rollout_latent_eval_maps")
+        del alive
+        return EvalMapsChunk(frame, seq, frames, *tail, z_last)
 
     # -- training rollout of the propagator (include/lns.h "training rollout") ------------------------------------
     def _ptr_array(self, tensors):

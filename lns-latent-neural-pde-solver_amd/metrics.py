@@ -176,6 +176,54 @@ def correlation_time(corr, steps, threshold=0.8):
     return torch.where(below.any(dim=1), steps_t[first], torch.full_like(first, -1))
 
 
+TIME_MAPS = ("mean_P", "mean_Q", "var_P", "var_Q", "cov", "mse", "max_err")
+
+
+def time_maps(y_hat, y, map_steps=None, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
+    """Per-pixel time maps of stored fields (lns_op_time_maps; include/lns.h "time maps"): y_hat and y [B,T,C,H,W], normalised,
+    denormalised as in `relative_l2` into forecast P and truth Q.  Returns [B,C,7,H,W], the planes TIME_MAPS: the time-means
+    of P and Q, their unbiased temporal variances and covariance, the mean squared error and the largest absolute error, over
+    the steps `map_steps` (None: every step; slice(from, None, every) or (from, every)).  Sums are float64, shifted by the
+    truth's first frame.  The kernel body of Engine.rollout_eval_maps."""
+    from .engine import eval_spec, normalize_map_steps
+    first, every = normalize_map_steps(map_steps)
+    for t in (y_hat, y):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 5:
+            raise _lib.LnsError("time_maps takes fp32 HIP tensors [B,T,C,H,W] (no CPU fallback)")
+    if y.shape != y_hat.shape or y.device != y_hat.device:
+        raise _lib.LnsError("y must have y_hat's shape %s and device, got %s" % (tuple(y_hat.shape), tuple(y.shape)))
+    B, T, C, H, W = (int(v) for v in y_hat.shape)
+    y_hat, y = y_hat.contiguous(), y.contiguous()
+    spec = eval_spec(C, mean=mean, std=std, eps=eps, zero_wall_channels=zero_wall_channels, clamp_channels=clamp_channels,
+                     clamp=clamp)
+    L = _lib.lib()
+    need = ctypes.c_size_t(0)
+    if L.lns_time_maps_state_bytes(B, C, H, W, ctypes.byref(need)) != 0:
+        raise _lib.LnsError("lns_time_maps_state_bytes failed: %s" % L.lns_create_error().decode())
+    maps = torch.empty((B, C, _lib.LNS_TIME_MAPS, H, W), dtype=torch.float32, device=y_hat.device)
+    state = torch.empty(int(need.value), dtype=torch.uint8, device=y_hat.device)
+    with torch.cuda.device(y_hat.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(y_hat.device).cuda_stream)
+        rc = L.lns_op_time_maps(y_hat.data_ptr(), y.data_ptr(), B, T, C, H, W, ctypes.byref(spec), first, every, maps.data_ptr(),
+                                state.data_ptr(), state.numel(), stream)
+    if rc != 0:
+        raise _lib.LnsError("lns_op_time_maps failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    return maps
+
+
+def rmse_map(maps):
+    """maps [.., 7, H, W] (time_maps, EvalMaps.maps) -> the root mean squared error per pixel, [.., H, W]."""
+    return maps[..., TIME_MAPS.index("mse"), :, :].sqrt()
+
+
+def temporal_correlation(maps):
+    """maps [.., 7, H, W] -> cov / sqrt(var_P var_Q) per pixel, [.., H, W]; 0 where either variance is 0 (a pixel constant in
+    time, or maps over a single step)."""
+    vP, vQ, cov = (maps[..., TIME_MAPS.index(k), :, :] for k in ("var_P", "var_Q", "cov"))
+    den = vP.sqrt() * vQ.sqrt()
+    return torch.where(den == 0, torch.zeros_like(den), cov / den)
+
+
 def spread_skill_ratio(scores, members):
     """spread * sqrt((M + 1) / M) / rmse of an `engine.EnsembleScores` (Engine.rollout_latent_ensemble_eval,
     LatentDynamics.validate_ensemble) with M = `members`: near 1 for a calibrated ensemble, below it for an
