@@ -8,10 +8,9 @@
 // thread's terms in ascending order from 0, wave_sum, then (w0 + w1) + (w2 + w3).  Nothing is fused.
 #define LNS_FS_MAX_BINS 256
 
-struct FsDenorm {
-    float sd, mean, lo, hi;
-    bool walls, clampv;
+struct FsDenorm : ChannelNorm {
     int H, W;
+    __device__ __forceinline__ FsDenorm(const FieldStatsArgs& a, int c) : ChannelNorm(a.norm, c), H(a.H), W(a.W) {}
     // pixel i = r * W + cx of a normalised plane p
     __device__ __forceinline__ float at(const float* p, int i, int r, int cx) const {
         const bool zero = walls && (r == 0 || r == H - 1 || cx == 0 || cx == W - 1);
@@ -162,10 +161,7 @@ __device__ __forceinline__ void field_stats_plane(const float* f, const float* g
 __device__ __forceinline__ void field_stats_block(const FieldStatsArgs& a, const float* f, const float* g, long oplane, int c) {
     __shared__ float red[36];                                  // 5 x 4 wave sums, 4 x 4 wave extrema
     __shared__ int cnt[2 * (LNS_FS_MAX_BINS + 2)];
-    const bool pc = a.per_channel;
-    FsDenorm D;
-    D.sd = pc ? a.spec.std[c] : a.sd; D.mean = pc ? a.spec.mean[c] : a.mean; D.lo = a.spec.lo; D.hi = a.spec.hi;
-    D.walls = pc && (a.spec.flags[c] & 1); D.clampv = pc && (a.spec.flags[c] & 2); D.H = a.H; D.W = a.W;
+    const FsDenorm D(a, c);
     const int hc = a.hist ? c : 0;                             // (histograms: C <= 8, checked on the host)
     field_stats_plane(f, g, a.stats + oplane * LNS_FIELD_STATS_N, a.hist ? a.hist + oplane * 2 * (a.nbins + 2) : nullptr, D,
                       a.eps, a.nbins, a.hlo[hc], a.hhi[hc], a.hscale[hc], red, cnt);
@@ -191,7 +187,7 @@ __global__ __launch_bounds__(256) void field_stats_stored_kernel(FieldStatsArgs 
 
 static bool field_stats_args_ok(const FieldStatsArgs& a) {
     if (!a.frames || !a.y || !a.stats || a.B < 1 || a.C < 1 || a.H < 1 || a.W < 1 || (long)a.H * a.W > (1L << 30)) return false;
-    if (a.per_channel && a.C > LNS_METRIC_MAX_CH) return false;
+    if (a.norm.per_channel && a.C > LNS_METRIC_MAX_CH) return false;
     if (a.hist && (a.nbins < 1 || a.nbins > LNS_FS_MAX_BINS || a.C > LNS_METRIC_MAX_CH)) return false;
     return true;
 }

@@ -1833,6 +1833,28 @@ static void add_maps_region(const lns_engine* e, int B, WsLayout* L) {
     L->total = L->maps_off + L->maps_bytes;
 }
 
+// An ascending list of steps on the host -- the kept frames, the spectrum steps, the statistics steps of a call -- under
+// the name the refusals use, with the cursor of the one walk rollout_loop makes over it
+struct StepList {
+    const int* steps; int n; const char* name; int next = 0;
+    // strictly ascending, in [0, T); the refusal's text into *err
+    int check(int T, std::string* err) const {
+        for (int i = 0; i < n; ++i)
+            if (steps[i] < 0 || steps[i] >= T || (i > 0 && steps[i] <= steps[i - 1])) {
+                *err = fmt("%s must be ascending steps in [0, %d): entry %d is %d", name, T, i, steps[i]);
+                return LNS_EINVAL;
+            }
+        return LNS_OK;
+    }
+    // the entries of the decode group of steps t0g .. t0g + kk - 1 (kk <= 8; ascending: each entry lies in one group),
+    // relative to t0g, into sel; returns their number.  The first of them is entry `next` before the call.
+    int pick(int t0g, int kk, unsigned char* sel) {
+        int m = 0;
+        for (; next < n && steps[next] < t0g + kk; ++next) sel[m++] = (unsigned char)(steps[next] - t0g);
+        return m;
+    }
+};
+
 // One rollout call, as the entry points (lns_rollout, lns_rollout_latent, their _eval / _select forms and
 // lns_rollout_latent_ensemble) describe it
 struct RolloutCall {
@@ -1850,15 +1872,16 @@ struct RolloutCall {
     // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
     const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
     float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
-    // SINK_SCORED with spectra (lns_rollout_eval_spectrum): spectra_out [B][n_spec][C][3][S] of the steps spec_steps[0 .. n_spec) (host, ascending)
-    bool spectra = false; const int* spec_steps = nullptr; int n_spec = 0; float* spectra_out = nullptr;
-    // SINK_SCORED with field statistics (lns_rollout_eval_stats): stats_out [B][n_stats][C][12] and, with hspec, hist_out
-    // [B][n_stats][C][2][nbins + 2] of the steps stats_steps[0 .. n_stats) (host, ascending)
-    bool stats = false; const int* stats_steps = nullptr; int n_stats = 0; const lns_stats_spec* hspec = nullptr;
-    float* stats_out = nullptr; int32_t* hist_out = nullptr;
-    // SINK_SCORED with time maps (lns_rollout_eval_maps): maps_out [B][C][7][Ly][Lx] over the steps t >= map_from of the horizon
-    // with (t - map_from) % map_every == 0; sel_bad: the call's lns_eval_select was null or of the wrong size
-    bool maps = false, sel_bad = false; int map_from = 0, map_every = 1; float* maps_out = nullptr;
+    // SINK_SCORED: the optional selections and their outputs, as include/lns.h states them for lns_eval_select, and which of
+    // them the entry form asks for.  spectra: spectra_out [B][n_spec][C][3][S] of the steps spectrum_steps_host (the
+    // _spectrum form: always; the others: n_spec != 0); stats: stats_out / hist_out of the steps stats_steps_host (the _stats
+    // form: always; _maps: n_stats != 0); maps: maps_out over the steps t >= map_from of the horizon with
+    // (t - map_from) % map_every == 0 (the _maps form); sel_bad: that form's lns_eval_select was null or of the wrong size
+    lns_eval_select sel = {};
+    bool spectra = false, stats = false, maps = false, sel_bad = false;
+    StepList keep_list() const { return {keep, n_keep, "keep_steps"}; }
+    StepList spectrum_list() const { return {sel.spectrum_steps_host, sel.n_spec, "spectrum_steps"}; }
+    StepList stats_list() const { return {sel.stats_steps_host, sel.n_stats, "stats_steps"}; }
     float* latents_out = nullptr;                        // optional side outputs: all T latents [B][T][zper],
     float* z_last = nullptr;                             // the latent after the last step [B][zper]
     void* ws = nullptr; size_t ws_bytes = 0; void* stream = nullptr;
@@ -2195,37 +2218,36 @@ int lns_propagate(lns_engine* e, const float* z_in, const float* param, int B, i
     return run_single(e, PK_PROP, B, H, W, ext, ws, ws_bytes, stream);
 }
 
-// the per-channel part of an lns_eval_spec as the kernels take it (as lns_metric_rel_l2_ch fills it)
-static void channel_spec(const lns_eval_spec* spec, int C, MetricChannelSpec* out) {
+// The denormalisation of an lns_eval_spec for C channels as every scored kernel takes it: the scalar form and the
+// per-channel part (as lns_metric_rel_l2_ch fills it).  The one place the rule is written on the host; its refusal
+// (the per-channel form needs C <= 8) is rollout_refusal's and op_spec_refused's.
+static void score_norm(const lns_eval_spec* spec, int C, ScoreNorm* out) {
+    out->per_channel = spec->per_channel != 0; out->mean = spec->mean; out->sd = spec->std;
     for (int ch = 0; ch < LNS_METRIC_MAX_CH; ++ch) {
         const bool in = ch < C;
-        out->mean[ch] = in ? spec->mean_c[ch] : 0.0f;
-        out->std[ch] = in ? spec->std_c[ch] : 1.0f;
-        out->flags[ch] = in ? spec->flags_c[ch] : 0;
+        out->spec.mean[ch] = in ? spec->mean_c[ch] : 0.0f;
+        out->spec.std[ch] = in ? spec->std_c[ch] : 1.0f;
+        out->spec.flags[ch] = in ? spec->flags_c[ch] : 0;
     }
-    out->lo = spec->clamp_lo; out->hi = spec->clamp_hi;
+    out->spec.lo = spec->clamp_lo; out->spec.hi = spec->clamp_hi;
 }
 
 // the scoring kernel's arguments for a SINK_SCORED call; frames / kk / y_t / p_t are set per decoded group
 static void metric_args(const lns_engine* e, const RolloutCall& c, const WsLayout& L, MetricGroupArgs* mp) {
     MetricGroupArgs& m = *mp;
-    const lns_eval_spec* spec = c.spec;
     m.frames = nullptr; m.y = c.y_true; m.part = reinterpret_cast<float*>(static_cast<char*>(c.ws) + L.part_off);
     m.B = c.B; m.C = e->cfg.in_channels; m.H = e->cfg.Ly; m.W = e->cfg.Lx; m.kk = 0;
     m.y_T = c.T_total; m.y_t = 0; m.p_T = c.T_total; m.p_t = 0;
-    m.per_channel = spec->per_channel != 0;
-    m.mean = spec->mean; m.sd = spec->std;
-    channel_spec(spec, m.C, &m.spec);
+    score_norm(c.spec, m.C, &m.norm);
 }
 
 // the spectrum kernel's arguments for a SINK_SCORED call with spectra; frames / n / sel / y_t / o_t are set per decoded group
 static void spectrum_args(const lns_engine* e, const RolloutCall& c, SpectrumArgs* sp) {
     SpectrumArgs& s = *sp;
-    s.frames = nullptr; s.y = c.y_true; s.out = c.spectra_out;
+    s.frames = nullptr; s.y = c.y_true; s.out = c.sel.spectra_out;
     s.B = c.B; s.C = e->cfg.in_channels; s.H = e->cfg.Ly; s.W = e->cfg.Lx; s.S = lns_spectrum::bins(s.H, s.W); s.K = 3;
-    s.n = 0; s.y_T = c.T_total; s.y_t = 0; s.o_T = c.n_spec; s.o_t = 0;
-    s.per_channel = c.spec->per_channel != 0; s.mean = c.spec->mean; s.sd = c.spec->std;
-    channel_spec(c.spec, s.C, &s.spec);
+    s.n = 0; s.y_T = c.T_total; s.y_t = 0; s.o_T = c.sel.n_spec; s.o_t = 0;
+    score_norm(c.spec, s.C, &s.norm);
     memset(s.sel, 0, sizeof s.sel);
 }
 
@@ -2256,24 +2278,22 @@ static const char* stats_hist_args(const lns_stats_spec* hs, const int32_t* hist
 static void field_stats_args(const lns_engine* e, const RolloutCall& c, FieldStatsArgs* fp) {
     FieldStatsArgs& f = *fp;
     memset(&f, 0, sizeof f);
-    f.y = c.y_true; f.stats = c.stats_out;
+    f.y = c.y_true; f.stats = c.sel.stats_out;
     f.B = c.B; f.C = e->cfg.in_channels; f.H = e->cfg.Ly; f.W = e->cfg.Lx;
-    f.y_T = c.T_total; f.o_T = c.n_stats;
-    f.per_channel = c.spec->per_channel != 0; f.mean = c.spec->mean; f.sd = c.spec->std; f.eps = c.spec->eps;
-    channel_spec(c.spec, f.C, &f.spec);
-    stats_hist_args(c.hspec, c.hist_out, f.C, &f);   // (accepted by rollout_refusal)
+    f.y_T = c.T_total; f.o_T = c.sel.n_stats; f.eps = c.spec->eps;
+    score_norm(c.spec, f.C, &f.norm);
+    stats_hist_args(c.sel.hspec, c.sel.hist_out, f.C, &f);   // (accepted by rollout_refusal)
 }
 
 // the accumulation kernel's arguments for a SINK_SCORED call with time maps; frames / n / sel / y_t are set per decoded group
 static void time_maps_args(const lns_engine* e, const RolloutCall& c, const WsLayout& L, TimeMapsArgs* tp) {
     TimeMapsArgs& t = *tp;
     memset(&t, 0, sizeof t);
-    t.y = c.y_true; t.state = static_cast<char*>(c.ws) + L.maps_off; t.maps = c.maps_out;
+    t.y = c.y_true; t.state = static_cast<char*>(c.ws) + L.maps_off; t.maps = c.sel.maps_out;
     t.B = c.B; t.C = e->cfg.in_channels; t.H = e->cfg.Ly; t.W = e->cfg.Lx;
-    t.y_T = c.T_total; t.first = c.map_from; t.every = c.map_every;
-    t.count = (c.T_total - 1 - c.map_from) / c.map_every + 1;
-    t.per_channel = c.spec->per_channel != 0; t.mean = c.spec->mean; t.sd = c.spec->std;
-    channel_spec(c.spec, t.C, &t.spec);
+    t.y_T = c.T_total; t.first = c.sel.map_from; t.every = c.sel.map_every;
+    t.count = (c.T_total - 1 - c.sel.map_from) / c.sel.map_every + 1;
+    score_norm(c.spec, t.C, &t.norm);
 }
 
 // the same for the scoring kernel of a scored SINK_ENSEMBLE call; frames / kk / y_t are set per decoded group
@@ -2281,9 +2301,7 @@ static void score_args(const lns_engine* e, const RolloutCall& c, EnsembleScoreA
     EnsembleScoreArgs& s = *sp;
     s.frames = nullptr; s.y = c.y_true; s.scores = c.scores_out; s.rank = c.rank_out; s.pixel = nullptr;
     s.B = c.traj; s.M = c.M; s.C = e->cfg.in_channels; s.H = e->cfg.Ly; s.W = e->cfg.Lx; s.kk = 0; s.y_T = c.n_keep; s.y_t = 0;
-    s.per_channel = c.spec->per_channel != 0;
-    s.mean = c.spec->mean; s.sd = c.spec->std;
-    channel_spec(c.spec, s.C, &s.spec);
+    score_norm(c.spec, s.C, &s.norm);
 }
 
 // the autoregressive loop of every rollout call: zcur -> T x (propagate ; what the sink does)   (train_stage2_ns2d.py:147-156)
@@ -2378,7 +2396,8 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
         npp ^= 1;
         return chain_step(t, znext);
     };
-    int g = 0, gi = 0, ki = 0, si = 0, fi = 0, t = 0; // ki / si / fi: next entry of c.keep / c.spec_steps / c.stats_steps (SINK_SCORED); t: next step of the chain
+    int g = 0, gi = 0, t = 0;                        // t: next step of the chain
+    StepList frames_kept = c.keep_list(), spec_steps = c.spectrum_list(), stats_steps = c.stats_list();   // SINK_SCORED: walked group by group
     for (int i0 = 0; i0 < n_dec;) {                  // i0: index in `out` of the group's first step
         const int kk = std::min(kdec, n_dec - i0);
         const int t0g = dec_step(i0);                // the group's first step
@@ -2407,18 +2426,18 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
         if (scored) {                                // (every step is decoded: t0g == i0)
             m.frames = fb; m.kk = kk; m.y_t = c.t0 + t0g; m.p_t = c.t0 + t0g;
             HIPCHK(e, launch_metric_group(m, dstream[d]));
-            for (; ki < c.n_keep && c.keep[ki] < t0g + kk; ++ki)     // ascending: each kept step lies in one group
-                HIPCHK(e, hipMemcpy2DAsync(c.frames_out + (long)ki * xper, (size_t)c.n_keep * xper * 4,
-                                           fb + (long)(c.keep[ki] - t0g) * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
+            unsigned char kj[8];
+            const int ki = frames_kept.next, nk = frames_kept.pick(t0g, kk, kj);
+            for (int i = 0; i < nk; ++i)
+                HIPCHK(e, hipMemcpy2DAsync(c.frames_out + (long)(ki + i) * xper, (size_t)c.n_keep * xper * 4,
+                                           fb + (long)kj[i] * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
                                            hipMemcpyDeviceToDevice, dstream[d]));
-            if (c.spectra) {                         // the group's selected steps (kk <= 8), one launch; none: no launch
-                sx.frames = fb; sx.y_t = c.t0 + t0g; sx.o_t = si; sx.n = 0;
-                for (; si < c.n_spec && c.spec_steps[si] < t0g + kk; ++si) sx.sel[sx.n++] = (unsigned char)(c.spec_steps[si] - t0g);
+            if (c.spectra) {                         // the group's selected steps, one launch; none: no launch
+                sx.frames = fb; sx.y_t = c.t0 + t0g; sx.o_t = spec_steps.next; sx.n = spec_steps.pick(t0g, kk, sx.sel);
                 if (sx.n) HIPCHK(e, launch_spectrum_group(sx, dstream[d]));
             }
             if (c.stats) {                           // likewise, beside the spectrum launch
-                fs.frames = fb; fs.y_t = c.t0 + t0g; fs.o_t = fi; fs.n = 0;
-                for (; fi < c.n_stats && c.stats_steps[fi] < t0g + kk; ++fi) fs.sel[fs.n++] = (unsigned char)(c.stats_steps[fi] - t0g);
+                fs.frames = fb; fs.y_t = c.t0 + t0g; fs.o_t = stats_steps.next; fs.n = stats_steps.pick(t0g, kk, fs.sel);
                 if (fs.n) HIPCHK(e, launch_field_stats_group(fs, dstream[d]));
             }
             if (c.maps) {
@@ -2429,7 +2448,7 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
                 tm.frames = fb; tm.y_t = c.t0 + t0g; tm.n = 0;
                 for (int j = 0; j < kk; ++j) {
                     const int ta = c.t0 + t0g + j;   // the step of the horizon
-                    if (ta >= c.map_from && (ta - c.map_from) % c.map_every == 0) tm.sel[tm.n++] = (unsigned char)j;
+                    if (ta >= c.sel.map_from && (ta - c.sel.map_from) % c.sel.map_every == 0) tm.sel[tm.n++] = (unsigned char)j;
                 }
                 if (tm.n) {
                     if (overlap && maps_d >= 0 && maps_d != d) HIPCHK(e, hipStreamWaitEvent(dstream[d], ev_maps[maps_d], 0));
@@ -2470,16 +2489,6 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     return LNS_OK;
 }
 
-// kept steps (SINK_SCORED: frames to copy out; SINK_KEPT: steps to decode): strictly ascending, in [0, T)
-static int check_keep_steps(lns_engine* e, const int* keep, int n_keep, int T) {
-    for (int i = 0; i < n_keep; ++i)
-        if (keep[i] < 0 || keep[i] >= T || (i > 0 && keep[i] <= keep[i - 1])) {
-            e->err = fmt("keep_steps must be ascending steps in [0, %d): entry %d is %d", T, i, keep[i]);
-            return LNS_EINVAL;
-        }
-    return LNS_OK;
-}
-
 // every refusal of a rollout call that needs no plan: nothing here touches the device.  The order is part of the
 // interface (which of two failing checks answers): arguments, batch, eval_max_steps, the model, param.
 static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
@@ -2513,40 +2522,32 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
     if ((scored || kept) && c.n_keep > 0) {
         if (!c.keep) return einval(e, scored ? "keep_steps is null but n_keep > 0" : "keep_steps is null");
         if (scored && !c.frames_out) return einval(e, "frames_out is null but n_keep > 0");
-        if (int krc = check_keep_steps(e, c.keep, c.n_keep, c.T)) return krc;
+        if (int krc = c.keep_list().check(c.T, &e->err)) return krc;
     }
     if (scored && c.spectra) {
-        if (!c.spectra_out) return einval(e, "spectra_out is null");
-        if (c.n_spec < 1) return einval(e, "n_spec must be at least 1");
-        if (!c.spec_steps) return einval(e, "spectrum_steps is null");
-        for (int i = 0; i < c.n_spec; ++i)
-            if (c.spec_steps[i] < 0 || c.spec_steps[i] >= c.T || (i > 0 && c.spec_steps[i] <= c.spec_steps[i - 1])) {
-                e->err = fmt("spectrum_steps must be ascending steps in [0, %d): entry %d is %d", c.T, i, c.spec_steps[i]);
-                return LNS_EINVAL;
-            }
+        if (!c.sel.spectra_out) return einval(e, "spectra_out is null");
+        if (c.sel.n_spec < 1) return einval(e, "n_spec must be at least 1");
+        if (!c.sel.spectrum_steps_host) return einval(e, "spectrum_steps is null");
+        if (int src = c.spectrum_list().check(c.T, &e->err)) return src;
         if (!lns_spectrum::supported(e->cfg.Ly, e->cfg.Lx)) {
             e->err = fmt("energy spectrum: a %d x %d plane is not supported (H, W <= 192 and H * W <= 18432)", e->cfg.Ly, e->cfg.Lx);
             return LNS_EINVAL;
         }
     }
     if (scored && c.stats) {
-        if (!c.stats_out) return einval(e, "stats_out is null");
-        if (c.n_stats < 1) return einval(e, "n_stats must be at least 1");
-        if (!c.stats_steps) return einval(e, "stats_steps is null");
-        for (int i = 0; i < c.n_stats; ++i)
-            if (c.stats_steps[i] < 0 || c.stats_steps[i] >= c.T || (i > 0 && c.stats_steps[i] <= c.stats_steps[i - 1])) {
-                e->err = fmt("stats_steps must be ascending steps in [0, %d): entry %d is %d", c.T, i, c.stats_steps[i]);
-                return LNS_EINVAL;
-            }
+        if (!c.sel.stats_out) return einval(e, "stats_out is null");
+        if (c.sel.n_stats < 1) return einval(e, "n_stats must be at least 1");
+        if (!c.sel.stats_steps_host) return einval(e, "stats_steps is null");
+        if (int src = c.stats_list().check(c.T, &e->err)) return src;
         FieldStatsArgs probe;
-        if (const char* why = stats_hist_args(c.hspec, c.hist_out, e->cfg.in_channels, &probe)) return einval(e, why);
+        if (const char* why = stats_hist_args(c.sel.hspec, c.sel.hist_out, e->cfg.in_channels, &probe)) return einval(e, why);
     }
     if (scored && c.maps) {
         if (c.sel_bad) return einval(e, "sel is null or its size field is not sizeof(lns_eval_select)");
-        if (!c.maps_out) return einval(e, "maps_out is null");
-        if (c.map_every < 1) return einval(e, "map_every must be at least 1");
-        if (c.map_from < 0 || c.map_from >= c.T_total) {
-            e->err = fmt("map_from must be a step in [0, %d), got %d", c.T_total, c.map_from);
+        if (!c.sel.maps_out) return einval(e, "maps_out is null");
+        if (c.sel.map_every < 1) return einval(e, "map_every must be at least 1");
+        if (c.sel.map_from < 0 || c.sel.map_from >= c.T_total) {
+            e->err = fmt("map_from must be a step in [0, %d), got %d", c.T_total, c.sel.map_from);
             return LNS_EINVAL;
         }
     }
@@ -2607,11 +2608,30 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     return r.finish();
 }
 
-static void score_into(RolloutCall& c, const float* y_true, int t0, int T_total, const lns_eval_spec* spec, float* frame_out,
-                       float* seq_out, const int* keep, int n_keep, float* frames_out) {
+// The one body of the eight scored entry points (lns_rollout_eval, lns_rollout_latent_eval and their _spectrum / _stats /
+// _maps forms): the union of their argument lists.  From x: encode, t0 = 0, T_total = T, no z_last.  The selections come
+// loose (the _spectrum and _stats forms; all null / 0 for the plain one) or, for SCORED_MAPS, in `sel`.
+enum ScoredForm { SCORED_PLAIN, SCORED_SPECTRUM, SCORED_STATS, SCORED_MAPS };
+static int scored_call(lns_engine* e, ScoredForm form, const float* start, bool encode, const float* param, const float* y_true,
+                       int B, int T, int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                       const int* keep, int n_keep, float* frames_out, float* z_last, void* ws, size_t ws_bytes, void* stream,
+                       const int* spectrum_steps, int n_spec, float* spectra_out, const int* stats_steps, int n_stats,
+                       const lns_stats_spec* hspec, float* stats_out, int32_t* hist_out, const lns_eval_select* sel) {
+    RolloutCall c(start, encode, param, B, T, ws, ws_bytes, stream);
     c.sink = SINK_SCORED;
     c.y_true = y_true; c.t0 = t0; c.T_total = T_total; c.spec = spec; c.frame_out = frame_out; c.seq_out = seq_out;
-    c.keep = keep; c.n_keep = n_keep; c.frames_out = frames_out;
+    c.keep = keep; c.n_keep = n_keep; c.frames_out = frames_out; c.z_last = z_last;
+    c.maps = form == SCORED_MAPS;
+    c.sel_bad = c.maps && (!sel || sel->size != sizeof(lns_eval_select));   // (the two selections then count as absent)
+    if (c.maps && !c.sel_bad) c.sel = *sel;
+    if (!c.maps) {
+        c.sel.spectrum_steps_host = spectrum_steps; c.sel.n_spec = n_spec; c.sel.spectra_out = spectra_out;
+        c.sel.stats_steps_host = stats_steps; c.sel.n_stats = n_stats; c.sel.hspec = hspec; c.sel.stats_out = stats_out;
+        c.sel.hist_out = hist_out;
+    }
+    c.spectra = form == SCORED_SPECTRUM || c.sel.n_spec != 0;
+    c.stats = form == SCORED_STATS || c.sel.n_stats != 0;
+    return rollout_call(e, c);
 }
 
 int lns_rollout(lns_engine* e, const float* x, const float* param, int B, int T, int to_x, float* out,
@@ -2632,19 +2652,17 @@ int lns_rollout_latent(lns_engine* e, const float* z_in, const float* param, int
 int lns_rollout_eval(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
                      const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
                      float* frames_out, void* ws, size_t ws_bytes, void* stream) {
-    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
-    score_into(c, y_true, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
-    return rollout_call(e, c);
+    return scored_call(e, SCORED_PLAIN, x, true, param, y_true, B, T, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep,
+                       frames_out, nullptr, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int lns_rollout_latent_eval(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
                             int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
                             const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* ws,
                             size_t ws_bytes, void* stream) {
-    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
-    score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
-    c.z_last = z_last;
-    return rollout_call(e, c);
+    return scored_call(e, SCORED_PLAIN, z_in, false, param, y_true, B, T, t0, T_total, spec, frame_out, seq_out, keep_steps_host,
+                       n_keep, frames_out, z_last, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                       nullptr);
 }
 
 // ---- streaming validation with energy spectra (include/lns.h) ----------------------------------------------------
@@ -2652,10 +2670,9 @@ int lns_rollout_eval_spectrum(lns_engine* e, const float* x, const float* param,
                               const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
                               float* frames_out, void* ws, size_t ws_bytes, void* stream, const int* spectrum_steps_host,
                               int n_spec, float* spectra_out) {
-    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
-    score_into(c, y_true, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
-    c.spectra = true; c.spec_steps = spectrum_steps_host; c.n_spec = n_spec; c.spectra_out = spectra_out;
-    return rollout_call(e, c);
+    return scored_call(e, SCORED_SPECTRUM, x, true, param, y_true, B, T, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep,
+                       frames_out, nullptr, ws, ws_bytes, stream, spectrum_steps_host, n_spec, spectra_out, nullptr, 0, nullptr,
+                       nullptr, nullptr, nullptr);
 }
 
 int lns_rollout_latent_eval_spectrum(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
@@ -2663,30 +2680,20 @@ int lns_rollout_latent_eval_spectrum(lns_engine* e, const float* z_in, const flo
                                      const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* ws,
                                      size_t ws_bytes, void* stream, const int* spectrum_steps_host, int n_spec,
                                      float* spectra_out) {
-    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
-    score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
-    c.z_last = z_last;
-    c.spectra = true; c.spec_steps = spectrum_steps_host; c.n_spec = n_spec; c.spectra_out = spectra_out;
-    return rollout_call(e, c);
+    return scored_call(e, SCORED_SPECTRUM, z_in, false, param, y_true, B, T, t0, T_total, spec, frame_out, seq_out,
+                       keep_steps_host, n_keep, frames_out, z_last, ws, ws_bytes, stream, spectrum_steps_host, n_spec, spectra_out,
+                       nullptr, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 // ---- streaming validation with field statistics (include/lns.h) ---------------------------------------------------
-static void stats_into(RolloutCall& c, const int* spectrum_steps_host, int n_spec, float* spectra_out, const int* stats_steps_host,
-                       int n_stats, const lns_stats_spec* hspec, float* stats_out, int32_t* hist_out) {
-    c.spectra = n_spec != 0; c.spec_steps = spectrum_steps_host; c.n_spec = n_spec; c.spectra_out = spectra_out;
-    c.stats = true; c.stats_steps = stats_steps_host; c.n_stats = n_stats; c.hspec = hspec; c.stats_out = stats_out;
-    c.hist_out = hist_out;
-}
-
 int lns_rollout_eval_stats(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
                            const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
                            float* frames_out, void* ws, size_t ws_bytes, void* stream, const int* spectrum_steps_host, int n_spec,
                            float* spectra_out, const int* stats_steps_host, int n_stats, const lns_stats_spec* hspec,
                            float* stats_out, int32_t* hist_out) {
-    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
-    score_into(c, y_true, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
-    stats_into(c, spectrum_steps_host, n_spec, spectra_out, stats_steps_host, n_stats, hspec, stats_out, hist_out);
-    return rollout_call(e, c);
+    return scored_call(e, SCORED_STATS, x, true, param, y_true, B, T, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep,
+                       frames_out, nullptr, ws, ws_bytes, stream, spectrum_steps_host, n_spec, spectra_out, stats_steps_host,
+                       n_stats, hspec, stats_out, hist_out, nullptr);
 }
 
 int lns_rollout_latent_eval_stats(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
@@ -2695,24 +2702,12 @@ int lns_rollout_latent_eval_stats(lns_engine* e, const float* z_in, const float*
                                   size_t ws_bytes, void* stream, const int* spectrum_steps_host, int n_spec, float* spectra_out,
                                   const int* stats_steps_host, int n_stats, const lns_stats_spec* hspec, float* stats_out,
                                   int32_t* hist_out) {
-    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
-    score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
-    c.z_last = z_last;
-    stats_into(c, spectrum_steps_host, n_spec, spectra_out, stats_steps_host, n_stats, hspec, stats_out, hist_out);
-    return rollout_call(e, c);
+    return scored_call(e, SCORED_STATS, z_in, false, param, y_true, B, T, t0, T_total, spec, frame_out, seq_out, keep_steps_host,
+                       n_keep, frames_out, z_last, ws, ws_bytes, stream, spectrum_steps_host, n_spec, spectra_out,
+                       stats_steps_host, n_stats, hspec, stats_out, hist_out, nullptr);
 }
 
 // ---- streaming validation with time maps (include/lns.h) ----------------------------------------------------------
-static void maps_into(RolloutCall& c, const lns_eval_select* sel) {
-    c.maps = true;
-    c.sel_bad = !sel || sel->size != sizeof(lns_eval_select);
-    if (c.sel_bad) return;
-    c.spectra = sel->n_spec != 0; c.spec_steps = sel->spectrum_steps_host; c.n_spec = sel->n_spec; c.spectra_out = sel->spectra_out;
-    c.stats = sel->n_stats != 0; c.stats_steps = sel->stats_steps_host; c.n_stats = sel->n_stats; c.hspec = sel->hspec;
-    c.stats_out = sel->stats_out; c.hist_out = sel->hist_out;
-    c.map_from = sel->map_from; c.map_every = sel->map_every; c.maps_out = sel->maps_out;
-}
-
 int lns_rollout_eval_maps_workspace_bytes(lns_engine* e, int B, size_t* bytes) {
     size_t base = 0;
     if (int rc = workspace_bytes(e, B, SINK_SCORED, &base)) return rc;
@@ -2726,21 +2721,17 @@ int lns_rollout_eval_maps_workspace_bytes(lns_engine* e, int B, size_t* bytes) {
 int lns_rollout_eval_maps(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
                           const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
                           float* frames_out, void* ws, size_t ws_bytes, void* stream, const lns_eval_select* sel) {
-    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
-    score_into(c, y_true, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
-    maps_into(c, sel);
-    return rollout_call(e, c);
+    return scored_call(e, SCORED_MAPS, x, true, param, y_true, B, T, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep,
+                       frames_out, nullptr, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, sel);
 }
 
 int lns_rollout_latent_eval_maps(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
                                  int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
                                  const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* ws,
                                  size_t ws_bytes, void* stream, const lns_eval_select* sel) {
-    RolloutCall c(z_in, false, param, B, T, ws, ws_bytes, stream);
-    score_into(c, y_true, t0, T_total, spec, frame_out, seq_out, keep_steps_host, n_keep, frames_out);
-    c.z_last = z_last;
-    maps_into(c, sel);
-    return rollout_call(e, c);
+    return scored_call(e, SCORED_MAPS, z_in, false, param, y_true, B, T, t0, T_total, spec, frame_out, seq_out, keep_steps_host,
+                       n_keep, frames_out, z_last, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                       sel);
 }
 
 // ---- selected-step rollout (include/lns.h) ----------------------------------------------------------------------
@@ -3147,26 +3138,32 @@ int lns_op_ensemble_stats(const float* frames, int B, int M, int64_t per, float*
     return LNS_OK;
 }
 
+// The refusals of an lns_op_*'s spec, under the op's name: null or of the wrong size, or (C given) the per-channel form for
+// more than 8 channels.  An op asks twice, where its other checks stand between the two (the order is interface).
+static bool op_spec_refused(const char* op, const lns_eval_spec* spec, int C = 0) {
+    if (!spec || spec->size != sizeof(lns_eval_spec)) g_create_error = fmt("%s: spec is null or its size field is not sizeof(lns_eval_spec)", op);
+    else if (spec->per_channel && C > LNS_METRIC_MAX_CH) g_create_error = fmt("%s: the per-channel form needs C <= 8", op);
+    else return false;
+    return true;
+}
+
 // ensemble_score_kernel and its finish kernel on stored member fields: frames [n][B][M][C][H][W], y [B][n][C][H][W]
 int lns_op_ensemble_score(const float* frames, const float* y, int n, int B, int M, int C, int H, int W, const lns_eval_spec* spec,
                           float* scores_out, float* seq_out, int32_t* rank_out, float* pixel_out, void* stream) {
     if (!frames || !y || !scores_out) { g_create_error = "ensemble_score: frames / y / scores_out is null"; return LNS_EINVAL; }
-    if (!spec || spec->size != sizeof(lns_eval_spec)) {
-        g_create_error = "ensemble_score: spec is null or its size field is not sizeof(lns_eval_spec)"; return LNS_EINVAL;
-    }
+    if (op_spec_refused("ensemble_score", spec)) return LNS_EINVAL;
     if (M < 2 || M > LNS_SCORE_MAX_MEMBERS) { g_create_error = "ensemble_score: M in 2 .. 128"; return LNS_EINVAL; }
     if (n < 1 || B < 1 || B > LNS_MAX_BATCH || C < 1 || H < 1 || W < 1 || (int64_t)H * W > (1 << 30) ||
         (int64_t)n * B * C > 0x7fffffffLL) {
         g_create_error = "ensemble_score: n >= 1, B in 1..65535, C, H, W >= 1, H * W <= 2^30, n * B * C < 2^31"; return LNS_EINVAL;
     }
-    if (spec->per_channel && C > LNS_METRIC_MAX_CH) { g_create_error = "ensemble_score: the per-channel form needs C <= 8"; return LNS_EINVAL; }
+    if (op_spec_refused("ensemble_score", spec, C)) return LNS_EINVAL;
     OPCHK(init_kernels());
     hipStream_t s = static_cast<hipStream_t>(stream);
     EnsembleScoreArgs a;
     a.frames = frames; a.y = y; a.scores = scores_out; a.rank = rank_out; a.pixel = pixel_out;
     a.B = B; a.M = M; a.C = C; a.H = H; a.W = W; a.kk = n; a.y_T = n; a.y_t = 0;
-    a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std;
-    channel_spec(spec, C, &a.spec);
+    score_norm(spec, C, &a.norm);
     OPCHK(launch_ensemble_score(a, s));
     OPCHK(launch_ensemble_score_finish(scores_out, B, n, C, H * W, spec->eps, seq_out, s));
     OPCHK(hipStreamSynchronize(s));
@@ -3182,22 +3179,19 @@ int lns_spectrum_bins(int H, int W) {
 int lns_op_energy_spectrum(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
                            float* out, void* stream) {
     if (!yhat || !out) { g_create_error = "energy_spectrum: yhat / out is null"; return LNS_EINVAL; }
-    if (!spec || spec->size != sizeof(lns_eval_spec)) {
-        g_create_error = "energy_spectrum: spec is null or its size field is not sizeof(lns_eval_spec)"; return LNS_EINVAL;
-    }
+    if (op_spec_refused("energy_spectrum", spec)) return LNS_EINVAL;
     if (B < 1 || T < 1 || C < 1 || (int64_t)B * T * C > 0x7fffffffLL) {
         g_create_error = "energy_spectrum: B, T, C >= 1 and B * T * C < 2^31"; return LNS_EINVAL;
     }
     if (!lns_spectrum::supported(H, W)) { g_create_error = "energy_spectrum: the plane needs 1 <= H, W <= 192 and H * W <= 18432"; return LNS_EINVAL; }
-    if (spec->per_channel && C > LNS_METRIC_MAX_CH) { g_create_error = "energy_spectrum: the per-channel form needs C <= 8"; return LNS_EINVAL; }
+    if (op_spec_refused("energy_spectrum", spec, C)) return LNS_EINVAL;
     OPCHK(init_kernels());
     hipStream_t s = static_cast<hipStream_t>(stream);
     SpectrumArgs a;
     memset(&a, 0, sizeof a);
     a.frames = yhat; a.y = y; a.out = out;
     a.B = B; a.C = C; a.H = H; a.W = W; a.S = lns_spectrum::bins(H, W); a.K = y ? 3 : 1; a.n = T;
-    a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std;
-    channel_spec(spec, C, &a.spec);
+    score_norm(spec, C, &a.norm);
     OPCHK(launch_spectrum_stored(a, s));
     OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
@@ -3209,13 +3203,11 @@ static_assert(LNS_FIELD_STATS_N == LNS_FIELD_STATS, "the kernels' and the header
 int lns_op_field_stats(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
                        const lns_stats_spec* hspec, float* stats_out, int32_t* hist_out, void* stream) {
     if (!yhat || !y || !stats_out) { g_create_error = "field_stats: yhat / y / stats_out is null"; return LNS_EINVAL; }
-    if (!spec || spec->size != sizeof(lns_eval_spec)) {
-        g_create_error = "field_stats: spec is null or its size field is not sizeof(lns_eval_spec)"; return LNS_EINVAL;
-    }
+    if (op_spec_refused("field_stats", spec)) return LNS_EINVAL;
     if (B < 1 || T < 1 || C < 1 || H < 1 || W < 1 || (int64_t)H * W > (1LL << 30) || (int64_t)B * T * C > 0x7fffffffLL) {
         g_create_error = "field_stats: B, T, C, H, W >= 1, H * W <= 2^30 and B * T * C < 2^31"; return LNS_EINVAL;
     }
-    if (spec->per_channel && C > LNS_METRIC_MAX_CH) { g_create_error = "field_stats: the per-channel form needs C <= 8"; return LNS_EINVAL; }
+    if (op_spec_refused("field_stats", spec, C)) return LNS_EINVAL;
     FieldStatsArgs a;
     memset(&a, 0, sizeof a);
     if (const char* why = stats_hist_args(hspec, hist_out, C, &a)) { g_create_error = std::string("field_stats: ") + why; return LNS_EINVAL; }
@@ -3223,8 +3215,8 @@ int lns_op_field_stats(const float* yhat, const float* y, int B, int T, int C, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     a.frames = yhat; a.y = y; a.stats = stats_out;
     a.B = B; a.C = C; a.H = H; a.W = W; a.n = T;
-    a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std; a.eps = spec->eps;
-    channel_spec(spec, C, &a.spec);
+    a.eps = spec->eps;
+    score_norm(spec, C, &a.norm);
     OPCHK(launch_field_stats_stored(a, s));
     OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
@@ -3244,13 +3236,11 @@ int lns_time_maps_state_bytes(int B, int C, int H, int W, size_t* bytes) {
 int lns_op_time_maps(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec, int map_from,
                      int map_every, float* maps_out, void* state, size_t state_bytes, void* stream) {
     if (!yhat || !y || !maps_out) { g_create_error = "time_maps: yhat / y / maps_out is null"; return LNS_EINVAL; }
-    if (!spec || spec->size != sizeof(lns_eval_spec)) {
-        g_create_error = "time_maps: spec is null or its size field is not sizeof(lns_eval_spec)"; return LNS_EINVAL;
-    }
+    if (op_spec_refused("time_maps", spec)) return LNS_EINVAL;
     if (T < 1 || B > LNS_MAX_BATCH) { g_create_error = "time_maps: T >= 1 and B <= 65535"; return LNS_EINVAL; }
     size_t need = 0;
     if (int rc = lns_time_maps_state_bytes(B, C, H, W, &need)) return rc;
-    if (spec->per_channel && C > LNS_METRIC_MAX_CH) { g_create_error = "time_maps: the per-channel form needs C <= 8"; return LNS_EINVAL; }
+    if (op_spec_refused("time_maps", spec, C)) return LNS_EINVAL;
     if (map_every < 1) { g_create_error = "time_maps: map_every must be at least 1"; return LNS_EINVAL; }
     if (map_from < 0 || map_from >= T) { g_create_error = fmt("time_maps: map_from must be a step in [0, %d), got %d", T, map_from); return LNS_EINVAL; }
     if (!state || (reinterpret_cast<uintptr_t>(state) & 7)) { g_create_error = "time_maps: state is null or not 8-byte aligned"; return LNS_EINVAL; }
@@ -3262,8 +3252,7 @@ int lns_op_time_maps(const float* yhat, const float* y, int B, int T, int C, int
     a.frames = yhat; a.y = y; a.state = state; a.maps = maps_out;
     a.B = B; a.C = C; a.H = H; a.W = W; a.y_T = T; a.first = map_from; a.every = map_every;
     a.n = a.count = (T - 1 - map_from) / map_every + 1;
-    a.per_channel = spec->per_channel != 0; a.mean = spec->mean; a.sd = spec->std;
-    channel_spec(spec, C, &a.spec);
+    score_norm(spec, C, &a.norm);
     OPCHK(hipMemsetAsync(state, 0, (size_t)B * C * H * W * LNS_TIME_MAPS_STATE_PER_PIXEL, s));
     OPCHK(launch_time_maps_stored(a, s));
     OPCHK(launch_time_maps_finish(a, s));

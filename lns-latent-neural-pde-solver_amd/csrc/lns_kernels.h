@@ -382,15 +382,18 @@ struct MetricChannelSpec {
 hipError_t launch_metric_rel_l2_ch(const float* yhat, const float* y, int B, int T, int C, int H, int W,
                                    const MetricChannelSpec& spec, float eps, float* frame_out, float* seq_out,
                                    float* scratch, hipStream_t s);
+// How a scored kernel denormalises: the scalar form (mean, sd) or, with per_channel, the per-channel one (spec) with its
+// walls and clamp.  One member `norm` of every argument block below; filled by score_norm (lns_engine.cpp), unpacked per
+// channel by ChannelNorm (lns_kernels.hip).
+struct ScoreNorm { int per_channel; float mean, sd; MetricChannelSpec spec; };
 
 // Streaming evaluation (lns_rollout_eval): per-plane sums of one decoded group of steps, frames [kk][B][C][H*W], against
 // y [B][y_T][C][H*W] at steps y_t .. y_t+kk-1 into part [B][p_T][C][2] at steps p_t .. p_t+kk-1 -- the scalar form
 // (mean, sd) or the per-channel one (spec), with the per-plane body of the kernels above; then the same finish kernel.
 struct MetricGroupArgs {
     const float* frames; const float* y; float* part;
-    int B, C, H, W, kk, y_T, y_t, p_T, p_t, per_channel;
-    float mean, sd;
-    MetricChannelSpec spec;
+    int B, C, H, W, kk, y_T, y_t, p_T, p_t;
+    ScoreNorm norm;
 };
 hipError_t launch_metric_group(const MetricGroupArgs& a, hipStream_t s);
 hipError_t launch_metric_finish(const float* part, int B, int T, int C, float eps, float* frame_out, float* seq_out, hipStream_t s);
@@ -407,12 +410,11 @@ hipError_t launch_ensemble_stats(const EnsembleStatsArgs& a, hipStream_t s);
 // y[b][y_t + j][c] of y [B][y_T][C][H*W]; one block per plane (j, b, c) writes the plane's four sums (SE, G, V, CR of
 // include/lns.h) to scores[b][y_t + j][c][0..3] and, when rank is given, its M + 1 rank counts to rank[b][y_t + j][c][0..M].
 // pixel (nullable, tests): [kk][B][C][H*W][4] = mu, var, crps, (float)rank of every pixel.  Dynamic LDS: M * 1 KB of columns and 4 M + 68 bytes.
-// The denormalisation is the scalar form (mean, sd) or the per-channel one (spec), as MetricGroupArgs; 2 <= M <= 128.
+// The denormalisation: norm, as MetricGroupArgs; 2 <= M <= 128.
 struct EnsembleScoreArgs {
     const float* frames; const float* y; float* scores; int* rank; float* pixel;
-    int B, M, C, H, W, kk, y_T, y_t, per_channel;
-    float mean, sd;
-    MetricChannelSpec spec;
+    int B, M, C, H, W, kk, y_T, y_t;
+    ScoreNorm norm;
 };
 #define LNS_SCORE_MAX_MEMBERS 128
 hipError_t launch_ensemble_score(const EnsembleScoreArgs& a, hipStream_t s);
@@ -427,9 +429,8 @@ hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int 
 // Dynamic LDS: lns_spectrum::lds_bytes(H, W), at most 154368 bytes (192 x 96).  The denormalisation: as MetricGroupArgs.
 struct SpectrumArgs {
     const float* frames; const float* y; float* out;
-    int B, C, H, W, S, K, n, y_T, y_t, o_T, o_t, per_channel;
-    float mean, sd;
-    MetricChannelSpec spec;
+    int B, C, H, W, S, K, n, y_T, y_t, o_T, o_t;
+    ScoreNorm norm;
     unsigned char sel[8];
 };
 hipError_t launch_spectrum_group(const SpectrumArgs& a, hipStream_t s);
@@ -445,9 +446,9 @@ hipError_t launch_spectrum_stored(const SpectrumArgs& a, hipStream_t s);
 #define LNS_FIELD_STATS_N 12
 struct FieldStatsArgs {
     const float* frames; const float* y; float* stats; int* hist;
-    int B, C, H, W, n, y_T, y_t, o_T, o_t, per_channel, nbins;
-    float mean, sd, eps;
-    MetricChannelSpec spec;
+    int B, C, H, W, n, y_T, y_t, o_T, o_t, nbins;
+    float eps;
+    ScoreNorm norm;
     float hlo[LNS_METRIC_MAX_CH], hhi[LNS_METRIC_MAX_CH], hscale[LNS_METRIC_MAX_CH];
     unsigned char sel[8];
 };
@@ -465,9 +466,8 @@ hipError_t launch_field_stats_stored(const FieldStatsArgs& a, hipStream_t s);
 #define LNS_TIME_MAPS_STATE_PER_PIXEL 52
 struct TimeMapsArgs {
     const float* frames; const float* y; void* state; float* maps;
-    int B, C, H, W, n, y_T, y_t, first, every, count, per_channel;
-    float mean, sd;
-    MetricChannelSpec spec;
+    int B, C, H, W, n, y_T, y_t, first, every, count;
+    ScoreNorm norm;
     unsigned char sel[8];
 };
 hipError_t launch_time_maps_group(const TimeMapsArgs& a, hipStream_t s);

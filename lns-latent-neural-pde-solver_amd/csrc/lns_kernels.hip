@@ -5006,13 +5006,13 @@ __global__ __launch_bounds__(256) void metric_group_kernel(MetricGroupArgs a) {
     const float* g = a.y + (((long)b * a.y_T + a.y_t + j) * a.C + c) * HW;
     float* out2 = a.part + (((long)b * a.p_T + a.p_t + j) * a.C + c) * 2;
     float d2 = 0.0f, g2 = 0.0f;
-    if (a.per_channel) {
-        metric_plane_ch_sums(f, g, c, a.H, a.W, a.spec, d2, g2);
+    if (a.norm.per_channel) {
+        metric_plane_ch_sums(f, g, c, a.H, a.W, a.norm.spec, d2, g2);
     } else {
         // the stored rollout's plane (b, t, c) has the truth plane's offset, hence (equal base alignment) its alignment
         const int n4 = (reinterpret_cast<uintptr_t>(g) & 15) == 0 ? HW / 4 : 0;
-        if ((reinterpret_cast<uintptr_t>(f) & 15) == 0) metric_plane_sums<true>(f, g, HW, n4, a.mean, a.sd, d2, g2);
-        else metric_plane_sums<false>(f, g, HW, n4, a.mean, a.sd, d2, g2);
+        if ((reinterpret_cast<uintptr_t>(f) & 15) == 0) metric_plane_sums<true>(f, g, HW, n4, a.norm.mean, a.norm.sd, d2, g2);
+        else metric_plane_sums<false>(f, g, HW, n4, a.norm.mean, a.norm.sd, d2, g2);
     }
     metric_plane_store(d2, g2, red, out2);
 }
@@ -5145,6 +5145,19 @@ __device__ __forceinline__ float score_denorm(float x, float sd, float mean, boo
     return v;
 }
 
+// Channel c of a ScoreNorm as score_denorm takes it: the scalar form has neither walls nor a clamp.  The one place the
+// scored kernels (this file, spectrum.inc, field_stats.inc, time_maps.inc) unpack the rule; which pixels lie on a wall
+// (`zero`) is the caller's geometry.
+struct ChannelNorm {
+    float sd, mean, lo, hi;
+    bool walls, clampv;
+    __device__ __forceinline__ ChannelNorm(const ScoreNorm& n, int c) {
+        const bool pc = n.per_channel;
+        sd = pc ? n.spec.std[c] : n.sd; mean = pc ? n.spec.mean[c] : n.mean; lo = n.spec.lo; hi = n.spec.hi;
+        walls = pc && (n.spec.flags[c] & 1); clampv = pc && (n.spec.flags[c] & 2);
+    }
+};
+
 __global__ __launch_bounds__(256) void ensemble_score_kernel(EnsembleScoreArgs a) {
 #pragma clang fp contract(off)
     // all LDS is dynamic (a kernel with static LDS cannot be granted the full 160 KB of dynamic LDS init_kernels asks for):
@@ -5160,9 +5173,7 @@ __global__ __launch_bounds__(256) void ensemble_score_kernel(EnsembleScoreArgs a
     const float* f = a.frames + ((long)s * M * a.C + c) * HW;
     const long plane = ((long)b * a.y_T + a.y_t + j) * a.C + c;
     const float* g = a.y + plane * HW;
-    const float sd = a.per_channel ? a.spec.std[c] : a.sd, mean = a.per_channel ? a.spec.mean[c] : a.mean;
-    const bool walls = a.per_channel && (a.spec.flags[c] & 1), clampv = a.per_channel && (a.spec.flags[c] & 2);
-    const float lo = a.spec.lo, hi = a.spec.hi;
+    const auto [sd, mean, lo, hi, walls, clampv] = ChannelNorm(a.norm, c);
     const float fm = (float)M, fm1 = (float)(M - 1), fpairs = (float)(M * (M - 1));
     float* col = reinterpret_cast<float*>(smem) + tid;
     for (int k = tid; k <= M; k += 256) hist[k] = 0;

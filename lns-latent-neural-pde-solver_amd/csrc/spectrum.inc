@@ -175,10 +175,8 @@ __global__ __launch_bounds__(256) void spectrum_group_kernel(SpectrumArgs a) {
     const float* f = a.frames + (((long)j * a.B + b) * a.C + c) * HW;
     const float* g = a.y ? a.y + (((long)b * a.y_T + a.y_t + j) * a.C + c) * HW : nullptr;
     float* out = a.out + (((long)b * a.o_T + a.o_t + i) * a.C + c) * a.K * a.S;
-    const bool pc = a.per_channel;
-    spectrum_plane(f, g, out, a.H, a.W, a.S, pc ? a.spec.std[c] : a.sd, pc ? a.spec.mean[c] : a.mean,
-                   pc && (a.spec.flags[c] & 1), pc && (a.spec.flags[c] & 2), a.spec.lo, a.spec.hi,
-                   reinterpret_cast<float*>(smem));
+    const ChannelNorm D(a.norm, c);
+    spectrum_plane(f, g, out, a.H, a.W, a.S, D.sd, D.mean, D.walls, D.clampv, D.lo, D.hi, reinterpret_cast<float*>(smem));
 }
 
 // stored fields yhat / y [B][T][C][H*W]: block = plane
@@ -187,10 +185,9 @@ __global__ __launch_bounds__(256) void spectrum_stored_kernel(SpectrumArgs a) {
     const long p = blockIdx.x;
     const int c = (int)(p % a.C);
     const long HW = (long)a.H * a.W;
-    const bool pc = a.per_channel;
+    const ChannelNorm D(a.norm, c);
     spectrum_plane(a.frames + p * HW, a.y ? a.y + p * HW : nullptr, a.out + p * a.K * a.S, a.H, a.W, a.S,
-                   pc ? a.spec.std[c] : a.sd, pc ? a.spec.mean[c] : a.mean, pc && (a.spec.flags[c] & 1),
-                   pc && (a.spec.flags[c] & 2), a.spec.lo, a.spec.hi, reinterpret_cast<float*>(smem));
+                   D.sd, D.mean, D.walls, D.clampv, D.lo, D.hi, reinterpret_cast<float*>(smem));
 }
 
 static bool spectrum_args_ok(const SpectrumArgs& a) {

@@ -42,14 +42,9 @@ __device__ __forceinline__ void tm_store(double* p, const double (&v)[V]) {
 
 // the denormalisation of channel c and which of the V pixels from `pix` (row-major in the plane) lie on a wall
 template <int V>
-struct TmDenorm {
-    float sd, mean, lo, hi;
-    bool clampv, zero[V];
-    __device__ __forceinline__ TmDenorm(const TimeMapsArgs& a, int c, int pix) {
-        const bool pc = a.per_channel;
-        sd = pc ? a.spec.std[c] : a.sd; mean = pc ? a.spec.mean[c] : a.mean; lo = a.spec.lo; hi = a.spec.hi;
-        const bool walls = pc && (a.spec.flags[c] & 1);
-        clampv = pc && (a.spec.flags[c] & 2);
+struct TmDenorm : ChannelNorm {
+    bool zero[V];
+    __device__ __forceinline__ TmDenorm(const TimeMapsArgs& a, int c, int pix) : ChannelNorm(a.norm, c) {
 #pragma unroll
         for (int u = 0; u < V; ++u) {
             const int r = (pix + u) / a.W, cx = (pix + u) % a.W;
@@ -152,7 +147,7 @@ __global__ __launch_bounds__(256) void time_maps_finish_kernel(TimeMapsArgs a) {
 static bool time_maps_args_ok(const TimeMapsArgs& a) {
     if (!a.y || !a.state || a.B < 1 || a.B > 65535 || a.C < 1 || a.H < 1 || a.W < 1 || (long)a.H * a.W > (1L << 30)) return false;
     if ((long)a.C * a.H * a.W > (1L << 38) || (reinterpret_cast<uintptr_t>(a.state) & 7)) return false;
-    if (a.per_channel && a.C > LNS_METRIC_MAX_CH) return false;
+    if (a.norm.per_channel && a.C > LNS_METRIC_MAX_CH) return false;
     return true;
 }
 

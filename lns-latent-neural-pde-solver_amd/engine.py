@@ -6,6 +6,7 @@ hot path on CUDA/HIP tensors.  torch is used for device memory and streams only.
 """
 import collections
 import ctypes
+import functools
 import numbers
 
 import numpy as np
@@ -704,6 +705,51 @@ class Engine:
         frames = torch.empty((B, len(keep), c.in_channels, c.Ly, c.Lx), dtype=torch.float32, device=y.device) if keep else None
         return y, B, T, T_total, spec, arr, len(keep), frames
 
+    @staticmethod
+    def _result(t, shape, device):
+        """A new fp32 result tensor of `shape`, or the caller's preallocated one once it is seen to fit."""
+        import torch
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=device)
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != device:
+            raise LnsError("preallocated result must be a contiguous fp32 tensor of shape %s on the input's device" % (shape,))
+        return t
+
+    def _scored_call(self, name, result, first, y, steps, t0, param, keep_steps, norm, select=None, frame=None, seq=None,
+                     maps=None):
+        """The one body behind the eight scored rollouts: C entry point `name`, from x (t0 None: `first` is x, steps < T
+        scores the first `steps` of y) or continued from a latent at step t0 (`first` is z; frame / seq / maps may be the
+        caller's).  select(T, B, device) -> (the entry point's arguments after the stream, the result's fields after
+        `frames`, the lns_eval_select whose maps this call owns or None); `result` builds what is returned from
+        frame, seq, frames, those fields, [maps, map_steps] and, from a latent, z_last."""
+        import torch
+        latent = t0 is not None
+        first = self._dev(first)
+        if latent:
+            t0 = int(t0)
+        elif steps is not None and int(steps) < y.shape[1]:
+            y = y[:, :int(steps)]
+        y, B, T, T_total, spec, keep, n_keep, frames = self._eval_common(first, y, steps, t0 if latent else 0, keep_steps, norm)
+        extra, tail, q = select(T, B, first.device) if select is not None else ((), (), None)
+        c = self.cfg
+        frame = self._result(frame, (B, T_total, c.in_channels), first.device)
+        seq = self._result(seq, (B, c.in_channels), first.device)
+        query = "lns_rollout_eval_workspace_bytes"
+        if q is not None:
+            maps = self._result(maps, (B, c.in_channels, _lib.LNS_TIME_MAPS, c.Ly, c.Lx), first.device)
+            q.maps_out = maps.data_ptr()
+            tail += (maps, (q.map_from, q.map_every))
+            query = "lns_rollout_eval_maps_workspace_bytes"
+        z_last = torch.empty_like(first) if latent else None
+        p = self._param(param, first)
+        with torch.cuda.device(first.device):
+            ws = self._sized_workspace(query, B, first.device)
+            self._check(getattr(self._L, name)(
+                self._h, first.data_ptr(), self._ptr(p), y.data_ptr(), B, T, *((t0, T_total) if latent else ()),
+                ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(), keep, n_keep, self._ptr(frames),
+                *((z_last.data_ptr(),) if latent else ()), ws.data_ptr(), ws.numel(), self._stream(first), *extra), name)
+        return result(frame, seq, frames, *tail, *((z_last,) if latent else ()))
+
     def rollout_eval(self, x, y, steps=None, param=None, keep_steps=(), **norm):
         """The validation loop's predict -> denormalize -> relative_lp_loss pair (train_stage2_ns2d.py:249-263) without the
         [B,T,C,Ly,Lx] rollout: every decoded group of steps is scored against the normalised ground truth y [B,T,C,Ly,Lx]
@@ -711,21 +757,7 @@ class Engine:
         `metrics.relative_l2` (so `**metrics.twophase_spec(...)` works).  steps < T scores the first `steps` of y.
         Returns (frame_wise [B,T,C], seq_wise [B,C], frames [B,len(keep_steps),C,Ly,Lx] or None): the same bits as
         `metrics.relative_l2(rollout(x, T), y, ...)` and `rollout(x, T)[:, keep_steps]`."""
-        import torch
-        x = self._dev(x)
-        if steps is not None and int(steps) < y.shape[1]:
-            y = y[:, :int(steps)]
-        y, B, T, _, spec, keep, n_keep, frames = self._eval_common(x, y, steps, 0, keep_steps, norm)
-        frame = torch.empty((B, T, self.cfg.in_channels), dtype=torch.float32, device=x.device)
-        seq = torch.empty((B, self.cfg.in_channels), dtype=torch.float32, device=x.device)
-        p = self._param(param, x)
-        with torch.cuda.device(x.device):
-            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, x.device)
-            self._check(self._L.lns_rollout_eval(self._h, x.data_ptr(), self._ptr(p), y.data_ptr(),
-                                                 B, T, ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(), keep, n_keep,
-                                                 self._ptr(frames), ws.data_ptr(),
-                                                 ws.numel(), self._stream(x)), "lns_rollout_eval")
-        return frame, seq, frames
+        return self._scored_call("lns_rollout_eval", lambda *r: r, x, y, steps, None, param, keep_steps, norm)
 
     def rollout_latent_eval(self, z, y, steps=None, t0=0, param=None, keep_steps=(), frame=None, seq=None, **norm):
         """rollout_eval continued from a latent: scores steps t0 .. t0+steps-1 of y [B,T_total,C,Ly,Lx] (steps=None: to
@@ -733,28 +765,8 @@ class Engine:
         stay in the engine's workspace, and the call that completes the horizon (t0 + steps == T_total) writes `frame`
         [B,T_total,C] and `seq` [B,C] (pass the tensors along, or take them from the last chunk's return value).
         keep_steps are relative to the chunk.  Returns (frame, seq, frames or None, z after the last step)."""
-        import torch
-        z = self._dev(z)
-        t0 = int(t0)
-        y, B, T, T_total, spec, keep, n_keep, frames = self._eval_common(z, y, steps, t0, keep_steps, norm)
-        C = self.cfg.in_channels
-        if frame is None:
-            frame = torch.empty((B, T_total, C), dtype=torch.float32, device=z.device)
-        if seq is None:
-            seq = torch.empty((B, C), dtype=torch.float32, device=z.device)
-        for t, shape in ((frame, (B, T_total, C)), (seq, (B, C))):
-            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != z.device:
-                raise LnsError("preallocated result must be a contiguous fp32 tensor of shape %s on the input's device" % (shape,))
-        z_last = torch.empty_like(z)
-        p = self._param(param, z)
-        with torch.cuda.device(z.device):
-            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, z.device)
-            self._check(self._L.lns_rollout_latent_eval(self._h, z.data_ptr(), self._ptr(p),
-                                                        y.data_ptr(), B, T, t0, T_total, ctypes.byref(spec), frame.data_ptr(),
-                                                        seq.data_ptr(), keep, n_keep,
-                                                        self._ptr(frames), z_last.data_ptr(),
-                                                        ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_eval")
-        return frame, seq, frames, z_last
+        return self._scored_call("lns_rollout_latent_eval", lambda *r: r, z, y, steps, t0, param, keep_steps, norm,
+                                 frame=frame, seq=seq)
 
     # -- streaming validation with energy spectra (include/lns.h "energy spectra") ----------------------------------
     def spectrum_bins(self, H=None, W=None):
@@ -763,12 +775,15 @@ class Engine:
         from . import metrics
         return metrics.spectrum_bins(H, W)
 
-    def _spectrum_select(self, spectrum_steps, T, B, device):
+    def _spectrum_select(self, spectrum_steps, T, B, device, optional=False):
+        """A `select` of _scored_call: the spectra of `spectrum_steps`; optional: an empty sequence asks for none."""
         import torch
+        if optional and spectrum_steps is not None and not isinstance(spectrum_steps, slice) and len(spectrum_steps) == 0:
+            return (None, 0, None), (None, []), None
         sel = normalize_keep_steps(range(T) if spectrum_steps is None else spectrum_steps, T)
         arr = (ctypes.c_int * len(sel))(*sel)
         spectra = torch.empty((B, len(sel), self.cfg.in_channels, 3, self.spectrum_bins()), dtype=torch.float32, device=device)
-        return sel, arr, spectra
+        return (arr, len(sel), spectra.data_ptr()), (spectra, sel), None
 
     def energy_spectrum(self, y_hat, y=None, **norm):
         """Shell-summed energy spectra of stored fields (lns_op_energy_spectrum): y_hat and y (optional) [B, T, C, H, W],
@@ -783,49 +798,15 @@ class Engine:
         and frames hold rollout_eval's bits, spectra [B, n, C, 3, S] those of
         `energy_spectrum(rollout(x, T)[:, spectrum_steps], y[:, spectrum_steps], ...)`.  Bins are index wavenumbers; on the
         non-periodic families a spectrum carries the leakage of the walls.  The workspace is rollout_eval's."""
-        import torch
-        x = self._dev(x)
-        if steps is not None and int(steps) < y.shape[1]:
-            y = y[:, :int(steps)]
-        y, B, T, _, spec, keep, n_keep, frames = self._eval_common(x, y, steps, 0, keep_steps, norm)
-        sel, sel_arr, spectra = self._spectrum_select(spectrum_steps, T, B, x.device)
-        frame = torch.empty((B, T, self.cfg.in_channels), dtype=torch.float32, device=x.device)
-        seq = torch.empty((B, self.cfg.in_channels), dtype=torch.float32, device=x.device)
-        p = self._param(param, x)
-        with torch.cuda.device(x.device):
-            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, x.device)
-            self._check(self._L.lns_rollout_eval_spectrum(
-                self._h, x.data_ptr(), self._ptr(p), y.data_ptr(), B, T, ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(),
-                keep, n_keep, self._ptr(frames), ws.data_ptr(), ws.numel(), self._stream(x), sel_arr, len(sel),
-                spectra.data_ptr()), "lns_rollout_eval_spectrum")
-        return EvalSpectra(frame, seq, frames, spectra, sel)
+        return self._scored_call("lns_rollout_eval_spectrum", EvalSpectra, x, y, steps, None, param, keep_steps, norm,
+                                 functools.partial(self._spectrum_select, spectrum_steps))
 
     def rollout_latent_eval_spectrum(self, z, y, steps=None, t0=0, param=None, keep_steps=(), spectrum_steps=None, frame=None,
                                      seq=None, **norm):
         """rollout_latent_eval with energy spectra: keep_steps and spectrum_steps are relative to the chunk, spectra
         [B, n, C, 3, S] belong to this chunk's steps.  Returns EvalSpectraChunk (see rollout_latent_eval for frame / seq)."""
-        import torch
-        z = self._dev(z)
-        t0 = int(t0)
-        y, B, T, T_total, spec, keep, n_keep, frames = self._eval_common(z, y, steps, t0, keep_steps, norm)
-        sel, sel_arr, spectra = self._spectrum_select(spectrum_steps, T, B, z.device)
-        C = self.cfg.in_channels
-        if frame is None:
-            frame = torch.empty((B, T_total, C), dtype=torch.float32, device=z.device)
-        if seq is None:
-            seq = torch.empty((B, C), dtype=torch.float32, device=z.device)
-        for t, shape in ((frame, (B, T_total, C)), (seq, (B, C))):
-            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != z.device:
-                raise LnsError("preallocated result must be a contiguous fp32 tensor of shape %s on the input's device" % (shape,))
-        z_last = torch.empty_like(z)
-        p = self._param(param, z)
-        with torch.cuda.device(z.device):
-            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, z.device)
-            self._check(self._L.lns_rollout_latent_eval_spectrum(
-                self._h, z.data_ptr(), self._ptr(p), y.data_ptr(), B, T, t0, T_total, ctypes.byref(spec), frame.data_ptr(),
-                seq.data_ptr(), keep, n_keep, self._ptr(frames), z_last.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(z),
-                sel_arr, len(sel), spectra.data_ptr()), "lns_rollout_latent_eval_spectrum")
-        return EvalSpectraChunk(frame, seq, frames, spectra, sel, z_last)
+        return self._scored_call("lns_rollout_latent_eval_spectrum", EvalSpectraChunk, z, y, steps, t0, param, keep_steps, norm,
+                                 functools.partial(self._spectrum_select, spectrum_steps), frame, seq)
 
     # -- streaming validation with field statistics (include/lns.h "field statistics") ----------------------------
     def field_stats(self, y_hat, y, hist=None, **norm):
@@ -834,8 +815,8 @@ class Engine:
         from . import metrics
         return metrics.field_stats(y_hat, y, hist=hist, **norm)
 
-    def _stats_select(self, stats_steps, spectrum_steps, hist, T, B, device):
-        """-> (stats steps, their array, stats, lns_stats_spec or None, hist or None, spectrum steps, their array or None, spectra or None)"""
+    def _stats_alloc(self, stats_steps, hist, T, B, device):
+        """-> (stats steps, their array, stats, lns_stats_spec or None, hist or None)"""
         import torch
         C = self.cfg.in_channels
         sel = normalize_keep_steps(range(T) if stats_steps is None else stats_steps, T)
@@ -847,9 +828,14 @@ class Engine:
             if not 1 <= hs.nbins <= 256:
                 raise LnsError("hist: nbins must be in 1 .. 256, got %d" % hs.nbins)
             counts = torch.empty((B, len(sel), C, 2, hs.nbins + 2), dtype=torch.int32, device=device)
-        no_spectra = spectrum_steps is not None and not isinstance(spectrum_steps, slice) and len(spectrum_steps) == 0
-        ssel, sarr, spectra = ([], None, None) if no_spectra else self._spectrum_select(spectrum_steps, T, B, device)
-        return sel, arr, stats, hs, counts, ssel, sarr, spectra
+        return sel, arr, stats, hs, counts
+
+    def _stats_select(self, stats_steps, hist, spectrum_steps, T, B, device):
+        """A `select` of _scored_call: the statistics of `stats_steps`, their histograms and (optional) spectra."""
+        sel, arr, stats, hs, counts = self._stats_alloc(stats_steps, hist, T, B, device)
+        sargs, stail, _ = self._spectrum_select(spectrum_steps, T, B, device, optional=True)
+        hp = ctypes.byref(hs) if hs is not None else None
+        return sargs + (arr, len(sel), hp, stats.data_ptr(), self._ptr(counts)), (stats, counts, sel) + stail, None
 
     def rollout_eval_stats(self, x, y, steps=None, param=None, keep_steps=(), stats_steps=None, hist=None, spectrum_steps=(),
                            **norm):
@@ -860,51 +846,15 @@ class Engine:
         `spectrum_steps` (default: none; None: every step) adds rollout_eval_spectrum's spectra in the same pass.  Returns
         EvalStats: frame, seq, frames and spectra hold the bits of the existing calls, stats / hist those of
         `field_stats(rollout(x, T)[:, stats_steps], y[:, stats_steps], hist, ...)`.  The workspace is rollout_eval's."""
-        import torch
-        x = self._dev(x)
-        if steps is not None and int(steps) < y.shape[1]:
-            y = y[:, :int(steps)]
-        y, B, T, _, spec, keep, n_keep, frames = self._eval_common(x, y, steps, 0, keep_steps, norm)
-        sel, arr, stats, hs, counts, ssel, sarr, spectra = self._stats_select(stats_steps, spectrum_steps, hist, T, B, x.device)
-        frame = torch.empty((B, T, self.cfg.in_channels), dtype=torch.float32, device=x.device)
-        seq = torch.empty((B, self.cfg.in_channels), dtype=torch.float32, device=x.device)
-        p = self._param(param, x)
-        with torch.cuda.device(x.device):
-            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, x.device)
-            self._check(self._L.lns_rollout_eval_stats(
-                self._h, x.data_ptr(), self._ptr(p), y.data_ptr(), B, T, ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(),
-                keep, n_keep, self._ptr(frames), ws.data_ptr(), ws.numel(), self._stream(x), sarr, len(ssel), self._ptr(spectra),
-                arr, len(sel), ctypes.byref(hs) if hs is not None else None, stats.data_ptr(), self._ptr(counts)),
-                "lns_rollout_eval_stats")
-        return EvalStats(frame, seq, frames, stats, counts, sel, spectra, ssel)
+        return self._scored_call("lns_rollout_eval_stats", EvalStats, x, y, steps, None, param, keep_steps, norm,
+                                 functools.partial(self._stats_select, stats_steps, hist, spectrum_steps))
 
     def rollout_latent_eval_stats(self, z, y, steps=None, t0=0, param=None, keep_steps=(), stats_steps=None, hist=None,
                                   spectrum_steps=(), frame=None, seq=None, **norm):
         """rollout_latent_eval with field statistics: keep_steps, stats_steps and spectrum_steps are relative to the chunk,
         stats / hist / spectra belong to this chunk's steps.  Returns EvalStatsChunk (see rollout_latent_eval for frame / seq)."""
-        import torch
-        z = self._dev(z)
-        t0 = int(t0)
-        y, B, T, T_total, spec, keep, n_keep, frames = self._eval_common(z, y, steps, t0, keep_steps, norm)
-        sel, arr, stats, hs, counts, ssel, sarr, spectra = self._stats_select(stats_steps, spectrum_steps, hist, T, B, z.device)
-        C = self.cfg.in_channels
-        if frame is None:
-            frame = torch.empty((B, T_total, C), dtype=torch.float32, device=z.device)
-        if seq is None:
-            seq = torch.empty((B, C), dtype=torch.float32, device=z.device)
-        for t, shape in ((frame, (B, T_total, C)), (seq, (B, C))):
-            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != z.device:
-                raise LnsError("preallocated result must be a contiguous fp32 tensor of shape %s on the input's device" % (shape,))
-        z_last = torch.empty_like(z)
-        p = self._param(param, z)
-        with torch.cuda.device(z.device):
-            ws = self._sized_workspace("lns_rollout_eval_workspace_bytes", B, z.device)
-            self._check(self._L.lns_rollout_latent_eval_stats(
-                self._h, z.data_ptr(), self._ptr(p), y.data_ptr(), B, T, t0, T_total, ctypes.byref(spec), frame.data_ptr(),
-                seq.data_ptr(), keep, n_keep, self._ptr(frames), z_last.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(z),
-                sarr, len(ssel), self._ptr(spectra), arr, len(sel), ctypes.byref(hs) if hs is not None else None,
-                stats.data_ptr(), self._ptr(counts)), "lns_rollout_latent_eval_stats")
-        return EvalStatsChunk(frame, seq, frames, stats, counts, sel, spectra, ssel, z_last)
+        return self._scored_call("lns_rollout_latent_eval_stats", EvalStatsChunk, z, y, steps, t0, param, keep_steps, norm,
+                                 functools.partial(self._stats_select, stats_steps, hist, spectrum_steps), frame, seq)
 
     # -- streaming validation with time maps (include/lns.h "time maps") -------------------------------------------
     def time_maps(self, y_hat, y, map_steps=None, **norm):
@@ -914,30 +864,25 @@ class Engine:
         return metrics.time_maps(y_hat, y, map_steps=map_steps, **norm)
 
     def _maps_select(self, map_steps, stats_steps, hist, spectrum_steps, T, B, device):
-        """-> (lns_eval_select, what it points to (kept alive by the caller), EvalMaps' fields from `stats` on)"""
-        import torch
-        C = self.cfg.in_channels
-        first, every = map_steps
-        none = lambda s: s is not None and not isinstance(s, slice) and len(s) == 0
-        if none(stats_steps):
-            if hist is not None:
-                raise LnsError("hist needs stats_steps")
-            sel, arr, stats, hs, counts = [], None, None, None, None
-        else:
-            sel, arr, stats, hs, counts, _, _, _ = self._stats_select(stats_steps, (), hist, T, B, device)
-        ssel, sarr, spectra = ([], None, None) if none(spectrum_steps) else self._spectrum_select(spectrum_steps, T, B, device)
-        maps = torch.empty((B, C, _lib.LNS_TIME_MAPS, self.cfg.Ly, self.cfg.Lx), dtype=torch.float32, device=device)
+        """A `select` of _scored_call: the lns_eval_select of the time maps over `map_steps` = (from, every) with the
+        (optional) statistics and spectra; the maps tensor itself is _scored_call's."""
         q = _lib.LnsEvalSelect()
         q.size = ctypes.sizeof(_lib.LnsEvalSelect)
-        q.n_spec, q.n_stats, q.map_from, q.map_every = len(ssel), len(sel), first, every
-        if ssel:
-            q.spectrum_steps_host, q.spectra_out = sarr, spectra.data_ptr()
-        if sel:
-            q.stats_steps_host, q.stats_out = arr, stats.data_ptr()
+        q.map_from, q.map_every = map_steps
+        tail = (None, None, [])
+        if stats_steps is not None and not isinstance(stats_steps, slice) and len(stats_steps) == 0:
+            if hist is not None:
+                raise LnsError("hist needs stats_steps")
+        else:
+            sel, arr, stats, hs, counts = self._stats_alloc(stats_steps, hist, T, B, device)
+            q.n_stats, q.stats_steps_host, q.stats_out = len(sel), arr, stats.data_ptr()
             if hs is not None:
                 q.hspec, q.hist_out = ctypes.pointer(hs), counts.data_ptr()
-        q.maps_out = maps.data_ptr()
-        return q, (arr, sarr, hs), (stats, counts, sel, spectra, ssel, maps, (first, every))
+            tail = (stats, counts, sel)
+        (sarr, n_spec, spectra), stail, _ = self._spectrum_select(spectrum_steps, T, B, device, optional=True)
+        if n_spec:
+            q.n_spec, q.spectrum_steps_host, q.spectra_out = n_spec, sarr, spectra
+        return (ctypes.byref(q),), tail + stail, q
 
     def rollout_eval_maps(self, x, y, steps=None, param=None, keep_steps=(), map_steps=None, stats_steps=(), hist=None,
                           spectrum_steps=(), **norm):
@@ -948,24 +893,9 @@ class Engine:
         rollout_eval_stats' statistics and rollout_eval_spectrum's spectra in the same pass.  Returns EvalMaps: every field but
         maps holds the bits of the existing calls, maps those of `time_maps(rollout(x, T), y, map_steps, ...)`.  The workspace is
         rollout_eval's plus 52 bytes per (trajectory, channel, pixel)."""
-        import torch
         ms = normalize_map_steps(map_steps)
-        x = self._dev(x)
-        if steps is not None and int(steps) < y.shape[1]:
-            y = y[:, :int(steps)]
-        y, B, T, _, spec, keep, n_keep, frames = self._eval_common(x, y, steps, 0, keep_steps, norm)
-        q, alive, tail = self._maps_select(ms, stats_steps, hist, spectrum_steps, T, B, x.device)
-        frame = torch.empty((B, T, self.cfg.in_channels), dtype=torch.float32, device=x.device)
-        seq = torch.empty((B, self.cfg.in_channels), dtype=torch.float32, device=x.device)
-        p = self._param(param, x)
-        with torch.cuda.device(x.device):
-            ws = self._sized_workspace("lns_rollout_eval_maps_workspace_bytes", B, x.device)
-            self._check(self._L.lns_rollout_eval_maps(
-                self._h, x.data_ptr(), self._ptr(p), y.data_ptr(), B, T, ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(),
-                keep, n_keep, self._ptr(frames), ws.data_ptr(), ws.numel(), self._stream(x), ctypes.byref(q)),
-                "lns_rollout_eval_maps")
-        del alive
-        return EvalMaps(frame, seq, frames, *tail)
+        return self._scored_call("lns_rollout_eval_maps", EvalMaps, x, y, steps, None, param, keep_steps, norm,
+                                 functools.partial(self._maps_select, ms, stats_steps, hist, spectrum_steps))
 
     def rollout_latent_eval_maps(self, z, y, steps=None, t0=0, param=None, keep_steps=(), map_steps=None, stats_steps=(),
                                  hist=None, spectrum_steps=(), frame=None, seq=None, maps=None, **norm):
@@ -974,34 +904,9 @@ class Engine:
         engine and batch, with nothing else run on it in between: the maps' state stays in the engine's workspace, and the chunk
         that completes the horizon writes `maps` (pass the tensor along like frame / seq, or take it from the last chunk's
         result; it is untouched until then).  Returns EvalMapsChunk."""
-        import torch
         ms = normalize_map_steps(map_steps)
-        z = self._dev(z)
-        t0 = int(t0)
-        y, B, T, T_total, spec, keep, n_keep, frames = self._eval_common(z, y, steps, t0, keep_steps, norm)
-        q, alive, tail = self._maps_select(ms, stats_steps, hist, spectrum_steps, T, B, z.device)
-        C = self.cfg.in_channels
-        if frame is None:
-            frame = torch.empty((B, T_total, C), dtype=torch.float32, device=z.device)
-        if seq is None:
-            seq = torch.empty((B, C), dtype=torch.float32, device=z.device)
-        if maps is None:
-            maps = tail[5]
-        for t, shape in ((frame, (B, T_total, C)), (seq, (B, C)), (maps, (B, C, _lib.LNS_TIME_MAPS, self.cfg.Ly, self.cfg.Lx))):
-            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != z.device:
-                raise LnsError("preallocated result must be a contiguous fp32 tensor of shape %s on the input's device" % (shape,))
-        q.maps_out = maps.data_ptr()
-        tail = tail[:5] + (maps,) + tail[6:]
-        z_last = torch.empty_like(z)
-        p = self._param(param, z)
-        with torch.cuda.device(z.device):
-            ws = self._sized_workspace("lns_rollout_eval_maps_workspace_bytes", B, z.device)
-            self._check(self._L.lns_rollout_latent_eval_maps(
-                self._h, z.data_ptr(), self._ptr(p), y.data_ptr(), B, T, t0, T_total, ctypes.byref(spec), frame.data_ptr(),
-                seq.data_ptr(), keep, n_keep, self._ptr(frames), z_last.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(z),
-                ctypes.byref(q)), "lns_rollout_latent_eval_maps")
-        del alive
-        return EvalMapsChunk(frame, seq, frames, *tail, z_last)
+        return self._scored_call("lns_rollout_latent_eval_maps", EvalMapsChunk, z, y, steps, t0, param, keep_steps, norm,
+                                 functools.partial(self._maps_select, ms, stats_steps, hist, spectrum_steps), frame, seq, maps)
 
     # -- training rollout of the propagator (include/lns.h "training rollout") ------------------------------------
     def _ptr_array(self, tensors):

@@ -269,11 +269,43 @@ def test_streaming_maps_same_bits_as_the_op_on_the_stored_rollout(case):
         eng.set_option("overlap", 1)
 
 
-@pytest.mark.parametrize("case", ["ns2d_mini", "twophase_cond"])
+def _chunked_with_every_selection(case):
+    """Chunks 4 + 3 of a horizon of 7 at B = 2 under decode_group = 2 (the second chunk ends in a ragged group), each carrying
+    spectra, statistics with histograms, maps and kept frames together: the two chunks against the one call, bit for bit, and
+    the maps against the op on the stored rollout."""
+    args, model, eng, xd, yd, pd, norm, denorm, y = teg._setup(case)
+    C, T7, x2 = args.in_channels, 7, xd[:2].contiguous()
+    g = torch.Generator(device="cuda").manual_seed(78)
+    y7 = torch.randn((2, T7, C, args.Ly, args.Lx), device="cuda", generator=g)
+    sel = dict(map_steps=(1, 2), hist=_hist_of(args))
+    z0 = eng.encode(x2)
+    try:
+        eng.set_option("decode_group", 2)
+        one = eng.rollout_eval_maps(x2, y7, keep_steps=(1, 4, 6), stats_steps=(1, 2, 6), spectrum_steps=(0, 3, 6), **sel, **norm)
+        a = eng.rollout_latent_eval_maps(z0, y7, steps=4, t0=0, keep_steps=(1,), stats_steps=(1, 2), spectrum_steps=(0, 3), **sel,
+                                         **norm)
+        b = eng.rollout_latent_eval_maps(a.z_last, y7, steps=3, t0=4, keep_steps=(0, 2), stats_steps=(2,), spectrum_steps=(2,),
+                                         frame=a.frame, seq=a.seq, maps=a.maps, **sel, **norm)
+        torch.cuda.synchronize()
+    finally:
+        eng.set_option("decode_group", 1)
+    _assert_bits(one.maps, eng.time_maps(eng.rollout(x2, T7), y7, map_steps=(1, 2), **norm), (case, "one call"))
+    assert b.maps is a.maps and b.frame is a.frame and b.seq is a.seq
+    _assert_bits(b.maps, one.maps, (case, "chunked"))
+    assert _same(b.frame, one.frame) and _same(b.seq, one.seq)
+    assert _same(torch.cat([a.stats, b.stats], 1), one.stats) and torch.equal(torch.cat([a.hist, b.hist], 1), one.hist)
+    assert _same(torch.cat([a.spectra, b.spectra], 1), one.spectra)
+    assert _same(torch.cat([a.frames, b.frames], 1), one.frames)
+
+
+@pytest.mark.parametrize("case", ["ns2d_mini", "twophase_cond", "ns2d_mini-4+3-every-selection"])
 def test_chunked_latent_calls_reproduce_the_one_call_result(case):
     """Chunks 3 + 1 + 4 of a horizon of 8 on one workspace.  (3, 2): map_from lies in the second chunk; (4, 3): the first two
-    chunks select nothing.  maps is untouched until the chunk that completes the horizon."""
+    chunks select nothing.  maps is untouched until the chunk that completes the horizon.  The third case:
+    _chunked_with_every_selection."""
     teg._need_gpu()
+    if case.endswith("-every-selection"):
+        return _chunked_with_every_selection(case.split("-")[0])
     args, model, eng, xd, yd, pd, norm, denorm, y = teg._setup(case)
     C, T8 = args.in_channels, 8
     g = torch.Generator(device="cuda").manual_seed(77)

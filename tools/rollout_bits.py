@@ -2,12 +2,16 @@
 """What do the rollout entry points enqueue?  One JSON object: "case/entry/options" -> {output tensor: first 16 hex digits of the
 sha256 of its bytes} for every rollout entry point of `Engine` (rollout, rollout with to_x=False, rollout with keep_steps,
 rollout_latent, rollout_latent with keep_steps, rollout_eval, rollout_latent_eval in one chunk and in two, 4 + 3,
-rollout_latent_ensemble with M = 3 members and rollout_latent_ensemble_eval on the same members where the library has them) under
+rollout_latent_ensemble with M = 3 members and rollout_latent_ensemble_eval on the same members where the library has them, and
+the six newer scored calls -- rollout_eval_spectrum / _stats / _maps from x and their rollout_latent_ forms in two chunks, 4 + 3:
+spectra at steps [0, 3, 6], statistics at [1, 2, 6] with an 8-bin histogram, maps from step 1 every 2, the _maps forms with all
+three selections together; every tensor they return is hashed, the chunks' per-step tensors concatenated) under
 decode_group {default, 1, 2, automatic} x decode_streams {1, 2} x overlap {0, 1}, at B = 2, T = 7 (decode_group = 2: a ragged last
 group), keep_steps = [1, 4, 6], on the shapes of the ns2d_mini, twophase_cond and sw_half_periodic fixtures with inputs
-from `filler`; plus "launches/<call>" -> {kernel class: launches} of one rollout, one rollout(keep_steps=...) and one
-rollout_eval of ns2d_mini under timing_enable(True).  Then, so that every kind of launch a plan can hold is reached, with the
-library's default options only: the ns2d_mini variants with self-attention, an attention encoder, Fourier blocks and two
+from `filler`; plus "launches/<call>" -> {kernel class: launches} of one rollout, one rollout(keep_steps=...), one
+rollout_eval and one rollout_eval_maps (all selections) of ns2d_mini under timing_enable(True).  An entry whose hashes are the
+same under all 16 settings is written once, as "case/entry/all 16 settings"; one whose hashes differ keeps a key per setting.
+Then, so that every kind of launch a plan can hold is reached, with the library's default options only: the ns2d_mini variants with self-attention, an attention encoder, Fourier blocks and two
 residual blocks per level and the unconditional two-phase model (EXTRA), and ns2d_64 (the smallest preset whose FABlock fits
 the fused kernel: 32 x 32 planes, 128 channels) under fa_fused 0 (plain sandwich), fa_fused 2 (input split + fused kernel) and
 fa_fused 0 with fa_chunk_mb 1 (the in_proj -> sandwich -> to_out chain re-issued per sample); "classes/<case>[/<options>]" ->
@@ -41,6 +45,7 @@ KEEP = [1, 4, 6]
 CHUNKS = ((0, 4, [1]), (4, 3, [0, 2]))              # (t0, steps, keep_steps of the chunk): KEEP again
 NORM = dict(mean=0.37, std=1.9)
 MEMBERS, NOISE = 3, 0.05                            # rollout_latent_ensemble: z0 + NOISE * filler.normal per member
+SPECTRUM_STEPS, STATS_STEPS, HIST, MAP_STEPS = [0, 3, 6], [1, 2, 6], (8, -4.0, 4.0), (1, 2)
 DECODE_GROUPS = (None, 1, 2, 0)                     # None: never set (it comes first); 0: automatic, here one group of all T steps
 
 
@@ -48,8 +53,24 @@ def sha(t):
     return hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:16]     # 64 bits: the first 16 digits of earlier records
 
 
+def merge_settings(rec):
+    """The keys "case/entry/dg*_ds*_ov*" of one entry -> one key "case/entry/all N settings" when their N values are equal."""
+    groups = {}
+    for k in rec:
+        m = re.fullmatch(r"(.*)/dg\w+_ds\d_ov\d", k)
+        if m:
+            groups.setdefault(m.group(1), []).append(k)
+    for prefix, keys in groups.items():
+        if all(rec[k] == rec[keys[0]] for k in keys):
+            v = rec[keys[0]]
+            for k in keys:
+                del rec[k]
+            rec["%s/all %d settings" % (prefix, len(keys))] = v
+    return rec
+
+
 def dumps(rec):
-    """One key per line (a record has some 600 keys of up to nine hashes): two records compare line by line."""
+    """One key per line (a record has some 200 keys of up to nine hashes): two records compare line by line."""
     return "{\n" + ",\n".join(" %s: %s" % (json.dumps(k), json.dumps(rec[k], sort_keys=True)) for k in sorted(rec)) + "\n}"
 
 
@@ -67,6 +88,34 @@ def setup(name):
     y = torch.from_numpy(filler.normal("y", (B, T, args.in_channels, args.Ly, args.Lx), seed)).cuda()
     p = torch.from_numpy(filler.uniform01("param", B, seed).astype(np.float32)).cuda() if args.family == "twophase_cond" else None
     return model._engine(x), x, y, p
+
+
+def chunk_steps(steps, t0, n):
+    """The steps of the horizon that fall into the chunk t0 .. t0 + n - 1, relative to it."""
+    return [s - t0 for s in steps if t0 <= s < t0 + n]
+
+
+def scored(res, z_last=None):
+    """Every tensor of an Eval* result (a namedtuple; the step lists and rules among its fields are not tensors)."""
+    d = {k: v for k, v in res._asdict().items() if isinstance(v, torch.Tensor)}
+    if z_last is not None:
+        d["z_last"] = z_last
+    return d
+
+
+def scored_chunks(call, z0, y, p, **sel):
+    """One horizon in CHUNKS through a rollout_latent_eval_* call: frame / seq / maps are passed along, the per-step tensors
+    of the chunks concatenated; **sel: the selections as steps of the horizon."""
+    z, carry, parts = z0, {}, {}
+    for t0, steps, keep in CHUNKS:
+        rel = {k: chunk_steps(v, t0, steps) for k, v in sel.items() if k.endswith("_steps") and k != "map_steps"}
+        res = call(z, y, steps=steps, t0=t0, param=p, keep_steps=keep, **dict(sel, **rel), **carry, **NORM)
+        z = res.z_last
+        carry = {k: getattr(res, k) for k in ("frame", "seq", "maps") if hasattr(res, k)}
+        for k in ("frames", "spectra", "stats", "hist"):
+            if getattr(res, k, None) is not None:
+                parts.setdefault(k, []).append(getattr(res, k))
+    return dict(carry, z_last=z, **{k: torch.cat(v, 1) for k, v in parts.items()})
 
 
 def entries(eng, x, y, p):
@@ -99,11 +148,18 @@ def entries(eng, x, y, p):
                                                  return_last=True, **NORM)
             yield "rollout_latent_ensemble_eval", dict(rel_l2=s.rel_l2, rmse=s.rmse, spread=s.spread, crps=s.crps, seq=s.seq,
                                                        rank=s.rank, mean=s.mean, var=s.var, z_last=s.z_last)
+    for name, sel in (("spectrum", dict(spectrum_steps=SPECTRUM_STEPS)), ("stats", dict(stats_steps=STATS_STEPS, hist=HIST)),
+                      ("maps", dict(map_steps=MAP_STEPS, stats_steps=STATS_STEPS, hist=HIST, spectrum_steps=SPECTRUM_STEPS))):
+        if eng._L.lns_build_has(b"eval_" + name.encode()) == 1:
+            yield "rollout_eval_" + name, scored(getattr(eng, "rollout_eval_" + name)(x, y, param=p, keep_steps=KEEP, **sel, **NORM))
+            yield "rollout_latent_eval_%s_4+3" % name, scored_chunks(getattr(eng, "rollout_latent_eval_" + name), z0, y, p, **sel)
 
 
 def launches(eng, x, y):
     calls = (("rollout", lambda: eng.rollout(x, T)), ("rollout_keep", lambda: eng.rollout(x, T, keep_steps=KEEP)),
-             ("rollout_eval", lambda: eng.rollout_eval(x, y, keep_steps=KEEP, **NORM)))
+             ("rollout_eval", lambda: eng.rollout_eval(x, y, keep_steps=KEEP, **NORM)),
+             ("rollout_eval_maps", lambda: eng.rollout_eval_maps(x, y, keep_steps=KEEP, map_steps=MAP_STEPS, stats_steps=STATS_STEPS,
+                                                                 hist=HIST, spectrum_steps=SPECTRUM_STEPS, **NORM)))
     rec = {}
     for name, fn in calls:
         eng.timing_enable(True)
@@ -156,7 +212,7 @@ def main():
     reached = {k for key, c in rec.items() if key.startswith("classes/") for k, n in c.items() if "/" not in k and n > 0}
     src = open(os.path.join(ROOT, "lns-latent-neural-pde-solver_amd", "csrc", "lns_engine.cpp")).read()
     every = set(re.findall(r'"([^"]+)"', re.search(r"kClsName\[CLS_COUNT\] = \{([^}]*)\}", src).group(1)))
-    text = dumps(rec)
+    text = dumps(merge_settings(rec))
     if a.out:
         with open(a.out, "w") as f:
             f.write(text + "\n")
