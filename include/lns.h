@@ -749,7 +749,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * lns_op_ensemble_score are there; "eval_spectrum" = lns_rollout_eval_spectrum, lns_rollout_latent_eval_spectrum,
  * lns_op_energy_spectrum and lns_spectrum_bins are there; "eval_stats" = lns_rollout_eval_stats,
  * lns_rollout_latent_eval_stats and lns_op_field_stats are there; "eval_maps" = lns_rollout_eval_maps,
- * lns_rollout_latent_eval_maps, their size query, lns_op_time_maps and lns_time_maps_state_bytes are there.
+ * lns_rollout_latent_eval_maps, their size query, lns_op_time_maps and lns_time_maps_state_bytes are there;
+ * "op_conv_gn" = lns_op_conv_gn is there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
@@ -771,6 +772,38 @@ int lns_op_conv2d(const float* x, int B, int Cin, int Hin, int Win, int Hv, int 
                   int dilation, int pad_t, int pad_b, int pad_l, int pad_r, int mode_y, int mode_x,
                   const float* ss, int act_in, int act_out, const float* residual,
                   const float* badd, float* y, int tile_variant, void* stream, unsigned* amax_out);
+/* GroupNorm from the tile statistics of the convolution that produced its input (unit tests of that path; "op_conv_gn" in
+ * lns_build_has): a producer convolution leaves per-(sample, 128-pixel tile, channel) (mean, M2) partials in its epilogue,
+ * and they are merged (a) by the finalize kernels into a [B,Cout,2] (scale, shift) table and / or (b) in the prologue of a
+ * consumer convolution, which needs no launch of its own ("the fold").  Whether a producer carries the statistics, over
+ * which pixel counts (exact 128-pixel tiles / one ragged tile / ragged tiles of a larger plane) and whether the fold is
+ * allowed is the planner's own rule, called by this entry point and the planner alike; a combination a plan never holds
+ * is LNS_EINVAL (message: lns_create_error()).  Existing launchers only.  Every check precedes the first launch; the call
+ * synchronises `stream`.
+ *   producer   lns_op_conv2d's arguments (x .. tile_variant, OCT8 bits included), y its stored output
+ *   part_out   device [B][tiles][Cout][2] or NULL: a copy of the producer's partials
+ *   part_in    device, same layout, or NULL: merged INSTEAD of the producer's (crafted (mean, M2) sets)
+ *   geom       host int[8] or NULL: tiles_x, tiles_y, log2 of the tile width, flat (1: a tile is 128 consecutive pixels of
+ *              the flattened plane, 1x1 producers), phase multiplier (4: upsampling form, partial (ty * tiles_x + tx) * 4 +
+ *              2 * py + px covers output pixels (2 sy + py, 2 sx + px) of source tile (ty, tx); else 1), mode (0 exact,
+ *              1 one ragged tile, 2 ragged tiles), foldable (0 / 1), tiles (= tiles_x * tiles_y * phase multiplier)
+ *   GroupNorm  groups, eps, gamma / beta HOST [Cout], premul device [B][Cout] or NULL (statistics of y * premul)
+ *   ss_out     device [B][Cout][2] or NULL: merge form (a)
+ *   consumer   merge form (b), when w2_host != NULL: y2 = conv2(act_in2(GroupNorm(y))) + bias2, a stride-1 "same"
+ *              convolution [Cout2,Cout,ksize2,ksize2] with the producer's padding modes, its GroupNorm
+ *              arguments set as the planner sets them; variant2 11 / 13 (3x3) or 7 (streaming 1x1), | 0x100 exactly when
+ *              the producer stores OCT8 (3x3 consumers only: the 1x1 kernel reads planar tensors); act_in2 0 / 1.  Refused
+ *              where the rule says the merge cannot be folded. */
+typedef struct lns_conv_gn_args {
+    const float* x; int B, Cin, Hin, Win, Hv, Wv;
+    const float* w_host; const float* bias_host; int Cout, ksize, stride, dilation, pad_t, pad_b, pad_l, pad_r, mode_y, mode_x;
+    const float* ss; int act_in, act_out; const float* residual; const float* badd; float* y; int tile_variant;
+    float* part_out; const float* part_in; int* geom;
+    int groups; float eps; const float* gamma_host; const float* beta_host; const float* premul;
+    float* ss_out;
+    const float* w2_host; const float* bias2_host; int Cout2, ksize2, act_in2, variant2; float* y2;
+} lns_conv_gn_args;
+int lns_op_conv_gn(const lns_conv_gn_args* args, void* stream);
 /* Diagnostic: runs two convolutions (GroupNorm+Swish prologue, circular padding, stride 1) repeatedly on two HIP
  * streams so that their workgroups share compute units, and counts output words that differ from what each
  * convolution produces alone.  variant_*: tile variant as in lns_op_conv2d (-1 automatic, 6 = bf16x3 3x3 kernel). */

@@ -117,6 +117,21 @@ class LnsUpdateSpec(ctypes.Structure):
     ]
 
 
+def _fields(spec):
+    """"x:p B:i eps:f ..." -> ctypes fields (p pointer, i int, f float)."""
+    kinds = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float}
+    return [(n, kinds[k]) for n, k in (t.split(":") for t in spec.split())]
+
+
+class LnsConvGnArgs(ctypes.Structure):
+    """Mirror of `struct lns_conv_gn_args` (include/lns.h): the arguments of lns_op_conv_gn."""
+    _fields_ = _fields(
+        "x:p B:i Cin:i Hin:i Win:i Hv:i Wv:i w_host:p bias_host:p Cout:i ksize:i stride:i dilation:i pad_t:i pad_b:i pad_l:i "
+        "pad_r:i mode_y:i mode_x:i ss:p act_in:i act_out:i residual:p badd:p y:p tile_variant:i part_out:p part_in:p geom:p "
+        "groups:i eps:f gamma_host:p beta_host:p premul:p ss_out:p w2_host:p bias2_host:p Cout2:i ksize2:i "
+        "act_in2:i variant2:i y2:p")
+
+
 # every symbol include/lns.h declares (tests check the library exports them all)
 SYMBOLS = [
     "lns_create_error", "lns_create", "lns_destroy", "lns_last_error", "lns_num_params",
@@ -138,7 +153,7 @@ SYMBOLS = [
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
     "lns_op_conv_wgrad_scratch_bytes", "lns_op_conv_wgrad",
     "lns_op_groupnorm_train", "lns_op_gelu_grad", "lns_op_bias_grad",
-    "lns_op_conv2d", "lns_op_conv_pair_stress", "lns_op_groupnorm_stats", "lns_op_attention", "lns_op_fa_sandwich", "lns_op_fa_pool", "lns_op_fourier_block",
+    "lns_op_conv2d", "lns_op_conv_gn", "lns_op_conv_pair_stress", "lns_op_groupnorm_stats", "lns_op_attention", "lns_op_fa_sandwich", "lns_op_fa_pool", "lns_op_fourier_block",
     "lns_fourier_block_create", "lns_fourier_block_forward", "lns_fourier_block_destroy", "lns_metric_rel_l2", "lns_metric_rel_l2_ch",
 ]
 
@@ -273,6 +288,8 @@ def lib():
     L.lns_timing_mfma_flops.argtypes = [vp, i, c.POINTER(c.c_double)]
     L.lns_op_conv2d.argtypes = [vp, i, i, i, i, i, i, vp, vp, i, i, i, i, i, i, i, i, i, i,
                                 vp, i, i, vp, vp, vp, i, vp, vp]
+    if hasattr(L, "lns_op_conv_gn"):
+        L.lns_op_conv_gn.argtypes = [c.POINTER(LnsConvGnArgs), vp]
     if hasattr(L, "lns_op_conv_wgrad"):
         L.lns_op_conv_wgrad_scratch_bytes.argtypes = [i, i, i, i, i, i, i, c.POINTER(c.c_size_t)]
         L.lns_op_conv_wgrad.argtypes = [vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, vp, c.c_size_t, vp]

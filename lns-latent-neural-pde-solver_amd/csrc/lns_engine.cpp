@@ -191,6 +191,70 @@ static bool conv_geometry(ConvGeom& g, int B, int Cout, int Hv, int Wv, int k, i
 }
 
 // ---------------------------------------------------------------------------
+// GroupNorm fed by the tile statistics of the convolution that produced its input: which producers leave per-tile
+// (mean, M2) partials in their epilogue (ConvArgs::stat_part), over which pixel counts, and whether the merge can be
+// folded into the consumer's prologue.  One rule for Planner::emit_gn and the op-level entry point lns_op_conv_gn, so that
+// the latter tests the decision itself.  Layer-static (never a function of the batch beyond the scratch capacity).
+// ---------------------------------------------------------------------------
+enum { GN_TILES_EXACT = 0, GN_TILES_RAGGED1 = 1, GN_TILES_RAGGEDN = 2 };
+struct GnTileRule {
+    int mode;              // GN_TILES_*
+    int tiles;             // partials per (sample, channel); the phase form of an upsampling conv: four per source tile
+    int stat_count;        // ConvArgs::stat_count of the producer: 0, H * W (one ragged tile) or -1 (ragged tiles)
+    int gn_count;          // pixels behind every partial: GN_TILE_PIXELS, H * W, or -1 (unequal: `geom`)
+    GnTileGeom geom;       // mode GN_TILES_RAGGEDN only
+    bool foldable;         // the merge may run in a split-operand consumer's prologue (ConvArgs::gn_part)
+};
+// c / variant: the producing convolution as emitted; H, W: the plane the GroupNorm sees (c.Cout channels); premul: the norm
+// has a per-sample channel multiplier; stat_cap: bytes of the partials scratch.  False: no tile statistics for this pair.
+static bool gn_tile_rule(GnTileRule& r, const ConvArgs& c, int variant, int H, int W, int groups, bool premul, int B, size_t stat_cap) {
+    // From 16 x 16 planes up (two 128-pixel tiles): below 1024 pixels the merge launch used to cost what the statistics
+    // launch cost, but the merge now happens inside the consumer convolution (no launch at all) whenever it can.
+    static const bool no_fold = getenv("LNS_GN_NO_FOLD") != nullptr;        // A/B knob: round 2's behaviour
+    static const long min_hw = getenv("LNS_GN_FUSE_MIN_HW") ? atol(getenv("LNS_GN_FUSE_MIN_HW")) : (no_fold ? 1024 : 256);
+    // producers with the statistics epilogue: the split-operand 3x3 kernels and the streaming 1x1 kernel (not its
+    // input-stationary form, not with a fused second conv: its statistics would be taken of the wrong tensor... they
+    // are taken of what is stored, which is right -- but only the plain form is covered by tests:
+    // tests/test_conv_gn_stats_gpu.py through lns_op_conv_gn)
+    // Planes below 128 pixels (the 7 x 15 latents of the two-phase models) are ONE ragged tile: its epilogue takes exact
+    // two-pass statistics over the valid pixels (ConvArgs::stat_count) -- the three statistics launches per conditional
+    // block were a quarter of config 4's dependency chain.  A per-sample channel multiplier (premul) is applied
+    // to the partials by whoever merges them.
+    static const bool no_ragged = getenv("LNS_GN_NO_RAGGED") != nullptr;
+    const bool ragged1 = !no_fold && !no_ragged && !c.up2 && c.tiles_x * c.tiles_y == 1 && H * W < GN_TILE_PIXELS;
+    // ... and planes whose 128-pixel tiles do not cover them exactly (14 x 30, 28 x 60, 61 x 121 in the two-phase decoder):
+    // every block counts its own valid pixels, the finalize kernel merges partials of unequal counts (never folded)
+    static const bool no_ragged_tiles = getenv("LNS_GN_NO_RAGGED_TILES") != nullptr;
+    const bool raggedN = !no_fold && !no_ragged && !no_ragged_tiles && !c.up2 && !ragged1 && H * W > GN_TILE_PIXELS;
+    const bool prod_ok = variant == CV_F64 || variant == CV_F32 || variant == CV_B64 ||
+                         (variant == CV_B1 && !no_fold && c.ct_per_block == 0 && !c.w2 &&
+                          ((H * W) % GN_TILE_PIXELS == 0 || ragged1 || raggedN));
+    if (!((!premul || ragged1 || raggedN) && prod_ok && ((long)H * W >= min_hw || ragged1))) return false;
+    const int BW = 1 << c.bw_log2, BH = GN_TILE_PIXELS / BW;
+    // (phase form of an upsampling conv: tiles are SOURCE tiles, each computed for four output phases)
+    const int um = c.up2 ? 2 : 1;
+    const int tiles = c.tiles_x * c.tiles_y * (c.up2 ? 4 : 1);
+    // the 128-pixel tiles cover the plane exactly (1x1: tiles of 128 consecutive pixels)
+    const bool exact = c.ks == 1 ? (c.tiles_x * GN_TILE_PIXELS == H * W && c.tiles_y == 1)
+                                 : (c.tiles_x * BW * um == W && c.tiles_y * BH * um == H);
+    if (!(exact || ragged1 || raggedN) || (size_t)B * tiles * c.Cout * 8 > stat_cap) return false;
+    // foldable into the consumer's prologue: few tiles, one group or power-of-two groups within a wave
+    const int cg = c.Cout / groups;
+    static const int fold_tiles = getenv("LNS_GN_FOLD_TILES") ? atoi(getenv("LNS_GN_FOLD_TILES")) : 2;
+    // (a per-sample channel multiplier is applied by stage_ss_from_partials in its one-group branch only:
+    //  with several groups the finalize kernel, which handles premul for any grouping, runs instead)
+    r.foldable = !no_fold && (exact || ragged1) && tiles <= fold_tiles && c.Cout <= 512 && (!premul || groups == 1) &&
+                 (groups == 1 || (cg <= 64 && (cg & (cg - 1)) == 0));
+    r.tiles = tiles;
+    r.mode = ragged1 ? GN_TILES_RAGGED1 : (exact ? GN_TILES_EXACT : GN_TILES_RAGGEDN);
+    r.stat_count = ragged1 ? H * W : (exact ? 0 : -1);
+    r.gn_count = ragged1 ? H * W : (exact ? GN_TILE_PIXELS : -1);
+    r.geom = GnTileGeom{0, 0, 0, 0, 0};
+    if (r.mode == GN_TILES_RAGGEDN) r.geom = GnTileGeom{c.tiles_x, c.bw_log2, H, W, c.ks == 1 ? 1 : 0};
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // arena allocator for plan temporaries (offsets into the caller's workspace)
 // ---------------------------------------------------------------------------
 struct Arena {
@@ -389,11 +453,7 @@ struct Planner {
         x.gn_bound = (vg >= 0 ? vec_absmax(vg) : 1.0f) * sqrtf((float)(x.C / groups) * x.H * x.W) + (vb >= 0 ? vec_absmax(vb) : 0.0f);
         // Fed by the 3x3 split-operand kernel right before it (nothing in between but traces), 128-pixel tiles
         // covering the plane exactly: the conv epilogue leaves per-tile (mean, M2) and this op only merges them.
-        // Layer-static decision, so results do not depend on the batch.
-        // From 16 x 16 planes up (two 128-pixel tiles): below 1024 pixels the merge launch used to cost what the statistics
-        // launch cost, but the merge now happens inside the consumer convolution (no launch at all) whenever it can.
-        static const bool no_fold = getenv("LNS_GN_NO_FOLD") != nullptr;        // A/B knob: round 2's behaviour
-        static const long min_hw = getenv("LNS_GN_FUSE_MIN_HW") ? atol(getenv("LNS_GN_FUSE_MIN_HW")) : (no_fold ? 1024 : 256);
+        // Layer-static decision (gn_tile_rule), so results do not depend on the batch.
         Op* prod = nullptr;
         for (size_t i = plan->ops.size(); i-- > 0;) {
             // (traces and the conditional blocks' per-sample vector ops touch no activation tensor)
@@ -402,67 +462,28 @@ struct Planner {
             prod = &plan->ops[i];
             break;
         }
-        // producers with the statistics epilogue: the split-operand 3x3 kernels and the streaming 1x1 kernel (not its
-        // input-stationary form, not with a fused second conv: its statistics would be taken of the wrong tensor... they
-        // are taken of what is stored, which is right -- but only the plain form is covered by tests)
-        // Planes below 128 pixels (the 7 x 15 latents of the two-phase models) are ONE ragged tile: its epilogue takes exact
-        // two-pass statistics over the valid pixels (ConvArgs::stat_count) -- the three statistics launches per conditional
-        // block were a quarter of config 4's dependency chain.  A per-sample channel multiplier (premul) is applied
-        // to the partials by whoever merges them.
-        static const bool no_ragged = getenv("LNS_GN_NO_RAGGED") != nullptr;
-        const bool ragged1 = !no_fold && !no_ragged && prod && prod->type == OP_CONV && !prod->conv.up2 &&
-                             prod->conv.tiles_x * prod->conv.tiles_y == 1 && x.H * x.W < GN_TILE_PIXELS;
-        // ... and planes whose 128-pixel tiles do not cover them exactly (14 x 30, 28 x 60, 61 x 121 in the two-phase decoder):
-        // every block counts its own valid pixels, the finalize kernel merges partials of unequal counts (never folded)
-        static const bool no_ragged_tiles = getenv("LNS_GN_NO_RAGGED_TILES") != nullptr;
-        const bool raggedN = !no_fold && !no_ragged && !no_ragged_tiles && prod && prod->type == OP_CONV && !prod->conv.up2 && !ragged1 &&
-                             x.H * x.W > GN_TILE_PIXELS;
-        const bool prod_ok = prod && prod->type == OP_CONV &&
-                             (prod->variant == CV_F64 || prod->variant == CV_F32 || prod->variant == CV_B64 ||
-                              (prod->variant == CV_B1 && !no_fold && prod->conv.ct_per_block == 0 && !prod->conv.w2 &&
-                               ((x.H * x.W) % GN_TILE_PIXELS == 0 || ragged1 || raggedN)));
-        if (stat_scratch && (!premul || ragged1 || raggedN) && prod_ok &&
-            prod->conv.y == as_ptr<float>(x.ptr) && prod->conv.Cout == x.C && ((long)x.H * x.W >= min_hw || ragged1)) {
-            const ConvArgs& c = prod->conv;
-            const int BW = 1 << c.bw_log2, BH = GN_TILE_PIXELS / BW;
-            // (phase form of an upsampling conv: tiles are SOURCE tiles, each computed for four output phases)
-            const int um = c.up2 ? 2 : 1;
-            const int tiles = c.tiles_x * c.tiles_y * (c.up2 ? 4 : 1);
-            // the 128-pixel tiles cover the plane exactly (1x1: tiles of 128 consecutive pixels)
-            const bool exact = c.ks == 1 ? (c.tiles_x * GN_TILE_PIXELS == x.H * x.W && c.tiles_y == 1)
-                                         : (c.tiles_x * BW * um == x.W && c.tiles_y * BH * um == x.H);
-            if ((exact || ragged1 || raggedN) && (size_t)B * tiles * x.C * 8 <= stat_cap) {
-                // foldable into the consumer's prologue: few tiles, one group or power-of-two groups within a wave
-                const int cg = x.C / groups;
-                static const int fold_tiles = getenv("LNS_GN_FOLD_TILES") ? atoi(getenv("LNS_GN_FOLD_TILES")) : 2;
-                // (a per-sample channel multiplier is applied by stage_ss_from_partials in its one-group branch only:
-                //  with several groups the finalize kernel, which handles premul for any grouping, runs instead)
-                const bool foldable = !no_fold && (exact || ragged1) && tiles <= fold_tiles && x.C <= 512 && (!premul || groups == 1) &&
-                                      (groups == 1 || (cg <= 64 && (cg & (cg - 1)) == 0));
-                const int li = (int)lazy_ops.size();
-                lazy_done.push_back(0); lazy_folded.push_back(0);
-                const uint64_t region = take_stat_region(name, li);
-                prod->conv.stat_part = as_ptr<float>(region);
-                op.gn_tile_part = as_ptr<const float>(region);
-                op.gn_tiles = tiles;
-                op.gn_count = ragged1 ? x.H * x.W : GN_TILE_PIXELS;
-                if (ragged1) prod->conv.stat_count = x.H * x.W;
-                if (!exact && !ragged1) {       // raggedN
-                    op.gn_count = -1;
-                    op.gn_geom = GnTileGeom{c.tiles_x, c.bw_log2, x.H, x.W, c.ks == 1 ? 1 : 0};
-                    prod->conv.stat_count = -1;
-                }
-                // a batch-chunked producer: every chunk's launch leaves the partials of its own samples
-                if (prod->chunk_group > 0)
-                    for (Op& o : plan->ops)
-                        if (o.type == OP_CONV && o.chunk_group == prod->chunk_group) {
-                            o.conv.stat_part = prod->conv.stat_part; o.conv.stat_count = prod->conv.stat_count;
-                        }
-                op.bytes = 2.0 * B * tiles * x.C * 8;
-                lazy_ops.push_back(op);
-                if (foldable) { x.gn_lazy = li; return; }
-                lazy_done[li] = 1;                       // finalize right away (below)
-            }
+        GnTileRule r;
+        if (stat_scratch && prod && prod->type == OP_CONV && prod->conv.y == as_ptr<float>(x.ptr) && prod->conv.Cout == x.C &&
+            gn_tile_rule(r, prod->conv, prod->variant, x.H, x.W, groups, premul != 0, B, stat_cap)) {
+            const int li = (int)lazy_ops.size();
+            lazy_done.push_back(0); lazy_folded.push_back(0);
+            const uint64_t region = take_stat_region(name, li);
+            prod->conv.stat_part = as_ptr<float>(region);
+            op.gn_tile_part = as_ptr<const float>(region);
+            op.gn_tiles = r.tiles;
+            op.gn_count = r.gn_count;
+            if (r.mode == GN_TILES_RAGGEDN) op.gn_geom = r.geom;
+            if (r.mode != GN_TILES_EXACT) prod->conv.stat_count = r.stat_count;
+            // a batch-chunked producer: every chunk's launch leaves the partials of its own samples
+            if (prod->chunk_group > 0)
+                for (Op& o : plan->ops)
+                    if (o.type == OP_CONV && o.chunk_group == prod->chunk_group) {
+                        o.conv.stat_part = prod->conv.stat_part; o.conv.stat_count = prod->conv.stat_count;
+                    }
+            op.bytes = 2.0 * B * r.tiles * x.C * 8;
+            lazy_ops.push_back(op);
+            if (r.foldable) { x.gn_lazy = li; return; }
+            lazy_done[li] = 1;                       // finalize right away (below)
         }
         plan->ops.push_back(op);
     }
@@ -2869,6 +2890,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "eval_spectrum")) return 1;
     if (!strcmp(feature, "eval_stats")) return 1;
     if (!strcmp(feature, "eval_maps")) return 1;
+    if (!strcmp(feature, "op_conv_gn")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else
@@ -2888,6 +2910,7 @@ struct OpConv {
     float* dw = nullptr;
     int* dmaps = nullptr;
     unsigned* damax = nullptr;     // [B] running max |x| of the input (dynamic activation scale of the split kernels)
+    bool defer_amax = false;       // op_conv_prepare launches nothing: the caller runs op_conv_amax after its own checks
     void release() { (void)hipFree(dw); (void)hipFree(dmaps); (void)hipFree(damax); dw = nullptr; dmaps = nullptr; damax = nullptr; }
 };
 
@@ -2986,8 +3009,10 @@ static int op_conv_prepare(OpConv& oc, const float* x, int B, int Cin, int Hin, 
     OPCHK(hipMalloc(reinterpret_cast<void**>(&oc.damax), (size_t)B * LNS_AMAX_SUB * 4));
     // (on the CALLER's stream: x may still be being produced there, and a non-blocking stream does not order with the
     //  null stream -- a maximum taken too early would give a scale that overflows fp16)
-    OPCHK(hipMemsetAsync(oc.damax, 0, (size_t)B * LNS_AMAX_SUB * 4, stream));
-    OPCHK(launch_amax(x, a.x_bs, (long)Cin * Hin * Win, B, oc.damax, stream));
+    if (!oc.defer_amax) {
+        OPCHK(hipMemsetAsync(oc.damax, 0, (size_t)B * LNS_AMAX_SUB * 4, stream));
+        OPCHK(launch_amax(x, a.x_bs, (long)Cin * Hin * Win, B, oc.damax, stream));
+    }
     a.amax_in = oc.damax;
     a.kc_log2 = g.sel_kc_log2; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.cout_tiles = g.cout_tiles;
     a.bw_log2 = g.bw_log2; a.PH = g.PH; a.PW = g.PW; a.B = B;
@@ -3037,6 +3062,103 @@ int lns_op_conv2d(const float* x, int B, int Cin, int Hin, int Win, int Hv, int 
     OPCHK(launch_conv(oc.variant, oc.a, s));
     OPCHK(hipStreamSynchronize(s));
     oc.release();
+    return LNS_OK;
+}
+
+// GroupNorm from the tile statistics of its producer (include/lns.h): producer convolution with ConvArgs::stat_part set by
+// gn_tile_rule -- the rule Planner::emit_gn applies --, then the finalize kernel and / or a consumer convolution whose
+// prologue merges the partials, its arguments set as Planner::emit_conv sets them.  Nothing is launched before the last check.
+int lns_op_conv_gn(const lns_conv_gn_args* p, void* stream) {
+    auto bad = [](const std::string& m) { g_create_error = "conv_gn: " + m; return (int)LNS_EINVAL; };
+    if (!p) return bad("args is null");
+    if (!p->x || !p->w_host || !p->y) return bad("x / w_host / y is null");
+    if (p->B < 1 || p->B > LNS_MAX_BATCH || p->Cout < 1 || p->groups < 1 || p->Cout % p->groups != 0)
+        return bad("B in 1..65535, groups a divisor of Cout");
+    if (!(p->eps > 0.0f) || !std::isfinite(p->eps)) return bad("eps must be positive and finite");
+    const bool consumer = p->w2_host != nullptr;
+    if (consumer && (!p->y2 || p->Cout2 < 1 || (p->ksize2 != 1 && p->ksize2 != 3)))
+        return bad("the consumer needs y2, Cout2 >= 1, ksize2 1 or 3");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int B = p->B, C = p->Cout;
+    OpConv prod, cons;
+    prod.defer_amax = cons.defer_amax = true;
+    float* dbuf = nullptr;                      // partials [B][tiles][C][2], gamma [C], beta [C]
+    auto done = [&](int rc) { prod.release(); cons.release(); (void)hipFree(dbuf); return rc; };
+    int rc = op_conv_prepare(prod, p->x, B, p->Cin, p->Hin, p->Win, p->Hv, p->Wv, p->w_host, p->bias_host, C, p->ksize, p->stride,
+                             p->dilation, p->pad_t, p->pad_b, p->pad_l, p->pad_r, p->mode_y, p->mode_x, p->ss, p->act_in, p->act_out,
+                             p->residual, p->badd, p->y, p->tile_variant, s);
+    if (rc) return done(rc == LNS_EINVAL ? bad("no such producer convolution (lns_op_conv2d's rules)") : rc);
+    const int H = prod.a.Hout, W = prod.a.Wout;
+    if (prod.a.up2 >= 2 || prod.a.w8 == 1) return done(bad("the experimental producer forms are not covered"));
+    GnTileRule r;
+    if (!gn_tile_rule(r, prod.a, prod.variant, H, W, p->groups, p->premul != nullptr, B, ~(size_t)0))
+        return done(bad(fmt("the planner attaches no tile statistics to this producer (variant %d%s%s, %d x %d plane, %d x %d tiles%s): "
+                            "split-operand 3x3 / streaming 1x1 kernels, exact tiles from 256 pixels, ragged tiles without upsampling",
+                            prod.variant, prod.a.up2 ? ", upsampling" : "", prod.a.ct_per_block ? ", input-stationary" : "", H, W,
+                            prod.a.tiles_x, prod.a.tiles_y, p->premul ? ", premul" : "")));
+    if (consumer) {
+        if (!r.foldable)
+            return done(bad(fmt("the rule does not fold this merge into a consumer (%d partials, %d channels in %d groups%s): at most "
+                                "2 partials of exact tiles or one ragged tile, <= 512 channels, premul with one group only, channels "
+                                "per group a power of two <= 64", r.tiles, C, p->groups, p->premul ? ", premul" : "")));
+        const int v2 = p->variant2 & 0xff;
+        if (p->variant2 < 0 || (p->variant2 & ~0x1ff) || !(v2 == CV_F64 || v2 == CV_F32 || v2 == CV_B1) || (v2 == CV_B1) != (p->ksize2 == 1))
+            return done(bad("consumer: variant2 11 / 13 with ksize2 3, or 7 with ksize2 1"));
+        if (((p->variant2 & 0x100) != 0) != (prod.a.y_oct != 0))
+            return done(bad("consumer: variant2 | 0x100 exactly when the producer stores OCT8"));
+        if (prod.a.y_oct && v2 == CV_B1) return done(bad("consumer: the 1x1 kernel reads planar tensors, the producer stores OCT8"));
+        const int pd = p->ksize2 / 2;
+        rc = op_conv_prepare(cons, p->y, B, C, H, W, H, W, p->w2_host, p->bias2_host, p->Cout2, p->ksize2, 1, 1, pd, pd, pd, pd,
+                             p->mode_y, p->mode_x, nullptr, p->act_in2, ACT_NONE, nullptr, nullptr, p->y2, p->variant2, s);
+        if (rc) return done(rc == LNS_EINVAL ? bad("no such consumer convolution (lns_op_conv2d's rules)") : rc);
+        if (cons.variant != v2 || cons.a.ct_per_block) return done(bad("consumer: not the requested kernel form"));
+    }
+    // ---- every check is done ----
+    const size_t npart = (size_t)B * r.tiles * C * 2;
+    hipError_t he = hipMalloc(reinterpret_cast<void**>(&dbuf), (npart + 2 * (size_t)C) * 4);
+    if (he != hipSuccess) { done(0); OPCHK(he); }
+    float *dpart = dbuf, *dgamma = p->gamma_host ? dbuf + npart : nullptr, *dbeta = p->beta_host ? dbuf + npart + C : nullptr;
+    auto ok = [&](hipError_t e) { if (he == hipSuccess) he = e; return he == hipSuccess; };
+    if (dgamma) ok(hipMemcpy(dgamma, p->gamma_host, (size_t)C * 4, hipMemcpyHostToDevice));
+    if (dbeta) ok(hipMemcpy(dbeta, p->beta_host, (size_t)C * 4, hipMemcpyHostToDevice));
+    if (p->geom) {
+        const int g8[8] = {prod.a.tiles_x, prod.a.tiles_y, prod.a.bw_log2, prod.a.ks == 1 ? 1 : 0, prod.a.up2 ? 4 : 1, r.mode, r.foldable ? 1 : 0, r.tiles};
+        memcpy(p->geom, g8, sizeof g8);
+    }
+    // an entry the epilogue does not write stays NaN
+    ok(hipMemsetAsync(dpart, 0xFF, npart * 4, s));
+    ok(hipMemsetAsync(prod.damax, 0, (size_t)B * LNS_AMAX_SUB * 4, s));
+    if (he == hipSuccess) ok(launch_amax(p->x, prod.a.x_bs, prod.a.x_bs, B, prod.damax, s));
+    prod.a.stat_part = dpart; prod.a.stat_count = r.stat_count;
+    if (he == hipSuccess) ok(launch_conv(prod.variant, prod.a, s));
+    if (p->part_out) ok(hipMemcpyAsync(p->part_out, dpart, npart * 4, hipMemcpyDeviceToDevice, s));
+    const float* merge = p->part_in ? p->part_in : dpart;
+    if (p->ss_out && he == hipSuccess) {
+        GnStatsArgs g;
+        memset(&g, 0, sizeof g);
+        g.C = C; g.HW = H * W; g.groups = p->groups; g.eps = p->eps; g.gamma = dgamma; g.beta = dbeta; g.premul = p->premul;
+        g.ss = p->ss_out; g.B = B;
+        ok(launch_gn_tile_finalize(g, merge, r.tiles, r.gn_count < 0 ? 0 : r.gn_count, r.geom, s));
+    }
+    if (consumer && he == hipSuccess) {
+        ConvArgs& a = cons.a;                   // Planner::emit_conv, the lazy-GroupNorm branch
+        a.ss = nullptr;
+        a.gn_part = merge; a.gn_tiles = r.tiles; a.gn_groups = p->groups; a.gn_eps = p->eps;
+        a.gn_count = r.gn_count == GN_TILE_PIXELS ? 0 : r.gn_count; a.gn_premul = p->premul;
+        a.gn_gamma = dgamma; a.gn_beta = dbeta;
+        // the GroupNorm output's bound, a layer constant (Planner::emit_gn): |gamma| sqrt(n_group) + |beta|
+        float gmax = p->gamma_host ? 0.0f : 1.0f, bmax = 0.0f;
+        for (int c = 0; c < C; ++c) {
+            if (p->gamma_host) gmax = std::max(gmax, fabsf(p->gamma_host[c]));
+            if (p->beta_host) bmax = std::max(bmax, fabsf(p->beta_host[c]));
+        }
+        a.amax_in = nullptr; a.amax_in_const = gmax * sqrtf((float)(C / p->groups) * H * W) + bmax; a.bound_final = 1;
+        ok(launch_conv(cons.variant, a, s));
+    }
+    const hipError_t hs = hipStreamSynchronize(s);
+    ok(hs);
+    done(0);
+    OPCHK(he);
     return LNS_OK;
 }
 
