@@ -559,6 +559,86 @@ int lns_rollout_latent_eval_maps(lns_engine* e, const float* z_in, const float* 
                                  const int* keep_steps_host, int n_keep, float* frames_out, float* z_last,
                                  void* workspace, size_t workspace_bytes, void* stream, const lns_eval_select* sel);
 
+/* ---- error attribution: the rollout error split into the autoencoder's floor and the propagator's drift ------------
+ * An LNS model is two separately trained parts.  The validation error of predict does not say which of them to retrain:
+ * that needs the reconstruction r_t = D(E(y_t)) of the truth -- the floor no propagator can beat, which the reference scores
+ * in the validation loop of every stage-1 script (train_stage1_ns2d.py:104-124, train_stage1_SW.py:107-110,
+ * train_stage1_twophase.py:111-114: x_hat = autoencoder(x[:, t]), denormalize, relative_lp_loss(reduce_dim=(-1, -2))) --
+ * next to the forecast yhat_t = D(f^t(E(x))) and the truth y_t, pixel by pixel.  These calls form it where the frame is
+ * decoded: beside the forecast of a decode group, the truth frames of the group are encoded, the propagated latents are
+ * compared with the encoded ones, and the encoded ones are decoded into a second frame buffer.
+ *
+ * The statement.  For a plane (b, t, c), D_c is the denormalisation of lns_eval_spec (above):
+ *     a = D_c(yhat) - D_c(r)      the propagator's error, seen through the decoder
+ *     b = D_c(r) - D_c(y)         the autoencoder's error
+ *     PP = sum a*a     RR = sum b*b     XX = sum a*b     G = sum D_c(y)^2
+ * per_channel = 0: a = (yhat - r) * std and b = (r - y) * std, as the metric forms its error; per_channel = 1: walls and clamp
+ * are applied to all three operands before the differences.  PP and XX: fp32, nothing fused, a thread of 256 adds its
+ * elements tid, tid + 256, ... ascending from 0, one by one (no float4 grouping: the bits depend on no alignment), then the
+ * wave sums and (w0 + w1) + (w2 + w3).  The G of prop and cross: D_c(y) in fp32 (product and sum rounded one by one), its
+ * square and the sum in float64 in the same order, rounded to fp32 once.  recon is what lns_metric_rel_l2{,_ch} forms for
+ * (r, y) -- the same device function, its own fp32 G: recon holds the bits of lns_metric_rel_l2(D(E(y)), y), as frame holds
+ * those of the forecast.  The metric's fp32 G is not reused for prop and cross: on a constant field (1e-12 x under a mean)
+ * all its threads round alike, it is 1.9e-7 off, and cross, linear in 1 / g, would miss max(2e-7, 3 x torch's own) by that
+ * alone; the two evaluations of the one quantity G differ by fp32 rounding, below what the identity resolves in fp32.
+ * Since (a + b) is the forecast's error, D = sum (a+b)^2 = PP + RR + 2 XX in exact arithmetic, and with g = max(G, eps):
+ *     frame^2 = prop^2 + recon^2 + cross      prop = sqrtf(PP / g)    recon = sqrtf(RR / g)    cross = (2.0f * XX) / g
+ * In exact arithmetic g is one number.  As computed, frame and recon divide by the metric's fp32 evaluation of G, prop and
+ * cross by the float64-summed one: two roundings of the same G, a few 1e-7 apart at most, so the identity holds to the fp32
+ * rounding of the four sums (tests: 2e-5 of its largest term), not to the bit.
+ * cross is signed: whether the propagator's error adds to the autoencoder's (> 0) or compensates it (< 0).
+ * The latent drift of (b, t) is latent = sqrtf(sum (z_t - E(y_t))^2 / max(sum E(y_t)^2, eps)) over the whole latent: the bits
+ * of lns_metric_rel_l2 on the stored latents viewed as [B][T][1][1][zper] with mean 0, std 1.
+ * Every column has a sequence-wise form: the sums are added over t ascending before the ratio, as the metric's finish does.
+ * One block writes each slot, no atomics: nothing depends on decode_group / decode_streams / overlap or on the chunking. */
+typedef struct lns_eval_attrib {          /* every pointer nullable; at least one set */
+    uint32_t size;                        /* sizeof(lns_eval_attrib) */
+    float *recon_frame,  *recon_seq;      /* [B,T_total,Cin], [B,Cin] */
+    float *prop_frame,   *prop_seq;
+    float *cross_frame,  *cross_seq;
+    float *latent_frame, *latent_seq;     /* [B,T_total], [B] */
+    float *z_true_out;                    /* [B,T_total,zper]: E(y_t) (written by every chunk for its steps) */
+    float *recon_frames_out;              /* [B,n_keep,Cin,Ly,Lx]: the reconstructions of keep_steps */
+} lns_eval_attrib;
+
+/* lns_rollout_eval_workspace_bytes(B), byte for byte, followed -- each part rounded up to 256 bytes -- by a second frame
+ * buffer per decode stream (the size of the first), a true-latent staging buffer [decode_group][B][zper rounded up to 4]
+ * floats per decode stream, and three more partial-sum arrays: [B]["eval_max_steps"][Cin][2] (reconstruction),
+ * [B]["eval_max_steps"][Cin][3] (PP, XX, G) and [B]["eval_max_steps"][2] (latent). */
+int lns_rollout_eval_attrib_workspace_bytes(lns_engine* e, int B, size_t* bytes);
+
+/* lns_rollout_eval / lns_rollout_latent_eval (same leading arguments, same bits in frame_out / seq_out / frames_out) with
+ * the outputs of `attrib`.  The frame- and sequence-wise columns are written by the call that completes the horizon
+ * (t0 + T == T_total); z_true_out and recon_frames_out by every call for its own steps.  Per decode group the call pays one
+ * encoder run per step at batch B (y_true is read in place through its batch stride; param goes to a conditional encoder)
+ * and one more decoder run; the truth encode does not depend on the chain and is enqueued ahead of the wait for it.
+ * Refusals (host only): those of lns_rollout_eval; then LNS_EINVAL for attrib null or attrib->size wrong, and for an attrib
+ * with no output set; LNS_ENOMEM for a workspace below lns_rollout_eval_attrib_workspace_bytes(B), with nothing enqueued.
+ * lns_check_finite after these calls: the truth encode and the reconstruction decode run in the decode arenas, where the
+ * encoder's and the decoder's records share their bytes, and the last run in every arena is a reconstruction decode.  A
+ * non-finite truth frame of the last group of a decode stream therefore shows in that decode's record (through its latent);
+ * which plan the message names is not guaranteed, and earlier groups are covered only as "track_nonfinite" covers earlier
+ * runs.  No test puts a non-finite truth frame through these calls. */
+int lns_rollout_eval_attrib(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                            const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host,
+                            int n_keep, float* frames_out, const lns_eval_attrib* attrib, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int lns_rollout_latent_eval_attrib(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                   int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                   const int* keep_steps_host, int n_keep, float* frames_out, float* z_last,
+                                   const lns_eval_attrib* attrib, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Stage-1 validation (the reference loops above): x [B,T,Cin,Ly,Lx] normalised -> frame_out [B,T,Cin], seq_out [B,Cin]
+ * (either may be NULL, not both) = lns_metric_rel_l2{,_ch}(autoencoder(x), x), bit for bit, and z_out (nullable)
+ * [B,T,zper] = E(x).  Per step: encode, decode into the frame buffer, the metric's group kernel against x itself; the finish
+ * kernel at the end; all on the caller's stream.  The reconstruction [B,T,Cin,Ly,Lx] is never stored.  param [B] (one per
+ * trajectory) goes to a conditional encoder.  No propagator is needed: LNS_ESTATE only without an autoencoder.  The workspace
+ * is the evaluation layout -- lns_rollout_eval_workspace_bytes(B) where that call answers; lns_autoencode_eval_workspace_bytes
+ * gives the same number and also serves an engine without propagator.  Refusals as lns_rollout_eval's, in its order. */
+int lns_autoencode_eval_workspace_bytes(lns_engine* e, int B, size_t* bytes);
+int lns_autoencode_eval(lns_engine* e, const float* x, const float* param, int B, int T, const lns_eval_spec* spec,
+                        float* frame_out, float* seq_out, float* z_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Post-run health check.  Every kernel of a plan records, per sample, the running maximum of |y| of the tensor it
  * produces (the side channel from which the split-operand convolutions derive their activation scale); a NaN or inf
  * anywhere in a tensor survives in it.  This call synchronises `stream`, reads those few KB back from `workspace`
@@ -750,7 +830,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * lns_op_energy_spectrum and lns_spectrum_bins are there; "eval_stats" = lns_rollout_eval_stats,
  * lns_rollout_latent_eval_stats and lns_op_field_stats are there; "eval_maps" = lns_rollout_eval_maps,
  * lns_rollout_latent_eval_maps, their size query, lns_op_time_maps and lns_time_maps_state_bytes are there;
- * "op_conv_gn" = lns_op_conv_gn is there.
+ * "op_conv_gn" = lns_op_conv_gn is there; "eval_attrib" = lns_rollout_eval_attrib, lns_rollout_latent_eval_attrib, their
+ * size query, lns_autoencode_eval, its size query, lns_op_eval_attrib and lns_op_latent_err are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
@@ -884,6 +965,22 @@ int lns_op_field_stats(const float* yhat, const float* y, int B, int T, int C, i
 int lns_time_maps_state_bytes(int B, int C, int H, int W, size_t* bytes);
 int lns_op_time_maps(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
                      int map_from, int map_every, float* maps_out, void* state, size_t state_bytes, void* stream);
+
+/* The attribution kernels of lns_rollout_eval_attrib on stored fields, without an engine: yhat (forecast), r (reconstruction
+ * of the truth) and y [B][T][C][H][W], normalised -> prop_frame / cross_frame [B][T][C], prop_seq / cross_seq [B][C] (each
+ * nullable, at least one set).  The per-plane body and the finish kernel are the streaming call's.
+ * Scratch: the partial sums (3 B T C floats) are allocated by the call with hipMalloc and freed before it returns.  H * W <= 2^30, B * T * C < 2^31; the per-channel form
+ * needs C <= 8.  Checks precede the launches (message: lns_create_error()); the call synchronises `stream`. */
+int lns_op_eval_attrib(const float* yhat, const float* r, const float* y, int B, int T, int C, int H, int W,
+                       const lns_eval_spec* spec, float* prop_frame, float* prop_seq, float* cross_frame, float* cross_seq,
+                       void* stream);
+
+/* The latent-drift kernel of lns_rollout_eval_attrib on one stored group, without an engine: z [T][B][zper] (a ring group's
+ * layout, any alignment) against ztrue [T][B][zstride] (zstride a multiple of 4 floats >= zper, ztrue 16-byte aligned) ->
+ * frame_out [B][T], seq_out [B] (either nullable): the bits of lns_metric_rel_l2 on the latents stored as [B][T][1][1][zper]
+ * with mean 0, std 1.  Scratch (2 B T floats) is allocated and freed by the call; it synchronises `stream`. */
+int lns_op_latent_err(const float* z, const float* ztrue, int B, int T, int zper, int64_t zstride, float eps, float* frame_out,
+                      float* seq_out, void* stream);
 
 /* GroupNorm statistics -> per-(b,c) (scale,shift) such that norm(x) = x*scale+shift. */
 int lns_op_groupnorm_stats(const float* x, int B, int C, int HW, int groups, float eps,

@@ -93,6 +93,13 @@ class LnsEvalSelect(ctypes.Structure):
     ]
 
 
+class LnsEvalAttrib(ctypes.Structure):
+    """Mirror of `struct lns_eval_attrib` (include/lns.h): the outputs of the error attribution, every pointer nullable."""
+    OUTPUTS = ("recon_frame", "recon_seq", "prop_frame", "prop_seq", "cross_frame", "cross_seq", "latent_frame", "latent_seq",
+               "z_true_out", "recon_frames_out")
+    _fields_ = [("size", ctypes.c_uint32)] + [(n, ctypes.c_void_p) for n in OUTPUTS]
+
+
 LNS_SL1_CHUNK = 4096
 
 
@@ -145,6 +152,8 @@ SYMBOLS = [
     "lns_rollout_eval_stats", "lns_rollout_latent_eval_stats", "lns_op_field_stats",
     "lns_rollout_eval_maps_workspace_bytes", "lns_rollout_eval_maps", "lns_rollout_latent_eval_maps",
     "lns_time_maps_state_bytes", "lns_op_time_maps",
+    "lns_rollout_eval_attrib_workspace_bytes", "lns_rollout_eval_attrib", "lns_rollout_latent_eval_attrib",
+    "lns_autoencode_eval_workspace_bytes", "lns_autoencode_eval", "lns_op_eval_attrib", "lns_op_latent_err",
     "lns_train_workspace_bytes", "lns_train_forward", "lns_train_backward",
     "lns_loss_smooth_l1", "lns_adam_step", "lns_adam_step_tensors", "lns_train_step_workspace_bytes", "lns_train_step",
     "lns_grad_norm_scratch_bytes", "lns_grad_norm_tensors", "lns_grad_scale_tensors", "lns_update_step_tensors",
@@ -253,6 +262,15 @@ def lib():
         L.lns_rollout_latent_eval_maps.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, vp, c.c_size_t, vp, qp]
         L.lns_time_maps_state_bytes.argtypes = [i, i, i, i, c.POINTER(c.c_size_t)]
         L.lns_op_time_maps.argtypes = [vp, vp, i, i, i, i, i, sp, i, i, vp, vp, c.c_size_t, vp]
+    if hasattr(L, "lns_rollout_eval_attrib"):
+        sp, ip, ap = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.POINTER(LnsEvalAttrib)
+        L.lns_rollout_eval_attrib_workspace_bytes.argtypes = [vp, i, c.POINTER(c.c_size_t)]
+        L.lns_rollout_eval_attrib.argtypes = [vp, vp, vp, vp, i, i, sp, vp, vp, ip, i, vp, ap, vp, c.c_size_t, vp]
+        L.lns_rollout_latent_eval_attrib.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, ap, vp, c.c_size_t, vp]
+        L.lns_autoencode_eval_workspace_bytes.argtypes = [vp, i, c.POINTER(c.c_size_t)]
+        L.lns_autoencode_eval.argtypes = [vp, vp, vp, i, i, sp, vp, vp, vp, vp, c.c_size_t, vp]
+        L.lns_op_eval_attrib.argtypes = [vp, vp, vp, i, i, i, i, i, sp, vp, vp, vp, vp, vp]
+        L.lns_op_latent_err.argtypes = [vp, vp, i, i, i, c.c_int64, c.c_float, vp, vp, vp]
     if hasattr(L, "lns_check_finite"):      # (absent from older builds loaded through LNS_HIP_LIB for A/B runs)
         L.lns_check_finite.argtypes = [vp, i, vp, c.c_size_t, vp]
     if hasattr(L, "lns_set_option"):

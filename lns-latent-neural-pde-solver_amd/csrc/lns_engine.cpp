@@ -1785,6 +1785,8 @@ struct WsLayout {
     size_t fbuf_off, fbuf_stride, part_off;   // SINK_SCORED; SINK_ENSEMBLE (no part)
     size_t pp_off[2];                         // SINK_KEPT, SINK_ENSEMBLE
     size_t maps_off = 0, maps_bytes = 0;      // SINK_SCORED with time maps (add_maps_region)
+    // SINK_SCORED with attribution (add_attrib_region): second frame buffers, true-latent staging, three partial-sum arrays
+    size_t fbuf2_off = 0, ztrue_off = 0, ztrue_stride = 0, part2_off = 0, ppart_off = 0, lpart_off = 0; long zstride = 0;
 };
 
 static int decode_group(const lns_engine* e, int B) {
@@ -1854,6 +1856,24 @@ static void add_maps_region(const lns_engine* e, int B, WsLayout* L) {
     L->total = L->maps_off + L->maps_bytes;
 }
 
+// The region of the error attribution (lns_rollout_eval_attrib), behind the SINK_SCORED layout, which it leaves byte for byte
+// as it is: per decode stream a second frame buffer (the reconstruction of the group's truth frames) and a staging buffer
+// [kdec][B][zstride] of their latents (zstride: zper rounded up to four floats, so that every slot is 16-byte aligned), then
+// the partial sums of the reconstruction [B][eval_max_steps][C][2], (PP, XX, G) [B][eval_max_steps][C][3] and the latent pairs
+// [B][eval_max_steps][2].
+static void add_attrib_region(const lns_engine* e, int B, WsLayout* L) {
+    const size_t zper = (size_t)std::max(1, e->lat_C) * std::max(1, e->lat_H) * std::max(1, e->lat_W);
+    const size_t planes = round_up_sz((size_t)B * e->opt_eval_max_steps * e->cfg.in_channels * 2 * 4, 256);
+    L->zstride = (long)((zper + 3) / 4 * 4);
+    L->fbuf2_off = round_up_sz(L->total, 256);
+    L->ztrue_off = L->fbuf2_off + (size_t)L->ndec * L->fbuf_stride;
+    L->ztrue_stride = round_up_sz((size_t)L->kdec * B * L->zstride * 4, 256);
+    L->part2_off = L->ztrue_off + (size_t)L->ndec * L->ztrue_stride;
+    L->ppart_off = L->part2_off + planes;
+    L->lpart_off = L->ppart_off + round_up_sz((size_t)B * e->opt_eval_max_steps * e->cfg.in_channels * 3 * 4, 256);
+    L->total = L->lpart_off + round_up_sz((size_t)B * e->opt_eval_max_steps * 2 * 4, 256);
+}
+
 // An ascending list of steps on the host -- the kept frames, the spectrum steps, the statistics steps of a call -- under
 // the name the refusals use, with the cursor of the one walk rollout_loop makes over it
 struct StepList {
@@ -1900,6 +1920,11 @@ struct RolloutCall {
     // (t - map_from) % map_every == 0 (the _maps form); sel_bad: that form's lns_eval_select was null or of the wrong size
     lns_eval_select sel = {};
     bool spectra = false, stats = false, maps = false, sel_bad = false;
+    // SINK_SCORED: the attribution outputs (the _attrib forms; include/lns.h lns_eval_attrib); at_bad: null or of the wrong size
+    lns_eval_attrib at = {};
+    bool attrib = false, at_bad = false;
+    // lns_autoencode_eval: no chain -- x [B][T] is encoded, decoded and scored against itself; only the autoencoder is needed
+    bool ae_only = false;
     StepList keep_list() const { return {keep, n_keep, "keep_steps"}; }
     StepList spectrum_list() const { return {sel.spectrum_steps_host, sel.n_spec, "spectrum_steps"}; }
     StepList stats_list() const { return {sel.stats_steps_host, sel.n_stats, "stats_steps"}; }
@@ -2392,6 +2417,22 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     TimeMapsArgs tm;
     if (scored && c.maps) time_maps_args(e, c, L, &tm);
     int maps_d = -1;                                 // the decode stream of the latest time-map accumulation of this call
+    // attribution: the encoder plan of the truth frames, the reconstruction's metric arguments, (PP, XX) and the latent pairs
+    const bool attrib = scored && c.attrib;
+    Plan* penc = nullptr;
+    MetricGroupArgs m2;
+    AttribGroupArgs ag;
+    LatentErrArgs la;
+    if (attrib) {
+        if ((rc = get_plan(e, PK_ENC, B, 0, 0, &penc))) return rc;
+        m2 = m; m2.part = reinterpret_cast<float*>(base + L.part2_off);
+        ag.frames = ag.recon = nullptr; ag.y = c.y_true; ag.part = reinterpret_cast<float*>(base + L.ppart_off);
+        ag.B = B; ag.C = m.C; ag.H = m.H; ag.W = m.W; ag.kk = 0; ag.y_T = c.T_total; ag.y_t = 0; ag.p_T = c.T_total; ag.p_t = 0;
+        ag.norm = m.norm;
+        la.z = la.ztrue = nullptr; la.part = reinterpret_cast<float*>(base + L.lpart_off);
+        la.zstride = L.zstride; la.zper = (int)zper; la.B = B; la.kk = 0; la.T_total = c.T_total; la.t = 0;
+        la.mean = 0.0f; la.sd = 1.0f;
+    }
     // A decode group is the next up to kdec DECODED steps: all steps, the kept ones, or none.  The chain writes the
     // latent of a decoded step into the group's next ring slot; the latent of a step nobody decodes goes into `out`
     // (SINK_LATENTS) or into the two ping-pong buffers in turn (SINK_KEPT, SINK_ENSEMBLE), so a step never writes the buffer it reads.
@@ -2435,9 +2476,31 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
         Plan* pd;
         if ((rc = get_plan(e, PK_DEC, B * kk, 0, 0, &pd))) return rc;
         const int d = gi % ndec;
+        Runner& rdec = overlap ? rd[d] : r;
+        float* zt = attrib ? reinterpret_cast<float*>(base + L.ztrue_off + (size_t)d * L.ztrue_stride) : nullptr;
+        if (attrib) {
+            // Truth encode: y_true[:, t0 + t0g + j] -> zt[j], read in place through the batch stride T_total * xper (every op
+            // that reads a plan's input takes its batch stride from the ExtT).  It does not depend on the chain, so it stands
+            // ahead of the wait on ev_z[g]; darena[d] and zt are this decode stream's own (stream order covers their reuse).
+            ExtT xe[EX_COUNT];
+            xe[EX_PARAM] = {c.param, 1};
+            for (int j = 0; j < kk; ++j) {
+                xe[EX_IN] = {c.y_true + (long)(c.t0 + t0g + j) * xper, (long)c.T_total * xper};
+                xe[EX_OUT] = {zt + (long)j * B * L.zstride, L.zstride};
+                if ((rc = rdec.run(*penc, xe, darena[d]))) return rc;
+                if (c.at.z_true_out)
+                    HIPCHK(e, hipMemcpy2DAsync(c.at.z_true_out + (long)(c.t0 + t0g + j) * zper, (size_t)c.T_total * zper * 4,
+                                               zt + (long)j * B * L.zstride, (size_t)L.zstride * 4, (size_t)zper * 4, B,
+                                               hipMemcpyDeviceToDevice, dstream[d]));
+            }
+        }
         if (overlap) {
             HIPCHK(e, hipEventRecord(ev_z[g], pstream));
             HIPCHK(e, hipStreamWaitEvent(dstream[d], ev_z[g], 0));
+        }
+        if (attrib) {                                // latent drift: ring group g against the staged true latents
+            la.z = reinterpret_cast<const float*>(gbase); la.ztrue = zt; la.kk = kk; la.t = c.t0 + t0g;
+            HIPCHK(e, launch_latent_err_group(la, dstream[d]));
         }
         ext[EX_IN] = {gbase, zper};
         float* fb = scored || ens ? reinterpret_cast<float*>(base + L.fbuf_off + (size_t)d * L.fbuf_stride) : nullptr;
@@ -2477,6 +2540,25 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
                     if (overlap && ndec > 1) HIPCHK(e, hipEventRecord(ev_maps[d], dstream[d]));
                     maps_d = d;
                 }
+            }
+            if (attrib) {
+                // Reconstruction: the group's true latents (the ring group's layout) through the same decode plan into the
+                // second frame buffer; the metric's group kernel gives (RR, G), the attribution kernel (PP, XX) from both buffers.
+                float* fb2 = reinterpret_cast<float*>(base + L.fbuf2_off + (size_t)d * L.fbuf_stride);
+                ExtT xr[EX_COUNT];
+                xr[EX_PARAM] = {c.param, 1};
+                xr[EX_IN] = {zt, L.zstride};
+                xr[EX_OUT] = {fb2, xper};
+                if ((rc = rdec.run(*pd, xr, darena[d]))) return rc;
+                m2.frames = fb2; m2.kk = kk; m2.y_t = c.t0 + t0g; m2.p_t = c.t0 + t0g;
+                HIPCHK(e, launch_metric_group(m2, dstream[d]));
+                ag.frames = fb; ag.recon = fb2; ag.kk = kk; ag.y_t = c.t0 + t0g; ag.p_t = c.t0 + t0g;
+                HIPCHK(e, launch_attrib_group(ag, dstream[d]));
+                if (c.at.recon_frames_out)
+                    for (int i = 0; i < nk; ++i)
+                        HIPCHK(e, hipMemcpy2DAsync(c.at.recon_frames_out + (long)(ki + i) * xper, (size_t)c.n_keep * xper * 4,
+                                                   fb2 + (long)kj[i] * B * xper, (size_t)xper * 4, (size_t)xper * 4, B,
+                                                   hipMemcpyDeviceToDevice, dstream[d]));
             }
         }
         if (ens && c.ens_scored) {                   // fb is [kk][traj][M][xper] against y_true[b][i0 .. i0 + kk)
@@ -2572,13 +2654,27 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
             return LNS_EINVAL;
         }
     }
+    if (scored && c.attrib) {
+        if (c.at_bad) return einval(e, "attrib is null or its size field is not sizeof(lns_eval_attrib)");
+        const lns_eval_attrib& a = c.at;
+        if (!a.recon_frame && !a.recon_seq && !a.prop_frame && !a.prop_seq && !a.cross_frame && !a.cross_seq && !a.latent_frame &&
+            !a.latent_seq && !a.z_true_out && !a.recon_frames_out)
+            return einval(e, "attrib: no output is set");
+    }
     if (int brc = check_batch(e, c.B)) return brc;
     if (scored && c.T_total > e->opt_eval_max_steps) {
         e->err = fmt("%d steps exceed the option eval_max_steps = %d (it sizes the evaluation workspace)", c.T_total, e->opt_eval_max_steps);
         return LNS_EINVAL;
     }
+    if (c.ae_only) {                                 // lns_autoencode_eval: the autoencoder alone, param for its encoder alone
+        if (e->enc.empty()) { e->err = "autoencode_eval needs an autoencoder"; return LNS_ESTATE; }
+        if (e->cfg.cond_encoder && !c.param) return einval(e, "conditional encoder needs param");
+        return LNS_OK;
+    }
     if (int mrc = need_model(e)) return mrc;
-    return need_param(e, c.encode, c.param);
+    if (int prc = need_param(e, c.encode, c.param)) return prc;
+    if (scored && c.attrib && e->cfg.cond_encoder && !c.param) return einval(e, "conditional encoder needs param");
+    return LNS_OK;
 }
 
 // the one call path behind the rollout entry points
@@ -2591,6 +2687,7 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     WsLayout L;
     if ((rc = ws_layout(e, c.B, c.sink, &L))) return rc;
     if (scored && c.maps) add_maps_region(e, c.B, &L);
+    if (scored && c.attrib) add_attrib_region(e, c.B, &L);
     if ((rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : (c.sink == SINK_ENSEMBLE ? "ensemble " : "")),
                        c.ws, c.ws_bytes))) return rc;
     Plan* pe = nullptr;
@@ -2618,6 +2715,18 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if (scored && c.t0 + c.T == c.T_total)
         HIPCHK(e, launch_metric_finish(reinterpret_cast<float*>(base + L.part_off), c.B, c.T_total, cfg.in_channels, c.spec->eps,
                                        c.frame_out, c.seq_out, r.stream));
+    if (scored && c.attrib && c.t0 + c.T == c.T_total) {   // likewise: the three further sum arrays -> the attribution columns
+        const lns_eval_attrib& a = c.at;
+        if (a.recon_frame || a.recon_seq)
+            HIPCHK(e, launch_metric_finish(reinterpret_cast<float*>(base + L.part2_off), c.B, c.T_total, cfg.in_channels, c.spec->eps,
+                                           a.recon_frame, a.recon_seq, r.stream));
+        if (a.prop_frame || a.prop_seq || a.cross_frame || a.cross_seq)
+            HIPCHK(e, launch_attrib_finish(reinterpret_cast<float*>(base + L.ppart_off), c.B, c.T_total, cfg.in_channels,
+                                           c.spec->eps, a.prop_frame, a.prop_seq, a.cross_frame, a.cross_seq, r.stream));
+        if (a.latent_frame || a.latent_seq)
+            HIPCHK(e, launch_metric_finish(reinterpret_cast<float*>(base + L.lpart_off), c.B, c.T_total, 1, c.spec->eps,
+                                           a.latent_frame, a.latent_seq, r.stream));
+    }
     if (scored && c.maps && c.t0 + c.T == c.T_total) {   // likewise: the state of all chunks -> the seven maps
         TimeMapsArgs tm;
         time_maps_args(e, c, L, &tm);
@@ -2632,14 +2741,18 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
 // The one body of the eight scored entry points (lns_rollout_eval, lns_rollout_latent_eval and their _spectrum / _stats /
 // _maps forms): the union of their argument lists.  From x: encode, t0 = 0, T_total = T, no z_last.  The selections come
 // loose (the _spectrum and _stats forms; all null / 0 for the plain one) or, for SCORED_MAPS, in `sel`.
-enum ScoredForm { SCORED_PLAIN, SCORED_SPECTRUM, SCORED_STATS, SCORED_MAPS };
+enum ScoredForm { SCORED_PLAIN, SCORED_SPECTRUM, SCORED_STATS, SCORED_MAPS, SCORED_ATTRIB };   // (_ATTRIB: the plain form + `attrib`)
 static int scored_call(lns_engine* e, ScoredForm form, const float* start, bool encode, const float* param, const float* y_true,
                        int B, int T, int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
                        const int* keep, int n_keep, float* frames_out, float* z_last, void* ws, size_t ws_bytes, void* stream,
                        const int* spectrum_steps, int n_spec, float* spectra_out, const int* stats_steps, int n_stats,
-                       const lns_stats_spec* hspec, float* stats_out, int32_t* hist_out, const lns_eval_select* sel) {
+                       const lns_stats_spec* hspec, float* stats_out, int32_t* hist_out, const lns_eval_select* sel,
+                       const lns_eval_attrib* attrib = nullptr) {
     RolloutCall c(start, encode, param, B, T, ws, ws_bytes, stream);
     c.sink = SINK_SCORED;
+    c.attrib = form == SCORED_ATTRIB;
+    c.at_bad = c.attrib && (!attrib || attrib->size != sizeof(lns_eval_attrib));
+    if (c.attrib && !c.at_bad) c.at = *attrib;
     c.y_true = y_true; c.t0 = t0; c.T_total = T_total; c.spec = spec; c.frame_out = frame_out; c.seq_out = seq_out;
     c.keep = keep; c.n_keep = n_keep; c.frames_out = frames_out; c.z_last = z_last;
     c.maps = form == SCORED_MAPS;
@@ -2753,6 +2866,92 @@ int lns_rollout_latent_eval_maps(lns_engine* e, const float* z_in, const float* 
     return scored_call(e, SCORED_MAPS, z_in, false, param, y_true, B, T, t0, T_total, spec, frame_out, seq_out, keep_steps_host,
                        n_keep, frames_out, z_last, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
                        sel);
+}
+
+// ---- streaming validation with error attribution (include/lns.h) --------------------------------------------------
+int lns_rollout_eval_attrib_workspace_bytes(lns_engine* e, int B, size_t* bytes) {
+    if (int rc = workspace_bytes(e, B, SINK_SCORED, nullptr)) return rc;
+    DeviceGuard dg(e);
+    WsLayout L;
+    if (int rc = ws_layout(e, B, SINK_SCORED, &L)) return rc;
+    add_attrib_region(e, B, &L);
+    if (bytes) *bytes = L.total;
+    return LNS_OK;
+}
+
+int lns_rollout_eval_attrib(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                            const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
+                            float* frames_out, const lns_eval_attrib* attrib, void* ws, size_t ws_bytes, void* stream) {
+    return scored_call(e, SCORED_ATTRIB, x, true, param, y_true, B, T, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep,
+                       frames_out, nullptr, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                       attrib);
+}
+
+int lns_rollout_latent_eval_attrib(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                   int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                   const int* keep_steps_host, int n_keep, float* frames_out, float* z_last,
+                                   const lns_eval_attrib* attrib, void* ws, size_t ws_bytes, void* stream) {
+    return scored_call(e, SCORED_ATTRIB, z_in, false, param, y_true, B, T, t0, T_total, spec, frame_out, seq_out, keep_steps_host,
+                       n_keep, frames_out, z_last, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                       nullptr, attrib);
+}
+
+// ---- stage-1 validation (include/lns.h) ---------------------------------------------------------------------------
+// the evaluation layout for an engine that may lack the propagator (ws_layout sizes a missing propagator's arena as 0)
+int lns_autoencode_eval_workspace_bytes(lns_engine* e, int B, size_t* bytes) {
+    if (!e) return LNS_EINVAL;
+    if (B <= 0) return einval(e, "B must be positive");
+    if (int brc = check_batch(e, B)) return brc;
+    if (e->enc.empty()) { e->err = "autoencode_eval needs an autoencoder"; return LNS_ESTATE; }
+    DeviceGuard dg(e);
+    WsLayout L;
+    if (int rc = ws_layout(e, B, SINK_SCORED, &L)) return rc;
+    if (bytes) *bytes = L.total;
+    return LNS_OK;
+}
+
+// x[:, t] -> z -> the frame buffer -> the metric's pair of plane (b, t, c) against x[:, t] itself, step by step on the
+// caller's stream in the first decode arena (stream order is the whole hazard argument); then the metric's finish kernel
+int lns_autoencode_eval(lns_engine* e, const float* x, const float* param, int B, int T, const lns_eval_spec* spec,
+                        float* frame_out, float* seq_out, float* z_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!e) return LNS_EINVAL;
+    RolloutCall c(x, true, param, B, T, ws, ws_bytes, stream);
+    c.sink = SINK_SCORED; c.ae_only = true;
+    c.y_true = x; c.t0 = 0; c.T_total = T; c.spec = spec; c.frame_out = frame_out; c.seq_out = seq_out;
+    int rc;
+    if ((rc = rollout_refusal(e, c))) return rc;
+    DeviceGuard dg(e);
+    WsLayout L;
+    if ((rc = ws_layout(e, B, SINK_SCORED, &L)) || (rc = check_ws(e, L, "evaluation ", ws, ws_bytes))) return rc;
+    Plan *pe, *pd;
+    if ((rc = get_plan(e, PK_ENC, B, 0, 0, &pe)) || (rc = get_plan(e, PK_DEC, B, 0, 0, &pd))) return rc;
+    const long zper = (long)e->lat_C * e->lat_H * e->lat_W;
+    const long xper = (long)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx;
+    char* base = static_cast<char*>(ws);
+    Runner r(e, static_cast<hipStream_t>(stream));
+    begin_run(e, ws, B);
+    if ((rc = arm_sticky(e, r.stream))) return rc;
+    MetricGroupArgs m;
+    metric_args(e, c, L, &m);
+    float* fb = reinterpret_cast<float*>(base + L.fbuf_off);
+    m.frames = fb; m.kk = 1;
+    ExtT ext[EX_COUNT];
+    ext[EX_PARAM] = {param, 1};
+    for (int t = 0; t < T; ++t) {
+        // the latent goes straight to its slot of z_out where the caller wants it, else to the layout's z0 buffer
+        const ExtT z = z_out ? ExtT{z_out + (long)t * zper, (long)T * zper} : ExtT{base, zper};
+        ext[EX_IN] = {x + (long)t * xper, (long)T * xper};
+        ext[EX_OUT] = z;
+        if ((rc = r.run(*pe, ext, base + L.arena_off))) return rc;
+        ext[EX_IN] = z;
+        ext[EX_OUT] = {fb, xper};
+        if ((rc = r.run(*pd, ext, base + L.arena_off))) return rc;
+        m.y_t = t; m.p_t = t;
+        HIPCHK(e, launch_metric_group(m, r.stream));
+    }
+    HIPCHK(e, launch_metric_finish(reinterpret_cast<float*>(base + L.part_off), B, T, e->cfg.in_channels, spec->eps, frame_out, seq_out,
+                                   r.stream));
+    return r.finish();
 }
 
 // ---- selected-step rollout (include/lns.h) ----------------------------------------------------------------------
@@ -2890,6 +3089,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "eval_spectrum")) return 1;
     if (!strcmp(feature, "eval_stats")) return 1;
     if (!strcmp(feature, "eval_maps")) return 1;
+    if (!strcmp(feature, "eval_attrib")) return 1;
     if (!strcmp(feature, "op_conv_gn")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
@@ -3379,6 +3579,57 @@ int lns_op_time_maps(const float* yhat, const float* y, int B, int T, int C, int
     OPCHK(launch_time_maps_stored(a, s));
     OPCHK(launch_time_maps_finish(a, s));
     OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+// attrib_group_kernel and attrib_finish_kernel of lns_rollout_eval_attrib on stored fields
+int lns_op_eval_attrib(const float* yhat, const float* r, const float* y, int B, int T, int C, int H, int W,
+                       const lns_eval_spec* spec, float* prop_frame, float* prop_seq, float* cross_frame, float* cross_seq,
+                       void* stream) {
+    if (!yhat || !r || !y) { g_create_error = "eval_attrib: yhat / r / y is null"; return LNS_EINVAL; }
+    if (!prop_frame && !prop_seq && !cross_frame && !cross_seq) { g_create_error = "eval_attrib: no output is set"; return LNS_EINVAL; }
+    if (op_spec_refused("eval_attrib", spec)) return LNS_EINVAL;
+    if (B < 1 || T < 1 || C < 1 || H < 1 || W < 1 || (int64_t)H * W > (1LL << 30) || (int64_t)B * T * C > 0x7fffffffLL) {
+        g_create_error = "eval_attrib: B, T, C, H, W >= 1, H * W <= 2^30 and B * T * C < 2^31"; return LNS_EINVAL;
+    }
+    if (op_spec_refused("eval_attrib", spec, C)) return LNS_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t planes = (size_t)B * T * C;
+    float* pp = nullptr;                             // (PP, XX, G) per plane
+    OPCHK(hipMalloc(reinterpret_cast<void**>(&pp), planes * 3 * 4));
+    float* scratch = pp;
+    AttribGroupArgs a;
+    a.frames = yhat; a.recon = r; a.y = y; a.part = pp;
+    a.B = 1; a.C = C; a.H = H; a.W = W; a.kk = B * T; a.y_T = B * T; a.y_t = 0; a.p_T = B * T; a.p_t = 0;
+    score_norm(spec, C, &a.norm);
+    hipError_t he = launch_attrib_group(a, s);
+    if (he == hipSuccess) he = launch_attrib_finish(pp, B, T, C, spec->eps, prop_frame, prop_seq, cross_frame, cross_seq, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    OPCHK(he);
+    return LNS_OK;
+}
+
+// latent_err_group_kernel of lns_rollout_eval_attrib on one stored group: z [T][B][zper] (a ring group's layout) against
+// ztrue [T][B][zstride] (the staging buffer's), then the metric's finish kernel with C = 1
+int lns_op_latent_err(const float* z, const float* ztrue, int B, int T, int zper, int64_t zstride, float eps, float* frame_out,
+                      float* seq_out, void* stream) {
+    if (!z || !ztrue || (!frame_out && !seq_out)) { g_create_error = "latent_err: z / ztrue is null, or frame_out and seq_out are"; return LNS_EINVAL; }
+    if (B < 1 || T < 1 || zper < 1 || (int64_t)B * T > 0x7fffffffLL) { g_create_error = "latent_err: B, T, zper >= 1 and B * T < 2^31"; return LNS_EINVAL; }
+    if (zstride < zper || (zstride & 3) || (reinterpret_cast<uintptr_t>(ztrue) & 15)) {
+        g_create_error = "latent_err: zstride must be a multiple of 4 floats, at least zper, and ztrue 16-byte aligned"; return LNS_EINVAL;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* part = nullptr;
+    OPCHK(hipMalloc(reinterpret_cast<void**>(&part), (size_t)B * T * 2 * 4));
+    LatentErrArgs a;
+    a.z = z; a.ztrue = ztrue; a.part = part; a.zstride = (long)zstride; a.zper = zper; a.B = B; a.kk = T; a.T_total = T; a.t = 0;
+    a.mean = 0.0f; a.sd = 1.0f;
+    hipError_t he = launch_latent_err_group(a, s);
+    if (he == hipSuccess) he = launch_metric_finish(part, B, T, 1, eps, frame_out, seq_out, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    (void)hipFree(part);
+    OPCHK(he);
     return LNS_OK;
 }
 

@@ -474,6 +474,32 @@ hipError_t launch_time_maps_group(const TimeMapsArgs& a, hipStream_t s);
 hipError_t launch_time_maps_stored(const TimeMapsArgs& a, hipStream_t s);
 hipError_t launch_time_maps_finish(const TimeMapsArgs& a, hipStream_t s);
 
+// Error attribution (lns_rollout_eval_attrib, lns_op_eval_attrib; the statement: include/lns.h): one block per plane of a
+// decoded group reads the forecast frames and the reconstruction frames, both [kk][B][C][H*W], and the truth plane
+// y[b][y_t + j][c] of y [B][y_T][C][H*W], and writes (PP, XX, G) to part[b][p_t + j][c][0..2] of part [B][p_T][C][3].
+// Element order, nothing fused, no float4 grouping: the bits do not depend on any alignment.  G is summed in float64.  Stored form: B = 1, kk = the
+// number of planes / C, y_T = p_T = kk.  The denormalisation: as MetricGroupArgs.
+struct AttribGroupArgs {
+    const float* frames; const float* recon; const float* y; float* part;
+    int B, C, H, W, kk, y_T, y_t, p_T, p_t;
+    ScoreNorm norm;
+};
+hipError_t launch_attrib_group(const AttribGroupArgs& a, hipStream_t s);
+// Latent drift: one block per (j, b) of a group; z [kk][B][zper] (a ring group) against ztrue [kk][B][zstride] (zstride a
+// multiple of four floats, 16-byte aligned base) -> (sum (z - ztrue)^2, sum ztrue^2) at part[b][t + j] of part [B][T_total][2],
+// with the per-plane body of the metric (mean, sd: 0, 1) in the order plane (b, t + j) of a stored, 16-byte-aligned
+// [B][T_total][zper] tensor would get.
+struct LatentErrArgs {
+    const float* z; const float* ztrue; float* part;
+    long zstride; int zper, B, kk, T_total, t;
+    float mean, sd;
+};
+hipError_t launch_latent_err_group(const LatentErrArgs& a, hipStream_t s);
+// pp [B][T][C][3] (PP, XX, G), g = max(G, eps) -> prop = sqrt(PP / g), cross = 2 XX / g per frame and, from the running sums
+// over t ascending, per sequence; every output nullable
+hipError_t launch_attrib_finish(const float* pp, int B, int T, int C, float eps, float* prop_frame,
+                                float* prop_seq, float* cross_frame, float* cross_seq, hipStream_t s);
+
 // per-sample max |x| (bit patterns) of a [B, n] tensor with batch stride x_bs into amax [B][LNS_AMAX_SUB] (atomic max)
 hipError_t launch_amax(const float* x, long x_bs, long n, int B, unsigned* amax, hipStream_t s);
 hipError_t launch_amax_sticky(const unsigned* amax, int n, unsigned* flag, hipStream_t s);

@@ -216,6 +216,23 @@ class SimpleAutoencoder(_Hosted):
     def forward(self, x):
         return self.decode(self.encode(x))
 
+    def _validate(self, x, param, norm):
+        """x [B,T,C,H,W] or [N,C,H,W] (scored as N trajectories of one step) -> (frame_wise, seq_wise)."""
+        _no_backward("SimpleAutoencoder.validate", x, params=self.parameters())
+        if x.dim() == 4:
+            x = x[:, None]
+        with torch.no_grad():
+            res = self._engine(x).autoencode_eval(x, param=param, **norm)
+        return res.frame, res.seq
+
+    def validate(self, x, **norm):
+        """The validation loop of the stage-1 scripts (train_stage1_ns2d.py:104-124; train_stage1_SW.py:107-110) in one call,
+            x_hat = denormalize(autoencoder(x[:, t])); relative_lp_loss(x_hat, denormalize(x[:, t]), reduce_dim=(-1, -2))
+        over every step of x [B,T,C,H,W] (or [N,C,H,W]: N single frames), without storing the reconstruction.  `norm` as in
+        `metrics.relative_l2`.  Returns (frame_wise [B,T,C], seq_wise [B,C]): the bits of
+        `metrics.relative_l2(autoencoder(x), x, **norm)`."""
+        return self._validate(x, None, norm)
+
     def load_checkpoint(self, path, device=None):
         ckpt = torch.load(path, map_location=device)
         self.load_state_dict(ckpt, strict=True)
@@ -250,6 +267,11 @@ class ConditionalSimpleAutoencoder(SimpleAutoencoder):
 
     def forward(self, x, param):
         return self.decode(self.encode(x, param))
+
+    def validate(self, x, param, **norm):
+        """SimpleAutoencoder.validate for the conditional encoder (train_stage1_twophase.py:111-114): param holds one value
+        per trajectory of x [B,T,C,H,W] (per frame of [N,C,H,W])."""
+        return self._validate(x, param, norm)
 
     def load_checkpoint(self, path):
         self.load_state_dict(torch.load(path), strict=True)
@@ -581,6 +603,26 @@ class LatentDynamics(_Hosted):
         x = self._fields(x)
         return self._engine(x).rollout_eval_maps(x, y, param=param, keep_steps=keep_steps, map_steps=map_steps,
                                                  stats_steps=stats_steps, hist=hist, spectrum_steps=spectrum_steps, **norm)
+
+
+    @torch.no_grad()
+    def validate_attribution(self, x, y, *rest, keep_steps=(), return_latents=False, **norm):
+        """validate_attribution(x, y, **norm) -- conditional: validate_attribution(x, y, param, **norm): `validate` with the
+        error of every plane split into the autoencoder's floor and the propagator's drift -- which of the two separately
+        trained parts to retrain.  Returns engine.EvalAttrib: frame, seq, frames as `validate` returns them; recon_* the
+        relative L2 of the reconstruction D(E(y)) (what the stage-1 scripts validate); prop_* and cross_* with
+        frame^2 = prop^2 + recon^2 + cross (metrics.attribution_shares); latent_* the relative drift of the propagated latent
+        from E(y_t); recon_frames the reconstructions of keep_steps; z_true (return_latents) the encoded truth."""
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("validate_attribution() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if rest:
+            raise TypeError("validate_attribution() takes (x, y, param, **norm)" if self._conditional
+                            else "validate_attribution() takes (x, y, **norm)")
+        x = self._fields(x)
+        return self._engine(x).rollout_eval_attrib(x, y, param=param, keep_steps=keep_steps, return_latents=return_latents, **norm)
 
 
 class LatentDynamicsSW(LatentDynamics):                # train_stage2_SW.py:90-159

@@ -218,6 +218,16 @@ EvalMapsChunk.__doc__ = """Result of Engine.rollout_latent_eval_maps: EvalMaps' 
 the chunk's last step.  maps is written by the chunk that completes the horizon."""
 
 
+# The streaming validation with error attribution (rollout_eval_attrib): frame / seq / frames as rollout_eval; recon_*, prop_*
+# and cross_* [B,T,C] / [B,C] with frame^2 = prop^2 + recon^2 + cross; latent_* [B,T] / [B]; recon_frames: the reconstructions
+# of keep_steps or None; z_true [B,T,c,h,w] = encode(y) or None.
+EvalAttrib = collections.namedtuple("EvalAttrib", "frame seq frames recon_frame recon_seq prop_frame prop_seq cross_frame "
+                                    "cross_seq latent_frame latent_seq recon_frames z_true")
+EvalAttribChunk = collections.namedtuple("EvalAttribChunk", EvalAttrib._fields + ("z_last",))
+# Stage-1 validation (autoencode_eval): frame [B,T,C], seq [B,C], z [B,T,c,h,w] or None
+AutoencodeEval = collections.namedtuple("AutoencodeEval", "frame seq z")
+
+
 def normalize_map_steps(map_steps):
     """The `map_steps` argument of the time maps -> (from, every): None is every step, (0, 1); slice(from, None, every) and a
     (from, every) pair name the steps from, from + every, ... of the horizon (burn-in and thinning).  Anything else -- a stop,
@@ -716,12 +726,13 @@ class Engine:
         return t
 
     def _scored_call(self, name, result, first, y, steps, t0, param, keep_steps, norm, select=None, frame=None, seq=None,
-                     maps=None):
+                     maps=None, attrib=None):
         """The one body behind the eight scored rollouts: C entry point `name`, from x (t0 None: `first` is x, steps < T
         scores the first `steps` of y) or continued from a latent at step t0 (`first` is z; frame / seq / maps may be the
         caller's).  select(T, B, device) -> (the entry point's arguments after the stream, the result's fields after
         `frames`, the lns_eval_select whose maps this call owns or None); `result` builds what is returned from
-        frame, seq, frames, those fields, [maps, map_steps] and, from a latent, z_last."""
+        frame, seq, frames, those fields, [maps, map_steps] and, from a latent, z_last.  attrib(B, T_total, device, frames) ->
+        (lns_eval_attrib, the result's fields after `frames`): the attribution forms, whose struct stands in front of the workspace."""
         import torch
         latent = t0 is not None
         first = self._dev(first)
@@ -740,6 +751,10 @@ class Engine:
             q.maps_out = maps.data_ptr()
             tail += (maps, (q.map_from, q.map_every))
             query = "lns_rollout_eval_maps_workspace_bytes"
+        front = ()
+        if attrib is not None:
+            at, atail = attrib(B, T_total, first.device, frames)
+            front, tail, query = (ctypes.byref(at),), tail + atail, "lns_rollout_eval_attrib_workspace_bytes"
         z_last = torch.empty_like(first) if latent else None
         p = self._param(param, first)
         with torch.cuda.device(first.device):
@@ -747,7 +762,7 @@ class Engine:
             self._check(getattr(self._L, name)(
                 self._h, first.data_ptr(), self._ptr(p), y.data_ptr(), B, T, *((t0, T_total) if latent else ()),
                 ctypes.byref(spec), frame.data_ptr(), seq.data_ptr(), keep, n_keep, self._ptr(frames),
-                *((z_last.data_ptr(),) if latent else ()), ws.data_ptr(), ws.numel(), self._stream(first), *extra), name)
+                *((z_last.data_ptr(),) if latent else ()), *front, ws.data_ptr(), ws.numel(), self._stream(first), *extra), name)
         return result(frame, seq, frames, *tail, *((z_last,) if latent else ()))
 
     def rollout_eval(self, x, y, steps=None, param=None, keep_steps=(), **norm):
@@ -907,6 +922,75 @@ class Engine:
         ms = normalize_map_steps(map_steps)
         return self._scored_call("lns_rollout_latent_eval_maps", EvalMapsChunk, z, y, steps, t0, param, keep_steps, norm,
                                  functools.partial(self._maps_select, ms, stats_steps, hist, spectrum_steps), frame, seq, maps)
+
+    # -- streaming validation with error attribution (include/lns.h "error attribution") ---------------------------
+    def eval_attrib(self, y_hat, r, y, **norm):
+        """The attribution columns of stored fields (lns_op_eval_attrib): see metrics.error_attribution.  The kernel bodies of
+        rollout_eval_attrib."""
+        from . import metrics
+        return metrics.error_attribution(y_hat, r, y, **norm)
+
+    def _attrib_select(self, return_latents, prev, B, T_total, device, frames):
+        """The `attrib` of _scored_call: the lns_eval_attrib with every column set (prev: the previous chunk's result, whose
+        tensors this chunk goes on filling) -> (the struct, EvalAttrib's fields after `frames`)."""
+        import torch
+        C = self.cfg.in_channels
+        shapes = dict(recon_frame=(B, T_total, C), recon_seq=(B, C), prop_frame=(B, T_total, C), prop_seq=(B, C),
+                      cross_frame=(B, T_total, C), cross_seq=(B, C), latent_frame=(B, T_total), latent_seq=(B,))
+        if return_latents:
+            shapes["z_true"] = (B, T_total) + self.latent_shape()
+        t = {k: self._result(getattr(prev, k) if prev is not None else None, s, device) for k, s in shapes.items()}
+        recon_frames = torch.empty_like(frames) if frames is not None else None
+        at = _lib.LnsEvalAttrib()
+        at.size = ctypes.sizeof(_lib.LnsEvalAttrib)
+        for k in EvalAttrib._fields[3:11]:
+            setattr(at, k, t[k].data_ptr())
+        at.z_true_out = self._ptr(t.get("z_true"))
+        at.recon_frames_out = self._ptr(recon_frames)
+        return at, tuple(t[k] for k in EvalAttrib._fields[3:11]) + (recon_frames, t.get("z_true"))
+
+    def rollout_eval_attrib(self, x, y, steps=None, param=None, keep_steps=(), return_latents=False, **norm):
+        """rollout_eval with the rollout error of every plane split into the autoencoder's floor and the propagator's drift:
+        beside the forecast of a decode group, the truth frames of the group are encoded and decoded again (r = D(E(y)), the
+        reconstruction no propagator can beat) and the three fields are compared where they are decoded.  Returns EvalAttrib:
+        frame / seq / frames hold rollout_eval's bits; recon_* those of `metrics.relative_l2(decode(encode(y)), y, ...)`;
+        prop_* and cross_* those of `metrics.error_attribution` on the stored tensors, with frame^2 = prop^2 + recon^2 + cross
+        (cross signed: > 0 the two errors add, < 0 they compensate; see metrics.attribution_shares); latent_* the relative L2
+        of the propagated latent against encode(y_t); recon_frames the reconstructions of keep_steps; z_true (return_latents)
+        encode(y).  Neither the rollout nor the reconstruction [B,T,C,Ly,Lx] is stored."""
+        return self._scored_call("lns_rollout_eval_attrib", EvalAttrib, x, y, steps, None, param, keep_steps, norm,
+                                 attrib=functools.partial(self._attrib_select, return_latents, None))
+
+    def rollout_latent_eval_attrib(self, z, y, steps=None, t0=0, param=None, keep_steps=(), return_latents=False, prev=None, **norm):
+        """rollout_latent_eval with error attribution.  The chunks of one horizon must follow each other on the same engine and
+        batch; pass the previous chunk's result as `prev`: its tensors are filled further, and the chunk that completes the
+        horizon writes every frame- and sequence-wise column.  keep_steps are relative to the chunk.  Returns EvalAttribChunk."""
+        return self._scored_call("lns_rollout_latent_eval_attrib", EvalAttribChunk, z, y, steps, t0, param, keep_steps, norm,
+                                 frame=prev.frame if prev is not None else None, seq=prev.seq if prev is not None else None,
+                                 attrib=functools.partial(self._attrib_select, return_latents, prev))
+
+    def autoencode_eval(self, x, param=None, return_latents=False, **norm):
+        """The validation loop of the stage-1 scripts (train_stage1_ns2d.py:104-124) in one call: x [B,T,C,Ly,Lx] normalised ->
+        AutoencodeEval(frame [B,T,C], seq [B,C], z [B,T,c,h,w] or None), the bits of
+        `metrics.relative_l2(autoencoder(x), x, ...)` without the reconstruction being stored.  param [B]: a conditional
+        encoder's, one value per trajectory.  Needs no propagator."""
+        import torch
+        x = self._dev(x)
+        c = self.cfg
+        if x.dim() != 5 or tuple(x.shape[2:]) != (c.in_channels, c.Ly, c.Lx):
+            raise LnsError("autoencode_eval takes [B, T, %d, %d, %d], got %s" % (c.in_channels, c.Ly, c.Lx, tuple(x.shape)))
+        B, T = int(x.shape[0]), int(x.shape[1])
+        spec = eval_spec(c.in_channels, **norm)
+        frame = torch.empty((B, T, c.in_channels), dtype=torch.float32, device=x.device)
+        seq = torch.empty((B, c.in_channels), dtype=torch.float32, device=x.device)
+        z = torch.empty((B, T) + self.latent_shape(), dtype=torch.float32, device=x.device) if return_latents else None
+        p = self._param(param, x)
+        with torch.cuda.device(x.device):
+            ws = self._sized_workspace("lns_autoencode_eval_workspace_bytes", B, x.device)
+            self._check(self._L.lns_autoencode_eval(self._h, x.data_ptr(), self._ptr(p), B, T, ctypes.byref(spec), frame.data_ptr(),
+                                                    seq.data_ptr(), self._ptr(z), ws.data_ptr(), ws.numel(), self._stream(x)),
+                        "lns_autoencode_eval")
+        return AutoencodeEval(frame, seq, z)
 
     # -- training rollout of the propagator (include/lns.h "training rollout") ------------------------------------
     def _ptr_array(self, tensors):

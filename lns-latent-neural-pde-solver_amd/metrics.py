@@ -224,6 +224,43 @@ def temporal_correlation(maps):
     return torch.where(den == 0, torch.zeros_like(den), cov / den)
 
 
+def error_attribution(y_hat, r, y, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
+    """The rollout error of stored fields split at the reconstruction (lns_op_eval_attrib; include/lns.h "error attribution"):
+    y_hat (forecast), r (the autoencoder's reconstruction of the truth) and y [B,T,C,H,W], normalised, denormalised as in
+    `relative_l2`.  Returns (prop_frame [B,T,C], prop_seq [B,C], cross_frame, cross_seq): prop = ||y_hat - r|| / ||y||, the
+    propagator's error seen through the decoder, and cross = 2 <y_hat - r, r - y> / ||y||^2, so that with
+    recon = relative_l2(r, y) and frame = relative_l2(y_hat, y): frame^2 = prop^2 + recon^2 + cross.  The kernel bodies of
+    Engine.rollout_eval_attrib."""
+    from .engine import eval_spec
+    for t in (y_hat, r, y):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 5:
+            raise _lib.LnsError("error_attribution takes fp32 HIP tensors [B,T,C,H,W] (no CPU fallback)")
+    for t in (y_hat, r):
+        if t.shape != y.shape or t.device != y.device:
+            raise _lib.LnsError("y_hat and r must have y's shape %s and device, got %s" % (tuple(y.shape), tuple(t.shape)))
+    B, T, C, H, W = (int(v) for v in y.shape)
+    y_hat, r, y = y_hat.contiguous(), r.contiguous(), y.contiguous()
+    spec = eval_spec(C, mean=mean, std=std, eps=eps, zero_wall_channels=zero_wall_channels, clamp_channels=clamp_channels,
+                     clamp=clamp)
+    out = [torch.empty(s, dtype=torch.float32, device=y.device) for s in ((B, T, C), (B, C), (B, T, C), (B, C))]
+    L = _lib.lib()
+    with torch.cuda.device(y.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
+        rc = L.lns_op_eval_attrib(y_hat.data_ptr(), r.data_ptr(), y.data_ptr(), B, T, C, H, W, ctypes.byref(spec),
+                                  *(t.data_ptr() for t in out), stream)
+    if rc != 0:
+        raise _lib.LnsError("lns_op_eval_attrib failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    return tuple(out)
+
+
+def attribution_shares(frame, prop, recon, cross):
+    """The three shares of frame^2 (columns of Engine.rollout_eval_attrib, frame- or sequence-wise): (prop^2, recon^2, cross)
+    / frame^2 -- what the propagator adds, the autoencoder's floor, and their interaction (signed).  They sum to 1 up to
+    rounding; NaN where frame is 0.  Host-side helper: plain tensor arithmetic on the small result columns."""
+    f2 = frame * frame
+    return prop * prop / f2, recon * recon / f2, cross / f2
+
+
 def spread_skill_ratio(scores, members):
     """spread * sqrt((M + 1) / M) / rmse of an `engine.EnsembleScores` (Engine.rollout_latent_ensemble_eval,
     LatentDynamics.validate_ensemble) with M = `members`: near 1 for a calibrated ensemble, below it for an
