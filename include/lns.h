@@ -830,7 +830,7 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * lns_op_energy_spectrum and lns_spectrum_bins are there; "eval_stats" = lns_rollout_eval_stats,
  * lns_rollout_latent_eval_stats and lns_op_field_stats are there; "eval_maps" = lns_rollout_eval_maps,
  * lns_rollout_latent_eval_maps, their size query, lns_op_time_maps and lns_time_maps_state_bytes are there;
- * "op_conv_gn" = lns_op_conv_gn is there; "eval_attrib" = lns_rollout_eval_attrib, lns_rollout_latent_eval_attrib, their
+ * "op_conv_gn" = lns_op_conv_gn is there; "op_fa_fused" = lns_op_fa_fused is there; "eval_attrib" = lns_rollout_eval_attrib, lns_rollout_latent_eval_attrib, their
  * size query, lns_autoencode_eval, its size query, lns_op_eval_attrib and lns_op_latent_err are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
@@ -885,6 +885,32 @@ typedef struct lns_conv_gn_args {
     const float* w2_host; const float* bias2_host; int Cout2, ksize2, act_in2, variant2; float* y2;
 } lns_conv_gn_args;
 int lns_op_conv_gn(const lns_conv_gn_args* args, void* stream);
+/* FABlock2D with in_proj inside the sandwich (unit tests of csrc/fa_fused.inc; "op_fa_fused" in lns_build_has): the input
+ * split pre-pass and the fused kernel on their own, their arguments set as the planner sets them,
+ *   G = x * scale + shift,  P[h * dim_head + d] = sum_c W[h * dim_head + d][c] G[c],  Y = Kx[b][h] P Ky[b][h]^T,
+ *   out = (Y - mean) / sqrt(var_biased + eps) per plane when instnorm, else Y.
+ * Existing launchers only: the call allocates the split input and the max |G| words, packs W with the planner's scales,
+ * runs the two launches, synchronises `stream` and frees what it allocated.  Every check precedes the first HIP call
+ * (LNS_EINVAL, message lns_create_error() starting "fa_fused: "): null x / w_host / kx / ky / out, B or heads outside 1..65535, a shape
+ * without a fused kernel (64 x 64 planes with 64 channels, 32 x 32 with 64 or 128; dim_head a multiple of 16), a gpb that
+ * does not divide dim_head / 16, form outside 0..2 or nonzero at 32 x 32, a bound that is not > 0, x_bs < Cin * H * W.
+ *   x          device, B samples of [Cin][H][W], x_bs floats apart
+ *   ss         device [B][Cin][2] (scale, shift), or NULL: identity
+ *   bound      a bound of |G| (inside a plan: max |gamma| sqrt(Cin H W) + max |beta| of the in_norm GroupNorm): G is split at
+ *              the power of two that puts it at 2^14 .. 2^15
+ *   w_host     HOST [heads * dim_head][Cin]
+ *   kx, ky     device [B][heads][H][H], [B][heads][W][W]
+ *   form       64 x 64: 0 the double-buffered kernel (shipped), 1 the single-buffered one, 2 the generic one; 32 x 32: 0
+ *   gpb        plane groups (of 16) a block walks; 0 = the planner's automatic choice.  b_rev: blocks take samples last to first
+ *   out        device [B][heads * dim_head][H][W]
+ *   amax_out   device [B] float or NULL: max |G| of each sample as the pre-pass recorded it (the maximum over its 16 words) */
+typedef struct lns_fa_fused_args {
+    const float* x; int64_t x_bs; const float* ss; float bound;
+    const float* w_host; const float* kx; const float* ky;
+    int B, heads, dim_head, Cin, H, W; float eps; int instnorm, form, gpb, b_rev;
+    float* out; float* amax_out;
+} lns_fa_fused_args;
+int lns_op_fa_fused(const lns_fa_fused_args* args, void* stream);
 /* Diagnostic: runs two convolutions (GroupNorm+Swish prologue, circular padding, stride 1) repeatedly on two HIP
  * streams so that their workgroups share compute units, and counts output words that differ from what each
  * convolution produces alone.  variant_*: tile variant as in lns_op_conv2d (-1 automatic, 6 = bf16x3 3x3 kernel). */

@@ -125,8 +125,8 @@ class LnsUpdateSpec(ctypes.Structure):
 
 
 def _fields(spec):
-    """"x:p B:i eps:f ..." -> ctypes fields (p pointer, i int, f float)."""
-    kinds = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float}
+    """"x:p B:i eps:f ..." -> ctypes fields (p pointer, i int, f float, q int64)."""
+    kinds = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "q": ctypes.c_int64}
     return [(n, kinds[k]) for n, k in (t.split(":") for t in spec.split())]
 
 
@@ -137,6 +137,13 @@ class LnsConvGnArgs(ctypes.Structure):
         "pad_r:i mode_y:i mode_x:i ss:p act_in:i act_out:i residual:p badd:p y:p tile_variant:i part_out:p part_in:p geom:p "
         "groups:i eps:f gamma_host:p beta_host:p premul:p ss_out:p w2_host:p bias2_host:p Cout2:i ksize2:i "
         "act_in2:i variant2:i y2:p")
+
+
+class LnsFaFusedArgs(ctypes.Structure):
+    """Mirror of `struct lns_fa_fused_args` (include/lns.h): the arguments of lns_op_fa_fused."""
+    _fields_ = _fields(
+        "x:p x_bs:q ss:p bound:f w_host:p kx:p ky:p B:i heads:i dim_head:i Cin:i H:i W:i eps:f instnorm:i form:i gpb:i "
+        "b_rev:i out:p amax_out:p")
 
 
 # every symbol include/lns.h declares (tests check the library exports them all)
@@ -162,7 +169,7 @@ SYMBOLS = [
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
     "lns_op_conv_wgrad_scratch_bytes", "lns_op_conv_wgrad",
     "lns_op_groupnorm_train", "lns_op_gelu_grad", "lns_op_bias_grad",
-    "lns_op_conv2d", "lns_op_conv_gn", "lns_op_conv_pair_stress", "lns_op_groupnorm_stats", "lns_op_attention", "lns_op_fa_sandwich", "lns_op_fa_pool", "lns_op_fourier_block",
+    "lns_op_conv2d", "lns_op_conv_gn", "lns_op_fa_fused", "lns_op_conv_pair_stress", "lns_op_groupnorm_stats", "lns_op_attention", "lns_op_fa_sandwich", "lns_op_fa_pool", "lns_op_fourier_block",
     "lns_fourier_block_create", "lns_fourier_block_forward", "lns_fourier_block_destroy", "lns_metric_rel_l2", "lns_metric_rel_l2_ch",
 ]
 
@@ -308,6 +315,8 @@ def lib():
                                 vp, i, i, vp, vp, vp, i, vp, vp]
     if hasattr(L, "lns_op_conv_gn"):
         L.lns_op_conv_gn.argtypes = [c.POINTER(LnsConvGnArgs), vp]
+    if hasattr(L, "lns_op_fa_fused"):
+        L.lns_op_fa_fused.argtypes = [c.POINTER(LnsFaFusedArgs), vp]
     if hasattr(L, "lns_op_conv_wgrad"):
         L.lns_op_conv_wgrad_scratch_bytes.argtypes = [i, i, i, i, i, i, i, c.POINTER(c.c_size_t)]
         L.lns_op_conv_wgrad.argtypes = [vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, vp, c.c_size_t, vp]

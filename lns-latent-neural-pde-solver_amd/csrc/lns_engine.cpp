@@ -255,6 +255,34 @@ static bool gn_tile_rule(GnTileRule& r, const ConvArgs& c, int variant, int H, i
 }
 
 // ---------------------------------------------------------------------------
+// FABlock2D with in_proj inside the sandwich (fa_fused.inc): the scales of the in_proj weight image and the plane groups a
+// block walks.  One rule each for Planner::lower_fa and the op-level entry point lns_op_fa_fused.
+// ---------------------------------------------------------------------------
+struct FaWeightScale {
+    float wscale;          // power of two the weights are multiplied by before their fp16 split (largest entry below 16000)
+    float wrow_max;        // largest absolute row sum of W times (1 + 1e-6): the device multiplies it by max |G| in fp32, and
+                           // the product must stay a bound of |P|
+};
+// wm: [planes][C] fp32.  An all-zero or non-finite matrix packs at scale 16000 / 1 and a row bound of at least 1.
+static FaWeightScale fa_fused_weight_scale(const float* wm, int planes, int C) {
+    float wmax = 0.0f, rowmax = 0.0f;
+    for (int r = 0; r < planes; ++r) {
+        float rs = 0.0f;
+        for (int k = 0; k < C; ++k) { const float v = fabsf(wm[(size_t)r * C + k]); wmax = std::max(wmax, v); rs += v; }
+        rowmax = std::max(rowmax, rs);
+    }
+    if (!(wmax > 0.0f) || !std::isfinite(rowmax)) { wmax = 1.0f; rowmax = std::max(rowmax, 1.0f); }
+    return FaWeightScale{exp2f(floorf(log2f(16000.0f / wmax))), rowmax * (1.0f + 1e-6f)};
+}
+// Plane groups (of 16) per block, scheduling only.  requested > 0: that many, lowered to the next divisor of `groups`;
+// 0 = automatic: all four groups of a head while the grid keeps two blocks per CU's worth of work.
+static int fa_fused_gpb_rule(int requested, int groups, int B, int heads) {
+    int gpb = requested > 0 ? std::min(requested, groups) : 4;
+    while (gpb > 1 && (groups % gpb || (requested <= 0 && (long)B * heads * (groups / gpb) < 512))) --gpb;
+    return gpb;
+}
+
+// ---------------------------------------------------------------------------
 // arena allocator for plan temporaries (offsets into the caller's workspace)
 // ---------------------------------------------------------------------------
 struct Arena {
@@ -938,34 +966,22 @@ struct Planner {
                 }
                 if ((int)row != planes) throw std::runtime_error("in_proj weight rows: " + l.name);
             }
-            float wmax = 0.0f, rowmax = 0.0f;
-            for (int r = 0; r < planes; ++r) {
-                float rs = 0.0f;
-                for (int k = 0; k < C; ++k) { const float v = fabsf(wm[(size_t)r * C + k]); wmax = std::max(wmax, v); rs += v; }
-                rowmax = std::max(rowmax, rs);
-            }
-            if (!(wmax > 0.0f) || !std::isfinite(rowmax)) { wmax = 1.0f; rowmax = std::max(rowmax, 1.0f); }
-            const float wscale = exp2f(floorf(log2f(16000.0f / wmax)));
+            const FaWeightScale ws = fa_fused_weight_scale(wm.data(), planes, C);
             std::vector<float> img(fa_fused_weight_bytes(planes, C) / 4);
-            fa_fused_pack_weight(img.data(), wm.data(), planes, C, wscale);
+            fa_fused_pack_weight(img.data(), wm.data(), planes, C, ws.wscale);
             Op op;
             op.type = OP_FAFUSED; op.name = l.name + ".sandwich"; op.cls = CLS_FASAND;
             op.ff.gs = as_ptr<const void>(tag(SP_WS, gs_off)); op.ff.amax_g = as_ptr<const unsigned>(amax_g); op.ff.bound = xin.gn_bound;
-            op.ff.wp = as_ptr<const void>(const_floats(img)); op.ff.w_inv = 1.0f / wscale;
-            op.ff.wrow_max = rowmax * (1.0f + 1e-6f);       // (the device multiplies it by max |G| in fp32: keep the product a bound)
+            op.ff.wp = as_ptr<const void>(const_floats(img)); op.ff.w_inv = 1.0f / ws.wscale;
+            op.ff.wrow_max = ws.wrow_max;
             op.ff.kx = as_ptr<const float>(tag(SP_WS, kx_off)); op.ff.ky = as_ptr<const float>(tag(SP_WS, ky_off));
             op.ff.B = B; op.ff.heads = heads; op.ff.C = dh; op.ff.Cin = C; op.ff.H = H; op.ff.W = W; op.ff.eps = 1e-5f; op.ff.instnorm = 1;
             op.ff.out = as_ptr<float>(uphi.ptr);
             static const bool no_rev = getenv("LNS_FA_NO_REVERSE") != nullptr;
             op.ff.b_rev = no_rev ? 0 : 1;
             op.ff.single_buffer = e->opt_fa_fused == 1 ? 1 : (e->opt_fa_fused == 3 ? 2 : 0);
-            {   // plane groups per block (scheduling only; "fa_fused_gpb" / LNS_FA_FUSED_GPB): by default all four groups of a
-                // head while the grid keeps two blocks per CU's worth of work
-                const int groups = dh / 16;
-                int gpb = e->opt_fa_fused_gpb > 0 ? std::min(e->opt_fa_fused_gpb, groups) : 4;
-                while (gpb > 1 && (groups % gpb || (e->opt_fa_fused_gpb <= 0 && (long)B * heads * (groups / gpb) < 512))) --gpb;
-                op.ff.gpb = gpb;
-            }
+            // plane groups per block (scheduling only; "fa_fused_gpb" / LNS_FA_FUSED_GPB)
+            op.ff.gpb = fa_fused_gpb_rule(e->opt_fa_fused_gpb, dh / 16, B, heads);
             op.flops = 2.0 * B * heads * dh * ((double)H * W * W + (double)H * H * W) + 2.0 * B * planes * (double)C * H * W;
             op.bytes = 4.0 * B * ((double)planes + C) * H * W;
             op.mfma_flops = (2.0 * B * heads * dh * ((double)H * W * W + (double)H * H * W) + 2.0 * B * planes * (double)C * H * W) * 3.0;
@@ -3091,6 +3107,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "eval_maps")) return 1;
     if (!strcmp(feature, "eval_attrib")) return 1;
     if (!strcmp(feature, "op_conv_gn")) return 1;
+    if (!strcmp(feature, "op_fa_fused")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else
@@ -3720,6 +3737,74 @@ int lns_op_fa_pool(const float* x, int64_t x_bs, const float* ss, int B, int C, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     OPCHK(launch_fa_pool(a, s));
     OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+// FABlock2D with in_proj inside the sandwich (include/lns.h): the input split pre-pass, then the fused kernel, their arguments
+// set as Planner::lower_fa sets them (fa_fused_weight_scale, fa_fused_gpb_rule).  No HIP call before the last check.
+int lns_op_fa_fused(const lns_fa_fused_args* p, void* stream) {
+    auto bad = [](const std::string& m) { g_create_error = "fa_fused: " + m; return (int)LNS_EINVAL; };
+    if (!p) return bad("args is null");
+    if (!p->x || !p->w_host || !p->kx || !p->ky || !p->out) return bad("x / w_host / kx / ky / out is null");
+    if (p->B < 1 || p->B > LNS_MAX_BATCH || p->heads < 1 || p->heads > 65535) return bad("B and heads in 1..65535");
+    if (p->dim_head < 1 || !fa_fused_fits(p->H, p->W, p->Cin, p->dim_head))
+        return bad(fmt("no fused kernel for %d x %d planes, %d channels, dim_head %d: 64 x 64 with 64 channels or 32 x 32 with 64 / 128, "
+                       "dim_head a multiple of 16", p->H, p->W, p->Cin, p->dim_head));
+    const int B = p->B, heads = p->heads, dh = p->dim_head, C = p->Cin, H = p->H, W = p->W, groups = dh / 16, planes = heads * dh;
+    if ((long)B * heads * groups > 0x7fffffffL) return bad("B * heads * dim_head / 16 exceeds the grid");
+    if (p->gpb < 0 || (p->gpb > 0 && groups % p->gpb != 0))
+        return bad(fmt("gpb %d does not divide the %d plane groups of a head (0 = automatic)", p->gpb, groups));
+    if (p->form < 0 || p->form > 2 || (p->form != 0 && H == 32))
+        return bad("form 0 (double-buffered), 1 (single-buffered) or 2 (generic) at 64 x 64, 0 at 32 x 32");
+    if (!(p->bound > 0.0f)) return bad("bound must be positive");
+    if (p->x_bs < (int64_t)C * H * W) return bad("x_bs is shorter than a sample");
+    // ---- every check is done ----
+    const FaWeightScale ws = fa_fused_weight_scale(p->w_host, planes, C);
+    std::vector<float> img(fa_fused_weight_bytes(planes, C) / 4);
+    fa_fused_pack_weight(img.data(), p->w_host, planes, C, ws.wscale);
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    void *dgs = nullptr, *dwp = nullptr;
+    unsigned* damax = nullptr;
+    const size_t amax_words = (size_t)B * LNS_AMAX_SUB;
+    hipError_t he = hipMalloc(&dgs, fa_fused_gs_bytes(B, H, W, C));
+    auto ok = [&](hipError_t e) { if (he == hipSuccess) he = e; return he == hipSuccess; };
+    if (he == hipSuccess) ok(hipMalloc(&dwp, img.size() * 4));
+    if (he == hipSuccess) ok(hipMalloc(reinterpret_cast<void**>(&damax), amax_words * 4));
+    if (he == hipSuccess) ok(hipMemcpyAsync(dwp, img.data(), img.size() * 4, hipMemcpyHostToDevice, s));
+    if (he == hipSuccess) ok(hipMemsetAsync(damax, 0, amax_words * 4, s));
+    if (he == hipSuccess) {
+        FaGsplitArgs g = {};
+        g.x = p->x; g.x_bs = (long)p->x_bs; g.Cin = C; g.HW = H * W; g.ss = p->ss; g.bound = p->bound;
+        g.gs = dgs; g.amax_out = damax; g.B = B;
+        ok(launch_fa_gsplit(g, s));
+    }
+    if (he == hipSuccess) {
+        FaFusedArgs a = {};
+        a.gs = dgs; a.amax_g = damax; a.bound = p->bound;
+        a.wp = dwp; a.w_inv = 1.0f / ws.wscale; a.wrow_max = ws.wrow_max;
+        a.kx = p->kx; a.ky = p->ky;
+        a.B = B; a.heads = heads; a.C = dh; a.Cin = C; a.H = H; a.W = W; a.eps = p->eps; a.instnorm = p->instnorm ? 1 : 0;
+        a.out = p->out; a.b_rev = p->b_rev ? 1 : 0; a.single_buffer = p->form;
+        a.gpb = p->gpb > 0 ? p->gpb : fa_fused_gpb_rule(0, groups, B, heads);
+        ok(launch_fa_fused(a, s));
+    }
+    if (he == hipSuccess) ok(hipStreamSynchronize(s));      // (img, the source of the weight copy, lives until here)
+    if (he == hipSuccess && p->amax_out) {                  // max |G| of a sample: the maximum over its sub-words (amax_load)
+        std::vector<unsigned> hw(amax_words);
+        std::vector<float> hm(B);
+        if (ok(hipMemcpy(hw.data(), damax, amax_words * 4, hipMemcpyDeviceToHost))) {
+            for (int b = 0; b < B; ++b) {
+                unsigned m = 0u;
+                for (int k = 0; k < LNS_AMAX_SUB; ++k) m = std::max(m, hw[(size_t)b * LNS_AMAX_SUB + k]);
+                memcpy(&hm[b], &m, 4);
+            }
+            ok(hipMemcpy(p->amax_out, hm.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        }
+    }
+    if (he != hipSuccess) (void)hipStreamSynchronize(s);
+    (void)hipFree(dgs); (void)hipFree(dwp); (void)hipFree(damax);
+    OPCHK(he);
     return LNS_OK;
 }
 
