@@ -164,6 +164,11 @@ int lns_finalize_weights(lns_engine* e, int device);
  *                     1x1 -> quant_conv.  The parameter table is unchanged; the layer trace shows the pair under the 1x1's name.
  *                     0: the pair as two launches, or as the 64 -> 64 1x1 in the first convolution's epilogue.  Any other
  *                     value: LNS_EINVAL.  Cached plans are rebuilt.
+ *   "up2_dual"        1 (default; LNS_UP2_DUAL=0 in the environment makes it 0): a 3x3 convolution behind an exactly-2x nearest
+ *                     upsample takes the dual-phase form (csrc/conv3_up2d.inc: one block per source tile and row phase computes
+ *                     both column phases and stores pixel pairs) wherever that form fits -- a per-layer rule; 0: the per-phase
+ *                     form everywhere, launch for launch the plan without the form.  The results have the same bits either way.
+ *                     Any other value: LNS_EINVAL.  Cached plans are rebuilt.
  * Defaults come from LNS_DECODE_GROUP / LNS_DECODE_STREAMS / LNS_NO_OVERLAP / LNS_PROP_PRIORITY at lns_create().
  * Changing an option changes the workspace size: call lns_prepare() again. */
 int lns_set_option(lns_engine* e, const char* name, long value);

@@ -662,6 +662,10 @@ struct Planner {
             static const bool res = getenv("LNS_UP2_RESIDENT") != nullptr;
             if (res) { a.up2 = 2; if (!convur_fits(a)) a.up2 = 1; }
             if (quad && convuq_fits(a)) a.up2 = 3;
+            // the dual-phase form (conv3_up2d.inc: one block per source tile and row phase computes both column phases --
+            // the patch staged once for the two, 8-byte stores of pixel pairs; same bits): a per-layer rule, "up2_dual"
+            // (no fused 1x1: ConvArgs::w2 is set below)
+            if (a.up2 == 1 && fuse_pack < 0 && e->opt_up2_dual && convud_fits(a)) a.up2 = 4;
         }
         op.flops = 2.0 * B * g.Hout * g.Wout * (double)pk.cout * pk.cin * k * k;
         op.bytes = 4.0 * B * ((double)in.C * in.H * in.W + (double)pk.cout * g.Hout * g.Wout * (res ? 2 : 1));
@@ -1618,7 +1622,8 @@ struct Runner {
                     const bool ts_match = getenv("LNS_TS_LAYER") && op.name.find(getenv("LNS_TS_LAYER")) != std::string::npos &&
                                           (cv_is_split_3x3(op.variant) || op.variant == CV_B1);
                     const long ts_skip = getenv("LNS_TS_SKIP") ? atol(getenv("LNS_TS_SKIP")) : 0, ts_max = getenv("LNS_TS_MAX") ? atol(getenv("LNS_TS_MAX")) : (1L << 40);
-                    const long nblk = (long)a.tiles_x * a.tiles_y * a.cout_tiles * a.B;
+                    // (the phase forms of the upsampling conv launch four / two blocks per source tile)
+                    const long nblk = (long)a.tiles_x * a.tiles_y * a.cout_tiles * a.B * (a.up2 == 1 ? 4 : a.up2 == 4 ? 2 : 1);
                     if (ts_match && ts_seen++ >= ts_skip && ts_seen - 1 - ts_skip < ts_max &&
                         ts_capture(nblk, 8, fmt("# launch %s B=%d Cin=%d Cout=%d H=%d W=%d blocks=%ld", op.name.c_str(), a.B, a.Cin, a.Cout, a.Hout, a.Wout, nblk),
                                    stream, rc, [&](long long* ts) { a.dbg_ts = ts; return launch_conv(op.variant, a, stream); })) break;
@@ -2009,6 +2014,7 @@ int lns_create(const lns_config* cfg, lns_engine** out) {
     if (const char* v = getenv("LNS_FA_FUSED")) e->opt_fa_fused = std::min(3, std::max(0, atoi(v)));
     if (const char* v = getenv("LNS_FA_FUSED_GPB")) e->opt_fa_fused_gpb = std::max(0, atoi(v));
     if (getenv("LNS_NO_FOLD_LINEAR")) e->opt_fold_linear = 0;
+    if (const char* v = getenv("LNS_UP2_DUAL")) e->opt_up2_dual = atoi(v) != 0;
     e->cfg.ae_prefix[sizeof(e->cfg.ae_prefix) - 1] = 0;
     e->cfg.prop_prefix[sizeof(e->cfg.prop_prefix) - 1] = 0;
     try {
@@ -2107,6 +2113,17 @@ int lns_set_option(lns_engine* e, const char* name, long value) {
             }
         }
         e->opt_fold_linear = (int)value;
+    }
+    else if (n == "up2_dual") {
+        if (value != 0 && value != 1) { e->err = "up2_dual: 0 (one block per output phase) or 1 (both column phases per block where the form fits)"; return LNS_EINVAL; }
+        if (e->opt_up2_dual != (int)value) {            // a planning rule of the decoder / encoder: cached plans are rebuilt
+            DeviceGuard dg(e);
+            for (auto* m : {&e->enc_plans, &e->dec_plans}) {
+                for (auto& kv : *m) if (kv.second.d_consts) (void)hipFree(kv.second.d_consts);
+                m->clear();
+            }
+        }
+        e->opt_up2_dual = (int)value;
     }
     else if (n == "fa_chunk_mb") {
         if (value < 0 || value > 4096) return LNS_EINVAL;
@@ -3149,7 +3166,8 @@ static int op_conv_prepare(OpConv& oc, const float* x, int B, int Cin, int Hin, 
     if (w8) tile_variant = CV_F64;
     const bool up2r = tile_variant == 18;           // test code: ... its resident-patch form (conv3_up2r.inc)
     const bool up2q = tile_variant == 20;           // test code: ... its quad-phase form (conv3_up2q.inc)
-    const bool up2 = tile_variant == 17 || up2r || up2q;    // test code: f16x2 3x3 kernel, phase form of an exactly-2x nearest upsample
+    const bool up2d = tile_variant == 21;           // ... its dual-phase form (conv3_up2d.inc): the planner's form where it fits
+    const bool up2 = tile_variant == 17 || up2r || up2q || up2d;    // test code: f16x2 3x3 kernel, phase form of an exactly-2x nearest upsample
     if (up2) {
         if (ksize != 3 || stride != 1 || dilation != 1 || Hv != 2 * Hin || Wv != 2 * Win || pad_t != 1 || pad_b != 1 || pad_l != 1 || pad_r != 1) return LNS_EINVAL;
         tile_variant = CV_F64; Hv = Hin; Wv = Win;
@@ -3245,6 +3263,10 @@ static int op_conv_prepare(OpConv& oc, const float* x, int B, int Cin, int Hin, 
     a.w8 = w8 ? 1 : (forced ? -1 : 0);              // a forced tile variant means that kernel
     a.x_oct = (layout & 0x100) ? 1 : 0; a.y_oct = (layout & 0x200) ? 1 : 0;
     if ((a.x_oct && (Cin & 7)) || (a.y_oct && (Cout & 7))) return LNS_EINVAL;
+    if (up2d) {
+        if (!convud_fits(a)) return LNS_EINVAL;
+        a.up2 = 4;
+    }
     if (stationary) {
         if (pk.Cin_pad > 64) return LNS_EINVAL;
         a.ct_per_block = g.cout_tiles < 3 ? g.cout_tiles : 3;
@@ -3266,7 +3288,8 @@ int lns_op_conv2d(const float* x, int B, int Cin, int Hin, int Win, int Hv, int 
     hipStream_t s = static_cast<hipStream_t>(stream);
 #ifdef LNS_TS
     // diagnostic build: per-block phase timestamps of the split-operand kernels, appended to $LNS_TS_FILE
-    const long nblk = (long)oc.a.tiles_x * oc.a.tiles_y * oc.a.cout_tiles * oc.a.B;     // an upper bound for the input-stationary 1x1 form
+    // (an upper bound for the input-stationary 1x1 form; the phase forms of the upsampling conv: four / two blocks per source tile)
+    const long nblk = (long)oc.a.tiles_x * oc.a.tiles_y * oc.a.cout_tiles * oc.a.B * (oc.a.up2 == 1 ? 4 : oc.a.up2 == 4 ? 2 : 1);
     hipError_t lrc = hipSuccess;
     if ((cv_is_split_3x3(oc.variant) || oc.variant == CV_B1) &&
         ts_capture(nblk, 8, fmt("# launch B=%d Cin=%d Cout=%d H=%d W=%d blocks=%ld", B, Cin, Cout, Hv, Wv, nblk), s, lrc,
@@ -3306,7 +3329,7 @@ int lns_op_conv_gn(const lns_conv_gn_args* p, void* stream) {
                              p->residual, p->badd, p->y, p->tile_variant, s);
     if (rc) return done(rc == LNS_EINVAL ? bad("no such producer convolution (lns_op_conv2d's rules)") : rc);
     const int H = prod.a.Hout, W = prod.a.Wout;
-    if (prod.a.up2 >= 2 || prod.a.w8 == 1) return done(bad("the experimental producer forms are not covered"));
+    if (prod.a.up2 == 2 || prod.a.up2 == 3 || prod.a.w8 == 1) return done(bad("the experimental producer forms are not covered"));
     GnTileRule r;
     if (!gn_tile_rule(r, prod.a, prod.variant, H, W, p->groups, p->premul != nullptr, B, ~(size_t)0))
         return done(bad(fmt("the planner attaches no tile statistics to this producer (variant %d%s%s, %d x %d plane, %d x %d tiles%s): "

@@ -185,6 +185,9 @@ struct lns_engine {
     // conv -> 1x1 conv with nothing in between runs as one conv on the composed weights (Layer::fold).  A planning rule
     // ("fold_linear" option / LNS_NO_FOLD_LINEAR); 0: the pair runs as two launches or as the fused 64 -> 64 epilogue
     int opt_fold_linear = 1;
+    // 1: the upsampling 3x3 convs take the dual-phase form (conv3_up2d.inc) where it fits ("up2_dual" option / LNS_UP2_DUAL);
+    // 0: the per-phase form everywhere.  Same bits either way.
+    int opt_up2_dual = 1;
     // what the last top-level call ran, for lns_check_finite: (plan kind, plan key, arena offset inside the caller's
     // workspace) -- no pointers into the plan caches or the workspace, which the caller may drop at any time -- plus
     // the workspace and batch of that call.  Cleared whenever plans are dropped.

@@ -57,7 +57,9 @@ struct ConvArgs {
     // x is the SOURCE tensor, tiles / patch / maps are those of a plain pad-1 3x3 convolution of the source, and
     // Hout = 2 Hin, Wout = 2 Win; every block computes 128 source pixels of one of the four output phases (f16x2 kernel)
     int up2;               // (2: the resident-weights form, conv3_up2r.inc, experimental; 3: the quad-phase form, conv3_up2q.inc --
-                           //  one block per source tile stages the patch once and walks the four phases, two blocks per CU)
+                           //  one block per source tile stages the patch once and walks the four phases, two blocks per CU;
+                           //  4: the dual-phase form, conv3_up2d.inc -- one block per (source tile, row phase) computes both
+                           //  column phases; the planner's form where convud_fits, "up2_dual")
     // GroupNorm folded into this convolution's prologue (split-operand 3x3 / 1x1 kernels): instead of the finished
     // (scale, shift) table `ss`, the per-(sample, 128-pixel tile, channel) (mean, M2) partials the PRODUCER's epilogue left
     // ([B][gn_tiles][Cin][2], ConvArgs::stat_part of that launch) plus gamma / beta; every block of a sample merges them
@@ -162,6 +164,8 @@ hipError_t launch_conv_pc(int nt, const ConvArgs& a, hipStream_t s);
 size_t convb_weight_bytes(int Cout, int Cin_pad);
 bool convuq_fits(const ConvArgs& a);        // quad-phase form of the upsampling conv (ConvArgs::up2 == 3; a.up2 != 0 on entry)
 size_t convuq_lds_bytes(const ConvArgs& a);
+bool convud_fits(const ConvArgs& a);        // dual-phase form of the upsampling conv (ConvArgs::up2 == 4; a.up2 != 0 on entry)
+size_t convud_lds_bytes(const ConvArgs& a);
 bool convur_fits(const ConvArgs& a);        // resident-patch form of the upsampling conv (ConvArgs::up2 == 2)
 size_t convur_lds_bytes(const ConvArgs& a);
 void convb_pack_weight(void* dst, const float* w, int co0, int cout, int cin, int Cin_pad);

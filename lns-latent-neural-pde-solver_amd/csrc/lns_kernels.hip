@@ -933,6 +933,10 @@ __device__ __forceinline__ void split2_pair_f16(float x, float y, unsigned& h, u
 // SHALF: the tile statistics go through the LDS scratch in two halves of 32 channels (17 KB instead of 34 KB; two more
 // barriers): the quad-phase upsampling conv (conv3_up2q.inc) keeps its whole split patch in LDS and has 18.5 KB of scratch.
 // NORES: the launch has no residual tensor (host-checked): the 32 registers of the residual tile are not reserved.
+// (convb_tile_stats, defined behind the epilogue, is its statistics tail: the dual-phase upsampling conv calls it per phase)
+template <int MT, int NT, bool SHALF>
+__device__ __forceinline__ void convb_tile_stats(const ConvArgs& a, const f32x16 (&acc)[MT][NT], int pix0, int b, int ct, int kh,
+                                                 int l31, int tid, float* sb, int sp_tile, int tile_mult);
 template <int NT, bool FUSE2, int MT = 2, bool STATS = true, bool OCT = true, bool SHALF = false, bool NORES = false, bool NTS = false>
 __device__ __forceinline__ void convb_epilogue(const ConvArgs& a, f32x16 (&acc_hi)[MT][NT], f32x16 (&acc_lo)[MT][NT],
                                                const int (&pix)[NT], int b, int ct, int kh, int l31, int tid, char* lds,
@@ -1278,8 +1282,17 @@ __device__ __forceinline__ void convb_epilogue(const ConvArgs& a, f32x16 (&acc_h
         }
     }
     LNS_ETS(4)
+    if (stats) convb_tile_stats<MT, NT, SHALF>(a, acc, pix[0], b, ct, kh, l31, tid, sb, sp_tile, tile_mult);
+}
+
+// GroupNorm tile partials of one stored tile (the tail of convb_epilogue; the dual-phase upsampling conv, conv3_up2d.inc,
+// calls it once per column phase): acc is the final register tile, sb the LDS scratch ([TM][SROW] floats + the masks, or
+// [32][SROW] with SHALF), already filled by the caller unless SHALF.  Block-uniform call, every thread of the block.
+template <int MT, int NT, bool SHALF>
+__device__ __forceinline__ void convb_tile_stats(const ConvArgs& a, const f32x16 (&acc)[MT][NT], int pix0, int b, int ct, int kh,
+                                                 int l31, int tid, float* sb, int sp_tile, int tile_mult) {
+    constexpr int TM = 32 * MT, SROW = 133;
     constexpr int SROWS = SHALF ? 32 : TM;          // channel rows of the scratch tile per pass
-    if (stats)
     for (int hf = 0; hf < (SHALF ? MT : 1); ++hf) {
         if (SHALF) {      // this half's 32 channels of the (final) register tile -> scratch
             if (hf) __syncthreads();                 // the previous half has been read
@@ -1292,7 +1305,7 @@ __device__ __forceinline__ void convb_epilogue(const ConvArgs& a, f32x16 (&acc_h
         }
         // ragged single tile (ConvArgs::stat_count valid pixels): which of a wave's 32 pixels exist, one word per wave
         unsigned* smask = reinterpret_cast<unsigned*>(sb + SROWS * SROW);
-        const unsigned long long have = __builtin_amdgcn_ballot_w64(pix[0] >= 0);     // (all lanes: lanes 0..31 are the wave's pixels)
+        const unsigned long long have = __builtin_amdgcn_ballot_w64(pix0 >= 0);     // (all lanes: lanes 0..31 are the wave's pixels)
         if (a.stat_count && (tid & 63) == 0) smask[tid >> 6] = (unsigned)have;
         __syncthreads();
         const int c = tid >> 2, q = tid & 3;
@@ -2545,6 +2558,7 @@ hipError_t launch_conv_up2r(const ConvArgs& a, hipStream_t s);
 hipError_t launch_conv_up2q(const ConvArgs& a, hipStream_t s);
 hipError_t launch_conv_w8(const ConvArgs& a, hipStream_t s);
 bool convw8_fits(const ConvArgs& a);
+hipError_t launch_conv_up2d(const ConvArgs& a, hipStream_t s);
 hipError_t launch_conv_bf16x3(int variant, const ConvArgs& a, hipStream_t s) {
     if (!convb_fits(a)) return hipErrorInvalidValue;
     if (cv_is_f16x2_3x3(variant) && !has_act_bound(a)) return hipErrorInvalidValue;
@@ -2558,6 +2572,7 @@ hipError_t launch_conv_bf16x3(int variant, const ConvArgs& a, hipStream_t s) {
         return hipGetLastError();
     }
     if (a.x_oct && (a.up2 >= 2 || a.w8 == 1)) return hipErrorInvalidValue;       // (these forms read planar tensors)
+    if (variant == CV_F64 && a.up2 == 4) return launch_conv_up2d(a, s);     // both column phases per block (conv3_up2d.inc): the planner's form
     if (variant == CV_F64 && a.up2 == 3) return launch_conv_up2q(a, s);     // all four phases per block, two blocks per CU (conv3_up2q.inc)
     if (variant == CV_F64 && a.up2 == 2) return launch_conv_up2r(a, s);     // ... with the source patch resident in LDS (conv3_up2r.inc)
     // OCT8 tensors (ConvArgs::x_oct / y_oct): whole octets, 32-bit byte offsets
@@ -2624,6 +2639,9 @@ hipError_t launch_conv_bf16x3(int variant, const ConvArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
 }
+
+// The dual-phase form of the upsampling conv: one block per (source tile, row phase), both column phases (ConvArgs::up2 == 4)
+#include "conv3_up2d.inc"
 
 // Four kernel forms that were built, proven bit-identical to the shipped kernels and MEASURED SLOWER or neutral (DESIGN.md
 // sections 6d, 6e): producer / consumer waves (conv3_pc.inc), the resident-weights upsampling conv (conv3_up2r.inc), the 8-wave
@@ -5320,6 +5338,7 @@ hipError_t init_kernels() {
 #define LNS_SET_LDS(k)                                                                            \
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds); \
     if (e != hipSuccess) return e;
+    LNS_SET_LDS(conv3_up2d_kernel)
 #ifdef LNS_EXPERIMENTAL
     LNS_SET_LDS((conv3_up2q_kernel<true>))
     LNS_SET_LDS((conv3_up2q_kernel<false>))

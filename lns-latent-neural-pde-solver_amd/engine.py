@@ -364,7 +364,9 @@ class Engine:
         Results never depend on the others.  "fa_fused" (default 2; 1 = single-buffered kernel, same bits; 0 = off) selects
         the arithmetic form of FABlock2D at 64 x 64 planes (in_proj inside the sandwich kernel): ~2e-7 relative on the fields.
         "fold_linear" (default 1; 0 = off) runs a convolution directly followed by a 1x1 convolution as one convolution on
-        weights composed at load_weights: the same order of difference."""
+        weights composed at load_weights: the same order of difference.
+        "up2_dual" (default 1; 0 = the per-phase form everywhere) picks the kernel form of the upsampling 3x3 convolutions:
+        the same bits either way."""
         self._check(self._L.lns_set_option(self._h, name.encode(), int(value)), "lns_set_option")
         self.options[name] = int(value)
         self._ws.clear()                      # the workspace size depends on the options
