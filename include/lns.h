@@ -366,6 +366,53 @@ int lns_rollout_latent_ensemble_eval(lns_engine* e, const float* z_in, const flo
                                      float* mean_out, float* var_out, float* z_last,
                                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ensemble quantiles: per-pixel quantiles and exceedance probabilities over the members -----------------------
+ * lns_rollout_latent_ensemble with, per kept step and pixel, quantiles of the M member values (a median, a 5-95 % band, the
+ * envelope) and the probability that the field exceeds a threshold: what a forecast user without a truth takes from an
+ * ensemble, and for a clamped or wall-zeroed channel what mean and variance do not say.  Each needs the M member values of
+ * a pixel at the same time, i.e. the [B*M, n_keep, Cin, Ly, Lx] tensor the ensemble call exists to avoid.  The chain, the
+ * kept steps, the frame buffers and the workspace are those of lns_rollout_latent_ensemble; a quantile kernel follows the
+ * decode of a group on its decode stream (one pixel per thread, grid over pixel tiles and planes).
+ *
+ * The statement, for one pixel of plane (b, kept step i, channel c):
+ *     v_m = D_c(f_m), D_c the map of lns_eval_spec as written above for lns_rollout_latent_ensemble_eval (product and sum
+ *     rounded one by one, wall-zero and clamp flags included; eps unused); norm == NULL: v_m = f_m, in normalised units as
+ *     mean_out is.
+ *     The M values are sorted ascending by the total order of their IEEE bit patterns:
+ *         key(x) = bits ^ (sign ? 0xFFFFFFFF : 0x80000000), compared as unsigned
+ *     (-0 below +0, NaNs ordered by their sign): the sorted sequence v_(0) <= ... <= v_(M-1) is unique, any sorting algorithm
+ *     gives the same bits.
+ *     Quantile position of the probability p_k, 0 <= p <= 1, on the host in double:
+ *         h = p (M - 1);  lo = floor(h);  frac = (float)(h - lo);  lo = M - 1 forces frac = 0
+ *     Quantile value (numpy's and torch's "linear" definition), fp32, nothing fused:
+ *         frac == 0:  Q_k = v_(lo)
+ *         otherwise:  d = v_(lo+1) - v_(lo);  t = frac * d;  Q_k = v_(lo) + t
+ *     so p = 0 is the member minimum and p = 1 the maximum.
+ *     Exceedance probability of the threshold thr[k][c] (in the units of v):
+ *         P_k = (float)#{m : v_m > thr[k][c]} / (float)M                        (a NaN compares false)
+ * There is no reduction across pixels: no plane sums, no finish kernel, no atomics; a result depends on its M inputs only,
+ * never on the grouping or the scheduling options.
+ *
+ * lns_ensemble_quantile_spec: n_q probabilities q[0 .. n_q) and n_thr thresholds thr[k][c], c < in_channels; size =
+ * sizeof(lns_ensemble_quantile_spec) and reserved = 0. */
+typedef struct lns_ensemble_quantile_spec {
+    uint32_t size; int32_t n_q, n_thr; uint32_t reserved; /* 0 */
+    double q[8];          /* probabilities in [0, 1] */
+    float  thr[8][8];     /* thr[k][c], c < in_channels */
+} lns_ensemble_quantile_spec;
+
+/* z_in, param, keep_steps_host, z_last, B, M, T: as lns_rollout_latent_ensemble, with 1 <= M <= 128.
+ * norm (nullable): the denormalisation; quant_out [B][n_keep][n_q][Cin][Ly][Lx] (needed when n_q > 0), prob_out
+ * [B][n_keep][n_thr][Cin][Ly][Lx] (needed when n_thr > 0; in_channels <= 8); n_q, n_thr in 0 .. 8, not both 0.  mean_out / var_out (both
+ * nullable; var_out needs mean_out and M >= 2): lns_rollout_latent_ensemble's outputs, same bits; the reduction kernel runs
+ * only when mean_out is given.  workspace: lns_rollout_ensemble_workspace_bytes(B, M), no more.
+ * Trace / timing modes, lns_check_finite (with B*M) and the status codes: as lns_rollout_latent_ensemble. */
+int lns_rollout_latent_ensemble_quantiles(lns_engine* e, const float* z_in, const float* param, int B, int M, int T,
+                                          const int* keep_steps_host, int n_keep, const lns_ensemble_quantile_spec* qspec,
+                                          const lns_eval_spec* norm /* nullable */, float* quant_out, float* prob_out,
+                                          float* mean_out, float* var_out, float* z_last,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- streaming validation: energy spectra of forecast, truth and error ---------------------------------------------
  * lns_rollout_eval / lns_rollout_latent_eval with, for selected steps, the shell-summed energy spectra of the forecast,
  * of the truth and of their difference, taken where the step is decoded: a spectrum needs the whole plane of a step, i.e.
@@ -836,7 +883,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * lns_rollout_latent_eval_stats and lns_op_field_stats are there; "eval_maps" = lns_rollout_eval_maps,
  * lns_rollout_latent_eval_maps, their size query, lns_op_time_maps and lns_time_maps_state_bytes are there;
  * "op_conv_gn" = lns_op_conv_gn is there; "op_fa_fused" = lns_op_fa_fused is there; "eval_attrib" = lns_rollout_eval_attrib, lns_rollout_latent_eval_attrib, their
- * size query, lns_autoencode_eval, its size query, lns_op_eval_attrib and lns_op_latent_err are there.
+ * size query, lns_autoencode_eval, its size query, lns_op_eval_attrib and lns_op_latent_err are there;
+ * "ensemble_quantiles" = lns_rollout_latent_ensemble_quantiles and lns_op_ensemble_quantiles are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
@@ -971,6 +1019,14 @@ int lns_op_ensemble_stats(const float* frames, int B, int M, int64_t per, float*
 int lns_op_ensemble_score(const float* frames, const float* y, int n, int B, int M, int C, int H, int W,
                           const lns_eval_spec* spec, float* scores_out, float* seq_out, int32_t* rank_out,
                           float* pixel_out, void* stream);
+
+/* The kernel of lns_rollout_latent_ensemble_quantiles on stored member fields, without an engine: frames
+ * [n][B][M][C][H][W] (the layout of a frame buffer) -> quant_out [B][n][n_q][C][H][W] and prob_out [B][n][n_thr][C][H][W] by the
+ * statement written there; norm nullable (the members as they are).  1 <= M <= 128, B in 1..65535, n * B * C < 2^31; the
+ * per-channel form needs C <= 8.  Checks precede the launch (message: lns_create_error()); the call synchronises `stream`. */
+int lns_op_ensemble_quantiles(const float* frames, int n, int B, int M, int C, int H, int W,
+                              const lns_ensemble_quantile_spec* qspec, const lns_eval_spec* norm /* nullable */,
+                              float* quant_out, float* prob_out, void* stream);
 
 /* The spectrum kernel of lns_rollout_eval_spectrum on stored fields, without an engine: yhat and y (nullable) [B][T][C][H][W],
  * normalised -> out [B][T][C][K][S], K = 3 (forecast, truth, error) when y is given, K = 1 (the forecast's row, same bits) when

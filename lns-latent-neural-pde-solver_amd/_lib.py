@@ -71,6 +71,14 @@ class LnsEvalSpec(ctypes.Structure):
     ]
 
 
+class LnsEnsembleQuantileSpec(ctypes.Structure):
+    """Mirror of `struct lns_ensemble_quantile_spec` (include/lns.h): the probabilities and thresholds of the ensemble quantiles."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("n_q", _I32), ("n_thr", _I32), ("reserved", ctypes.c_uint32),
+        ("q", ctypes.c_double * 8), ("thr", (ctypes.c_float * LNS_METRIC_MAX_CH) * 8),
+    ]
+
+
 LNS_FIELD_STATS = 12
 
 
@@ -155,6 +163,7 @@ SYMBOLS = [
     "lns_rollout_select_workspace_bytes", "lns_rollout_select", "lns_rollout_latent_select",
     "lns_rollout_ensemble_workspace_bytes", "lns_rollout_latent_ensemble", "lns_op_ensemble_stats",
     "lns_rollout_latent_ensemble_eval", "lns_op_ensemble_score",
+    "lns_rollout_latent_ensemble_quantiles", "lns_op_ensemble_quantiles",
     "lns_spectrum_bins", "lns_rollout_eval_spectrum", "lns_rollout_latent_eval_spectrum", "lns_op_energy_spectrum",
     "lns_rollout_eval_stats", "lns_rollout_latent_eval_stats", "lns_op_field_stats",
     "lns_rollout_eval_maps_workspace_bytes", "lns_rollout_eval_maps", "lns_rollout_latent_eval_maps",
@@ -248,6 +257,10 @@ def lib():
         sp, ip = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int)
         L.lns_rollout_latent_ensemble_eval.argtypes = [vp, vp, vp, vp, i, i, i, ip, i, sp, vp, vp, vp, vp, vp, vp, vp, c.c_size_t, vp]
         L.lns_op_ensemble_score.argtypes = [vp, vp, i, i, i, i, i, i, sp, vp, vp, vp, vp, vp]
+    if hasattr(L, "lns_rollout_latent_ensemble_quantiles"):
+        sp, ip, qp = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.POINTER(LnsEnsembleQuantileSpec)
+        L.lns_rollout_latent_ensemble_quantiles.argtypes = [vp, vp, vp, i, i, i, ip, i, qp, sp, vp, vp, vp, vp, vp, vp, c.c_size_t, vp]
+        L.lns_op_ensemble_quantiles.argtypes = [vp, i, i, i, i, i, i, qp, sp, vp, vp, vp]
     if hasattr(L, "lns_rollout_eval_spectrum"):
         sp, ip = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int)
         L.lns_spectrum_bins.argtypes = [i, i]

@@ -1785,7 +1785,8 @@ struct Runner {
 //   SINK_ENSEMBLE the chain runs at batch N = B * M (launch sample b * M + m is member m of trajectory b); the steps
 //                 keep[0 .. n_keep) are decoded into a frame buffer of the workspace and reduced over the members right there
 //                 into `out` (mean) and `var_out` [B][n_keep][xper]; with `scores_out` (lns_rollout_latent_ensemble_eval) also
-//                 scored there against y_true, and `out` may be null
+//                 scored there against y_true, and `out` may be null; with `qspec` (lns_rollout_latent_ensemble_quantiles) the
+//                 members' quantiles and exceedance probabilities are taken there too, and `out` may be null
 enum SinkKind { SINK_LATENTS, SINK_STEPS, SINK_KEPT, SINK_SCORED, SINK_ENSEMBLE };
 
 // workspace layout: [ z0 | latent ring: NGROUP groups x kdec steps x [B][zper] | NDEC decode arenas | propagator arena ]
@@ -1931,6 +1932,9 @@ struct RolloutCall {
     int traj = 0, M = 0; float* var_out = nullptr;
     // SINK_ENSEMBLE with ens_scored: y_true [traj][n_keep], spec and seq_out below; the plane sums go straight into scores_out
     bool ens_scored = false; float* scores_out = nullptr; int32_t* rank_out = nullptr;
+    // SINK_ENSEMBLE with ens_quant (lns_rollout_latent_ensemble_quantiles): qspec, the outputs it asks for, and `spec` below as the
+    // nullable denormalisation; `out` (the mean) is optional
+    bool ens_quant = false; const lns_ensemble_quantile_spec* qspec = nullptr; float *quant_out = nullptr, *prob_out = nullptr;
     // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
     const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
     float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
@@ -2383,6 +2387,41 @@ static void score_args(const lns_engine* e, const RolloutCall& c, EnsembleScoreA
     score_norm(c.spec, s.C, &s.norm);
 }
 
+// The position of probability p among M sorted members (include/lns.h): h = p (M - 1) in double, lo = floor(h), frac = (float)(h - lo)
+static void quantile_position(double p, int M, int* lo, float* frac) {
+    const double h = p * (double)(M - 1);
+    int l = (int)std::floor(h);
+    float f = (float)(h - (double)l);
+    if (l >= M - 1) { l = M - 1; f = 0.0f; }
+    *lo = l; *frac = f;
+}
+
+// the refusals of a lns_ensemble_quantile_spec and its outputs, in the order of include/lns.h; nullptr: accepted
+static const char* quantile_spec_refusal(const lns_ensemble_quantile_spec* qs, const float* quant_out, const float* prob_out) {
+    if (!qs || qs->size != sizeof(lns_ensemble_quantile_spec)) return "qspec is null or its size field is not sizeof(lns_ensemble_quantile_spec)";
+    if (qs->n_q < 0 || qs->n_q > LNS_QUANTILE_MAX || qs->n_thr < 0 || qs->n_thr > LNS_QUANTILE_MAX || (qs->n_q == 0 && qs->n_thr == 0))
+        return "qspec: n_q and n_thr must be in 0 .. 8 and not both 0";
+    for (int k = 0; k < qs->n_q; ++k)
+        if (!(qs->q[k] >= 0.0 && qs->q[k] <= 1.0)) return "qspec: every probability must be in [0, 1]";
+    if (qs->n_q > 0 && !quant_out) return "quant_out is null but n_q > 0";
+    if (qs->n_thr > 0 && !prob_out) return "prob_out is null but n_thr > 0";
+    return nullptr;
+}
+
+// the quantile kernel's arguments (an accepted qspec; norm nullable); frames / kk / o_T / o_t are the caller's
+static void quantile_args(const lns_ensemble_quantile_spec* qs, const lns_eval_spec* norm, int B, int M, int C, int H, int W,
+                          float* quant_out, float* prob_out, EnsembleQuantileArgs* qp) {
+    EnsembleQuantileArgs& q = *qp;
+    memset(&q, 0, sizeof q);
+    q.quant = quant_out; q.prob = prob_out;
+    q.B = B; q.M = M; q.C = C; q.H = H; q.W = W; q.n_q = qs->n_q; q.n_thr = qs->n_thr;
+    q.denorm = norm != nullptr;
+    if (norm) score_norm(norm, C, &q.norm);
+    for (int k = 0; k < qs->n_q; ++k) quantile_position(qs->q[k], M, &q.lo[k], &q.frac[k]);
+    for (int k = 0; k < qs->n_thr; ++k)
+        for (int ch = 0; ch < LNS_METRIC_MAX_CH; ++ch) q.thr[k][ch] = qs->thr[k][ch];
+}
+
 // the autoregressive loop of every rollout call: zcur -> T x (propagate ; what the sink does)   (train_stage2_ns2d.py:147-156)
 // The latent chain z_t -> z_{t+1} is strictly sequential, but decode(z_t) depends on z_t only: the chain runs ahead
 // (on the engine's side stream when overlapping; own arena) writing groups of `kdec` consecutive decoded latents into
@@ -2443,6 +2482,11 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     if (scored) metric_args(e, c, L, &m);
     EnsembleScoreArgs sc;
     if (ens && c.ens_scored) score_args(e, c, &sc);
+    EnsembleQuantileArgs qa;
+    if (ens && c.ens_quant) {
+        quantile_args(c.qspec, c.spec, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, c.quant_out, c.prob_out, &qa);
+        qa.o_T = c.n_keep;
+    }
     SpectrumArgs sx;
     if (scored && c.spectra) spectrum_args(e, c, &sx);
     FieldStatsArgs fs;
@@ -2598,6 +2642,10 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
             sc.frames = fb; sc.kk = kk; sc.y_t = i0;
             HIPCHK(e, launch_ensemble_score(sc, dstream[d]));
         }
+        if (ens && c.ens_quant) {                    // fb is [kk][traj][M][xper] -> quantiles / probabilities of kept steps i0 .. i0 + kk - 1
+            qa.frames = fb; qa.kk = kk; qa.o_t = i0;
+            HIPCHK(e, launch_ensemble_quantile(qa, dstream[d]));
+        }
         if (ens && c.out) {                          // fb is [kk][traj][M][xper] -> mean / var of out[b][i0 .. i0 + kk)
             EnsembleStatsArgs es;
             es.frames = fb; es.mean = c.out + (long)i0 * xper; es.var = c.var_out ? c.var_out + (long)i0 * xper : nullptr;
@@ -2630,10 +2678,13 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
 static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
     const bool scored = c.sink == SINK_SCORED, ens = c.sink == SINK_ENSEMBLE, kept = c.sink == SINK_KEPT || ens;
     const bool ens_scored = ens && c.ens_scored;     // lns_rollout_latent_ensemble_eval: every output but scores_out is optional
+    const bool ens_quant = ens && c.ens_quant;       // lns_rollout_latent_ensemble_quantiles: the mean is optional
     if (!c.start) return einval(e, c.encode ? "x is null" : "z_in is null");
     if ((scored || ens_scored) && !c.y_true) return einval(e, "y_true is null");
     if (ens_scored && !c.scores_out) return einval(e, "scores_out is null");
-    if (!scored && !ens_scored && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
+    if (ens_quant)
+        if (const char* why = quantile_spec_refusal(c.qspec, c.quant_out, c.prob_out)) return einval(e, why);
+    if (!scored && !ens_scored && !ens_quant && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
     if ((ens ? c.traj : c.B) <= 0) return einval(e, "B must be positive");
     if (ens && c.M <= 0) return einval(e, "M must be positive");
     if (c.T <= 0) return einval(e, "T must be positive");
@@ -2641,6 +2692,13 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
     if (ens_scored) {
         if (c.M < 2 || c.M > LNS_SCORE_MAX_MEMBERS) return einval(e, "ensemble scoring needs M in 2 .. 128");
         if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
+    }
+    if (ens_quant) {
+        if (c.M > LNS_SCORE_MAX_MEMBERS) return einval(e, "ensemble quantiles need M in 1 .. 128");
+        if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
+        if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
+        if (c.spec && c.spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "norm: the per-channel form needs in_channels <= 8");
+        if (c.qspec->n_thr > 0 && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "thresholds need in_channels <= 8");
     }
     if (scored) {
         if (c.t0 < 0 || (long)c.t0 + c.T > c.T_total) {
@@ -3025,6 +3083,18 @@ int lns_rollout_latent_ensemble_eval(lns_engine* e, const float* z_in, const flo
     return rollout_call(e, c);
 }
 
+// ---- ensemble quantiles (include/lns.h) -------------------------------------------------------------------------
+int lns_rollout_latent_ensemble_quantiles(lns_engine* e, const float* z_in, const float* param, int B, int M, int T,
+                                          const int* keep_steps_host, int n_keep, const lns_ensemble_quantile_spec* qspec,
+                                          const lns_eval_spec* norm, float* quant_out, float* prob_out, float* mean_out,
+                                          float* var_out, float* z_last, void* ws, size_t ws_bytes, void* stream) {
+    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
+    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
+    c.ens_quant = true; c.qspec = qspec; c.spec = norm; c.quant_out = quant_out; c.prob_out = prob_out;
+    c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
+    return rollout_call(e, c);
+}
+
 int lns_check_finite(lns_engine* e, int B, void* ws, size_t ws_bytes, void* stream) {
     if (!e || B <= 0 || !ws) return LNS_EINVAL;
     // The amax vectors live in the CALLER's workspace: they are read through the `ws` handed in here, which must be
@@ -3119,6 +3189,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "rollout_select")) return 1;
     if (!strcmp(feature, "rollout_ensemble")) return 1;
     if (!strcmp(feature, "ensemble_score")) return 1;
+    if (!strcmp(feature, "ensemble_quantiles")) return 1;
     if (!strcmp(feature, "eval_spectrum")) return 1;
     if (!strcmp(feature, "eval_stats")) return 1;
     if (!strcmp(feature, "eval_maps")) return 1;
@@ -3528,6 +3599,29 @@ int lns_op_ensemble_score(const float* frames, const float* y, int n, int B, int
     score_norm(spec, C, &a.norm);
     OPCHK(launch_ensemble_score(a, s));
     OPCHK(launch_ensemble_score_finish(scores_out, B, n, C, H * W, spec->eps, seq_out, s));
+    OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+// ensemble_quantile_kernel on stored member fields: frames [n][B][M][C][H][W] -> quant_out [B][n][n_q][C][H][W], prob_out [B][n][n_thr][C][H][W]
+int lns_op_ensemble_quantiles(const float* frames, int n, int B, int M, int C, int H, int W, const lns_ensemble_quantile_spec* qspec,
+                              const lns_eval_spec* norm, float* quant_out, float* prob_out, void* stream) {
+    if (!frames) { g_create_error = "ensemble_quantiles: frames is null"; return LNS_EINVAL; }
+    if (const char* why = quantile_spec_refusal(qspec, quant_out, prob_out)) { g_create_error = fmt("ensemble_quantiles: %s", why); return LNS_EINVAL; }
+    if (norm && op_spec_refused("ensemble_quantiles", norm)) return LNS_EINVAL;
+    if (M < 1 || M > LNS_SCORE_MAX_MEMBERS) { g_create_error = "ensemble_quantiles: M in 1 .. 128"; return LNS_EINVAL; }
+    if (n < 1 || B < 1 || B > LNS_MAX_BATCH || C < 1 || H < 1 || W < 1 || (int64_t)H * W > (1 << 30) ||
+        (int64_t)n * B * C > 0x7fffffffLL) {
+        g_create_error = "ensemble_quantiles: n >= 1, B in 1..65535, C, H, W >= 1, H * W <= 2^30, n * B * C < 2^31"; return LNS_EINVAL;
+    }
+    if (qspec->n_thr > 0 && C > LNS_METRIC_MAX_CH) { g_create_error = "ensemble_quantiles: thresholds need C <= 8"; return LNS_EINVAL; }
+    if (norm && op_spec_refused("ensemble_quantiles", norm, C)) return LNS_EINVAL;
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EnsembleQuantileArgs a;
+    quantile_args(qspec, norm, B, M, C, H, W, quant_out, prob_out, &a);
+    a.frames = frames; a.kk = n; a.o_T = n; a.o_t = 0;
+    OPCHK(launch_ensemble_quantile(a, s));
     OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
 }

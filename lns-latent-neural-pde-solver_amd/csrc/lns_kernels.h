@@ -425,6 +425,22 @@ hipError_t launch_ensemble_score(const EnsembleScoreArgs& a, hipStream_t s);
 // scores [B][T][C][4] plane sums -> rel_l2, rmse, spread, crps in place; seq (nullable) [B][C][4] over the T steps
 hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int HW, float eps, float* seq, hipStream_t s);
 
+// Ensemble quantiles (lns_rollout_latent_ensemble_quantiles, lns_op_ensemble_quantiles; the statement: include/lns.h): member
+// frames [kk][B][M][C][H*W] -> per pixel the n_q quantiles at the positions (lo[k], frac[k]) of the sorted members into
+// quant[b][o_t + j][k][c][pixel] of quant [B][o_T][n_q][C][H*W], and the n_thr exceedance probabilities of thr[k][c] into
+// prob[b][o_t + j][k][c][pixel] of prob [B][o_T][n_thr][C][H*W].  Grid (pixel tiles of 256, planes (j, b, c)), one pixel per
+// thread; dynamic LDS: M * 1 KB of columns.  denorm = 0: the members as they are (norm unused); else norm, as MetricGroupArgs.
+// 1 <= M <= 128; lo[k] + 1 < M wherever frac[k] != 0.  q0: the launch's first plane (set by the launcher).
+#define LNS_QUANTILE_MAX 8
+struct EnsembleQuantileArgs {
+    const float* frames; float* quant; float* prob;
+    int B, M, C, H, W, kk, o_T, o_t, n_q, n_thr, denorm, q0;
+    ScoreNorm norm;
+    int lo[LNS_QUANTILE_MAX]; float frac[LNS_QUANTILE_MAX];
+    float thr[LNS_QUANTILE_MAX][LNS_METRIC_MAX_CH];
+};
+hipError_t launch_ensemble_quantile(const EnsembleQuantileArgs& a, hipStream_t s);
+
 // Energy spectra (lns_rollout_eval_spectrum, lns_op_energy_spectrum; the statement: include/lns.h): one block per plane
 // writes its K x S shell energies, K = 3 (forecast, truth, error) with y, K = 1 (forecast) without; S = lns_spectrum::bins(H, W).
 // Group form: frames [kk][B][C][H*W] (a decode stream's frame buffer); the n <= 8 selected steps sel[0 .. n) of the group

@@ -5296,6 +5296,7 @@ hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int 
 #include "field_stats.inc"
 #include "time_maps.inc"
 #include "eval_attrib.inc"
+#include "ensemble_quantile.inc"
 
 // per-sample max |x| of a [B, n] tensor: grid (chunks, B); one atomic per wave
 __global__ __launch_bounds__(256) void amax_kernel(const float* x, long x_bs, long n, unsigned* amax) {
@@ -5460,6 +5461,7 @@ hipError_t init_kernels() {
     LNS_SET_LDS(fa_pool_kernel)
     LNS_SET_LDS(fa_reducer_kernel)
     LNS_SET_LDS(ensemble_score_kernel)                                   // 128 members: 128 KB of columns
+    LNS_SET_LDS(ensemble_quantile_kernel)                                // likewise
 #undef LNS_SET_LDS
     return hipSuccess;
 }

@@ -504,6 +504,32 @@ class LatentDynamics(_Hosted):
         return self._engine(z).rollout_latent_ensemble(z, steps, param=param, keep_steps=keep_steps, return_var=return_var)
 
     @torch.no_grad()
+    def predict_quantiles(self, x, steps, *rest, quantiles=(0.05, 0.5, 0.95), thresholds=(), generator=None, control=True,
+                          keep_steps=None, return_mean=False, return_var=False, **norm):
+        """predict_quantiles(x, steps, members, noise_level) -- conditional: predict_quantiles(x, steps, param, members,
+        noise_level): the ensemble forecast of `predict_ensemble` (same encode, same noise from the same generator state, same
+        `control`) summarised per kept step and pixel by quantiles of the member values (a median, a band, the envelope)
+        and by the share of the members above each threshold -- what a clamped or wall-zeroed channel needs where a mean and
+        a variance say little.  Returns engine.EnsembleQuantiles; return_mean / return_var add predict_ensemble's mean and
+        variance (same bits).  thresholds: scalars or per-channel sequences, in the units of the values; `norm` as in
+        `validate` (none: normalised values); keep_steps as for predict."""
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("predict_quantiles() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if len(rest) != 2:
+            raise TypeError("predict_quantiles() takes (x, steps, param, members, noise_level)" if self._conditional
+                            else "predict_quantiles() takes (x, steps, members, noise_level)")
+        members, noise_level = int(rest[0]), float(rest[1])
+        if members < 1:
+            raise LnsError("members must be at least 1, got %d" % members)
+        z = self._ensemble_latents(x, members, noise_level, generator, control)
+        return self._engine(z).rollout_latent_ensemble_quantiles(z, steps, quantiles=quantiles, thresholds=thresholds, param=param,
+                                                                 keep_steps=keep_steps, return_mean=return_mean,
+                                                                 return_var=return_var, **norm)
+
+    @torch.no_grad()
     def validate_ensemble(self, x, y, *rest, generator=None, control=True, keep_steps=None, **norm):
         """validate_ensemble(x, y, members, noise_level, **norm) -- conditional: validate_ensemble(x, y, param, members,
         noise_level, **norm): the ensemble forecast of `predict_ensemble` over T = y.shape[1] steps (same encode, same noise

@@ -190,6 +190,36 @@ EnsembleScores.__doc__ = """Result of Engine.rollout_latent_ensemble_eval / ense
 [B, n_keep, C, M + 1] int32 or None, and mean, var, z_last where asked for (None otherwise)."""
 
 
+EnsembleQuantiles = collections.namedtuple("EnsembleQuantiles", "quantiles prob mean var z_last")
+EnsembleQuantiles.__doc__ = """Result of Engine.rollout_latent_ensemble_quantiles / ensemble_quantiles: quantiles
+[B, n_keep, n_q, C, Ly, Lx] (None without a probability), prob [B, n_keep, n_thr, C, Ly, Lx], the share of the members above each
+threshold (None without a threshold), and mean, var, z_last where asked for (None otherwise)."""
+
+
+def quantile_spec(C, members, quantiles=(), thresholds=()):
+    """`lns_ensemble_quantile_spec` from the probabilities and the thresholds (each a scalar for every channel, or a
+    per-channel sequence); pure host code, so a bad request is refused before any device use."""
+    from . import metrics
+    quantiles = [float(q) for q in quantiles]
+    metrics.quantile_positions(quantiles, max(1, int(members)))           # (refuses a probability outside [0, 1])
+    rows = metrics.threshold_table(thresholds, C)
+    if len(quantiles) > 8 or len(rows) > 8:
+        raise ValueError("at most 8 quantiles and 8 thresholds per call")
+    if not quantiles and not rows:
+        raise ValueError("neither a quantile nor a threshold was asked for")
+    if rows and C > _lib.LNS_METRIC_MAX_CH:
+        raise ValueError("thresholds: at most %d channels" % _lib.LNS_METRIC_MAX_CH)
+    spec = _lib.LnsEnsembleQuantileSpec()
+    spec.size = ctypes.sizeof(_lib.LnsEnsembleQuantileSpec)
+    spec.n_q, spec.n_thr = len(quantiles), len(rows)
+    for k, q in enumerate(quantiles):
+        spec.q[k] = q
+    for k, row in enumerate(rows):
+        for c, v in enumerate(row):
+            spec.thr[k][c] = v
+    return spec
+
+
 EvalSpectra = collections.namedtuple("EvalSpectra", "frame seq frames spectra spectrum_steps")
 EvalSpectra.__doc__ = """Result of Engine.rollout_eval_spectrum: frame [B, T, C], seq [B, C] and frames (or None) as rollout_eval
 returns them, spectra [B, len(spectrum_steps), C, 3, S] (rows: forecast, truth, error; S = metrics.spectrum_bins(Ly, Lx)) and
@@ -695,6 +725,72 @@ class Engine:
                 seq.data_ptr(), self._ptr(rank), self._ptr(mean), self._ptr(var), self._ptr(z_last), ws.data_ptr(), ws.numel(),
                 self._stream(z)), "lns_rollout_latent_ensemble_eval")
         return self._scores_result(scores, seq, rank, mean, var, z_last)
+
+    # -- ensemble quantiles (include/lns.h "ensemble quantiles") -------------------------------------------------------
+    def ensemble_quantiles(self, frames, quantiles=(), thresholds=(), **norm):
+        """The quantile kernel on stored member fields (lns_op_ensemble_quantiles): frames [n, B, M, C, H, W] (a frame
+        buffer's layout), normalised; quantiles: probabilities in [0, 1]; thresholds: each a scalar (every channel) or a
+        per-channel sequence, in the units of the denormalised values; `norm` as in `rollout_eval` (none: the values as they
+        are).  Returns EnsembleQuantiles (mean, var, z_last None)."""
+        import torch
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.float32 or frames.dim() != 6:
+            raise LnsError("ensemble_quantiles takes an fp32 HIP tensor [n, B, M, C, H, W]")
+        n, B, M, C, H, W = (int(v) for v in frames.shape)
+        frames = frames.contiguous()
+        qs = quantile_spec(C, M, quantiles, thresholds)
+        spec = eval_spec(C, **norm) if norm else None
+        quant = torch.empty((B, n, qs.n_q, C, H, W), dtype=torch.float32, device=frames.device) if qs.n_q else None
+        prob = torch.empty((B, n, qs.n_thr, C, H, W), dtype=torch.float32, device=frames.device) if qs.n_thr else None
+        with torch.cuda.device(frames.device):
+            rc = self._L.lns_op_ensemble_quantiles(frames.data_ptr(), n, B, M, C, H, W, ctypes.byref(qs),
+                                                   ctypes.byref(spec) if spec is not None else None, self._ptr(quant),
+                                                   self._ptr(prob), self._stream(frames))
+        if rc != 0:
+            raise LnsError("lns_op_ensemble_quantiles failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return EnsembleQuantiles(quant, prob, None, None, None)
+
+    def rollout_latent_ensemble_quantiles(self, z, steps, quantiles=(0.05, 0.5, 0.95), thresholds=(), param=None, keep_steps=None,
+                                          return_mean=False, return_var=False, return_last=False, **norm):
+        """rollout_latent_ensemble with, per kept step and pixel, quantiles of the member values and the share of the members
+        above each threshold, taken as the members are decoded: z [B, M, c, h, w] as there (1 <= M <= 128); quantiles:
+        probabilities in [0, 1] (numpy's "linear" definition; 0 / 1: the member minimum / maximum); thresholds: each a scalar
+        (every channel) or a per-channel sequence, in the units of the values; `norm` as in `rollout_eval` -- without it the
+        values are normalised, as the mean is.  Returns EnsembleQuantiles; return_mean / return_var / return_last add
+        rollout_latent_ensemble's outputs.  The member fields are never stored; the workspace is rollout_latent_ensemble's."""
+        import torch
+        z = self._dev(z)
+        C, H, W = self.latent_shape()
+        c = self.cfg
+        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
+            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
+        B, M = int(z.shape[0]), int(z.shape[1])
+        if return_var and not return_mean:
+            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
+        if return_var and M < 2:
+            raise LnsError("the variance needs at least 2 members, got M = %d" % M)
+        steps = int(steps)
+        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
+        arr = (ctypes.c_int * len(keep))(*keep)
+        nk = len(keep)
+        qs = quantile_spec(c.in_channels, M, quantiles, thresholds)
+        spec = eval_spec(c.in_channels, **norm) if norm else None
+        tail = (c.in_channels, c.Ly, c.Lx)
+        quant = torch.empty((B, nk, qs.n_q) + tail, dtype=torch.float32, device=z.device) if qs.n_q else None
+        prob = torch.empty((B, nk, qs.n_thr) + tail, dtype=torch.float32, device=z.device) if qs.n_thr else None
+        mean = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_mean else None
+        var = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_var else None
+        z_last = torch.empty_like(z) if return_last else None
+        p = self._member_param(param, z, B, M)
+        with torch.cuda.device(z.device):
+            n = ctypes.c_size_t(0)
+            self._check(self._L.lns_rollout_ensemble_workspace_bytes(self._h, B, M, ctypes.byref(n)),
+                        "lns_rollout_ensemble_workspace_bytes")
+            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+            self._check(self._L.lns_rollout_latent_ensemble_quantiles(
+                self._h, z.data_ptr(), self._ptr(p), B, M, steps, arr, nk, ctypes.byref(qs),
+                ctypes.byref(spec) if spec is not None else None, self._ptr(quant), self._ptr(prob), self._ptr(mean), self._ptr(var),
+                self._ptr(z_last), ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_quantiles")
+        return EnsembleQuantiles(quant, prob, mean, var, z_last)
 
     # -- streaming validation rollout (include/lns.h "streaming validation rollout") --------------------------------
     def _eval_common(self, first, y, steps, t0, keep_steps, norm):

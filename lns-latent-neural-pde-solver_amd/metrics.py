@@ -271,6 +271,111 @@ def spread_skill_ratio(scores, members):
     return scores.spread * float((members + 1) / members) ** 0.5 / scores.rmse
 
 
+def quantile_positions(quantiles, members):
+    """[(lo, frac)] of the probabilities among `members` sorted values, as include/lns.h states it: h = p (M - 1) in double,
+    lo = floor(h), frac = (float)(h - lo), and lo = M - 1 forces frac = 0."""
+    import math
+    import numpy as np
+    M = int(members)
+    out = []
+    for p in quantiles:
+        p = float(p)
+        if not 0.0 <= p <= 1.0:                                   # (a NaN fails both comparisons)
+            raise ValueError("a quantile's probability must be in [0, 1], got %r" % (p,))
+        h = p * (M - 1)
+        lo = int(math.floor(h))
+        frac = float(np.float32(h - lo))
+        out.append((M - 1, 0.0) if lo >= M - 1 else (lo, frac))
+    return out
+
+
+def threshold_table(thresholds, C):
+    """thresholds (each a scalar for every channel, or a per-channel sequence of C values) -> [[float] * C] per threshold."""
+    rows = []
+    for t in thresholds:
+        row = [float(t)] * C if isinstance(t, (int, float)) else [float(v) for v in t]
+        if len(row) != C:
+            raise ValueError("a per-channel threshold needs %d entries, got %d" % (C, len(row)))
+        rows.append(row)
+    return rows
+
+
+def _denormalise(x, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
+    """D_c of include/lns.h on x [..., C, H, W] in unfused fp32 torch ops: x * std_c + mean_c (the product and the sum rounded on
+    their own), 0 on the wall rows / columns of `zero_wall_channels`, fmin(fmax(., lo), hi) on `clamp_channels`."""
+    C, H, W = x.shape[-3:]
+
+    def per_c(v):
+        v = [float(v)] * C if isinstance(v, (int, float)) else [float(e) for e in v]
+        if len(v) != C:
+            raise ValueError("per-channel statistics need %d entries" % C)
+        return torch.tensor(v, dtype=torch.float32, device=x.device).view(C, 1, 1)
+    p = x * per_c(std)
+    v = p + per_c(mean)
+    if len(zero_wall_channels) > 0:
+        mask = torch.zeros((C, H, W), dtype=torch.bool, device=x.device)
+        for c in zero_wall_channels:
+            mask[c, 0, :] = mask[c, -1, :] = True
+            mask[c, :, 0] = mask[c, :, -1] = True
+        v = torch.where(mask, torch.zeros_like(v), v)
+    if len(clamp_channels) > 0:
+        lo = torch.tensor(float(clamp[0]), dtype=torch.float32, device=x.device)
+        hi = torch.tensor(float(clamp[1]), dtype=torch.float32, device=x.device)
+        sel = torch.zeros((C, 1, 1), dtype=torch.bool, device=x.device)
+        for c in clamp_channels:
+            sel[c] = True
+        v = torch.where(sel.expand(C, H, W), torch.fmin(torch.fmax(v, lo), hi), v)
+    return v
+
+
+def sort_by_bits(v, dim=0):
+    """fp32 `v` sorted ascending along `dim` by the total order of the IEEE bit patterns (include/lns.h):
+    key(x) = bits ^ (sign ? 0xFFFFFFFF : 0x80000000) compared as unsigned -- held in int64, sorted, and mapped back, so -0 lies
+    below +0, NaNs are ordered by their sign, and the result is the same bits whatever the sorting algorithm."""
+    bits = v.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    key = bits ^ torch.where(bits >= 0x80000000, torch.full_like(bits, 0xFFFFFFFF), torch.full_like(bits, 0x80000000))
+    key = key.sort(dim=dim).values
+    bits = key ^ torch.where(key >= 0x80000000, torch.full_like(key, 0x80000000), torch.full_like(key, 0xFFFFFFFF))
+    bits = torch.where(bits >= 0x80000000, bits - 0x100000000, bits)
+    return bits.to(torch.int32).view(torch.float32)
+
+
+@torch.no_grad()
+def ensemble_quantiles(fields, quantiles=(), thresholds=(), **norm):
+    """The stored-path statement of Engine.rollout_latent_ensemble_quantiles / ensemble_quantiles (include/lns.h "ensemble
+    quantiles") in unfused fp32 torch ops, on whatever device `fields` lives on: fields [B, M, n, C, H, W], the stored member
+    rollouts -> (quantiles [B, n, n_q, C, H, W] or None, prob [B, n, n_thr, C, H, W] or None).  `norm` as in `relative_l2`
+    (none: the values as they are).  It needs the member fields the streaming call never stores: for checks and small cases."""
+    if fields.dim() != 6 or fields.dtype != torch.float32:
+        raise ValueError("expected fp32 member fields [B, M, n, C, H, W]")
+    B, M, n, C, H, W = fields.shape
+    pos = quantile_positions(quantiles, M)
+    thr = threshold_table(thresholds, C)
+    if not pos and not thr:
+        raise ValueError("neither a quantile nor a threshold was asked for")
+    v = _denormalise(fields, **norm) if norm else fields
+    v = sort_by_bits(v.permute(1, 0, 2, 3, 4, 5), dim=0)                 # [M, B, n, C, H, W]
+    quant = prob = None
+    if pos:
+        rows = []
+        for lo, frac in pos:
+            if frac == 0.0:
+                rows.append(v[lo])
+                continue
+            d = v[lo + 1] - v[lo]
+            t = torch.full_like(d, frac) * d
+            rows.append(v[lo] + t)
+        quant = torch.stack(rows, 2)
+    if thr:
+        fm = torch.full((B, n, C, H, W), float(M), dtype=torch.float32, device=fields.device)
+        rows = []
+        for row in thr:
+            th = torch.tensor(row, dtype=torch.float32, device=fields.device).view(C, 1, 1)
+            rows.append((v > th).sum(0).to(torch.float32) / fm)
+        prob = torch.stack(rows, 2)
+    return quant, prob
+
+
 def sw_norm(u_mean, u_std, v_mean, v_std, pres_mean, pres_std):
     """Keyword arguments for encode_dataset restating Stage2_SW.normalize (dataset/Stage2_SW.py:74-78): channels
     (u, v, pres), each by its own statistics, no epsilon."""
