@@ -14,6 +14,7 @@
 #include <tuple>
 #include <stdexcept>
 
+#include "lns_conv_launch.h"
 #include "lns_engine.h"
 #include "lns_fold.h"
 #include "lns_resolve.h"
@@ -47,36 +48,7 @@ static std::string fmt(const char* f, ...) {
 
 static size_t round_up_sz(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
-// ---------------------------------------------------------------------------
-// host helpers shared by the planner and the op-level test entry points
-// ---------------------------------------------------------------------------
-// legacy 'nearest': src = min(floor(dst*scale), in-1), scale = in/out in fp32 unless given
-// (F.interpolate(scale_factor=2.0) basics.py:296 -> scale 0.5; nn.Upsample(size) autoencoder2d.py:134)
-static int nearest_src(int dst, int in, int out, float scale) {
-    if (in == out) return dst;
-    const float sc = scale > 0.0f ? scale : (float)in / (float)out;
-    int s = (int)floorf((float)dst * sc);
-    return s < in - 1 ? s : in - 1;
-}
-
-// padded/virtual coordinate -> source index (or -1 = zero).  `len` entries.
-static void build_axis_map(std::vector<int>& out, int len, int in, int virt, float scale, int pad_lo, int pad_hi,
-                           int mode) {
-    out.resize(len);
-    for (int p = 0; p < len; ++p) {
-        int u = p - pad_lo;
-        int src = -1;
-        if (p < virt + pad_lo + pad_hi) {
-            if (u < 0 || u >= virt) {
-                if (mode == LNS_PAD_CIRCULAR) { u %= virt; if (u < 0) u += virt; }
-                else u = -1;
-            }
-            if (u >= 0) src = nearest_src(u, in, virt, scale);
-        }
-        out[p] = src;
-    }
-}
-
+// (how the planner, the op-level entry points and training build a conv launch: lns_conv_launch.h)
 // [Cout][Cin][k][k] slices -> [taps][Cin_pad][Cout_pad]
 static void pack_conv_weight(float* dst, const float* src, int cout_off, int cout, int cin, int k, int Cin_pad,
                              int Cout_pad) {
@@ -85,109 +57,6 @@ static void pack_conv_weight(float* dst, const float* src, int cout_off, int cou
         for (int ci = 0; ci < cin; ++ci)
             for (int t = 0; t < taps; ++t)
                 dst[((size_t)t * Cin_pad + ci) * Cout_pad + cout_off + co] = src[((size_t)co * cin + ci) * taps + t];
-}
-
-struct ConvGeom { int variant, bw_log2, tiles_x, tiles_y, cout_tiles, PH, PW, Hout, Wout, kc_log2, sel_kc_log2; };
-
-static bool conv_geometry(ConvGeom& g, int B, int Cout, int Hv, int Wv, int k, int stride, int dil, const int* pad,
-                          int kc_log2_pack, int Cout_pad, int force_variant, bool need_wgm1 = false,
-                          bool allow_bf16x3 = false, int Cin = 1 << 30, bool f16x2 = false, bool allow_thin = false,
-                          int force_bw_log2 = -1 /* 3x3: only this tile width (the quad-phase upsampling conv wants 8 x 16 tiles) */) {
-    g.Hout = (Hv + pad[0] + pad[1] - dil * (k - 1) - 1) / stride + 1;
-    g.Wout = (Wv + pad[2] + pad[3] - dil * (k - 1) - 1) / stride + 1;
-    if (g.Hout <= 0 || g.Wout <= 0) return false;
-    std::vector<int> cands;
-    if (force_variant >= 0) cands = {force_variant};
-    else if (Cout <= 32) cands = {CV_S32};
-    else if (Cout <= 64) cands = need_wgm1 ? std::vector<int>{CV_L64, CV_M64} : std::vector<int>{CV_L64, CV_M64, CV_S64};
-    else if (getenv("LNS_CONV_USE_128")) cands = {CV_L128, CV_M128, CV_S64};   // tuning knob (tile choice only)
-    else cands = {CV_L64, CV_M64, CV_S64};   // 64-cout tiles at 2 waves/SIMD beat 128-cout tiles at 1 (measured)
-    // bf16x3 kernel for every eligible 3x3 conv.  Eligibility is a function of the layer only (never of B):
-    // the fp32 variants accumulate in a different order, and a trajectory must not change bitwise with the
-    // batch it is computed in.
-    static const bool no_bf16x3 = getenv("LNS_CONV_FP32_MFMA") != nullptr;
-    const bool use_b = allow_bf16x3 && !no_bf16x3 && k == 3 && stride == 1 && Cout > 32;
-    if (force_variant < 0 && use_b) {   // fp32 variants only if the geometry rules the bf16x3 tiles out
-        cands.insert(cands.begin(), f16x2 ? (int)CV_F64 : (int)CV_B64);
-    }
-    static const bool no_b1 = getenv("LNS_CONV1_FP32_MFMA") != nullptr;
-    // 1x1: bf16x3 unless the layer is a thin projection (few output channels / a handful of input channels:
-    // bandwidth-bound, and a 64-cout MFMA tile would be mostly padding) -- again a per-layer rule
-    if (force_variant < 0 && allow_bf16x3 && !no_bf16x3 && !no_b1 && k == 1 && stride == 1 && Cout > 32 && Cin >= 16)
-        cands = {(int)CV_B1};
-    // <= 4 output channels (the decoder's last conv): streaming VALU kernel, one HBM read of the input
-    static const bool no_thin = getenv("LNS_CONV1_NO_THIN") != nullptr;
-    if (force_variant < 0 && allow_thin && !no_thin && k == 1 && stride == 1 && Cout <= 4 && Cin <= 512 && (Hv * Wv) % 4 == 0)
-        cands = {(int)CV_THIN};
-    g.kc_log2 = conv_pick_kc_log2(k, stride, kc_log2_pack);
-    static const int pref[] = {5, 6, 4, 7, 3, 8};   // log2 BW preference on ties: 32,64,16,128,8,256
-    bool found = false;
-    for (size_t ci = 0; ci < cands.size(); ++ci) {
-        const ConvVariantInfo vi = conv_variant_info(cands[ci]);
-        if (cands[ci] < CV_B64 && Cout_pad % vi.TM != 0) continue;   // fp32 pack layout
-        ConvArgs tmp;
-        memset(&tmp, 0, sizeof tmp);
-        tmp.ks = k; tmp.kc_log2 = g.kc_log2; tmp.Cin_pad = 1 << kc_log2_pack;
-        if (cands[ci] >= CV_B64) { tmp.stride = stride; tmp.Cin_pad = 512; tmp.wb = &tmp; }
-        int best_bw = -1, txn = 0, tyn = 0, best_kc = g.kc_log2;
-        if (k == 1) {
-            // 1x1: the image is a flat array of H*W pixels, a tile is TN consecutive pixels
-            if (stride != 1 || pad[0] || pad[1] || pad[2] || pad[3]) return false;
-            tmp.PH = 1; tmp.PW = 1;
-            if (!conv_fits(cands[ci], tmp)) continue;
-            best_bw = 0;
-            while ((1 << best_bw) < vi.TN) ++best_bw;
-            txn = (g.Hout * g.Wout + vi.TN - 1) / vi.TN; tyn = 1;
-        } else {
-            long best_cost = -1;
-            for (int pi = 0; pi < 6; ++pi) {
-                const int lb = pref[pi];
-                const int BW = 1 << lb;
-                if (BW > vi.TN || (force_bw_log2 >= 0 && lb != force_bw_log2)) continue;
-                const int BH = vi.TN / BW;
-                const long cost = (long)((g.Hout + BH - 1) / BH) * BH * ((g.Wout + BW - 1) / BW) * BW;
-                tmp.PH = (BH - 1) * stride + (k - 1) * dil + 1;
-                tmp.PW = (BW - 1) * stride + (k - 1) * dil + 1;
-                tmp.kc_log2 = g.kc_log2;
-                if (!conv_fits(cands[ci], tmp)) {
-                    if (cands[ci] == CV_B64) continue;
-                    tmp.kc_log2 = 2;
-                    if (!conv_fits(cands[ci], tmp)) continue;
-                }
-                if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_bw = lb; best_kc = tmp.kc_log2; }
-            }
-            if (best_bw < 0) continue;
-            const int BW = 1 << best_bw, BH = vi.TN / BW;
-            txn = (g.Wout + BW - 1) / BW; tyn = (g.Hout + BH - 1) / BH;
-            tmp.PH = (BH - 1) * stride + (k - 1) * dil + 1;
-            tmp.PW = (BW - 1) * stride + (k - 1) * dil + 1;
-        }
-        const long blocks = (long)B * txn * tyn * ((Cout + vi.TM - 1) / vi.TM);
-        g.variant = cands[ci]; g.bw_log2 = best_bw; g.tiles_x = txn; g.tiles_y = tyn;
-        g.cout_tiles = (Cout + vi.TM - 1) / vi.TM;
-        g.PH = tmp.PH; g.PW = tmp.PW; g.sel_kc_log2 = best_kc;
-        found = true;
-        static const long min_blocks = getenv("LNS_CONV_MIN_BLOCKS") ? atol(getenv("LNS_CONV_MIN_BLOCKS")) : 128;
-        if (cands[ci] == CV_B64 && Cout >= 64 && !need_wgm1 && force_variant < 0) {
-            // 32-cout tiles (same accumulation order, same bits) when 64-cout tiles give fewer blocks than this.
-            // Measured on NS2d-128 (16x16 latent layers, 256 -> 512 blocks): no gain (17.9k vs 18.7k
-            // trajectory-steps/s), so the default is off; kept as a tuning knob and covered by the kernel tests.
-            static const long want = getenv("LNS_CONVB32_BELOW") ? atol(getenv("LNS_CONVB32_BELOW")) : 0;
-            if (blocks < want) { g.variant = CV_B32; g.cout_tiles = (Cout + 31) / 32; }
-        }
-        if (cands[ci] == CV_F64 && Cout >= 64 && !need_wgm1 && force_variant < 0) {
-            // the same for the f16x2 form.  On 256-block launches (the 16x16 latent layers of NS2d at B = 64) it measured
-            // neutral to slower (round 1: rollout 144.3 -> 148.1 ms; round 3: 22.6 -> 22.9 us per layer -- every block still
-            // stages and splits the whole patch), but launches that leave three quarters of the CUs idle gain: the 7 x 15
-            // latent layers of the two-phase models at B = 32 (64 blocks) 19.7 -> 15.3 us, dilated 20.5 -> 17.8
-            // (tools/conv_time.py lat_tp / lat_tp_d4, variant 13).  Same bits either way, so the batch may decide.
-            static const long wantf = getenv("LNS_CONVF32_BELOW") ? atol(getenv("LNS_CONVF32_BELOW")) : 100;
-            if (blocks < wantf) { g.variant = CV_F32; g.cout_tiles = (Cout + 31) / 32; }
-        }
-        if (cands[ci] >= CV_B64) break;                        // never fall through to another kernel family by launch size
-        if (blocks >= min_blocks) break;
-    }
-    return found;
 }
 
 // ---------------------------------------------------------------------------
@@ -272,7 +141,7 @@ static FaWeightScale fa_fused_weight_scale(const float* wm, int planes, int C) {
         rowmax = std::max(rowmax, rs);
     }
     if (!(wmax > 0.0f) || !std::isfinite(rowmax)) { wmax = 1.0f; rowmax = std::max(rowmax, 1.0f); }
-    return FaWeightScale{exp2f(floorf(log2f(16000.0f / wmax))), rowmax * (1.0f + 1e-6f)};
+    return FaWeightScale{conv_f16_weight_scale(wmax), rowmax * (1.0f + 1e-6f)};
 }
 // Plane groups (of 16) per block, scheduling only.  requested > 0: that many, lowered to the next divisor of `groups`;
 // 0 = automatic: all four groups of a head while the grid keeps two blocks per CU's worth of work.
@@ -477,8 +346,7 @@ struct Planner {
         x.ss = tag(SP_WS, x.ss_off); x.ss_owned = true;
         op.gn.ss = as_ptr<float>(x.ss); op.gn.B = B;
         op.bytes = 2.0 * B * x.C * x.H * x.W * 4;
-        // |(v - mean) rstd| <= sqrt(n - 1) over a group of n values (biased variance), for any data
-        x.gn_bound = (vg >= 0 ? vec_absmax(vg) : 1.0f) * sqrtf((float)(x.C / groups) * x.H * x.W) + (vb >= 0 ? vec_absmax(vb) : 0.0f);
+        x.gn_bound = gn_output_bound(vg >= 0 ? vec_absmax(vg) : 1.0f, vb >= 0 ? vec_absmax(vb) : 0.0f, x.C / groups, x.H, x.W);
         // Fed by the 3x3 split-operand kernel right before it (nothing in between but traces), 128-pixel tiles
         // covering the plane exactly: the conv epilogue leaves per-tile (mean, M2) and this op only merges them.
         // Layer-static decision (gn_tile_rule), so results do not depend on the batch.
@@ -539,12 +407,12 @@ struct Planner {
                              (in.act == ACT_NONE || (in.act == ACT_SWISH && in.ss != 0));
         // split-operand kernels only where the input carries a bound for the dynamic activation scale (tensors
         // handed in by the caller do not: those few convolutions stay on the fp32 matrix instruction)
-        if (!conv_geometry(g, B, pk.cout, Hv, Wv, k, stride, dil, pad, pk.kc_log2, pk.Cout_pad, -1, fuse_pack >= 0,
-                           pk.has_wb && in.bounded(), pk.cin, pk.f16, thin_ok))
-            throw std::runtime_error("no conv tiling for " + name);
-        if (up2 && g.variant == CV_F32 &&          // (a small launch: the phase form exists for 64-cout tiles only)
-            !conv_geometry(g, B, pk.cout, Hv, Wv, k, stride, dil, pad, pk.kc_log2, pk.Cout_pad, CV_F64, fuse_pack >= 0,
-                           pk.has_wb && in.bounded(), pk.cin, pk.f16, thin_ok))
+        auto tiling = [&](ConvGeom& gg, int force_variant, int force_bw_log2 = -1) {
+            return conv_geometry(gg, B, pk.cout, Hv, Wv, k, stride, dil, pad, pk.kc_log2, pk.Cout_pad, force_variant, fuse_pack >= 0,
+                                 pk.has_wb && in.bounded(), pk.cin, pk.f16, thin_ok, force_bw_log2);
+        };
+        if (!tiling(g, -1)) throw std::runtime_error("no conv tiling for " + name);
+        if (up2 && g.variant == CV_F32 && !tiling(g, CV_F64))      // (a small launch: the phase form exists for 64-cout tiles only)
             throw std::runtime_error("no conv tiling for " + name);
         if (up2 && g.variant != CV_F64) throw std::runtime_error("phase form needs the f16x2 64-cout tiles: " + name);
         // Round 4: the quad-phase form of the upsampling conv (conv3_up2q.inc: the patch staged once, four phases per block,
@@ -557,9 +425,7 @@ struct Planner {
         {
             static const bool no_quad = getenv("LNS_UP2_QUAD") == nullptr || getenv("LNS_UP2_RESIDENT") != nullptr;
             ConvGeom gq;
-            if (up2 && !no_quad && !res && pk.Cin_pad <= 64 && pk.Cin_pad % 16 == 0 &&
-                conv_geometry(gq, B, pk.cout, Hv, Wv, k, stride, dil, pad, pk.kc_log2, pk.Cout_pad, CV_F64, fuse_pack >= 0,
-                              pk.has_wb && in.bounded(), pk.cin, pk.f16, thin_ok, 4)) {
+            if (up2 && !no_quad && !res && pk.Cin_pad <= 64 && pk.Cin_pad % 16 == 0 && tiling(gq, CV_F64, 4)) {
                 ConvArgs t;
                 memset(&t, 0, sizeof t);
                 t.ks = 3; t.stride = 1; t.dil = 1; t.up2 = 1; t.wb = &t; t.Cin_pad = pk.Cin_pad; t.PH = gq.PH; t.PW = gq.PW;
@@ -572,12 +438,9 @@ struct Planner {
             throw NoGeluPrologue("GELU prologue is only built into the f16x2 3x3 kernel: " + name);
         if (up2) { g.Hout = 2 * in.H; g.Wout = 2 * in.W; }
         const ConvVariantInfo vi = conv_variant_info(g.variant);
-        const int BW = 1 << g.bw_log2, BH = vi.TN / BW;
         std::vector<int> rm, cm;
-        if (k == 3) {
-            build_axis_map(rm, (g.tiles_y - 1) * BH * stride + g.PH, in.H, Hv, up2 ? 0.0f : in.sch, pad[0], pad[1], my);
-            build_axis_map(cm, (g.tiles_x - 1) * BW * stride + g.PW, in.W, Wv, up2 ? 0.0f : in.scw, pad[2], pad[3], mx);
-        } else if (in.vH) throw std::runtime_error("1x1 conv of a resized tensor is not supported: " + name);
+        if (k == 3) conv_tile_maps(rm, cm, g, stride, in.H, in.W, Hv, Wv, up2 ? 0.0f : in.sch, up2 ? 0.0f : in.scw, pad, my, mx);
+        else if (in.vH) throw std::runtime_error("1x1 conv of a resized tensor is not supported: " + name);
         TRef out;
         if (out_forced) out = *out_forced;
         else out = alloc_t(pk.cout, g.Hout, g.Wout);
@@ -590,7 +453,9 @@ struct Planner {
         op.type = OP_CONV; op.name = name; op.cls = k == 3 ? CLS_CONV3 : CLS_CONV1; op.variant = g.variant;
         ConvArgs& a = op.conv;
         memset(&a, 0, sizeof a);
-        a.x = as_ptr<const float>(in.ptr); a.x_bs = in.bs; a.Cin = in.C; a.Hin = in.H; a.Win = in.W;
+        conv_set_geometry(a, g, B, in.C, in.H, in.W, pk.cout, k, stride, dil, pk.Cin_pad, pk.Cout_pad);
+        a.x = as_ptr<const float>(in.ptr); a.x_bs = in.bs;        // (strides of the TRefs: an external slot's is a sentinel)
+        a.y = as_ptr<float>(out.ptr); a.y_bs = out.bs;
         a.w = as_ptr<const float>(wt(pk.w_off));
         if (g.variant >= CV_B64) a.wb = as_ptr<const void>(wt(up2 ? pk.wu_off : pk.wb_off));   // CV_B32 included
         a.up2 = up2 ? 1 : 0;
@@ -610,10 +475,7 @@ struct Planner {
             // their own prologue (no launch); every other consumer gets the finalize op now
             if (g.variant == CV_F64 || g.variant == CV_F32 || g.variant == CV_B1) {
                 const Op& lo = lazy_ops[in.gn_lazy];
-                a.ss = nullptr;
-                a.gn_part = lo.gn_tile_part; a.gn_tiles = lo.gn_tiles; a.gn_groups = lo.gn.groups; a.gn_eps = lo.gn.eps;
-                a.gn_count = lo.gn_count == GN_TILE_PIXELS ? 0 : lo.gn_count; a.gn_premul = lo.gn.premul;
-                a.gn_gamma = lo.gn.gamma; a.gn_beta = lo.gn.beta;
+                conv_fold_gn(a, lo.gn_tile_part, lo.gn_tiles, lo.gn_count, lo.gn.groups, lo.gn.eps, lo.gn.premul, lo.gn.gamma, lo.gn.beta);
                 lazy_folded[in.gn_lazy] = 1;
             } else {
                 flush_gn(in);
@@ -623,25 +485,12 @@ struct Planner {
         if (k == 3) {
             a.rowmap = as_ptr<const int>(const_ints(rm));
             a.colmap = as_ptr<const int>(const_ints(cm));
-            // no resize, pads inside one period: the split-operand kernel computes the maps itself (ConvArgs::map_arith)
-            static const bool no_arith = getenv("LNS_NO_ARITH_MAPS") != nullptr;
-            const bool plain = up2 || (!in.vH && !in.vW);
-            if (!no_arith && plain && cv_is_split_3x3(g.variant) && pad[0] <= in.H && pad[1] <= in.H && pad[2] <= in.W && pad[3] <= in.W &&
-                (my == LNS_PAD_ZEROS || my == LNS_PAD_CIRCULAR) && (mx == LNS_PAD_ZEROS || mx == LNS_PAD_CIRCULAR)) {
-                a.map_arith = 1;
-                a.map_circ[0] = my == LNS_PAD_CIRCULAR; a.map_circ[1] = mx == LNS_PAD_CIRCULAR;
-                a.map_pad[0] = pad[0]; a.map_pad[1] = pad[2];
-                a.map_ext[0] = in.H + pad[0] + pad[1]; a.map_ext[1] = in.W + pad[2] + pad[3];
-            }
+            conv_set_map_arith(a, g.variant, k, in.H, in.W, Hv, Wv, pad, my, mx);
         }
-        // 16-byte patch loads: every channel row of every sample must start 16-byte aligned
-        a.vec4 = (k == 1 && ((in.H * in.W) % 4 == 0)) ? 1 : 0;
-        a.y = as_ptr<float>(out.ptr); a.y_bs = out.bs; a.Cout = pk.cout; a.Hout = g.Hout; a.Wout = g.Wout;
         if (res) { a.res = as_ptr<const float>(res->ptr); a.res_bs = res->bs; }
         a.badd = as_ptr<const float>(badd);
-        a.ks = k; a.stride = stride; a.dil = dil;
-        a.unscale = (cv_is_f16x2_3x3(g.variant) || g.variant == CV_B1) ? 1.0f / (up2 ? pk.wscale_up : pk.wscale) : 1.0f;   // x 1/S in the kernel
-        if (in.ss != 0 && in.gn_bound > 0.0f) { a.amax_in_const = in.gn_bound; a.bound_final = 1; }   // GroupNorm output: layer constant
+        a.unscale = conv_unscale(g.variant, up2 ? pk.wscale_up : pk.wscale);   // x 1/S in the kernel
+        if (in.ss != 0 && in.gn_bound > 0.0f) conv_set_final_bound(a, in.gn_bound);   // GroupNorm output: layer constant
         else {
             a.amax_in = as_ptr<const unsigned>(in.amax); a.amax_in_const = in.amax_const;
             if (!in.amax && in.ss == 0) a.bound_final = 1;     // analytic bound of a raw tensor (LayerNorm / InstanceNorm output)
@@ -650,10 +499,6 @@ struct Planner {
         // a tensor written to a caller's buffer (the plan's output) is always recorded: nobody scales by it, but
         // lns_check_finite must see a NaN born in the last layer as well
         if ((want_amax && g.variant != CV_THIN) || out_forced) { out.amax = new_amax(name); a.amax_out = as_ptr<unsigned>(out.amax); }
-        a.Cin_pad = pk.Cin_pad; a.Cout_pad = pk.Cout_pad; a.kc_log2 = g.sel_kc_log2;
-        a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.cout_tiles = g.cout_tiles; a.bw_log2 = g.bw_log2;
-        a.PH = g.PH; a.PW = g.PW; a.B = B;
-        a.ph_magic = g.PH > 1 ? (unsigned)((0x100000000ull + g.PH - 1) / g.PH) : 0u;
         if (up2) {
             // narrow inputs: the split patch of ALL channels can stay in LDS while one block walks the four phases (same
             // bits, conv3_up2r.inc).  Measured SLOWER (fused 128^2 layer 294 - 299 vs 215 us, rollout 31.9k vs 33.4k): at
@@ -700,7 +545,7 @@ struct Planner {
                 float mx = 0.0f;
                 for (const std::string& key : p2.wkeys)
                     for (float v : e->params[e->pindex.at(key)].host) mx = std::max(mx, fabsf(v));
-                a.w2scale = (mx > 0.0f && std::isfinite(mx)) ? exp2f(floorf(log2f(16000.0f / mx))) : 1.0f;
+                a.w2scale = (mx > 0.0f && std::isfinite(mx)) ? conv_f16_weight_scale(mx) : 1.0f;
             }
             op.flops += 2.0 * B * g.Hout * g.Wout * 64.0 * 64.0;
         }
@@ -1344,6 +1189,15 @@ static void release_overlap_objects(lns_engine* e) {
     e->dec_streams.clear();
 }
 
+// Drop the cached encoder / decoder plans (and the propagator's): the next call plans again.  The engine's device is current.
+static void drop_plans(lns_engine* e, bool with_propagator) {
+    for (auto* m : {&e->enc_plans, &e->dec_plans, &e->prop_plans}) {
+        if (m == &e->prop_plans && !with_propagator) continue;
+        for (auto& kv : *m) if (kv.second.d_consts) (void)hipFree(kv.second.d_consts);
+        m->clear();
+    }
+}
+
 static int finalize_weights(lns_engine* e, int device) {
     for (const Param& p : e->params)
         if (!p.is_set) { e->err = "weight not set: " + p.key; return LNS_ESTATE; }
@@ -1389,7 +1243,7 @@ static int finalize_weights(lns_engine* e, int device) {
         if (p.fold_a >= 0) for (float v : fold_w[&p - e->packs.data()]) mx = std::max(mx, fabsf(v));
         if (!(mx > 0.0f) || !std::isfinite(mx)) { if (p.k == 1) p.wscale = 1.0f; continue; }   // all-zero weights: scale 1 (3x3: bf16x3)
         p.f16 = p.k == 3;
-        p.wscale = exp2f(floorf(log2f(16000.0f / mx)));
+        p.wscale = conv_f16_weight_scale(mx);
         p.wscale_up = p.wscale * 0.25f;          // a phase tap sums up to four taps: keep the fp16 high term below 2^14 as well
     }
     for (const ConvPack& p : e->packs) {
@@ -1445,10 +1299,7 @@ static int finalize_weights(lns_engine* e, int device) {
     e->device = device;
     e->finalized = true;
     // plans hold weight offsets only, but rotary tables depend on inv_freq: drop cached plans
-    for (auto* m : {&e->enc_plans, &e->dec_plans, &e->prop_plans}) {
-        for (auto& kv : *m) if (kv.second.d_consts) (void)hipFree(kv.second.d_consts);
-        m->clear();
-    }
+    drop_plans(e, true);
     e->ran.clear(); e->ran_ws = nullptr; e->ran_B = 0;     // lns_check_finite has nothing to look at until the next run
     return LNS_OK;
 }
@@ -2037,8 +1888,7 @@ void lns_train_release(const lns_engine* e);
 void lns_destroy(lns_engine* e) {
     if (!e) return;
     lns_train_release(e);
-    for (auto* m : {&e->enc_plans, &e->dec_plans, &e->prop_plans})
-        for (auto& kv : *m) if (kv.second.d_consts) (void)hipFree(kv.second.d_consts);
+    drop_plans(e, true);
     if (e->d_weights) (void)hipFree(e->d_weights);
     if (e->d_sticky) (void)hipFree(e->d_sticky);
     release_overlap_objects(e);
@@ -2084,6 +1934,8 @@ int lns_finalize_weights(lns_engine* e, int device) {
 int lns_set_option(lns_engine* e, const char* name, long value) {
     if (!e || !name) return LNS_EINVAL;
     const std::string n = name;
+    // a planning rule of the decoder / encoder: cached plans are rebuilt when it changes
+    auto set_rule = [e, value](int& opt) { if (opt != (int)value) { DeviceGuard dg(e); drop_plans(e, false); } opt = (int)value; };
     if (n == "decode_group") { if (value < 0 || value > 8) return LNS_EINVAL; e->opt_decode_group = (int)value; }
     else if (n == "decode_streams") { if (value < 1 || value > NDEC) return LNS_EINVAL; e->opt_decode_streams = (int)value; }
     else if (n == "overlap") e->opt_overlap = value != 0;
@@ -2093,53 +1945,17 @@ int lns_set_option(lns_engine* e, const char* name, long value) {
         if (value != 0 && value != 1) { e->err = "train_wgrad: 0 (one block per output tile) or 1 (batch-parallel)"; return LNS_EINVAL; }
         e->opt_train_wgrad = (int)value;
     }
-    else if (n == "fa_fused" || n == "fa_fused_gpb") {
-        if (n == "fa_fused_gpb" && (value < 0 || value > 64)) return LNS_EINVAL;
-        if (n == "fa_fused" && (value < 0 || value > 3)) return LNS_EINVAL;
-        const bool changed = n == "fa_fused" ? e->opt_fa_fused != (int)value : e->opt_fa_fused_gpb != (int)value;
-        if (changed) {                                  // a planning rule of the decoder / encoder: cached plans are rebuilt
-            DeviceGuard dg(e);
-            for (auto* m : {&e->enc_plans, &e->dec_plans}) {
-                for (auto& kv : *m) if (kv.second.d_consts) (void)hipFree(kv.second.d_consts);
-                m->clear();
-            }
-        }
-        if (n == "fa_fused") e->opt_fa_fused = (int)value;
-        else e->opt_fa_fused_gpb = (int)value;
-    }
+    else if (n == "fa_fused") { if (value < 0 || value > 3) return LNS_EINVAL; set_rule(e->opt_fa_fused); }
+    else if (n == "fa_fused_gpb") { if (value < 0 || value > 64) return LNS_EINVAL; set_rule(e->opt_fa_fused_gpb); }
     else if (n == "fold_linear") {
         if (value != 0 && value != 1) { e->err = "fold_linear: 0 (the pair as it stands) or 1 (one conv on the composed weights)"; return LNS_EINVAL; }
-        if (e->opt_fold_linear != (int)value) {         // a planning rule of the decoder / encoder: cached plans are rebuilt
-            DeviceGuard dg(e);
-            for (auto* m : {&e->enc_plans, &e->dec_plans}) {
-                for (auto& kv : *m) if (kv.second.d_consts) (void)hipFree(kv.second.d_consts);
-                m->clear();
-            }
-        }
-        e->opt_fold_linear = (int)value;
+        set_rule(e->opt_fold_linear);
     }
     else if (n == "up2_dual") {
         if (value != 0 && value != 1) { e->err = "up2_dual: 0 (one block per output phase) or 1 (both column phases per block where the form fits)"; return LNS_EINVAL; }
-        if (e->opt_up2_dual != (int)value) {            // a planning rule of the decoder / encoder: cached plans are rebuilt
-            DeviceGuard dg(e);
-            for (auto* m : {&e->enc_plans, &e->dec_plans}) {
-                for (auto& kv : *m) if (kv.second.d_consts) (void)hipFree(kv.second.d_consts);
-                m->clear();
-            }
-        }
-        e->opt_up2_dual = (int)value;
+        set_rule(e->opt_up2_dual);
     }
-    else if (n == "fa_chunk_mb") {
-        if (value < 0 || value > 4096) return LNS_EINVAL;
-        if (e->opt_fa_chunk_mb != (int)value) {         // a planning rule of the decoder / encoder: cached plans are rebuilt
-            DeviceGuard dg(e);
-            for (auto* m : {&e->enc_plans, &e->dec_plans}) {
-                for (auto& kv : *m) if (kv.second.d_consts) (void)hipFree(kv.second.d_consts);
-                m->clear();
-            }
-        }
-        e->opt_fa_chunk_mb = (int)value;
-    }
+    else if (n == "fa_chunk_mb") { if (value < 0 || value > 4096) return LNS_EINVAL; set_rule(e->opt_fa_chunk_mb); }
     else if (n == "prop_priority") {
         if (e->opt_prop_priority != (value != 0)) { DeviceGuard dg(e); release_overlap_objects(e); }   // recreated with the new priority
         e->opt_prop_priority = value != 0;
@@ -3243,11 +3059,7 @@ static int op_conv_prepare(OpConv& oc, const float* x, int B, int Cin, int Hin, 
         if (ksize != 3 || stride != 1 || dilation != 1 || Hv != 2 * Hin || Wv != 2 * Win || pad_t != 1 || pad_b != 1 || pad_l != 1 || pad_r != 1) return LNS_EINVAL;
         tile_variant = CV_F64; Hv = Hin; Wv = Win;
     }
-    ConvPack pk;
-    pk.cin = Cin; pk.cout = Cout; pk.k = ksize;
-    pk.kc_log2 = ksize == 3 ? 3 : 5;
-    pk.Cin_pad = (Cin + (1 << pk.kc_log2) - 1) / (1 << pk.kc_log2) * (1 << pk.kc_log2);
-    pk.Cout_pad = Cout <= 32 ? 32 : (Cout <= 64 ? 64 : (Cout + 127) / 128 * 128);
+    ConvPadded pk = conv_padded_sizes(ksize, Cin, Cout);
     if (tile_variant >= 0) {
         const int TM = conv_variant_info(tile_variant).TM;
         pk.Cout_pad = (Cout + TM - 1) / TM * TM;
@@ -3259,13 +3071,10 @@ static int op_conv_prepare(OpConv& oc, const float* x, int B, int Cin, int Hin, 
     ConvGeom g;
     if (!conv_geometry(g, B, Cout, Hv, Wv, ksize, stride, dilation, pad, pk.kc_log2, pk.Cout_pad, tile_variant, false, false, 1 << 30, false,
                        false, up2q ? 4 : -1)) return LNS_EINVAL;
-    const ConvVariantInfo vi = conv_variant_info(g.variant);
-    const int BW = 1 << g.bw_log2, BH = vi.TN / BW;
     std::vector<int> rm, cm;
     if (up2) { g.Hout = 2 * Hin; g.Wout = 2 * Win; }
     const float sch = (Hv == 2 * Hin) ? 0.5f : 0.0f, scw = (Wv == 2 * Win) ? 0.5f : 0.0f;
-    build_axis_map(rm, (g.tiles_y - 1) * BH * stride + g.PH, Hin, Hv, sch, pad_t, pad_b, mode_y);
-    build_axis_map(cm, (g.tiles_x - 1) * BW * stride + g.PW, Win, Wv, scw, pad_l, pad_r, mode_x);
+    conv_tile_maps(rm, cm, g, stride, Hin, Win, Hv, Wv, sch, scw, pad, mode_y, mode_x);
     const size_t wcount = (size_t)ksize * ksize * pk.Cin_pad * pk.Cout_pad;
     std::vector<float> hw(wcount + pk.Cout_pad, 0.0f);
     pack_conv_weight(hw.data(), w_host, 0, Cout, Cin, ksize, pk.Cin_pad, pk.Cout_pad);
@@ -3274,7 +3083,7 @@ static int op_conv_prepare(OpConv& oc, const float* x, int B, int Cin, int Hin, 
     if (cv_is_f16x2_3x3(g.variant) || (g.variant == CV_B1 && convb1_is_f16())) {
         float mx = 0.0f;
         for (size_t i = 0; i < (size_t)Cout * Cin * ksize * ksize; ++i) mx = std::max(mx, fabsf(w_host[i]));
-        if (mx > 0.0f) wscale = exp2f(floorf(log2f(16000.0f / mx)));
+        if (mx > 0.0f) wscale = conv_f16_weight_scale(mx);
         if (up2) wscale *= 0.25f;
     }
     const size_t wb_floats = up2 ? convu_weight_bytes(Cout, pk.Cin_pad) / 4 : cv_is_split_3x3(g.variant) ? convb_weight_bytes(Cout, pk.Cin_pad) / 4
@@ -3293,23 +3102,14 @@ static int op_conv_prepare(OpConv& oc, const float* x, int B, int Cin, int Hin, 
     OPCHK(hipMemcpy(oc.dmaps + rm.size(), cm.data(), cm.size() * 4, hipMemcpyHostToDevice));
     ConvArgs& a = oc.a;
     memset(&a, 0, sizeof a);
-    a.x = x; a.x_bs = (long)Cin * Hin * Win; a.Cin = Cin; a.Hin = Hin; a.Win = Win;
+    conv_set_geometry(a, g, B, Cin, Hin, Win, Cout, ksize, stride, dilation, pk.Cin_pad, pk.Cout_pad);
+    a.x = x; a.y = y;
     a.w = oc.dw; a.bias = bias_host ? oc.dw + wcount : nullptr; a.ss = ss; a.act_in = act_in; a.act_out = act_out;
     if (wb_floats) a.wb = oc.dw + wcount + pk.Cout_pad;
     a.rowmap = oc.dmaps; a.colmap = oc.dmaps + rm.size();
-    if (ksize == 3 && Hv == Hin && Wv == Win && cv_is_split_3x3(g.variant) && getenv("LNS_NO_ARITH_MAPS") == nullptr &&
-        pad_t <= Hin && pad_b <= Hin && pad_l <= Win && pad_r <= Win && (mode_y == LNS_PAD_ZEROS || mode_y == LNS_PAD_CIRCULAR) &&
-        (mode_x == LNS_PAD_ZEROS || mode_x == LNS_PAD_CIRCULAR)) {       // same rule as Planner::emit_conv
-        a.map_arith = 1;
-        a.map_circ[0] = mode_y == LNS_PAD_CIRCULAR; a.map_circ[1] = mode_x == LNS_PAD_CIRCULAR;
-        a.map_pad[0] = pad_t; a.map_pad[1] = pad_l;
-        a.map_ext[0] = Hin + pad_t + pad_b; a.map_ext[1] = Win + pad_l + pad_r;
-    }
-    a.vec4 = (ksize == 1 && ((Hin * Win) % 4 == 0)) ? 1 : 0;
-    a.y = y; a.y_bs = (long)Cout * g.Hout * g.Wout; a.Cout = Cout; a.Hout = g.Hout; a.Wout = g.Wout;
+    conv_set_map_arith(a, g.variant, ksize, Hin, Win, Hv, Wv, pad, mode_y, mode_x);
     a.res = residual; a.res_bs = a.y_bs; a.badd = badd;
-    a.ks = ksize; a.stride = stride; a.dil = dilation; a.Cin_pad = pk.Cin_pad; a.Cout_pad = pk.Cout_pad;
-    a.unscale = (cv_is_f16x2_3x3(g.variant) || g.variant == CV_B1) ? 1.0f / wscale : 1.0f;
+    a.unscale = conv_unscale(g.variant, wscale);
     a.up2 = up2 ? 1 : 0;
     // the input's per-sample maximum, as the producing kernel of a plan would have recorded it
     OPCHK(hipMalloc(reinterpret_cast<void**>(&oc.damax), (size_t)B * LNS_AMAX_SUB * 4));
@@ -3320,9 +3120,6 @@ static int op_conv_prepare(OpConv& oc, const float* x, int B, int Cin, int Hin, 
         OPCHK(launch_amax(x, a.x_bs, (long)Cin * Hin * Win, B, oc.damax, stream));
     }
     a.amax_in = oc.damax;
-    a.kc_log2 = g.sel_kc_log2; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.cout_tiles = g.cout_tiles;
-    a.bw_log2 = g.bw_log2; a.PH = g.PH; a.PW = g.PW; a.B = B;
-    a.ph_magic = g.PH > 1 ? (unsigned)((0x100000000ull + g.PH - 1) / g.PH) : 0u;
     if (up2r) {
         a.up2 = 2;
         if (!convur_fits(a)) return LNS_EINVAL;
@@ -3377,8 +3174,8 @@ int lns_op_conv2d(const float* x, int B, int Cin, int Hin, int Win, int Hv, int 
 }
 
 // GroupNorm from the tile statistics of its producer (include/lns.h): producer convolution with ConvArgs::stat_part set by
-// gn_tile_rule -- the rule Planner::emit_gn applies --, then the finalize kernel and / or a consumer convolution whose
-// prologue merges the partials, its arguments set as Planner::emit_conv sets them.  Nothing is launched before the last check.
+// gn_tile_rule, then the finalize kernel and / or a consumer convolution whose prologue merges the partials (conv_fold_gn,
+// gn_output_bound: the planner's calls).  Nothing is launched before the last check.
 int lns_op_conv_gn(const lns_conv_gn_args* p, void* stream) {
     auto bad = [](const std::string& m) { g_create_error = "conv_gn: " + m; return (int)LNS_EINVAL; };
     if (!p) return bad("args is null");
@@ -3452,18 +3249,14 @@ int lns_op_conv_gn(const lns_conv_gn_args* p, void* stream) {
         ok(launch_gn_tile_finalize(g, merge, r.tiles, r.gn_count < 0 ? 0 : r.gn_count, r.geom, s));
     }
     if (consumer && he == hipSuccess) {
-        ConvArgs& a = cons.a;                   // Planner::emit_conv, the lazy-GroupNorm branch
-        a.ss = nullptr;
-        a.gn_part = merge; a.gn_tiles = r.tiles; a.gn_groups = p->groups; a.gn_eps = p->eps;
-        a.gn_count = r.gn_count == GN_TILE_PIXELS ? 0 : r.gn_count; a.gn_premul = p->premul;
-        a.gn_gamma = dgamma; a.gn_beta = dbeta;
-        // the GroupNorm output's bound, a layer constant (Planner::emit_gn): |gamma| sqrt(n_group) + |beta|
+        ConvArgs& a = cons.a;
+        conv_fold_gn(a, merge, r.tiles, r.gn_count, p->groups, p->eps, p->premul, dgamma, dbeta);
         float gmax = p->gamma_host ? 0.0f : 1.0f, bmax = 0.0f;
         for (int c = 0; c < C; ++c) {
             if (p->gamma_host) gmax = std::max(gmax, fabsf(p->gamma_host[c]));
             if (p->beta_host) bmax = std::max(bmax, fabsf(p->beta_host[c]));
         }
-        a.amax_in = nullptr; a.amax_in_const = gmax * sqrtf((float)(C / p->groups) * H * W) + bmax; a.bound_final = 1;
+        conv_set_final_bound(a, gn_output_bound(gmax, bmax, C / p->groups, H, W));
         ok(launch_conv(cons.variant, a, s));
     }
     const hipError_t hs = hipStreamSynchronize(s);

@@ -8,12 +8,11 @@
 #include <cstring>
 #include <stdexcept>
 
+#include "lns_conv_launch.h"
 #include "lns_engine.h"
 #include "lns_fold.h"
 
 namespace lns {
-
-static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 struct Builder {
     lns_engine* e;
@@ -31,9 +30,8 @@ struct Builder {
     }
 
     static void size_pack(ConvPack& p) {
-        p.kc_log2 = (p.k == 3) ? 3 : 5;
-        p.Cin_pad = round_up(p.cin, 1 << p.kc_log2);
-        p.Cout_pad = p.cout <= 32 ? 32 : (p.cout <= 64 ? 64 : round_up(p.cout, 128));
+        const ConvPadded ps = conv_padded_sizes(p.k, p.cin, p.cout);
+        p.kc_log2 = ps.kc_log2; p.Cin_pad = ps.Cin_pad; p.Cout_pad = ps.Cout_pad;
     }
 
     // nn.Conv2d(cin, cout, k) parameters `${pfx}.weight` / `${pfx}.bias`

@@ -25,7 +25,7 @@
 namespace {
 
 struct TConv {                       // one convolution geometry with its gather maps on the device
-    int Cin = 0, Cout = 0, k = 1, dil = 1, Cin_pad = 0, Cout_pad = 0, variant = 0;
+    int Cin = 0, Cout = 0, k = 1, dil = 1, kc_log2 = 3, Cin_pad = 0, Cout_pad = 0, variant = 0;
     int wg_S = 1;                    // slices of the batch-parallel weight gradient (wgrad_split_slices of the plan's shape)
     ConvArgs base;                   // everything but x / y / w / bias / res
     int* d_maps = nullptr;           // forward kernel's tile maps (rowmap | colmap)
@@ -77,26 +77,22 @@ int train_same_device(lns_engine* e, int device, const void* p, const char* what
 }
 
 // channel counts and pads of a convolution: all the workspace layout needs (no device, no tiling)
-int tconv_dims(TConv& t, int Cin, int Cout, int k, int dil) {
+void tconv_dims(TConv& t, int Cin, int Cout, int k, int dil) {
     t.Cin = Cin; t.Cout = Cout; t.k = k; t.dil = dil;
-    const int kc_log2 = k == 3 ? 3 : 5;
-    t.Cin_pad = (Cin + (1 << kc_log2) - 1) / (1 << kc_log2) * (1 << kc_log2);
-    t.Cout_pad = Cout <= 32 ? 32 : (Cout <= 64 ? 64 : (Cout + 127) / 128 * 128);
-    return kc_log2;
+    const ConvPadded ps = conv_padded_sizes(k, Cin, Cout);
+    t.kc_log2 = ps.kc_log2; t.Cin_pad = ps.Cin_pad; t.Cout_pad = ps.Cout_pad;
 }
 
-int tconv_setup(lns_engine* e, TConv& t, int B, int Cin, int Cout, int H, int W, int k, int dil, int my, int mx) {
-    const int kc_log2 = tconv_dims(t, Cin, Cout, k, dil);
+// tiling, device maps and launch arguments of a convolution whose dims train_plan_dims has set
+int tconv_setup(lns_engine* e, TConv& t, int B, int H, int W, int my, int mx) {
+    const int Cin = t.Cin, Cout = t.Cout, k = t.k, dil = t.dil;
     const int p = dil * (k - 1) / 2;
     const int pad[4] = {p, p, p, p};
     ConvGeom g;
-    if (!conv_geometry(g, B, Cout, H, W, k, 1, dil, pad, kc_log2, t.Cout_pad, -1)) { e->err = "training: no conv tiling"; return LNS_EINVAL; }
+    if (!conv_geometry(g, B, Cout, H, W, k, 1, dil, pad, t.kc_log2, t.Cout_pad, -1)) { e->err = "training: no conv tiling"; return LNS_EINVAL; }
     t.variant = g.variant;
-    const ConvVariantInfo vi = conv_variant_info(g.variant);
-    const int BW = 1 << g.bw_log2, BH = vi.TN / BW;
     std::vector<int> rm, cm, fr, fc;
-    build_axis_map(rm, (g.tiles_y - 1) * BH + g.PH, H, H, 0.0f, p, p, my);
-    build_axis_map(cm, (g.tiles_x - 1) * BW + g.PW, W, W, 0.0f, p, p, mx);
+    conv_tile_maps(rm, cm, g, 1, H, W, H, W, 0.0f, 0.0f, pad, my, mx);
     build_axis_map(fr, H + 2 * p, H, H, 0.0f, p, p, my);
     build_axis_map(fc, W + 2 * p, W, W, 0.0f, p, p, mx);
     HIPCHK(e, hipMalloc(reinterpret_cast<void**>(&t.d_maps), (rm.size() + cm.size()) * 4));
@@ -108,16 +104,10 @@ int tconv_setup(lns_engine* e, TConv& t, int B, int Cin, int Cout, int H, int W,
     t.full_rows = (int)fr.size();
     ConvArgs& a = t.base;
     memset(&a, 0, sizeof a);
-    a.x_bs = (long)Cin * H * W; a.Cin = Cin; a.Hin = H; a.Win = W;
+    conv_set_geometry(a, g, B, Cin, H, W, Cout, k, 1, dil, t.Cin_pad, t.Cout_pad);    // "same" padding: the output plane is H x W
     a.rowmap = t.d_maps; a.colmap = t.d_maps + rm.size();
-    a.vec4 = (k == 1 && ((H * W) % 4 == 0)) ? 1 : 0;
-    a.y_bs = (long)Cout * H * W; a.Cout = Cout; a.Hout = g.Hout; a.Wout = g.Wout;
     a.res_bs = a.y_bs;
-    a.ks = k; a.stride = 1; a.dil = dil; a.Cin_pad = t.Cin_pad; a.Cout_pad = t.Cout_pad;
-    a.unscale = 1.0f;
-    a.kc_log2 = g.sel_kc_log2; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.cout_tiles = g.cout_tiles;
-    a.bw_log2 = g.bw_log2; a.PH = g.PH; a.PW = g.PW; a.B = B;
-    a.ph_magic = g.PH > 1 ? (unsigned)((0x100000000ull + g.PH - 1) / g.PH) : 0u;
+    a.unscale = conv_unscale(g.variant, 1.0f);
     return LNS_OK;
 }
 
@@ -147,13 +137,8 @@ int get_train_plan(lns_engine* e, int device, int B, int H, int W, TrainPlan** o
     if ((rc = train_plan_dims(e, B, H, W, p))) return rc;
     HIPCHK(e, init_train_kernels());      // dynamic-LDS attributes of the batch-parallel weight gradient: per device, at plan build
     const int my = c.prop_pad_y, mx = c.prop_pad_x;
-    if ((rc = tconv_setup(e, p.in_proj, B, p.c, p.D, p.H, p.W, 1, 1, my, mx)) ||
-        (rc = tconv_setup(e, p.in_proj_T, B, p.D, p.c, p.H, p.W, 1, 1, my, mx)) ||
-        (rc = tconv_setup(e, p.c_d1, B, p.D, p.D, p.H, p.W, 3, 1, my, mx)) ||
-        (rc = tconv_setup(e, p.c_dd, B, p.D, p.D, p.H, p.W, 3, p.dil, my, mx)) ||
-        (rc = tconv_setup(e, p.c_1, B, p.D, p.D, p.H, p.W, 1, 1, my, mx)) ||
-        (rc = tconv_setup(e, p.out_proj, B, p.D, p.c, p.H, p.W, 1, 1, my, mx)) ||
-        (rc = tconv_setup(e, p.out_proj_T, B, p.c, p.D, p.H, p.W, 1, 1, my, mx))) { p.release(); return rc; }
+    for (TConv* t : {&p.in_proj, &p.in_proj_T, &p.c_d1, &p.c_dd, &p.c_1, &p.out_proj, &p.out_proj_T})
+        if ((rc = tconv_setup(e, *t, B, p.H, p.W, my, mx))) { p.release(); return rc; }
     auto res = g_train_plans.emplace(key, p);
     *out = &res.first->second;
     return LNS_OK;

@@ -17,7 +17,10 @@ residual blocks per level and the unconditional two-phase model (EXTRA), and ns2
 the fused kernel: 32 x 32 planes, 128 channels) under fa_fused 0 (plain sandwich), fa_fused 2 (input split + fused kernel) and
 fa_fused 0 with fa_chunk_mb 1 (the in_proj -> sandwich -> to_out chain re-issued per sample); "classes/<case>[/<options>]" ->
 {kernel class or class/form: launches} of one rollout of each case.  The tool fails if a kernel class of the library is
-launched by none of them.  Two builds that enqueue the same work print the same object.
+launched by none of them.  Beside the rollouts, the two other sites that build conv launches: "op_conv/<idx>" -> the output of
+every op-level conv case of the kernel tests (tests/gpu_checks.py CONV_CASES) and "train/<case>" -> loss and parameter gradients
+of one training step (train_wgrad 0) of ns2d_mini and twophase_cond at B = 2, T = 3, the tensors whose hashes repeat when the step
+runs twice.  Two builds that enqueue the same work print the same object.
 
     python tools/rollout_bits.py [--out FILE]
 """
@@ -42,6 +45,7 @@ EXTRA = ("ns2d_mini_sa", "ns2d_mini_attn_enc", "ns2d_mini_attn_enc_sa", "ns2d_mi
 FA_CASE = "ns2d_64"
 FA_OPTIONS = (dict(fa_fused=0, fa_chunk_mb=0), dict(fa_fused=2, fa_chunk_mb=0), dict(fa_fused=0, fa_chunk_mb=1))
 B, T = 2, 7
+TRAIN_CASES, TRAIN_T = ("ns2d_mini", "twophase_cond"), 3
 KEEP = [1, 4, 6]
 CHUNKS = ((0, 4, [1]), (4, 3, [0, 2]))              # (t0, steps, keep_steps of the chunk): KEEP again
 NORM = dict(mean=0.37, std=1.9)
@@ -186,11 +190,57 @@ def classes(eng, x, p):
     return rec
 
 
+def op_conv():
+    """"op_conv/<idx>": the output of every op-level conv case of the kernel tests (tests/gpu_checks.py CONV_CASES, seeded by
+    its index as tests/test_gpu_parity.py::test_conv_kernel seeds it) that the build compiles."""
+    for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+        sys.path.insert(0, p)
+    import gpu_checks
+    from lns_amd import _lib
+    experimental = _lib.lib().lns_build_has(b"experimental") == 1
+    rec = {}
+    for idx, case in enumerate(gpu_checks.CONV_CASES):
+        if case.get("variant") in (15, 16, 18, 19, 20) and not experimental:      # forms of -DLNS_EXPERIMENTAL builds only
+            continue
+        rec["op_conv/%d" % idx] = {"y": sha(torch.from_numpy(np.ascontiguousarray(gpu_checks.conv_case(seed=idx, ret_y=True, **case)[2])))}
+    return rec
+
+
+def train(name):
+    """"train/<case>": loss and every parameter gradient of one training step (train_wgrad 0, no update) at B = 2, T = 3.  The
+    step runs twice on fresh gradients: a tensor whose hashes differ between the two (atomics) is not recorded but named."""
+    from lns_amd import train as lns_train
+    print("train", name, file=sys.stderr, flush=True)
+    d = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
+    meta = json.loads(bytes(d["meta"]).decode())
+    args = config.preset(meta["preset"], **meta["overrides"])
+    model = dropin.build_dynamics(args)
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in filler.synthetic_state_dict(shapes, meta["weight_seed"]).items()})
+    model = model.to("cuda:0")
+    c, h, w = model._eng.latent_shape()
+    z_in = torch.from_numpy(filler.normal("z_in", (B, 1, c, h, w), 5) * np.float32(0.5)).cuda()
+    z_out = torch.from_numpy(filler.normal("z_out", (B, TRAIN_T, c, h, w), 5) * np.float32(0.5)).cuda()
+    prm = (torch.from_numpy(filler.uniform01("param", B, 5).astype(np.float32)).cuda(),) if args.family == "twophase_cond" else ()
+    tr = lns_train.Stage2Trainer(model, wgrad="tile")
+    runs = []
+    for _ in range(2):
+        for p in model.propagator.parameters():
+            p.grad = None
+        loss = tr.step(z_in, z_out, *prm, update=False)
+        torch.cuda.synchronize()
+        runs.append(dict({"loss": sha(loss)}, **{"grad/" + k: sha(p.grad) for k, p in model.propagator.named_parameters()}))
+    same = {k: v for k, v in runs[0].items() if runs[1][k] == v}
+    return {"train/" + name: same, "train/%s/not repeatable" % name: sorted(set(runs[0]) - set(same))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    rec = {}
+    rec = op_conv()
+    for case in TRAIN_CASES:
+        rec.update(train(case))
     for case in CASES:
         eng, x, y, p = setup(case)
         for dg, ds, ov in itertools.product(DECODE_GROUPS, (1, 2), (0, 1)):
