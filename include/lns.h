@@ -413,6 +413,50 @@ int lns_rollout_latent_ensemble_quantiles(lns_engine* e, const float* z_in, cons
                                           float* mean_out, float* var_out, float* z_last,
                                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ensemble exceedance: contingency tables of the event "field above a threshold" --------------------------------
+ * lns_rollout_latent_ensemble with the members' exceedance forecast P(field > threshold) verified against the truth where
+ * the members are decoded.  The Brier score and its reliability / resolution / uncertainty split, the reliability diagram,
+ * the ROC curve and its area, and for one forecast hits / misses / false alarms (the IoU of the region above the threshold)
+ * are all functions of one integer table per plane: how many pixels had n of the M members above the threshold while the
+ * truth was (o = 1) or was not (o = 0) above it.  Taking it needs the M member values and the truth of a pixel at the same
+ * time, i.e. the [B*M, n_keep, Cin, Ly, Lx] tensor the ensemble call exists to avoid.  The chain, the kept steps, the frame
+ * buffers and the workspace are those of lns_rollout_latent_ensemble; a counting kernel follows the decode of a group on its
+ * decode stream (one pixel per thread, grid over pixel tiles and planes, as the quantile kernel).
+ *
+ * The statement, for one pixel of plane (b, kept step i, channel c) and threshold k:
+ *     v_m = D_c(f_m), q = D_c(y), D_c the map of lns_eval_spec as written above for lns_rollout_latent_ensemble_eval (product
+ *     and sum rounded one by one, wall-zero and clamp flags included; eps unused); norm == NULL: v_m = f_m and q = y, in
+ *     normalised units.
+ *         n = #{m : v_m > thr[k][c]}        (0 .. M)
+ *         o = (q > thr[k][c]) ? 1 : 0
+ *     thr[k][c] in the units of v; a NaN compares false in both comparisons.
+ *     table[b][i][k][c][o][n] = the number of the plane's H * W pixels with that (o, n)
+ * table_out is int32 [B][n_keep][n_thr][Cin][2][M+1]; every [b][i][k][c] slice sums to H * W (H * W <= 2^30 keeps a count
+ * inside int32); there is nothing else in it and no floating point.  The call overwrites the whole table: the caller does
+ * not zero it.  Counts are added with integer atomics (LDS per block, then one global add per non-zero bin); integer adds
+ * commute and never round, so the table is the same bits whatever the grouping or the scheduling options, and there is no
+ * finish kernel.  The scores are float64 functions of the table, taken on the host (the Python package: metrics.brier_scores,
+ * reliability_curve, roc_curve, contingency_scores).
+ *
+ * lns_ensemble_exceed_spec: n_thr thresholds thr[k][c], c < in_channels; size = sizeof(lns_ensemble_exceed_spec). */
+typedef struct lns_ensemble_exceed_spec {
+    uint32_t size; int32_t n_thr;   /* 1 .. 8 */
+    float thr[8][8];                /* thr[k][c], c < in_channels, in the units of v */
+} lns_ensemble_exceed_spec;
+
+/* z_in, param, keep_steps_host, z_last, B, M, T: as lns_rollout_latent_ensemble, with 1 <= M <= 128; in_channels <= 8.
+ * y_true [B][n_keep][Cin][Ly][Lx]: the normalised truth of the KEPT steps, as for lns_rollout_latent_ensemble_eval.
+ * norm (nullable): the denormalisation of members and truth.  mean_out / var_out (both nullable; var_out needs mean_out and
+ * M >= 2): lns_rollout_latent_ensemble's outputs, same bits; the reduction kernel runs only when mean_out is given.
+ * workspace: lns_rollout_ensemble_workspace_bytes(B, M), no more.
+ * Trace / timing modes, lns_check_finite (with B*M) and the status codes: as lns_rollout_latent_ensemble. */
+int lns_rollout_latent_ensemble_exceed(lns_engine* e, const float* z_in, const float* param, const float* y_true,
+                                       int B, int M, int T, const int* keep_steps_host, int n_keep,
+                                       const lns_ensemble_exceed_spec* xspec, const lns_eval_spec* norm /* nullable */,
+                                       int32_t* table_out,   /* [B][n_keep][n_thr][Cin][2][M+1] */
+                                       float* mean_out, float* var_out, float* z_last,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- streaming validation: energy spectra of forecast, truth and error ---------------------------------------------
  * lns_rollout_eval / lns_rollout_latent_eval with, for selected steps, the shell-summed energy spectra of the forecast,
  * of the truth and of their difference, taken where the step is decoded: a spectrum needs the whole plane of a step, i.e.
@@ -884,7 +928,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * lns_rollout_latent_eval_maps, their size query, lns_op_time_maps and lns_time_maps_state_bytes are there;
  * "op_conv_gn" = lns_op_conv_gn is there; "op_fa_fused" = lns_op_fa_fused is there; "eval_attrib" = lns_rollout_eval_attrib, lns_rollout_latent_eval_attrib, their
  * size query, lns_autoencode_eval, its size query, lns_op_eval_attrib and lns_op_latent_err are there;
- * "ensemble_quantiles" = lns_rollout_latent_ensemble_quantiles and lns_op_ensemble_quantiles are there.
+ * "ensemble_quantiles" = lns_rollout_latent_ensemble_quantiles and lns_op_ensemble_quantiles are there;
+ * "ensemble_exceed" = lns_rollout_latent_ensemble_exceed and lns_op_ensemble_exceed are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
@@ -1027,6 +1072,15 @@ int lns_op_ensemble_score(const float* frames, const float* y, int n, int B, int
 int lns_op_ensemble_quantiles(const float* frames, int n, int B, int M, int C, int H, int W,
                               const lns_ensemble_quantile_spec* qspec, const lns_eval_spec* norm /* nullable */,
                               float* quant_out, float* prob_out, void* stream);
+
+/* The kernel of lns_rollout_latent_ensemble_exceed on stored member fields, without an engine: frames [n][B][M][C][H][W]
+ * (the layout of a frame buffer) against y [B][n][C][H][W] -> table_out [B][n][n_thr][C][2][M+1] (int32) by the statement
+ * written there; norm nullable (members and truth as they are).  The call zeroes the table ahead of its launch: the whole
+ * table is overwritten.  1 <= M <= 128, B in 1..65535, C <= 8, H * W <= 2^30, n * B * C < 2^31.  Checks precede the launch
+ * (message: lns_create_error()); the call synchronises `stream`. */
+int lns_op_ensemble_exceed(const float* frames, const float* y, int n, int B, int M, int C, int H, int W,
+                           const lns_ensemble_exceed_spec* xspec, const lns_eval_spec* norm /* nullable */,
+                           int32_t* table_out, void* stream);
 
 /* The spectrum kernel of lns_rollout_eval_spectrum on stored fields, without an engine: yhat and y (nullable) [B][T][C][H][W],
  * normalised -> out [B][T][C][K][S], K = 3 (forecast, truth, error) when y is given, K = 1 (the forecast's row, same bits) when

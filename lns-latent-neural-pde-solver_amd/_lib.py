@@ -79,6 +79,13 @@ class LnsEnsembleQuantileSpec(ctypes.Structure):
     ]
 
 
+class LnsEnsembleExceedSpec(ctypes.Structure):
+    """Mirror of `struct lns_ensemble_exceed_spec` (include/lns.h): the thresholds of the exceedance contingency tables."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("n_thr", _I32), ("thr", (ctypes.c_float * LNS_METRIC_MAX_CH) * 8),
+    ]
+
+
 LNS_FIELD_STATS = 12
 
 
@@ -164,6 +171,7 @@ SYMBOLS = [
     "lns_rollout_ensemble_workspace_bytes", "lns_rollout_latent_ensemble", "lns_op_ensemble_stats",
     "lns_rollout_latent_ensemble_eval", "lns_op_ensemble_score",
     "lns_rollout_latent_ensemble_quantiles", "lns_op_ensemble_quantiles",
+    "lns_rollout_latent_ensemble_exceed", "lns_op_ensemble_exceed",
     "lns_spectrum_bins", "lns_rollout_eval_spectrum", "lns_rollout_latent_eval_spectrum", "lns_op_energy_spectrum",
     "lns_rollout_eval_stats", "lns_rollout_latent_eval_stats", "lns_op_field_stats",
     "lns_rollout_eval_maps_workspace_bytes", "lns_rollout_eval_maps", "lns_rollout_latent_eval_maps",
@@ -261,6 +269,10 @@ def lib():
         sp, ip, qp = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.POINTER(LnsEnsembleQuantileSpec)
         L.lns_rollout_latent_ensemble_quantiles.argtypes = [vp, vp, vp, i, i, i, ip, i, qp, sp, vp, vp, vp, vp, vp, vp, c.c_size_t, vp]
         L.lns_op_ensemble_quantiles.argtypes = [vp, i, i, i, i, i, i, qp, sp, vp, vp, vp]
+    if hasattr(L, "lns_rollout_latent_ensemble_exceed"):
+        sp, ip, xp = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.POINTER(LnsEnsembleExceedSpec)
+        L.lns_rollout_latent_ensemble_exceed.argtypes = [vp, vp, vp, vp, i, i, i, ip, i, xp, sp, vp, vp, vp, vp, vp, c.c_size_t, vp]
+        L.lns_op_ensemble_exceed.argtypes = [vp, vp, i, i, i, i, i, i, xp, sp, vp, vp]
     if hasattr(L, "lns_rollout_eval_spectrum"):
         sp, ip = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int)
         L.lns_spectrum_bins.argtypes = [i, i]

@@ -1637,7 +1637,9 @@ struct Runner {
 //                 keep[0 .. n_keep) are decoded into a frame buffer of the workspace and reduced over the members right there
 //                 into `out` (mean) and `var_out` [B][n_keep][xper]; with `scores_out` (lns_rollout_latent_ensemble_eval) also
 //                 scored there against y_true, and `out` may be null; with `qspec` (lns_rollout_latent_ensemble_quantiles) the
-//                 members' quantiles and exceedance probabilities are taken there too, and `out` may be null
+//                 members' quantiles and exceedance probabilities are taken there too, and `out` may be null; with `xspec`
+//                 (lns_rollout_latent_ensemble_exceed) the exceedance contingency tables against y_true are counted there, and
+//                 `out` may be null
 enum SinkKind { SINK_LATENTS, SINK_STEPS, SINK_KEPT, SINK_SCORED, SINK_ENSEMBLE };
 
 // workspace layout: [ z0 | latent ring: NGROUP groups x kdec steps x [B][zper] | NDEC decode arenas | propagator arena ]
@@ -1786,6 +1788,9 @@ struct RolloutCall {
     // SINK_ENSEMBLE with ens_quant (lns_rollout_latent_ensemble_quantiles): qspec, the outputs it asks for, and `spec` below as the
     // nullable denormalisation; `out` (the mean) is optional
     bool ens_quant = false; const lns_ensemble_quantile_spec* qspec = nullptr; float *quant_out = nullptr, *prob_out = nullptr;
+    // SINK_ENSEMBLE with ens_exceed (lns_rollout_latent_ensemble_exceed): xspec, y_true [traj][n_keep], the table, and `spec` below
+    // as the nullable denormalisation; `out` (the mean) is optional
+    bool ens_exceed = false; const lns_ensemble_exceed_spec* xspec = nullptr; int32_t* table_out = nullptr;
     // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
     const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
     float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
@@ -2238,6 +2243,32 @@ static void quantile_args(const lns_ensemble_quantile_spec* qs, const lns_eval_s
         for (int ch = 0; ch < LNS_METRIC_MAX_CH; ++ch) q.thr[k][ch] = qs->thr[k][ch];
 }
 
+// the refusals of a lns_ensemble_exceed_spec and its output, in the order of include/lns.h; nullptr: accepted
+static const char* exceed_spec_refusal(const lns_ensemble_exceed_spec* xs, const int32_t* table_out) {
+    if (!xs || xs->size != sizeof(lns_ensemble_exceed_spec)) return "xspec is null or its size field is not sizeof(lns_ensemble_exceed_spec)";
+    if (xs->n_thr < 1 || xs->n_thr > LNS_EXCEED_MAX) return "xspec: n_thr must be in 1 .. 8";
+    if (!table_out) return "table_out is null";
+    return nullptr;
+}
+
+// the exceedance kernel's arguments (an accepted xspec; norm nullable); frames / kk / y_T / y_t / o_T / o_t are the caller's
+static void exceed_args(const lns_ensemble_exceed_spec* xs, const lns_eval_spec* norm, const float* y, int B, int M, int C, int H, int W,
+                        int32_t* table_out, EnsembleExceedArgs* xp) {
+    EnsembleExceedArgs& x = *xp;
+    memset(&x, 0, sizeof x);
+    x.y = y; x.table = table_out;
+    x.B = B; x.M = M; x.C = C; x.H = H; x.W = W; x.n_thr = xs->n_thr;
+    x.denorm = norm != nullptr;
+    if (norm) score_norm(norm, C, &x.norm);
+    for (int k = 0; k < xs->n_thr; ++k)
+        for (int ch = 0; ch < LNS_METRIC_MAX_CH; ++ch) x.thr[k][ch] = xs->thr[k][ch];
+}
+
+// bytes of an exceedance table [B][n][n_thr][C][2][M + 1]
+static size_t exceed_table_bytes(int B, int n, int n_thr, int C, int M) {
+    return (size_t)B * n * n_thr * C * 2 * (M + 1) * sizeof(int32_t);
+}
+
 // the autoregressive loop of every rollout call: zcur -> T x (propagate ; what the sink does)   (train_stage2_ns2d.py:147-156)
 // The latent chain z_t -> z_{t+1} is strictly sequential, but decode(z_t) depends on z_t only: the chain runs ahead
 // (on the engine's side stream when overlapping; own arena) writing groups of `kdec` consecutive decoded latents into
@@ -2302,6 +2333,11 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     if (ens && c.ens_quant) {
         quantile_args(c.qspec, c.spec, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, c.quant_out, c.prob_out, &qa);
         qa.o_T = c.n_keep;
+    }
+    EnsembleExceedArgs xa;
+    if (ens && c.ens_exceed) {
+        exceed_args(c.xspec, c.spec, c.y_true, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, c.table_out, &xa);
+        xa.y_T = xa.o_T = c.n_keep;
     }
     SpectrumArgs sx;
     if (scored && c.spectra) spectrum_args(e, c, &sx);
@@ -2462,6 +2498,10 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
             qa.frames = fb; qa.kk = kk; qa.o_t = i0;
             HIPCHK(e, launch_ensemble_quantile(qa, dstream[d]));
         }
+        if (ens && c.ens_exceed) {                   // fb is [kk][traj][M][xper] against y_true[b][i0 .. i0 + kk) -> counts added into table_out
+            xa.frames = fb; xa.kk = kk; xa.y_t = xa.o_t = i0;
+            HIPCHK(e, launch_ensemble_exceed(xa, dstream[d]));
+        }
         if (ens && c.out) {                          // fb is [kk][traj][M][xper] -> mean / var of out[b][i0 .. i0 + kk)
             EnsembleStatsArgs es;
             es.frames = fb; es.mean = c.out + (long)i0 * xper; es.var = c.var_out ? c.var_out + (long)i0 * xper : nullptr;
@@ -2495,12 +2535,15 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
     const bool scored = c.sink == SINK_SCORED, ens = c.sink == SINK_ENSEMBLE, kept = c.sink == SINK_KEPT || ens;
     const bool ens_scored = ens && c.ens_scored;     // lns_rollout_latent_ensemble_eval: every output but scores_out is optional
     const bool ens_quant = ens && c.ens_quant;       // lns_rollout_latent_ensemble_quantiles: the mean is optional
+    const bool ens_exceed = ens && c.ens_exceed;     // lns_rollout_latent_ensemble_exceed: likewise
     if (!c.start) return einval(e, c.encode ? "x is null" : "z_in is null");
-    if ((scored || ens_scored) && !c.y_true) return einval(e, "y_true is null");
+    if ((scored || ens_scored || ens_exceed) && !c.y_true) return einval(e, "y_true is null");
     if (ens_scored && !c.scores_out) return einval(e, "scores_out is null");
     if (ens_quant)
         if (const char* why = quantile_spec_refusal(c.qspec, c.quant_out, c.prob_out)) return einval(e, why);
-    if (!scored && !ens_scored && !ens_quant && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
+    if (ens_exceed)
+        if (const char* why = exceed_spec_refusal(c.xspec, c.table_out)) return einval(e, why);
+    if (!scored && !ens_scored && !ens_quant && !ens_exceed && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
     if ((ens ? c.traj : c.B) <= 0) return einval(e, "B must be positive");
     if (ens && c.M <= 0) return einval(e, "M must be positive");
     if (c.T <= 0) return einval(e, "T must be positive");
@@ -2515,6 +2558,12 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
         if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
         if (c.spec && c.spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "norm: the per-channel form needs in_channels <= 8");
         if (c.qspec->n_thr > 0 && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "thresholds need in_channels <= 8");
+    }
+    if (ens_exceed) {
+        if (c.M > LNS_SCORE_MAX_MEMBERS) return einval(e, "ensemble exceedance needs M in 1 .. 128");
+        if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
+        if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
+        if (e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "thresholds need in_channels <= 8");
     }
     if (scored) {
         if (c.t0 < 0 || (long)c.t0 + c.T > c.T_total) {
@@ -2616,6 +2665,10 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     }
     // time maps: the horizon's first call clears the state on the caller's stream, which every stream of the loop starts behind
     if (scored && c.maps && c.t0 == 0) HIPCHK(e, hipMemsetAsync(base + L.maps_off, 0, L.maps_bytes, r.stream));
+    // exceedance tables: the kernels of every decode stream add into table_out, so it is cleared here, on the caller's stream,
+    // which every stream of the loop starts behind (its fork event is recorded after this memset)
+    if (c.sink == SINK_ENSEMBLE && c.ens_exceed)
+        HIPCHK(e, hipMemsetAsync(c.table_out, 0, exceed_table_bytes(c.traj, c.n_keep, c.xspec->n_thr, cfg.in_channels, c.M), r.stream));
     if ((rc = rollout_loop(e, r, z0, c, L))) return rc;
     // every plane's pair is in place once the decode streams have joined: frame- and sequence-wise ratios, once the
     // horizon is complete (the pairs of the earlier chunks are in the workspace)
@@ -2911,6 +2964,18 @@ int lns_rollout_latent_ensemble_quantiles(lns_engine* e, const float* z_in, cons
     return rollout_call(e, c);
 }
 
+// ---- ensemble exceedance tables (include/lns.h) -----------------------------------------------------------------
+int lns_rollout_latent_ensemble_exceed(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int M, int T,
+                                       const int* keep_steps_host, int n_keep, const lns_ensemble_exceed_spec* xspec,
+                                       const lns_eval_spec* norm, int32_t* table_out, float* mean_out, float* var_out,
+                                       float* z_last, void* ws, size_t ws_bytes, void* stream) {
+    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
+    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
+    c.ens_exceed = true; c.xspec = xspec; c.spec = norm; c.y_true = y_true; c.table_out = table_out;
+    c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
+    return rollout_call(e, c);
+}
+
 int lns_check_finite(lns_engine* e, int B, void* ws, size_t ws_bytes, void* stream) {
     if (!e || B <= 0 || !ws) return LNS_EINVAL;
     // The amax vectors live in the CALLER's workspace: they are read through the `ws` handed in here, which must be
@@ -3006,6 +3071,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "rollout_ensemble")) return 1;
     if (!strcmp(feature, "ensemble_score")) return 1;
     if (!strcmp(feature, "ensemble_quantiles")) return 1;
+    if (!strcmp(feature, "ensemble_exceed")) return 1;
     if (!strcmp(feature, "eval_spectrum")) return 1;
     if (!strcmp(feature, "eval_stats")) return 1;
     if (!strcmp(feature, "eval_maps")) return 1;
@@ -3415,6 +3481,29 @@ int lns_op_ensemble_quantiles(const float* frames, int n, int B, int M, int C, i
     quantile_args(qspec, norm, B, M, C, H, W, quant_out, prob_out, &a);
     a.frames = frames; a.kk = n; a.o_T = n; a.o_t = 0;
     OPCHK(launch_ensemble_quantile(a, s));
+    OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+// ensemble_exceed_kernel on stored member fields: frames [n][B][M][C][H][W] against y [B][n][C][H][W] -> table_out [B][n][n_thr][C][2][M + 1]
+int lns_op_ensemble_exceed(const float* frames, const float* y, int n, int B, int M, int C, int H, int W,
+                           const lns_ensemble_exceed_spec* xspec, const lns_eval_spec* norm, int32_t* table_out, void* stream) {
+    if (!frames || !y) { g_create_error = "ensemble_exceed: frames or y is null"; return LNS_EINVAL; }
+    if (const char* why = exceed_spec_refusal(xspec, table_out)) { g_create_error = fmt("ensemble_exceed: %s", why); return LNS_EINVAL; }
+    if (norm && op_spec_refused("ensemble_exceed", norm)) return LNS_EINVAL;
+    if (M < 1 || M > LNS_SCORE_MAX_MEMBERS) { g_create_error = "ensemble_exceed: M in 1 .. 128"; return LNS_EINVAL; }
+    if (n < 1 || B < 1 || B > LNS_MAX_BATCH || C < 1 || H < 1 || W < 1 || (int64_t)H * W > (1 << 30) ||
+        (int64_t)n * B * C > 0x7fffffffLL) {
+        g_create_error = "ensemble_exceed: n >= 1, B in 1..65535, C, H, W >= 1, H * W <= 2^30, n * B * C < 2^31"; return LNS_EINVAL;
+    }
+    if (C > LNS_METRIC_MAX_CH) { g_create_error = "ensemble_exceed: thresholds need C <= 8"; return LNS_EINVAL; }
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EnsembleExceedArgs a;
+    exceed_args(xspec, norm, y, B, M, C, H, W, table_out, &a);
+    a.frames = frames; a.kk = n; a.y_T = a.o_T = n; a.y_t = a.o_t = 0;
+    OPCHK(hipMemsetAsync(table_out, 0, exceed_table_bytes(B, n, xspec->n_thr, C, M), s));   // the kernel adds
+    OPCHK(launch_ensemble_exceed(a, s));
     OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
 }

@@ -441,6 +441,22 @@ struct EnsembleQuantileArgs {
 };
 hipError_t launch_ensemble_quantile(const EnsembleQuantileArgs& a, hipStream_t s);
 
+// Ensemble exceedance tables (lns_rollout_latent_ensemble_exceed, lns_op_ensemble_exceed; the statement: include/lns.h): member
+// frames [kk][B][M][C][H*W] against the truth planes y[b][y_t + j][c] of y [B][y_T][C][H*W] -> per plane and threshold k the
+// counts of its pixels by (o, n), o = truth above thr[k][c], n = members above it, ADDED into
+// table[b][o_t + j][k][c][o][n] of table [B][o_T][n_thr][C][2][M + 1] (int32), which the caller zeroes ahead of the launch.
+// Grid (pixel tiles of 256, planes (j, b, c)), one pixel per thread; dynamic LDS: n_thr * 2 * (M + 1) * 4 bytes.
+// denorm = 0: members and truth as they are (norm unused); else norm, as MetricGroupArgs.  1 <= M <= 128, 1 <= n_thr <= 8,
+// C <= 8, H * W <= 2^30.  q0: the launch's first plane (set by the launcher).
+#define LNS_EXCEED_MAX 8
+struct EnsembleExceedArgs {
+    const float* frames; const float* y; int* table;
+    int B, M, C, H, W, kk, y_T, y_t, o_T, o_t, n_thr, denorm, q0;
+    ScoreNorm norm;
+    float thr[LNS_EXCEED_MAX][LNS_METRIC_MAX_CH];
+};
+hipError_t launch_ensemble_exceed(const EnsembleExceedArgs& a, hipStream_t s);
+
 // Energy spectra (lns_rollout_eval_spectrum, lns_op_energy_spectrum; the statement: include/lns.h): one block per plane
 // writes its K x S shell energies, K = 3 (forecast, truth, error) with y, K = 1 (forecast) without; S = lns_spectrum::bins(H, W).
 // Group form: frames [kk][B][C][H*W] (a decode stream's frame buffer); the n <= 8 selected steps sel[0 .. n) of the group

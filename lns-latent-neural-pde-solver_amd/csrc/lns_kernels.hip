@@ -5297,6 +5297,7 @@ hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int 
 #include "time_maps.inc"
 #include "eval_attrib.inc"
 #include "ensemble_quantile.inc"
+#include "ensemble_exceed.inc"
 
 // per-sample max |x| of a [B, n] tensor: grid (chunks, B); one atomic per wave
 __global__ __launch_bounds__(256) void amax_kernel(const float* x, long x_bs, long n, unsigned* amax) {

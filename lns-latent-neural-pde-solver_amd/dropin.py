@@ -552,6 +552,30 @@ class LatentDynamics(_Hosted):
         return self._engine(z).rollout_latent_ensemble_eval(z, y, param=param, keep_steps=keep_steps, **norm)
 
     @torch.no_grad()
+    def validate_exceedance(self, x, y, *rest, thresholds, generator=None, control=True, keep_steps=None, **norm):
+        """validate_exceedance(x, y, members, noise_level, thresholds=...) -- conditional: validate_exceedance(x, y, param,
+        members, noise_level, thresholds=...): the ensemble forecast of `validate_ensemble` over T = y.shape[1] steps (same
+        encode, same noise from the same generator state, same `control`) verified as an event forecast: for every kept step,
+        threshold and channel the integer table of how many pixels had n of the members above the threshold while the truth
+        was / was not above it, counted as the members are decoded (engine.EnsembleExceedance).  `metrics.brier_scores`,
+        `reliability_curve`, `roc_curve` and `contingency_scores` turn a table into scores; `predict_quantiles`' `prob` is the
+        forecast they verify.  thresholds: scalars or per-channel sequences, in the units of the values; `norm` as in
+        `validate` (none: normalised values); keep_steps as for predict (None: every step).  members >= 1."""
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("validate_exceedance() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if len(rest) != 2:
+            raise TypeError("validate_exceedance() takes (x, y, param, members, noise_level)" if self._conditional
+                            else "validate_exceedance() takes (x, y, members, noise_level)")
+        members, noise_level = int(rest[0]), float(rest[1])
+        if members < 1:
+            raise LnsError("members must be at least 1, got %d" % members)
+        z = self._ensemble_latents(x, members, noise_level, generator, control)
+        return self._engine(z).rollout_latent_ensemble_exceed(z, y, None, thresholds, param=param, keep_steps=keep_steps, **norm)
+
+    @torch.no_grad()
     def validate(self, x, y, *rest, keep_steps=(), **norm):
         """validate(x, y, **norm) -- conditional: validate(x, y, param, **norm): the body of the reference's validation
         loop (train_stage2_ns2d.py:249-263) in one call,

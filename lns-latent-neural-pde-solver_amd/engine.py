@@ -220,6 +220,30 @@ def quantile_spec(C, members, quantiles=(), thresholds=()):
     return spec
 
 
+EnsembleExceedance = collections.namedtuple("EnsembleExceedance", "table mean var z_last")
+EnsembleExceedance.__doc__ = """Result of Engine.rollout_latent_ensemble_exceed: table [B, n_keep, n_thr, C, 2, M + 1] int32, the
+number of a plane's pixels with the truth above the threshold (index 1 of dim 4) or not (index 0) and n of the M members above
+it (dim 5); and mean, var, z_last where asked for (None otherwise).  The scores: metrics.brier_scores & co."""
+
+
+def exceed_spec(C, thresholds):
+    """`lns_ensemble_exceed_spec` from the thresholds (each a scalar for every channel, or a per-channel sequence); pure
+    host code, so a bad request is refused before any device use."""
+    from . import metrics
+    rows = metrics.threshold_table(thresholds, C)
+    if not 1 <= len(rows) <= 8:
+        raise ValueError("between 1 and 8 thresholds per call, got %d" % len(rows))
+    if C > _lib.LNS_METRIC_MAX_CH:
+        raise ValueError("thresholds: at most %d channels" % _lib.LNS_METRIC_MAX_CH)
+    spec = _lib.LnsEnsembleExceedSpec()
+    spec.size = ctypes.sizeof(_lib.LnsEnsembleExceedSpec)
+    spec.n_thr = len(rows)
+    for k, row in enumerate(rows):
+        for c, v in enumerate(row):
+            spec.thr[k][c] = v
+    return spec
+
+
 EvalSpectra = collections.namedtuple("EvalSpectra", "frame seq frames spectra spectrum_steps")
 EvalSpectra.__doc__ = """Result of Engine.rollout_eval_spectrum: frame [B, T, C], seq [B, C] and frames (or None) as rollout_eval
 returns them, spectra [B, len(spectrum_steps), C, 3, S] (rows: forecast, truth, error; S = metrics.spectrum_bins(Ly, Lx)) and
@@ -791,6 +815,87 @@ class Engine:
                 ctypes.byref(spec) if spec is not None else None, self._ptr(quant), self._ptr(prob), self._ptr(mean), self._ptr(var),
                 self._ptr(z_last), ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_quantiles")
         return EnsembleQuantiles(quant, prob, mean, var, z_last)
+
+    # -- ensemble exceedance tables (include/lns.h "ensemble exceedance") ---------------------------------------------
+    def ensemble_exceed(self, frames, y, thresholds, **norm):
+        """The counting kernel of the exceedance tables on stored member fields (lns_op_ensemble_exceed): frames
+        [n, B, M, C, H, W] (a frame buffer's layout), y [B, n, C, H, W], both normalised; thresholds: each a scalar (every
+        channel) or a per-channel sequence, in the units of the denormalised values; `norm` as in `rollout_eval` (none: the
+        values as they are).  Returns the int32 table [B, n, n_thr, C, 2, M + 1]."""
+        import torch
+        for t in (frames, y):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+                raise LnsError("ensemble_exceed takes fp32 HIP tensors")
+        if frames.dim() != 6 or y.dim() != 5 or y.device != frames.device:
+            raise LnsError("ensemble_exceed takes frames [n, B, M, C, H, W] and y [B, n, C, H, W] on one device")
+        n, B, M, C, H, W = (int(v) for v in frames.shape)
+        if tuple(y.shape) != (B, n, C, H, W):
+            raise LnsError("y must be %s for frames %s, got %s" % ((B, n, C, H, W), tuple(frames.shape), tuple(y.shape)))
+        frames, y = frames.contiguous(), y.contiguous()
+        xs = exceed_spec(C, thresholds)
+        spec = eval_spec(C, **norm) if norm else None
+        table = torch.empty((B, n, xs.n_thr, C, 2, M + 1), dtype=torch.int32, device=y.device)
+        with torch.cuda.device(y.device):
+            rc = self._L.lns_op_ensemble_exceed(frames.data_ptr(), y.data_ptr(), n, B, M, C, H, W, ctypes.byref(xs),
+                                                ctypes.byref(spec) if spec is not None else None, table.data_ptr(),
+                                                self._stream(y))
+        if rc != 0:
+            raise LnsError("lns_op_ensemble_exceed failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return table
+
+    def rollout_latent_ensemble_exceed(self, z, y, steps, thresholds, param=None, keep_steps=None, return_mean=False,
+                                       return_var=False, return_last=False, **norm):
+        """rollout_latent_ensemble with, per kept step, threshold and channel, the contingency table of the event "value above
+        the threshold": how many of the plane's pixels had n of the M members above it while the truth was (1) or was not (0)
+        above it, counted as the members are decoded.  z [B, M, c, h, w] as there (1 <= M <= 128), y [B, T, C, Ly, Lx] the
+        normalised truth of all `steps` = T steps (None: y.shape[1]; the kept ones, y[:, keep_steps], are what is compared);
+        thresholds: each a scalar (every channel) or a per-channel sequence, in the units of the values; `norm` as in
+        `rollout_eval` -- without it members and truth are compared in normalised units.  Returns EnsembleExceedance;
+        return_mean / return_var / return_last add rollout_latent_ensemble's outputs.  The member fields are never stored;
+        the workspace is rollout_latent_ensemble's.  The scores are functions of the table: metrics.brier_scores,
+        reliability_curve, roc_curve, contingency_scores."""
+        import torch
+        z = self._dev(z)
+        y = self._dev(y)
+        C, H, W = self.latent_shape()
+        c = self.cfg
+        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
+            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
+        B, M = int(z.shape[0]), int(z.shape[1])
+        if y.dim() != 5 or y.shape[0] != B or tuple(y.shape[2:]) != (c.in_channels, c.Ly, c.Lx) or y.dtype != torch.float32:
+            raise LnsError("ground truth must be fp32 [B, T, %d, %d, %d] with the latents' batch, got %s"
+                           % (c.in_channels, c.Ly, c.Lx, tuple(y.shape)))
+        if y.device != z.device:
+            raise LnsError("ground truth is on %s but the latents are on %s" % (y.device, z.device))
+        if return_var and not return_mean:
+            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
+        if return_var and M < 2:
+            raise LnsError("the variance needs at least 2 members, got M = %d" % M)
+        steps = int(y.shape[1]) if steps is None else int(steps)
+        if steps > y.shape[1]:
+            raise LnsError("%d steps do not fit the %d steps of the ground truth" % (steps, y.shape[1]))
+        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
+        arr = (ctypes.c_int * len(keep))(*keep)
+        nk = len(keep)
+        yk = y[:, keep].contiguous()
+        xs = exceed_spec(c.in_channels, thresholds)
+        spec = eval_spec(c.in_channels, **norm) if norm else None
+        table = torch.empty((B, nk, xs.n_thr, c.in_channels, 2, M + 1), dtype=torch.int32, device=z.device)
+        shape = (B, nk, c.in_channels, c.Ly, c.Lx)
+        mean = torch.empty(shape, dtype=torch.float32, device=z.device) if return_mean else None
+        var = torch.empty(shape, dtype=torch.float32, device=z.device) if return_var else None
+        z_last = torch.empty_like(z) if return_last else None
+        p = self._member_param(param, z, B, M)
+        with torch.cuda.device(z.device):
+            n = ctypes.c_size_t(0)
+            self._check(self._L.lns_rollout_ensemble_workspace_bytes(self._h, B, M, ctypes.byref(n)),
+                        "lns_rollout_ensemble_workspace_bytes")
+            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+            self._check(self._L.lns_rollout_latent_ensemble_exceed(
+                self._h, z.data_ptr(), self._ptr(p), yk.data_ptr(), B, M, steps, arr, nk, ctypes.byref(xs),
+                ctypes.byref(spec) if spec is not None else None, table.data_ptr(), self._ptr(mean), self._ptr(var),
+                self._ptr(z_last), ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_exceed")
+        return EnsembleExceedance(table, mean, var, z_last)
 
     # -- streaming validation rollout (include/lns.h "streaming validation rollout") --------------------------------
     def _eval_common(self, first, y, steps, t0, keep_steps, norm):

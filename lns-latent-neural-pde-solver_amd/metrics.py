@@ -10,6 +10,7 @@ The other datasets' denormalize() (per-channel statistics, dataset/Stage2_SW.py:
 zeroed and VOF clamped, dataset/twophase_flow_stage2.py:370-390) are the same kernel with a per-channel spec:
 `relative_l2(..., mean=[...], std=[...], zero_wall_channels=(0, 1), clamp_channels=(3,))` or `twophase_spec(...)`.
 """
+import collections
 import ctypes
 
 import torch
@@ -374,6 +375,139 @@ def ensemble_quantiles(fields, quantiles=(), thresholds=(), **norm):
             rows.append((v > th).sum(0).to(torch.float32) / fm)
         prob = torch.stack(rows, 2)
     return quant, prob
+
+
+@torch.no_grad()
+def exceedance_table(fields, y, thresholds, **norm):
+    """The stored-path statement of Engine.rollout_latent_ensemble_exceed / ensemble_exceed (include/lns.h "ensemble
+    exceedance") in elementwise torch ops and `bincount`, on whatever device `fields` lives on: fields [B, M, n, C, H, W], the
+    stored member rollouts, y [B, n, C, H, W] the truth of the same steps -> int32 table [B, n, n_thr, C, 2, M + 1]: per plane
+    and threshold the number of pixels with the truth above the threshold (dim 4: 1) or not (0) and n members above it
+    (dim 5).  `norm` as in `relative_l2` (none: the values as they are).  It needs the member fields the streaming call never
+    stores: for checks and small cases."""
+    if fields.dim() != 6 or fields.dtype != torch.float32:
+        raise ValueError("expected fp32 member fields [B, M, n, C, H, W]")
+    B, M, n, C, H, W = fields.shape
+    if tuple(y.shape) != (B, n, C, H, W) or y.dtype != torch.float32 or y.device != fields.device:
+        raise ValueError("expected the fp32 truth [B, n, C, H, W] of the member fields, on their device")
+    thr = threshold_table(thresholds, C)
+    if not 1 <= len(thr) <= 8:
+        raise ValueError("between 1 and 8 thresholds per call, got %d" % len(thr))
+    v = _denormalise(fields, **norm) if norm else fields
+    q = _denormalise(y, **norm) if norm else y
+    M1 = M + 1
+    plane = torch.arange(B * n * C, dtype=torch.int64, device=fields.device).view(B, n, C, 1, 1) * (2 * M1)
+    rows = []
+    for row in thr:
+        th = torch.tensor(row, dtype=torch.float32, device=fields.device).view(C, 1, 1)
+        cnt = (v > th).sum(1, dtype=torch.int64)                        # [B, n, C, H, W]: n of the statement
+        obs = (q > th).to(torch.int64)
+        idx = plane + obs * M1 + cnt
+        rows.append(torch.bincount(idx.reshape(-1), minlength=B * n * C * 2 * M1).view(B, n, C, 2, M1))
+    return torch.stack(rows, 2).to(torch.int32)
+
+
+def _table64(table):
+    """An exceedance table [..., 2, M + 1] (torch or numpy, any integer type) -> (N0, N1, M) as float64 numpy arrays [..., M + 1]."""
+    import numpy as np
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    if t.ndim < 2 or t.shape[-2] != 2 or t.shape[-1] < 2:
+        raise ValueError("expected an exceedance table [..., 2, M + 1], got %s" % (tuple(t.shape),))
+    t = t.astype(np.float64)
+    return t[..., 0, :], t[..., 1, :], t.shape[-1] - 1
+
+
+BrierScores = collections.namedtuple("BrierScores", "bs bs_fair reliability resolution uncertainty base_rate")
+BrierScores.__doc__ = """metrics.brier_scores: the Brier score, its fair (member-count corrected) form, the reliability,
+resolution and uncertainty terms (bs = reliability - resolution + uncertainty) and the event's base rate; float64 [...]."""
+RocCurve = collections.namedtuple("RocCurve", "pofd pod auc")
+RocCurve.__doc__ = """metrics.roc_curve: probability of false detection and of detection [..., M + 2] for the cut-offs n >= j,
+j = M + 1 .. 0 (from (0, 0) to (1, 1)), and the area under them by the trapezoid rule [...]; float64."""
+ContingencyScores = collections.namedtuple("ContingencyScores", "hits misses false_alarms correct_negatives pod far csi")
+ContingencyScores.__doc__ = """metrics.contingency_scores: the 2 x 2 counts (int64 [...]) of the forecast "at least min_members
+members above the threshold" and POD = hits / (hits + misses), FAR = false_alarms / (hits + false_alarms), CSI = hits /
+(hits + misses + false_alarms) -- the IoU of the forecast region and the true one; float64 [...], NaN over 0."""
+
+
+def brier_scores(table):
+    """Brier score of the exceedance probability p = n / M and its decomposition, from an exceedance table [..., 2, M + 1]
+    (frame-wise as the call returns it, or `table.sum(1, dtype=torch.int64)` for the sequence-wise form); float64, on the host.
+    With N[o][n] the counts, N their sum, p_n = n / M, N_n = N[0][n] + N[1][n], obar_n = N[1][n] / N_n (empty bins skipped),
+    base = sum N[1] / N:
+        bs = (1/N) sum_n [N[1][n] (1 - p_n)^2 + N[0][n] p_n^2]
+        reliability = (1/N) sum N_n (p_n - obar_n)^2;  resolution = (1/N) sum N_n (obar_n - base)^2;  uncertainty = base (1 - base)
+        bs_fair = bs - (1/N) sum N_n n (M - n) / (M^2 (M - 1))          (M = 1: bs_fair = bs)
+    The forecast takes M + 1 values only, so bs = reliability - resolution + uncertainty exactly (no within-bin term).  An
+    event that never or always occurs has uncertainty = resolution = 0 and bs = reliability; members that all agree have
+    bs_fair = bs; an empty table (N = 0) gives NaN."""
+    import numpy as np
+    N0, N1, M = _table64(table)
+    n = np.arange(M + 1, dtype=np.float64)
+    p = n / M
+    Nn = N0 + N1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        N = Nn.sum(-1)
+        inv = np.where(N > 0, 1.0 / N, np.nan)
+        base = N1.sum(-1) * inv
+        obar = np.where(Nn > 0, N1 / np.where(Nn > 0, Nn, 1.0), 0.0)
+        bs = (N1 * (1.0 - p) ** 2 + N0 * p ** 2).sum(-1) * inv
+        rel = (Nn * (p - obar) ** 2).sum(-1) * inv                      # (an empty bin has N_n = 0: no term)
+        res = (Nn * (obar - base[..., None]) ** 2).sum(-1) * inv
+        unc = base * (1.0 - base)
+        fair = bs - (Nn * (n * (M - n) / (M * M * (M - 1.0)))).sum(-1) * inv if M > 1 else bs.copy()
+    return BrierScores(bs, fair, rel, res, unc, base)
+
+
+def reliability_curve(table):
+    """The reliability diagram of an exceedance table [..., 2, M + 1]: (p_n [M + 1], obar_n [..., M + 1], N_n [..., M + 1]) --
+    the forecast probability n / M, the observed frequency of the event among the pixels that got it (NaN for an empty bin)
+    and their number (int64); float64, on the host."""
+    import numpy as np
+    N0, N1, M = _table64(table)
+    Nn = N0 + N1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        obar = np.where(Nn > 0, N1 / np.where(Nn > 0, Nn, 1.0), np.nan)
+    return np.arange(M + 1, dtype=np.float64) / M, obar, Nn.astype(np.int64)
+
+
+def roc_curve(table):
+    """The ROC curve of an exceedance table [..., 2, M + 1]: the forecast "at least j members above the threshold" for
+    j = M + 1 .. 0 has pod_j = sum_{n >= j} N[1][n] / sum N[1] and pofd_j = sum_{n >= j} N[0][n] / sum N[0] (M + 2 points from
+    (0, 0) to (1, 1)); auc by the trapezoid rule, which is the Mann-Whitney statistic P(n_event > n_other) + P(equal) / 2.
+    Where the event never occurs pod and auc are NaN, where it always occurs pofd and auc are NaN.  RocCurve, float64."""
+    import numpy as np
+    N0, N1, M = _table64(table)
+
+    def tail(Nx):                                                       # j = M + 1 .. 0: 0, N[M], N[M] + N[M-1], ...
+        c = np.cumsum(Nx[..., ::-1], -1)
+        c = np.concatenate([np.zeros_like(c[..., :1]), c], -1)
+        tot = c[..., -1:]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(tot > 0, c / np.where(tot > 0, tot, 1.0), np.nan)
+    pofd, pod = tail(N0), tail(N1)
+    auc = ((pofd[..., 1:] - pofd[..., :-1]) * (pod[..., 1:] + pod[..., :-1]) * 0.5).sum(-1)
+    return RocCurve(pofd, pod, auc)
+
+
+def contingency_scores(table, min_members):
+    """Hits, misses, false alarms and correct negatives of the yes / no forecast "at least `min_members` of the M members
+    above the threshold" (1 <= min_members <= M) from an exceedance table [..., 2, M + 1], and POD, FAR, CSI from them
+    (ContingencyScores).  With M = 1 and min_members = 1 this is the deterministic forecast's table, and CSI the IoU of the
+    forecast region and the true one.  A ratio over 0 (no event and no forecast of it) is NaN."""
+    import numpy as np
+    N0, N1, M = _table64(table)
+    j = int(min_members)
+    if not 1 <= j <= M:
+        raise ValueError("min_members must be in 1 .. %d, got %d" % (M, j))
+    hits, misses = N1[..., j:].sum(-1), N1[..., :j].sum(-1)
+    fa, cn = N0[..., j:].sum(-1), N0[..., :j].sum(-1)
+
+    def ratio(a, b):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(b > 0, a / np.where(b > 0, b, 1.0), np.nan)
+    i64 = lambda a: a.astype(np.int64)                                  # noqa: E731
+    return ContingencyScores(i64(hits), i64(misses), i64(fa), i64(cn), ratio(hits, hits + misses), ratio(fa, hits + fa),
+                             ratio(hits, hits + misses + fa))
 
 
 def sw_norm(u_mean, u_std, v_mean, v_std, pres_mean, pres_std):

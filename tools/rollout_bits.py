@@ -2,8 +2,9 @@
 """What do the rollout entry points enqueue?  One JSON object: "case/entry/options" -> {output tensor: first 16 hex digits of the
 sha256 of its bytes} for every rollout entry point of `Engine` (rollout, rollout with to_x=False, rollout with keep_steps,
 rollout_latent, rollout_latent with keep_steps, rollout_eval, rollout_latent_eval in one chunk and in two, 4 + 3,
-rollout_latent_ensemble with M = 3 members, rollout_latent_ensemble_eval and rollout_latent_ensemble_quantiles (three quantiles,
-one threshold, mean / var / z_last as well) on the same members where the library has them, and
+rollout_latent_ensemble with M = 3 members, rollout_latent_ensemble_eval, rollout_latent_ensemble_quantiles (three quantiles,
+one threshold, mean / var / z_last as well) and rollout_latent_ensemble_exceed (the same threshold against y; mean / var / z_last
+as well) on the same members where the library has them, and
 the six newer scored calls -- rollout_eval_spectrum / _stats / _maps from x and their rollout_latent_ forms in two chunks, 4 + 3:
 spectra at steps [0, 3, 6], statistics at [1, 2, 6] with an 8-bin histogram, maps from step 1 every 2, the _maps forms with all
 three selections together; every tensor they return is hashed, the chunks' per-step tensors concatenated) under
@@ -50,7 +51,7 @@ KEEP = [1, 4, 6]
 CHUNKS = ((0, 4, [1]), (4, 3, [0, 2]))              # (t0, steps, keep_steps of the chunk): KEEP again
 NORM = dict(mean=0.37, std=1.9)
 MEMBERS, NOISE = 3, 0.05                            # rollout_latent_ensemble: z0 + NOISE * filler.normal per member
-QUANTILES, THRESHOLDS = (0.05, 0.5, 0.95), (0.5,)      # rollout_latent_ensemble_quantiles
+QUANTILES, THRESHOLDS = (0.05, 0.5, 0.95), (0.5,)      # rollout_latent_ensemble_quantiles, rollout_latent_ensemble_exceed
 SPECTRUM_STEPS, STATS_STEPS, HIST, MAP_STEPS = [0, 3, 6], [1, 2, 6], (8, -4.0, 4.0), (1, 2)
 DECODE_GROUPS = (None, 1, 2, 0)                     # None: never set (it comes first); 0: automatic, here one group of all T steps
 
@@ -158,6 +159,10 @@ def entries(eng, x, y, p):
             q = eng.rollout_latent_ensemble_quantiles(ze, T, QUANTILES, THRESHOLDS, param=p, keep_steps=KEEP, return_mean=True,
                                                       return_var=True, return_last=True, **NORM)
             yield "rollout_latent_ensemble_quantiles", dict(quantiles=q.quantiles, prob=q.prob, mean=q.mean, var=q.var, z_last=q.z_last)
+        if eng._L.lns_build_has(b"ensemble_exceed") == 1:
+            r = eng.rollout_latent_ensemble_exceed(ze, y, T, THRESHOLDS, param=p, keep_steps=KEEP, return_mean=True, return_var=True,
+                                                   return_last=True, **NORM)
+            yield "rollout_latent_ensemble_exceed", dict(table=r.table, mean=r.mean, var=r.var, z_last=r.z_last)
     for name, sel in (("spectrum", dict(spectrum_steps=SPECTRUM_STEPS)), ("stats", dict(stats_steps=STATS_STEPS, hist=HIST)),
                       ("maps", dict(map_steps=MAP_STEPS, stats_steps=STATS_STEPS, hist=HIST, spectrum_steps=SPECTRUM_STEPS))):
         if eng._L.lns_build_has(b"eval_" + name.encode()) == 1:
