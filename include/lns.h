@@ -929,7 +929,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * "op_conv_gn" = lns_op_conv_gn is there; "op_fa_fused" = lns_op_fa_fused is there; "eval_attrib" = lns_rollout_eval_attrib, lns_rollout_latent_eval_attrib, their
  * size query, lns_autoencode_eval, its size query, lns_op_eval_attrib and lns_op_latent_err are there;
  * "ensemble_quantiles" = lns_rollout_latent_ensemble_quantiles and lns_op_ensemble_quantiles are there;
- * "ensemble_exceed" = lns_rollout_latent_ensemble_exceed and lns_op_ensemble_exceed are there.
+ * "ensemble_exceed" = lns_rollout_latent_ensemble_exceed and lns_op_ensemble_exceed are there; "op_fa_axis" =
+ * lns_op_fa_reducer, lns_op_fa_lrk, lns_op_ln_pe, lns_op_apply, lns_rotary_table and the two fit predicates are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
@@ -1009,6 +1010,59 @@ typedef struct lns_fa_fused_args {
     float* out; float* amax_out;
 } lns_fa_fused_args;
 int lns_op_fa_fused(const lns_fa_fused_args* args, void* stream);
+/* The kernels that build a FABlock's Kx / Ky, the SABlock pre-norm and the GroupNorm materialisation at op level (unit tests;
+ * "op_fa_axis" in lns_build_has).  Existing launchers only, their arguments set as the planner sets them.  Device pointers
+ * are fp32; weights are HOST pointers in the reference's state_dict layout ([out][in]), transposed by the planner's own
+ * helper.  Every check precedes the first HIP call (LNS_EINVAL, message lns_create_error() starting "fa_reducer: ",
+ * "fa_lrk: ", "ln_pe: ", "apply: "); each call synchronises `stream` and frees what it allocated.
+ *
+ * Supported shapes, the planner's own predicates (a plan whose FABlock has none fails at plan time, naming the layer):
+ *   lns_fa_reducer_fits(C, Hid, Out, merged)   the MFMA form (C, Hid multiples of 32, C <= 256, LDS (max(C Hid, 128 Hid, 128 Out)
+ *                                              + 33 (2 C + Hid) + 256) * 4 <= 160 KB) or, one axis per launch only, the
+ *                                              scalar form (LDS (C C + C Hid + Hid Out + 16 (2 C + Hid)) * 4 <= 160 KB)
+ *   lns_fa_lrk_fits(DK, n)                     DK even, LDS 2 DK (n rounded up to 32) * 4 <= 160 KB
+ * 1 / 0; no device needed.
+ *
+ * lns_op_fa_reducer: PoolingReducer on pooled rows, u = W2 gelu(W1 LayerNorm(W_in m)) + b2 (LayerNorm over C, eps 1e-5).
+ *   mx, my       device [B][nx][C], [B][ny][C]; my NULL: the x axis alone (every *_y member is ignored)
+ *   to_in_*      HOST [C][C];  ln_g_*, ln_b_* HOST [C];  w1_* HOST [Hid][C];  w2_* HOST [Out][Hid];  b2_* HOST [Out]
+ *   ux, uy       device [B][Out][nx], [B][Out][ny]
+ *   amax_x/_y    device [B] float or NULL: max |u| of each sample as the kernel recorded it (the maximum over its 16 words)
+ *   form         0: both axes in one launch (needs both; MFMA form only), 1: one launch per axis (MFMA form where it fits,
+ *                else the scalar form).  Hid is a parameter; the planner passes 2 C. */
+typedef struct lns_fa_reducer_args {
+    const float* mx; const float* my; int B, nx, ny, C, Hid, Out, form;
+    const float* to_in_x; const float* ln_g_x; const float* ln_b_x; const float* w1_x; const float* w2_x; const float* b2_x;
+    const float* to_in_y; const float* ln_g_y; const float* ln_b_y; const float* w1_y; const float* w2_y; const float* b2_y;
+    float* ux; float* uy; float* amax_x; float* amax_y;
+} lns_fa_reducer_args;
+int lns_fa_reducer_fits(int C, int Hid, int Out, int merged);
+int lns_op_fa_reducer(const lns_fa_reducer_args* args, void* stream);
+/* lns_op_fa_lrk: LowRankKernel after to_qk, K[b][h] = rot(q[b][h]) rot(k[b][h])^T, no softmax, no scaling.
+ *   qk_x, qk_y   device [B][2 heads DK][n]: q of head h in channels h DK .., k in (heads + h) DK ..; qk_y NULL: the x axis alone
+ *   inv_freq_*   HOST [DK / 2]: the rotary frequencies; the table is lns_rotary_table's
+ *   kx, ky       device [B][heads][n][n]
+ *   form         0: both axes in one launch (needs both, with the same B, heads and DK), 1: one launch per axis */
+typedef struct lns_fa_lrk_args {
+    const float* qk_x; const float* qk_y; int B_x, heads_x, DK_x, nx, B_y, heads_y, DK_y, ny, form;
+    const float* inv_freq_x; const float* inv_freq_y; float* kx; float* ky;
+} lns_fa_lrk_args;
+int lns_fa_lrk_fits(int DK, int n);
+int lns_op_fa_lrk(const lns_fa_lrk_args* args, void* stream);
+/* The rotary table of a plan, no device needed: pos = torch.linspace(0, 1, n) in its float32 arithmetic, f = (pos * 64) *
+ * inv_freq[d] in float32, out_host [half][n][2] = (float)cos((double)f), (float)sin((double)f). */
+int lns_rotary_table(int n, const float* inv_freq_host, int half, float* out_host);
+/* SABlock pre-norm: h[b][c][i] = LayerNorm_c(x[b][:][i]) gamma[c] + beta[c] + pe[i][c].  x device, sample b at x + b * x_bs
+ * floats, [C][n]; gamma, beta HOST [C]; pe_host HOST [pe_len][C] (pe_len >= n) or NULL; h device [B][C][n].
+ * bound_out (HOST float, nullable): the bound of |h| the planner hands the consumer of h,
+ * sqrt(C) max|gamma| + max|beta| + max|pe|. */
+int lns_op_ln_pe(const float* x, int64_t x_bs, int B, int C, int n, const float* gamma_host, const float* beta_host,
+                 const float* pe_host, int pe_len, float eps, float* h, float* bound_out, void* stream);
+/* y[b][c] = act(x[b][c] * scale + shift): x device, sample b at x + b * x_bs floats, [C][HW]; ss device [B][C][2] or NULL:
+ * identity; act 0 none, 1 swish, 2 gelu, 3 relu, 4 tanh, 5 sigmoid; y device [B][C][HW]; amax_out device [B][16] unsigned,
+ * zero-initialised by the caller, or NULL (lns_op_conv2d's side channel: the maximum over the 16 words is max |y[b]|). */
+int lns_op_apply(const float* x, int64_t x_bs, const float* ss, int act, int B, int C, int HW, float* y, unsigned* amax_out,
+                 void* stream);
 /* Diagnostic: runs two convolutions (GroupNorm+Swish prologue, circular padding, stride 1) repeatedly on two HIP
  * streams so that their workgroups share compute units, and counts output words that differ from what each
  * convolution produces alone.  variant_*: tile variant as in lns_op_conv2d (-1 automatic, 6 = bf16x3 3x3 kernel). */

@@ -161,6 +161,19 @@ class LnsFaFusedArgs(ctypes.Structure):
         "b_rev:i out:p amax_out:p")
 
 
+class LnsFaReducerArgs(ctypes.Structure):
+    """Mirror of `struct lns_fa_reducer_args` (include/lns.h): the arguments of lns_op_fa_reducer."""
+    _fields_ = _fields(
+        "mx:p my:p B:i nx:i ny:i C:i Hid:i Out:i form:i to_in_x:p ln_g_x:p ln_b_x:p w1_x:p w2_x:p b2_x:p "
+        "to_in_y:p ln_g_y:p ln_b_y:p w1_y:p w2_y:p b2_y:p ux:p uy:p amax_x:p amax_y:p")
+
+
+class LnsFaLrkArgs(ctypes.Structure):
+    """Mirror of `struct lns_fa_lrk_args` (include/lns.h): the arguments of lns_op_fa_lrk."""
+    _fields_ = _fields(
+        "qk_x:p qk_y:p B_x:i heads_x:i DK_x:i nx:i B_y:i heads_y:i DK_y:i ny:i form:i inv_freq_x:p inv_freq_y:p kx:p ky:p")
+
+
 # every symbol include/lns.h declares (tests check the library exports them all)
 SYMBOLS = [
     "lns_create_error", "lns_create", "lns_destroy", "lns_last_error", "lns_num_params",
@@ -186,6 +199,7 @@ SYMBOLS = [
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
     "lns_op_conv_wgrad_scratch_bytes", "lns_op_conv_wgrad",
     "lns_op_groupnorm_train", "lns_op_gelu_grad", "lns_op_bias_grad",
+    "lns_op_fa_reducer", "lns_fa_reducer_fits", "lns_op_fa_lrk", "lns_fa_lrk_fits", "lns_rotary_table", "lns_op_ln_pe", "lns_op_apply",
     "lns_op_conv2d", "lns_op_conv_gn", "lns_op_fa_fused", "lns_op_conv_pair_stress", "lns_op_groupnorm_stats", "lns_op_attention", "lns_op_fa_sandwich", "lns_op_fa_pool", "lns_op_fourier_block",
     "lns_fourier_block_create", "lns_fourier_block_forward", "lns_fourier_block_destroy", "lns_metric_rel_l2", "lns_metric_rel_l2_ch",
 ]
@@ -342,6 +356,14 @@ def lib():
         L.lns_op_conv_gn.argtypes = [c.POINTER(LnsConvGnArgs), vp]
     if hasattr(L, "lns_op_fa_fused"):
         L.lns_op_fa_fused.argtypes = [c.POINTER(LnsFaFusedArgs), vp]
+    if hasattr(L, "lns_op_fa_reducer"):
+        L.lns_op_fa_reducer.argtypes = [c.POINTER(LnsFaReducerArgs), vp]
+        L.lns_fa_reducer_fits.argtypes = [i, i, i, i]
+        L.lns_op_fa_lrk.argtypes = [c.POINTER(LnsFaLrkArgs), vp]
+        L.lns_fa_lrk_fits.argtypes = [i, i]
+        L.lns_rotary_table.argtypes = [i, vp, i, vp]
+        L.lns_op_ln_pe.argtypes = [vp, c.c_int64, i, i, i, vp, vp, vp, i, c.c_float, vp, fp, vp]
+        L.lns_op_apply.argtypes = [vp, c.c_int64, vp, i, i, i, i, vp, vp, vp]
     if hasattr(L, "lns_op_conv_wgrad"):
         L.lns_op_conv_wgrad_scratch_bytes.argtypes = [i, i, i, i, i, i, i, c.POINTER(c.c_size_t)]
         L.lns_op_conv_wgrad.argtypes = [vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, vp, c.c_size_t, vp]

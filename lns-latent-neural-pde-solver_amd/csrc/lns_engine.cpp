@@ -152,6 +152,44 @@ static int fa_fused_gpb_rule(int requested, int groups, int B, int heads) {
 }
 
 // ---------------------------------------------------------------------------
+// Host pieces of the FABlock axis kernels and of ln_pe, shared by the planner and the op-level entry points
+// (lns_op_fa_reducer, lns_op_fa_lrk, lns_op_ln_pe).
+// ---------------------------------------------------------------------------
+// src [rows][cols] -> dst [cols][rows]: the in-major layout of the reducer matrices (VX_TRANSPOSE2D) and of the positional
+// table (VX_PE_T)
+static void transpose_rows(float* dst, const float* src, size_t rows, size_t cols) {
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t c = 0; c < cols; ++c) dst[c * rows + r] = src[r * cols + c];
+}
+// rotary table for LowRankKernel: pos = torch.linspace(0,1,n) (fp32 arithmetic of
+// torch.linspace), t = pos * (scale/min_freq) = pos*64, freqs = t * inv_freq  (embedding.py:171-176)
+// out: [half][n][2] (cos, sin), frequency-major
+static void rotary_table_fill(int n, const float* inv_freq, int half, float* cs) {
+    const float step = n > 1 ? (1.0f - 0.0f) / (float)(n - 1) : 0.0f;
+    for (int i = 0; i < n; ++i) {
+        // torch.linspace evaluates end - step * k with ONE rounding (a fused multiply-add; torch 2.10's CPU kernel, bit for bit):
+        // the separately rounded product is an ulp off at 6160 of the 80199 positions of n = 2 .. 400, n = 15 and 16 among
+        // them.  n == 1: torch.linspace(0, 1, 1) is [0], the start.
+        float pos = (i < n / 2 || n == 1) ? (0.0f + step * (float)i) : std::fmaf(-step, (float)(n - 1 - i), 1.0f);
+        const float t = pos * 64.0f;
+        for (int d = 0; d < half; ++d) {
+            const float f = t * inv_freq[d];
+            cs[((size_t)d * n + i) * 2] = (float)std::cos((double)f);            // [half][n][2]: a wave reads one frequency's
+            cs[((size_t)d * n + i) * 2 + 1] = (float)std::sin((double)f);        // row, positions on consecutive lanes
+        }
+    }
+}
+// LayerNorm output: |(x - mean) rstd| <= sqrt(C - 1), so |h| <= sqrt(C) max|gamma| + max|beta| + max|pe|
+static float ln_pe_bound(int C, float g_absmax, float b_absmax, float pe_absmax) {
+    return sqrtf((float)C) * g_absmax + b_absmax + pe_absmax;
+}
+static std::string fa_axis_limits(int C, int Hid, int Out) {
+    return fmt("C = %d, Hid = %d, Out = %d: the MFMA form (C and Hid multiples of 32, C <= 256) needs %zu bytes of LDS, the "
+               "scalar form %zu, the limit is %d", C, Hid, Out, fa_reducer_mfma_lds_bytes(C, Hid, Out),
+               fa_reducer_scalar_lds_bytes(C, Hid, Out), (int)FA_AXIS_LDS_LIMIT);
+}
+
+// ---------------------------------------------------------------------------
 // arena allocator for plan temporaries (offsets into the caller's workspace)
 // ---------------------------------------------------------------------------
 struct Arena {
@@ -590,8 +628,7 @@ struct Planner {
         const int n = x.H * x.W, inner = l.heads * l.dim_head;
         if (l.pe >= 0 && n > l.pe_len) throw std::runtime_error("SABlock: more tokens than positional table rows");
         TRef h = alloc_t(x.C, x.H, x.W);
-        // LayerNorm output: |(x - mean) rstd| <= sqrt(C - 1), so |h| <= sqrt(C) max|gamma| + max|beta| + max|pe|
-        h.amax_const = sqrtf((float)x.C) * vec_absmax(l.ln_g) + vec_absmax(l.ln_b) + vec_absmax(l.pe);
+        h.amax_const = ln_pe_bound(x.C, vec_absmax(l.ln_g), vec_absmax(l.ln_b), vec_absmax(l.pe));
         {
             Op op;
             op.type = OP_LNPE; op.name = l.name + ".ln_pe"; op.cls = CLS_LNPE;
@@ -629,22 +666,11 @@ struct Planner {
         return out;
     }
 
-    // rotary table for LowRankKernel: pos = torch.linspace(0,1,n) (fp32 arithmetic of
-    // torch.linspace), t = pos * (scale/min_freq) = pos*64, freqs = t * inv_freq  (embedding.py:171-176)
     uint64_t rotary_table(int n, const std::string& invf_key) {
         const Param& p = e->params[e->pindex.at(invf_key)];
         const int half = (int)p.numel();
         std::vector<float> cs((size_t)n * half * 2);
-        const float step = n > 1 ? (1.0f - 0.0f) / (float)(n - 1) : 0.0f;
-        for (int i = 0; i < n; ++i) {
-            float pos = (i < n / 2) ? (0.0f + step * (float)i) : (1.0f - step * (float)(n - 1 - i));
-            const float t = pos * 64.0f;
-            for (int d = 0; d < half; ++d) {
-                const float f = t * p.host[d];
-                cs[((size_t)d * n + i) * 2] = (float)std::cos((double)f);            // [half][n][2]: a wave reads one frequency's
-                cs[((size_t)d * n + i) * 2 + 1] = (float)std::sin((double)f);        // row, positions on consecutive lanes
-            }
-        }
+        rotary_table_fill(n, p.host.data(), half, cs.data());
         return const_floats(cs);
     }
 
@@ -737,7 +763,13 @@ struct Planner {
         // PoolingReducer of both axes in ONE launch, rotary + q k^T of both axes in one more
         // (LNS_FA_NO_MERGE restores one launch per axis)
         static const bool no_merge = getenv("LNS_FA_NO_MERGE") != nullptr;
-        const bool merge = !no_merge && C % 32 == 0 && C <= 256;
+        const bool merge = !no_merge && fa_reducer_fits(C, 2 * C, lat, true);
+        // no form for this shape: say so here, by name, not at the first launch
+        if (!merge && !fa_reducer_fits(C, 2 * C, lat, false))
+            throw std::runtime_error(l.name + ": no PoolingReducer kernel for " + fa_axis_limits(C, 2 * C, lat));
+        if (!fa_lrk_fits(DK, std::max(H, W)))
+            throw std::runtime_error(l.name + fmt(": no LowRankKernel kernel for DK = %d, n = %d: q' and k' need %zu bytes of LDS, the limit is %d",
+                                                  DK, std::max(H, W), fa_lrk_lds_bytes(DK, std::max(H, W)), (int)FA_AXIS_LDS_LIMIT));
         auto fill_reducer = [&](FaReducerArgs& fr, int ax) {
             const int* r = ax == 0 ? l.rx : l.ry;
             const int n = ax == 0 ? H : W;
@@ -1279,15 +1311,8 @@ static int finalize_weights(lns_engine* e, int device) {
         }
         float* dst = host.data() + v.off;
         if (v.xform == VX_NONE) memcpy(dst, src, v.count * 4);
-        else if (v.xform == VX_TRANSPOSE2D) {   // [out][in] -> [in][out]
-            const size_t rows = (size_t)p.shape[0], cols = v.count / rows;
-            for (size_t r = 0; r < rows; ++r)
-                for (size_t c = 0; c < cols; ++c) dst[c * rows + r] = src[r * cols + c];
-        } else if (v.xform == VX_PE_T) {        // [1][L][C] -> [C][L]
-            const size_t L = (size_t)p.shape[1], C = (size_t)p.shape[2];
-            for (size_t i = 0; i < L; ++i)
-                for (size_t c = 0; c < C; ++c) dst[c * L + i] = src[i * C + c];
-        }
+        else if (v.xform == VX_TRANSPOSE2D) transpose_rows(dst, src, (size_t)p.shape[0], v.count / (size_t)p.shape[0]);   // [out][in] -> [in][out]
+        else if (v.xform == VX_PE_T) transpose_rows(dst, src, (size_t)p.shape[1], (size_t)p.shape[2]);                    // [1][L][C] -> [C][L]
     }
     HIPCHK(e, hipSetDevice(device));
     HIPCHK(e, init_kernels());
@@ -3078,6 +3103,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "eval_attrib")) return 1;
     if (!strcmp(feature, "op_conv_gn")) return 1;
     if (!strcmp(feature, "op_fa_fused")) return 1;
+    if (!strcmp(feature, "op_fa_axis")) return 1;
 #ifdef LNS_DIAG
     if (!strcmp(feature, "diag")) return 1;
 #else
@@ -3739,6 +3765,20 @@ int lns_op_fa_pool(const float* x, int64_t x_bs, const float* ss, int B, int C, 
     return LNS_OK;
 }
 
+// max |.| of a sample as a float: the maximum over the sample's sub-words (amax_load), words [B][LNS_AMAX_SUB] device ->
+// dev_out [B] device
+static hipError_t amax_words_to_float(const unsigned* words, int B, float* dev_out) {
+    std::vector<unsigned> hw((size_t)B * LNS_AMAX_SUB);
+    std::vector<float> hm(B);
+    if (hipError_t err = hipMemcpy(hw.data(), words, hw.size() * 4, hipMemcpyDeviceToHost)) return err;
+    for (int b = 0; b < B; ++b) {
+        unsigned m = 0u;
+        for (int k = 0; k < LNS_AMAX_SUB; ++k) m = std::max(m, hw[(size_t)b * LNS_AMAX_SUB + k]);
+        memcpy(&hm[b], &m, 4);
+    }
+    return hipMemcpy(dev_out, hm.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+}
+
 // FABlock2D with in_proj inside the sandwich (include/lns.h): the input split pre-pass, then the fused kernel, their arguments
 // set as Planner::lower_fa sets them (fa_fused_weight_scale, fa_fused_gpb_rule).  No HIP call before the last check.
 int lns_op_fa_fused(const lns_fa_fused_args* p, void* stream) {
@@ -3789,21 +3829,197 @@ int lns_op_fa_fused(const lns_fa_fused_args* p, void* stream) {
         ok(launch_fa_fused(a, s));
     }
     if (he == hipSuccess) ok(hipStreamSynchronize(s));      // (img, the source of the weight copy, lives until here)
-    if (he == hipSuccess && p->amax_out) {                  // max |G| of a sample: the maximum over its sub-words (amax_load)
-        std::vector<unsigned> hw(amax_words);
-        std::vector<float> hm(B);
-        if (ok(hipMemcpy(hw.data(), damax, amax_words * 4, hipMemcpyDeviceToHost))) {
-            for (int b = 0; b < B; ++b) {
-                unsigned m = 0u;
-                for (int k = 0; k < LNS_AMAX_SUB; ++k) m = std::max(m, hw[(size_t)b * LNS_AMAX_SUB + k]);
-                memcpy(&hm[b], &m, 4);
-            }
-            ok(hipMemcpy(p->amax_out, hm.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-        }
-    }
+    if (he == hipSuccess && p->amax_out) ok(amax_words_to_float(damax, B, p->amax_out));   // max |G| of a sample
     if (he != hipSuccess) (void)hipStreamSynchronize(s);
     (void)hipFree(dgs); (void)hipFree(dwp); (void)hipFree(damax);
     OPCHK(he);
+    return LNS_OK;
+}
+
+// ---- the FABlock axis kernels, ln_pe and apply at op level (include/lns.h, "op_fa_axis") ---------------------------------
+int lns_fa_reducer_fits(int C, int Hid, int Out, int merged) { return fa_reducer_fits(C, Hid, Out, merged != 0) ? 1 : 0; }
+int lns_fa_lrk_fits(int DK, int n) { return fa_lrk_fits(DK, n) ? 1 : 0; }
+int lns_rotary_table(int n, const float* inv_freq_host, int half, float* out_host) {
+    if (n < 1 || half < 1 || !inv_freq_host || !out_host) return LNS_EINVAL;
+    rotary_table_fill(n, inv_freq_host, half, out_host);
+    return LNS_OK;
+}
+
+// Device memory an op-level entry point owns for the length of one call; the first failure sticks and later calls do nothing.
+struct OpScratch {
+    std::vector<void*> ptrs;
+    hipError_t err = hipSuccess;
+    void* alloc(size_t words) {                                    // 4-byte words
+        void* p = nullptr;
+        if (err == hipSuccess) err = hipMalloc(&p, std::max<size_t>(words, 1) * 4);
+        if (err != hipSuccess) return nullptr;
+        ptrs.push_back(p);
+        return p;
+    }
+    float* upload(const std::vector<float>& host) { return upload(host.data(), host.size()); }
+    float* upload(const float* host, size_t count) {
+        float* p = static_cast<float*>(alloc(count));
+        if (p) err = hipMemcpy(p, host, count * 4, hipMemcpyHostToDevice);
+        return p;
+    }
+    unsigned* amax_words(int B, hipStream_t s) {                   // [B][LNS_AMAX_SUB], zeroed in stream order
+        unsigned* p = static_cast<unsigned*>(alloc((size_t)B * LNS_AMAX_SUB));
+        if (p) err = hipMemsetAsync(p, 0, (size_t)B * LNS_AMAX_SUB * 4, s);
+        return p;
+    }
+    void amax_to_float(const unsigned* words, int B, float* dev_out) {
+        if (err == hipSuccess && dev_out) err = amax_words_to_float(words, B, dev_out);
+    }
+    ~OpScratch() { for (void* p : ptrs) (void)hipFree(p); }
+};
+
+static std::vector<float> transposed(const float* src, size_t rows, size_t cols) {
+    std::vector<float> t(rows * cols);
+    transpose_rows(t.data(), src, rows, cols);
+    return t;
+}
+
+int lns_op_fa_reducer(const lns_fa_reducer_args* p, void* stream) {
+    auto bad = [](const std::string& m) { g_create_error = "fa_reducer: " + m; return (int)LNS_EINVAL; };
+    if (!p) return bad("args is null");
+    const bool has_y = p->my != nullptr;
+    if (!p->mx || !p->ux || !p->to_in_x || !p->ln_g_x || !p->ln_b_x || !p->w1_x || !p->w2_x || !p->b2_x)
+        return bad("mx / ux or a weight of the x axis is null");
+    if (has_y && (!p->uy || !p->to_in_y || !p->ln_g_y || !p->ln_b_y || !p->w1_y || !p->w2_y || !p->b2_y))
+        return bad("my is set but uy or a weight of the y axis is null");
+    if (p->form != 0 && p->form != 1) return bad("form 0 (both axes in one launch) or 1 (one launch per axis)");
+    if (p->form == 0 && !has_y) return bad("form 0 (the merged launch) needs both axes");
+    if (p->B < 1 || p->B > LNS_MAX_BATCH) return bad("B in 1..65535");
+    if (p->nx < 1 || p->nx > 65535 || (has_y && (p->ny < 1 || p->ny > 65535))) return bad("nx and ny in 1..65535");
+    if (!fa_reducer_fits(p->C, p->Hid, p->Out, p->form == 0))
+        return bad(std::string(p->form == 0 ? "no merged kernel for " : "no kernel for ") + fa_axis_limits(p->C, p->Hid, p->Out));
+    // ---- every check is done ----
+    const int B = p->B, C = p->C, Hid = p->Hid, Out = p->Out;
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    OpScratch sc;
+    FaReducerArgs fr[2];
+    for (int ax = 0; ax < (has_y ? 2 : 1); ++ax) {               // Planner::lower_fa's fill_reducer on the caller's operands
+        FaReducerArgs& a = fr[ax];
+        memset(&a, 0, sizeof a);
+        const int n = ax == 0 ? p->nx : p->ny;
+        a.m = ax == 0 ? p->mx : p->my; a.rows = (long)B * n; a.n = n; a.C = C; a.Hid = Hid; a.Out = Out;
+        a.win_t = sc.upload(transposed(ax == 0 ? p->to_in_x : p->to_in_y, C, C));
+        a.ln_g = sc.upload(ax == 0 ? p->ln_g_x : p->ln_g_y, C); a.ln_b = sc.upload(ax == 0 ? p->ln_b_x : p->ln_b_y, C);
+        a.w1_t = sc.upload(transposed(ax == 0 ? p->w1_x : p->w1_y, Hid, C));
+        a.w2_t = sc.upload(transposed(ax == 0 ? p->w2_x : p->w2_y, Out, Hid));
+        a.b2 = sc.upload(ax == 0 ? p->b2_x : p->b2_y, Out);
+        a.u = ax == 0 ? p->ux : p->uy;
+        a.amax_out = sc.amax_words(B, s);
+    }
+    hipError_t& he = sc.err;
+    if (he == hipSuccess) {
+        if (p->form == 0) he = launch_fa_reducer2(fr[0], fr[1], s);
+        else {
+            he = launch_fa_reducer(fr[0], s);
+            if (he == hipSuccess && has_y) he = launch_fa_reducer(fr[1], s);
+        }
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    sc.amax_to_float(fr[0].amax_out, B, p->amax_x);
+    if (has_y) sc.amax_to_float(fr[1].amax_out, B, p->amax_y);
+    if (he != hipSuccess) (void)hipStreamSynchronize(s);
+    OPCHK(he);
+    return LNS_OK;
+}
+
+int lns_op_fa_lrk(const lns_fa_lrk_args* p, void* stream) {
+    auto bad = [](const std::string& m) { g_create_error = "fa_lrk: " + m; return (int)LNS_EINVAL; };
+    if (!p) return bad("args is null");
+    const bool has_y = p->qk_y != nullptr;
+    if (!p->qk_x || !p->inv_freq_x || !p->kx) return bad("qk_x / inv_freq_x / kx is null");
+    if (has_y && (!p->inv_freq_y || !p->ky)) return bad("qk_y is set but inv_freq_y / ky is null");
+    if (p->form != 0 && p->form != 1) return bad("form 0 (both axes in one launch) or 1 (one launch per axis)");
+    if (p->form == 0 && !has_y) return bad("form 0 (the merged launch) needs both axes");
+    const int Bs[2] = {p->B_x, p->B_y}, hs[2] = {p->heads_x, p->heads_y}, dks[2] = {p->DK_x, p->DK_y}, ns[2] = {p->nx, p->ny};
+    for (int ax = 0; ax < (has_y ? 2 : 1); ++ax) {
+        if (Bs[ax] < 1 || Bs[ax] > LNS_MAX_BATCH || hs[ax] < 1 || hs[ax] > 65535) return bad("B and heads in 1..65535");
+        if (dks[ax] < 2 || dks[ax] % 2) return bad(fmt("DK = %d: the rotary embedding pairs channel d with d + DK / 2, DK must be even", dks[ax]));
+        if (ns[ax] < 1) return bad("nx and ny must be positive");
+    }
+    if (p->form == 0 && (Bs[0] != Bs[1] || hs[0] != hs[1] || dks[0] != dks[1]))
+        return bad("the merged launch needs the same B, heads and DK on both axes");
+    for (int ax = 0; ax < (has_y ? 2 : 1); ++ax)
+        if (!fa_lrk_fits(dks[ax], ns[ax]))
+            return bad(fmt("no kernel for DK = %d, n = %d: q' and k' need %zu bytes of LDS, the limit is %d", dks[ax], ns[ax],
+                           fa_lrk_lds_bytes(dks[ax], ns[ax]), (int)FA_AXIS_LDS_LIMIT));
+    // ---- every check is done ----
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    OpScratch sc;
+    FaLrkArgs fl[2];
+    for (int ax = 0; ax < (has_y ? 2 : 1); ++ax) {
+        std::vector<float> cs((size_t)ns[ax] * (dks[ax] / 2) * 2);
+        rotary_table_fill(ns[ax], ax == 0 ? p->inv_freq_x : p->inv_freq_y, dks[ax] / 2, cs.data());
+        FaLrkArgs& a = fl[ax];
+        memset(&a, 0, sizeof a);
+        a.qk = ax == 0 ? p->qk_x : p->qk_y; a.B = Bs[ax]; a.heads = hs[ax]; a.DK = dks[ax]; a.n = ns[ax];
+        a.cs = sc.upload(cs); a.kmat = ax == 0 ? p->kx : p->ky;
+    }
+    hipError_t& he = sc.err;
+    if (he == hipSuccess) {
+        if (p->form == 0) he = launch_fa_lrk2(fl[0], fl[1], s);
+        else {
+            he = launch_fa_lrk(fl[0], s);
+            if (he == hipSuccess && has_y) he = launch_fa_lrk(fl[1], s);
+        }
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    else (void)hipStreamSynchronize(s);
+    OPCHK(he);
+    return LNS_OK;
+}
+
+int lns_op_ln_pe(const float* x, int64_t x_bs, int B, int C, int n, const float* gamma_host, const float* beta_host,
+                 const float* pe_host, int pe_len, float eps, float* h, float* bound_out, void* stream) {
+    auto bad = [](const std::string& m) { g_create_error = "ln_pe: " + m; return (int)LNS_EINVAL; };
+    if (!x || !h || !gamma_host || !beta_host) return bad("x / h / gamma / beta is null");
+    if (B < 1 || B > LNS_MAX_BATCH) return bad("B in 1..65535");
+    if (C < 1 || n < 1 || (int64_t)C * n > 0x7fffffffLL) return bad("C, n >= 1 and C * n < 2^31");
+    if (x_bs < (int64_t)C * n) return bad("x_bs is shorter than a sample");
+    if (pe_host && pe_len < n) return bad("more tokens than positional table rows");
+    if (!(eps > 0.0f)) return bad("eps must be positive");
+    // ---- every check is done ----
+    auto absmax = [](const float* v, size_t count) { float m = 0.0f; for (size_t i = 0; v && i < count; ++i) m = std::max(m, fabsf(v[i])); return m; };
+    if (bound_out) *bound_out = ln_pe_bound(C, absmax(gamma_host, C), absmax(beta_host, C), absmax(pe_host, (size_t)pe_len * C));
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    OpScratch sc;
+    LnPeArgs a;
+    memset(&a, 0, sizeof a);                                     // Planner::lower_sa's arguments
+    a.x = x; a.x_bs = (long)x_bs; a.C = C; a.n = n; a.eps = eps;
+    a.gamma = sc.upload(gamma_host, C); a.beta = sc.upload(beta_host, C);
+    a.pe_t = pe_host ? sc.upload(transposed(pe_host, pe_len, C)) : nullptr; a.pe_stride = pe_len;
+    a.h = h; a.B = B;
+    hipError_t& he = sc.err;
+    if (he == hipSuccess) he = launch_ln_pe(a, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    else (void)hipStreamSynchronize(s);
+    OPCHK(he);
+    return LNS_OK;
+}
+
+int lns_op_apply(const float* x, int64_t x_bs, const float* ss, int act, int B, int C, int HW, float* y, unsigned* amax_out,
+                 void* stream) {
+    auto bad = [](const std::string& m) { g_create_error = "apply: " + m; return (int)LNS_EINVAL; };
+    if (!x || !y) return bad("x / y is null");
+    if (act < ACT_NONE || act > ACT_SIGMOID) return bad("act in 0..5 (none, swish, gelu, relu, tanh, sigmoid)");
+    if (B < 1 || B > LNS_MAX_BATCH) return bad("B in 1..65535");
+    if (C < 1 || HW < 1 || (int64_t)C * HW > 0x7fffffffLL) return bad("C, HW >= 1 and C * HW < 2^31");
+    if (x_bs < (int64_t)C * HW) return bad("x_bs is shorter than a sample");
+    // ---- every check is done ----
+    OPCHK(init_kernels());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ApplyArgs a;
+    memset(&a, 0, sizeof a);
+    a.x = x; a.x_bs = (long)x_bs; a.ss = ss; a.act = act; a.y = y; a.B = B; a.C = C; a.HW = HW; a.amax_out = amax_out;
+    OPCHK(launch_apply(a, s));
+    OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
 }
 

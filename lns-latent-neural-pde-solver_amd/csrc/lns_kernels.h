@@ -269,6 +269,17 @@ template <class F> void for_each_ptr(FaLrkArgs& a, F&& f) { f(a.qk); f(a.cs); f(
 LNS_ARGS_SIZE(FaLrkArgs, 40);
 hipError_t launch_fa_lrk(const FaLrkArgs& a, hipStream_t s);
 hipError_t launch_fa_lrk2(const FaLrkArgs& ax, const FaLrkArgs& ay, hipStream_t s);   // both axes in one launch
+// The shapes the axis kernels accept: one predicate per family, asked by the launchers, by Planner::lower_fa and by the
+// op-level entry points (DESIGN.md "axis kernels: supported shapes").  LDS per block, limit FA_AXIS_LDS_LIMIT:
+//   reducer, MFMA form (C % 32 == 0, Hid % 32 == 0, C <= 256): (max(C Hid, 128 Hid, 128 Out) + 33 (2 C + Hid) + 256) * 4
+//   reducer, scalar form (any C, one axis per launch only):    (C C + C Hid + Hid Out + 16 (2 C + Hid)) * 4
+//   low-rank kernel:                                            2 DK * (n rounded up to 32) * 4, DK even
+#define FA_AXIS_LDS_LIMIT (160 * 1024)
+size_t fa_reducer_mfma_lds_bytes(int C, int Hid, int Out);
+size_t fa_reducer_scalar_lds_bytes(int C, int Hid, int Out);
+size_t fa_lrk_lds_bytes(int DK, int n);
+bool fa_reducer_fits(int C, int Hid, int Out, bool merged);   // merged: launch_fa_reducer2, which has the MFMA form only
+bool fa_lrk_fits(int DK, int n);                              // (the merged launch: n = the longer axis)
 
 struct FaSandwichArgs {
     const float* u; const float* kx; const float* ky;

@@ -3133,7 +3133,7 @@ __global__ __launch_bounds__(256) void ln_pe_kernel(LnPeArgs a) {
         float ga[CQ], be[CQ], pe[CQ];
 #pragma unroll
         for (int u = 0; u < CQ; ++u) {
-            const int c = c_lo + u < c_hi ? c_lo + u : c_lo;
+            const int c = c_lo + u < c_hi ? c_lo + u : min(c_lo, a.C - 1);      // (a quarter past the last channel, C = 5: c_lo = 6)
             ga[u] = a.gamma[c]; be[u] = a.beta[c];
             pe[u] = a.pe_t ? a.pe_t[(long)c * a.pe_stride + i] : 0.0f;
         }
@@ -3555,9 +3555,21 @@ __global__ __launch_bounds__(256) void fa_reducer_kernel(FaReducerArgs a) {
 // through one LDS region per GEMM, the last one in chunks of 128 outputs.
 #define FARM_R 32
 #define FARM_RP 33
-static size_t fa_reducer_mfma_lds(const FaReducerArgs& a) {
-    const size_t wt = (size_t)std::max(std::max(a.C * a.Hid, a.Hid * 128), a.Out * 128);
-    return (wt + (size_t)(2 * a.C + a.Hid + (a.qk ? a.Out : 0)) * FARM_RP + 256) * 4;
+static size_t fa_reducer_mfma_lds(int C, int Hid, int Out, bool fused_qk) {
+    const size_t wt = std::max(std::max((size_t)C * Hid, (size_t)Hid * 128), (size_t)Out * 128);
+    return (wt + ((size_t)2 * C + Hid + (fused_qk ? Out : 0)) * FARM_RP + 256) * 4;
+}
+static size_t fa_reducer_mfma_lds(const FaReducerArgs& a) { return fa_reducer_mfma_lds(a.C, a.Hid, a.Out, a.qk != nullptr); }
+size_t fa_reducer_mfma_lds_bytes(int C, int Hid, int Out) { return fa_reducer_mfma_lds(C, Hid, Out, false); }
+size_t fa_reducer_scalar_lds_bytes(int C, int Hid, int Out) {
+    return ((size_t)C * C + (size_t)C * Hid + (size_t)Hid * Out + (size_t)FAR_ROWS * ((size_t)2 * C + Hid)) * 4;
+}
+static bool fa_reducer_mfma_shape(int C, int Hid, int Out) {
+    return C % 32 == 0 && Hid % 32 == 0 && C <= 256 && fa_reducer_mfma_lds_bytes(C, Hid, Out) <= FA_AXIS_LDS_LIMIT;
+}
+bool fa_reducer_fits(int C, int Hid, int Out, bool merged) {
+    if (C < 1 || Hid < 1 || Out < 1 || C > 65536 || Hid > 65536 || Out > 65536) return false;
+    return fa_reducer_mfma_shape(C, Hid, Out) || (!merged && fa_reducer_scalar_lds_bytes(C, Hid, Out) <= FA_AXIS_LDS_LIMIT);
 }
 
 __device__ __forceinline__ void fa_reducer_mfma_body(const FaReducerArgs& a, int block, char* smem) {
@@ -3723,7 +3735,7 @@ __global__ __launch_bounds__(256) void fa_reducer2_mfma_kernel(FaReducerArgs ax,
 }
 
 static bool fa_reducer_mfma_ok(const FaReducerArgs& a) {
-    return a.C % 32 == 0 && a.Hid % 32 == 0 && a.C <= 256 && (!a.qk || a.Out % 2 == 0) && fa_reducer_mfma_lds(a) <= 160 * 1024;
+    return fa_reducer_fits(a.C, a.Hid, a.Out, true) && (!a.qk || a.Out % 2 == 0) && fa_reducer_mfma_lds(a) <= FA_AXIS_LDS_LIMIT;
 }
 
 hipError_t launch_fa_reducer2(const FaReducerArgs& ax, const FaReducerArgs& ay, hipStream_t s) {
@@ -3736,6 +3748,7 @@ hipError_t launch_fa_reducer2(const FaReducerArgs& ax, const FaReducerArgs& ay, 
 
 hipError_t launch_fa_reducer(const FaReducerArgs& a, hipStream_t s) {
     static const bool scalar_only = getenv("LNS_FA_REDUCER_SCALAR") != nullptr;   // A/B knob
+    if (!fa_reducer_fits(a.C, a.Hid, a.Out, false)) return hipErrorInvalidValue;
     if (a.qk && !(fa_reducer_mfma_ok(a) && !scalar_only)) return hipErrorInvalidValue;   // the fused projection needs the MFMA form
     if (!scalar_only && fa_reducer_mfma_ok(a)) {
         const size_t lds = fa_reducer_mfma_lds(a);
@@ -3745,9 +3758,8 @@ hipError_t launch_fa_reducer(const FaReducerArgs& a, hipStream_t s) {
             return hipGetLastError();
         }
     }
-    const size_t lds = ((size_t)a.C * a.C + (size_t)a.C * a.Hid + (size_t)a.Hid * a.Out +
-                        (size_t)FAR_ROWS * (2 * a.C + a.Hid)) * 4;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = fa_reducer_scalar_lds_bytes(a.C, a.Hid, a.Out);
+    if (lds > FA_AXIS_LDS_LIMIT) return hipErrorInvalidValue;      // (reached with the A/B knob only: the predicate covers the rest)
     const unsigned nb = (unsigned)((a.rows + FAR_ROWS - 1) / FAR_ROWS);
     hipLaunchKernelGGL(fa_reducer_kernel, dim3(nb), dim3(256), lds, s, a);
     return hipGetLastError();
@@ -3830,19 +3842,22 @@ __device__ __forceinline__ void fa_lrk_body(const FaLrkArgs& a, char* smem) {
     }
 }
 
+size_t fa_lrk_lds_bytes(int DK, int n) { return (size_t)2 * DK * (((size_t)n + 31) / 32 * 32) * 4; }
+bool fa_lrk_fits(int DK, int n) {
+    return DK >= 2 && DK % 2 == 0 && DK <= 65536 && n >= 1 && n <= 65536 && fa_lrk_lds_bytes(DK, n) <= FA_AXIS_LDS_LIMIT;
+}
+
 hipError_t launch_fa_lrk2(const FaLrkArgs& ax, const FaLrkArgs& ay, hipStream_t s) {
     if (ax.heads != ay.heads || ax.B != ay.B || ax.DK != ay.DK) return hipErrorInvalidValue;
-    const int npx = ((ax.n + 31) / 32) * 32, npy = ((ay.n + 31) / 32) * 32;
-    const size_t lds = (size_t)2 * ax.DK * std::max(npx, npy) * 4;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (!fa_lrk_fits(ax.DK, std::max(ax.n, ay.n))) return hipErrorInvalidValue;
+    const size_t lds = fa_lrk_lds_bytes(ax.DK, std::max(ax.n, ay.n));
     hipLaunchKernelGGL(fa_lrk2_kernel, dim3(ax.heads, ax.B, 2), dim3(256), lds, s, ax, ay);
     return hipGetLastError();
 }
 
 hipError_t launch_fa_lrk(const FaLrkArgs& a, hipStream_t s) {
-    const int npad = ((a.n + 31) / 32) * 32;
-    const size_t lds = (size_t)2 * a.DK * npad * 4;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (!fa_lrk_fits(a.DK, a.n)) return hipErrorInvalidValue;
+    const size_t lds = fa_lrk_lds_bytes(a.DK, a.n);
     hipLaunchKernelGGL(fa_lrk_kernel, dim3(a.heads, a.B), dim3(256), lds, s, a);
     return hipGetLastError();
 }
