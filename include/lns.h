@@ -169,6 +169,13 @@ int lns_finalize_weights(lns_engine* e, int device);
  *                     both column phases and stores pixel pairs) wherever that form fits -- a per-layer rule; 0: the per-phase
  *                     form everywhere, launch for launch the plan without the form.  The results have the same bits either way.
  *                     Any other value: LNS_EINVAL.  Cached plans are rebuilt.
+ * One option selects WHICH RESULT is computed (a third kind: no scheduling option interacts with it, and it changes no
+ * workspace size):
+ *   "spectrum_basis"  basis of the energy spectra of the streaming calls (the _spectrum, _stats and _maps entry points and
+ *                     their _latent_ forms): basis_y | basis_x << 1 with LNS_SPECTRUM_DFT (0) or LNS_SPECTRUM_DCT (1) per
+ *                     axis; default 0 (DFT on both axes, the bits of the library without the option).  It is read when a
+ *                     call is enqueued; spectra_out then holds S = lns_spectrum_bins_basis(Ly, Lx, basis_y, basis_x) bins.
+ *                     Outside 0 .. 3: LNS_EINVAL (host only, nothing is touched).
  * Defaults come from LNS_DECODE_GROUP / LNS_DECODE_STREAMS / LNS_NO_OVERLAP / LNS_PROP_PRIORITY at lns_create().
  * Changing an option changes the workspace size: call lns_prepare() again. */
 int lns_set_option(lns_engine* e, const char* name, long value);
@@ -490,16 +497,48 @@ int lns_rollout_latent_ensemble_exceed(lns_engine* e, const float* z_in, const f
  * the scheduling options, so the streaming calls and lns_op_energy_spectrum (one device function) produce the same bits.
  * A NaN pixel makes every bin of its own plane's spectra that read it NaN and touches no other plane.
  * Bins are index wavenumbers (no physical lengths; on a non-square plane ky and kx count cycles per side).  On the
- * non-periodic families the DFT sees the jump across the walls: those spectra carry its leakage (a k^-2 tail).
+ * non-periodic families the DFT sees the jump across the walls: those spectra carry its leakage (a k^-2 tail).  Give an
+ * axis with walls the basis LNS_SPECTRUM_DCT (below): the DCT-II is the DFT of the plane's mirror extension, which has no
+ * jump (measured in float64 on a 96 x 192 ramp in y: 6.8e-3 of the energy at 20 cycles and above under the DFT, 4.0e-7 with
+ * a DCT along y).
  *
  * Supported planes: 1 <= H, W <= 192 and H * W <= 18432 (96 x 192); lns_spectrum_bins is host-only and returns S, or
- * LNS_EINVAL for an unsupported plane. */
+ * LNS_EINVAL for an unsupported plane.
+ *
+ * A basis per axis.  LNS_SPECTRUM_DFT is everything above (both axes DFT: nothing changes, bit for bit).  An axis of
+ * length N with the basis LNS_SPECTRUM_DCT is transformed by a DCT-II:
+ *     coefficient index m = 0 .. N-1;  table t_N[r] = cospif((float)r / (float)(2N)) in fp32, read at r = (m (2n + 1)) mod 4N
+ *     weight 1 for m = 0, else 2 (no Nyquist exception);  no imaginary part
+ * A DFT axis is as above: x keeps kx = 0 .. W/2 with its conjugate weights, y keeps every ky with signed wavenumbers.
+ *     row pass     over x ascending, one chain per part: Rre always, Rim only if x is DFT
+ *     column pass  over y ascending.  y DCT: re = chain t_H . Rre, im = chain t_H . Rim if Rim exists.
+ *                  y DFT: the two-segment chains above, without the Rim terms when Rim does not exist
+ *                  (re = chain c_H . Rre, im = chain m_H . Rre)
+ *     power        a = re * inv, b = im * inv;  p = (wy * wx) * (a*a + b*b), or (wy * wx) * (a*a) where there is no im
+ *                  (fp32, nothing fused; the weights are 1, 2 or 4 and do not round;  wy = 1 on a DFT y axis)
+ *     shells       unless both axes are DFT, wavenumbers count HALF cycles per side: a DCT index m counts m, a DFT
+ *                  wavenumber k counts 2k; r2 is the sum of the two squares, shell(r2) the integer rule above, so bin s
+ *                  lies at s / 2 cycles per side.  S = shell(qy_max^2 + qx_max^2) + 1 with q_max = N - 1 for a DCT axis
+ *                  and 2 (N / 2) for a DFT axis.  S for (dft,dft) / (dct-y,dft-x) / (dft-y,dct-x) / (dct,dct):
+ *                  24x48: 28 / 54 / 54 / 53;  61x121: 68 / 135 / 135 / 135;  96x192: 108 / 215 / 215 / 214;
+ *                  128x128: 92 / 181 / 181 / 181.  The largest S of a supported plane is 215 (one thread per bin).
+ *     shell sums   as above: 32-column tiles (a DCT x axis has W columns instead of W/2 + 1), runs of equal shell along a
+ *                  row in ascending column (with y DCT and x DFT the shell can rise by two per column: a skipped shell
+ *                  has no run in that row), then ascending row in storage order.
+ * Parseval holds for every basis: sum_s E[s] = mean(u^2).  Unchanged: the supported planes, the three fields per plane, the
+ * error differenced per pixel before the transform, NaN containment, one block per plane, no atomics.
+ * lns_spectrum_bins_basis is host-only and returns S, or LNS_EINVAL for an unsupported plane or a basis other than 0 / 1. */
+#define LNS_SPECTRUM_DFT 0
+#define LNS_SPECTRUM_DCT 1
 int lns_spectrum_bins(int H, int W);
+int lns_spectrum_bins_basis(int H, int W, int basis_y, int basis_x);
 
 /* lns_rollout_eval / lns_rollout_latent_eval (same arguments, same frame_out / seq_out / frames_out bits, same workspace:
  * lns_rollout_eval_workspace_bytes(B) and nothing more) followed by the spectrum selection: spectrum_steps_host, n_spec >= 1
  * ascending 0-based steps of this call's T (HOST array, read during the call; independent of keep_steps_host), and
  * spectra_out [B][n_spec][Cin][3][S], S = lns_spectrum_bins(Ly, Lx), which every block writes with final values.
+ * (With the option "spectrum_basis" set: S = lns_spectrum_bins_basis(Ly, Lx, basis_y, basis_x); the same holds for the
+ * spectra of the _stats and _maps entry points.  The entry points are not forked: the basis travels as that option.)
  * Refusals: those of lns_rollout_eval, then (host only, ahead of the batch check) LNS_EINVAL for spectra_out null,
  * n_spec < 1, spectrum_steps_host null / out of range / not ascending, and an unsupported plane.  Trace / timing modes
  * (single stream) and lns_check_finite: as lns_rollout_eval. */
@@ -923,7 +962,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * are there; "rollout_select" = lns_rollout_select & co. are there; "rollout_ensemble" = lns_rollout_latent_ensemble,
  * its size query and lns_op_ensemble_stats are there; "ensemble_score" = lns_rollout_latent_ensemble_eval and
  * lns_op_ensemble_score are there; "eval_spectrum" = lns_rollout_eval_spectrum, lns_rollout_latent_eval_spectrum,
- * lns_op_energy_spectrum and lns_spectrum_bins are there; "eval_stats" = lns_rollout_eval_stats,
+ * lns_op_energy_spectrum and lns_spectrum_bins are there; "spectrum_basis" = lns_spectrum_bins_basis,
+ * lns_op_energy_spectrum_basis and the option "spectrum_basis" are there; "eval_stats" = lns_rollout_eval_stats,
  * lns_rollout_latent_eval_stats and lns_op_field_stats are there; "eval_maps" = lns_rollout_eval_maps,
  * lns_rollout_latent_eval_maps, their size query, lns_op_time_maps and lns_time_maps_state_bytes are there;
  * "op_conv_gn" = lns_op_conv_gn is there; "op_fa_fused" = lns_op_fa_fused is there; "eval_attrib" = lns_rollout_eval_attrib, lns_rollout_latent_eval_attrib, their
@@ -1142,6 +1182,10 @@ int lns_op_ensemble_exceed(const float* frames, const float* y, int n, int B, in
  * the per-channel form needs C <= 8.  Checks precede the launch (message: lns_create_error()); the call synchronises `stream`. */
 int lns_op_energy_spectrum(const float* yhat, const float* y /* nullable */, int B, int T, int C, int H, int W,
                            const lns_eval_spec* spec, float* out, void* stream);
+/* The same with a basis per axis (LNS_SPECTRUM_DFT / LNS_SPECTRUM_DCT; anything else: LNS_EINVAL ahead of the launch):
+ * S = lns_spectrum_bins_basis(H, W, basis_y, basis_x).  (.., 0, 0) is lns_op_energy_spectrum, bit for bit. */
+int lns_op_energy_spectrum_basis(const float* yhat, const float* y /* nullable */, int B, int T, int C, int H, int W,
+                                 const lns_eval_spec* spec, float* out, void* stream, int basis_y, int basis_x);
 
 /* The statistics kernel of lns_rollout_eval_stats on stored fields, without an engine: yhat and y [B][T][C][H][W],
  * normalised -> stats_out [B][T][C][12] and, with hspec and hist_out, hist_out [B][T][C][2][nbins + 2].  The per-plane body

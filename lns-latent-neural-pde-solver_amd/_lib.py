@@ -18,6 +18,7 @@ LNS_ABI_VERSION = 2
 LNS_AE_NONE, LNS_AE_SQUARE, LNS_AE_NONSQUARED, LNS_AE_HALF_PERIODIC = 0, 1, 2, 3
 LNS_PROP_NONE, LNS_PROP_PLAIN, LNS_PROP_CONDITIONAL = 0, 1, 2
 LNS_PAD_ZEROS, LNS_PAD_CIRCULAR = 0, 1
+LNS_SPECTRUM_DFT, LNS_SPECTRUM_DCT = 0, 1
 # status codes (include/lns.h)
 LNS_OK, LNS_EINVAL, LNS_ENOKEY, LNS_ESTATE, LNS_ENOMEM, LNS_EHIP, LNS_ENONFINITE = 0, -1, -2, -3, -4, -5, -6
 
@@ -186,6 +187,7 @@ SYMBOLS = [
     "lns_rollout_latent_ensemble_quantiles", "lns_op_ensemble_quantiles",
     "lns_rollout_latent_ensemble_exceed", "lns_op_ensemble_exceed",
     "lns_spectrum_bins", "lns_rollout_eval_spectrum", "lns_rollout_latent_eval_spectrum", "lns_op_energy_spectrum",
+    "lns_spectrum_bins_basis", "lns_op_energy_spectrum_basis",
     "lns_rollout_eval_stats", "lns_rollout_latent_eval_stats", "lns_op_field_stats",
     "lns_rollout_eval_maps_workspace_bytes", "lns_rollout_eval_maps", "lns_rollout_latent_eval_maps",
     "lns_time_maps_state_bytes", "lns_op_time_maps",
@@ -294,6 +296,9 @@ def lib():
         L.lns_rollout_latent_eval_spectrum.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, vp, c.c_size_t, vp,
                                                        ip, i, vp]
         L.lns_op_energy_spectrum.argtypes = [vp, vp, i, i, i, i, i, sp, vp, vp]
+    if hasattr(L, "lns_op_energy_spectrum_basis"):
+        L.lns_spectrum_bins_basis.argtypes = [i, i, i, i]
+        L.lns_op_energy_spectrum_basis.argtypes = [vp, vp, i, i, i, i, i, c.POINTER(LnsEvalSpec), vp, vp, i, i]
     if hasattr(L, "lns_rollout_eval_stats"):
         sp, ip, hp = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.POINTER(LnsStatsSpec)
         L.lns_rollout_eval_stats.argtypes = [vp, vp, vp, vp, i, i, sp, vp, vp, ip, i, vp, vp, c.c_size_t, vp, ip, i, vp,

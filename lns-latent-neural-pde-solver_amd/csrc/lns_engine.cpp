@@ -1976,6 +1976,11 @@ int lns_set_option(lns_engine* e, const char* name, long value) {
         if (value != 0 && value != 1) { e->err = "train_wgrad: 0 (one block per output tile) or 1 (batch-parallel)"; return LNS_EINVAL; }
         e->opt_train_wgrad = (int)value;
     }
+    else if (n == "spectrum_basis") {
+        if (value < 0 || value > 3) { e->err = "spectrum_basis: basis_y | basis_x << 1 with LNS_SPECTRUM_DFT (0) or LNS_SPECTRUM_DCT (1), i.e. 0 .. 3"; return LNS_EINVAL; }
+        e->opt_spectrum_basis = (int)value;
+        return LNS_OK;                               // it schedules nothing: the records of the last run stay
+    }
     else if (n == "fa_fused") { if (value < 0 || value > 3) return LNS_EINVAL; set_rule(e->opt_fa_fused); }
     else if (n == "fa_fused_gpb") { if (value < 0 || value > 64) return LNS_EINVAL; set_rule(e->opt_fa_fused_gpb); }
     else if (n == "fold_linear") {
@@ -2175,7 +2180,9 @@ static void metric_args(const lns_engine* e, const RolloutCall& c, const WsLayou
 static void spectrum_args(const lns_engine* e, const RolloutCall& c, SpectrumArgs* sp) {
     SpectrumArgs& s = *sp;
     s.frames = nullptr; s.y = c.y_true; s.out = c.sel.spectra_out;
-    s.B = c.B; s.C = e->cfg.in_channels; s.H = e->cfg.Ly; s.W = e->cfg.Lx; s.S = lns_spectrum::bins(s.H, s.W); s.K = 3;
+    s.B = c.B; s.C = e->cfg.in_channels; s.H = e->cfg.Ly; s.W = e->cfg.Lx; s.K = 3;
+    s.basis = e->opt_spectrum_basis;                 // read here, as the call is enqueued
+    s.S = lns_spectrum::bins(s.H, s.W, s.basis & 1, s.basis >> 1);
     s.n = 0; s.y_T = c.T_total; s.y_t = 0; s.o_T = c.sel.n_spec; s.o_t = 0;
     score_norm(c.spec, s.C, &s.norm);
     memset(s.sel, 0, sizeof s.sel);
@@ -3099,6 +3106,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "ensemble_quantiles")) return 1;
     if (!strcmp(feature, "ensemble_exceed")) return 1;
     if (!strcmp(feature, "eval_spectrum")) return 1;
+    if (!strcmp(feature, "spectrum_basis")) return 1;
     if (!strcmp(feature, "eval_stats")) return 1;
     if (!strcmp(feature, "eval_maps")) return 1;
     if (!strcmp(feature, "eval_attrib")) return 1;

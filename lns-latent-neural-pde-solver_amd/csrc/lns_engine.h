@@ -198,6 +198,7 @@ struct lns_engine {
     // "track_nonfinite" option: a device word per plan kind that remembers a non-finite amax record of ANY plan run of
     // the last call (one extra 1-block launch per plan run; off by default)
     int opt_track_nonfinite = 0;
+    int opt_spectrum_basis = 0;    // basis of the streaming calls' energy spectra: basis_y | basis_x << 1 (which result, not how it is scheduled)
     int opt_train_wgrad = 0;       // weight gradient of the training step: 0 one block per output tile, 1 batch-parallel (wgrad_split.inc)
     unsigned* d_sticky = nullptr;
     bool sticky_armed = false;

@@ -469,14 +469,15 @@ struct EnsembleExceedArgs {
 hipError_t launch_ensemble_exceed(const EnsembleExceedArgs& a, hipStream_t s);
 
 // Energy spectra (lns_rollout_eval_spectrum, lns_op_energy_spectrum; the statement: include/lns.h): one block per plane
-// writes its K x S shell energies, K = 3 (forecast, truth, error) with y, K = 1 (forecast) without; S = lns_spectrum::bins(H, W).
+// writes its K x S shell energies, K = 3 (forecast, truth, error) with y, K = 1 (forecast) without; S = lns_spectrum::bins(H, W, basis_y, basis_x).
 // Group form: frames [kk][B][C][H*W] (a decode stream's frame buffer); the n <= 8 selected steps sel[0 .. n) of the group
 // against the truth planes y[b][y_t + sel[i]][c] of y [B][y_T][C][H*W] into out[b][o_t + i][c] of out [B][o_T][C][K][S].
 // Stored form: frames and y are [B][n][C][H*W], out [B][n][C][K][S] (sel, y_T, y_t, o_T, o_t unused).
-// Dynamic LDS: lns_spectrum::lds_bytes(H, W), at most 154368 bytes (192 x 96).  The denormalisation: as MetricGroupArgs.
+// Dynamic LDS: lns_spectrum::lds_bytes(H, W, basis_y, basis_x), at most 155904 bytes (192 x 96, DCT y with DFT x).  The denormalisation: as MetricGroupArgs.
 struct SpectrumArgs {
     const float* frames; const float* y; float* out;
     int B, C, H, W, S, K, n, y_T, y_t, o_T, o_t;
+    int basis;                      // basis_y | basis_x << 1 (lns_spectrum::DFT / DCT); S = lns_spectrum::bins(H, W, basis_y, basis_x)
     ScoreNorm norm;
     unsigned char sel[8];
 };

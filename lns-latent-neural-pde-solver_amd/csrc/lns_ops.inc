@@ -439,24 +439,38 @@ int lns_spectrum_bins(int H, int W) {
     return S < 0 ? LNS_EINVAL : S;
 }
 
-// spectrum_stored_kernel on stored fields: the per-plane body of the streaming call (spectrum_plane)
-int lns_op_energy_spectrum(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
-                           float* out, void* stream) {
+static_assert(LNS_SPECTRUM_DFT == lns_spectrum::DFT && LNS_SPECTRUM_DCT == lns_spectrum::DCT, "the header's and the kernels' basis codes differ");
+
+int lns_spectrum_bins_basis(int H, int W, int basis_y, int basis_x) {
+    const int S = lns_spectrum::bins(H, W, basis_y, basis_x);
+    return S < 0 ? LNS_EINVAL : S;
+}
+
+// spectrum_stored_kernel on stored fields: the per-plane body of the streaming call (spectrum_plane / spectrum_plane_basis)
+int lns_op_energy_spectrum_basis(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
+                                 float* out, void* stream, int basis_y, int basis_x) {
     if (!yhat || !out) return op_refuse("energy_spectrum", "yhat / out is null");
     if (op_spec_refused("energy_spectrum", spec)) return LNS_EINVAL;
     if (B < 1 || T < 1 || C < 1 || (int64_t)B * T * C > 0x7fffffffLL) return op_refuse("energy_spectrum", "B, T, C >= 1 and B * T * C < 2^31");
     if (!lns_spectrum::supported(H, W)) return op_refuse("energy_spectrum", "the plane needs 1 <= H, W <= 192 and H * W <= 18432");
+    if (!lns_spectrum::basis_ok(basis_y, basis_x)) return op_refuse("energy_spectrum", "basis_y, basis_x: LNS_SPECTRUM_DFT (0) or LNS_SPECTRUM_DCT (1)");
     if (op_spec_refused("energy_spectrum", spec, C)) return LNS_EINVAL;
     OPCHK(init_kernels());
     hipStream_t s = static_cast<hipStream_t>(stream);
     SpectrumArgs a;
     memset(&a, 0, sizeof a);
     a.frames = yhat; a.y = y; a.out = out;
-    a.B = B; a.C = C; a.H = H; a.W = W; a.S = lns_spectrum::bins(H, W); a.K = y ? 3 : 1; a.n = T;
+    a.B = B; a.C = C; a.H = H; a.W = W; a.S = lns_spectrum::bins(H, W, basis_y, basis_x); a.K = y ? 3 : 1; a.n = T;
+    a.basis = basis_y | basis_x << 1;
     score_norm(spec, C, &a.norm);
     OPCHK(launch_spectrum_stored(a, s));
     OPCHK(hipStreamSynchronize(s));
     return LNS_OK;
+}
+
+int lns_op_energy_spectrum(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
+                           float* out, void* stream) {
+    return lns_op_energy_spectrum_basis(yhat, y, B, T, C, H, W, spec, out, stream, LNS_SPECTRUM_DFT, LNS_SPECTRUM_DFT);
 }
 
 static_assert(LNS_FIELD_STATS_N == LNS_FIELD_STATS, "the kernels' and the header's number of statistics differ");

@@ -596,12 +596,14 @@ class LatentDynamics(_Hosted):
         return self._engine(x).rollout_eval(x, y, param=param, keep_steps=keep_steps, **norm)
 
     @torch.no_grad()
-    def validate_spectrum(self, x, y, *rest, spectrum_steps=None, keep_steps=(), **norm):
+    def validate_spectrum(self, x, y, *rest, spectrum_steps=None, keep_steps=(), spectrum_basis="dft", **norm):
         """validate_spectrum(x, y, **norm) -- conditional: validate_spectrum(x, y, param, **norm): `validate` with the
         shell-summed energy spectra of forecast, truth and error of the steps `spectrum_steps` (a sequence, range or slice;
         None: every step), taken as the steps are decoded.  Returns engine.EvalSpectra: frame, seq, frames as `validate`
         returns them, spectra [B,n,C,3,S] (S = metrics.spectrum_bins(Ly, Lx); rows forecast, truth, error) and the steps.
-        Bins are index wavenumbers; on the non-periodic families a spectrum carries the leakage of the walls."""
+        Bins are index wavenumbers; under spectrum_basis="dft" a spectrum of a non-periodic family carries the leakage of the
+        walls: spectrum_basis="auto" (or "dct" / a pair (y, x)) takes a DCT-II on the axes with walls, S =
+        metrics.spectrum_bins(Ly, Lx, basis) bins at metrics.spectrum_wavenumbers."""
         param = None
         if self._conditional:
             if not rest:
@@ -611,10 +613,12 @@ class LatentDynamics(_Hosted):
             raise TypeError("validate_spectrum() takes (x, y, param, **norm)" if self._conditional
                             else "validate_spectrum() takes (x, y, **norm)")
         x = self._fields(x)
-        return self._engine(x).rollout_eval_spectrum(x, y, param=param, keep_steps=keep_steps, spectrum_steps=spectrum_steps, **norm)
+        return self._engine(x).rollout_eval_spectrum(x, y, param=param, keep_steps=keep_steps, spectrum_steps=spectrum_steps,
+                                                     basis=spectrum_basis, **norm)
 
     @torch.no_grad()
-    def validate_stats(self, x, y, *rest, stats_steps=None, hist=None, spectrum_steps=(), keep_steps=(), **norm):
+    def validate_stats(self, x, y, *rest, stats_steps=None, hist=None, spectrum_steps=(), keep_steps=(), spectrum_basis="dft",
+                       **norm):
         """validate_stats(x, y, **norm) -- conditional: validate_stats(x, y, param, **norm): `validate` with the per-plane
         field statistics (metrics.FIELD_STATS: means, variances, correlation, gradient-domain error, extrema) of the steps
         `stats_steps` (a sequence, range or slice; None: every step) and, with hist = (nbins, lo, hi), the value histograms
@@ -630,10 +634,11 @@ class LatentDynamics(_Hosted):
                             else "validate_stats() takes (x, y, **norm)")
         x = self._fields(x)
         return self._engine(x).rollout_eval_stats(x, y, param=param, keep_steps=keep_steps, stats_steps=stats_steps, hist=hist,
-                                                  spectrum_steps=spectrum_steps, **norm)
+                                                  spectrum_steps=spectrum_steps, spectrum_basis=spectrum_basis, **norm)
 
     @torch.no_grad()
-    def validate_maps(self, x, y, *rest, map_steps=None, stats_steps=(), hist=None, spectrum_steps=(), keep_steps=(), **norm):
+    def validate_maps(self, x, y, *rest, map_steps=None, stats_steps=(), hist=None, spectrum_steps=(), keep_steps=(),
+                      spectrum_basis="dft", **norm):
         """validate_maps(x, y, **norm) -- conditional: validate_maps(x, y, param, **norm): `validate` with the per-pixel time
         maps (metrics.TIME_MAPS: time-mean of forecast and truth, temporal variances and covariance, mean squared and largest
         error) over the steps `map_steps` (None: every step; slice(from, None, every) or (from, every) for burn-in and
@@ -652,7 +657,8 @@ class LatentDynamics(_Hosted):
                             else "validate_maps() takes (x, y, **norm)")
         x = self._fields(x)
         return self._engine(x).rollout_eval_maps(x, y, param=param, keep_steps=keep_steps, map_steps=map_steps,
-                                                 stats_steps=stats_steps, hist=hist, spectrum_steps=spectrum_steps, **norm)
+                                                 stats_steps=stats_steps, hist=hist, spectrum_steps=spectrum_steps,
+                                                 spectrum_basis=spectrum_basis, **norm)
 
 
     @torch.no_grad()

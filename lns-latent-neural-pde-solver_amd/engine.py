@@ -5,6 +5,7 @@ engine's parameter table (= the reference state_dict keys/shapes) and runs the
 hot path on CUDA/HIP tensors.  torch is used for device memory and streams only.
 """
 import collections
+import contextlib
 import ctypes
 import functools
 import numbers
@@ -420,7 +421,9 @@ class Engine:
         "fold_linear" (default 1; 0 = off) runs a convolution directly followed by a 1x1 convolution as one convolution on
         weights composed at load_weights: the same order of difference.
         "up2_dual" (default 1; 0 = the per-phase form everywhere) picks the kernel form of the upsampling 3x3 convolutions:
-        the same bits either way."""
+        the same bits either way.
+        "spectrum_basis" (default 0; basis_y | basis_x << 1, 0 = dft, 1 = dct) selects which energy spectrum the streaming
+        calls compute; their basis= / spectrum_basis= keywords set it for one call and put it back."""
         self._check(self._L.lns_set_option(self._h, name.encode(), int(value)), "lns_set_option")
         self.options[name] = int(value)
         self._ws.clear()                      # the workspace size depends on the options
@@ -987,44 +990,73 @@ class Engine:
                                  frame=frame, seq=seq)
 
     # -- streaming validation with energy spectra (include/lns.h "energy spectra") ----------------------------------
-    def spectrum_bins(self, H=None, W=None):
-        """Number of shells S of an H x W plane (default: the model's Ly x Lx); host only."""
+    def spectrum_bins(self, H=None, W=None, basis="dft"):
+        """Number of shells S of an H x W plane (default: the model's Ly x Lx) under `basis` ("dft", "dct", a pair (y, x) or
+        "auto": see metrics.spectrum_basis); host only."""
         H, W = (self.cfg.Ly if H is None else int(H)), (self.cfg.Lx if W is None else int(W))
         from . import metrics
-        return metrics.spectrum_bins(H, W)
+        return metrics.spectrum_bins(H, W, self._basis_names(basis))
 
-    def _spectrum_select(self, spectrum_steps, T, B, device, optional=False):
+    def _basis_names(self, basis):
+        """`basis` with "auto" resolved against this model, as a pair of names; host only, a bad name raises LnsError."""
+        from . import metrics
+        by, bx = metrics.spectrum_basis(basis, self.cfg)
+        return metrics.SPECTRUM_BASES[by], metrics.SPECTRUM_BASES[bx]
+
+    @contextlib.contextmanager
+    def _spectrum_basis(self, basis):
+        """The option "spectrum_basis" (include/lns.h: which spectrum the streaming calls compute) set for one call and put
+        back afterwards.  It sizes no workspace, so the cached workspaces stay."""
+        from . import metrics
+        by, bx = metrics.spectrum_basis(basis, self.cfg)
+        code, old = by | bx << 1, self.options.get("spectrum_basis", 0)
+        if code != old:
+            self._check(self._L.lns_set_option(self._h, b"spectrum_basis", code), "lns_set_option")
+            self.options["spectrum_basis"] = code
+        try:
+            yield (metrics.SPECTRUM_BASES[by], metrics.SPECTRUM_BASES[bx])
+        finally:
+            if code != old:
+                self._check(self._L.lns_set_option(self._h, b"spectrum_basis", old), "lns_set_option")
+                self.options["spectrum_basis"] = old
+
+    def _spectrum_select(self, spectrum_steps, T, B, device, optional=False, basis="dft"):
         """A `select` of _scored_call: the spectra of `spectrum_steps`; optional: an empty sequence asks for none."""
         import torch
         if optional and spectrum_steps is not None and not isinstance(spectrum_steps, slice) and len(spectrum_steps) == 0:
             return (None, 0, None), (None, []), None
         sel = normalize_keep_steps(range(T) if spectrum_steps is None else spectrum_steps, T)
         arr = (ctypes.c_int * len(sel))(*sel)
-        spectra = torch.empty((B, len(sel), self.cfg.in_channels, 3, self.spectrum_bins()), dtype=torch.float32, device=device)
+        spectra = torch.empty((B, len(sel), self.cfg.in_channels, 3, self.spectrum_bins(basis=basis)), dtype=torch.float32, device=device)
         return (arr, len(sel), spectra.data_ptr()), (spectra, sel), None
 
-    def energy_spectrum(self, y_hat, y=None, **norm):
+    def energy_spectrum(self, y_hat, y=None, basis="dft", **norm):
         """Shell-summed energy spectra of stored fields (lns_op_energy_spectrum): y_hat and y (optional) [B, T, C, H, W],
         normalised; `norm` as in `rollout_eval` (eps is not used).  Returns [B, T, C, 3, S] (forecast, truth, error = forecast -
-        truth differenced before the transform) or, without y, [B, T, C, 1, S]: the kernel body of rollout_eval_spectrum."""
+        truth differenced before the transform) or, without y, [B, T, C, 1, S]: the kernel body of rollout_eval_spectrum.
+        `basis`: "dft", "dct", a pair (y, x), or "auto" ("dct" on the axes this model's autoencoder does not pad circularly)."""
         from . import metrics
-        return metrics.energy_spectrum(y_hat, y, **norm)
+        return metrics.energy_spectrum(y_hat, y, basis=self._basis_names(basis), **norm)
 
-    def rollout_eval_spectrum(self, x, y, steps=None, param=None, keep_steps=(), spectrum_steps=None, **norm):
+    def rollout_eval_spectrum(self, x, y, steps=None, param=None, keep_steps=(), spectrum_steps=None, basis="dft", **norm):
         """rollout_eval with the energy spectra of forecast, truth and error of the steps `spectrum_steps` (what
         `normalize_keep_steps` takes; None: every step), taken where the step is decoded.  Returns EvalSpectra: frame, seq
         and frames hold rollout_eval's bits, spectra [B, n, C, 3, S] those of
-        `energy_spectrum(rollout(x, T)[:, spectrum_steps], y[:, spectrum_steps], ...)`.  Bins are index wavenumbers; on the
-        non-periodic families a spectrum carries the leakage of the walls.  The workspace is rollout_eval's."""
-        return self._scored_call("lns_rollout_eval_spectrum", EvalSpectra, x, y, steps, None, param, keep_steps, norm,
-                                 functools.partial(self._spectrum_select, spectrum_steps))
+        `energy_spectrum(rollout(x, T)[:, spectrum_steps], y[:, spectrum_steps], ...)`.  Bins are index wavenumbers; under
+        basis="dft" a spectrum of a non-periodic family carries the leakage of the walls: pass basis="auto" (or "dct" / a pair
+        (y, x)) for a DCT-II on the axes with walls, S = spectrum_bins(basis=basis) bins at metrics.spectrum_wavenumbers.
+        The workspace is rollout_eval's."""
+        with self._spectrum_basis(basis) as names:
+            return self._scored_call("lns_rollout_eval_spectrum", EvalSpectra, x, y, steps, None, param, keep_steps, norm,
+                                     functools.partial(self._spectrum_select, spectrum_steps, basis=names))
 
     def rollout_latent_eval_spectrum(self, z, y, steps=None, t0=0, param=None, keep_steps=(), spectrum_steps=None, frame=None,
-                                     seq=None, **norm):
+                                     seq=None, basis="dft", **norm):
         """rollout_latent_eval with energy spectra: keep_steps and spectrum_steps are relative to the chunk, spectra
         [B, n, C, 3, S] belong to this chunk's steps.  Returns EvalSpectraChunk (see rollout_latent_eval for frame / seq)."""
-        return self._scored_call("lns_rollout_latent_eval_spectrum", EvalSpectraChunk, z, y, steps, t0, param, keep_steps, norm,
-                                 functools.partial(self._spectrum_select, spectrum_steps), frame, seq)
+        with self._spectrum_basis(basis) as names:
+            return self._scored_call("lns_rollout_latent_eval_spectrum", EvalSpectraChunk, z, y, steps, t0, param, keep_steps, norm,
+                                     functools.partial(self._spectrum_select, spectrum_steps, basis=names), frame, seq)
 
     # -- streaming validation with field statistics (include/lns.h "field statistics") ----------------------------
     def field_stats(self, y_hat, y, hist=None, **norm):
@@ -1048,15 +1080,15 @@ class Engine:
             counts = torch.empty((B, len(sel), C, 2, hs.nbins + 2), dtype=torch.int32, device=device)
         return sel, arr, stats, hs, counts
 
-    def _stats_select(self, stats_steps, hist, spectrum_steps, T, B, device):
+    def _stats_select(self, stats_steps, hist, spectrum_steps, T, B, device, basis="dft"):
         """A `select` of _scored_call: the statistics of `stats_steps`, their histograms and (optional) spectra."""
         sel, arr, stats, hs, counts = self._stats_alloc(stats_steps, hist, T, B, device)
-        sargs, stail, _ = self._spectrum_select(spectrum_steps, T, B, device, optional=True)
+        sargs, stail, _ = self._spectrum_select(spectrum_steps, T, B, device, optional=True, basis=basis)
         hp = ctypes.byref(hs) if hs is not None else None
         return sargs + (arr, len(sel), hp, stats.data_ptr(), self._ptr(counts)), (stats, counts, sel) + stail, None
 
     def rollout_eval_stats(self, x, y, steps=None, param=None, keep_steps=(), stats_steps=None, hist=None, spectrum_steps=(),
-                           **norm):
+                           spectrum_basis="dft", **norm):
         """rollout_eval with, for the steps `stats_steps` (what `normalize_keep_steps` takes; None: every step), the twelve
         per-plane statistics metrics.FIELD_STATS of the decoded frame against the truth -- means, variances, centred
         correlation, the reference's pointwise_correlation, the gradient-domain relative L2 in y and x, and the extrema -- and,
@@ -1064,15 +1096,17 @@ class Engine:
         `spectrum_steps` (default: none; None: every step) adds rollout_eval_spectrum's spectra in the same pass.  Returns
         EvalStats: frame, seq, frames and spectra hold the bits of the existing calls, stats / hist those of
         `field_stats(rollout(x, T)[:, stats_steps], y[:, stats_steps], hist, ...)`.  The workspace is rollout_eval's."""
-        return self._scored_call("lns_rollout_eval_stats", EvalStats, x, y, steps, None, param, keep_steps, norm,
-                                 functools.partial(self._stats_select, stats_steps, hist, spectrum_steps))
+        with self._spectrum_basis(spectrum_basis) as names:
+            return self._scored_call("lns_rollout_eval_stats", EvalStats, x, y, steps, None, param, keep_steps, norm,
+                                     functools.partial(self._stats_select, stats_steps, hist, spectrum_steps, basis=names))
 
     def rollout_latent_eval_stats(self, z, y, steps=None, t0=0, param=None, keep_steps=(), stats_steps=None, hist=None,
-                                  spectrum_steps=(), frame=None, seq=None, **norm):
+                                  spectrum_steps=(), frame=None, seq=None, spectrum_basis="dft", **norm):
         """rollout_latent_eval with field statistics: keep_steps, stats_steps and spectrum_steps are relative to the chunk,
         stats / hist / spectra belong to this chunk's steps.  Returns EvalStatsChunk (see rollout_latent_eval for frame / seq)."""
-        return self._scored_call("lns_rollout_latent_eval_stats", EvalStatsChunk, z, y, steps, t0, param, keep_steps, norm,
-                                 functools.partial(self._stats_select, stats_steps, hist, spectrum_steps), frame, seq)
+        with self._spectrum_basis(spectrum_basis) as names:
+            return self._scored_call("lns_rollout_latent_eval_stats", EvalStatsChunk, z, y, steps, t0, param, keep_steps, norm,
+                                     functools.partial(self._stats_select, stats_steps, hist, spectrum_steps, basis=names), frame, seq)
 
     # -- streaming validation with time maps (include/lns.h "time maps") -------------------------------------------
     def time_maps(self, y_hat, y, map_steps=None, **norm):
@@ -1081,7 +1115,7 @@ class Engine:
         from . import metrics
         return metrics.time_maps(y_hat, y, map_steps=map_steps, **norm)
 
-    def _maps_select(self, map_steps, stats_steps, hist, spectrum_steps, T, B, device):
+    def _maps_select(self, map_steps, stats_steps, hist, spectrum_steps, T, B, device, basis="dft"):
         """A `select` of _scored_call: the lns_eval_select of the time maps over `map_steps` = (from, every) with the
         (optional) statistics and spectra; the maps tensor itself is _scored_call's."""
         q = _lib.LnsEvalSelect()
@@ -1097,13 +1131,13 @@ class Engine:
             if hs is not None:
                 q.hspec, q.hist_out = ctypes.pointer(hs), counts.data_ptr()
             tail = (stats, counts, sel)
-        (sarr, n_spec, spectra), stail, _ = self._spectrum_select(spectrum_steps, T, B, device, optional=True)
+        (sarr, n_spec, spectra), stail, _ = self._spectrum_select(spectrum_steps, T, B, device, optional=True, basis=basis)
         if n_spec:
             q.n_spec, q.spectrum_steps_host, q.spectra_out = n_spec, sarr, spectra
         return (ctypes.byref(q),), tail + stail, q
 
     def rollout_eval_maps(self, x, y, steps=None, param=None, keep_steps=(), map_steps=None, stats_steps=(), hist=None,
-                          spectrum_steps=(), **norm):
+                          spectrum_steps=(), spectrum_basis="dft", **norm):
         """rollout_eval with the seven per-pixel time maps metrics.TIME_MAPS -- time-mean of forecast and truth, their unbiased
         temporal variances and covariance, the mean squared error and the largest absolute error -- over the steps `map_steps`
         (None: every step; slice(from, None, every) or (from, every): burn-in and thinning), accumulated as the steps are decoded:
@@ -1112,19 +1146,21 @@ class Engine:
         maps holds the bits of the existing calls, maps those of `time_maps(rollout(x, T), y, map_steps, ...)`.  The workspace is
         rollout_eval's plus 52 bytes per (trajectory, channel, pixel)."""
         ms = normalize_map_steps(map_steps)
-        return self._scored_call("lns_rollout_eval_maps", EvalMaps, x, y, steps, None, param, keep_steps, norm,
-                                 functools.partial(self._maps_select, ms, stats_steps, hist, spectrum_steps))
+        with self._spectrum_basis(spectrum_basis) as names:
+            return self._scored_call("lns_rollout_eval_maps", EvalMaps, x, y, steps, None, param, keep_steps, norm,
+                                     functools.partial(self._maps_select, ms, stats_steps, hist, spectrum_steps, basis=names))
 
     def rollout_latent_eval_maps(self, z, y, steps=None, t0=0, param=None, keep_steps=(), map_steps=None, stats_steps=(),
-                                 hist=None, spectrum_steps=(), frame=None, seq=None, maps=None, **norm):
+                                 hist=None, spectrum_steps=(), frame=None, seq=None, maps=None, spectrum_basis="dft", **norm):
         """rollout_latent_eval with time maps: `map_steps` names steps of the horizon (the same in every chunk); keep_steps,
         stats_steps and spectrum_steps are relative to the chunk.  The chunks of one horizon must follow each other on the same
         engine and batch, with nothing else run on it in between: the maps' state stays in the engine's workspace, and the chunk
         that completes the horizon writes `maps` (pass the tensor along like frame / seq, or take it from the last chunk's
         result; it is untouched until then).  Returns EvalMapsChunk."""
         ms = normalize_map_steps(map_steps)
-        return self._scored_call("lns_rollout_latent_eval_maps", EvalMapsChunk, z, y, steps, t0, param, keep_steps, norm,
-                                 functools.partial(self._maps_select, ms, stats_steps, hist, spectrum_steps), frame, seq, maps)
+        with self._spectrum_basis(spectrum_basis) as names:
+            return self._scored_call("lns_rollout_latent_eval_maps", EvalMapsChunk, z, y, steps, t0, param, keep_steps, norm,
+                                     functools.partial(self._maps_select, ms, stats_steps, hist, spectrum_steps, basis=names), frame, seq, maps)
 
     # -- streaming validation with error attribution (include/lns.h "error attribution") ---------------------------
     def eval_attrib(self, y_hat, r, y, **norm):

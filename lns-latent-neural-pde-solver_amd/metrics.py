@@ -78,29 +78,70 @@ def _launch_metric(L, per_channel, y_hat, y, B, T, C, H, W, mean, std, eps, zero
     return rc
 
 
-def spectrum_bins(H, W):
+SPECTRUM_BASES = ("dft", "dct")
+
+
+def spectrum_basis(basis, cfg=None):
+    """(basis_y, basis_x) as LNS_SPECTRUM_DFT / LNS_SPECTRUM_DCT (0 / 1) from "dft", "dct", a pair (y, x) of the two names, or
+    "auto": per axis "dft" where the model's autoencoder pads that axis circularly (cfg.ae_pad_y / ae_pad_x of an engine's
+    configuration), else "dct" -- dft / dft for ns2d*, dct / dft for sw_half_periodic, dct / dct for the two-phase presets.
+    Host only; anything else raises LnsError."""
+    def one(b):
+        if not isinstance(b, str) or b not in SPECTRUM_BASES:
+            raise _lib.LnsError('spectrum basis: "dft", "dct", a pair (y, x) of them or "auto", got %r' % (basis,))
+        return SPECTRUM_BASES.index(b)
+    if isinstance(basis, str):
+        if basis == "auto":
+            if cfg is None:
+                raise _lib.LnsError('spectrum basis "auto" needs a model (Engine.energy_spectrum / the rollout calls): '
+                                    'name the basis of stored fields')
+            return tuple(0 if pad == _lib.LNS_PAD_CIRCULAR else 1 for pad in (cfg.ae_pad_y, cfg.ae_pad_x))
+        return one(basis), one(basis)
+    try:
+        by, bx = basis
+    except (TypeError, ValueError):
+        raise _lib.LnsError('spectrum basis: "dft", "dct", a pair (y, x) of them or "auto", got %r' % (basis,))
+    return one(by), one(bx)
+
+
+def spectrum_bins(H, W, basis="dft"):
     """Number of shells S of the energy spectrum of an H x W plane (include/lns.h "energy spectra"): the shell of the
-    corner mode (H/2, W/2) plus one.  Host only; an unsupported plane (H, W <= 192 and H * W <= 18432) raises."""
-    S = _lib.lib().lns_spectrum_bins(int(H), int(W))
+    corner mode plus one -- (H/2, W/2) for dft / dft, else in half cycles per side (`spectrum_wavenumbers`).  Host only; an
+    unsupported plane (H, W <= 192 and H * W <= 18432) raises."""
+    by, bx = spectrum_basis(basis)
+    L = _lib.lib()
+    S = L.lns_spectrum_bins(int(H), int(W)) if (by, bx) == (0, 0) else L.lns_spectrum_bins_basis(int(H), int(W), by, bx)
     if S < 0:
         raise _lib.LnsError("energy spectrum: a %d x %d plane is not supported (H, W <= 192 and H * W <= 18432)" % (H, W))
     return int(S)
 
 
-def energy_spectrum(y_hat, y=None, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
+def spectrum_wavenumbers(H, W, basis="dft"):
+    """Bin centres of `energy_spectrum` in cycles per side, a float64 tensor [S]: s for dft / dft, s / 2 once an axis is
+    "dct" (its wavenumbers count half cycles)."""
+    by, bx = spectrum_basis(basis)
+    k = torch.arange(spectrum_bins(H, W, basis), dtype=torch.float64)
+    return k if (by, bx) == (0, 0) else k / 2
+
+
+def energy_spectrum(y_hat, y=None, mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8),
+                    basis="dft"):
     """Shell-summed energy spectra of stored fields (lns_op_energy_spectrum): y_hat and y (optional) [B,T,C,H,W],
     normalised, denormalised as in `relative_l2` (eps is not used).  Returns [B,T,C,3,S] -- forecast, truth and error
-    (forecast - truth, differenced before the transform) -- or, without y, [B,T,C,1,S]; S = spectrum_bins(H, W), bin s
-    holds the energy of the modes whose index wavenumber rounds to s, and the bins of a row sum to mean(u^2).  On the
-    non-periodic families a spectrum carries the leakage of the walls.  The kernel body of Engine.rollout_eval_spectrum."""
+    (forecast - truth, differenced before the transform) -- or, without y, [B,T,C,1,S]; S = spectrum_bins(H, W, basis), bin s
+    holds the energy of the modes whose index wavenumber rounds to s, and the bins of a row sum to mean(u^2).  `basis`:
+    "dft" (default), "dct" or a pair (y, x).  Under "dft" an axis with walls puts the jump across them into the spectrum (a
+    k^-2 tail); give such an axis "dct" (DCT-II, the DFT of the mirror extension: no jump), and read the bins with
+    `spectrum_wavenumbers`.  The kernel body of Engine.rollout_eval_spectrum."""
     from .engine import eval_spec
+    by, bx = spectrum_basis(basis)
     for t in (y_hat, y):
         if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 5):
             raise _lib.LnsError("energy_spectrum takes fp32 HIP tensors [B,T,C,H,W] (no CPU fallback)")
     if y is not None and (y.shape != y_hat.shape or y.device != y_hat.device):
         raise _lib.LnsError("y must have y_hat's shape %s and device, got %s" % (tuple(y_hat.shape), tuple(y.shape)))
     B, T, C, H, W = (int(v) for v in y_hat.shape)
-    S = spectrum_bins(H, W)
+    S = spectrum_bins(H, W, SPECTRUM_BASES[by] if by == bx else (SPECTRUM_BASES[by], SPECTRUM_BASES[bx]))
     y_hat = y_hat.contiguous()
     y = y.contiguous() if y is not None else None
     spec = eval_spec(C, mean=mean, std=std, eps=eps, zero_wall_channels=zero_wall_channels, clamp_channels=clamp_channels,
@@ -109,8 +150,8 @@ def energy_spectrum(y_hat, y=None, mean=0.0, std=1.0, eps=1e-8, zero_wall_channe
     L = _lib.lib()
     with torch.cuda.device(y_hat.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(y_hat.device).cuda_stream)
-        rc = L.lns_op_energy_spectrum(y_hat.data_ptr(), y.data_ptr() if y is not None else None, B, T, C, H, W,
-                                      ctypes.byref(spec), out.data_ptr(), stream)
+        args = (y_hat.data_ptr(), y.data_ptr() if y is not None else None, B, T, C, H, W, ctypes.byref(spec), out.data_ptr(), stream)
+        rc = L.lns_op_energy_spectrum(*args) if (by, bx) == (0, 0) else L.lns_op_energy_spectrum_basis(*args, by, bx)
     if rc != 0:
         raise _lib.LnsError("lns_op_energy_spectrum failed (%d): %s" % (rc, L.lns_create_error().decode()))
     return out
