@@ -774,6 +774,95 @@ int lns_autoencode_eval_workspace_bytes(lns_engine* e, int B, size_t* bytes);
 int lns_autoencode_eval(lns_engine* e, const float* x, const float* param, int B, int T, const lns_eval_spec* spec,
                         float* frame_out, float* seq_out, float* z_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- streaming validation: flow diagnostics (vorticity, divergence, kinetic energy, enstrophy) -----------------------
+ * Everything above looks at one channel plane at a time.  Every model family here forecasts a 2-D flow with a velocity pair,
+ * and what a flow surrogate is asked first -- does it stay divergence-free like the truth, does it keep the kinetic energy and
+ * the enstrophy, how wrong is the vorticity -- needs two channels and their neighbours at once.  These calls take it where
+ * the step is decoded, so the [B,T,Cin,Ly,Lx] rollout is never stored: a flow kernel follows the statistics launch of a
+ * decoded group on its decode stream (one launch per group for the group's selected steps; none selected: no launch; one
+ * block of 256 threads per (b, step)), and a pointwise kernel writes the vorticity of the group's kept steps.
+ * (No reference counterpart: the reference has no differential diagnostics.)
+ *
+ * The statement, for a frame (b, step) of H x W pixels.  P = forecast and Q = truth, each denormalised per pixel by D_c, the
+ * map of lns_eval_spec as written above for lns_rollout_latent_ensemble_eval (product and sum rounded one by one, wall-zero
+ * and clamp flags included).  U = D_cu(.) and V = D_cv(.) are the two channels lns_flow_spec names; x is the column index, y
+ * the row index, both increasing; U is the x-component.  Everything is fp32, nothing is fused.
+ * Host constants per axis with spacing d:  rc = (float)(1.0 / (2.0 * (double)d)),  re = (float)(1.0 / (double)d).
+ * The derivative of a field f along an axis of length n at index i: the difference rounded first, then the product --
+ *     n == 1:                 0.0f
+ *     periodic:               (f[(i+1) % n] - f[(i-1+n) % n]) * rc
+ *     wall, 0 < i < n-1:      (f[i+1] - f[i-1]) * rc
+ *     wall, i == 0:           (f[1] - f[0]) * re
+ *     wall, i == n-1:         (f[n-1] - f[n-2]) * re
+ * i.e. numpy.gradient(..., edge_order=1) on a wall axis and a wrapped central difference on a periodic one.  A neighbour is
+ * D_c of the value at the neighbour's position: a wall-zero channel is zero on the border for the stencil too.
+ * Per pixel, one rounded operation per written operator:
+ *     w = dxV - dyU   (vorticity)        dv = dxU + dyV   (divergence)        k = U*U + V*V
+ * Every plane sum is taken in the order of the metric kernels over the row-major pixel index: thread t of 256 adds its terms
+ * t, t + 256, ... in ascending order, starting from 0; then the wave sum; then (w0 + w1) + (w2 + w3) over the four waves.
+ *     KP = sum k_P         KQ = sum k_Q         WP = sum w_P*w_P     WQ = sum w_Q*w_Q     DP = sum dv_P*dv_P    DQ = sum dv_Q*dv_Q
+ *     WE = sum (w_P-w_Q)^2                      WX = sum w_P*w_Q     VE = sum (a*a + b*b),  a = U_P-U_Q,  b = V_P-V_Q
+ * The maxima of fabsf(w_P), fabsf(w_Q) and fabsf(dv_P) are taken with fmaxf, starting from 0 (a NaN pixel is skipped by them
+ * and poisons the sums).  Thread 0 finishes in fp32, every op rounded, N = (float)(H*W), eps = spec.eps, and stores
+ * LNS_FLOW_STATS = 12 floats per (b, step), in this order:
+ *     ke_P = (0.5f*KP)/N        ke_Q = (0.5f*KQ)/N        ens_P = (0.5f*WP)/N       ens_Q = (0.5f*WQ)/N
+ *     div_P = sqrtf(DP/N)       div_Q = sqrtf(DQ/N)
+ *     vort_err = sqrtf(WE / (WQ < eps ? eps : WQ))
+ *     vort_cos = WX / ((sqrtf(WP)+eps) * (sqrtf(WQ)+eps))
+ *     vel_err  = sqrtf(VE / (KQ < eps ? eps : KQ))
+ *     maxvort_P, maxvort_Q, maxdiv_P
+ * The vorticity histogram (the PDF of w) is optional: nbins (0: none, else 1 .. 256) and one edge pair lo < hi in units of w;
+ * the bin rule is the one written for the field statistics (scale = (float)nbins / (hi - lo); a NaN is counted nowhere).
+ * hist_out is int32 [B][n_flow][2][nbins + 2], row 0 of the forecast, row 1 of the truth; counted with integer LDS atomics,
+ * stored with ordinary stores.  vort_frames_out [B][n_keep][Ly][Lx] holds w_P of the keep_steps frames (pointwise; the
+ * truth's vorticity comes from lns_op_vorticity on y).
+ * One block owns one (b, step) and writes its 12 floats and its counts itself: no float atomics, no finish kernel, no
+ * workspace beyond lns_rollout_eval_workspace_bytes(B).  The neighbours are re-read from global memory, so planes of any
+ * size work (H * W <= 2^30), axes of length 1 and 2 included.  The result therefore has the same bits for every
+ * decode_group / decode_streams / overlap setting, for any chunking of the horizon, and as lns_op_flow_stats /
+ * lns_op_vorticity compute it on the stored rollout (one device function). */
+#define LNS_FLOW_STATS 12
+#define LNS_FLOW_PERIODIC 0
+#define LNS_FLOW_WALL 1
+typedef struct lns_flow_spec {
+    uint32_t size;          /* sizeof(lns_flow_spec) */
+    int32_t cu, cv;         /* the channels of the x- and of the y-component */
+    int32_t bc_y, bc_x;     /* LNS_FLOW_PERIODIC / LNS_FLOW_WALL per axis */
+    float dy, dx;           /* grid spacings, in the units the derivatives are wanted in */
+    int32_t nbins;          /* 0: no vorticity histogram, else 1 .. 256 */
+    float lo, hi;           /* its edges, in units of the vorticity */
+} lns_flow_spec;
+typedef struct lns_eval_flow {
+    uint32_t size;                    /* sizeof(lns_eval_flow) */
+    int32_t n_flow;                   /* >= 1 */
+    const int* flow_steps_host;       /* n_flow ascending 0-based steps of this call's T (HOST array, read during the call) */
+    const lns_flow_spec* fspec;
+    float* flow_out;                  /* [B][n_flow][12] */
+    int32_t* hist_out;                /* nullable: [B][n_flow][2][nbins + 2] */
+    float* vort_frames_out;           /* nullable: [B][n_keep][Ly][Lx]; needs n_keep > 0 */
+} lns_eval_flow;
+
+/* lns_rollout_eval / lns_rollout_latent_eval (same leading arguments) followed by `sel` (nullable: the spectra and the
+ * statistics of lns_eval_select, honoured with the bits of their own calls) and `flow`.  frame_out / seq_out / frames_out
+ * keep the bits of the existing calls; the workspace is lns_rollout_eval_workspace_bytes(B) and nothing more, which is why
+ * a `sel` that asks for time maps (maps_out set, or map_from / map_every not 0) is LNS_EINVAL in this form.
+ * Refusals (host only, ahead of the first HIP call), where the time-map form has its own: those of lns_rollout_eval's
+ * arguments, of the spectrum selection when n_spec != 0 and of the statistics selection when n_stats != 0; then LNS_EINVAL for
+ * a sel of the wrong size (the two selections then count as absent) or one that asks for maps; then for flow null or of the
+ * wrong size, flow_out null, n_flow < 1, flow_steps_host null / out of range / not ascending, fspec null or of the wrong size,
+ * cu == cv or either outside [0, in_channels), a boundary code other than 0 / 1, dx / dy not finite or <= 0, nbins outside
+ * 0 .. 256, a non-finite edge or hi <= lo when nbins > 0, hist_out with nbins == 0, vort_frames_out with n_keep == 0; then
+ * lns_rollout_eval's batch, eval_max_steps, model and param refusals. */
+int lns_rollout_eval_flow(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                          const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host,
+                          int n_keep, float* frames_out, void* workspace, size_t workspace_bytes, void* stream,
+                          const lns_eval_select* sel /* nullable */, const lns_eval_flow* flow);
+int lns_rollout_latent_eval_flow(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                 int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                 const int* keep_steps_host, int n_keep, float* frames_out, float* z_last,
+                                 void* workspace, size_t workspace_bytes, void* stream,
+                                 const lns_eval_select* sel /* nullable */, const lns_eval_flow* flow);
+
 /* Post-run health check.  Every kernel of a plan records, per sample, the running maximum of |y| of the tensor it
  * produces (the side channel from which the split-operand convolutions derive their activation scale); a NaN or inf
  * anywhere in a tensor survives in it.  This call synchronises `stream`, reads those few KB back from `workspace`
@@ -970,7 +1059,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * size query, lns_autoencode_eval, its size query, lns_op_eval_attrib and lns_op_latent_err are there;
  * "ensemble_quantiles" = lns_rollout_latent_ensemble_quantiles and lns_op_ensemble_quantiles are there;
  * "ensemble_exceed" = lns_rollout_latent_ensemble_exceed and lns_op_ensemble_exceed are there; "op_fa_axis" =
- * lns_op_fa_reducer, lns_op_fa_lrk, lns_op_ln_pe, lns_op_apply, lns_rotary_table and the two fit predicates are there.
+ * lns_op_fa_reducer, lns_op_fa_lrk, lns_op_ln_pe, lns_op_apply, lns_rotary_table and the two fit predicates are there;
+ * "eval_flow" = lns_rollout_eval_flow, lns_rollout_latent_eval_flow, lns_op_flow_stats and lns_op_vorticity are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
@@ -1194,6 +1284,17 @@ int lns_op_energy_spectrum_basis(const float* yhat, const float* y /* nullable *
 int lns_op_field_stats(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
                        const lns_stats_spec* hspec /* nullable */, float* stats_out, int32_t* hist_out /* nullable */,
                        void* stream);
+
+/* The flow kernels of lns_rollout_eval_flow on stored fields, without an engine.  lns_op_flow_stats: yhat and y
+ * [B][T][C][H][W], normalised -> flow_out [B][T][12] and, with fspec->nbins > 0 and hist_out, hist_out [B][T][2][nbins + 2].
+ * lns_op_vorticity: fields [B][T][C][H][W], normalised -> vort_out [B][T][H][W], the vorticity of every frame (of a forecast
+ * or of the truth).  The per-frame bodies are the streaming call's (one device function).  C >= 2, H * W <= 2^30,
+ * B * T < 2^24; the per-channel form needs C <= 8.  Checks precede the launch (message: lns_create_error()): the pointers,
+ * spec, the shape, then fspec in the order written for lns_rollout_eval_flow; the calls synchronise `stream`. */
+int lns_op_flow_stats(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
+                      const lns_flow_spec* fspec, float* flow_out, int32_t* hist_out /* nullable */, void* stream);
+int lns_op_vorticity(const float* fields, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
+                     const lns_flow_spec* fspec, float* vort_out, void* stream);
 
 /* The time maps of lns_rollout_eval_maps on stored fields, without an engine: yhat and y [B][T][C][H][W], normalised ->
  * maps_out [B][C][7][H][W] over the steps map_from, map_from + map_every, ... below T (the horizon is T, K is y[b][0]).

@@ -116,6 +116,27 @@ class LnsEvalAttrib(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32)] + [(n, ctypes.c_void_p) for n in OUTPUTS]
 
 
+LNS_FLOW_STATS = 12
+
+
+class LnsFlowSpec(ctypes.Structure):
+    """Mirror of `struct lns_flow_spec` (include/lns.h): the velocity channels, boundaries, spacings and vorticity histogram of
+    the flow diagnostics."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("cu", _I32), ("cv", _I32), ("bc_y", _I32), ("bc_x", _I32),
+        ("dy", ctypes.c_float), ("dx", ctypes.c_float), ("nbins", _I32), ("lo", ctypes.c_float), ("hi", ctypes.c_float),
+    ]
+
+
+class LnsEvalFlow(ctypes.Structure):
+    """Mirror of `struct lns_eval_flow` (include/lns.h): the selection and the outputs of lns_rollout_eval_flow."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("n_flow", _I32),
+        ("flow_steps_host", ctypes.POINTER(ctypes.c_int)), ("fspec", ctypes.POINTER(LnsFlowSpec)),
+        ("flow_out", ctypes.c_void_p), ("hist_out", ctypes.c_void_p), ("vort_frames_out", ctypes.c_void_p),
+    ]
+
+
 LNS_SL1_CHUNK = 4096
 
 
@@ -193,6 +214,7 @@ SYMBOLS = [
     "lns_time_maps_state_bytes", "lns_op_time_maps",
     "lns_rollout_eval_attrib_workspace_bytes", "lns_rollout_eval_attrib", "lns_rollout_latent_eval_attrib",
     "lns_autoencode_eval_workspace_bytes", "lns_autoencode_eval", "lns_op_eval_attrib", "lns_op_latent_err",
+    "lns_rollout_eval_flow", "lns_rollout_latent_eval_flow", "lns_op_flow_stats", "lns_op_vorticity",
     "lns_train_workspace_bytes", "lns_train_forward", "lns_train_backward",
     "lns_loss_smooth_l1", "lns_adam_step", "lns_adam_step_tensors", "lns_train_step_workspace_bytes", "lns_train_step",
     "lns_grad_norm_scratch_bytes", "lns_grad_norm_tensors", "lns_grad_scale_tensors", "lns_update_step_tensors",
@@ -322,6 +344,13 @@ def lib():
         L.lns_autoencode_eval.argtypes = [vp, vp, vp, i, i, sp, vp, vp, vp, vp, c.c_size_t, vp]
         L.lns_op_eval_attrib.argtypes = [vp, vp, vp, i, i, i, i, i, sp, vp, vp, vp, vp, vp]
         L.lns_op_latent_err.argtypes = [vp, vp, i, i, i, c.c_int64, c.c_float, vp, vp, vp]
+    if hasattr(L, "lns_rollout_eval_flow"):
+        sp, ip, qp = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.POINTER(LnsEvalSelect)
+        fp_, wp = c.POINTER(LnsFlowSpec), c.POINTER(LnsEvalFlow)
+        L.lns_rollout_eval_flow.argtypes = [vp, vp, vp, vp, i, i, sp, vp, vp, ip, i, vp, vp, c.c_size_t, vp, qp, wp]
+        L.lns_rollout_latent_eval_flow.argtypes = [vp, vp, vp, vp, i, i, i, i, sp, vp, vp, ip, i, vp, vp, vp, c.c_size_t, vp, qp, wp]
+        L.lns_op_flow_stats.argtypes = [vp, vp, i, i, i, i, i, sp, fp_, vp, vp, vp]
+        L.lns_op_vorticity.argtypes = [vp, i, i, i, i, i, sp, fp_, vp, vp]
     if hasattr(L, "lns_check_finite"):      # (absent from older builds loaded through LNS_HIP_LIB for A/B runs)
         L.lns_check_finite.argtypes = [vp, i, vp, c.c_size_t, vp]
     if hasattr(L, "lns_set_option"):

@@ -1830,6 +1830,11 @@ struct RolloutCall {
     // SINK_SCORED: the attribution outputs (the _attrib forms; include/lns.h lns_eval_attrib); at_bad: null or of the wrong size
     lns_eval_attrib at = {};
     bool attrib = false, at_bad = false;
+    // SINK_SCORED: the flow diagnostics (the _flow forms; include/lns.h lns_eval_flow) beside the spectra / statistics of `sel`;
+    // flow_bad: null or of the wrong size; sel_bad here: a non-null lns_eval_select of the wrong size
+    lns_eval_flow fl = {};
+    bool flow = false, flow_bad = false;
+    StepList flow_list() const { return {fl.flow_steps_host, fl.n_flow, "flow_steps"}; }
     // lns_autoencode_eval: no chain -- x [B][T] is encoded, decoded and scored against itself; only the autoencoder is needed
     bool ae_only = false;
     StepList keep_list() const { return {keep, n_keep, "keep_steps"}; }
@@ -2222,6 +2227,54 @@ static void field_stats_args(const lns_engine* e, const RolloutCall& c, FieldSta
     stats_hist_args(c.sel.hspec, c.sel.hist_out, f.C, &f);   // (accepted by rollout_refusal)
 }
 
+// The refusals of an lns_flow_spec for C channels and of a histogram destination, in the order of include/lns.h.  Returns
+// the refusal's text, or null when the description is usable.  Host only.
+static const char* flow_spec_refusal(const lns_flow_spec* fs, int C, const int32_t* hist_out) {
+    if (!fs || fs->size != sizeof(lns_flow_spec)) return "fspec is null or its size field is not sizeof(lns_flow_spec)";
+    if (fs->cu == fs->cv || fs->cu < 0 || fs->cu >= C || fs->cv < 0 || fs->cv >= C)
+        return "fspec: cu and cv must be two different channels of the fields";
+    if ((fs->bc_y != LNS_FLOW_PERIODIC && fs->bc_y != LNS_FLOW_WALL) || (fs->bc_x != LNS_FLOW_PERIODIC && fs->bc_x != LNS_FLOW_WALL))
+        return "fspec: bc_y and bc_x must be LNS_FLOW_PERIODIC (0) or LNS_FLOW_WALL (1)";
+    if (!std::isfinite(fs->dx) || !std::isfinite(fs->dy) || !(fs->dx > 0.0f) || !(fs->dy > 0.0f))
+        return "fspec: dx and dy must be finite and positive";
+    if (fs->nbins < 0 || fs->nbins > 256) return "fspec: nbins must be in 0 .. 256";
+    if (fs->nbins > 0 && (!std::isfinite(fs->lo) || !std::isfinite(fs->hi) || !(fs->hi > fs->lo)))
+        return "fspec: the edges must be finite with hi > lo";
+    if (hist_out && fs->nbins == 0) return "hist_out needs fspec->nbins > 0";
+    return nullptr;
+}
+
+// the refusals of the flow part of a scored call, in the order of include/lns.h
+static const char* flow_refusal(const RolloutCall& c, int C, std::string* err) {
+    if (c.flow_bad) return "flow is null or its size field is not sizeof(lns_eval_flow)";
+    if (!c.fl.flow_out) return "flow_out is null";
+    if (c.fl.n_flow < 1) return "n_flow must be at least 1";
+    if (!c.fl.flow_steps_host) return "flow_steps is null";
+    if (c.flow_list().check(c.T, err)) return err->c_str();
+    if (const char* why = flow_spec_refusal(c.fl.fspec, C, c.fl.hist_out)) return why;
+    if (c.fl.vort_frames_out && c.n_keep == 0) return "vort_frames_out needs n_keep > 0";
+    return nullptr;
+}
+
+// The flow kernels' arguments from an accepted lns_flow_spec (flow_spec_refusal) and the denormalisation, for [C][H][W] frames;
+// the pointers, n and the step bookkeeping are the caller's
+static void flow_args(const lns_flow_spec* fs, const lns_eval_spec* spec, int B, int C, int H, int W, FlowStatsArgs* fp) {
+    FlowStatsArgs& f = *fp;
+    memset(&f, 0, sizeof f);
+    f.B = B; f.C = C; f.H = H; f.W = W;
+    f.cu = fs->cu; f.cv = fs->cv; f.bc_y = fs->bc_y; f.bc_x = fs->bc_x;
+    f.rcy = (float)(1.0 / (2.0 * (double)fs->dy)); f.rey = (float)(1.0 / (double)fs->dy);
+    f.rcx = (float)(1.0 / (2.0 * (double)fs->dx)); f.rex = (float)(1.0 / (double)fs->dx);
+    f.eps = spec->eps;
+    f.nbins = fs->nbins; f.hlo = 0.0f; f.hhi = 1.0f; f.hscale = 1.0f;
+    if (fs->nbins > 0) {
+        f.hlo = fs->lo; f.hhi = fs->hi;
+        const float width = fs->hi - fs->lo;
+        f.hscale = (float)fs->nbins / width;
+    }
+    score_norm(spec, C, &f.norm);
+}
+
 // the accumulation kernel's arguments for a SINK_SCORED call with time maps; frames / n / sel / y_t are set per decoded group
 static void time_maps_args(const lns_engine* e, const RolloutCall& c, const WsLayout& L, TimeMapsArgs* tp) {
     TimeMapsArgs& t = *tp;
@@ -2376,6 +2429,13 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     if (scored && c.spectra) spectrum_args(e, c, &sx);
     FieldStatsArgs fs;
     if (scored && c.stats) field_stats_args(e, c, &fs);
+    FlowStatsArgs fw, fv;                            // the flow statistics of the selected steps, the vorticity of the kept ones
+    if (scored && c.flow) {
+        flow_args(c.fl.fspec, c.spec, B, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, &fw);
+        fv = fw;
+        fw.y = c.y_true; fw.stats = c.fl.flow_out; fw.hist = c.fl.hist_out; fw.y_T = c.T_total; fw.o_T = c.fl.n_flow;
+        fv.vort = c.fl.vort_frames_out; fv.o_T = c.n_keep;
+    }
     TimeMapsArgs tm;
     if (scored && c.maps) time_maps_args(e, c, L, &tm);
     int maps_d = -1;                                 // the decode stream of the latest time-map accumulation of this call
@@ -2422,6 +2482,7 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     };
     int g = 0, gi = 0, t = 0;                        // t: next step of the chain
     StepList frames_kept = c.keep_list(), spec_steps = c.spectrum_list(), stats_steps = c.stats_list();   // SINK_SCORED: walked group by group
+    StepList flow_steps = c.flow_list();
     for (int i0 = 0; i0 < n_dec;) {                  // i0: index in `out` of the group's first step
         const int kk = std::min(kdec, n_dec - i0);
         const int t0g = dec_step(i0);                // the group's first step
@@ -2485,6 +2546,15 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
             if (c.stats) {                           // likewise, beside the spectrum launch
                 fs.frames = fb; fs.y_t = c.t0 + t0g; fs.o_t = stats_steps.next; fs.n = stats_steps.pick(t0g, kk, fs.sel);
                 if (fs.n) HIPCHK(e, launch_field_stats_group(fs, dstream[d]));
+            }
+            if (c.flow) {                            // behind the statistics launch; the frame buffer is reused in stream order
+                fw.frames = fb; fw.y_t = c.t0 + t0g; fw.o_t = flow_steps.next; fw.n = flow_steps.pick(t0g, kk, fw.sel);
+                if (fw.n) HIPCHK(e, launch_flow_stats_group(fw, dstream[d]));
+                if (fv.vort && nk) {                 // the vorticity of the group's kept steps, beside their copies
+                    fv.frames = fb; fv.o_t = ki; fv.n = nk;
+                    for (int i = 0; i < nk; ++i) fv.sel[i] = kj[i];
+                    HIPCHK(e, launch_vorticity_group(fv, dstream[d]));
+                }
             }
             if (c.maps) {
                 // The one result of the scored path that is reduced across groups: a pixel's sums take its steps in ascending
@@ -2650,6 +2720,13 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
             !a.latent_seq && !a.z_true_out && !a.recon_frames_out)
             return einval(e, "attrib: no output is set");
     }
+    if (scored && c.flow) {
+        if (c.sel_bad) return einval(e, "sel: the size field is not sizeof(lns_eval_select)");
+        if (c.sel.maps_out || c.sel.map_from != 0 || c.sel.map_every != 0)
+            return einval(e, "sel asks for time maps: the flow form keeps the workspace of lns_rollout_eval (lns_rollout_eval_maps has them)");
+        std::string steps_err;
+        if (const char* why = flow_refusal(c, e->cfg.in_channels, &steps_err)) return einval(e, why);
+    }
     if (int brc = check_batch(e, c.B)) return brc;
     if (scored && c.T_total > e->opt_eval_max_steps) {
         e->err = fmt("%d steps exceed the option eval_max_steps = %d (it sizes the evaluation workspace)", c.T_total, e->opt_eval_max_steps);
@@ -2734,13 +2811,13 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
 // The one body of the eight scored entry points (lns_rollout_eval, lns_rollout_latent_eval and their _spectrum / _stats /
 // _maps forms): the union of their argument lists.  From x: encode, t0 = 0, T_total = T, no z_last.  The selections come
 // loose (the _spectrum and _stats forms; all null / 0 for the plain one) or, for SCORED_MAPS, in `sel`.
-enum ScoredForm { SCORED_PLAIN, SCORED_SPECTRUM, SCORED_STATS, SCORED_MAPS, SCORED_ATTRIB };   // (_ATTRIB: the plain form + `attrib`)
+enum ScoredForm { SCORED_PLAIN, SCORED_SPECTRUM, SCORED_STATS, SCORED_MAPS, SCORED_ATTRIB, SCORED_FLOW };   // (_ATTRIB: the plain form + `attrib`; _FLOW: a nullable `sel` without maps + `flow`)
 static int scored_call(lns_engine* e, ScoredForm form, const float* start, bool encode, const float* param, const float* y_true,
                        int B, int T, int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
                        const int* keep, int n_keep, float* frames_out, float* z_last, void* ws, size_t ws_bytes, void* stream,
                        const int* spectrum_steps, int n_spec, float* spectra_out, const int* stats_steps, int n_stats,
                        const lns_stats_spec* hspec, float* stats_out, int32_t* hist_out, const lns_eval_select* sel,
-                       const lns_eval_attrib* attrib = nullptr) {
+                       const lns_eval_attrib* attrib = nullptr, const lns_eval_flow* flow = nullptr) {
     RolloutCall c(start, encode, param, B, T, ws, ws_bytes, stream);
     c.sink = SINK_SCORED;
     c.attrib = form == SCORED_ATTRIB;
@@ -2751,7 +2828,14 @@ static int scored_call(lns_engine* e, ScoredForm form, const float* start, bool 
     c.maps = form == SCORED_MAPS;
     c.sel_bad = c.maps && (!sel || sel->size != sizeof(lns_eval_select));   // (the two selections then count as absent)
     if (c.maps && !c.sel_bad) c.sel = *sel;
-    if (!c.maps) {
+    c.flow = form == SCORED_FLOW;
+    if (c.flow) {
+        c.sel_bad = sel && sel->size != sizeof(lns_eval_select);
+        if (sel && !c.sel_bad) c.sel = *sel;
+        c.flow_bad = !flow || flow->size != sizeof(lns_eval_flow);
+        if (!c.flow_bad) c.fl = *flow;
+    }
+    if (!c.maps && !c.flow) {
         c.sel.spectrum_steps_host = spectrum_steps; c.sel.n_spec = n_spec; c.sel.spectra_out = spectra_out;
         c.sel.stats_steps_host = stats_steps; c.sel.n_stats = n_stats; c.sel.hspec = hspec; c.sel.stats_out = stats_out;
         c.sel.hist_out = hist_out;
@@ -2887,6 +2971,25 @@ int lns_rollout_latent_eval_attrib(lns_engine* e, const float* z_in, const float
     return scored_call(e, SCORED_ATTRIB, z_in, false, param, y_true, B, T, t0, T_total, spec, frame_out, seq_out, keep_steps_host,
                        n_keep, frames_out, z_last, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
                        nullptr, attrib);
+}
+
+// ---- streaming validation with flow diagnostics (include/lns.h) ---------------------------------------------------
+int lns_rollout_eval_flow(lns_engine* e, const float* x, const float* param, const float* y_true, int B, int T,
+                          const lns_eval_spec* spec, float* frame_out, float* seq_out, const int* keep_steps_host, int n_keep,
+                          float* frames_out, void* ws, size_t ws_bytes, void* stream, const lns_eval_select* sel,
+                          const lns_eval_flow* flow) {
+    return scored_call(e, SCORED_FLOW, x, true, param, y_true, B, T, 0, T, spec, frame_out, seq_out, keep_steps_host, n_keep,
+                       frames_out, nullptr, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, sel,
+                       nullptr, flow);
+}
+
+int lns_rollout_latent_eval_flow(lns_engine* e, const float* z_in, const float* param, const float* y_true, int B, int T,
+                                 int t0, int T_total, const lns_eval_spec* spec, float* frame_out, float* seq_out,
+                                 const int* keep_steps_host, int n_keep, float* frames_out, float* z_last, void* ws,
+                                 size_t ws_bytes, void* stream, const lns_eval_select* sel, const lns_eval_flow* flow) {
+    return scored_call(e, SCORED_FLOW, z_in, false, param, y_true, B, T, t0, T_total, spec, frame_out, seq_out, keep_steps_host,
+                       n_keep, frames_out, z_last, ws, ws_bytes, stream, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                       sel, nullptr, flow);
 }
 
 // ---- stage-1 validation (include/lns.h) ---------------------------------------------------------------------------
@@ -3110,6 +3213,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "eval_stats")) return 1;
     if (!strcmp(feature, "eval_maps")) return 1;
     if (!strcmp(feature, "eval_attrib")) return 1;
+    if (!strcmp(feature, "eval_flow")) return 1;
     if (!strcmp(feature, "op_conv_gn")) return 1;
     if (!strcmp(feature, "op_fa_fused")) return 1;
     if (!strcmp(feature, "op_fa_axis")) return 1;

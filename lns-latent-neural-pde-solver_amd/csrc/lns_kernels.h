@@ -503,6 +503,32 @@ struct FieldStatsArgs {
 hipError_t launch_field_stats_group(const FieldStatsArgs& a, hipStream_t s);
 hipError_t launch_field_stats_stored(const FieldStatsArgs& a, hipStream_t s);
 
+// Flow diagnostics (lns_rollout_eval_flow, lns_op_flow_stats, lns_op_vorticity; the statement: include/lns.h): across the two
+// velocity channels cu (x-component) and cv.  Statistics: one block per frame (b, step) writes its LNS_FLOW_STATS_N floats to
+// stats and, when hist is given, its 2 x (nbins + 2) int32 counts of the vorticity (forecast row, truth row).
+// Group form: frames [kk][B][C][H*W]; the n <= 8 selected steps sel[0 .. n) of the group against the truth frames
+// y[b][y_t + sel[i]] of y [B][y_T][C][H*W] into frame (b, o_t + i) of stats [B][o_T][12] / hist [B][o_T][2][nbins + 2].
+// Stored form: frames and y are [B][n][C][H*W], the outputs [B][n][..] (sel, y_T, y_t, o_T, o_t unused).
+// Vorticity: the forecast's vorticity of the same frames into vort [B][o_T][H*W] (group) / [B][n][H*W] (stored); y, stats, hist unused.
+// bc_y / bc_x: 0 periodic, 1 wall; rc* = 1 / (2 d), re* = 1 / d of the axis (formed on the host); hscale = (float)nbins / (hhi - hlo).
+// n * B < 2^24 per launch.  Static LDS only (2.3 KB).  The denormalisation: as MetricGroupArgs.
+#define LNS_FLOW_STATS_N 12
+struct FlowStatsArgs {
+    const float* frames; const float* y; float* stats; int* hist; float* vort;
+    int B, C, H, W, n, y_T, y_t, o_T, o_t, nbins;
+    int cu, cv, bc_y, bc_x;
+    float rcy, rey, rcx, rex;
+    float eps, hlo, hhi, hscale;
+    ScoreNorm norm;
+    unsigned char sel[8];
+};
+template <class F> void for_each_ptr(FlowStatsArgs& a, F&& f) { f(a.frames); f(a.y); f(a.stats); f(a.hist); f(a.vort); }
+LNS_ARGS_SIZE(FlowStatsArgs, 256);
+hipError_t launch_flow_stats_group(const FlowStatsArgs& a, hipStream_t s);
+hipError_t launch_flow_stats_stored(const FlowStatsArgs& a, hipStream_t s);
+hipError_t launch_vorticity_group(const FlowStatsArgs& a, hipStream_t s);
+hipError_t launch_vorticity_stored(const FlowStatsArgs& a, hipStream_t s);
+
 // Time maps (lns_rollout_eval_maps, lns_op_time_maps; the statement: include/lns.h): per (b, c, pixel) six float64 sums and
 // an fp32 running maximum over the selected steps, in `state`: [6][N] doubles (Sa, Sb, Saa, Sbb, Sab, See) followed by [N]
 // floats, N = B * C * H * W, 52 N bytes; 8-byte aligned, zeroed before the first step of a horizon.

@@ -5309,6 +5309,7 @@ hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int 
 
 #include "spectrum.inc"
 #include "field_stats.inc"
+#include "flow_stats.inc"
 #include "time_maps.inc"
 #include "eval_attrib.inc"
 #include "ensemble_quantile.inc"

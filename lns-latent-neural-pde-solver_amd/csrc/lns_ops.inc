@@ -496,6 +496,53 @@ int lns_op_field_stats(const float* yhat, const float* y, int B, int T, int C, i
     return LNS_OK;
 }
 
+static_assert(LNS_FLOW_STATS_N == LNS_FLOW_STATS, "the kernels' and the header's number of flow statistics differ");
+
+// The shape bounds of the flow ops on stored fields [B][T][C][H][W]: one block (row of blocks) per frame, 256 threads each
+static bool op_flow_shape_refused(const char* op, int B, int T, int C, int H, int W) {
+    if (B >= 1 && T >= 1 && C >= 2 && H >= 1 && W >= 1 && (int64_t)H * W <= (1LL << 30) && (int64_t)B * T < (1LL << 24)) return false;
+    op_refuse(op, "B, T, H, W >= 1, C >= 2, H * W <= 2^30 and B * T < 2^24");
+    return true;
+}
+
+// flow_stats_stored_kernel on stored fields: the per-frame body of the streaming call (flow_stats_plane)
+int lns_op_flow_stats(const float* yhat, const float* y, int B, int T, int C, int H, int W, const lns_eval_spec* spec,
+                      const lns_flow_spec* fspec, float* flow_out, int32_t* hist_out, void* stream) {
+    if (!yhat || !y || !flow_out) return op_refuse("flow_stats", "yhat / y / flow_out is null");
+    if (op_spec_refused("flow_stats", spec)) return LNS_EINVAL;
+    if (op_flow_shape_refused("flow_stats", B, T, C, H, W)) return LNS_EINVAL;
+    if (op_spec_refused("flow_stats", spec, C)) return LNS_EINVAL;
+    if (const char* why = flow_spec_refusal(fspec, C, hist_out)) return op_refuse("flow_stats", why);
+    OpScratch sc;                                    // (no device memory of its own: the first failure and the final wait)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FlowStatsArgs a;
+    flow_args(fspec, spec, B, C, H, W, &a);
+    a.frames = yhat; a.y = y; a.stats = flow_out; a.hist = hist_out; a.n = T;
+    if (sc.ok()) sc.note(init_kernels());
+    if (sc.ok()) sc.note(launch_flow_stats_stored(a, s));
+    OPCHK(sc.finish(s));
+    return LNS_OK;
+}
+
+// vorticity_stored_kernel on stored fields: the pixel function of the statistics, pointwise
+int lns_op_vorticity(const float* fields, int B, int T, int C, int H, int W, const lns_eval_spec* spec, const lns_flow_spec* fspec,
+                     float* vort_out, void* stream) {
+    if (!fields || !vort_out) return op_refuse("vorticity", "fields / vort_out is null");
+    if (op_spec_refused("vorticity", spec)) return LNS_EINVAL;
+    if (op_flow_shape_refused("vorticity", B, T, C, H, W)) return LNS_EINVAL;
+    if (op_spec_refused("vorticity", spec, C)) return LNS_EINVAL;
+    if (const char* why = flow_spec_refusal(fspec, C, nullptr)) return op_refuse("vorticity", why);
+    OpScratch sc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FlowStatsArgs a;
+    flow_args(fspec, spec, B, C, H, W, &a);
+    a.frames = fields; a.vort = vort_out; a.n = T;
+    if (sc.ok()) sc.note(init_kernels());
+    if (sc.ok()) sc.note(launch_vorticity_stored(a, s));
+    OPCHK(sc.finish(s));
+    return LNS_OK;
+}
+
 static_assert(LNS_TIME_MAPS_N == LNS_TIME_MAPS, "the kernels' and the header's number of time maps differ");
 
 int lns_time_maps_state_bytes(int B, int C, int H, int W, size_t* bytes) {

@@ -660,6 +660,30 @@ class LatentDynamics(_Hosted):
                                                  stats_steps=stats_steps, hist=hist, spectrum_steps=spectrum_steps,
                                                  spectrum_basis=spectrum_basis, **norm)
 
+    @torch.no_grad()
+    def validate_flow(self, x, y, *rest, flow_steps=None, u=0, v=1, dx=1.0, dy=1.0, boundary="auto", vort_hist=None,
+                      stats_steps=(), hist=None, spectrum_steps=(), keep_steps=(), spectrum_basis="dft", **norm):
+        """validate_flow(x, y, **norm) -- conditional: validate_flow(x, y, param, **norm): `validate` with the flow diagnostics
+        (metrics.FLOW_STATS: kinetic energy, enstrophy, rms divergence, vorticity error and cosine, velocity error, extrema) of
+        the steps `flow_steps` (a sequence, range or slice; None: every step) across the velocity channels u (x-component)
+        and v, taken as the steps are decoded: does the forecast stay divergence-free like the truth, does it keep the energy
+        and the enstrophy, how wrong is its vorticity.  dx / dy: the grid spacings; boundary: "periodic", "wall", a pair
+        (y, x) or "auto" (periodic where the autoencoder pads circularly); vort_hist = (nbins, lo, hi): the vorticity
+        histograms of forecast and truth; keep_steps: the kept frames and their vorticity; `stats_steps` / `hist` and
+        `spectrum_steps` add validate_stats' statistics and validate_spectrum's spectra in the same pass.  `norm` restates the
+        dataset's denormalize, zero_wall_channels and clamp included.  Returns engine.EvalFlow."""
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("validate_flow() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if rest:
+            raise TypeError("validate_flow() takes (x, y, param, **norm)" if self._conditional
+                            else "validate_flow() takes (x, y, **norm)")
+        x = self._fields(x)
+        return self._engine(x).rollout_eval_flow(x, y, param=param, keep_steps=keep_steps, flow_steps=flow_steps, u=u, v=v, dx=dx,
+                                                 dy=dy, boundary=boundary, vort_hist=vort_hist, stats_steps=stats_steps,
+                                                 hist=hist, spectrum_steps=spectrum_steps, spectrum_basis=spectrum_basis, **norm)
 
     @torch.no_grad()
     def validate_attribution(self, x, y, *rest, keep_steps=(), return_latents=False, **norm):

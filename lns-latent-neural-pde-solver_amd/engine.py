@@ -328,6 +328,38 @@ def stats_spec(C, hist):
     return hs
 
 
+EvalFlow = collections.namedtuple("EvalFlow", "frame seq frames flow hist vort_frames steps stats stats_hist stats_steps spectra "
+                                  "spectrum_steps")
+EvalFlow.__doc__ = """Result of Engine.rollout_eval_flow: frame [B, T, C], seq [B, C] and frames (or None) as rollout_eval returns them,
+flow [B, len(steps), 12] (columns: metrics.FLOW_STATS), hist [B, len(steps), 2, nbins + 2] int32 (the vorticity of forecast and
+truth; bins: metrics.histogram_edges) or None, vort_frames [B, len(keep_steps), Ly, Lx] (the forecast's vorticity of the kept
+frames) or None, steps (the steps flow / hist belong to), then rollout_eval_stats' stats / stats_hist / stats_steps and spectra /
+spectrum_steps (None and empty where they were not asked for)."""
+EvalFlowChunk = collections.namedtuple("EvalFlowChunk", EvalFlow._fields + ("z_last",))
+EvalFlowChunk.__doc__ = """Result of Engine.rollout_latent_eval_flow: EvalFlow's fields for the chunk, then z_last, the latent after
+the chunk's last step."""
+
+
+def flow_spec(u=0, v=1, dx=1.0, dy=1.0, boundary="periodic", vort_hist=None, cfg=None):
+    """`lns_flow_spec`: the velocity channels u (x-component) and v, the spacings, `boundary` as metrics.flow_boundary takes it
+    ("auto" needs cfg) and vort_hist = (nbins, lo, hi) in units of the vorticity or None."""
+    from . import metrics
+    fs = _lib.LnsFlowSpec()
+    fs.size = ctypes.sizeof(_lib.LnsFlowSpec)
+    fs.cu, fs.cv = int(u), int(v)
+    fs.bc_y, fs.bc_x = metrics.flow_boundary(boundary, cfg)
+    fs.dy, fs.dx = float(dy), float(dx)
+    if vort_hist is not None:
+        try:
+            nbins, lo, hi = vort_hist
+            fs.nbins, fs.lo, fs.hi = int(nbins), float(lo), float(hi)
+        except (TypeError, ValueError):
+            raise LnsError("vort_hist must be (nbins, lo, hi) with scalar edges, got %r" % (vort_hist,))
+        if not 1 <= fs.nbins <= 256:
+            raise LnsError("vort_hist: nbins must be in 1 .. 256, got %d" % fs.nbins)
+    return fs
+
+
 def normalize_keep_steps(keep_steps, steps):
     """The `keep_steps` argument of the selected-step rollout -> list of ints, strictly ascending, in [0, steps).
     A slice is resolved against `steps` as indexing a [.., steps, ..] tensor would (slice(None, None, 5) is `::5`); a
@@ -1115,12 +1147,10 @@ class Engine:
         from . import metrics
         return metrics.time_maps(y_hat, y, map_steps=map_steps, **norm)
 
-    def _maps_select(self, map_steps, stats_steps, hist, spectrum_steps, T, B, device, basis="dft"):
-        """A `select` of _scored_call: the lns_eval_select of the time maps over `map_steps` = (from, every) with the
-        (optional) statistics and spectra; the maps tensor itself is _scored_call's."""
+    def _select_struct(self, stats_steps, hist, spectrum_steps, T, B, device, basis="dft"):
+        """-> (an lns_eval_select with the (optional) statistics and spectra, EvalStats' fields after `frames`)"""
         q = _lib.LnsEvalSelect()
         q.size = ctypes.sizeof(_lib.LnsEvalSelect)
-        q.map_from, q.map_every = map_steps
         tail = (None, None, [])
         if stats_steps is not None and not isinstance(stats_steps, slice) and len(stats_steps) == 0:
             if hist is not None:
@@ -1134,7 +1164,14 @@ class Engine:
         (sarr, n_spec, spectra), stail, _ = self._spectrum_select(spectrum_steps, T, B, device, optional=True, basis=basis)
         if n_spec:
             q.n_spec, q.spectrum_steps_host, q.spectra_out = n_spec, sarr, spectra
-        return (ctypes.byref(q),), tail + stail, q
+        return q, tail + stail
+
+    def _maps_select(self, map_steps, stats_steps, hist, spectrum_steps, T, B, device, basis="dft"):
+        """A `select` of _scored_call: the lns_eval_select of the time maps over `map_steps` = (from, every) with the
+        (optional) statistics and spectra; the maps tensor itself is _scored_call's."""
+        q, tail = self._select_struct(stats_steps, hist, spectrum_steps, T, B, device, basis)
+        q.map_from, q.map_every = map_steps
+        return (ctypes.byref(q),), tail, q
 
     def rollout_eval_maps(self, x, y, steps=None, param=None, keep_steps=(), map_steps=None, stats_steps=(), hist=None,
                           spectrum_steps=(), spectrum_basis="dft", **norm):
@@ -1161,6 +1198,74 @@ class Engine:
         with self._spectrum_basis(spectrum_basis) as names:
             return self._scored_call("lns_rollout_latent_eval_maps", EvalMapsChunk, z, y, steps, t0, param, keep_steps, norm,
                                      functools.partial(self._maps_select, ms, stats_steps, hist, spectrum_steps, basis=names), frame, seq, maps)
+
+    # -- streaming validation with flow diagnostics (include/lns.h "flow diagnostics") -----------------------------
+    def _boundary_names(self, boundary):
+        """`boundary` with "auto" resolved against this model, as a pair of names; host only, a bad name raises LnsError."""
+        from . import metrics
+        by, bx = metrics.flow_boundary(boundary, self.cfg)
+        return metrics.FLOW_BOUNDARIES[by], metrics.FLOW_BOUNDARIES[bx]
+
+    def flow_stats(self, y_hat, y, u=0, v=1, dx=1.0, dy=1.0, boundary="auto", vort_hist=None, **norm):
+        """Flow diagnostics of stored fields (lns_op_flow_stats): see metrics.flow_stats; boundary="auto" is resolved against
+        this model.  The kernel body of rollout_eval_flow."""
+        from . import metrics
+        return metrics.flow_stats(y_hat, y, u=u, v=v, dx=dx, dy=dy, boundary=self._boundary_names(boundary), vort_hist=vort_hist, **norm)
+
+    def vorticity(self, fields, u=0, v=1, dx=1.0, dy=1.0, boundary="auto", **norm):
+        """The vorticity of stored fields [B,T,C,H,W] -> [B,T,H,W] (lns_op_vorticity): see metrics.vorticity."""
+        from . import metrics
+        return metrics.vorticity(fields, u=u, v=v, dx=dx, dy=dy, boundary=self._boundary_names(boundary), **norm)
+
+    def _flow_select(self, fs, flow_steps, n_keep, stats_steps, hist, spectrum_steps, T, B, device, basis="dft"):
+        """A `select` of _scored_call: the lns_eval_flow of the steps `flow_steps` under the lns_flow_spec fs, the vorticity of
+        the n_keep kept frames, and the lns_eval_select of the (optional) statistics and spectra, or null."""
+        import torch
+        c = self.cfg
+        sel = normalize_keep_steps(range(T) if flow_steps is None else flow_steps, T)
+        arr = (ctypes.c_int * len(sel))(*sel)
+        flow = torch.empty((B, len(sel), _lib.LNS_FLOW_STATS), dtype=torch.float32, device=device)
+        counts = torch.empty((B, len(sel), 2, fs.nbins + 2), dtype=torch.int32, device=device) if fs.nbins else None
+        vort = torch.empty((B, n_keep, c.Ly, c.Lx), dtype=torch.float32, device=device) if n_keep else None
+        fl = _lib.LnsEvalFlow()
+        fl.size = ctypes.sizeof(_lib.LnsEvalFlow)
+        fl.n_flow, fl.flow_steps_host, fl.fspec = len(sel), arr, ctypes.pointer(fs)
+        fl.flow_out, fl.hist_out, fl.vort_frames_out = flow.data_ptr(), self._ptr(counts), self._ptr(vort)
+        q, stail = self._select_struct(stats_steps, hist, spectrum_steps, T, B, device, basis)
+        qp = ctypes.byref(q) if (q.n_stats or q.n_spec) else None
+        return (qp, ctypes.byref(fl)), (flow, counts, vort, sel) + stail, None
+
+    def rollout_eval_flow(self, x, y, steps=None, param=None, keep_steps=(), flow_steps=None, u=0, v=1, dx=1.0, dy=1.0,
+                          boundary="auto", vort_hist=None, vort_frames=True, stats_steps=(), hist=None, spectrum_steps=(),
+                          spectrum_basis="dft", **norm):
+        """rollout_eval with, for the steps `flow_steps` (what `normalize_keep_steps` takes; None: every step), the twelve flow
+        diagnostics metrics.FLOW_STATS of the decoded frame against the truth across the velocity channels u (x-component) and
+        v -- kinetic energy, enstrophy, rms divergence, vorticity error and cosine, velocity error, extrema -- with spacings
+        dx / dy and `boundary` ("periodic", "wall", a pair (y, x) or "auto": periodic where this model's autoencoder pads
+        circularly).  vort_hist = (nbins, lo, hi) adds the vorticity histograms of both; keep_steps with vort_frames adds the
+        forecast's vorticity of the kept frames; `stats_steps` / `hist` and `spectrum_steps` (default: none) add
+        rollout_eval_stats' statistics and rollout_eval_spectrum's spectra in the same pass.  Returns EvalFlow: flow / hist /
+        vort_frames hold the bits of `flow_stats` / `vorticity` on rollout(x, T), every other field those of the existing
+        calls.  The workspace is rollout_eval's."""
+        fs = flow_spec(u, v, dx, dy, boundary, vort_hist, cfg=self.cfg)
+        n_keep = len([int(s) for s in keep_steps]) if vort_frames else 0
+        with self._spectrum_basis(spectrum_basis) as names:
+            return self._scored_call("lns_rollout_eval_flow", EvalFlow, x, y, steps, None, param, keep_steps, norm,
+                                     functools.partial(self._flow_select, fs, flow_steps, n_keep, stats_steps, hist, spectrum_steps,
+                                                       basis=names))
+
+    def rollout_latent_eval_flow(self, z, y, steps=None, t0=0, param=None, keep_steps=(), flow_steps=None, u=0, v=1, dx=1.0,
+                                 dy=1.0, boundary="auto", vort_hist=None, vort_frames=True, stats_steps=(), hist=None,
+                                 spectrum_steps=(), frame=None, seq=None, spectrum_basis="dft", **norm):
+        """rollout_latent_eval with flow diagnostics: keep_steps, flow_steps, stats_steps and spectrum_steps are relative to the
+        chunk, and flow / hist / vort_frames / stats / spectra belong to this chunk's steps.  Returns EvalFlowChunk (see
+        rollout_latent_eval for frame / seq)."""
+        fs = flow_spec(u, v, dx, dy, boundary, vort_hist, cfg=self.cfg)
+        n_keep = len([int(s) for s in keep_steps]) if vort_frames else 0
+        with self._spectrum_basis(spectrum_basis) as names:
+            return self._scored_call("lns_rollout_latent_eval_flow", EvalFlowChunk, z, y, steps, t0, param, keep_steps, norm,
+                                     functools.partial(self._flow_select, fs, flow_steps, n_keep, stats_steps, hist, spectrum_steps,
+                                                       basis=names), frame, seq)
 
     # -- streaming validation with error attribution (include/lns.h "error attribution") ---------------------------
     def eval_attrib(self, y_hat, r, y, **norm):

@@ -196,6 +196,94 @@ def field_stats(y_hat, y, hist=None, mean=0.0, std=1.0, eps=1e-8, zero_wall_chan
     return stats, counts
 
 
+FLOW_STATS = ("ke_P", "ke_Q", "ens_P", "ens_Q", "div_P", "div_Q", "vort_err", "vort_cos", "vel_err", "maxvort_P", "maxvort_Q",
+              "maxdiv_P")
+FLOW_BOUNDARIES = ("periodic", "wall")
+
+
+def flow_boundary(boundary, cfg=None):
+    """(bc_y, bc_x) as LNS_FLOW_PERIODIC / LNS_FLOW_WALL (0 / 1) from "periodic", "wall", a pair (y, x) of the two names, or
+    "auto": per axis "periodic" where the model's autoencoder pads that axis circularly (cfg.ae_pad_y / ae_pad_x of an engine's
+    configuration), else "wall" -- the rule of `spectrum_basis`: periodic / periodic for ns2d*, wall / periodic for
+    sw_half_periodic, wall / wall for the two-phase presets.  Host only; anything else raises LnsError."""
+    def one(b):
+        if not isinstance(b, str) or b not in FLOW_BOUNDARIES:
+            raise _lib.LnsError('flow boundary: "periodic", "wall", a pair (y, x) of them or "auto", got %r' % (boundary,))
+        return FLOW_BOUNDARIES.index(b)
+    if isinstance(boundary, str):
+        if boundary == "auto":
+            if cfg is None:
+                raise _lib.LnsError('flow boundary "auto" needs a model (Engine.flow_stats / the rollout calls): '
+                                    'name the boundaries of stored fields')
+            return tuple(0 if pad == _lib.LNS_PAD_CIRCULAR else 1 for pad in (cfg.ae_pad_y, cfg.ae_pad_x))
+        return one(boundary), one(boundary)
+    try:
+        by, bx = boundary
+    except (TypeError, ValueError):
+        raise _lib.LnsError('flow boundary: "periodic", "wall", a pair (y, x) of them or "auto", got %r' % (boundary,))
+    return one(by), one(bx)
+
+
+def _flow_fields(name, tensors):
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 5:
+            raise _lib.LnsError("%s takes fp32 HIP tensors [B,T,C,H,W] (no CPU fallback)" % name)
+
+
+def flow_stats(y_hat, y, u=0, v=1, dx=1.0, dy=1.0, boundary="periodic", vort_hist=None, mean=0.0, std=1.0, eps=1e-8,
+               zero_wall_channels=(), clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
+    """Flow diagnostics of stored fields (lns_op_flow_stats; include/lns.h "flow diagnostics"): y_hat and y [B,T,C,H,W],
+    normalised, denormalised as in `relative_l2` into forecast P and truth Q; channels u (x-component) and v are the velocity
+    pair, dx / dy the grid spacings, `boundary` what `flow_boundary` takes ("auto" needs a model: Engine.flow_stats).
+    Returns (flow [B,T,12], hist): the columns are FLOW_STATS -- mean kinetic energy and enstrophy of P and Q, their rms
+    divergence, the relative L2 error and the cosine of the vorticity, the relative L2 error of the velocity, and the largest
+    |vorticity| of P and Q and |divergence| of P.  Derivatives are central differences, wrapped on a periodic axis and
+    one-sided at the two ends of a wall axis (numpy.gradient).  vort_hist = (nbins, lo, hi) adds the int32 counts
+    [B,T,2,nbins+2] of the vorticity (rows forecast, truth; bins as `histogram_edges`), else None.
+    The kernel body of Engine.rollout_eval_flow."""
+    from .engine import eval_spec, flow_spec
+    fs = flow_spec(u, v, dx, dy, boundary, vort_hist)                  # (a bad boundary is named before the tensors are looked at)
+    _flow_fields("flow_stats", (y_hat, y))
+    if y.shape != y_hat.shape or y.device != y_hat.device:
+        raise _lib.LnsError("y must have y_hat's shape %s and device, got %s" % (tuple(y_hat.shape), tuple(y.shape)))
+    B, T, C, H, W = (int(n) for n in y_hat.shape)
+    y_hat, y = y_hat.contiguous(), y.contiguous()
+    spec = eval_spec(C, mean=mean, std=std, eps=eps, zero_wall_channels=zero_wall_channels, clamp_channels=clamp_channels,
+                     clamp=clamp)
+    flow = torch.empty((B, T, _lib.LNS_FLOW_STATS), dtype=torch.float32, device=y_hat.device)
+    counts = torch.empty((B, T, 2, fs.nbins + 2), dtype=torch.int32, device=y_hat.device) if fs.nbins else None
+    L = _lib.lib()
+    with torch.cuda.device(y_hat.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(y_hat.device).cuda_stream)
+        rc = L.lns_op_flow_stats(y_hat.data_ptr(), y.data_ptr(), B, T, C, H, W, ctypes.byref(spec), ctypes.byref(fs),
+                                 flow.data_ptr(), counts.data_ptr() if counts is not None else None, stream)
+    if rc != 0:
+        raise _lib.LnsError("lns_op_flow_stats failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    return flow, counts
+
+
+def vorticity(fields, u=0, v=1, dx=1.0, dy=1.0, boundary="periodic", mean=0.0, std=1.0, eps=1e-8, zero_wall_channels=(),
+              clamp_channels=(), clamp=(0.0, 1.0 + 1e-8)):
+    """The vorticity dv/dx - du/dy of stored fields (lns_op_vorticity): fields [B,T,C,H,W], normalised (a forecast or the
+    truth), denormalised and differenced as in `flow_stats` -> [B,T,H,W].  The pixel function of the statistics and of the
+    vort_frames of Engine.rollout_eval_flow."""
+    from .engine import eval_spec, flow_spec
+    fs = flow_spec(u, v, dx, dy, boundary, None)
+    _flow_fields("vorticity", (fields,))
+    B, T, C, H, W = (int(n) for n in fields.shape)
+    fields = fields.contiguous()
+    spec = eval_spec(C, mean=mean, std=std, eps=eps, zero_wall_channels=zero_wall_channels, clamp_channels=clamp_channels,
+                     clamp=clamp)
+    out = torch.empty((B, T, H, W), dtype=torch.float32, device=fields.device)
+    L = _lib.lib()
+    with torch.cuda.device(fields.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(fields.device).cuda_stream)
+        rc = L.lns_op_vorticity(fields.data_ptr(), B, T, C, H, W, ctypes.byref(spec), ctypes.byref(fs), out.data_ptr(), stream)
+    if rc != 0:
+        raise _lib.LnsError("lns_op_vorticity failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    return out
+
+
 def histogram_edges(nbins, lo, hi):
     """The nbins + 1 edges lo + k (hi - lo) / nbins of the interior bins of a field_stats histogram, float64 [nbins + 1]
     (lo, hi scalars) or [C, nbins + 1] (per channel).  Bin 0 of the counts lies below edges[0], bin k in 1 .. nbins between
