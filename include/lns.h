@@ -886,7 +886,7 @@ int lns_check_finite(lns_engine* e, int B, void* workspace, size_t workspace_byt
  * do not belong to the propagator are ignored and may be null); parameters are read from the device at every call
  * (an optimiser updates them in place between calls) -- lns_set_weight / lns_finalize_weights are not involved.
  * All contractions run on the exact-fp32 matrix instruction.  Plain propagators (NS2d, SW, two-phase) and the
- * conditional one (train_stage2_twophase_conditional.py:25-121; `param` [B], no gradient w.r.t. it).  The same
+ * conditional one (train_stage2_twophase_conditional.py:25-121; `param` [B]; its gradient: lns_train_backward_ex).  The same
  * workspace and parameter values must be used for the backward call.
  * lns_train_workspace_bytes needs no device for the size; when the process has one it also builds the shape's plan (device
  * index maps) on the caller's current device, so that the first run call does not.
@@ -1020,6 +1020,90 @@ int lns_train_step_clip(lns_engine* e, float* const* params, const float* z_in, 
                         float* const* exp_avg_sq, const lns_update_spec* spec, float* loss_out, float* norm_out,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- latent fit: the rollout run backwards onto data -----------------------------------------------------------------
+ * No reference counterpart: the reference trains the propagator and never differentiates with respect to its inputs.
+ * Which initial latent makes the rollout agree with several observed frames, and which `param` explains an observed
+ * sequence, are answered by descending on z0 [B,c,h,w] and / or param [B] with the propagator's weights held fixed.
+ *
+ * lns_train_backward_ex = lns_train_backward (same arguments, same launches, same bits) with two additions:
+ *   * grads == NULL selects the STATE-ONLY ADJOINT: no weight-gradient, bias-gradient or GroupNorm-affine launch and no
+ *     parameter output of the conditional vector network (their kernels take null outputs; nothing is written anywhere in
+ *     their place), and the copy that only feeds the one-block-per-tile in_proj weight gradient is skipped.  The data path
+ *     is the same kernels in the same order: grad_z_in has the bits of the full call.  The workspace only has to cover the
+ *     layout WITHOUT the partial-sum area of "train_wgrad" = 1 (which is appended), so one sized under either value is
+ *     accepted.  lns_train_backward itself still refuses grads == NULL.
+ *   * grad_param [B] (nullable; both modes): d loss / d param of the conditional propagator (LNS_EINVAL on a plain one).
+ *     The chain: the per-block d m and d emb sums and the vector network's backward as they are, d ce summed over the
+ *     blocks, then d fe = W0^T d l0 and
+ *         grad_param[b] = sum_k f_k (-sin(a_k) dfe[b,k] + cos(a_k) dfe[b,half+k]),  a_k = param[b] f_k,
+ *     f_k = exp(-ln(1e4) k / half) as the forward forms it, summed in ascending k by one thread per sample in fp32; the
+ *     zero column of an odd embedding width is not read.  cos(a_k) and sin(a_k) are the forward's own fe, which the
+ *     workspace still holds: the call takes no `param`. */
+int lns_train_backward_ex(lns_engine* e, const float* const* params, const float* z_in, const float* z_pred,
+                          const float* grad_z_pred, int B, int h, int w, int T, float* const* grads_or_null, float* grad_z_in,
+                          void* workspace, size_t workspace_bytes, void* stream, float* grad_param_or_null);
+
+/* Observation loss of a rollout and its gradient, one loss per trajectory (each sample is its own inverse problem).
+ * z_pred [B,T,n] (n = c*h*w), obs [B,n_obs,n]; HOST arrays obs_steps[n_obs] (0-based indices into the T axis, strictly
+ * ascending, each < T) and obs_weight[n_obs] (finite, >= 0; NULL: all 1); 1 <= n_obs <= LNS_OBS_MAX (the table travels
+ * in the kernel-argument block).  z0 and z_background [B,n] come together or not at all: the background term
+ * `background` (lambda >= 0) * mean_i (z0 - z_background)_i^2.
+ *     per  [B,n_obs] (nullable)  m_bk = (1/n) sum_i d_i^2,  d_i = z_pred[b,t_k,i] - obs[b,k,i]
+ *     loss [B]                   sum_k w_k m_bk + lambda (1/n) sum_i (z0 - z_b)_i^2
+ *     grad_z_pred [B,T,n]        (float)(2 w_k / n) * d_i on observed steps, exact zeros on every other step whatever the
+ *                                buffer held
+ *     grad_z0_bg [B,n] (nullable, needs z0)   (float)(2 lambda / n) * (z0 - z_b)_i
+ * Order: d in fp32; its square and every sum in double.  One 256-thread block per (b, t) plane: a thread adds its
+ * elements i = tid, tid + 256, ... in ascending order, the 64 lanes of a wave are summed as a balanced butterfly
+ * (neighbours first), the four waves as (w0 + w1) + (w2 + w3).  A finishing launch, one thread per sample, forms m_bk =
+ * sum * (1/n), adds w_k m_bk in ascending k and the background term last, all in double, and rounds once.  No atomics:
+ * bit-reproducible.  The coefficients 2 w_k / n and 2 lambda / n are rounded once on the host from double; the gradient is
+ * one fp32 subtraction and one fp32 multiplication per element, not contracted.  Scalar accesses: the bits do not depend
+ * on the alignment of the pointers.  scratch: device, lns_loss_obs_mse_scratch_bytes = 8 * B * (n_obs + 1) rounded up to
+ * 256 (LNS_ENOMEM when null or short).  No engine: the message of a refused call is lns_create_error()'s. */
+#define LNS_OBS_MAX 64
+int lns_loss_obs_mse_scratch_bytes(int B, int n_obs, size_t* bytes);
+int lns_loss_obs_mse(const float* z_pred, const float* obs, int B, int T, int64_t n, int n_obs, const int* obs_steps_host,
+                     const double* obs_weight_host_or_null, const float* z0_or_null, const float* z_background_or_null,
+                     double background, float* per_or_null, float* loss, float* grad_z_pred, float* grad_z0_bg_or_null,
+                     void* scratch, size_t scratch_bytes, void* stream);
+
+/* One iteration of the fit, enqueued on `stream` in this order:
+ *     lns_train_forward over T = obs_steps[n_obs-1] + 1 steps from z0 -> lns_loss_obs_mse -> the state-only
+ *     lns_train_backward_ex -> g_z = grad_z_in + grad_z0_bg (a separate fp32 add, only with z_background) ->
+ *     lns_update_step_tensors on z0 (spec.state) and on param (spec.param), one launch each, coef == NULL
+ * -- the bits of those calls made one after the other.  flags: LNS_FIT_STATE and / or LNS_FIT_PARAM (neither, or another
+ * bit: LNS_EINVAL; LNS_FIT_PARAM on a plain propagator: LNS_EINVAL).  z0 [B,c,h,w] and param [B] are updated IN PLACE when
+ * fitted and only read otherwise (param: required by the conditional propagator, ignored by the plain one).  obs
+ * [B,n_obs,c,h,w]; z_background [B,c,h,w] or NULL (no background term; background > 0 without it is LNS_EINVAL; the term
+ * enters the loss whenever it is given and the gradient when the state is fitted).  obs_steps (each < 2^24) / obs_weight as
+ * in lns_loss_obs_mse.
+ * state / param: an lns_update_spec each (own learning rate and step count); their flags and max_norm must be 0
+ * (LNS_EINVAL naming the field: there is no norm pass inside the step).  g_z / exp_avg_z / exp_avg_sq_z [B,c,h,w] and g_p /
+ * exp_avg_p / exp_avg_sq_p [B]: the caller's, required for what is fitted; the gradients stay in g_z / g_p.  loss [B]: the
+ * loss BEFORE the update; per [B,n_obs] nullable.  As in lns_train_step: no host synchronisation, no allocation, no copy
+ * from host memory, every refusal decided before the first HIP call.
+ * Workspace (lns_fit_step_workspace_bytes(e, B, h, w, T, n_obs); LNS_ENOMEM names the needed size): lns_train_step_
+ * workspace_bytes' layout for T steps | the double partials, 8 * B * (n_obs + 1) bytes | grad_z0_bg, 4 * B * c * h * w
+ * bytes -- each part rounded up to 256 bytes. */
+#define LNS_FIT_STATE 1u
+#define LNS_FIT_PARAM 2u
+typedef struct lns_fit_spec {
+    uint32_t size;                              /* sizeof(lns_fit_spec) */
+    uint32_t flags;                             /* LNS_FIT_* */
+    int32_t n_obs;
+    int32_t reserved;                           /* 0 */
+    const int* obs_steps;                       /* host, n_obs entries */
+    const double* obs_weight;                   /* host, n_obs entries, or NULL */
+    double background;                          /* lambda */
+    lns_update_spec state, param;
+} lns_fit_spec;
+int lns_fit_step_workspace_bytes(lns_engine* e, int B, int h, int w, int T, int n_obs, size_t* bytes);
+int lns_fit_step(lns_engine* e, const float* const* params, float* z0, float* param_or_null, const float* obs,
+                 const float* z_background_or_null, int B, int h, int w, const lns_fit_spec* spec, float* g_z,
+                 float* exp_avg_z, float* exp_avg_sq_z, float* g_p, float* exp_avg_p, float* exp_avg_sq_p, float* loss,
+                 float* per_or_null, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- diagnostics -------------------------------------------------------- */
 /* Layer trace: when enabled the run calls synchronise after every reference
  * module boundary and keep a host copy of its output (tests compare them with
@@ -1060,7 +1144,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * "ensemble_quantiles" = lns_rollout_latent_ensemble_quantiles and lns_op_ensemble_quantiles are there;
  * "ensemble_exceed" = lns_rollout_latent_ensemble_exceed and lns_op_ensemble_exceed are there; "op_fa_axis" =
  * lns_op_fa_reducer, lns_op_fa_lrk, lns_op_ln_pe, lns_op_apply, lns_rotary_table and the two fit predicates are there;
- * "eval_flow" = lns_rollout_eval_flow, lns_rollout_latent_eval_flow, lns_op_flow_stats and lns_op_vorticity are there.
+ * "eval_flow" = lns_rollout_eval_flow, lns_rollout_latent_eval_flow, lns_op_flow_stats and lns_op_vorticity are there;
+ * "latent_fit" = lns_train_backward_ex, lns_loss_obs_mse, its size query, lns_fit_step and its size query are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);

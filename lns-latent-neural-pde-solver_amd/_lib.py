@@ -161,6 +161,20 @@ class LnsUpdateSpec(ctypes.Structure):
     ]
 
 
+LNS_OBS_MAX = 64
+LNS_FIT_STATE, LNS_FIT_PARAM = 1, 2
+
+
+class LnsFitSpec(ctypes.Structure):
+    """Mirror of `struct lns_fit_spec` (include/lns.h): what is fitted, the observation table (host arrays), the weight of
+    the background term and one lns_update_spec each for the state and for `param`."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_obs", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("obs_steps", ctypes.POINTER(ctypes.c_int)), ("obs_weight", ctypes.POINTER(ctypes.c_double)),
+        ("background", ctypes.c_double), ("state", LnsUpdateSpec), ("param", LnsUpdateSpec),
+    ]
+
+
 def _fields(spec):
     """"x:p B:i eps:f ..." -> ctypes fields (p pointer, i int, f float, q int64)."""
     kinds = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "q": ctypes.c_int64}
@@ -219,6 +233,7 @@ SYMBOLS = [
     "lns_loss_smooth_l1", "lns_adam_step", "lns_adam_step_tensors", "lns_train_step_workspace_bytes", "lns_train_step",
     "lns_grad_norm_scratch_bytes", "lns_grad_norm_tensors", "lns_grad_scale_tensors", "lns_update_step_tensors",
     "lns_train_step_clip_workspace_bytes", "lns_train_step_clip",
+    "lns_train_backward_ex", "lns_loss_obs_mse_scratch_bytes", "lns_loss_obs_mse", "lns_fit_step_workspace_bytes", "lns_fit_step",
     "lns_trace_enable", "lns_trace_count", "lns_trace_info", "lns_trace_copy",
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
     "lns_op_conv_wgrad_scratch_bytes", "lns_op_conv_wgrad",
@@ -374,6 +389,14 @@ def lib():
         L.lns_update_step_tensors.argtypes = [i, vp, vp, vp, vp, i64p, up, vp, vp]
         L.lns_train_step_clip_workspace_bytes.argtypes = [vp, i, i, i, i, c.POINTER(c.c_size_t)]
         L.lns_train_step_clip.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, c.c_float, vp, vp, vp, up, vp, vp, vp, c.c_size_t, vp]
+    if hasattr(L, "lns_fit_step"):
+        ip, dp = c.POINTER(c.c_int), c.POINTER(c.c_double)
+        L.lns_train_backward_ex.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, c.c_size_t, vp, vp]
+        L.lns_loss_obs_mse_scratch_bytes.argtypes = [i, i, c.POINTER(c.c_size_t)]
+        L.lns_loss_obs_mse.argtypes = [vp, vp, i, i, c.c_int64, i, ip, dp, vp, vp, c.c_double, vp, vp, vp, vp, vp, c.c_size_t, vp]
+        L.lns_fit_step_workspace_bytes.argtypes = [vp, i, i, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_fit_step.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, c.POINTER(LnsFitSpec), vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                   c.c_size_t, vp]
     L.lns_build_has.argtypes = [c.c_char_p]
     L.lns_trace_enable.argtypes = [vp, i]
     L.lns_trace_count.argtypes = [vp]

@@ -3203,6 +3203,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "train_wgrad_split")) return 1;
     if (!strcmp(feature, "train_clip")) return 1;
     if (!strcmp(feature, "train_ops")) return 1;
+    if (!strcmp(feature, "latent_fit")) return 1;
     if (!strcmp(feature, "rollout_select")) return 1;
     if (!strcmp(feature, "rollout_ensemble")) return 1;
     if (!strcmp(feature, "ensemble_score")) return 1;

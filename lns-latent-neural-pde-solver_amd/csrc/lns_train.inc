@@ -19,6 +19,8 @@
 //   m = cond_conv2(emb) (GroupNorm / 1x1 convs on [B, D, 1, 1]) ; x2 = x1 + ffn(x1 (1 + m)),
 // with ce = cond_emb_proj(fourier_embedding(param)).  ce / emb / m depend on `param` only: they are computed once per
 // call, their gradients are accumulated over the steps ([B, D] per block) and pushed through the vector network once.
+// lns_train_backward_ex adds the state-only adjoint (no parameter gradient at all) and the gradient w.r.t. `param`; the
+// latent fit built on them (observation loss, lns_fit_step) is at the end of this file.
 // ---------------------------------------------------------------------------------------------------------------------
 #include "lns_train_kernels.h"
 
@@ -473,24 +475,32 @@ int lns_train_forward(lns_engine* e, const float* const* params, const float* z_
     return LNS_OK;
 }
 
-int lns_train_backward(lns_engine* e, const float* const* params, const float* z_in, const float* z_pred, const float* grad_z_pred,
-                       int B, int H, int Wd, int T, float* const* grads, float* grad_z_in, void* ws, size_t ws_bytes, void* stream) {
-    if (!e || !params || !z_in || !z_pred || !grad_z_pred || !grads || B <= 0 || T <= 0) return LNS_EINVAL;
+// grads == null: the state-only adjoint -- every launch below that only produces a parameter gradient is left out (so),
+// the data path is the same kernels in the same order.  grad_param: d loss / d param of the conditional propagator.
+int lns_train_backward_ex(lns_engine* e, const float* const* params, const float* z_in, const float* z_pred, const float* grad_z_pred,
+                          int B, int H, int Wd, int T, float* const* grads, float* grad_z_in, void* ws, size_t ws_bytes, void* stream,
+                          float* grad_param) {
+    if (!e || !params || !z_in || !z_pred || !grad_z_pred || B <= 0 || T <= 0) return LNS_EINVAL;
     if (int brc = check_batch(e, B)) return brc;
+    if (grad_param && e->cfg.prop_kind != LNS_PROP_CONDITIONAL) { e->err = "training rollout: grad_param needs the conditional propagator"; return LNS_EINVAL; }
+    const bool so = grads == nullptr;
     int device = -1, rc;
     if ((rc = train_device_of(e, z_in, &device)) || (rc = train_same_device(e, device, z_pred, "z_pred")) ||
         (rc = train_same_device(e, device, grad_z_pred, "grad_z_pred")) || (rc = train_same_device(e, device, ws, "the workspace")) ||
-        (rc = train_same_device(e, device, grad_z_in, "grad_z_in"))) return rc;
+        (rc = train_same_device(e, device, grad_z_in, "grad_z_in")) || (rc = train_same_device(e, device, grad_param, "grad_param"))) return rc;
     DeviceGuard dg(device);
     TrainPlan* pl;
     if ((rc = get_train_plan(e, device, B, H, Wd, &pl))) return rc;
     const TrainPlan& p = *pl;
     TrainLayout L;
-    train_layout(p, T, L, e->opt_train_wgrad);
+    // the partial-sum area of the batch-parallel weight gradient is appended to the layout: without weight gradients a
+    // workspace sized under either "train_wgrad" value covers what is used
+    const int wgrad_form = so ? 0 : e->opt_train_wgrad;
+    train_layout(p, T, L, wgrad_form);
     if (!ws || ws_bytes < L.total * 4) { e->err = fmt("training workspace too small: need %zu bytes", L.total * 4); return LNS_ENOMEM; }
     const PropParams* ppp;
     if ((rc = prop_params(e, &ppp)) || (rc = check_params(e, *ppp, params, "parameter")) ||
-        (rc = check_params(e, *ppp, const_cast<const float* const*>(grads), "gradient"))) return rc;
+        (!so && (rc = check_params(e, *ppp, const_cast<const float* const*>(grads), "gradient")))) return rc;
     const PropParams& pp = *ppp;
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* W = static_cast<float*>(ws);
@@ -502,7 +512,7 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
     float* dz = dD + np;                 // [B][c][HW] gradient w.r.t. the step's output (contiguous)
     float* dz2 = dz + nlp;
     float* part = dz2 + nlp;             // [B][D][2]
-    float* wgp = e->opt_train_wgrad == 1 ? W + L.wg_part : nullptr;      // batch-parallel weight gradient: its partial sums
+    float* wgp = wgrad_form == 1 ? W + L.wg_part : nullptr;      // batch-parallel weight gradient: its partial sums
     const long nbs = (long)p.D * HW;     // sample stride of the D-channel tensors
     const int Bn = p.B, BD = p.B * p.D;
     for (int t = T - 1; t >= 0; --t) {
@@ -515,14 +525,14 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
         // ---- out_proj: z = conv1(nO) + b ; nO = GN32(xL)
         float* stO = tp + L.off_stats + (size_t)p.nb * L.st_blk;
         const float* xL = p.nb ? tp + L.off_blk + (size_t)(p.nb - 1) * L.blk_stride + TB_X2 * (L.blk_stride / TB_COUNT) : tp + L.off_x0;
-        HIPCHK(e, launch_bias_grad(dz, Bn, p.c, (int)HW, grads[pp.out_b], acc, s));
-        if ((rc = run_wgrad(e, p.out_proj, p, dz, tp + L.off_nO, nbs, grads[pp.out_w], acc, wgp, s))) return rc;
+        if (!so) HIPCHK(e, launch_bias_grad(dz, Bn, p.c, (int)HW, grads[pp.out_b], acc, s));
+        if (!so && (rc = run_wgrad(e, p.out_proj, p, dz, tp + L.off_nO, nbs, grads[pp.out_w], acc, wgp, s))) return rc;
         if ((rc = run_tconv(e, p.out_proj_T, dz, W + L.pk_outT, nullptr, dA, nullptr, s))) return rc;        // d nO
         {
             GnTrainArgs g = gn_args(p, 32, 1e-6f, xL, nullptr, stO, params[pp.out_g], params[pp.out_be]);
             g.dy = dA; g.dx = dB; g.add = nullptr; g.part = part;
             HIPCHK(e, launch_gn_train_bwd(g, s));
-            HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[pp.out_g], grads[pp.out_be], acc, s));
+            if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[pp.out_g], grads[pp.out_be], acc, s));
         }
         float* dx = dB;                    // gradient w.r.t. the current block's output x2
         float* f1 = dA; float* f2 = dC; float* f3 = dD;     // free scratch tensors
@@ -533,24 +543,24 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
             float* st = tp + L.off_stats + (size_t)i * L.st_blk;
             const float* xin = i == 0 ? tp + L.off_x0 : tp + L.off_blk + (size_t)(i - 1) * L.blk_stride + TB_X2 * ts;
             // x2 = x1 + ffn.3(g): d w(f3), d g
-            if ((rc = run_wgrad(e, p.c_1, p, dx, tb + TB_G * ts, nbs, grads[b.f3w], acc, wgp, s))) return rc;
+            if (!so && (rc = run_wgrad(e, p.c_1, p, dx, tb + TB_G * ts, nbs, grads[b.f3w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_1, dx, W + L.pk_f3T[i], nullptr, f1, nullptr, s))) return rc;           // d g
             HIPCHK(e, launch_gelu_bwd(f1, tb + TB_V * ts, f2, n, s));                                            // d v
-            if ((rc = run_wgrad(e, p.c_1, p, f2, tb + TB_N2 * ts, nbs, grads[b.f1w], acc, wgp, s))) return rc;
+            if (!so && (rc = run_wgrad(e, p.c_1, p, f2, tb + TB_N2 * ts, nbs, grads[b.f1w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_1, f2, W + L.pk_f1T[i], nullptr, f1, nullptr, s))) return rc;           // d n2
             float* dx1;                                                                                          // gradient w.r.t. x1
             if (!p.cond) {
                 GnTrainArgs g = gn_args(p, 1, 1e-5f, tb + TB_X1 * ts, nullptr, st + L.st_blk / 3, params[b.g2], params[b.b2]);
                 g.dy = f1; g.dx = f3; g.add = dx; g.part = part;                                                 // d x1 = d x2 + GN path
                 HIPCHK(e, launch_gn_train_bwd(g, s));
-                HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.g2], grads[b.b2], acc, s));
+                if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.g2], grads[b.b2], acc, s));
                 dx1 = f3;
             } else {
                 // ffn input was xm = x1 (1 + m): d xm through the GroupNorm, then d m += <d xm, x1>, d x1 = d x2 + d xm (1 + m)
                 GnTrainArgs g = gn_args(p, 1, 1e-5f, tb + TB_XM * ts, nullptr, st + L.st_blk / 3, params[b.g2], params[b.b2]);
                 g.dy = f1; g.dx = f3; g.add = nullptr; g.part = part;
                 HIPCHK(e, launch_gn_train_bwd(g, s));
-                HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.g2], grads[b.b2], acc, s));
+                if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.g2], grads[b.b2], acc, s));
                 HIPCHK(e, launch_chan_dot(f3, tb + TB_X1 * ts, vv.blk(L, W, i, TV_DM, p.B, p.D), BD, (int)HW, acc, s));
                 HIPCHK(e, launch_chan_scale(f3, vv.blk(L, W, i, TV_M, p.B, p.D), dx, f1, BD, (int)HW, s));
                 dx1 = f1;
@@ -558,8 +568,8 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
             float* g1 = dx1 == f3 ? f1 : f3;           // two scratch tensors besides dx1 (dx is free from here on)
             float* g2 = f2;
             // x1 = x + conv.5 / cond_conv1.2 (a2)
-            HIPCHK(e, launch_bias_grad(dx1, Bn, p.D, (int)HW, grads[b.c5b], acc, s));
-            if ((rc = run_wgrad(e, p.c_d1, p, dx1, tb + TB_A2 * ts, nbs, grads[b.c5w], acc, wgp, s))) return rc;
+            if (!so) HIPCHK(e, launch_bias_grad(dx1, Bn, p.D, (int)HW, grads[b.c5b], acc, s));
+            if (!so && (rc = run_wgrad(e, p.c_d1, p, dx1, tb + TB_A2 * ts, nbs, grads[b.c5w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_d1, dx1, W + L.pk_c5T[i], nullptr, g1, nullptr, s))) return rc;         // d a2
             if (!p.cond) {
                 HIPCHK(e, launch_gelu_bwd(g1, tb + TB_U2 * ts, g2, n, s));                                        // d u2
@@ -568,44 +578,47 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
                 GnTrainArgs g = gn_args(p, 1, 1e-5f, tb + TB_U2 * ts, nullptr, st + 2 * (L.st_blk / 3), params[b.cg], params[b.cb]);
                 g.dy = g2; g.dx = g1; g.add = nullptr; g.part = part;                                            // d h
                 HIPCHK(e, launch_gn_train_bwd(g, s));
-                HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.cg], grads[b.cb], acc, s));
+                if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.cg], grads[b.cb], acc, s));
                 HIPCHK(e, launch_chan_dot(g1, nullptr, vv.blk(L, W, i, TV_DEMB, p.B, p.D), BD, (int)HW, acc, s));   // h = .. + emb
                 std::swap(g1, g2);                                                                               // d h is in g2 now
             }
-            HIPCHK(e, launch_bias_grad(g2, Bn, p.D, (int)HW, grads[b.c3b], acc, s));
-            if ((rc = run_wgrad(e, p.c_dd, p, g2, tb + TB_A1 * ts, nbs, grads[b.c3w], acc, wgp, s))) return rc;
+            if (!so) HIPCHK(e, launch_bias_grad(g2, Bn, p.D, (int)HW, grads[b.c3b], acc, s));
+            if (!so && (rc = run_wgrad(e, p.c_dd, p, g2, tb + TB_A1 * ts, nbs, grads[b.c3w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_dd, g2, W + L.pk_c3T[i], nullptr, g1, nullptr, s))) return rc;          // d a1
             HIPCHK(e, launch_gelu_bwd(g1, tb + TB_U1 * ts, g2, n, s));                                            // d u1
-            HIPCHK(e, launch_bias_grad(g2, Bn, p.D, (int)HW, grads[b.c1b], acc, s));
-            if ((rc = run_wgrad(e, p.c_d1, p, g2, tb + TB_N1 * ts, nbs, grads[b.c1w], acc, wgp, s))) return rc;
+            if (!so) HIPCHK(e, launch_bias_grad(g2, Bn, p.D, (int)HW, grads[b.c1b], acc, s));
+            if (!so && (rc = run_wgrad(e, p.c_d1, p, g2, tb + TB_N1 * ts, nbs, grads[b.c1w], acc, wgp, s))) return rc;
             if ((rc = run_tconv(e, p.c_d1, g2, W + L.pk_c1T[i], nullptr, g1, nullptr, s))) return rc;          // d n1
             {
                 GnTrainArgs g = gn_args(p, 1, 1e-5f, xin, nullptr, st, params[b.g1], params[b.b1]);
                 g.dy = g1; g.dx = dx; g.add = dx1; g.part = part;                                                // d x = d x1 + GN path
                 HIPCHK(e, launch_gn_train_bwd(g, s));
-                HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.g1], grads[b.b1], acc, s));
+                if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.g1], grads[b.b1], acc, s));
             }
         }
         // ---- in_proj: x0 = conv1(z_in) + b
         const float* zin = t == 0 ? z_in : z_pred + (size_t)(t - 1) * p.c * HW;
-        HIPCHK(e, launch_bias_grad(dx, Bn, p.D, (int)HW, grads[pp.in_b], acc, s));
+        if (!so) HIPCHK(e, launch_bias_grad(dx, Bn, p.D, (int)HW, grads[pp.in_b], acc, s));
         {
             // the weight-gradient kernel reads x with a plain [B][Cin][HW] layout: step t > 0 reads z_pred through its
             // T-strided batch axis, so it is copied to a contiguous buffer first (small: B x c x HW)
             // (the batch-parallel form takes a batch stride and reads z_pred in place)
             const float* zc = zin;
             long zbs = t == 0 ? (long)p.c * HW : (long)T * p.c * HW;
-            if (t > 0 && !wgp) {
+            if (t > 0 && !wgp && !so) {                          // (state-only: nothing reads the copy)
                 HIPCHK(e, launch_add_rows(zin, (long)T * p.c * HW, nullptr, 0, dz, (long)p.c * HW, Bn, (long)(p.c * HW), s));
                 zc = dz; zbs = (long)p.c * HW;
             }
-            if ((rc = run_wgrad(e, p.in_proj, p, dx, zc, zbs, grads[pp.in_w], acc, wgp, s))) return rc;
+            if (!so && (rc = run_wgrad(e, p.in_proj, p, dx, zc, zbs, grads[pp.in_w], acc, wgp, s))) return rc;
         }
         float* dzin = t == 0 ? (grad_z_in ? grad_z_in : dz2) : dz2;
         if ((rc = run_tconv(e, p.in_proj_T, dx, W + L.pk_inT, nullptr, dzin, nullptr, s))) return rc;            // d z_{t-1}
     }
-    if (p.cond) {
-        // the vector network, once: accumulated d m / d emb of every block -> cond_conv2, cond_emb, cond_emb_proj
+    if (p.cond && (!so || grad_param)) {
+        // the vector network, once: accumulated d m / d emb of every block -> cond_conv2, cond_emb, cond_emb_proj.
+        // G(i): the parameter-gradient output of a vector kernel, null in the state-only adjoint (the kernel then leaves
+        // that output out: nothing is written, there is no sink buffer)
+        auto G = [&](int i) -> float* { return so ? nullptr : grads[i]; };
         const int E = p.E, D = p.D;
         for (int i = 0; i < p.nb; ++i) {
             const PropParams::Blk& b = pp.blk[i];
@@ -613,20 +626,29 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
             float* dm = vv.blk(L, W, i, TV_DM, Bn, D);
             float* demb = vv.blk(L, W, i, TV_DEMB, Bn, D);
             // m = W3 c1g + b3 ; c1g = GELU(c1) ; c1 = W1 vg + b1 ; vg = GN(emb)
-            HIPCHK(e, launch_vec_linear_bwd(dm, vv.blk(L, W, i, TV_C1G, Bn, D), params[b.v3w], vv.t1, 0, grads[b.v3w], grads[b.v3b], 0, Bn, D, D, s));
+            HIPCHK(e, launch_vec_linear_bwd(dm, vv.blk(L, W, i, TV_C1G, Bn, D), params[b.v3w], vv.t1, 0, G(b.v3w), G(b.v3b), 0, Bn, D, D, s));
             HIPCHK(e, launch_vec_gelu(vv.blk(L, W, i, TV_C1, Bn, D), vv.t1, vv.t2, Bn * D, s));
-            HIPCHK(e, launch_vec_linear_bwd(vv.t2, vv.blk(L, W, i, TV_VG, Bn, D), params[b.v1w], vv.t1, 0, grads[b.v1w], grads[b.v1b], 0, Bn, D, D, s));
-            HIPCHK(e, launch_vec_gn(vv.blk(L, W, i, TV_EMB, Bn, D), params[b.vg], params[b.vb], nullptr, nullptr, vv.t1, vv.t2, grads[b.vg], grads[b.vb], 0, Bn, D, 1e-5f, s));
+            HIPCHK(e, launch_vec_linear_bwd(vv.t2, vv.blk(L, W, i, TV_VG, Bn, D), params[b.v1w], vv.t1, 0, G(b.v1w), G(b.v1b), 0, Bn, D, D, s));
+            HIPCHK(e, launch_vec_gn(vv.blk(L, W, i, TV_EMB, Bn, D), params[b.vg], params[b.vb], nullptr, nullptr, vv.t1, vv.t2, G(b.vg), G(b.vb), 0, Bn, D, 1e-5f, s));
             HIPCHK(e, launch_add(vv.t2, demb, vv.t3, (long)Bn * D, s));                                          // d emb, both paths
             // emb = Wce ce + bce : d ce accumulates over the blocks
-            HIPCHK(e, launch_vec_linear_bwd(vv.t3, vv.ce, params[b.ce_w], vv.dce, i > 0 ? 1 : 0, grads[b.ce_w], grads[b.ce_b], 0, Bn, E, D, s));
+            HIPCHK(e, launch_vec_linear_bwd(vv.t3, vv.ce, params[b.ce_w], vv.dce, i > 0 ? 1 : 0, G(b.ce_w), G(b.ce_b), 0, Bn, E, D, s));
         }
         // ce = W2 GELU(l0) + b2 ; l0 = W0 fe + b0
-        HIPCHK(e, launch_vec_linear_bwd(vv.dce, vv.l0g, params[pp.m2w], vv.t1, 0, grads[pp.m2w], grads[pp.m2b], 0, Bn, E, E, s));
+        HIPCHK(e, launch_vec_linear_bwd(vv.dce, vv.l0g, params[pp.m2w], vv.t1, 0, G(pp.m2w), G(pp.m2b), 0, Bn, E, E, s));
         HIPCHK(e, launch_vec_gelu(vv.l0, vv.t1, vv.t2, Bn * E, s));
-        HIPCHK(e, launch_vec_linear_bwd(vv.t2, vv.fe, params[pp.m0w], nullptr, 0, grads[pp.m0w], grads[pp.m0b], 0, Bn, E, E, s));
+        // l0 = W0 fe + b0: d fe only when d param is asked for, into vv.t1 (free: vec_gelu above was its last reader)
+        HIPCHK(e, launch_vec_linear_bwd(vv.t2, vv.fe, params[pp.m0w], grad_param ? vv.t1 : nullptr, 0, G(pp.m0w), G(pp.m0b), 0, Bn, E, E, s));
+        // fe = [cos(param f_k) | sin(param f_k)]: the forward's fe is the derivative's sin / cos
+        if (grad_param) HIPCHK(e, launch_vec_fourier_bwd(vv.fe, vv.t1, grad_param, Bn, E, s));
     }
     return LNS_OK;
+}
+
+int lns_train_backward(lns_engine* e, const float* const* params, const float* z_in, const float* z_pred, const float* grad_z_pred,
+                       int B, int H, int Wd, int T, float* const* grads, float* grad_z_in, void* ws, size_t ws_bytes, void* stream) {
+    if (e && !grads) return LNS_EINVAL;              // the state-only adjoint is lns_train_backward_ex's
+    return lns_train_backward_ex(e, params, z_in, z_pred, grad_z_pred, B, H, Wd, T, grads, grad_z_in, ws, ws_bytes, stream, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1060,5 +1082,176 @@ int lns_op_bias_grad(const float* dy, int B, int C, int HW, float* db, int accum
     hipStream_t s = static_cast<hipStream_t>(stream);
     OPCHK(launch_bias_grad(dy, B, C, HW, db, accumulate, s));
     OPCHK(hipStreamSynchronize(s));
+    return LNS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Latent fit (include/lns.h "latent fit"): the observation loss of a rollout, and one iteration of fitting the initial
+// latent and / or `param` to observed latents -- training forward, observation loss, state-only adjoint, Adam on z0 / param.
+// No reference counterpart (the reference never differentiates with respect to its inputs).  Every argument check is
+// host-only and precedes the first HIP call.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(LNS_OBS_MAX == OBS_MAX, "include/lns.h and lns_train_kernels.h name the same table length");
+
+// the observation table -> the kernels' argument; T < 0: the steps only have to ascend
+int obs_table(int n_obs, const int* steps, const double* weight, int T, int64_t n, double lambda, bool has_bg, ObsTable& tb, std::string& err) {
+    if (n_obs < 1 || n_obs > OBS_MAX) { err = fmt("obs loss: n_obs must be in 1 .. %d, got %d", OBS_MAX, n_obs); return LNS_EINVAL; }
+    if (!steps) { err = "obs loss: obs_steps is null"; return LNS_EINVAL; }
+    if (n < 1 || n >= (int64_t)1 << 31) { err = "obs loss: n (elements of a latent) must be in 1 .. 2^31 - 1"; return LNS_EINVAL; }
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) { err = "obs loss: background must be finite and >= 0"; return LNS_EINVAL; }
+    memset(&tb, 0, sizeof tb);
+    tb.n_obs = n_obs; tb.has_bg = has_bg ? 1 : 0;
+    tb.inv_n = 1.0 / (double)n; tb.lambda = lambda;
+    tb.coef_bg = (float)(2.0 * lambda / (double)n);
+    for (int k = 0; k < n_obs; ++k) {
+        if (steps[k] < 0 || steps[k] >= (1 << 24) || (T >= 0 && steps[k] >= T) || (k > 0 && steps[k] <= steps[k - 1])) {
+            err = fmt("obs loss: obs_steps must be strictly ascending 0-based steps%s (entry %d is %d)", T >= 0 ? " below T" : "", k, steps[k]);
+            return LNS_EINVAL;
+        }
+        const double w = weight ? weight[k] : 1.0;
+        if (!(w >= 0.0) || !std::isfinite(w)) { err = fmt("obs loss: obs_weight must be finite and >= 0 (entry %d)", k); return LNS_EINVAL; }
+        tb.steps[k] = steps[k]; tb.weight[k] = w;
+        tb.coef[k] = (float)(2.0 * w / (double)n);                  // rounded once from double
+    }
+    return LNS_OK;
+}
+
+size_t obs_part_bytes(int B, int n_obs) { return round256((size_t)B * (size_t)(n_obs + 1) * 8); }
+
+// workspace of the fit step (bytes): lns_train_step's layout for T steps | double partials | gradient of the background term
+struct FitLayout { StepLayout S; size_t part = 0, gbg = 0, total = 0; };
+int fit_layout(lns_engine* e, int B, int H, int W, int T, int n_obs, FitLayout& F) {
+    if (int rc = step_layout(e, B, H, W, T, F.S)) return rc;
+    F.part = F.S.total;
+    F.gbg = F.part + obs_part_bytes(B, n_obs);
+    F.total = F.gbg + round256(F.S.n / (size_t)T * 4);
+    return LNS_OK;
+}
+
+// an update spec of the fit: lns_update_spec's checks, and neither flags nor clipping (there is no norm pass in the step)
+int fit_update(const lns_update_spec* sp, const char* which, UpdatePlan& u, std::string& err) {
+    std::string inner;
+    if (int rc = update_scalars(sp, u, inner)) { err = fmt("fit step: %s: %s", which, inner.c_str()); return rc; }
+    if (sp->flags != 0) { err = fmt("fit step: %s.flags must be 0", which); return LNS_EINVAL; }
+    if (sp->max_norm != 0.0) { err = fmt("fit step: %s.max_norm must be 0 (no clipping inside the fit step)", which); return LNS_EINVAL; }
+    return LNS_OK;
+}
+
+}  // namespace
+
+int lns_loss_obs_mse_scratch_bytes(int B, int n_obs, size_t* bytes) {
+    std::string& err = g_create_error;
+    if (!bytes) { err = "obs loss: bytes is null"; return LNS_EINVAL; }
+    if (B < 1 || B > LNS_MAX_BATCH) { err = fmt("obs loss: B must be in 1 .. %d", LNS_MAX_BATCH); return LNS_EINVAL; }
+    if (n_obs < 1 || n_obs > OBS_MAX) { err = fmt("obs loss: n_obs must be in 1 .. %d, got %d", OBS_MAX, n_obs); return LNS_EINVAL; }
+    *bytes = obs_part_bytes(B, n_obs);
+    return LNS_OK;
+}
+
+int lns_loss_obs_mse(const float* z_pred, const float* obs, int B, int T, int64_t n, int n_obs, const int* obs_steps,
+                     const double* obs_weight, const float* z0, const float* z_background, double background, float* per,
+                     float* loss, float* grad_z_pred, float* grad_z0_bg, void* scratch, size_t scratch_bytes, void* stream) {
+    std::string& err = g_create_error;
+    if (!z_pred || !obs) { err = "obs loss: z_pred / obs is null"; return LNS_EINVAL; }
+    if (!loss || !grad_z_pred) { err = "obs loss: loss / grad_z_pred is null"; return LNS_EINVAL; }
+    if (B < 1 || B > LNS_MAX_BATCH) { err = fmt("obs loss: B must be in 1 .. %d", LNS_MAX_BATCH); return LNS_EINVAL; }
+    if (T < 1) { err = "obs loss: T must be >= 1"; return LNS_EINVAL; }
+    if ((z0 == nullptr) != (z_background == nullptr)) { err = "obs loss: z0 and z_background come together (the background term) or not at all"; return LNS_EINVAL; }
+    const bool has_bg = z0 != nullptr;
+    if (!has_bg && background > 0.0) { err = "obs loss: background > 0 needs z0 and z_background"; return LNS_EINVAL; }
+    if (!has_bg && grad_z0_bg) { err = "obs loss: grad_z0_bg needs z0 and z_background"; return LNS_EINVAL; }
+    ObsTable tb;
+    if (int rc = obs_table(n_obs, obs_steps, obs_weight, T, n, background, has_bg, tb, err)) return rc;
+    const size_t need = obs_part_bytes(B, n_obs);
+    if (!scratch || scratch_bytes < need) { err = fmt("obs loss: scratch must hold %zu bytes", need); return LNS_ENOMEM; }
+    const hipError_t rc = launch_obs_mse(tb, z_pred, obs, z0, z_background, B, T, (long)n, per, loss, grad_z_pred, grad_z0_bg,
+                                         static_cast<double*>(scratch), static_cast<hipStream_t>(stream));
+    if (rc != hipSuccess) { err = std::string("obs loss: ") + hipGetErrorString(rc); return LNS_EHIP; }
+    return LNS_OK;
+}
+
+int lns_fit_step_workspace_bytes(lns_engine* e, int B, int H, int W, int T, int n_obs, size_t* bytes) {
+    if (!e) return LNS_EINVAL;
+    if (B < 1) { e->err = "fit step: B must be >= 1"; return LNS_EINVAL; }
+    if (T < 1) { e->err = "fit step: T must be >= 1"; return LNS_EINVAL; }
+    if (n_obs < 1 || n_obs > OBS_MAX) { e->err = fmt("fit step: n_obs must be in 1 .. %d, got %d", OBS_MAX, n_obs); return LNS_EINVAL; }
+    if (!bytes) { e->err = "fit step: bytes is null"; return LNS_EINVAL; }
+    if (e->cfg.prop_kind != LNS_PROP_PLAIN && e->cfg.prop_kind != LNS_PROP_CONDITIONAL) { e->err = "fit step: engine has no propagator"; return LNS_ESTATE; }
+    if (int brc = check_batch(e, B)) return brc;
+    FitLayout F; int rc;
+    if ((rc = fit_layout(e, B, H, W, T, n_obs, F))) return rc;
+    *bytes = F.total;
+    size_t tb = 0;                       // build the plan now when a device is there, as lns_train_workspace_bytes does
+    return lns_train_workspace_bytes(e, B, H, W, T, &tb);
+}
+
+int lns_fit_step(lns_engine* e, const float* const* params, float* z0, float* param, const float* obs, const float* z_background,
+                 int B, int H, int W, const lns_fit_spec* spec, float* g_z, float* exp_avg_z, float* exp_avg_sq_z, float* g_p,
+                 float* exp_avg_p, float* exp_avg_sq_p, float* loss, float* per, void* ws, size_t ws_bytes, void* stream) {
+    if (!e) return LNS_EINVAL;
+    // ---- host-only checks ----
+    const bool cond = e->cfg.prop_kind == LNS_PROP_CONDITIONAL;
+    if (e->cfg.prop_kind != LNS_PROP_PLAIN && !cond) { e->err = "fit step: engine has no propagator"; return LNS_ESTATE; }
+    if (!spec || spec->size != sizeof(lns_fit_spec)) { e->err = "fit step: spec is null or its size field is not sizeof(lns_fit_spec)"; return LNS_EINVAL; }
+    if ((spec->flags & ~(LNS_FIT_STATE | LNS_FIT_PARAM)) || !(spec->flags & (LNS_FIT_STATE | LNS_FIT_PARAM))) {
+        e->err = fmt("fit step: flags 0x%x: LNS_FIT_STATE and / or LNS_FIT_PARAM, nothing else", spec->flags); return LNS_EINVAL;
+    }
+    const bool fit_z = spec->flags & LNS_FIT_STATE, fit_p = spec->flags & LNS_FIT_PARAM;
+    if (fit_p && !cond) { e->err = "fit step: flags: LNS_FIT_PARAM needs the conditional propagator"; return LNS_EINVAL; }
+    if (B < 1) { e->err = "fit step: B must be >= 1"; return LNS_EINVAL; }
+    if (int brc = check_batch(e, B)) return brc;
+    if (!params) { e->err = "fit step: params array is null"; return LNS_EINVAL; }
+    if (!z0 || !obs) { e->err = "fit step: z0 / obs is null"; return LNS_EINVAL; }
+    if (cond && !param) { e->err = "fit step: conditional propagator needs param"; return LNS_EINVAL; }
+    if (!loss) { e->err = "fit step: loss is null"; return LNS_EINVAL; }
+    if (fit_z && (!g_z || !exp_avg_z || !exp_avg_sq_z)) { e->err = "fit step: LNS_FIT_STATE needs g_z, exp_avg_z and exp_avg_sq_z"; return LNS_EINVAL; }
+    if (fit_p && (!g_p || !exp_avg_p || !exp_avg_sq_p)) { e->err = "fit step: LNS_FIT_PARAM needs g_p, exp_avg_p and exp_avg_sq_p"; return LNS_EINVAL; }
+    int rc;
+    TrainPlan dims;
+    if ((rc = train_plan_dims(e, B, H, W, dims))) return rc;
+    const int64_t n = (int64_t)dims.c * H * W;
+    if ((int64_t)B * n >= (int64_t)1 << 31) { e->err = "fit step: z0 has 2^31 or more elements"; return LNS_EINVAL; }
+    const bool has_bg = z_background != nullptr;
+    if (!has_bg && spec->background > 0.0) { e->err = "fit step: background > 0 needs z_background"; return LNS_EINVAL; }
+    ObsTable tb;
+    if ((rc = obs_table(spec->n_obs, spec->obs_steps, spec->obs_weight, -1, n, spec->background, has_bg, tb, e->err))) return rc;
+    const int T = spec->obs_steps[spec->n_obs - 1] + 1;
+    UpdatePlan uz, up;
+    if (fit_z && (rc = fit_update(&spec->state, "state", uz, e->err))) return rc;
+    if (fit_p && (rc = fit_update(&spec->param, "param", up, e->err))) return rc;
+    const PropParams* pp;
+    if ((rc = prop_params(e, &pp)) || (rc = check_params(e, *pp, params, "parameter"))) return rc;
+    FitLayout F;
+    if ((rc = fit_layout(e, B, H, W, T, spec->n_obs, F))) return rc;
+    if (!ws || ws_bytes < F.total) { e->err = fmt("fit step workspace too small: need %zu bytes", F.total); return LNS_ENOMEM; }
+    // ---- where the tensors live (pointer attributes: the first HIP calls), still before anything is enqueued ----
+    int device = -1;
+    if ((rc = train_device_of(e, z0, &device)) || (rc = train_same_device(e, device, obs, "obs")) ||
+        (rc = train_same_device(e, device, z_background, "z_background")) || (rc = train_same_device(e, device, loss, "loss")) ||
+        (rc = train_same_device(e, device, per, "per")) || (rc = train_same_device(e, device, ws, "the workspace")) ||
+        (rc = train_same_device(e, device, g_z, "g_z")) || (rc = train_same_device(e, device, g_p, "g_p"))) return rc;
+    // ---- device work, in stream order ----
+    char* base = static_cast<char*>(ws);
+    float* z_pred = reinterpret_cast<float*>(base + F.S.z_pred);
+    float* dz = reinterpret_cast<float*>(base + F.S.dz);
+    double* part = reinterpret_cast<double*>(base + F.part);
+    float* gbg = fit_z && has_bg ? reinterpret_cast<float*>(base + F.gbg) : nullptr;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if ((rc = lns_train_forward(e, params, z0, param, B, H, W, T, z_pred, ws, F.S.train, stream))) return rc;
+    DeviceGuard dg(device);
+    HIPCHK(e, launch_obs_mse(tb, z_pred, obs, has_bg ? z0 : nullptr, z_background, B, T, (long)n, per, loss, dz, gbg, part, s));
+    if ((rc = lns_train_backward_ex(e, params, z0, z_pred, dz, B, H, W, T, nullptr, fit_z ? g_z : nullptr, ws, F.S.train, stream,
+                                    fit_p ? g_p : nullptr))) return rc;
+    if (gbg) HIPCHK(e, launch_add(g_z, gbg, g_z, (long)((int64_t)B * n), s));          // g_z = grad_z_in + grad_z0_bg, on its own
+    if (fit_z) {
+        AdamTensor t{z0, g_z, exp_avg_z, exp_avg_sq_z, (unsigned)((int64_t)B * n), 0u};
+        HIPCHK(e, launch_update_multi(&t, 1, uz.sc, nullptr, uz.decoupled, uz.decay, s));
+    }
+    if (fit_p) {
+        AdamTensor t{param, g_p, exp_avg_p, exp_avg_sq_p, (unsigned)B, 0u};
+        HIPCHK(e, launch_update_multi(&t, 1, up.sc, nullptr, up.decoupled, up.decay, s));
+    }
     return LNS_OK;
 }

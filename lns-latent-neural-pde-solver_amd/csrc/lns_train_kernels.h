@@ -53,11 +53,32 @@ hipError_t launch_chan_dot(const float* a, const float* b2, float* out, int BC, 
 hipError_t launch_chan_scale(const float* x, const float* m, const float* add, float* y, int BC, int HW, hipStream_t s);
 hipError_t launch_vec_fourier(const float* param, float* out, int B, int E, hipStream_t s);
 hipError_t launch_vec_linear_fwd(const float* x, const float* W, const float* bias, float* y, int B, int I, int O, hipStream_t s);
+// dx, dW, db: each nullable (a null output is not computed)
 hipError_t launch_vec_linear_bwd(const float* dy, const float* x, const float* W, float* dx, int dx_acc, float* dW, float* db, int p_acc,
                                  int B, int I, int O, hipStream_t s);
 hipError_t launch_vec_gelu(const float* u, const float* dy, float* out, int n, hipStream_t s);
 hipError_t launch_vec_gn(const float* x, const float* gamma, const float* beta, float* y, float* stats, const float* dy, float* dx,
                          float* dgamma, float* dbeta, int p_acc, int B, int D, float eps, hipStream_t s);
+// (backward: dgamma / dbeta null = the state-only adjoint, dx alone)
+
+// ---- latent fit (latent_fit.inc) ---------------------------------------------------------------------------------------
+// d loss / d param of the conditional propagator from d fe [B][E] and the forward's fe = [cos | sin] (one thread per sample)
+hipError_t launch_vec_fourier_bwd(const float* fe, const float* dfe, float* grad_param, int B, int E, hipStream_t s);
+// Observation loss of a rollout, per trajectory.  The table is a kernel argument: steps ascending, coef[k] = (float)(2 w_k / n),
+// coef_bg = (float)(2 lambda / n), the weights themselves and 1 / n in double for the finishing sum.
+constexpr int OBS_MAX = 64;
+struct ObsTable {
+    int n_obs, has_bg;
+    int steps[OBS_MAX];
+    float coef[OBS_MAX];
+    float coef_bg, pad;
+    double weight[OBS_MAX];
+    double lambda, inv_n;
+};
+// z_pred [B][T][n], obs [B][n_obs][n], z0 / zb [B][n] (read when tb.has_bg) -> per [B][n_obs] (nullable), loss [B],
+// grad [B][T][n] (zeros on steps that are not observed), gbg [B][n] (nullable); part: B * (n_obs + 1) doubles.
+hipError_t launch_obs_mse(const ObsTable& tb, const float* z_pred, const float* obs, const float* z0, const float* zb, int B, int T,
+                          long n, float* per, float* loss, float* grad, float* gbg, double* part, hipStream_t s);
 
 // ---- loss and optimiser of the training step (lns_optim.inc) ----------------------------------------------------------
 // F.smooth_l1_loss(pred, target, 'mean', beta) -> *loss_out (device float) and, if grad != null, dL/dpred, in one pass.

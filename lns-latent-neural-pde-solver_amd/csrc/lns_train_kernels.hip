@@ -354,6 +354,7 @@ __global__ __launch_bounds__(256) void vec_linear_fwd_kernel(const float* x, con
     }
 }
 // dx[b][i] (+)= sum_o dy[b][o] W[o][i] ; dW[o][i] (+)= sum_b dy[b][o] x[b][i] ; db[o] (+)= sum_b dy[b][o]
+// (dx, dW, db each nullable: the state-only adjoint asks for dx alone)
 __global__ __launch_bounds__(256) void vec_linear_bwd_kernel(const float* dy, const float* x, const float* W, float* dx, int dx_acc,
                                                              float* dW, float* db, int p_acc, int B, int I, int O) {
     if (dx)
@@ -363,12 +364,13 @@ __global__ __launch_bounds__(256) void vec_linear_bwd_kernel(const float* dy, co
             for (int o = 0; o < O; ++o) s = fmaf(dy[b * O + o], W[o * I + i], s);
             dx[e] = dx_acc ? dx[e] + s : s;
         }
-    for (int e = threadIdx.x; e < O * I; e += 256) {
-        const int o = e / I, i = e - o * I;
-        float s = 0.0f;
-        for (int b = 0; b < B; ++b) s = fmaf(dy[b * O + o], x[b * I + i], s);
-        dW[e] = p_acc ? dW[e] + s : s;
-    }
+    if (dW)
+        for (int e = threadIdx.x; e < O * I; e += 256) {
+            const int o = e / I, i = e - o * I;
+            float s = 0.0f;
+            for (int b = 0; b < B; ++b) s = fmaf(dy[b * O + o], x[b * I + i], s);
+            dW[e] = p_acc ? dW[e] + s : s;
+        }
     if (db)
         for (int o = threadIdx.x; o < O; o += 256) {
             float s = 0.0f;
@@ -410,7 +412,7 @@ __global__ __launch_bounds__(256) void vec_gn_kernel(const float* x, const float
             }
         }
     }
-    if (dy) {
+    if (dy && dgamma) {                                  // dgamma null: the state-only adjoint, dx alone
         __syncthreads();
         for (int i = threadIdx.x; i < D; i += 256) {
             float sg = 0.0f, sb = 0.0f;
@@ -445,5 +447,6 @@ hipError_t launch_vec_gn(const float* x, const float* gamma, const float* beta, 
 }
 
 #include "lns_optim.inc"
+#include "latent_fit.inc"
 
 }  // namespace lns

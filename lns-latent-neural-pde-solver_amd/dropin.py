@@ -330,9 +330,9 @@ class SimpleCNNConditional(SimpleCNN):        # train_stage2_twophase_conditiona
 
 # ---------------------------------------------------------------------------
 class _LatentRolloutFn(torch.autograd.Function):
-    """z_pred = rollout(z0; propagator parameters) on the HIP engine, differentiable w.r.t. the parameters and z0
-    (include/lns.h "training rollout"; csrc/lns_train.inc).  The parameters are read from their device tensors at every
-    call, so an optimiser's in-place updates need no re-upload."""
+    """z_pred = rollout(z0; propagator parameters) on the HIP engine, differentiable w.r.t. the parameters, z0 and -- the
+    conditional model -- `param` (include/lns.h "training rollout", lns_train_backward_ex; csrc/lns_train.inc).  The
+    parameters are read from their device tensors at every call, so an optimiser's in-place updates need no re-upload."""
 
     @staticmethod
     def forward(ctx, own, names, T, z0, param, *tensors):
@@ -346,6 +346,8 @@ class _LatentRolloutFn(torch.autograd.Function):
         with torch.cuda.device(z0.device):
             z_pred, ws = eng.train_forward(params, z0.detach(), T, param=param)
         ctx.own, ctx.names, ctx.ws = own, names, ws
+        if isinstance(param, torch.Tensor):
+            ctx.param_shape, ctx.param_dtype = param.shape, param.dtype
         ctx.save_for_backward(z0, z_pred, *tensors)
         return z_pred
 
@@ -353,10 +355,16 @@ class _LatentRolloutFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         z0, z_pred, *tensors = ctx.saved_tensors
         params = {k: t.detach() for k, t in zip(ctx.names, tensors)}
+        gp = None
         with torch.cuda.device(z0.device):
-            grads, gz = ctx.own._eng.train_backward(params, z0, z_pred, grad_out.contiguous().float(), ctx.ws,
-                                                    need_z_grad=ctx.needs_input_grad[3])
-        out = [None, None, None, gz, None]
+            if ctx.needs_input_grad[4]:
+                grads, gz, gp = ctx.own._eng.train_backward(params, z0, z_pred, grad_out.contiguous().float(), ctx.ws,
+                                                            need_z_grad=ctx.needs_input_grad[3], need_param_grad=True)
+                gp = gp.reshape(ctx.param_shape).to(ctx.param_dtype)
+            else:
+                grads, gz = ctx.own._eng.train_backward(params, z0, z_pred, grad_out.contiguous().float(), ctx.ws,
+                                                        need_z_grad=ctx.needs_input_grad[3])
+        out = [None, None, None, gz, gp]
         for i, k in enumerate(ctx.names):
             out.append(grads[k] if ctx.needs_input_grad[5 + i] else None)
         return tuple(out)
@@ -419,8 +427,9 @@ class LatentDynamics(_Hosted):
         (train_stage2_ns2d.py:126-141; conditional train_stage2_twophase_conditional.py:160-175).
         With autograd enabled (training, train_stage2_ns2d.py:213-215) the rollout runs through `_LatentRolloutFn`:
         the HIP training forward keeps a tape and `loss.backward()` runs the HIP backward through time, filling `.grad`
-        of the propagator's parameters (no gradient w.r.t. `param`).  Under torch.no_grad() (validation) it is the
-        inference rollout."""
+        of the propagator's parameters -- and of `param` when it requires grad (model(z_in, z_out,
+        param.requires_grad_(), loss_fn) fills param.grad; otherwise no gradient w.r.t. it is computed).  Under
+        torch.no_grad() (validation) it is the inference rollout."""
         if torch.is_grad_enabled():
             if len(rest) != (2 if self._conditional else 1):
                 raise TypeError("forward() takes (z_in, z_out, param, loss_fn)" if self._conditional else "forward() takes (z_in, z_out, loss_fn)")
@@ -447,6 +456,44 @@ class LatentDynamics(_Hosted):
         z0 = z_in[:, 0].contiguous()
         z_pred, _ = self._engine(z0).rollout_latent(z0, z_out.shape[1], param=param, to_x=False)
         return loss_fn(z_pred, z_out)
+
+    def assimilate(self, x0, y_obs, obs_steps, *rest, iters=40, weights=None, chunk=32, **fit):
+        """assimilate(x0, y_obs, obs_steps, iters=...) -- conditional: assimilate(x0, y_obs, obs_steps, param, iters=...):
+        which initial latent makes the rollout agree with ALL the observed frames, and (conditional model) which `param`
+        explains them.  x0 [B,C,Ly,Lx]: the frame the forecast would start from -- its encoding is the start of the fit and
+        its background; y_obs [B,n_obs,C,Ly,Lx]: the frames observed at the 0-based rollout steps `obs_steps` (step 0 = one
+        propagator step after x0), encoded `chunk` frames per call as metrics.encode_dataset does.  `fit`: LatentFit's
+        arguments (lr_state, lr_param, betas, eps, background, fit_state, fit_param).  Returns fit.FitResult (z0, param,
+        loss [iters, B], per [B, n_obs]); `model._engine(z0).rollout_latent(z0, steps, param=...)` forecasts from it.
+        With a conditional ENCODER fitting `param` is refused: the encoding of the observations would depend on the
+        unknown (LatentFit.run on latents has no such limit)."""
+        from . import fit as _fit
+        from . import metrics as _metrics
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("assimilate() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if rest:
+            raise TypeError("assimilate() takes (x0, y_obs, obs_steps, param, ...)" if self._conditional
+                            else "assimilate() takes (x0, y_obs, obs_steps, ...)")
+        fitter = _fit.LatentFit(self, **fit)
+        cond_enc = bool(getattr(self.args, "cond_encoder", False))
+        if cond_enc and fitter.fit_param:
+            raise LnsError("assimilate: the encoder is conditional, so the encoding of the observations would depend on the "
+                           "param being fitted; pass fit_param=False, or fit latents with lns_amd.fit.LatentFit.run")
+        x0 = self._fields(x0)
+        if y_obs.dim() != 5 or y_obs.shape[0] != x0.shape[0] or y_obs.shape[2:] != x0.shape[1:]:
+            raise LnsError("y_obs must be [B,n_obs,C,Ly,Lx] matching x0 %s, got %s" % (tuple(x0.shape), tuple(y_obs.shape)))
+        B, n_obs = int(y_obs.shape[0]), int(y_obs.shape[1])
+        with torch.no_grad():
+            enc_p = param if cond_enc else None
+            z0 = _metrics.encode_dataset(self._ae, x0, chunk=chunk, out_device=x0.device, param=enc_p)
+            frames = y_obs.reshape((B * n_obs,) + tuple(y_obs.shape[2:]))
+            enc_po = torch.as_tensor(param).reshape(B, 1).expand(B, n_obs).reshape(-1) if cond_enc else None
+            z_obs = _metrics.encode_dataset(self._ae, frames, chunk=chunk, out_device=x0.device, param=enc_po)
+        z_obs = z_obs.reshape((B, n_obs) + tuple(z_obs.shape[1:]))
+        return fitter.run(z0, z_obs, obs_steps, param=param, weights=weights, iters=iters)
 
     @staticmethod
     def _fields(x):

@@ -131,6 +131,89 @@ def update_spec(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, max_
     return spec
 
 
+def normalize_obs(obs_steps, weights=None):
+    """(steps, weights) of an observation table as plain lists: 0-based, strictly ascending steps, 1 .. LNS_OBS_MAX of them;
+    weights finite and >= 0 (None: all 1).  The C calls check the same things; this is the early, readable refusal."""
+    import math
+    steps = [int(t) for t in obs_steps]
+    if not 1 <= len(steps) <= _lib.LNS_OBS_MAX:
+        raise LnsError("obs_steps must hold 1 .. %d steps, got %d" % (_lib.LNS_OBS_MAX, len(steps)))
+    if steps[0] < 0 or any(b <= a for a, b in zip(steps, steps[1:])):
+        raise LnsError("obs_steps must be 0-based and strictly ascending, got %s" % (steps,))
+    w = [1.0] * len(steps) if weights is None else [float(v) for v in weights]
+    if len(w) != len(steps) or any(not math.isfinite(v) or v < 0 for v in w):
+        raise LnsError("weights must be %d finite values >= 0, got %s" % (len(steps), w))
+    return steps, w
+
+
+def fit_spec(obs_steps, weights=None, background=0.0, state=None, param=None):
+    """`lns_fit_spec`: the observation table, the weight of the background term, and an update_spec(...) for each of the
+    state and `param` that is fitted (None: not fitted).  The host arrays are kept alive by the returned object."""
+    steps, w = normalize_obs(obs_steps, weights)
+    spec = _lib.LnsFitSpec()
+    spec.size = ctypes.sizeof(_lib.LnsFitSpec)
+    spec.flags = (_lib.LNS_FIT_STATE if state is not None else 0) | (_lib.LNS_FIT_PARAM if param is not None else 0)
+    spec.n_obs = len(steps)
+    spec._steps = (ctypes.c_int * len(steps))(*steps)
+    spec._weights = (ctypes.c_double * len(w))(*w)
+    spec.obs_steps = ctypes.cast(spec._steps, ctypes.POINTER(ctypes.c_int))
+    spec.obs_weight = ctypes.cast(spec._weights, ctypes.POINTER(ctypes.c_double))
+    spec.background = float(background)
+    if state is not None:
+        spec.state = state
+    if param is not None:
+        spec.param = param
+    return spec
+
+
+def obs_loss(z_pred, obs, obs_steps, weights=None, z0=None, z_background=None, background=0.0, need_per=True, need_bg_grad=None,
+             grad_out=None):
+    """Observation loss of a latent rollout and its gradient, one loss per trajectory (lns_loss_obs_mse): z_pred
+    [B,T,c,h,w] (or [B,T,n]), obs [B,n_obs,...] observed at the 0-based steps `obs_steps` with `weights`; z0 and
+    z_background [B,...] add background * mean((z0 - z_background)^2).  Returns (loss [B], per [B,n_obs] or None,
+    grad_z_pred like z_pred -- exact zeros on the steps that are not observed --, grad_z0_bg like z0 or None).
+    grad_out: a buffer for grad_z_pred (every element is written).  Bit-reproducible; never synchronises.  Module-level
+    because the op needs no engine."""
+    import torch
+    z_pred, obs = Engine._dev(z_pred), Engine._dev(obs)
+    steps, w = normalize_obs(obs_steps, weights)
+    if z_pred.dim() < 3 or obs.dim() != z_pred.dim() or obs.shape[0] != z_pred.shape[0] or obs.shape[1] != len(steps) \
+            or obs.shape[2:] != z_pred.shape[2:] or obs.device != z_pred.device:
+        raise LnsError("obs must be [B,%d,...] matching z_pred %s on its device, got %s on %s"
+                       % (len(steps), tuple(z_pred.shape), tuple(obs.shape), obs.device))
+    B, T = int(z_pred.shape[0]), int(z_pred.shape[1])
+    n = z_pred[0, 0].numel()
+    if (z0 is None) != (z_background is None):
+        raise LnsError("z0 and z_background come together (the background term) or not at all")
+    if z0 is not None:
+        z0, z_background = Engine._dev(z0), Engine._dev(z_background)
+        for t_, name in ((z0, "z0"), (z_background, "z_background")):
+            if t_.shape[0] != B or t_[0].numel() != n or t_.device != z_pred.device:
+                raise LnsError("%s must be [B,...] with %d elements per sample on z_pred's device" % (name, n))
+    if need_bg_grad is None:
+        need_bg_grad = z0 is not None
+    L = _lib.lib()
+    nb = ctypes.c_size_t(0)
+    rc = L.lns_loss_obs_mse_scratch_bytes(B, len(steps), ctypes.byref(nb))
+    if rc == 0:
+        with torch.cuda.device(z_pred.device):
+            dev = z_pred.device
+            loss = torch.empty(B, dtype=torch.float32, device=dev)
+            per = torch.empty((B, len(steps)), dtype=torch.float32, device=dev) if need_per else None
+            grad = torch.empty_like(z_pred) if grad_out is None else grad_out
+            if grad.shape != z_pred.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != dev:
+                raise LnsError("grad_out must be a contiguous fp32 tensor like z_pred")
+            gbg = torch.empty_like(z0) if need_bg_grad else None
+            scratch = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+            rc = L.lns_loss_obs_mse(z_pred.data_ptr(), obs.data_ptr(), B, T, n, len(steps), (ctypes.c_int * len(steps))(*steps),
+                                    (ctypes.c_double * len(w))(*w), Engine._ptr(z0), Engine._ptr(z_background), float(background),
+                                    Engine._ptr(per), loss.data_ptr(), grad.data_ptr(), Engine._ptr(gbg), scratch.data_ptr(),
+                                    scratch.numel(), Engine._stream(z_pred))
+    if rc != 0:
+        raise LnsError("lns_loss_obs_mse failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    return loss, per, grad, gbg
+
+
 def smooth_l1(pred, target, beta=1.0, need_grad=True, loss_out=None, grad_out=None):
     """F.smooth_l1_loss(pred, target, beta=beta) (train_stage2_ns2d.py:213) and dL/dpred in one pass on the HIP kernel
     (lns_loss_smooth_l1): returns (0-dim device tensor, gradient like pred or None).  Bit-reproducible; never
@@ -1366,20 +1449,82 @@ class Engine:
                                               ws.data_ptr(), ws.numel(), self._stream(z_in)), "lns_train_forward")
         return z_pred, ws
 
-    def train_backward(self, params, z_in, z_pred, grad_z_pred, ws, need_z_grad=False):
-        """{key: gradient tensor} of every propagator parameter (+ grad of z_in if asked) for dL/dz_pred."""
+    def train_backward(self, params, z_in, z_pred, grad_z_pred, ws, need_z_grad=False, need_param_grad=False, state_only=False):
+        """{key: gradient tensor} of every propagator parameter (+ grad of z_in if asked) for dL/dz_pred.
+        need_param_grad (conditional propagator): a third result, d loss / d param [B].  state_only: the state-only adjoint
+        (lns_train_backward_ex with no gradient array) -- no parameter gradient is computed, the first result is {}."""
         import torch
         z_in = self._dev(z_in)
         g = self._dev(grad_z_pred)
         B, T, c, h, w = z_pred.shape
         prefix = self.cfg.prop_prefix.decode()
-        grads = {k: torch.empty(tuple(shp), dtype=torch.float32, device=z_in.device)
-                 for k, shp, _ in self.params if k.startswith(prefix)}
+        grads = {} if state_only else {k: torch.empty(tuple(shp), dtype=torch.float32, device=z_in.device)
+                                       for k, shp, _ in self.params if k.startswith(prefix)}
         gz = torch.empty_like(z_in) if need_z_grad else None
-        self._check(self._L.lns_train_backward(self._h, self._ptr_array(params), z_in.data_ptr(), z_pred.data_ptr(), g.data_ptr(),
-                                               B, h, w, T, self._ptr_array(grads), gz.data_ptr() if gz is not None else None,
-                                               ws.data_ptr(), ws.numel(), self._stream(z_in)), "lns_train_backward")
-        return grads, gz
+        if not need_param_grad and not state_only:
+            self._check(self._L.lns_train_backward(self._h, self._ptr_array(params), z_in.data_ptr(), z_pred.data_ptr(), g.data_ptr(),
+                                                   B, h, w, T, self._ptr_array(grads), gz.data_ptr() if gz is not None else None,
+                                                   ws.data_ptr(), ws.numel(), self._stream(z_in)), "lns_train_backward")
+            return grads, gz
+        gp = torch.empty(B, dtype=torch.float32, device=z_in.device) if need_param_grad else None
+        self._check(self._L.lns_train_backward_ex(self._h, self._ptr_array(params), z_in.data_ptr(), z_pred.data_ptr(), g.data_ptr(),
+                                                  B, h, w, T, None if state_only else self._ptr_array(grads), self._ptr(gz),
+                                                  ws.data_ptr(), ws.numel(), self._stream(z_in), self._ptr(gp)),
+                    "lns_train_backward_ex")
+        return (grads, gz, gp) if need_param_grad else (grads, gz)
+
+    # -- latent fit (include/lns.h "latent fit") ---------------------------------------------------------------------
+    obs_loss = staticmethod(obs_loss)
+
+    def fit_step_workspace_bytes(self, B, h, w, T, n_obs):
+        """Bytes of the workspace of fit_step for T = last observed step + 1 rollout steps and n_obs observations."""
+        n = ctypes.c_size_t(0)
+        self._check(self._L.lns_fit_step_workspace_bytes(self._h, int(B), int(h), int(w), int(T), int(n_obs), ctypes.byref(n)),
+                    "lns_fit_step_workspace_bytes")
+        return int(n.value)
+
+    def fit_step(self, params, z0, obs, spec, param=None, z_background=None, g_z=None, exp_avg_z=None, exp_avg_sq_z=None, g_p=None,
+                 exp_avg_p=None, exp_avg_sq_p=None, loss=None, per=None, workspace=None):
+        """One iteration of fitting z0 [B,c,h,w] and / or param [B] to the observed latents obs [B,n_obs,c,h,w]
+        (lns_fit_step): training forward, observation loss, state-only adjoint, Adam -- z0 / param are updated IN PLACE.
+        spec: fit_spec(...).  params: {key: tensor} or the pointer array `_ptr_array` returns.  g_* / exp_avg_*: the caller's
+        gradient buffers and Adam moments of what is fitted.  Returns (loss [B] before the update, per [B,n_obs]); nothing
+        here synchronises, and with loss / per / workspace given nothing allocates."""
+        import torch
+        for t_, name in ((z0, "z0"), (param, "param")):
+            if isinstance(t_, torch.Tensor) and not t_.is_contiguous():
+                raise LnsError("fit_step updates %s in place: it must be contiguous" % name)
+        z0, obs = self._dev(z0), self._dev(obs)
+        B, c, h, w = z0.shape
+        if obs.dim() != 5 or obs.shape[0] != B or obs.shape[1] != spec.n_obs or tuple(obs.shape[2:]) != (c, h, w) or obs.device != z0.device:
+            raise LnsError("obs must be [B,%d,%d,%d,%d] on z0's device, got %s on %s" % (spec.n_obs, c, h, w, tuple(obs.shape), obs.device))
+        if param is not None:
+            param = self._dev(param)
+            if tuple(param.shape) != (B,) or param.device != z0.device:
+                raise LnsError("param must be [B] on z0's device")
+        if z_background is not None:
+            z_background = self._dev(z_background)
+            if z_background.shape != z0.shape or z_background.device != z0.device:
+                raise LnsError("z_background must match z0")
+        for t_, like, name in ((g_z, z0, "g_z"), (exp_avg_z, z0, "exp_avg_z"), (exp_avg_sq_z, z0, "exp_avg_sq_z"), (g_p, param, "g_p"),
+                               (exp_avg_p, param, "exp_avg_p"), (exp_avg_sq_p, param, "exp_avg_sq_p")):
+            if t_ is not None and (like is None or t_.shape != like.shape or t_.device != z0.device or t_.dtype != torch.float32
+                                   or not t_.is_contiguous()):
+                raise LnsError("%s must be a contiguous fp32 tensor like what it belongs to" % name)
+        T = int(spec._steps[spec.n_obs - 1]) + 1
+        with torch.cuda.device(z0.device):
+            if workspace is None:
+                workspace = torch.empty(self.fit_step_workspace_bytes(B, h, w, T, spec.n_obs), dtype=torch.uint8, device=z0.device)
+            if loss is None:
+                loss = torch.empty(B, dtype=torch.float32, device=z0.device)
+            if per is None:
+                per = torch.empty((B, spec.n_obs), dtype=torch.float32, device=z0.device)
+            self._check(self._L.lns_fit_step(self._h, self._ptr_array(params) if isinstance(params, dict) else params, z0.data_ptr(),
+                                             self._ptr(param), obs.data_ptr(), self._ptr(z_background), B, h, w, ctypes.byref(spec),
+                                             self._ptr(g_z), self._ptr(exp_avg_z), self._ptr(exp_avg_sq_z), self._ptr(g_p),
+                                             self._ptr(exp_avg_p), self._ptr(exp_avg_sq_p), loss.data_ptr(), per.data_ptr(),
+                                             workspace.data_ptr(), workspace.numel(), self._stream(z0)), "lns_fit_step")
+        return loss, per
 
     # -- device-resident training step (include/lns.h "device-resident training step") -------------------------------
     smooth_l1 = staticmethod(smooth_l1)

@@ -44,6 +44,33 @@ LOSS_RING = 4096
 WGRAD_FORMS = {"tile": 0, "split": 1}
 
 
+def propagator_tensors(own, eng, who="Stage2Trainer"):
+    """[(table index, key, Parameter)] of the propagator's tensors in the engine's parameter-table order, each checked to
+    be what the device-resident calls read through a raw pointer: present in the model, on the HIP device, contiguous fp32
+    of the table's shape.  The one rule by which Stage2Trainer and lns_amd.fit.LatentFit resolve parameter pointers."""
+    prefix = eng.cfg.prop_prefix.decode()
+    named = dict(own.named_parameters())
+    out = []
+    for i, (k, shape, isb) in enumerate(eng.params):
+        if not k.startswith(prefix) or isb:
+            continue
+        p = named.get(k)
+        if p is None:
+            raise LnsError("%s: the model has no parameter %s" % (who, k))
+        if not p.is_cuda:
+            raise LnsError("%s: parameter %s is on %s; the training step runs on HIP device tensors only "
+                           "(call model.cuda()); there is no CPU fallback" % (who, k, p.device))
+        if p.dtype != torch.float32 or not p.is_contiguous() or tuple(p.shape) != tuple(shape):
+            raise LnsError("%s: %s must be a contiguous fp32 tensor of shape %s" % (who, k, tuple(shape)))
+        out.append((i, k, p))
+    if not out:
+        raise LnsError("%s: the model has no propagator parameters" % who)
+    dev = out[0][2].device
+    if any(p.device != dev for _, _, p in out):
+        raise LnsError("%s: the propagator's parameters live on several devices" % who)
+    return out
+
+
 class Stage2Trainer:
     def __init__(self, model, optimizer=None, lr=1e-3, beta=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  loss_ring=LOSS_RING, wgrad=None, max_grad_norm=None, skip_nonfinite=False):
@@ -80,9 +107,7 @@ class Stage2Trainer:
     # -- one-time resolution -------------------------------------------------------------------------------------------
     def _resolve(self):
         eng, opt = self._eng, self.optimizer
-        prefix = eng.cfg.prop_prefix.decode()
-        named = dict(self._own.named_parameters())
-        table = [(i, k, shape) for i, (k, shape, isb) in enumerate(eng.params) if k.startswith(prefix) and not isb]
+        table = propagator_tensors(self._own, eng)
         group = opt.param_groups[0]
         in_group = {id(p) for p in group["params"]}
         n = len(eng.params)
@@ -90,15 +115,7 @@ class Stage2Trainer:
         params, grads, states = [], [], []
         old = {id(p): g for p, g in zip(getattr(self, "_params", ()), getattr(self, "_grads", ()))}
         prev = getattr(self, "_by_key", {})
-        for i, k, shape in table:
-            p = named.get(k)
-            if p is None:
-                raise LnsError("Stage2Trainer: the model has no parameter %s" % k)
-            if not p.is_cuda:
-                raise LnsError("Stage2Trainer: parameter %s is on %s; the training step runs on HIP device tensors only "
-                               "(call model.cuda()); there is no CPU fallback" % (k, p.device))
-            if p.dtype != torch.float32 or not p.is_contiguous() or tuple(p.shape) != tuple(shape):
-                raise LnsError("Stage2Trainer: %s must be a contiguous fp32 tensor of shape %s" % (k, tuple(shape)))
+        for i, k, p in table:
             if id(p) not in in_group and k in prev:
                 # the Parameter object was replaced (`prop.in_proj.weight = nn.Parameter(...)`): the new tensor takes the
                 # old one's place in the param group and, when the shape is the same, its Adam state
@@ -124,15 +141,11 @@ class Stage2Trainer:
             for a, t in zip(arrs, (p, g, st["exp_avg"], st["exp_avg_sq"])):
                 a[i] = t.data_ptr()
             params.append(p); grads.append(g); states.append(st)
-        if not params:
-            raise LnsError("Stage2Trainer: the model has no propagator parameters")
         if len(params) != len(group["params"]) or len(opt.param_groups) != 1:
             raise LnsError("Stage2Trainer: the optimizer must hold exactly the propagator's parameters in one param group")
         dev = params[0].device
-        if any(p.device != dev for p in params):
-            raise LnsError("Stage2Trainer: the propagator's parameters live on several devices")
         self._params, self._grads, self._states = params, grads, states
-        self._by_key = {k: named[k] for _, k, _ in table}
+        self._by_key = {k: p for _, k, p in table}
         self._steps = [st["step"] for st in states]
         self._arrs = arrs
         self._device = dev
