@@ -1104,6 +1104,53 @@ int lns_fit_step(lns_engine* e, const float* const* params, float* z0, float* pa
                  float* exp_avg_z, float* exp_avg_sq_z, float* g_p, float* exp_avg_p, float* exp_avg_sq_p, float* loss,
                  float* per_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- tangent-linear rollout: perturbations carried forward along a trajectory -----------------------------------------
+ * No reference counterpart: the reference never linearises its propagator.  lns_train_backward_ex with no gradient array
+ * carries a cotangent back through the rollout, J^T w; this is the other half of the pair, J v, so that
+ * <J v, w> = <v, J^T w> holds between the two calls.
+ *
+ * lns_train_tangent follows an lns_train_forward(..., T, ...) on the SAME workspace with the SAME params and reads that
+ * call's tape and forward weight packs.  v [B,K,c,h,w] holds K tangents of every sample's latent BEFORE step t0; the call
+ * advances them through the steps t0 .. t0 + nsteps - 1 of the taped trajectory, in place (v <- J_t v per step, J_t the
+ * Jacobian of propagator step t with respect to its input latent, at the tape's point), and with jv_out
+ * [B,K,nsteps,c,h,w] also stores them after every one of those steps (its last step is v's new value, bit for bit).  It
+ * takes neither z_in nor param: the tape has what they gave, and the conditional propagator's emb and m depend on param
+ * only, so their tangents are zero (dh = conv1.3(da1) with no broadcast add, dxm = dx1 (1 + m)).
+ * Per step, lns_train_forward's text line by line: every convolution is the forward launch without bias on the plan of
+ * batch B*K (K tangents ride the batch axis; row r = b*K + k reads the tape of sample b = r / K); GroupNorm becomes
+ *     dy = gamma rstd (dx - mean_g(dx) - xh mean_g(dx xh)),  xh = (x - mean) rstd from the tape's x and (mean, rstd),
+ * GELU becomes da = du gelu'(u) with the derivative as the backward writes it, the channel scale dxm = dx1 (1 + m).
+ * Order of the sums: the GroupNorm JVP is one 256-thread block per (group, row); dx xh is a rounded fp32 product (never
+ * contracted into the sum); a thread adds its elements i = tid, tid + 256, ... ascending in fp32, the wave is summed by
+ * the fixed cross-lane sequence of the training kernels (t_wave_sum), the four waves as (w0 + w1) + (w2 + w3); where a
+ * group holds one value, dx - mean_g(dx) is exactly 0.  No atomics; scalar accesses; bit-reproducible.  [t0, t0 + n) in
+ * one call has the bits of [t0, t0 + s) then [t0 + s, t0 + n).  The tiling of the convolutions follows B*K, so one
+ * (sample, tangent) run alone agrees with its row of a batch to rounding, not bit for bit.
+ * Workspace (lns_train_tangent_workspace_bytes(e, B, h, w, T, K); needs no GPU): lns_train_workspace_bytes' layout under
+ * the engine's current "train_wgrad", no offset moved | four tangent tensors of 4 * B * K * D * h * w bytes | one latent
+ * tangent of 4 * B * K * c * h * w bytes -- each part rounded up to 256 bytes.  The forward must be given this workspace.
+ * Refusals, decided on the host in this order before anything is enqueued: null e / params / v (size query: bytes); K
+ * outside 1 .. LNS_TANGENT_MAX; B < 1 or B*K beyond the batch limit; t0 < 0, nsteps < 1 or t0 + nsteps > T; no propagator
+ * (LNS_ESTATE); v / jv_out / workspace not device memory of one device; workspace null or short (LNS_ENOMEM naming the
+ * bytes); a null propagator parameter pointer.  No host synchronisation, allocation or host copy inside the call. */
+#define LNS_TANGENT_MAX 32
+int lns_train_tangent_workspace_bytes(lns_engine* e, int B, int h, int w, int T, int K, size_t* bytes);
+int lns_train_tangent(lns_engine* e, const float* const* params, int B, int h, int w, int T, int K, int t0, int nsteps,
+                      float* v, float* jv_out_or_null, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One pass of modified Gram-Schmidt over the K vectors of every sample, v [B,K,n] fp32 in place: for k ascending, for
+ * j < k ascending
+ *     r_jk = <q_j, v_k>,   v_k[i] = (float)((double)v_k[i] - r_jk * (double)q_j[i])        (rounded once per projection;
+ * the v_k of an inner product is the one the earlier projections left), then
+ *     R_kk = sqrt(<v_k, v_k>),   q_k[i] = (float)((double)v_k[i] / R_kk)                   (rounded once).
+ * Order: every product and sum in double (a product of two floats is exact there), as lns_loss_obs_mse sums: one
+ * 256-thread block per sample, a thread adds i = tid, tid + 256, ... ascending, the wave is a butterfly with neighbours
+ * first, the four waves (w0 + w1) + (w2 + w3).  r [B,K,K] double (nullable): the upper triangle, zeros below;
+ * logr_acc [B,K] double (nullable): += log(R_kk) -- the caller zeroes it.  R_kk == 0: q_k = 0 and the contribution is
+ * -inf; no NaN.  Scalar accesses: the bits do not depend on the pointer's alignment.  Refuses K outside
+ * 1 .. LNS_TANGENT_MAX, n < 1, B < 1 (message: lns_create_error()); never synchronises. */
+int lns_op_orthonormalize(float* v, int B, int K, int64_t n, double* r_or_null, double* logr_acc_or_null, void* stream);
+
 /* ---- diagnostics -------------------------------------------------------- */
 /* Layer trace: when enabled the run calls synchronise after every reference
  * module boundary and keep a host copy of its output (tests compare them with
@@ -1145,7 +1192,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * "ensemble_exceed" = lns_rollout_latent_ensemble_exceed and lns_op_ensemble_exceed are there; "op_fa_axis" =
  * lns_op_fa_reducer, lns_op_fa_lrk, lns_op_ln_pe, lns_op_apply, lns_rotary_table and the two fit predicates are there;
  * "eval_flow" = lns_rollout_eval_flow, lns_rollout_latent_eval_flow, lns_op_flow_stats and lns_op_vorticity are there;
- * "latent_fit" = lns_train_backward_ex, lns_loss_obs_mse, its size query, lns_fit_step and its size query are there.
+ * "latent_fit" = lns_train_backward_ex, lns_loss_obs_mse, its size query, lns_fit_step and its size query are there;
+ * "rollout_tangent" = lns_train_tangent, its size query and lns_op_orthonormalize are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);

@@ -163,6 +163,7 @@ class LnsUpdateSpec(ctypes.Structure):
 
 LNS_OBS_MAX = 64
 LNS_FIT_STATE, LNS_FIT_PARAM = 1, 2
+LNS_TANGENT_MAX = 32
 
 
 class LnsFitSpec(ctypes.Structure):
@@ -234,6 +235,7 @@ SYMBOLS = [
     "lns_grad_norm_scratch_bytes", "lns_grad_norm_tensors", "lns_grad_scale_tensors", "lns_update_step_tensors",
     "lns_train_step_clip_workspace_bytes", "lns_train_step_clip",
     "lns_train_backward_ex", "lns_loss_obs_mse_scratch_bytes", "lns_loss_obs_mse", "lns_fit_step_workspace_bytes", "lns_fit_step",
+    "lns_train_tangent_workspace_bytes", "lns_train_tangent", "lns_op_orthonormalize",
     "lns_trace_enable", "lns_trace_count", "lns_trace_info", "lns_trace_copy",
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
     "lns_op_conv_wgrad_scratch_bytes", "lns_op_conv_wgrad",
@@ -397,6 +399,10 @@ def lib():
         L.lns_fit_step_workspace_bytes.argtypes = [vp, i, i, i, i, i, c.POINTER(c.c_size_t)]
         L.lns_fit_step.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, c.POINTER(LnsFitSpec), vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                    c.c_size_t, vp]
+    if hasattr(L, "lns_train_tangent"):
+        L.lns_train_tangent_workspace_bytes.argtypes = [vp, i, i, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_train_tangent.argtypes = [vp, vp, i, i, i, i, i, i, i, vp, vp, vp, c.c_size_t, vp]
+        L.lns_op_orthonormalize.argtypes = [vp, i, i, c.c_int64, vp, vp, vp]
     L.lns_build_has.argtypes = [c.c_char_p]
     L.lns_trace_enable.argtypes = [vp, i]
     L.lns_trace_count.argtypes = [vp]

@@ -3204,6 +3204,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "train_clip")) return 1;
     if (!strcmp(feature, "train_ops")) return 1;
     if (!strcmp(feature, "latent_fit")) return 1;
+    if (!strcmp(feature, "rollout_tangent")) return 1;
     if (!strcmp(feature, "rollout_select")) return 1;
     if (!strcmp(feature, "rollout_ensemble")) return 1;
     if (!strcmp(feature, "ensemble_score")) return 1;
@@ -3231,3 +3232,4 @@ int lns_build_has(const char* feature) {
 }  // extern "C"
 
 #include "lns_train.inc"
+#include "lns_tangent.inc"

@@ -80,6 +80,25 @@ struct ObsTable {
 hipError_t launch_obs_mse(const ObsTable& tb, const float* z_pred, const float* obs, const float* z0, const float* zb, int B, int T,
                           long n, float* per, float* loss, float* grad, float* gbg, double* part, hipStream_t s);
 
+// ---- tangent-linear rollout (tangent.inc) --------------------------------------------------------------------------------
+// Tangent tensors are [B*K][C][HW], row r = b*K + k; what is read from the forward's tape belongs to sample b = r / K.
+struct GnJvpArgs {
+    const float* x;                    // tape: the GroupNorm's input [B][C][HW]
+    const float* stats;                // tape: [B][groups][2] (mean, rstd)
+    const float* gamma;
+    const float* dx; float* dy;        // [B*K][C][HW]: dy = gamma rstd (dx - mean_g(dx) - xh mean_g(dx xh)) [+ add]
+    const float* add;                  // [B*K][C][HW] or null
+    int B, K, C, HW, groups;
+};
+hipError_t launch_gn_train_jvp(const GnJvpArgs& a, hipStream_t s);
+// da[r][i] = du[r][i] gelu'(u[r / K][i]); n: elements of one sample; da may be du
+hipError_t launch_gelu_jvp(const float* du, const float* u, float* da, int rows, int K, long n, hipStream_t s);
+// dxm[r][c][p] = dx1[r][c][p] (1 + m[r / K][c])
+hipError_t launch_chan_scale_rows(const float* dx1, const float* m, float* dxm, int rows, int K, int C, int HW, hipStream_t s);
+// One pass of modified Gram-Schmidt over the K vectors of every sample, V [B][K][n] in place, sums in double in
+// obs_mse_kernel's order.  R [B][K][K] (upper triangle, zeros below) and logr_acc [B][K] (+= log R_kk) are nullable.
+hipError_t launch_orthonormalize(float* V, int B, int K, long n, double* R, double* logr_acc, hipStream_t s);
+
 // ---- loss and optimiser of the training step (lns_optim.inc) ----------------------------------------------------------
 // F.smooth_l1_loss(pred, target, 'mean', beta) -> *loss_out (device float) and, if grad != null, dL/dpred, in one pass.
 // partial: device scratch of smooth_l1_partials(n) floats (one per SL1_CHUNK elements).  n >= 1, beta > 0.

@@ -448,5 +448,6 @@ hipError_t launch_vec_gn(const float* x, const float* gamma, const float* beta, 
 
 #include "lns_optim.inc"
 #include "latent_fit.inc"
+#include "tangent.inc"
 
 }  // namespace lns

@@ -495,6 +495,28 @@ class LatentDynamics(_Hosted):
         z_obs = z_obs.reshape((B, n_obs) + tuple(z_obs.shape[1:]))
         return fitter.run(z0, z_obs, obs_steps, param=param, weights=weights, iters=iters)
 
+    def lyapunov(self, x, steps, *rest, k=4, **kw):
+        """lyapunov(x, steps, k=4, ...) -- conditional: lyapunov(x, steps, param, k=4, ...): the k leading finite-time
+        Lyapunov exponents of the learned dynamics along the `steps`-step forecast started at the frame x [B,C,Ly,Lx]
+        (its encoding is the start).  `kw`: TangentRollout.lyapunov's arguments (renorm, burn_in, chunk, generator, dt).
+        Returns tangent.LyapunovResult (exponents [B,k], history, vectors [B,k,c,h,w], z_last); 1 / exponents[:, 0] is
+        the e-folding time of a perturbation in units of dt, and `vectors` are the growing directions at z_last."""
+        from . import metrics as _metrics
+        from . import tangent as _tangent
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("lyapunov() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if rest:
+            raise TypeError("lyapunov() takes (x, steps, param, k=...)" if self._conditional else "lyapunov() takes (x, steps, k=...)")
+        roll = _tangent.TangentRollout(self)
+        x = self._fields(x)
+        with torch.no_grad():
+            enc_p = param if bool(getattr(self.args, "cond_encoder", False)) else None
+            z0 = _metrics.encode_dataset(self._ae, x, chunk=32, out_device=x.device, param=enc_p)
+        return roll.lyapunov(z0, steps, k=k, param=param, **kw)
+
     @staticmethod
     def _fields(x):
         # SW / two-phase loaders hand [B,1,C,H,W]; the reference squeezes (B=1 safe here, SURVEY F9)

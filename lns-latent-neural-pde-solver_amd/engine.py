@@ -214,6 +214,30 @@ def obs_loss(z_pred, obs, obs_steps, weights=None, z0=None, z_background=None, b
     return loss, per, grad, gbg
 
 
+def orthonormalize(v, r_out=None, logr_acc=None, need_r=False):
+    """One pass of modified Gram-Schmidt over the K vectors of every sample (lns_op_orthonormalize): v [B,K,...] fp32 is
+    orthonormalised IN PLACE, sums in double in a fixed order.  r_out [B,K,K] float64 (or need_r: allocated): the upper
+    triangle R of v = Q R; logr_acc [B,K] float64: += log(R_kk).  Returns (v, r_out).  Bit-reproducible; never
+    synchronises.  Module-level because the op needs no engine."""
+    import torch
+    if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or v.dim() < 3 or not v.is_contiguous():
+        raise LnsError("orthonormalize works in place on a contiguous fp32 [B,K,...] HIP device tensor (there is no CPU fallback), "
+                       "got %s" % (("%s %s on %s" % (v.dtype, tuple(v.shape), v.device)) if isinstance(v, torch.Tensor) else type(v),))
+    B, K = int(v.shape[0]), int(v.shape[1])
+    n = v[0, 0].numel() if B and K else 0
+    with torch.cuda.device(v.device):
+        if need_r and r_out is None:
+            r_out = torch.empty((B, K, K), dtype=torch.float64, device=v.device)
+        for t_, shape, name in ((r_out, (B, K, K), "r_out"), (logr_acc, (B, K), "logr_acc")):
+            if t_ is not None and (tuple(t_.shape) != shape or t_.dtype != torch.float64 or not t_.is_contiguous() or t_.device != v.device):
+                raise LnsError("%s must be a contiguous float64 %s tensor on v's device" % (name, shape))
+        L = _lib.lib()
+        rc = L.lns_op_orthonormalize(v.data_ptr(), B, K, n, Engine._ptr(r_out), Engine._ptr(logr_acc), Engine._stream(v))
+    if rc != 0:
+        raise LnsError("lns_op_orthonormalize failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    return v, r_out
+
+
 def smooth_l1(pred, target, beta=1.0, need_grad=True, loss_out=None, grad_out=None):
     """F.smooth_l1_loss(pred, target, beta=beta) (train_stage2_ns2d.py:213) and dL/dpred in one pass on the HIP kernel
     (lns_loss_smooth_l1): returns (0-dim device tensor, gradient like pred or None).  Bit-reproducible; never
@@ -1433,18 +1457,22 @@ class Engine:
             arr[i] = t.data_ptr()
         return arr
 
-    def train_forward(self, params, z_in, T, param=None):
+    def train_forward(self, params, z_in, T, param=None, workspace=None):
         """z_pred [B,T,c,h,w] of the latent rollout started at z_in [B,c,h,w], with the tape kept for train_backward.
-        params: {state_dict key: device tensor} of (at least) the propagator's parameters; param: [B] (conditional)."""
+        params: {state_dict key: device tensor} of (at least) the propagator's parameters, or the pointer array
+        `_ptr_array` returns; param: [B] (conditional).  workspace: the caller's (train_tangent needs the larger one of
+        train_tangent_workspace_bytes); None: one of lns_train_workspace_bytes is allocated."""
         import torch
         z_in = self._dev(z_in)
         pc = self._param(param, z_in)
         B, c, h, w = z_in.shape
-        n = ctypes.c_size_t(0)
-        self._check(self._L.lns_train_workspace_bytes(self._h, B, h, w, int(T), ctypes.byref(n)), "lns_train_workspace_bytes")
-        ws = torch.empty(int(n.value), dtype=torch.uint8, device=z_in.device)
+        ws = workspace
+        if ws is None:
+            n = ctypes.c_size_t(0)
+            self._check(self._L.lns_train_workspace_bytes(self._h, B, h, w, int(T), ctypes.byref(n)), "lns_train_workspace_bytes")
+            ws = torch.empty(int(n.value), dtype=torch.uint8, device=z_in.device)
         z_pred = torch.empty((B, int(T), c, h, w), dtype=torch.float32, device=z_in.device)
-        self._check(self._L.lns_train_forward(self._h, self._ptr_array(params), z_in.data_ptr(),
+        self._check(self._L.lns_train_forward(self._h, self._ptr_array(params) if isinstance(params, dict) else params, z_in.data_ptr(),
                                               pc.data_ptr() if pc is not None else None, B, h, w, int(T), z_pred.data_ptr(),
                                               ws.data_ptr(), ws.numel(), self._stream(z_in)), "lns_train_forward")
         return z_pred, ws
@@ -1472,6 +1500,39 @@ class Engine:
                                                   ws.data_ptr(), ws.numel(), self._stream(z_in), self._ptr(gp)),
                     "lns_train_backward_ex")
         return (grads, gz, gp) if need_param_grad else (grads, gz)
+
+    # -- tangent-linear rollout (include/lns.h "tangent-linear rollout") ---------------------------------------------
+    orthonormalize = staticmethod(orthonormalize)
+
+    def train_tangent_workspace_bytes(self, B, h, w, T, K):
+        """Bytes of the workspace train_forward(..., workspace=) and train_tangent share for K tangents per sample: the
+        training workspace under the current "train_wgrad" plus the tangent scratch.  Needs no GPU."""
+        n = ctypes.c_size_t(0)
+        self._check(self._L.lns_train_tangent_workspace_bytes(self._h, int(B), int(h), int(w), int(T), int(K), ctypes.byref(n)),
+                    "lns_train_tangent_workspace_bytes")
+        return int(n.value)
+
+    def train_tangent(self, params, v, T, workspace, t0=0, nsteps=None, keep=False, jv_out=None):
+        """J v along the trajectory of the train_forward(..., T, workspace=workspace) that precedes this call: v [B,K,c,h,w]
+        (K tangents of every sample's latent before step t0) is advanced IN PLACE through the steps t0 .. t0 + nsteps - 1
+        (nsteps None: to T).  keep / jv_out: also the tangents after every one of those steps, [B,K,nsteps,c,h,w]
+        (returned; None otherwise).  params as in train_forward.  Never synchronises; allocates only jv_out under keep."""
+        import torch
+        if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or v.dim() != 5 or not v.is_contiguous():
+            raise LnsError("train_tangent advances v in place: a contiguous fp32 [B,K,c,h,w] HIP device tensor, got %s"
+                           % (tuple(v.shape) if isinstance(v, torch.Tensor) else type(v),))
+        B, K, c, h, w = v.shape
+        nsteps = int(T) - int(t0) if nsteps is None else int(nsteps)
+        if keep and jv_out is None:
+            jv_out = torch.empty((B, K, max(nsteps, 0), c, h, w), dtype=torch.float32, device=v.device)
+        if jv_out is not None and (tuple(jv_out.shape) != (B, K, nsteps, c, h, w) or jv_out.dtype != torch.float32
+                                   or not jv_out.is_contiguous() or jv_out.device != v.device):
+            raise LnsError("jv_out must be a contiguous fp32 [B,K,nsteps,c,h,w] tensor on v's device")
+        with torch.cuda.device(v.device):
+            self._check(self._L.lns_train_tangent(self._h, self._ptr_array(params) if isinstance(params, dict) else params, B, h, w,
+                                                  int(T), K, int(t0), nsteps, v.data_ptr(), self._ptr(jv_out), workspace.data_ptr(),
+                                                  workspace.numel(), self._stream(v)), "lns_train_tangent")
+        return jv_out
 
     # -- latent fit (include/lns.h "latent fit") ---------------------------------------------------------------------
     obs_loss = staticmethod(obs_loss)
