@@ -464,6 +464,80 @@ int lns_rollout_latent_ensemble_exceed(lns_engine* e, const float* z_in, const f
                                        float* mean_out, float* var_out, float* z_last,
                                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ensemble transform Kalman filter on sparse, decoded observations --------------------------------------------
+ * lns_rollout_latent_ensemble with the ensemble corrected by observations in PHYSICAL space: a few sensors, one observed
+ * channel, a masked region.  An ensemble transform Kalman filter (ETKF; Hunt, Kostelich, Szunyogh 2007, without
+ * localisation) needs no adjoint: it needs the decoded members at the observed steps -- the frame buffers of the ensemble
+ * sink -- the M x M Gram matrix of their anomalies under the observation weights, a symmetric inverse square root of it, and
+ * an M x M transform of the latent members.  The same transform updates a per-member param, so a parameter is estimated
+ * from sparse decoded observations also where the encoder is conditional.
+ *
+ * Notation: M members, p runs over the Cin*Ly*Lx values of a frame, r_p >= 0 is the inverse observation-error variance of
+ * value p (0: not observed).  rinv is fp32 and addressed as rinv + b * rinv_bs + i * rinv_ss + p for sample b and kept step i
+ * (strides in floats, >= 0; 0: the map is shared).
+ *
+ * 1. Gram (per sample b and kept step i; double throughout):
+ *     f_m = D_c(member m), y = D_c(y_obs): the map of lns_eval_spec as written for lns_rollout_latent_ensemble_eval (the one
+ *     denormalisation device function of the scored kernels; norm == NULL: the values as they are), then converted to double
+ *         ybar_p = (f_0 + f_1 + ... + f_{M-1}) / M          (m ascending)
+ *         Y_m = f_m - ybar,   d = y - ybar,   w_m = r_p * Y_m
+ *         S_ij = sum_p w_i Y_j   for i <= j,   S_ji = S_ij            g_i = sum_p w_i d
+ *         stat = (sum_p (r_p d) d,  sum_p r_p,  #{p : r_p > 0})
+ *     A value with !(r_p > 0) contributes nothing whatever y_obs and the members hold there (a select, not a product with 0:
+ *     NaN and inf at unobserved values are harmless, and they are not read).
+ *     Order: the frame is cut into slices of LNS_ETKF_SLICE = 1024 consecutive values p; inside a slice every sum starts at
+ *     0 and takes one fused multiply-add per value, p ascending: acc = fma(w_i, Y_j, acc), fma(w_i, d, acc), fma(r_p d, d, acc)
+ *     (sum r_p: plain adds; an unobserved value adds fma(0, 0, acc) or is skipped); then the slices are added in ascending
+ *     order, starting from slice 0.  The slice length is a constant: the result depends on its inputs only, never on the
+ *     grouping, the streams or any scheduling option.  No atomics.
+ * 2. Transform (per sample; double, nothing fused):
+ *     S_tot, g_tot: the sums over the n kept steps, ascending (the 4D form: the observations of several steps of one window
+ *     give one set of weights).  A = dg I + S_tot with dg = (M - 1) / rho on the diagonal (dg + S_ii), rho >= 1 the
+ *     multiplicative inflation.  Cyclic Jacobi, A = Q Lambda Q^T: a sweep is n' - 1 rounds over n' = M + (M & 1) indices in the
+ *     round-robin order -- round r = 0 .. n' - 2 holds the n'/2 disjoint pairs {n' - 1, r} and, for k = 1 .. n'/2 - 1,
+ *     {(r + k) mod (n' - 1), (r - k) mod (n' - 1)}; a pair with the padding index of an odd M rests.  For a pair p < q
+ *     with a_pq != 0:  theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1),
+ *     s = t c, all from the matrix before the round; then rows (a_pj, a_qj) <- (c a_pj - s a_qj, s a_pj + c a_qj) for every
+ *     pair, then columns (a_ip, a_iq) <- (c a_ip - s a_iq, s a_ip + c a_iq) with a_pq = a_qp = 0 set, and the same column
+ *     step on Q (disjoint rotations commute).  Ahead of every sweep: if every |a_pq| <= 2^-52 sqrt(a_pp a_qq), p < q, the
+ *     iteration ends (status 0); after LNS_ETKF_MAX_SWEEPS = 30 sweeps without that it ends with status 2 and the result
+ *     stands as it is.  lam_k = a_kk, taken in ascending order (ties: ascending index) in every sum over k below.
+ *         wbar_i = sum_k Q_ik u_k,    u_k = (sum_i Q_ik g_tot_i) / lam_k                (= Q Lambda^-1 Q^T g_tot)
+ *         W_ij = ((sum_k (Q_ik f_k) Q_jk) + (sum_k (Q_jk f_k) Q_ik)) / 2,   f_k = sqrt((M - 1) / lam_k)
+ *                                                                                        (= sqrt(M-1) Q Lambda^-1/2 Q^T, symmetric)
+ *         X_km = W_km + wbar_k
+ *     A non-finite entry of S_tot or g_tot: status 1, and X, wbar, lam of THAT sample are NaN; other samples are untouched.
+ *     The kernel makes no host read.  With all r = 0: A = dg I, no rotation, X = sqrt((M-1)/dg) I, wbar = 0.
+ * 3. Update (per element e of z [B][M][n], double, nothing fused, k ascending):
+ *         zbar = (z_0 + ... + z_{M-1}) / M,   Z_k = z_k - zbar,   out_m = (float)(zbar + sum_k Z_k X_km)
+ *     (sum: acc = 0; acc = acc + Z_k * X_km).  A thread reads its M values before it writes any, so out may be z; accesses are
+ *     scalar: the bits do not depend on alignment.  n = 1 is the update of a per-member param.
+ *
+ * Not there: localisation, M > 64, additive inflation, correlated observation errors (R is diagonal), observation
+ * operators that are not pointwise in the decoded (denormalised) frame.
+ *
+ * z_in, param, keep_steps_host, B, M, T, mean_out, var_out, z_last: as lns_rollout_latent_ensemble, with 2 <= M <=
+ * LNS_ETKF_MAX_MEMBERS.  y_obs [B][n_keep][Cin][Ly][Lx]: the normalised observations of the kept steps (any value where
+ * r = 0).  z_analysis [B][M][zper]: the forecast latents of step T - 1 (z_last) updated by X.  Nullable outputs:
+ * param_analysis [B][M] (needs param; the per-member param updated by X), X [B][M][M], wbar [B][M], lam [B][M] (ascending),
+ * stat [B][n_keep][3] (double), status [B] (int32), mean_out / var_out (lns_rollout_latent_ensemble's bits; var_out needs
+ * mean_out), z_last.  The Gram launch follows the decode of each group on its decode stream; the slice sums, the transform and
+ * the updates follow the join on the caller's stream.  workspace: lns_rollout_ensemble_analysis_workspace_bytes(B, M, n_keep)
+ * = the ensemble layout byte for byte, then one region for the slice partials, S, g, stat, X, wbar, lam, status.
+ * Refused before any device work (lns_last_error), in this order: z_in null; y_obs null; rinv null; z_analysis null; a
+ * negative stride of rinv; rho < 1 or not finite; B, M, T not positive; M outside 2 .. 64; var_out without mean_out;
+ * param_analysis without param; norm of the wrong size; n_keep < 1 and keep_steps as lns_rollout_latent_ensemble; the batch
+ * B * M; the model; param. */
+#define LNS_ETKF_MAX_MEMBERS 64
+int lns_rollout_ensemble_analysis_workspace_bytes(lns_engine* e, int B, int M, int n_keep, size_t* bytes);
+int lns_rollout_latent_ensemble_analysis(lns_engine* e, const float* z_in, const float* param, const float* y_obs,
+                                         const float* rinv, int64_t rinv_bs, int64_t rinv_ss, int B, int M, int T,
+                                         const int* keep_steps_host, int n_keep, const lns_eval_spec* norm /* nullable */,
+                                         double rho, float* z_analysis,
+                                         float* param_analysis, double* X, double* wbar, double* lam, double* stat,
+                                         int32_t* status, float* mean_out, float* var_out, float* z_last, /* all nullable */
+                                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- streaming validation: energy spectra of forecast, truth and error ---------------------------------------------
  * lns_rollout_eval / lns_rollout_latent_eval with, for selected steps, the shell-summed energy spectra of the forecast,
  * of the truth and of their difference, taken where the step is decoded: a spectrum needs the whole plane of a step, i.e.
@@ -1193,7 +1267,9 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * lns_op_fa_reducer, lns_op_fa_lrk, lns_op_ln_pe, lns_op_apply, lns_rotary_table and the two fit predicates are there;
  * "eval_flow" = lns_rollout_eval_flow, lns_rollout_latent_eval_flow, lns_op_flow_stats and lns_op_vorticity are there;
  * "latent_fit" = lns_train_backward_ex, lns_loss_obs_mse, its size query, lns_fit_step and its size query are there;
- * "rollout_tangent" = lns_train_tangent, its size query and lns_op_orthonormalize are there.
+ * "rollout_tangent" = lns_train_tangent, its size query and lns_op_orthonormalize are there; "ensemble_etkf" =
+ * lns_rollout_latent_ensemble_analysis, its size query, lns_op_ensemble_obs_gram, lns_op_etkf_transform and
+ * lns_op_ensemble_transform are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
@@ -1398,6 +1474,25 @@ int lns_op_ensemble_quantiles(const float* frames, int n, int B, int M, int C, i
 int lns_op_ensemble_exceed(const float* frames, const float* y, int n, int B, int M, int C, int H, int W,
                            const lns_ensemble_exceed_spec* xspec, const lns_eval_spec* norm /* nullable */,
                            int32_t* table_out, void* stream);
+
+/* The three kernels of lns_rollout_latent_ensemble_analysis without an engine, by the statement written there.
+ * lns_op_ensemble_obs_gram: frames [n][B][M][C][H][W] (the layout of a frame buffer), y_obs [B][n][C][H][W], rinv with its two
+ * strides, norm nullable -> S_out [B][n][M][M] (full, symmetric), g_out [B][n][M], stat_out [B][n][3], all double; the slice
+ * partials live in device memory the call owns, and the call synchronises `stream`.  Refusals in this order: frames, y_obs or
+ * rinv null; an output null; norm of the wrong size; M outside 2 .. 64; the shape (as lns_op_ensemble_exceed); a negative
+ * stride; the per-channel norm with C > 8.
+ * lns_op_etkf_transform: S [B][n][M][M], g [B][n][M] -> X [B][M][M], wbar [B][M], lam [B][M] (double), status [B] (int32); one
+ * block per sample, no host read, never synchronises.  Refusals: S or g null; an output null; M outside 2 .. 64; B, n < 1;
+ * rho < 1 or not finite.
+ * lns_op_ensemble_transform: z [B][M][n] fp32, X [B][M][M] double -> out [B][M][n], which may be z; never synchronises.
+ * Refusals: a null pointer; M outside 2 .. 64; B outside 1..65535 or n outside 1..2^38.
+ * Messages: lns_create_error(). */
+int lns_op_ensemble_obs_gram(const float* frames, const float* y_obs, const float* rinv, int64_t rinv_bs, int64_t rinv_ss,
+                             int n, int B, int M, int C, int H, int W, const lns_eval_spec* norm /* nullable */,
+                             double* S_out, double* g_out, double* stat_out, void* stream);
+int lns_op_etkf_transform(const double* S, const double* g, int B, int n, int M, double rho, double* X, double* wbar,
+                          double* lam, int32_t* status, void* stream);
+int lns_op_ensemble_transform(const float* z, const double* X, int B, int M, int64_t n, float* out, void* stream);
 
 /* The spectrum kernel of lns_rollout_eval_spectrum on stored fields, without an engine: yhat and y (nullable) [B][T][C][H][W],
  * normalised -> out [B][T][C][K][S], K = 3 (forecast, truth, error) when y is given, K = 1 (the forecast's row, same bits) when

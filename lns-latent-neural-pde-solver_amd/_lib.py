@@ -222,6 +222,8 @@ SYMBOLS = [
     "lns_rollout_latent_ensemble_eval", "lns_op_ensemble_score",
     "lns_rollout_latent_ensemble_quantiles", "lns_op_ensemble_quantiles",
     "lns_rollout_latent_ensemble_exceed", "lns_op_ensemble_exceed",
+    "lns_rollout_ensemble_analysis_workspace_bytes", "lns_rollout_latent_ensemble_analysis",
+    "lns_op_ensemble_obs_gram", "lns_op_etkf_transform", "lns_op_ensemble_transform",
     "lns_spectrum_bins", "lns_rollout_eval_spectrum", "lns_rollout_latent_eval_spectrum", "lns_op_energy_spectrum",
     "lns_spectrum_bins_basis", "lns_op_energy_spectrum_basis",
     "lns_rollout_eval_stats", "lns_rollout_latent_eval_stats", "lns_op_field_stats",
@@ -328,6 +330,14 @@ def lib():
         sp, ip, xp = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.POINTER(LnsEnsembleExceedSpec)
         L.lns_rollout_latent_ensemble_exceed.argtypes = [vp, vp, vp, vp, i, i, i, ip, i, xp, sp, vp, vp, vp, vp, vp, c.c_size_t, vp]
         L.lns_op_ensemble_exceed.argtypes = [vp, vp, i, i, i, i, i, i, xp, sp, vp, vp]
+    if hasattr(L, "lns_rollout_latent_ensemble_analysis"):
+        sp, ip, i64, dbl = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.c_int64, c.c_double
+        L.lns_rollout_ensemble_analysis_workspace_bytes.argtypes = [vp, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_rollout_latent_ensemble_analysis.argtypes = [vp, vp, vp, vp, vp, i64, i64, i, i, i, ip, i, sp, dbl, vp,
+                                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c.c_size_t, vp]
+        L.lns_op_ensemble_obs_gram.argtypes = [vp, vp, vp, i64, i64, i, i, i, i, i, i, sp, vp, vp, vp, vp]
+        L.lns_op_etkf_transform.argtypes = [vp, vp, i, i, i, dbl, vp, vp, vp, vp, vp]
+        L.lns_op_ensemble_transform.argtypes = [vp, vp, i, i, i64, vp, vp]
     if hasattr(L, "lns_rollout_eval_spectrum"):
         sp, ip = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int)
         L.lns_spectrum_bins.argtypes = [i, i]

@@ -1686,6 +1686,7 @@ struct WsLayout {
     size_t fbuf_off, fbuf_stride, part_off;   // SINK_SCORED; SINK_ENSEMBLE (no part)
     size_t pp_off[2];                         // SINK_KEPT, SINK_ENSEMBLE
     size_t maps_off = 0, maps_bytes = 0;      // SINK_SCORED with time maps (add_maps_region)
+    size_t etkf_off = 0;                      // SINK_ENSEMBLE with ens_obs (etkf_region)
     // SINK_SCORED with attribution (add_attrib_region): second frame buffers, true-latent staging, three partial-sum arrays
     size_t fbuf2_off = 0, ztrue_off = 0, ztrue_stride = 0, part2_off = 0, ppart_off = 0, lpart_off = 0; long zstride = 0;
 };
@@ -1817,6 +1818,12 @@ struct RolloutCall {
     // SINK_ENSEMBLE with ens_exceed (lns_rollout_latent_ensemble_exceed): xspec, y_true [traj][n_keep], the table, and `spec` below
     // as the nullable denormalisation; `out` (the mean) is optional
     bool ens_exceed = false; const lns_ensemble_exceed_spec* xspec = nullptr; int32_t* table_out = nullptr;
+    // SINK_ENSEMBLE with ens_obs (lns_rollout_latent_ensemble_analysis): y_true [traj][n_keep] holds the observations, rinv their
+    // weights with its two strides, `spec` below the nullable denormalisation, rho the inflation; z_analysis and the nullable
+    // outputs of the filter; `out` (the mean) is optional
+    bool ens_obs = false; const float* rinv = nullptr; int64_t rinv_bs = 0, rinv_ss = 0; double rho = 1.0;
+    float *z_analysis = nullptr, *param_analysis = nullptr;
+    double *X_out = nullptr, *wbar_out = nullptr, *lam_out = nullptr, *stat_out = nullptr; int32_t* status_out = nullptr;
     // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
     const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
     float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
@@ -2355,6 +2362,42 @@ static size_t exceed_table_bytes(int B, int n, int n_thr, int C, int M) {
     return (size_t)B * n * n_thr * C * 2 * (M + 1) * sizeof(int32_t);
 }
 
+// the refusals of the ensemble transform Kalman filter's member count and inflation (include/lns.h); nullptr: accepted
+static_assert(LNS_ETKF_MAX_MEMBERS == 64, "the header's LNS_ETKF_MAX_MEMBERS, the messages below and the kernels' LDS budgets say 64");
+static const char* etkf_members_refusal(int M) {
+    return M < 2 || M > LNS_ETKF_MAX_MEMBERS ? "M in 2 .. 64 (the transform keeps A and Q in LDS; 65 .. 128 members are not supported)" : nullptr;
+}
+static const char* etkf_rho_refusal(double rho) {
+    return !(rho >= 1.0) || std::isinf(rho) ? "rho (the multiplicative inflation) must be finite and >= 1" : nullptr;
+}
+
+// the Gram kernel's arguments (norm nullable); frames / part / kk / y_T / y_t / o_T / o_t are the caller's
+static void obs_gram_args(const lns_eval_spec* norm, const float* y, const float* rinv, int64_t r_bs, int64_t r_ss, int B, int M, int C,
+                          int H, int W, EnsembleObsGramArgs* gp) {
+    EnsembleObsGramArgs& g = *gp;
+    memset(&g, 0, sizeof g);
+    g.y = y; g.rinv = rinv; g.r_bs = (long)r_bs; g.r_ss = (long)r_ss;
+    g.B = B; g.M = M; g.C = C; g.H = H; g.W = W; g.nsl = etkf_slices((long)C * H * W);
+    g.denorm = norm != nullptr;
+    if (norm) score_norm(norm, C, &g.norm);
+}
+
+// The region of lns_rollout_latent_ensemble_analysis behind the SINK_ENSEMBLE layout, which it leaves byte for byte as it is:
+// the slice partials [B][n_keep][slices][M*M + M + 3], then S [B][n_keep][M][M], g [B][n_keep][M], stat [B][n_keep][3], X [B][M][M],
+// wbar [B][M], lam [B][M] (all double) and status [B] (int32); offsets from the region's start
+struct EtkfRegion { size_t part, S, g, stat, X, wbar, lam, status, bytes; };
+static EtkfRegion etkf_region(const lns_engine* e, size_t B, size_t M, size_t n_keep) {
+    const size_t nsl = (size_t)etkf_slices((long)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx), bn = B * n_keep;
+    EtkfRegion r;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off = round_up_sz(off + bytes, 256); return at; };
+    r.part = take(bn * nsl * etkf_part_doubles((int)M) * 8);
+    r.S = take(bn * M * M * 8); r.g = take(bn * M * 8); r.stat = take(bn * 3 * 8);
+    r.X = take(B * M * M * 8); r.wbar = take(B * M * 8); r.lam = take(B * M * 8); r.status = take(B * 4);
+    r.bytes = off;
+    return r;
+}
+
 // the autoregressive loop of every rollout call: zcur -> T x (propagate ; what the sink does)   (train_stage2_ns2d.py:147-156)
 // The latent chain z_t -> z_{t+1} is strictly sequential, but decode(z_t) depends on z_t only: the chain runs ahead
 // (on the engine's side stream when overlapping; own arena) writing groups of `kdec` consecutive decoded latents into
@@ -2424,6 +2467,12 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     if (ens && c.ens_exceed) {
         exceed_args(c.xspec, c.spec, c.y_true, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, c.table_out, &xa);
         xa.y_T = xa.o_T = c.n_keep;
+    }
+    EnsembleObsGramArgs oa;
+    if (ens && c.ens_obs) {                          // the slice partials of kept step i land in the region's part[b][i]
+        obs_gram_args(c.spec, c.y_true, c.rinv, c.rinv_bs, c.rinv_ss, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, &oa);
+        oa.part = reinterpret_cast<double*>(base + L.etkf_off + etkf_region(e, c.traj, c.M, c.n_keep).part);
+        oa.y_T = oa.o_T = c.n_keep;
     }
     SpectrumArgs sx;
     if (scored && c.spectra) spectrum_args(e, c, &sx);
@@ -2605,6 +2654,10 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
             xa.frames = fb; xa.kk = kk; xa.y_t = xa.o_t = i0;
             HIPCHK(e, launch_ensemble_exceed(xa, dstream[d]));
         }
+        if (ens && c.ens_obs) {                      // fb is [kk][traj][M][xper] against y_obs[b][i0 .. i0 + kk) -> the slice partials of those steps
+            oa.frames = fb; oa.kk = kk; oa.y_t = oa.o_t = i0;
+            HIPCHK(e, launch_ensemble_obs_gram(oa, dstream[d]));
+        }
         if (ens && c.out) {                          // fb is [kk][traj][M][xper] -> mean / var of out[b][i0 .. i0 + kk)
             EnsembleStatsArgs es;
             es.frames = fb; es.mean = c.out + (long)i0 * xper; es.var = c.var_out ? c.var_out + (long)i0 * xper : nullptr;
@@ -2639,14 +2692,22 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
     const bool ens_scored = ens && c.ens_scored;     // lns_rollout_latent_ensemble_eval: every output but scores_out is optional
     const bool ens_quant = ens && c.ens_quant;       // lns_rollout_latent_ensemble_quantiles: the mean is optional
     const bool ens_exceed = ens && c.ens_exceed;     // lns_rollout_latent_ensemble_exceed: likewise
+    const bool ens_obs = ens && c.ens_obs;           // lns_rollout_latent_ensemble_analysis: likewise
     if (!c.start) return einval(e, c.encode ? "x is null" : "z_in is null");
+    if (ens_obs) {
+        if (!c.y_true) return einval(e, "y_obs is null");
+        if (!c.rinv) return einval(e, "rinv is null");
+        if (!c.z_analysis) return einval(e, "z_analysis is null");
+        if (c.rinv_bs < 0 || c.rinv_ss < 0) return einval(e, "the strides of rinv must be >= 0 (0: shared)");
+        if (const char* why = etkf_rho_refusal(c.rho)) return einval(e, why);
+    }
     if ((scored || ens_scored || ens_exceed) && !c.y_true) return einval(e, "y_true is null");
     if (ens_scored && !c.scores_out) return einval(e, "scores_out is null");
     if (ens_quant)
         if (const char* why = quantile_spec_refusal(c.qspec, c.quant_out, c.prob_out)) return einval(e, why);
     if (ens_exceed)
         if (const char* why = exceed_spec_refusal(c.xspec, c.table_out)) return einval(e, why);
-    if (!scored && !ens_scored && !ens_quant && !ens_exceed && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
+    if (!scored && !ens_scored && !ens_quant && !ens_exceed && !ens_obs && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
     if ((ens ? c.traj : c.B) <= 0) return einval(e, "B must be positive");
     if (ens && c.M <= 0) return einval(e, "M must be positive");
     if (c.T <= 0) return einval(e, "T must be positive");
@@ -2667,6 +2728,13 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
         if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
         if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
         if (e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "thresholds need in_channels <= 8");
+    }
+    if (ens_obs) {
+        if (const char* why = etkf_members_refusal(c.M)) { e->err = std::string("ensemble analysis needs ") + why; return LNS_EINVAL; }
+        if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
+        if (c.param_analysis && !c.param) return einval(e, "param_analysis needs param");
+        if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
+        if (c.spec && c.spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "norm: the per-channel form needs in_channels <= 8");
     }
     if (scored) {
         if (c.t0 < 0 || (long)c.t0 + c.T > c.T_total) {
@@ -2754,7 +2822,14 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if ((rc = ws_layout(e, c.B, c.sink, &L))) return rc;
     if (scored && c.maps) add_maps_region(e, c.B, &L);
     if (scored && c.attrib) add_attrib_region(e, c.B, &L);
-    if ((rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : (c.sink == SINK_ENSEMBLE ? "ensemble " : "")),
+    const bool ens_obs = c.sink == SINK_ENSEMBLE && c.ens_obs;
+    EtkfRegion R = {};
+    if (ens_obs) {
+        R = etkf_region(e, c.traj, c.M, c.n_keep);
+        L.etkf_off = round_up_sz(L.total, 256);
+        L.total = L.etkf_off + R.bytes;
+    }
+    if ((rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : (ens_obs ? "ensemble analysis " : (c.sink == SINK_ENSEMBLE ? "ensemble " : ""))),
                        c.ws, c.ws_bytes))) return rc;
     Plan* pe = nullptr;
     if (c.encode && (rc = get_plan(e, PK_ENC, c.B, 0, 0, &pe))) return rc;
@@ -2805,6 +2880,23 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if (c.sink == SINK_ENSEMBLE && c.ens_scored)     // likewise: the plane sums in scores_out -> the scores, in place
         HIPCHK(e, launch_ensemble_score_finish(c.scores_out, c.traj, c.n_keep, cfg.in_channels, cfg.Ly * cfg.Lx, c.spec->eps,
                                                c.seq_out, r.stream));
+    if (ens_obs) {
+        // The filter, on the caller's stream behind the join: every Gram launch of the decode streams and the copy of the last
+        // latents (c.z_last: the caller's buffer or z_analysis itself) are ordered before it.
+        char* rb = base + L.etkf_off;
+        double* S = reinterpret_cast<double*>(rb + R.S);
+        double* g = reinterpret_cast<double*>(rb + R.g);
+        double* stat = c.stat_out ? c.stat_out : reinterpret_cast<double*>(rb + R.stat);
+        EtkfTransformArgs ta = {S, g, c.X_out ? c.X_out : reinterpret_cast<double*>(rb + R.X),
+                                c.wbar_out ? c.wbar_out : reinterpret_cast<double*>(rb + R.wbar),
+                                c.lam_out ? c.lam_out : reinterpret_cast<double*>(rb + R.lam),
+                                c.status_out ? c.status_out : reinterpret_cast<int*>(rb + R.status), c.rho, c.traj, c.n_keep, c.M};
+        HIPCHK(e, launch_ensemble_obs_gram_finish(reinterpret_cast<const double*>(rb + R.part), c.traj * c.n_keep,
+                                                  etkf_slices((long)cfg.in_channels * cfg.Ly * cfg.Lx), c.M, S, g, stat, r.stream));
+        HIPCHK(e, launch_etkf_transform(ta, r.stream));
+        HIPCHK(e, launch_ensemble_transform(c.z_last, ta.X, c.traj, c.M, zper, c.z_analysis, r.stream));
+        if (c.param && c.param_analysis) HIPCHK(e, launch_ensemble_transform(c.param, ta.X, c.traj, c.M, 1, c.param_analysis, r.stream));
+    }
     return r.finish();
 }
 
@@ -3112,6 +3204,34 @@ int lns_rollout_latent_ensemble_exceed(lns_engine* e, const float* z_in, const f
     return rollout_call(e, c);
 }
 
+// ---- ensemble transform Kalman filter (include/lns.h) -----------------------------------------------------------
+int lns_rollout_ensemble_analysis_workspace_bytes(lns_engine* e, int B, int M, int n_keep, size_t* bytes) {
+    if (!e) return LNS_EINVAL;
+    if (B <= 0) return einval(e, "B must be positive");
+    if (M <= 0) return einval(e, "M must be positive");
+    if (const char* why = etkf_members_refusal(M)) { e->err = std::string("ensemble analysis needs ") + why; return LNS_EINVAL; }
+    if (n_keep < 1) return einval(e, "n_keep must be at least 1");
+    size_t base = 0;
+    if (int rc = workspace_bytes(e, ensemble_batch(B, M), SINK_ENSEMBLE, &base)) return rc;
+    if (bytes) *bytes = round_up_sz(base, 256) + etkf_region(e, B, M, n_keep).bytes;
+    return LNS_OK;
+}
+
+int lns_rollout_latent_ensemble_analysis(lns_engine* e, const float* z_in, const float* param, const float* y_obs, const float* rinv,
+                                         int64_t rinv_bs, int64_t rinv_ss, int B, int M, int T, const int* keep_steps_host, int n_keep,
+                                         const lns_eval_spec* norm, double rho, float* z_analysis, float* param_analysis, double* X_out,
+                                         double* wbar_out, double* lam_out, double* stat_out, int32_t* status_out, float* mean_out,
+                                         float* var_out, float* z_last, void* ws, size_t ws_bytes, void* stream) {
+    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
+    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
+    c.ens_obs = true; c.y_true = y_obs; c.rinv = rinv; c.rinv_bs = rinv_bs; c.rinv_ss = rinv_ss; c.spec = norm; c.rho = rho;
+    c.z_analysis = z_analysis; c.param_analysis = param_analysis; c.X_out = X_out; c.wbar_out = wbar_out; c.lam_out = lam_out;
+    c.stat_out = stat_out; c.status_out = status_out;
+    c.out = mean_out; c.var_out = var_out;
+    c.z_last = z_last ? z_last : z_analysis;         // the forecast latents of step T - 1: the update reads them (in place without z_last)
+    return rollout_call(e, c);
+}
+
 int lns_check_finite(lns_engine* e, int B, void* ws, size_t ws_bytes, void* stream) {
     if (!e || B <= 0 || !ws) return LNS_EINVAL;
     // The amax vectors live in the CALLER's workspace: they are read through the `ws` handed in here, which must be
@@ -3210,6 +3330,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "ensemble_score")) return 1;
     if (!strcmp(feature, "ensemble_quantiles")) return 1;
     if (!strcmp(feature, "ensemble_exceed")) return 1;
+    if (!strcmp(feature, "ensemble_etkf")) return 1;
     if (!strcmp(feature, "eval_spectrum")) return 1;
     if (!strcmp(feature, "spectrum_basis")) return 1;
     if (!strcmp(feature, "eval_stats")) return 1;

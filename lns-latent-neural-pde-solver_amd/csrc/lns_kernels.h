@@ -468,6 +468,33 @@ struct EnsembleExceedArgs {
 };
 hipError_t launch_ensemble_exceed(const EnsembleExceedArgs& a, hipStream_t s);
 
+// Ensemble transform Kalman filter (lns_rollout_latent_ensemble_analysis, lns_op_ensemble_obs_gram, lns_op_etkf_transform,
+// lns_op_ensemble_transform; the statement and every summation order: include/lns.h), ensemble_etkf.inc.
+// Gram: member frames [kk][B][M][C][H*W] against the observed planes y[b][y_t + j] of y [B][y_T][C][H*W] under the weights
+// rinv + b * r_bs + (o_t + j) * r_ss (strides in floats, 0 = shared) -> per slice of LNS_ETKF_SLICE values of the frame the
+// partial sums part[(b * o_T + o_t + j) * nsl + slice][M * M + M + 3] (the upper triangle of S, g, stat), all double.
+// Grid (slices, B, kk); the finish kernel adds the slices in ascending order and mirrors the triangle.  2 <= M <= 64.
+// denorm = 0: members and observation as they are (norm unused); else norm, as MetricGroupArgs.
+#define LNS_ETKF_MAX_MEMBERS 64
+#define LNS_ETKF_SLICE 1024
+#define LNS_ETKF_MAX_SWEEPS 30
+struct EnsembleObsGramArgs {
+    const float* frames; const float* y; const float* rinv; double* part;
+    long r_bs, r_ss;
+    int B, M, C, H, W, kk, y_T, y_t, o_T, o_t, denorm, nsl;
+    ScoreNorm norm;
+};
+inline int etkf_slices(long values) { return (int)((values + LNS_ETKF_SLICE - 1) / LNS_ETKF_SLICE); }
+inline size_t etkf_part_doubles(int M) { return (size_t)M * M + M + 3; }
+hipError_t launch_ensemble_obs_gram(const EnsembleObsGramArgs& a, hipStream_t s);
+// part [BN][nsl][M * M + M + 3] -> S [BN][M][M] (full, symmetric), g [BN][M], stat [BN][3]
+hipError_t launch_ensemble_obs_gram_finish(const double* part, int BN, int nsl, int M, double* S, double* g, double* stat, hipStream_t s);
+// S [B][n][M][M], g [B][n][M] -> X [B][M][M], wbar [B][M], lam [B][M], status [B]; one block per sample
+struct EtkfTransformArgs { const double* S; const double* g; double* X; double* wbar; double* lam; int* status; double rho; int B, n, M; };
+hipError_t launch_etkf_transform(const EtkfTransformArgs& a, hipStream_t s);
+// z [B][M][n] fp32, X [B][M][M] double -> out [B][M][n] (may be z)
+hipError_t launch_ensemble_transform(const float* z, const double* X, int B, int M, long n, float* out, hipStream_t s);
+
 // Energy spectra (lns_rollout_eval_spectrum, lns_op_energy_spectrum; the statement: include/lns.h): one block per plane
 // writes its K x S shell energies, K = 3 (forecast, truth, error) with y, K = 1 (forecast) without; S = lns_spectrum::bins(H, W, basis_y, basis_x).
 // Group form: frames [kk][B][C][H*W] (a decode stream's frame buffer); the n <= 8 selected steps sel[0 .. n) of the group

@@ -5314,6 +5314,7 @@ hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int 
 #include "eval_attrib.inc"
 #include "ensemble_quantile.inc"
 #include "ensemble_exceed.inc"
+#include "ensemble_etkf.inc"
 
 // per-sample max |x| of a [B, n] tensor: grid (chunks, B); one atomic per wave
 __global__ __launch_bounds__(256) void amax_kernel(const float* x, long x_bs, long n, unsigned* amax) {
@@ -5479,6 +5480,9 @@ hipError_t init_kernels() {
     LNS_SET_LDS(fa_reducer_kernel)
     LNS_SET_LDS(ensemble_score_kernel)                                   // 128 members: 128 KB of columns
     LNS_SET_LDS(ensemble_quantile_kernel)                                // likewise
+    LNS_SET_LDS(ensemble_obs_gram_kernel<4>)                             // 64 members: 67.5 KB of anomalies
+    LNS_SET_LDS(etkf_transform_kernel)                                   // 64 members: A and Q, 64 KB
+    LNS_SET_LDS(ensemble_transform_kernel)                               // 64 members: 64 KB of columns and X
 #undef LNS_SET_LDS
     return hipSuccess;
 }

@@ -434,6 +434,55 @@ int lns_op_ensemble_exceed(const float* frames, const float* y, int n, int B, in
     return LNS_OK;
 }
 
+// ensemble_obs_gram_kernel and its finish kernel on stored member fields: frames [n][B][M][C][H][W] against y_obs [B][n][C][H][W]
+// under rinv (+ b * rinv_bs + i * rinv_ss) -> S_out [B][n][M][M], g_out [B][n][M], stat_out [B][n][3], double
+int lns_op_ensemble_obs_gram(const float* frames, const float* y_obs, const float* rinv, int64_t rinv_bs, int64_t rinv_ss, int n, int B,
+                             int M, int C, int H, int W, const lns_eval_spec* norm, double* S_out, double* g_out, double* stat_out,
+                             void* stream) {
+    if (!frames || !y_obs || !rinv) return op_refuse("ensemble_obs_gram", "frames, y_obs or rinv is null");
+    if (!S_out || !g_out || !stat_out) return op_refuse("ensemble_obs_gram", "S_out, g_out or stat_out is null");
+    if (norm && op_spec_refused("ensemble_obs_gram", norm)) return LNS_EINVAL;
+    if (const char* why = etkf_members_refusal(M)) return op_refuse("ensemble_obs_gram", why);
+    if (op_ensemble_shape_refused("ensemble_obs_gram", n, B, C, H, W)) return LNS_EINVAL;
+    if (rinv_bs < 0 || rinv_ss < 0) return op_refuse("ensemble_obs_gram", "the strides of rinv must be >= 0 (0: shared)");
+    if (norm && op_spec_refused("ensemble_obs_gram", norm, C)) return LNS_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EnsembleObsGramArgs a;
+    obs_gram_args(norm, y_obs, rinv, rinv_bs, rinv_ss, B, M, C, H, W, &a);
+    a.frames = frames; a.kk = n; a.y_T = a.o_T = n; a.y_t = a.o_t = 0;
+    OpScratch sc;
+    a.part = static_cast<double*>(sc.alloc((size_t)B * n * a.nsl * etkf_part_doubles(M) * 2));
+    if (sc.ok()) sc.note(init_kernels());
+    if (sc.ok()) sc.note(launch_ensemble_obs_gram(a, s));
+    if (sc.ok()) sc.note(launch_ensemble_obs_gram_finish(a.part, B * n, a.nsl, M, S_out, g_out, stat_out, s));
+    OPCHK(sc.finish(s));
+    return LNS_OK;
+}
+
+// etkf_transform_kernel: S [B][n][M][M], g [B][n][M] -> X [B][M][M], wbar [B][M], lam [B][M], status [B]; never synchronises
+int lns_op_etkf_transform(const double* S, const double* g, int B, int n, int M, double rho, double* X, double* wbar, double* lam,
+                          int32_t* status, void* stream) {
+    if (!S || !g) return op_refuse("etkf_transform", "S or g is null");
+    if (!X || !wbar || !lam || !status) return op_refuse("etkf_transform", "X, wbar, lam or status is null");
+    if (const char* why = etkf_members_refusal(M)) return op_refuse("etkf_transform", why);
+    if (B < 1 || n < 1) return op_refuse("etkf_transform", "B, n >= 1");
+    if (const char* why = etkf_rho_refusal(rho)) return op_refuse("etkf_transform", why);
+    OPCHK(init_kernels());
+    const EtkfTransformArgs a = {S, g, X, wbar, lam, status, rho, B, n, M};
+    OPCHK(launch_etkf_transform(a, static_cast<hipStream_t>(stream)));
+    return LNS_OK;
+}
+
+// ensemble_transform_kernel: z [B][M][n], X [B][M][M] -> out [B][M][n] (may be z); never synchronises
+int lns_op_ensemble_transform(const float* z, const double* X, int B, int M, int64_t n, float* out, void* stream) {
+    if (!z || !X || !out) return op_refuse("ensemble_transform", "z, X or out is null");
+    if (const char* why = etkf_members_refusal(M)) return op_refuse("ensemble_transform", why);
+    if (B < 1 || B > LNS_MAX_BATCH || n < 1 || n > ((int64_t)1 << 38)) return op_refuse("ensemble_transform", "B in 1..65535, n in 1..2^38");
+    OPCHK(init_kernels());
+    OPCHK(launch_ensemble_transform(z, X, B, M, (long)n, out, static_cast<hipStream_t>(stream)));
+    return LNS_OK;
+}
+
 int lns_spectrum_bins(int H, int W) {
     const int S = lns_spectrum::bins(H, W);
     return S < 0 ? LNS_EINVAL : S;

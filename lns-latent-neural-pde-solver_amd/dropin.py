@@ -495,6 +495,49 @@ class LatentDynamics(_Hosted):
         z_obs = z_obs.reshape((B, n_obs) + tuple(z_obs.shape[1:]))
         return fitter.run(z0, z_obs, obs_steps, param=param, weights=weights, iters=iters)
 
+    @torch.no_grad()
+    def assimilate_ensemble(self, x0, y_obs, obs_steps, *rest, rinv, inflation=1.0, window=1, generator=None, param_spread=0.0,
+                            **norm):
+        """assimilate_ensemble(x0, y_obs, obs_steps, members, noise_level, rinv=...) -- conditional:
+        assimilate_ensemble(x0, y_obs, obs_steps, param, members, noise_level, rinv=...): an ensemble of forecasts from x0
+        corrected by SPARSE observations of the decoded fields (a few sensors, one channel, a masked region) with an ensemble
+        transform Kalman filter (lns_amd.enkf.EnsembleFilter) -- where `assimilate` needs complete frames it can encode.
+        x0 [B,C,Ly,Lx] is encoded and perturbed as `predict_ensemble` does without a control member; y_obs
+        [B,n_obs,C,Ly,Lx]: the normalised observations at the rollout steps `obs_steps` (`assimilate`'s convention: step 0 =
+        one propagator step after x0), any value where rinv is 0; rinv: the inverse observation-error variance per value,
+        [C,Ly,Lx], [n_obs,C,Ly,Lx] or [B,n_obs,C,Ly,Lx], in the units `norm` gives (`validate`'s arguments; none:
+        normalised units); inflation >= 1; window: observations taken in per analysis; param_spread > 0: param [B] becomes
+        param + randn * param_spread per member and is estimated with the state (also with a conditional encoder).
+        Returns enkf.EnKFResult; `model._engine(z).rollout_latent_ensemble(result.z, steps, param=result.param)` forecasts
+        from the analysis, which stands at the last observed step."""
+        from . import enkf as _enkf
+        param = None
+        if self._conditional:
+            if not rest:
+                raise TypeError("assimilate_ensemble() missing required argument: 'param'")
+            param, rest = rest[0], rest[1:]
+        if len(rest) != 2:
+            raise TypeError("assimilate_ensemble() takes (x0, y_obs, obs_steps, param, members, noise_level)" if self._conditional
+                            else "assimilate_ensemble() takes (x0, y_obs, obs_steps, members, noise_level)")
+        members, noise_level = int(rest[0]), float(rest[1])
+        if members < 2:
+            raise LnsError("the filter needs at least 2 members, got %d" % members)
+        x0 = self._fields(x0)
+        if y_obs.dim() != 5 or y_obs.shape[0] != x0.shape[0] or y_obs.shape[2:] != x0.shape[1:]:
+            raise LnsError("y_obs must be [B,n_obs,C,Ly,Lx] matching x0 %s, got %s" % (tuple(x0.shape), tuple(y_obs.shape)))
+        if bool(getattr(self.args, "cond_encoder", False)):
+            from . import metrics as _metrics        # (the encoder reads the first-guess param; the filter then moves the members')
+            z0 = _metrics.encode_dataset(self._ae, x0, chunk=32, out_device=x0.device, param=param)
+            B = z0.shape[0]
+            z = z0[:, None] + torch.randn((B, members) + tuple(z0.shape[1:]), device=z0.device, dtype=z0.dtype,
+                                          generator=generator) * noise_level
+        else:
+            z = self._ensemble_latents(x0, members, noise_level, generator, False)
+        if param is not None and float(param_spread) > 0.0:
+            p = torch.as_tensor(param, device=z.device, dtype=torch.float32).reshape(-1, 1)
+            param = p + torch.randn((p.shape[0], members), device=z.device, generator=generator) * float(param_spread)
+        return _enkf.EnsembleFilter(self, inflation).run(z.contiguous(), y_obs, rinv, obs_steps, window=window, param=param, **norm)
+
     def lyapunov(self, x, steps, *rest, k=4, **kw):
         """lyapunov(x, steps, k=4, ...) -- conditional: lyapunov(x, steps, param, k=4, ...): the k leading finite-time
         Lyapunov exponents of the learned dynamics along the `steps`-step forecast started at the frame x [B,C,Ly,Lx]

@@ -328,6 +328,12 @@ def quantile_spec(C, members, quantiles=(), thresholds=()):
     return spec
 
 
+EnsembleAnalysis = collections.namedtuple("EnsembleAnalysis", "z param X wbar lam stat status mean var z_last")
+EnsembleAnalysis.__doc__ = """Result of Engine.rollout_latent_ensemble_analysis: z [B, M, c, h, w] the analysis latents (the forecast
+latents of the last step transformed by X), param [B, M] the transformed per-member param (None unless it was given per
+member), X [B, M, M], wbar [B, M], lam [B, M] (the eigenvalues of (M-1)/rho I + S, ascending) and stat [B, n_keep, 3] (the
+forecast mean's weighted misfit sum r d^2, sum r, the number of observed values) in float64, status [B] int32 (0 ok, 1 non-finite
+Gram, 2 not converged), and (return_mean / return_var / return_last) rollout_latent_ensemble's outputs."""
 EnsembleExceedance = collections.namedtuple("EnsembleExceedance", "table mean var z_last")
 EnsembleExceedance.__doc__ = """Result of Engine.rollout_latent_ensemble_exceed: table [B, n_keep, n_thr, C, 2, M + 1] int32, the
 number of a plane's pixels with the truth above the threshold (index 1 of dim 4) or not (index 0) and n of the M members above
@@ -1038,6 +1044,149 @@ class Engine:
                 ctypes.byref(spec) if spec is not None else None, table.data_ptr(), self._ptr(mean), self._ptr(var),
                 self._ptr(z_last), ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_exceed")
         return EnsembleExceedance(table, mean, var, z_last)
+
+    # -- ensemble transform Kalman filter (include/lns.h "ensemble transform Kalman filter") --------------------------
+    @staticmethod
+    def _rinv(rinv, B, n, tail, device):
+        """rinv [C, H, W] (shared), [n, C, H, W] (per step) or [B, n, C, H, W] -> (fp32 contiguous tensor, batch stride, step
+        stride) as lns_op_ensemble_obs_gram addresses it."""
+        import torch
+        if not isinstance(rinv, torch.Tensor) or not rinv.is_cuda or rinv.dtype != torch.float32 or rinv.device != device:
+            raise LnsError("rinv must be an fp32 HIP tensor on the device of the fields")
+        per = int(tail[0] * tail[1] * tail[2])
+        shape = tuple(rinv.shape)
+        if shape == tuple(tail):
+            return rinv.contiguous(), 0, 0
+        if shape == (n,) + tuple(tail):
+            return rinv.contiguous(), 0, per
+        if shape == (B, n) + tuple(tail):
+            return rinv.contiguous(), n * per, per
+        raise LnsError("rinv must be %s, %s or %s, got %s" % (tuple(tail), (n,) + tuple(tail), (B, n) + tuple(tail), shape))
+
+    def ensemble_obs_gram(self, frames, y_obs, rinv, **norm):
+        """The Gram kernel of the ensemble Kalman filter on stored member fields (lns_op_ensemble_obs_gram): frames
+        [n, B, M, C, H, W] (a frame buffer's layout), y_obs [B, n, C, H, W], both normalised; rinv: the inverse
+        observation-error variance per value, [C, H, W], [n, C, H, W] or [B, n, C, H, W] (0: not observed); `norm` as in
+        `rollout_eval` (none: the values as they are).  Returns (S [B, n, M, M], g [B, n, M], stat [B, n, 3]) in float64."""
+        import torch
+        for t in (frames, y_obs):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+                raise LnsError("ensemble_obs_gram takes fp32 HIP tensors")
+        if frames.dim() != 6 or y_obs.dim() != 5 or y_obs.device != frames.device:
+            raise LnsError("ensemble_obs_gram takes frames [n, B, M, C, H, W] and y_obs [B, n, C, H, W] on one device")
+        n, B, M, C, H, W = (int(v) for v in frames.shape)
+        if tuple(y_obs.shape) != (B, n, C, H, W):
+            raise LnsError("y_obs must be %s for frames %s, got %s" % ((B, n, C, H, W), tuple(frames.shape), tuple(y_obs.shape)))
+        frames, y_obs = frames.contiguous(), y_obs.contiguous()
+        r, r_bs, r_ss = self._rinv(rinv, B, n, (C, H, W), frames.device)
+        spec = eval_spec(C, **norm) if norm else None
+        S = torch.empty((B, n, M, M), dtype=torch.float64, device=frames.device)
+        g = torch.empty((B, n, M), dtype=torch.float64, device=frames.device)
+        stat = torch.empty((B, n, 3), dtype=torch.float64, device=frames.device)
+        with torch.cuda.device(frames.device):
+            rc = self._L.lns_op_ensemble_obs_gram(frames.data_ptr(), y_obs.data_ptr(), r.data_ptr(), r_bs, r_ss, n, B, M, C, H, W,
+                                                  ctypes.byref(spec) if spec is not None else None, S.data_ptr(), g.data_ptr(),
+                                                  stat.data_ptr(), self._stream(frames))
+        if rc != 0:
+            raise LnsError("lns_op_ensemble_obs_gram failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return S, g, stat
+
+    def etkf_transform(self, S, g, rho=1.0):
+        """The transform kernel of the filter (lns_op_etkf_transform): S [B, n, M, M], g [B, n, M] float64 (summed over the n
+        steps) and the multiplicative inflation rho >= 1 -> (X [B, M, M], wbar [B, M], lam [B, M] ascending, status [B] int32:
+        0 ok, 1 non-finite Gram (that sample's X is NaN), 2 not converged).  Nothing is read back."""
+        import torch
+        for t in (S, g):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
+                raise LnsError("etkf_transform takes float64 HIP tensors")
+        if S.dim() != 4 or S.shape[2] != S.shape[3] or tuple(g.shape) != tuple(S.shape[:3]) or g.device != S.device:
+            raise LnsError("etkf_transform takes S [B, n, M, M] and g [B, n, M] on one device, got %s and %s" % (tuple(S.shape), tuple(g.shape)))
+        B, n, M = (int(v) for v in S.shape[:3])
+        S, g = S.contiguous(), g.contiguous()
+        X = torch.empty((B, M, M), dtype=torch.float64, device=S.device)
+        wbar = torch.empty((B, M), dtype=torch.float64, device=S.device)
+        lam = torch.empty((B, M), dtype=torch.float64, device=S.device)
+        status = torch.empty((B,), dtype=torch.int32, device=S.device)
+        with torch.cuda.device(S.device):
+            rc = self._L.lns_op_etkf_transform(S.data_ptr(), g.data_ptr(), B, n, M, float(rho), X.data_ptr(), wbar.data_ptr(),
+                                               lam.data_ptr(), status.data_ptr(), self._stream(S))
+        if rc != 0:
+            raise LnsError("lns_op_etkf_transform failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return X, wbar, lam, status
+
+    def ensemble_transform(self, z, X, out=None):
+        """The update kernel of the filter (lns_op_ensemble_transform): z [B, M, ...] fp32, X [B, M, M] float64 -> the members
+        transformed about their mean, out_m = zbar + sum_k (z_k - zbar) X_km; out may be z itself.  [B, M] is the update of
+        a per-member param."""
+        import torch
+        if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.float32 or z.dim() < 2 or not z.is_contiguous():
+            raise LnsError("ensemble_transform takes a contiguous fp32 HIP tensor [B, M, ...]")
+        B, M = int(z.shape[0]), int(z.shape[1])
+        if not isinstance(X, torch.Tensor) or X.dtype != torch.float64 or X.device != z.device or tuple(X.shape) != (B, M, M):
+            raise LnsError("X must be float64 %s on the device of z, got %s" % ((B, M, M), tuple(getattr(X, "shape", ()))))
+        if out is None:
+            out = torch.empty_like(z)
+        elif out.shape != z.shape or out.dtype != z.dtype or out.device != z.device or not out.is_contiguous():
+            raise LnsError("out must be a contiguous tensor of z's shape, dtype and device")
+        n = z[0, 0].numel() if z.dim() > 2 else 1
+        with torch.cuda.device(z.device):
+            rc = self._L.lns_op_ensemble_transform(z.data_ptr(), X.contiguous().data_ptr(), B, M, n, out.data_ptr(), self._stream(z))
+        if rc != 0:
+            raise LnsError("lns_op_ensemble_transform failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return out
+
+    def rollout_latent_ensemble_analysis(self, z, y_obs, rinv, steps, param=None, keep_steps=None, rho=1.0, return_mean=False,
+                                         return_var=False, return_last=False, **norm):
+        """One window of the ensemble transform Kalman filter: rollout_latent_ensemble over `steps` steps with the decoded
+        members compared with sparse observations as they are decoded, and the forecast latents of the last step corrected
+        by them.  z [B, M, c, h, w] (2 <= M <= 64); keep_steps: the observed steps (None: every step); y_obs
+        [B, n_keep, C, Ly, Lx]: the normalised observations of those steps (any value where rinv is 0); rinv [C, Ly, Lx],
+        [n_keep, C, Ly, Lx] or [B, n_keep, C, Ly, Lx]: the inverse observation-error variance in the units of the values
+        (`norm` as in `rollout_eval`; none: normalised units); rho >= 1: the multiplicative inflation; param: per trajectory
+        or per member -- given per member ([B, M]) it is updated by the same transform.  Returns EnsembleAnalysis.  The
+        member fields are never stored and nothing is read back."""
+        import torch
+        z = self._dev(z)
+        y_obs = self._dev(y_obs)
+        C, H, W = self.latent_shape()
+        c = self.cfg
+        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
+            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
+        B, M = int(z.shape[0]), int(z.shape[1])
+        steps = int(steps)
+        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
+        nk = len(keep)
+        tail = (c.in_channels, c.Ly, c.Lx)
+        if tuple(y_obs.shape) != (B, nk) + tail or y_obs.device != z.device:
+            raise LnsError("y_obs must be %s on the latents' device, got %s" % ((B, nk) + tail, tuple(y_obs.shape)))
+        if return_var and not return_mean:
+            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
+        arr = (ctypes.c_int * nk)(*keep)
+        y_obs = y_obs.contiguous()
+        r, r_bs, r_ss = self._rinv(rinv, B, nk, tail, z.device)
+        spec = eval_spec(c.in_channels, **norm) if norm else None
+        f64 = dict(dtype=torch.float64, device=z.device)
+        za = torch.empty_like(z)
+        p = self._member_param(param, z, B, M)
+        per_member = p is not None and torch.as_tensor(param).numel() == B * M and M > 1
+        pa = torch.empty_like(p) if per_member else None
+        X, wbar, lam = torch.empty((B, M, M), **f64), torch.empty((B, M), **f64), torch.empty((B, M), **f64)
+        stat = torch.empty((B, nk, 3), **f64)
+        status = torch.empty((B,), dtype=torch.int32, device=z.device)
+        mean = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_mean else None
+        var = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_var else None
+        z_last = torch.empty_like(z) if return_last else None
+        with torch.cuda.device(z.device):
+            n = ctypes.c_size_t(0)
+            self._check(self._L.lns_rollout_ensemble_analysis_workspace_bytes(self._h, B, M, nk, ctypes.byref(n)),
+                        "lns_rollout_ensemble_analysis_workspace_bytes")
+            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+            self._check(self._L.lns_rollout_latent_ensemble_analysis(
+                self._h, z.data_ptr(), self._ptr(p), y_obs.data_ptr(), r.data_ptr(), r_bs, r_ss, B, M, steps, arr, nk,
+                ctypes.byref(spec) if spec is not None else None, float(rho), za.data_ptr(), self._ptr(pa), X.data_ptr(),
+                wbar.data_ptr(), lam.data_ptr(), stat.data_ptr(), status.data_ptr(), self._ptr(mean), self._ptr(var),
+                self._ptr(z_last), ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_analysis")
+        return EnsembleAnalysis(za, pa, X, wbar, lam, stat, status, mean, var, z_last)
 
     # -- streaming validation rollout (include/lns.h "streaming validation rollout") --------------------------------
     def _eval_common(self, first, y, steps, t0, keep_steps, norm):

@@ -3,8 +3,9 @@
 sha256 of its bytes} for every rollout entry point of `Engine` (rollout, rollout with to_x=False, rollout with keep_steps,
 rollout_latent, rollout_latent with keep_steps, rollout_eval, rollout_latent_eval in one chunk and in two, 4 + 3,
 rollout_latent_ensemble with M = 3 members, rollout_latent_ensemble_eval, rollout_latent_ensemble_quantiles (three quantiles,
-one threshold, mean / var / z_last as well) and rollout_latent_ensemble_exceed (the same threshold against y; mean / var / z_last
-as well) on the same members where the library has them, and
+one threshold, mean / var / z_last as well), rollout_latent_ensemble_exceed (the same threshold against y; mean / var / z_last
+as well) and rollout_latent_ensemble_analysis (every 4th pixel of channel 0 of y observed at the kept steps, rho = 1.1; z, X, wbar,
+lam, stat, status, mean / var / z_last) on the same members where the library has them, and
 the six newer scored calls -- rollout_eval_spectrum / _stats / _maps from x and their rollout_latent_ forms in two chunks, 4 + 3:
 spectra at steps [0, 3, 6], statistics at [1, 2, 6] with an 8-bin histogram, maps from step 1 every 2, the _maps forms with all
 three selections together; every tensor they return is hashed, the chunks' per-step tensors concatenated) under
@@ -163,6 +164,13 @@ def entries(eng, x, y, p):
             r = eng.rollout_latent_ensemble_exceed(ze, y, T, THRESHOLDS, param=p, keep_steps=KEEP, return_mean=True, return_var=True,
                                                    return_last=True, **NORM)
             yield "rollout_latent_ensemble_exceed", dict(table=r.table, mean=r.mean, var=r.var, z_last=r.z_last)
+        if eng._L.lns_build_has(b"ensemble_etkf") == 1:
+            rinv = torch.zeros(tuple(y.shape[2:]), device=y.device)
+            rinv[0].view(-1)[::4] = 4.0                             # every 4th pixel of channel 0 observed
+            r = eng.rollout_latent_ensemble_analysis(ze, y[:, KEEP].contiguous(), rinv, T, param=p, keep_steps=KEEP, rho=1.1,
+                                                     return_mean=True, return_var=True, return_last=True, **NORM)
+            yield "rollout_latent_ensemble_analysis", dict(z=r.z, X=r.X, wbar=r.wbar, lam=r.lam, stat=r.stat, status=r.status,
+                                                           mean=r.mean, var=r.var, z_last=r.z_last)
     for name, sel in (("spectrum", dict(spectrum_steps=SPECTRUM_STEPS)), ("stats", dict(stats_steps=STATS_STEPS, hist=HIST)),
                       ("maps", dict(map_steps=MAP_STEPS, stats_steps=STATS_STEPS, hist=HIST, spectrum_steps=SPECTRUM_STEPS))):
         if eng._L.lns_build_has(b"eval_" + name.encode()) == 1:
