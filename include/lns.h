@@ -537,6 +537,73 @@ int lns_rollout_latent_ensemble_analysis(lns_engine* e, const float* z_in, const
                                          float* param_analysis, double* X, double* wbar, double* lam, double* stat,
                                          int32_t* status, float* mean_out, float* var_out, float* z_last, /* all nullable */
                                          void* workspace, size_t workspace_bytes, void* stream);
+/* The localised form of this filter, one transform per latent pixel: the next section. */
+
+/* ---- localised ensemble transform Kalman filter: one transform per latent pixel (LETKF) ------------------------------
+ * The transform above lies in the span of M - 1 anomaly directions while a latent has hundreds to thousands of degrees of
+ * freedom: a sensor in one corner of the plane corrects the latent in the opposite corner through sampling noise alone.
+ * The cure is localisation (Hunt, Kostelich, Szunyogh 2007: the LOCAL ETKF), here R-localisation at patch granularity.  The
+ * latent of every family is a convolutional [c][h][w] grid over the plane: the decoded frame is cut into the h x w patches of
+ * that grid, the Gram sums are taken per patch, the Gram of the local domain of latent pixel l is the Gaspari-Cohn-weighted
+ * sum of the patch Grams around it, one Jacobi problem is solved per (sample, latent pixel), and X_l is applied to the c
+ * channels of latent pixel l.  A per-member param is not spatial: it is updated by the global transform, taken from the same
+ * patch sums with weight 1.  Notation as above; the frame is [C][Ly][Lx], the latent [c][h][w], l = i * w + j.
+ *
+ * 1. Patches: value p = (ch, y, x) belongs to patch t = ty * w + tx, ty = (y * h) / Ly, tx = (x * w) / Lx in integer arithmetic
+ *     (61 x 121 on 7 x 15: patches of 8 or 9 rows and columns).  A patch may be empty (h > Ly); its sums are 0.
+ * 2. Patch Gram (per sample b, kept step i and patch t; double): f_m, y, ybar, Y_m, d, w_m = r_p Y_m exactly as in step 1 above,
+ *     the one denormalisation device function and the select on r_p > 0 included (unobserved values are not read; NaN there is
+ *     harmless).  G_ij (i <= j, G_ji = G_ij), g_i and stat as S_ij, g_i and stat above over the values of the patch: every sum
+ *     starts at 0 and takes one fused multiply-add per value of the patch, p ascending (channel, then row, then column); sum r_p:
+ *     plain adds.  No slices, no atomics: the result depends on the inputs only.
+ * 3. Taper: domain l = (i, j), patch t = (ti, tj): dy = |i - ti|, replaced by min(dy, h - dy) where the y axis is periodic; dx
+ *     likewise along x with w.  dist = sqrt((double)(dy*dy + dx*dx)), r = dist / radius, radius the Gaspari-Cohn half-width in
+ *     latent pixels (support 2 radius).  With r2 = r r, r3 = r2 r, r4 = r3 r, r5 = r4 r, the terms added from the left in the
+ *     order written, nothing fused, the constants 5/3, 5/8, 1/12 each the double quotient:
+ *         r <= 1:     rho = (((1 - (5/3) r2) + (5/8) r3) + (1/2) r4) - (1/4) r5
+ *         1 < r < 2:  rho = max(0, (((((4 - 5 r) + (5/3) r2) + (5/8) r3) - (1/2) r4) + (1/12) r5) - 2 / (3 r))
+ *         r >= 2:     rho = 0
+ *     Only + - * / sqrt in IEEE double: a numpy statement of it is held to the bit.
+ * 4. Local Gram (per sample and domain; double, nothing fused):
+ *         S_l = sum_steps (ascending) sum_t (ascending, rho_lt > 0) rho_lt * G_t,   g_l likewise
+ *     as acc = acc + rho * G starting at 0.  S_glob, g_glob: the same sums with rho = 1 over all patches; stat [B][n_keep][3]: per
+ *     kept step the sum over all patches, ascending.
+ * 5. Transform: step 2 above on (S_l, g_l) for each of the B * h * w domains and once per sample on (S_glob, g_glob) -- the same
+ *     kernel, launched with B * h * w blocks (and with B) and n = 1.  Status 1 (a non-finite Gram) marks that domain alone.
+ * 6. Update (per sample b, latent pixel l and channel ch, over the M values z_k = z[b][k][ch][l]): zbar, Z_k and
+ *         out[b][m][ch][l] = (float)(zbar + sum_k Z_k X_l[k][m])
+ *     in the arithmetic and order of step 3 above.  A block reads all it needs before it writes: out may be z.
+ *     param_analysis is step 3 above with X_glob.
+ * A domain whose support holds no observed value has S_l = 0, hence X_l = sqrt(rho_infl) I and wbar = 0: it keeps its forecast
+ * members, apart from inflation.  That is the property that makes the filter local.
+ *
+ * Not there: M > 64, additive inflation, correlated observation errors, observation operators that are not pointwise in the
+ * decoded frame, domains finer or coarser than a latent pixel, a taper other than Gaspari-Cohn, a latent grid above
+ * LNS_LETKF_MAX_DOMAINS = 4096 pixels.  The receptive field of the decoder is wider than a patch: the localisation is a
+ * modelling choice about which observations may move which latent pixel, not a statement about the decoder.
+ *
+ * The call: the arguments of lns_rollout_latent_ensemble_analysis plus loc_radius (finite, > 0) and bc_y / bc_x
+ * (LNS_FLOW_PERIODIC / LNS_FLOW_WALL: whether the taper's distance wraps along that axis).  Nullable outputs: X_local
+ * [B][h*w][M][M], wbar_local and lam_local [B][h*w][M] (double), status_local [B][h*w] (int32); the global X [B][M][M], wbar, lam
+ * [B][M], status [B] and stat [B][n_keep][3] of (S_glob, g_glob); param_analysis, mean_out, var_out, z_last as above.  The
+ * patch-Gram launch follows the decode of each group on its decode stream; combine, the two transform launches and the updates
+ * follow the join on the caller's stream.  No host read, no allocation, no event beyond those of the call above.
+ * workspace: lns_rollout_ensemble_analysis_local_workspace_bytes(B, M, n_keep) = the ensemble layout byte for byte, then one
+ * region: the patch sums [B][n_keep][h*w][M*M + M + 3] doubles, which dominate it, then S_l, g_l, X_l, wbar_l, lam_l, status_l and
+ * the global S, g, stat, X, wbar, lam, status.  A window of a few observed steps is the intended use.
+ * Refused before any device work (lns_last_error), in the order of the call above, with two checks directly after the one on
+ * rho: "loc_radius must be finite and > 0", then "bc_y / bc_x must be LNS_FLOW_PERIODIC or LNS_FLOW_WALL"; and a latent grid
+ * above 4096 pixels after the check of norm. */
+#define LNS_LETKF_MAX_DOMAINS 4096
+int lns_rollout_ensemble_analysis_local_workspace_bytes(lns_engine* e, int B, int M, int n_keep, size_t* bytes);
+int lns_rollout_latent_ensemble_analysis_local(lns_engine* e, const float* z_in, const float* param, const float* y_obs,
+                                               const float* rinv, int64_t rinv_bs, int64_t rinv_ss, int B, int M, int T,
+                                               const int* keep_steps_host, int n_keep, const lns_eval_spec* norm /* nullable */,
+                                               double rho, double loc_radius, int bc_y, int bc_x, float* z_analysis,
+                                               double* X_local, double* wbar_local, double* lam_local, int32_t* status_local,
+                                               float* param_analysis, double* X, double* wbar, double* lam, double* stat,
+                                               int32_t* status, float* mean_out, float* var_out, float* z_last, /* all nullable */
+                                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- streaming validation: energy spectra of forecast, truth and error ---------------------------------------------
  * lns_rollout_eval / lns_rollout_latent_eval with, for selected steps, the shell-summed energy spectra of the forecast,
@@ -1269,7 +1336,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * "latent_fit" = lns_train_backward_ex, lns_loss_obs_mse, its size query, lns_fit_step and its size query are there;
  * "rollout_tangent" = lns_train_tangent, its size query and lns_op_orthonormalize are there; "ensemble_etkf" =
  * lns_rollout_latent_ensemble_analysis, its size query, lns_op_ensemble_obs_gram, lns_op_etkf_transform and
- * lns_op_ensemble_transform are there.
+ * lns_op_ensemble_transform are there; "ensemble_letkf" = lns_rollout_latent_ensemble_analysis_local, its size query,
+ * lns_op_ensemble_patch_gram, lns_op_letkf_combine and lns_op_ensemble_transform_local are there.
  * 1 / 0; -1: unknown name.
  * (No reference counterpart: the reference is pure Python.) */
 int lns_build_has(const char* feature);
@@ -1493,6 +1561,27 @@ int lns_op_ensemble_obs_gram(const float* frames, const float* y_obs, const floa
 int lns_op_etkf_transform(const double* S, const double* g, int B, int n, int M, double rho, double* X, double* wbar,
                           double* lam, int32_t* status, void* stream);
 int lns_op_ensemble_transform(const float* z, const double* X, int B, int M, int64_t n, float* out, void* stream);
+
+/* The three kernels that lns_rollout_latent_ensemble_analysis_local adds, without an engine, by the statement written there
+ * (the transform between them is lns_op_etkf_transform on S_local viewed as [B * h * w][1][M][M]).  None synchronises.
+ * lns_op_ensemble_patch_gram: frames, y_obs, rinv, norm as lns_op_ensemble_obs_gram, the [C][H][W] frame cut into h x w patches
+ * -> part_out [B][n][h*w][M*M + M + 3] double: per patch G [M][M] (full, symmetric), g [M], stat [3]; an empty patch: zeros.
+ * Refusals in this order: frames, y_obs or rinv null; part_out null; norm of the wrong size; M outside 2 .. 64; the shape (as
+ * lns_op_ensemble_exceed); n > 65535; h or w < 1 or h * w > 4096; a negative stride; the per-channel norm with C > 8.
+ * lns_op_letkf_combine: part [B][n][h*w][M*M + M + 3] -> S_local [B][h*w][M][M], g_local [B][h*w][M], S_glob [B][M][M], g_glob
+ * [B][M], stat [B][n][3] (nullable).  Refusals: part null; an output but stat null; M outside 2 .. 64; B outside 1..65535 or
+ * n < 1; the grid; loc_radius not finite or <= 0; bc_y / bc_x not LNS_FLOW_PERIODIC / LNS_FLOW_WALL.
+ * lns_op_ensemble_transform_local: z [B][M][c][h][w] fp32, X_local [B][h*w][M][M] double -> out [B][M][c][h][w], which may be z.
+ * Refusals: a null pointer; M outside 2 .. 64; B outside 1..65535 or c outside 1..65536; the grid.
+ * Messages: lns_create_error(). */
+int lns_op_ensemble_patch_gram(const float* frames, const float* y_obs, const float* rinv, int64_t rinv_bs, int64_t rinv_ss,
+                               int n, int B, int M, int C, int H, int W, int h, int w, const lns_eval_spec* norm /* nullable */,
+                               double* part_out, void* stream);
+int lns_op_letkf_combine(const double* part, int B, int n, int M, int h, int w, double loc_radius, int bc_y, int bc_x,
+                         double* S_local, double* g_local, double* S_glob, double* g_glob, double* stat /* nullable */,
+                         void* stream);
+int lns_op_ensemble_transform_local(const float* z, const double* X_local, int B, int M, int c, int h, int w, float* out,
+                                    void* stream);
 
 /* The spectrum kernel of lns_rollout_eval_spectrum on stored fields, without an engine: yhat and y (nullable) [B][T][C][H][W],
  * normalised -> out [B][T][C][K][S], K = 3 (forecast, truth, error) when y is given, K = 1 (the forecast's row, same bits) when

@@ -224,6 +224,8 @@ SYMBOLS = [
     "lns_rollout_latent_ensemble_exceed", "lns_op_ensemble_exceed",
     "lns_rollout_ensemble_analysis_workspace_bytes", "lns_rollout_latent_ensemble_analysis",
     "lns_op_ensemble_obs_gram", "lns_op_etkf_transform", "lns_op_ensemble_transform",
+    "lns_rollout_ensemble_analysis_local_workspace_bytes", "lns_rollout_latent_ensemble_analysis_local",
+    "lns_op_ensemble_patch_gram", "lns_op_letkf_combine", "lns_op_ensemble_transform_local",
     "lns_spectrum_bins", "lns_rollout_eval_spectrum", "lns_rollout_latent_eval_spectrum", "lns_op_energy_spectrum",
     "lns_spectrum_bins_basis", "lns_op_energy_spectrum_basis",
     "lns_rollout_eval_stats", "lns_rollout_latent_eval_stats", "lns_op_field_stats",
@@ -338,6 +340,15 @@ def lib():
         L.lns_op_ensemble_obs_gram.argtypes = [vp, vp, vp, i64, i64, i, i, i, i, i, i, sp, vp, vp, vp, vp]
         L.lns_op_etkf_transform.argtypes = [vp, vp, i, i, i, dbl, vp, vp, vp, vp, vp]
         L.lns_op_ensemble_transform.argtypes = [vp, vp, i, i, i64, vp, vp]
+    if hasattr(L, "lns_rollout_latent_ensemble_analysis_local"):
+        sp, ip, i64, dbl = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int), c.c_int64, c.c_double
+        L.lns_rollout_ensemble_analysis_local_workspace_bytes.argtypes = [vp, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_rollout_latent_ensemble_analysis_local.argtypes = [vp, vp, vp, vp, vp, i64, i64, i, i, i, ip, i, sp, dbl, dbl, i, i, vp,
+                                                                 vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                                 vp, c.c_size_t, vp]
+        L.lns_op_ensemble_patch_gram.argtypes = [vp, vp, vp, i64, i64, i, i, i, i, i, i, i, i, sp, vp, vp]
+        L.lns_op_letkf_combine.argtypes = [vp, i, i, i, i, i, dbl, i, i, vp, vp, vp, vp, vp, vp]
+        L.lns_op_ensemble_transform_local.argtypes = [vp, vp, i, i, i, i, i, vp, vp]
     if hasattr(L, "lns_rollout_eval_spectrum"):
         sp, ip = c.POINTER(LnsEvalSpec), c.POINTER(c.c_int)
         L.lns_spectrum_bins.argtypes = [i, i]

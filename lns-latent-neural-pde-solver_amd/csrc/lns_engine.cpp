@@ -1824,6 +1824,10 @@ struct RolloutCall {
     bool ens_obs = false; const float* rinv = nullptr; int64_t rinv_bs = 0, rinv_ss = 0; double rho = 1.0;
     float *z_analysis = nullptr, *param_analysis = nullptr;
     double *X_out = nullptr, *wbar_out = nullptr, *lam_out = nullptr, *stat_out = nullptr; int32_t* status_out = nullptr;
+    // ens_obs with ens_local (lns_rollout_latent_ensemble_analysis_local): the patch Gram takes the Gram's place; the taper's
+    // half-width and boundary codes, and the nullable per-domain outputs
+    bool ens_local = false; double loc_radius = 0.0; int bc_y = 0, bc_x = 0;
+    double *X_loc_out = nullptr, *wbar_loc_out = nullptr, *lam_loc_out = nullptr; int32_t* status_loc_out = nullptr;
     // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
     const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
     float *frame_out = nullptr, *seq_out = nullptr, *frames_out = nullptr;
@@ -2398,6 +2402,44 @@ static EtkfRegion etkf_region(const lns_engine* e, size_t B, size_t M, size_t n_
     return r;
 }
 
+// the refusals of the localised filter's taper (include/lns.h); nullptr: accepted
+static const char* letkf_radius_refusal(double radius) {
+    return !(radius > 0.0) || std::isinf(radius) ? "loc_radius must be finite and > 0" : nullptr;
+}
+static const char* letkf_bc_refusal(int bc_y, int bc_x) {
+    return (bc_y != LNS_FLOW_PERIODIC && bc_y != LNS_FLOW_WALL) || (bc_x != LNS_FLOW_PERIODIC && bc_x != LNS_FLOW_WALL)
+               ? "bc_y / bc_x must be LNS_FLOW_PERIODIC or LNS_FLOW_WALL" : nullptr;
+}
+
+// the patch Gram kernel's arguments (norm nullable); frames / part / kk / y_T / y_t / o_T / o_t are the caller's
+static void patch_gram_args(const lns_eval_spec* norm, const float* y, const float* rinv, int64_t r_bs, int64_t r_ss, int B, int M, int C,
+                            int H, int W, int h, int w, LetkfPatchGramArgs* gp) {
+    LetkfPatchGramArgs& g = *gp;
+    memset(&g, 0, sizeof g);
+    g.y = y; g.rinv = rinv; g.r_bs = (long)r_bs; g.r_ss = (long)r_ss;
+    g.B = B; g.M = M; g.C = C; g.H = H; g.W = W; g.h = h; g.w = w;
+    g.denorm = norm != nullptr;
+    if (norm) score_norm(norm, C, &g.norm);
+}
+
+// The region of lns_rollout_latent_ensemble_analysis_local behind the SINK_ENSEMBLE layout: the patch sums
+// [B][n_keep][h*w][M*M + M + 3], then per domain S [B][h*w][M][M], g [B][h*w][M], X [B][h*w][M][M], wbar, lam [B][h*w][M], status
+// [B][h*w], then the global S [B][M][M], g [B][M], stat [B][n_keep][3], X [B][M][M], wbar [B][M], lam [B][M], status [B]
+struct LetkfRegion { size_t part, S_loc, g_loc, X_loc, wbar_loc, lam_loc, status_loc, S, g, stat, X, wbar, lam, status, bytes; };
+static LetkfRegion letkf_region(const lns_engine* e, size_t B, size_t M, size_t n_keep) {
+    const size_t hw = (size_t)e->lat_H * e->lat_W, bd = B * hw;
+    LetkfRegion r;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off = round_up_sz(off + bytes, 256); return at; };
+    r.part = take(B * n_keep * hw * etkf_part_doubles((int)M) * 8);
+    r.S_loc = take(bd * M * M * 8); r.g_loc = take(bd * M * 8);
+    r.X_loc = take(bd * M * M * 8); r.wbar_loc = take(bd * M * 8); r.lam_loc = take(bd * M * 8); r.status_loc = take(bd * 4);
+    r.S = take(B * M * M * 8); r.g = take(B * M * 8); r.stat = take(B * n_keep * 3 * 8);
+    r.X = take(B * M * M * 8); r.wbar = take(B * M * 8); r.lam = take(B * M * 8); r.status = take(B * 4);
+    r.bytes = off;
+    return r;
+}
+
 // the autoregressive loop of every rollout call: zcur -> T x (propagate ; what the sink does)   (train_stage2_ns2d.py:147-156)
 // The latent chain z_t -> z_{t+1} is strictly sequential, but decode(z_t) depends on z_t only: the chain runs ahead
 // (on the engine's side stream when overlapping; own arena) writing groups of `kdec` consecutive decoded latents into
@@ -2469,7 +2511,13 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
         xa.y_T = xa.o_T = c.n_keep;
     }
     EnsembleObsGramArgs oa;
-    if (ens && c.ens_obs) {                          // the slice partials of kept step i land in the region's part[b][i]
+    LetkfPatchGramArgs pga;
+    if (ens && c.ens_obs && c.ens_local) {           // the patch sums of kept step i land in the region's part[b][i]
+        patch_gram_args(c.spec, c.y_true, c.rinv, c.rinv_bs, c.rinv_ss, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, e->lat_H,
+                        e->lat_W, &pga);
+        pga.part = reinterpret_cast<double*>(base + L.etkf_off + letkf_region(e, c.traj, c.M, c.n_keep).part);
+        pga.y_T = pga.o_T = c.n_keep;
+    } else if (ens && c.ens_obs) {                   // the slice partials of kept step i land in the region's part[b][i]
         obs_gram_args(c.spec, c.y_true, c.rinv, c.rinv_bs, c.rinv_ss, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, &oa);
         oa.part = reinterpret_cast<double*>(base + L.etkf_off + etkf_region(e, c.traj, c.M, c.n_keep).part);
         oa.y_T = oa.o_T = c.n_keep;
@@ -2654,7 +2702,10 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
             xa.frames = fb; xa.kk = kk; xa.y_t = xa.o_t = i0;
             HIPCHK(e, launch_ensemble_exceed(xa, dstream[d]));
         }
-        if (ens && c.ens_obs) {                      // fb is [kk][traj][M][xper] against y_obs[b][i0 .. i0 + kk) -> the slice partials of those steps
+        if (ens && c.ens_obs && c.ens_local) {       // fb is [kk][traj][M][xper] against y_obs[b][i0 .. i0 + kk) -> the patch sums of those steps
+            pga.frames = fb; pga.kk = kk; pga.y_t = pga.o_t = i0;
+            HIPCHK(e, launch_letkf_patch_gram(pga, dstream[d]));
+        } else if (ens && c.ens_obs) {               // fb is [kk][traj][M][xper] against y_obs[b][i0 .. i0 + kk) -> the slice partials of those steps
             oa.frames = fb; oa.kk = kk; oa.y_t = oa.o_t = i0;
             HIPCHK(e, launch_ensemble_obs_gram(oa, dstream[d]));
         }
@@ -2700,6 +2751,10 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
         if (!c.z_analysis) return einval(e, "z_analysis is null");
         if (c.rinv_bs < 0 || c.rinv_ss < 0) return einval(e, "the strides of rinv must be >= 0 (0: shared)");
         if (const char* why = etkf_rho_refusal(c.rho)) return einval(e, why);
+        if (c.ens_local) {
+            if (const char* why = letkf_radius_refusal(c.loc_radius)) return einval(e, why);
+            if (const char* why = letkf_bc_refusal(c.bc_y, c.bc_x)) return einval(e, why);
+        }
     }
     if ((scored || ens_scored || ens_exceed) && !c.y_true) return einval(e, "y_true is null");
     if (ens_scored && !c.scores_out) return einval(e, "scores_out is null");
@@ -2735,6 +2790,7 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
         if (c.param_analysis && !c.param) return einval(e, "param_analysis needs param");
         if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
         if (c.spec && c.spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "norm: the per-channel form needs in_channels <= 8");
+        if (c.ens_local && (long)e->lat_H * e->lat_W > LNS_LETKF_MAX_DOMAINS) return einval(e, "local ensemble analysis needs a latent grid of at most 4096 pixels");
     }
     if (scored) {
         if (c.t0 < 0 || (long)c.t0 + c.T > c.T_total) {
@@ -2823,13 +2879,19 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if (scored && c.maps) add_maps_region(e, c.B, &L);
     if (scored && c.attrib) add_attrib_region(e, c.B, &L);
     const bool ens_obs = c.sink == SINK_ENSEMBLE && c.ens_obs;
+    const bool ens_local = ens_obs && c.ens_local;
     EtkfRegion R = {};
-    if (ens_obs) {
+    LetkfRegion RL = {};
+    if (ens_local) {
+        RL = letkf_region(e, c.traj, c.M, c.n_keep);
+        L.etkf_off = round_up_sz(L.total, 256);
+        L.total = L.etkf_off + RL.bytes;
+    } else if (ens_obs) {
         R = etkf_region(e, c.traj, c.M, c.n_keep);
         L.etkf_off = round_up_sz(L.total, 256);
         L.total = L.etkf_off + R.bytes;
     }
-    if ((rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : (ens_obs ? "ensemble analysis " : (c.sink == SINK_ENSEMBLE ? "ensemble " : ""))),
+    if ((rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : (ens_local ? "local ensemble analysis " : (ens_obs ? "ensemble analysis " : (c.sink == SINK_ENSEMBLE ? "ensemble " : "")))),
                        c.ws, c.ws_bytes))) return rc;
     Plan* pe = nullptr;
     if (c.encode && (rc = get_plan(e, PK_ENC, c.B, 0, 0, &pe))) return rc;
@@ -2880,7 +2942,28 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if (c.sink == SINK_ENSEMBLE && c.ens_scored)     // likewise: the plane sums in scores_out -> the scores, in place
         HIPCHK(e, launch_ensemble_score_finish(c.scores_out, c.traj, c.n_keep, cfg.in_channels, cfg.Ly * cfg.Lx, c.spec->eps,
                                                c.seq_out, r.stream));
-    if (ens_obs) {
+    if (ens_local) {
+        // The localised filter, on the caller's stream behind the join, as the global one below: the patch sums of every decode
+        // stream and the copy of the last latents are ordered before it.  Every buffer has one writer and is read behind it
+        // in stream order.
+        char* rb = base + L.etkf_off;
+        auto dbl = [&](size_t off) { return reinterpret_cast<double*>(rb + off); };
+        const int hw = e->lat_H * e->lat_W;
+        LetkfCombineArgs ca = {dbl(RL.part), dbl(RL.S_loc), dbl(RL.g_loc), dbl(RL.S), dbl(RL.g), c.stat_out ? c.stat_out : dbl(RL.stat),
+                               c.loc_radius, c.traj, c.n_keep, c.M, e->lat_H, e->lat_W, c.bc_y, c.bc_x};
+        EtkfTransformArgs tl = {ca.S_loc, ca.g_loc, c.X_loc_out ? c.X_loc_out : dbl(RL.X_loc), c.wbar_loc_out ? c.wbar_loc_out : dbl(RL.wbar_loc),
+                                c.lam_loc_out ? c.lam_loc_out : dbl(RL.lam_loc),
+                                c.status_loc_out ? c.status_loc_out : reinterpret_cast<int*>(rb + RL.status_loc), c.rho, c.traj * hw, 1, c.M};
+        EtkfTransformArgs tg = {ca.S_glob, ca.g_glob, c.X_out ? c.X_out : dbl(RL.X), c.wbar_out ? c.wbar_out : dbl(RL.wbar),
+                                c.lam_out ? c.lam_out : dbl(RL.lam), c.status_out ? c.status_out : reinterpret_cast<int*>(rb + RL.status),
+                                c.rho, c.traj, 1, c.M};
+        HIPCHK(e, launch_letkf_combine(ca, r.stream));
+        HIPCHK(e, launch_etkf_transform(tl, r.stream));
+        HIPCHK(e, launch_etkf_transform(tg, r.stream));
+        const LetkfUpdateArgs ua = {c.z_last, tl.X, c.z_analysis, c.traj, c.M, e->lat_C, hw};
+        HIPCHK(e, launch_letkf_update(ua, r.stream));
+        if (c.param && c.param_analysis) HIPCHK(e, launch_ensemble_transform(c.param, tg.X, c.traj, c.M, 1, c.param_analysis, r.stream));
+    } else if (ens_obs) {
         // The filter, on the caller's stream behind the join: every Gram launch of the decode streams and the copy of the last
         // latents (c.z_last: the caller's buffer or z_analysis itself) are ordered before it.
         char* rb = base + L.etkf_off;
@@ -3232,6 +3315,39 @@ int lns_rollout_latent_ensemble_analysis(lns_engine* e, const float* z_in, const
     return rollout_call(e, c);
 }
 
+// ---- localised ensemble transform Kalman filter (include/lns.h) --------------------------------------------------
+int lns_rollout_ensemble_analysis_local_workspace_bytes(lns_engine* e, int B, int M, int n_keep, size_t* bytes) {
+    if (!e) return LNS_EINVAL;
+    if (B <= 0) return einval(e, "B must be positive");
+    if (M <= 0) return einval(e, "M must be positive");
+    if (const char* why = etkf_members_refusal(M)) { e->err = std::string("ensemble analysis needs ") + why; return LNS_EINVAL; }
+    if (n_keep < 1) return einval(e, "n_keep must be at least 1");
+    if ((long)e->lat_H * e->lat_W > LNS_LETKF_MAX_DOMAINS) return einval(e, "local ensemble analysis needs a latent grid of at most 4096 pixels");
+    size_t base = 0;
+    if (int rc = workspace_bytes(e, ensemble_batch(B, M), SINK_ENSEMBLE, &base)) return rc;
+    if (bytes) *bytes = round_up_sz(base, 256) + letkf_region(e, B, M, n_keep).bytes;
+    return LNS_OK;
+}
+
+int lns_rollout_latent_ensemble_analysis_local(lns_engine* e, const float* z_in, const float* param, const float* y_obs, const float* rinv,
+                                               int64_t rinv_bs, int64_t rinv_ss, int B, int M, int T, const int* keep_steps_host,
+                                               int n_keep, const lns_eval_spec* norm, double rho, double loc_radius, int bc_y, int bc_x,
+                                               float* z_analysis, double* X_local, double* wbar_local, double* lam_local,
+                                               int32_t* status_local, float* param_analysis, double* X_out, double* wbar_out,
+                                               double* lam_out, double* stat_out, int32_t* status_out, float* mean_out, float* var_out,
+                                               float* z_last, void* ws, size_t ws_bytes, void* stream) {
+    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
+    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
+    c.ens_obs = true; c.y_true = y_obs; c.rinv = rinv; c.rinv_bs = rinv_bs; c.rinv_ss = rinv_ss; c.spec = norm; c.rho = rho;
+    c.ens_local = true; c.loc_radius = loc_radius; c.bc_y = bc_y; c.bc_x = bc_x;
+    c.X_loc_out = X_local; c.wbar_loc_out = wbar_local; c.lam_loc_out = lam_local; c.status_loc_out = status_local;
+    c.z_analysis = z_analysis; c.param_analysis = param_analysis; c.X_out = X_out; c.wbar_out = wbar_out; c.lam_out = lam_out;
+    c.stat_out = stat_out; c.status_out = status_out;
+    c.out = mean_out; c.var_out = var_out;
+    c.z_last = z_last ? z_last : z_analysis;         // the forecast latents of step T - 1: the update reads them (in place without z_last)
+    return rollout_call(e, c);
+}
+
 int lns_check_finite(lns_engine* e, int B, void* ws, size_t ws_bytes, void* stream) {
     if (!e || B <= 0 || !ws) return LNS_EINVAL;
     // The amax vectors live in the CALLER's workspace: they are read through the `ws` handed in here, which must be
@@ -3331,6 +3447,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "ensemble_quantiles")) return 1;
     if (!strcmp(feature, "ensemble_exceed")) return 1;
     if (!strcmp(feature, "ensemble_etkf")) return 1;
+    if (!strcmp(feature, "ensemble_letkf")) return 1;
     if (!strcmp(feature, "eval_spectrum")) return 1;
     if (!strcmp(feature, "spectrum_basis")) return 1;
     if (!strcmp(feature, "eval_stats")) return 1;

@@ -495,6 +495,34 @@ hipError_t launch_etkf_transform(const EtkfTransformArgs& a, hipStream_t s);
 // z [B][M][n] fp32, X [B][M][M] double -> out [B][M][n] (may be z)
 hipError_t launch_ensemble_transform(const float* z, const double* X, int B, int M, long n, float* out, hipStream_t s);
 
+// Localised ensemble transform Kalman filter (lns_rollout_latent_ensemble_analysis_local, lns_op_ensemble_patch_gram,
+// lns_op_letkf_combine, lns_op_ensemble_transform_local; the statement: include/lns.h), ensemble_letkf.inc.
+// Patch Gram: EnsembleObsGramArgs' frames, observations and weights, the frame cut into the h x w patches of the latent grid
+// (value (ch, y, x) in patch ((y * h) / H) * w + (x * w) / W) -> part[(b * o_T + o_t + j) * h * w + patch][M * M + M + 3]: S (full,
+// symmetric), g, stat of the patch, all double.  Grid (h * w, B, kk); an empty patch writes zeros.  2 <= M <= 64.
+#define LNS_LETKF_MAX_DOMAINS 4096
+struct LetkfPatchGramArgs {
+    const float* frames; const float* y; const float* rinv; double* part;
+    long r_bs, r_ss;
+    int B, M, C, H, W, h, w, kk, y_T, y_t, o_T, o_t, denorm;
+    ScoreNorm norm;
+};
+hipError_t launch_letkf_patch_gram(const LetkfPatchGramArgs& a, hipStream_t s);
+// part [B][n][h * w][M * M + M + 3] -> S_loc [B][h * w][M][M], g_loc [B][h * w][M]: the Gaspari-Cohn-weighted sums over steps and
+// patches per domain (radius in latent pixels; bc_y / bc_x: 0 periodic, 1 wall), and S_glob [B][M][M], g_glob [B][M], stat [B][n][3]
+// (nullable): the same sums with weight 1.  Grid (ceil(h * w / 4) + 1, B, entries of (S, g) in chunks of 256): four domains a block,
+// one entry a thread; dynamic LDS 36 bytes per patch
+// (h * w <= LNS_LETKF_MAX_DOMAINS).
+struct LetkfCombineArgs {
+    const double* part; double* S_loc; double* g_loc; double* S_glob; double* g_glob; double* stat;
+    double radius;
+    int B, n, M, h, w, bc_y, bc_x;
+};
+hipError_t launch_letkf_combine(const LetkfCombineArgs& a, hipStream_t s);
+// z [B][M][c][hw] fp32, X [B][hw][M][M] double -> out [B][M][c][hw] (may be z): pixel l of every channel under X[b][l].  Grid (hw, B).
+struct LetkfUpdateArgs { const float* z; const double* X; float* out; int B, M, c, hw; };
+hipError_t launch_letkf_update(const LetkfUpdateArgs& a, hipStream_t s);
+
 // Energy spectra (lns_rollout_eval_spectrum, lns_op_energy_spectrum; the statement: include/lns.h): one block per plane
 // writes its K x S shell energies, K = 3 (forecast, truth, error) with y, K = 1 (forecast) without; S = lns_spectrum::bins(H, W, basis_y, basis_x).
 // Group form: frames [kk][B][C][H*W] (a decode stream's frame buffer); the n <= 8 selected steps sel[0 .. n) of the group

@@ -5315,6 +5315,7 @@ hipError_t launch_ensemble_score_finish(float* scores, int B, int T, int C, int 
 #include "ensemble_quantile.inc"
 #include "ensemble_exceed.inc"
 #include "ensemble_etkf.inc"
+#include "ensemble_letkf.inc"
 
 // per-sample max |x| of a [B, n] tensor: grid (chunks, B); one atomic per wave
 __global__ __launch_bounds__(256) void amax_kernel(const float* x, long x_bs, long n, unsigned* amax) {
@@ -5481,6 +5482,8 @@ hipError_t init_kernels() {
     LNS_SET_LDS(ensemble_score_kernel)                                   // 128 members: 128 KB of columns
     LNS_SET_LDS(ensemble_quantile_kernel)                                // likewise
     LNS_SET_LDS(ensemble_obs_gram_kernel<4>)                             // 64 members: 67.5 KB of anomalies
+    LNS_SET_LDS(letkf_patch_gram_kernel<4>)                              // likewise
+    LNS_SET_LDS(letkf_combine_kernel)                                    // 4096 domains: 144 KB of weights and the patch list
     LNS_SET_LDS(etkf_transform_kernel)                                   // 64 members: A and Q, 64 KB
     LNS_SET_LDS(ensemble_transform_kernel)                               // 64 members: 64 KB of columns and X
 #undef LNS_SET_LDS

@@ -483,6 +483,62 @@ int lns_op_ensemble_transform(const float* z, const double* X, int B, int M, int
     return LNS_OK;
 }
 
+// the latent grid of the three localised ops: h, w >= 1 and h * w <= LNS_LETKF_MAX_DOMAINS
+static_assert(LNS_LETKF_MAX_DOMAINS == 4096, "the messages here and in lns_engine.cpp say 4096");
+static const char* letkf_grid_refusal(int h, int w) {
+    return h < 1 || w < 1 || (int64_t)h * w > LNS_LETKF_MAX_DOMAINS ? "h, w >= 1 and h * w <= 4096 (the latent grid)" : nullptr;
+}
+
+// letkf_patch_gram_kernel on stored member fields: frames [n][B][M][C][H][W] against y_obs [B][n][C][H][W] under rinv (+ b * rinv_bs
+// + i * rinv_ss), the frame cut into h x w patches -> part_out [B][n][h*w][M*M + M + 3] double; never synchronises
+int lns_op_ensemble_patch_gram(const float* frames, const float* y_obs, const float* rinv, int64_t rinv_bs, int64_t rinv_ss, int n, int B,
+                               int M, int C, int H, int W, int h, int w, const lns_eval_spec* norm, double* part_out, void* stream) {
+    if (!frames || !y_obs || !rinv) return op_refuse("ensemble_patch_gram", "frames, y_obs or rinv is null");
+    if (!part_out) return op_refuse("ensemble_patch_gram", "part_out is null");
+    if (norm && op_spec_refused("ensemble_patch_gram", norm)) return LNS_EINVAL;
+    if (const char* why = etkf_members_refusal(M)) return op_refuse("ensemble_patch_gram", why);
+    if (op_ensemble_shape_refused("ensemble_patch_gram", n, B, C, H, W)) return LNS_EINVAL;
+    if (n > 65535) return op_refuse("ensemble_patch_gram", "n in 1..65535");
+    if (const char* why = letkf_grid_refusal(h, w)) return op_refuse("ensemble_patch_gram", why);
+    if (rinv_bs < 0 || rinv_ss < 0) return op_refuse("ensemble_patch_gram", "the strides of rinv must be >= 0 (0: shared)");
+    if (norm && op_spec_refused("ensemble_patch_gram", norm, C)) return LNS_EINVAL;
+    OPCHK(init_kernels());
+    LetkfPatchGramArgs a;
+    patch_gram_args(norm, y_obs, rinv, rinv_bs, rinv_ss, B, M, C, H, W, h, w, &a);
+    a.frames = frames; a.part = part_out; a.kk = n; a.y_T = a.o_T = n; a.y_t = a.o_t = 0;
+    OPCHK(launch_letkf_patch_gram(a, static_cast<hipStream_t>(stream)));
+    return LNS_OK;
+}
+
+// letkf_combine_kernel: part [B][n][h*w][M*M + M + 3] -> S_local [B][h*w][M][M], g_local [B][h*w][M], S_glob [B][M][M], g_glob [B][M],
+// stat [B][n][3] (nullable); never synchronises
+int lns_op_letkf_combine(const double* part, int B, int n, int M, int h, int w, double loc_radius, int bc_y, int bc_x, double* S_local,
+                         double* g_local, double* S_glob, double* g_glob, double* stat, void* stream) {
+    if (!part) return op_refuse("letkf_combine", "part is null");
+    if (!S_local || !g_local || !S_glob || !g_glob) return op_refuse("letkf_combine", "S_local, g_local, S_glob or g_glob is null");
+    if (const char* why = etkf_members_refusal(M)) return op_refuse("letkf_combine", why);
+    if (B < 1 || B > LNS_MAX_BATCH || n < 1) return op_refuse("letkf_combine", "B in 1..65535, n >= 1");
+    if (const char* why = letkf_grid_refusal(h, w)) return op_refuse("letkf_combine", why);
+    if (const char* why = letkf_radius_refusal(loc_radius)) return op_refuse("letkf_combine", why);
+    if (const char* why = letkf_bc_refusal(bc_y, bc_x)) return op_refuse("letkf_combine", why);
+    OPCHK(init_kernels());
+    const LetkfCombineArgs a = {part, S_local, g_local, S_glob, g_glob, stat, loc_radius, B, n, M, h, w, bc_y, bc_x};
+    OPCHK(launch_letkf_combine(a, static_cast<hipStream_t>(stream)));
+    return LNS_OK;
+}
+
+// letkf_update_kernel: z [B][M][c][h][w], X_local [B][h*w][M][M] -> out [B][M][c][h][w] (may be z); never synchronises
+int lns_op_ensemble_transform_local(const float* z, const double* X_local, int B, int M, int c, int h, int w, float* out, void* stream) {
+    if (!z || !X_local || !out) return op_refuse("ensemble_transform_local", "z, X_local or out is null");
+    if (const char* why = etkf_members_refusal(M)) return op_refuse("ensemble_transform_local", why);
+    if (B < 1 || B > LNS_MAX_BATCH || c < 1 || c > 65536) return op_refuse("ensemble_transform_local", "B in 1..65535, c in 1..65536");
+    if (const char* why = letkf_grid_refusal(h, w)) return op_refuse("ensemble_transform_local", why);
+    OPCHK(init_kernels());
+    const LetkfUpdateArgs a = {z, X_local, out, B, M, c, h * w};
+    OPCHK(launch_letkf_update(a, static_cast<hipStream_t>(stream)));
+    return LNS_OK;
+}
+
 int lns_spectrum_bins(int H, int W) {
     const int S = lns_spectrum::bins(H, W);
     return S < 0 ? LNS_EINVAL : S;

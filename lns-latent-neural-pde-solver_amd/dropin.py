@@ -497,7 +497,7 @@ class LatentDynamics(_Hosted):
 
     @torch.no_grad()
     def assimilate_ensemble(self, x0, y_obs, obs_steps, *rest, rinv, inflation=1.0, window=1, generator=None, param_spread=0.0,
-                            **norm):
+                            loc_radius=None, loc_boundary="auto", **norm):
         """assimilate_ensemble(x0, y_obs, obs_steps, members, noise_level, rinv=...) -- conditional:
         assimilate_ensemble(x0, y_obs, obs_steps, param, members, noise_level, rinv=...): an ensemble of forecasts from x0
         corrected by SPARSE observations of the decoded fields (a few sensors, one channel, a masked region) with an ensemble
@@ -508,6 +508,9 @@ class LatentDynamics(_Hosted):
         [C,Ly,Lx], [n_obs,C,Ly,Lx] or [B,n_obs,C,Ly,Lx], in the units `norm` gives (`validate`'s arguments; none:
         normalised units); inflation >= 1; window: observations taken in per analysis; param_spread > 0: param [B] becomes
         param + randn * param_spread per member and is estimated with the state (also with a conditional encoder).
+        loc_radius (None: the global filter): the Gaspari-Cohn half-width, in latent pixels, of the localised filter
+        (lns_amd.enkf.LocalEnsembleFilter: one transform per latent pixel; returns enkf.LocalEnKFResult), loc_boundary its
+        boundary rule ("auto": the model's padding per axis).
         Returns enkf.EnKFResult; `model._engine(z).rollout_latent_ensemble(result.z, steps, param=result.param)` forecasts
         from the analysis, which stands at the last observed step."""
         from . import enkf as _enkf
@@ -536,7 +539,9 @@ class LatentDynamics(_Hosted):
         if param is not None and float(param_spread) > 0.0:
             p = torch.as_tensor(param, device=z.device, dtype=torch.float32).reshape(-1, 1)
             param = p + torch.randn((p.shape[0], members), device=z.device, generator=generator) * float(param_spread)
-        return _enkf.EnsembleFilter(self, inflation).run(z.contiguous(), y_obs, rinv, obs_steps, window=window, param=param, **norm)
+        flt = _enkf.EnsembleFilter(self, inflation) if loc_radius is None else \
+            _enkf.LocalEnsembleFilter(self, loc_radius, inflation, loc_boundary)
+        return flt.run(z.contiguous(), y_obs, rinv, obs_steps, window=window, param=param, **norm)
 
     def lyapunov(self, x, steps, *rest, k=4, **kw):
         """lyapunov(x, steps, k=4, ...) -- conditional: lyapunov(x, steps, param, k=4, ...): the k leading finite-time

@@ -334,6 +334,13 @@ latents of the last step transformed by X), param [B, M] the transformed per-mem
 member), X [B, M, M], wbar [B, M], lam [B, M] (the eigenvalues of (M-1)/rho I + S, ascending) and stat [B, n_keep, 3] (the
 forecast mean's weighted misfit sum r d^2, sum r, the number of observed values) in float64, status [B] int32 (0 ok, 1 non-finite
 Gram, 2 not converged), and (return_mean / return_var / return_last) rollout_latent_ensemble's outputs."""
+LocalEnsembleAnalysis = collections.namedtuple(
+    "LocalEnsembleAnalysis", "z param X_local wbar_local lam_local status_local X wbar lam stat status mean var z_last")
+LocalEnsembleAnalysis.__doc__ = """Result of Engine.rollout_latent_ensemble_analysis_local: z [B, M, c, h, w] the analysis latents (latent
+pixel l of the forecast latents of the last step transformed by X_local[:, l]), X_local [B, h*w, M, M], wbar_local and lam_local
+[B, h*w, M] (float64), status_local [B, h*w] int32 per domain; param, X, wbar, lam, stat, status: the global transform from the same
+patch sums with weight 1 (param: the per-member param it updates, None unless given per member); mean, var, z_last as
+EnsembleAnalysis."""
 EnsembleExceedance = collections.namedtuple("EnsembleExceedance", "table mean var z_last")
 EnsembleExceedance.__doc__ = """Result of Engine.rollout_latent_ensemble_exceed: table [B, n_keep, n_thr, C, 2, M + 1] int32, the
 number of a plane's pixels with the truth above the threshold (index 1 of dim 4) or not (index 0) and n of the M members above
@@ -1187,6 +1194,136 @@ class Engine:
                 wbar.data_ptr(), lam.data_ptr(), stat.data_ptr(), status.data_ptr(), self._ptr(mean), self._ptr(var),
                 self._ptr(z_last), ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_analysis")
         return EnsembleAnalysis(za, pa, X, wbar, lam, stat, status, mean, var, z_last)
+
+    # -- localised ensemble transform Kalman filter (include/lns.h "localised ensemble transform Kalman filter") ------
+    def ensemble_patch_gram(self, frames, y_obs, rinv, grid, **norm):
+        """The patch Gram kernel of the localised filter on stored member fields (lns_op_ensemble_patch_gram): frames, y_obs, rinv
+        and `norm` as `ensemble_obs_gram`; grid = (h, w): the latent grid whose patches cut the frame.  Returns part
+        [B, n, h*w, M*M + M + 3] float64: per patch the Gram [M, M] (symmetric), g [M] and stat [3]."""
+        import torch
+        for t in (frames, y_obs):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+                raise LnsError("ensemble_patch_gram takes fp32 HIP tensors")
+        if frames.dim() != 6 or y_obs.dim() != 5 or y_obs.device != frames.device:
+            raise LnsError("ensemble_patch_gram takes frames [n, B, M, C, H, W] and y_obs [B, n, C, H, W] on one device")
+        n, B, M, C, H, W = (int(v) for v in frames.shape)
+        if tuple(y_obs.shape) != (B, n, C, H, W):
+            raise LnsError("y_obs must be %s for frames %s, got %s" % ((B, n, C, H, W), tuple(frames.shape), tuple(y_obs.shape)))
+        h, w = (int(v) for v in grid)
+        frames, y_obs = frames.contiguous(), y_obs.contiguous()
+        r, r_bs, r_ss = self._rinv(rinv, B, n, (C, H, W), frames.device)
+        spec = eval_spec(C, **norm) if norm else None
+        part = torch.empty((B, n, max(h * w, 0), M * M + M + 3), dtype=torch.float64, device=frames.device)
+        with torch.cuda.device(frames.device):
+            rc = self._L.lns_op_ensemble_patch_gram(frames.data_ptr(), y_obs.data_ptr(), r.data_ptr(), r_bs, r_ss, n, B, M, C, H, W, h, w,
+                                                    ctypes.byref(spec) if spec is not None else None, part.data_ptr(),
+                                                    self._stream(frames))
+        if rc != 0:
+            raise LnsError("lns_op_ensemble_patch_gram failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return part
+
+    def letkf_combine(self, part, grid, radius, boundary=("periodic", "periodic")):
+        """The combine kernel of the localised filter (lns_op_letkf_combine): part [B, n, h*w, M*M + M + 3] float64, grid = (h, w),
+        radius: the Gaspari-Cohn half-width in latent pixels, boundary: as metrics.flow_boundary (not "auto") -> (S_local
+        [B, h*w, M, M], g_local [B, h*w, M], S_glob [B, M, M], g_glob [B, M], stat [B, n, 3]) in float64."""
+        import torch
+        from . import metrics
+        h, w = (int(v) for v in grid)
+        if not isinstance(part, torch.Tensor) or not part.is_cuda or part.dtype != torch.float64 or part.dim() != 4 or part.shape[2] != h * w:
+            raise LnsError("letkf_combine takes a float64 HIP tensor [B, n, h*w, M*M + M + 3]")
+        B, n, hw, E = (int(v) for v in part.shape)
+        M = int(round((-1 + (1 + 4 * (E - 3)) ** 0.5) / 2))
+        if M * M + M + 3 != E:
+            raise LnsError("the last axis of part must be M*M + M + 3, got %d" % E)
+        bc_y, bc_x = metrics.flow_boundary(boundary)
+        part = part.contiguous()
+        f64 = dict(dtype=torch.float64, device=part.device)
+        S_l, g_l = torch.empty((B, hw, M, M), **f64), torch.empty((B, hw, M), **f64)
+        S_g, g_g, stat = torch.empty((B, M, M), **f64), torch.empty((B, M), **f64), torch.empty((B, n, 3), **f64)
+        with torch.cuda.device(part.device):
+            rc = self._L.lns_op_letkf_combine(part.data_ptr(), B, n, M, h, w, float(radius), bc_y, bc_x, S_l.data_ptr(), g_l.data_ptr(),
+                                              S_g.data_ptr(), g_g.data_ptr(), stat.data_ptr(), self._stream(part))
+        if rc != 0:
+            raise LnsError("lns_op_letkf_combine failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return S_l, g_l, S_g, g_g, stat
+
+    def ensemble_transform_local(self, z, X_local, out=None):
+        """The update kernel of the localised filter (lns_op_ensemble_transform_local): z [B, M, c, h, w] fp32, X_local
+        [B, h*w, M, M] float64 -> latent pixel l of every channel transformed by X_local[:, l]; out may be z itself."""
+        import torch
+        if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.float32 or z.dim() != 5 or not z.is_contiguous():
+            raise LnsError("ensemble_transform_local takes a contiguous fp32 HIP tensor [B, M, c, h, w]")
+        B, M, c, h, w = (int(v) for v in z.shape)
+        if not isinstance(X_local, torch.Tensor) or X_local.dtype != torch.float64 or X_local.device != z.device or \
+                tuple(X_local.shape) != (B, h * w, M, M):
+            raise LnsError("X_local must be float64 %s on the device of z, got %s" % ((B, h * w, M, M), tuple(getattr(X_local, "shape", ()))))
+        if out is None:
+            out = torch.empty_like(z)
+        elif out.shape != z.shape or out.dtype != z.dtype or out.device != z.device or not out.is_contiguous():
+            raise LnsError("out must be a contiguous tensor of z's shape, dtype and device")
+        with torch.cuda.device(z.device):
+            rc = self._L.lns_op_ensemble_transform_local(z.data_ptr(), X_local.contiguous().data_ptr(), B, M, c, h, w, out.data_ptr(),
+                                                         self._stream(z))
+        if rc != 0:
+            raise LnsError("lns_op_ensemble_transform_local failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        return out
+
+    def rollout_latent_ensemble_analysis_local(self, z, y_obs, rinv, steps, loc_radius, boundary="auto", param=None, keep_steps=None,
+                                               rho=1.0, return_mean=False, return_var=False, return_last=False, return_X=True, **norm):
+        """One window of the localised filter: rollout_latent_ensemble_analysis with one transform per latent pixel.  loc_radius:
+        the Gaspari-Cohn half-width in latent pixels (the weights vanish at 2 loc_radius); boundary: "auto" (the model's padding
+        per axis), "periodic", "wall" or a pair (y, x), as metrics.flow_boundary; return_X = False leaves X_local, wbar_local in
+        the workspace.  Everything else as rollout_latent_ensemble_analysis.  Returns LocalEnsembleAnalysis."""
+        import torch
+        from . import metrics
+        z = self._dev(z)
+        y_obs = self._dev(y_obs)
+        C, H, W = self.latent_shape()
+        c = self.cfg
+        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
+            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
+        B, M = int(z.shape[0]), int(z.shape[1])
+        steps = int(steps)
+        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
+        nk = len(keep)
+        tail = (c.in_channels, c.Ly, c.Lx)
+        if tuple(y_obs.shape) != (B, nk) + tail or y_obs.device != z.device:
+            raise LnsError("y_obs must be %s on the latents' device, got %s" % ((B, nk) + tail, tuple(y_obs.shape)))
+        if return_var and not return_mean:
+            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
+        bc_y, bc_x = metrics.flow_boundary(boundary, c)
+        arr = (ctypes.c_int * nk)(*keep)
+        y_obs = y_obs.contiguous()
+        r, r_bs, r_ss = self._rinv(rinv, B, nk, tail, z.device)
+        spec = eval_spec(c.in_channels, **norm) if norm else None
+        f64 = dict(dtype=torch.float64, device=z.device)
+        za = torch.empty_like(z)
+        p = self._member_param(param, z, B, M)
+        per_member = p is not None and torch.as_tensor(param).numel() == B * M and M > 1
+        pa = torch.empty_like(p) if per_member else None
+        hw = H * W
+        Xl = torch.empty((B, hw, M, M), **f64) if return_X else None
+        wl = torch.empty((B, hw, M), **f64) if return_X else None
+        ll = torch.empty((B, hw, M), **f64)
+        sl = torch.empty((B, hw), dtype=torch.int32, device=z.device)
+        X, wbar, lam = torch.empty((B, M, M), **f64), torch.empty((B, M), **f64), torch.empty((B, M), **f64)
+        stat = torch.empty((B, nk, 3), **f64)
+        status = torch.empty((B,), dtype=torch.int32, device=z.device)
+        mean = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_mean else None
+        var = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_var else None
+        z_last = torch.empty_like(z) if return_last else None
+        with torch.cuda.device(z.device):
+            n = ctypes.c_size_t(0)
+            self._check(self._L.lns_rollout_ensemble_analysis_local_workspace_bytes(self._h, B, M, nk, ctypes.byref(n)),
+                        "lns_rollout_ensemble_analysis_local_workspace_bytes")
+            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+            self._check(self._L.lns_rollout_latent_ensemble_analysis_local(
+                self._h, z.data_ptr(), self._ptr(p), y_obs.data_ptr(), r.data_ptr(), r_bs, r_ss, B, M, steps, arr, nk,
+                ctypes.byref(spec) if spec is not None else None, float(rho), float(loc_radius), bc_y, bc_x, za.data_ptr(),
+                self._ptr(Xl), self._ptr(wl), ll.data_ptr(), sl.data_ptr(), self._ptr(pa), X.data_ptr(), wbar.data_ptr(),
+                lam.data_ptr(), stat.data_ptr(), status.data_ptr(), self._ptr(mean), self._ptr(var), self._ptr(z_last),
+                ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_analysis_local")
+        return LocalEnsembleAnalysis(za, pa, Xl, wl, ll, sl, X, wbar, lam, stat, status, mean, var, z_last)
 
     # -- streaming validation rollout (include/lns.h "streaming validation rollout") --------------------------------
     def _eval_common(self, first, y, steps, t0, keep_steps, norm):
