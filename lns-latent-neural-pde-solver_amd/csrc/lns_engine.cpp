@@ -1661,12 +1661,15 @@ struct Runner {
 //                 of the steps keep[0 .. n_keep) are copied to frames_out
 //   SINK_ENSEMBLE the chain runs at batch N = B * M (launch sample b * M + m is member m of trajectory b); the steps
 //                 keep[0 .. n_keep) are decoded into a frame buffer of the workspace and reduced over the members right there
-//                 into `out` (mean) and `var_out` [B][n_keep][xper]; with `scores_out` (lns_rollout_latent_ensemble_eval) also
-//                 scored there against y_true, and `out` may be null; with `qspec` (lns_rollout_latent_ensemble_quantiles) the
-//                 members' quantiles and exceedance probabilities are taken there too, and `out` may be null; with `xspec`
-//                 (lns_rollout_latent_ensemble_exceed) the exceedance contingency tables against y_true are counted there, and
-//                 `out` may be null
+//                 into `out` (mean) and `var_out` [B][n_keep][xper]; what else is taken from the frames there: EnsForm
 enum SinkKind { SINK_LATENTS, SINK_STEPS, SINK_KEPT, SINK_SCORED, SINK_ENSEMBLE };
+
+// What a SINK_ENSEMBLE call takes from a decoded group beside the mean / variance (lns_rollout_latent_ensemble and its five
+// forms): nothing, for which alone `out` is mandatory; the scores against y_true (_eval); the members' quantiles and exceedance
+// probabilities (_quantiles); the exceedance tables against y_true (_exceed); the Gram against the observations, then the filter
+// (_analysis); the patch Gram, then one transform per latent pixel (_analysis_local).  Under any other sink it means nothing.
+enum EnsForm { ENS_STATS, ENS_SCORED, ENS_QUANT, ENS_EXCEED, ENS_ANALYSIS, ENS_ANALYSIS_LOCAL };
+static bool ens_analysis(EnsForm f) { return f == ENS_ANALYSIS || f == ENS_ANALYSIS_LOCAL; }
 
 // workspace layout: [ z0 | latent ring: NGROUP groups x kdec steps x [B][zper] | NDEC decode arenas | propagator arena ]
 // The propagator gets its own arena because it runs on a second stream, concurrently with decode.
@@ -1686,7 +1689,7 @@ struct WsLayout {
     size_t fbuf_off, fbuf_stride, part_off;   // SINK_SCORED; SINK_ENSEMBLE (no part)
     size_t pp_off[2];                         // SINK_KEPT, SINK_ENSEMBLE
     size_t maps_off = 0, maps_bytes = 0;      // SINK_SCORED with time maps (add_maps_region)
-    size_t etkf_off = 0;                      // SINK_ENSEMBLE with ens_obs (etkf_region)
+    size_t etkf_off = 0;                      // SINK_ENSEMBLE, the analysis forms (add_analysis_region)
     // SINK_SCORED with attribution (add_attrib_region): second frame buffers, true-latent staging, three partial-sum arrays
     size_t fbuf2_off = 0, ztrue_off = 0, ztrue_stride = 0, part2_off = 0, ppart_off = 0, lpart_off = 0; long zstride = 0;
 };
@@ -1758,6 +1761,43 @@ static void add_maps_region(const lns_engine* e, int B, WsLayout* L) {
     L->total = L->maps_off + L->maps_bytes;
 }
 
+// The region of the two analysis forms behind the SINK_ENSEMBLE layout, which it leaves byte for byte as it is; offsets from the
+// region's start, the *_loc ones for ENS_ANALYSIS_LOCAL only.
+struct AnalysisRegion {
+    size_t part, S, g, stat, X, wbar, lam, status, S_loc = 0, g_loc = 0, X_loc = 0, wbar_loc = 0, lam_loc = 0, status_loc = 0, bytes = 0;
+    size_t take(size_t n) { const size_t at = bytes; bytes = round_up_sz(bytes + n, 256); return at; }   // the next buffer, 256-byte aligned
+};
+// lns_rollout_latent_ensemble_analysis: the slice partials [B][n_keep][slices][M*M + M + 3], then S [B][n_keep][M][M],
+// g [B][n_keep][M], stat [B][n_keep][3], X [B][M][M], wbar [B][M], lam [B][M] (all double) and status [B] (int32)
+static AnalysisRegion etkf_region(const lns_engine* e, size_t B, size_t M, size_t n_keep) {
+    const size_t nsl = (size_t)etkf_slices((long)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx), bn = B * n_keep;
+    AnalysisRegion r;
+    r.part = r.take(bn * nsl * etkf_part_doubles((int)M) * 8);
+    r.S = r.take(bn * M * M * 8); r.g = r.take(bn * M * 8); r.stat = r.take(bn * 3 * 8);
+    r.X = r.take(B * M * M * 8); r.wbar = r.take(B * M * 8); r.lam = r.take(B * M * 8); r.status = r.take(B * 4);
+    return r;
+}
+// lns_rollout_latent_ensemble_analysis_local: the patch sums [B][n_keep][h*w][M*M + M + 3], then per domain S [B][h*w][M][M],
+// g [B][h*w][M], X [B][h*w][M][M], wbar, lam [B][h*w][M], status [B][h*w], then the global S [B][M][M], g [B][M],
+// stat [B][n_keep][3], X [B][M][M], wbar [B][M], lam [B][M], status [B]
+static AnalysisRegion letkf_region(const lns_engine* e, size_t B, size_t M, size_t n_keep) {
+    const size_t hw = (size_t)e->lat_H * e->lat_W, bd = B * hw;
+    AnalysisRegion r;
+    r.part = r.take(B * n_keep * hw * etkf_part_doubles((int)M) * 8);
+    r.S_loc = r.take(bd * M * M * 8); r.g_loc = r.take(bd * M * 8);
+    r.X_loc = r.take(bd * M * M * 8); r.wbar_loc = r.take(bd * M * 8); r.lam_loc = r.take(bd * M * 8); r.status_loc = r.take(bd * 4);
+    r.S = r.take(B * M * M * 8); r.g = r.take(B * M * 8); r.stat = r.take(B * n_keep * 3 * 8);
+    r.X = r.take(B * M * M * 8); r.wbar = r.take(B * M * 8); r.lam = r.take(B * M * 8); r.status = r.take(B * 4);
+    return r;
+}
+static AnalysisRegion analysis_region(const lns_engine* e, EnsForm form, size_t B, size_t M, size_t n_keep) {
+    return form == ENS_ANALYSIS_LOCAL ? letkf_region(e, B, M, n_keep) : etkf_region(e, B, M, n_keep);
+}
+static void add_analysis_region(const lns_engine* e, EnsForm form, int B, int M, int n_keep, WsLayout* L) {
+    L->etkf_off = round_up_sz(L->total, 256);
+    L->total = L->etkf_off + analysis_region(e, form, B, M, n_keep).bytes;
+}
+
 // The region of the error attribution (lns_rollout_eval_attrib), behind the SINK_SCORED layout, which it leaves byte for byte
 // as it is: per decode stream a second frame buffer (the reconstruction of the group's truth frames) and a staging buffer
 // [kdec][B][zstride] of their latents (zstride: zper rounded up to four floats, so that every slot is 16-byte aligned), then
@@ -1810,23 +1850,21 @@ struct RolloutCall {
     const int* keep = nullptr; int n_keep = 0;           // SINK_KEPT, SINK_ENSEMBLE (n_keep >= 1), SINK_SCORED (n_keep >= 0); host, ascending
     // SINK_ENSEMBLE: B above is the chain's batch N = traj * M (clipped to int; 0 when either factor is not positive)
     int traj = 0, M = 0; float* var_out = nullptr;
-    // SINK_ENSEMBLE with ens_scored: y_true [traj][n_keep], spec and seq_out below; the plane sums go straight into scores_out
-    bool ens_scored = false; float* scores_out = nullptr; int32_t* rank_out = nullptr;
-    // SINK_ENSEMBLE with ens_quant (lns_rollout_latent_ensemble_quantiles): qspec, the outputs it asks for, and `spec` below as the
-    // nullable denormalisation; `out` (the mean) is optional
-    bool ens_quant = false; const lns_ensemble_quantile_spec* qspec = nullptr; float *quant_out = nullptr, *prob_out = nullptr;
-    // SINK_ENSEMBLE with ens_exceed (lns_rollout_latent_ensemble_exceed): xspec, y_true [traj][n_keep], the table, and `spec` below
-    // as the nullable denormalisation; `out` (the mean) is optional
-    bool ens_exceed = false; const lns_ensemble_exceed_spec* xspec = nullptr; int32_t* table_out = nullptr;
-    // SINK_ENSEMBLE with ens_obs (lns_rollout_latent_ensemble_analysis): y_true [traj][n_keep] holds the observations, rinv their
-    // weights with its two strides, `spec` below the nullable denormalisation, rho the inflation; z_analysis and the nullable
-    // outputs of the filter; `out` (the mean) is optional
-    bool ens_obs = false; const float* rinv = nullptr; int64_t rinv_bs = 0, rinv_ss = 0; double rho = 1.0;
+    EnsForm ens_form = ENS_STATS;                        // SINK_ENSEMBLE: which of the fields below the call reads
+    // ENS_SCORED: y_true [traj][n_keep], spec and seq_out below; the plane sums go straight into scores_out
+    float* scores_out = nullptr; int32_t* rank_out = nullptr;
+    // ENS_QUANT: qspec, the outputs it asks for, and `spec` below as the nullable denormalisation
+    const lns_ensemble_quantile_spec* qspec = nullptr; float *quant_out = nullptr, *prob_out = nullptr;
+    // ENS_EXCEED: xspec, y_true [traj][n_keep], the table, and `spec` below as the nullable denormalisation
+    const lns_ensemble_exceed_spec* xspec = nullptr; int32_t* table_out = nullptr;
+    // ENS_ANALYSIS, ENS_ANALYSIS_LOCAL: y_true [traj][n_keep] holds the observations, rinv their weights with its two strides,
+    // `spec` below the nullable denormalisation, rho the inflation; z_analysis and the nullable outputs of the filter
+    const float* rinv = nullptr; int64_t rinv_bs = 0, rinv_ss = 0; double rho = 1.0;
     float *z_analysis = nullptr, *param_analysis = nullptr;
     double *X_out = nullptr, *wbar_out = nullptr, *lam_out = nullptr, *stat_out = nullptr; int32_t* status_out = nullptr;
-    // ens_obs with ens_local (lns_rollout_latent_ensemble_analysis_local): the patch Gram takes the Gram's place; the taper's
-    // half-width and boundary codes, and the nullable per-domain outputs
-    bool ens_local = false; double loc_radius = 0.0; int bc_y = 0, bc_x = 0;
+    // ENS_ANALYSIS_LOCAL: the patch Gram takes the Gram's place; the taper's half-width and boundary codes, and the nullable
+    // per-domain outputs
+    double loc_radius = 0.0; int bc_y = 0, bc_x = 0;
     double *X_loc_out = nullptr, *wbar_loc_out = nullptr, *lam_loc_out = nullptr; int32_t* status_loc_out = nullptr;
     // SINK_SCORED: y_true and the per-plane sums hold T_total steps, of which the call's step 0 is step t0
     const float* y_true = nullptr; int t0 = 0, T_total = 0; const lns_eval_spec* spec = nullptr;
@@ -2297,14 +2335,6 @@ static void time_maps_args(const lns_engine* e, const RolloutCall& c, const WsLa
     score_norm(c.spec, t.C, &t.norm);
 }
 
-// the same for the scoring kernel of a scored SINK_ENSEMBLE call; frames / kk / y_t are set per decoded group
-static void score_args(const lns_engine* e, const RolloutCall& c, EnsembleScoreArgs* sp) {
-    EnsembleScoreArgs& s = *sp;
-    s.frames = nullptr; s.y = c.y_true; s.scores = c.scores_out; s.rank = c.rank_out; s.pixel = nullptr;
-    s.B = c.traj; s.M = c.M; s.C = e->cfg.in_channels; s.H = e->cfg.Ly; s.W = e->cfg.Lx; s.kk = 0; s.y_T = c.n_keep; s.y_t = 0;
-    score_norm(c.spec, s.C, &s.norm);
-}
-
 // The position of probability p among M sorted members (include/lns.h): h = p (M - 1) in double, lo = floor(h), frac = (float)(h - lo)
 static void quantile_position(double p, int M, int* lo, float* frac) {
     const double h = p * (double)(M - 1);
@@ -2386,22 +2416,6 @@ static void obs_gram_args(const lns_eval_spec* norm, const float* y, const float
     if (norm) score_norm(norm, C, &g.norm);
 }
 
-// The region of lns_rollout_latent_ensemble_analysis behind the SINK_ENSEMBLE layout, which it leaves byte for byte as it is:
-// the slice partials [B][n_keep][slices][M*M + M + 3], then S [B][n_keep][M][M], g [B][n_keep][M], stat [B][n_keep][3], X [B][M][M],
-// wbar [B][M], lam [B][M] (all double) and status [B] (int32); offsets from the region's start
-struct EtkfRegion { size_t part, S, g, stat, X, wbar, lam, status, bytes; };
-static EtkfRegion etkf_region(const lns_engine* e, size_t B, size_t M, size_t n_keep) {
-    const size_t nsl = (size_t)etkf_slices((long)e->cfg.in_channels * e->cfg.Ly * e->cfg.Lx), bn = B * n_keep;
-    EtkfRegion r;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off = round_up_sz(off + bytes, 256); return at; };
-    r.part = take(bn * nsl * etkf_part_doubles((int)M) * 8);
-    r.S = take(bn * M * M * 8); r.g = take(bn * M * 8); r.stat = take(bn * 3 * 8);
-    r.X = take(B * M * M * 8); r.wbar = take(B * M * 8); r.lam = take(B * M * 8); r.status = take(B * 4);
-    r.bytes = off;
-    return r;
-}
-
 // the refusals of the localised filter's taper (include/lns.h); nullptr: accepted
 static const char* letkf_radius_refusal(double radius) {
     return !(radius > 0.0) || std::isinf(radius) ? "loc_radius must be finite and > 0" : nullptr;
@@ -2422,23 +2436,46 @@ static void patch_gram_args(const lns_eval_spec* norm, const float* y, const flo
     if (norm) score_norm(norm, C, &g.norm);
 }
 
-// The region of lns_rollout_latent_ensemble_analysis_local behind the SINK_ENSEMBLE layout: the patch sums
-// [B][n_keep][h*w][M*M + M + 3], then per domain S [B][h*w][M][M], g [B][h*w][M], X [B][h*w][M][M], wbar, lam [B][h*w][M], status
-// [B][h*w], then the global S [B][M][M], g [B][M], stat [B][n_keep][3], X [B][M][M], wbar [B][M], lam [B][M], status [B]
-struct LetkfRegion { size_t part, S_loc, g_loc, X_loc, wbar_loc, lam_loc, status_loc, S, g, stat, X, wbar, lam, status, bytes; };
-static LetkfRegion letkf_region(const lns_engine* e, size_t B, size_t M, size_t n_keep) {
-    const size_t hw = (size_t)e->lat_H * e->lat_W, bd = B * hw;
-    LetkfRegion r;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off = round_up_sz(off + bytes, 256); return at; };
-    r.part = take(B * n_keep * hw * etkf_part_doubles((int)M) * 8);
-    r.S_loc = take(bd * M * M * 8); r.g_loc = take(bd * M * 8);
-    r.X_loc = take(bd * M * M * 8); r.wbar_loc = take(bd * M * 8); r.lam_loc = take(bd * M * 8); r.status_loc = take(bd * 4);
-    r.S = take(B * M * M * 8); r.g = take(B * M * 8); r.stat = take(B * n_keep * 3 * 8);
-    r.X = take(B * M * M * 8); r.wbar = take(B * M * 8); r.lam = take(B * M * 8); r.status = take(B * 4);
-    r.bytes = off;
-    return r;
-}
+// What a SINK_ENSEMBLE call launches on a decoded group ahead of the mean / variance: the one kernel of the call's form and
+// its arguments.  prepare fills them once per call; launch takes the group -- fb [kk][traj][M][xper], the kept steps
+// i0 .. i0 + kk - 1 of y_true / y_obs and of the outputs [traj][n_keep] -- and enqueues the kernel.
+struct EnsGroup {
+    EnsForm form = ENS_STATS;
+    union { EnsembleScoreArgs sc; EnsembleQuantileArgs qa; EnsembleExceedArgs xa; EnsembleObsGramArgs oa; LetkfPatchGramArgs pga; };
+    void prepare(const lns_engine* e, const RolloutCall& c, const WsLayout& L) {
+        const int C = e->cfg.in_channels, H = e->cfg.Ly, W = e->cfg.Lx;
+        form = c.ens_form;
+        // the analysis forms: the sums of kept step i land in the region's part[b][i]
+        double* part = ens_analysis(form) ? reinterpret_cast<double*>(static_cast<char*>(c.ws) + L.etkf_off +
+                                                                      analysis_region(e, form, c.traj, c.M, c.n_keep).part) : nullptr;
+        switch (form) {
+        case ENS_STATS: break;
+        case ENS_SCORED:
+            sc.frames = nullptr; sc.y = c.y_true; sc.scores = c.scores_out; sc.rank = c.rank_out; sc.pixel = nullptr;
+            sc.B = c.traj; sc.M = c.M; sc.C = C; sc.H = H; sc.W = W; sc.kk = 0; sc.y_T = c.n_keep; sc.y_t = 0;
+            score_norm(c.spec, C, &sc.norm); break;
+        case ENS_QUANT: quantile_args(c.qspec, c.spec, c.traj, c.M, C, H, W, c.quant_out, c.prob_out, &qa); qa.o_T = c.n_keep; break;
+        case ENS_EXCEED: exceed_args(c.xspec, c.spec, c.y_true, c.traj, c.M, C, H, W, c.table_out, &xa); xa.y_T = xa.o_T = c.n_keep; break;
+        case ENS_ANALYSIS:
+            obs_gram_args(c.spec, c.y_true, c.rinv, c.rinv_bs, c.rinv_ss, c.traj, c.M, C, H, W, &oa);
+            oa.part = part; oa.y_T = oa.o_T = c.n_keep; break;
+        case ENS_ANALYSIS_LOCAL:
+            patch_gram_args(c.spec, c.y_true, c.rinv, c.rinv_bs, c.rinv_ss, c.traj, c.M, C, H, W, e->lat_H, e->lat_W, &pga);
+            pga.part = part; pga.y_T = pga.o_T = c.n_keep; break;
+        }
+    }
+    hipError_t launch(const float* fb, int kk, int i0, hipStream_t s) {
+        switch (form) {
+        case ENS_STATS: break;
+        case ENS_SCORED: sc.frames = fb; sc.kk = kk; sc.y_t = i0; return launch_ensemble_score(sc, s);
+        case ENS_QUANT: qa.frames = fb; qa.kk = kk; qa.o_t = i0; return launch_ensemble_quantile(qa, s);
+        case ENS_EXCEED: xa.frames = fb; xa.kk = kk; xa.y_t = xa.o_t = i0; return launch_ensemble_exceed(xa, s);   // counts added into table_out
+        case ENS_ANALYSIS: oa.frames = fb; oa.kk = kk; oa.y_t = oa.o_t = i0; return launch_ensemble_obs_gram(oa, s);
+        case ENS_ANALYSIS_LOCAL: pga.frames = fb; pga.kk = kk; pga.y_t = pga.o_t = i0; return launch_letkf_patch_gram(pga, s);
+        }
+        return hipSuccess;
+    }
+};
 
 // the autoregressive loop of every rollout call: zcur -> T x (propagate ; what the sink does)   (train_stage2_ns2d.py:147-156)
 // The latent chain z_t -> z_{t+1} is strictly sequential, but decode(z_t) depends on z_t only: the chain runs ahead
@@ -2498,30 +2535,8 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     std::vector<char> used(ngroup, 0);
     MetricGroupArgs m;
     if (scored) metric_args(e, c, L, &m);
-    EnsembleScoreArgs sc;
-    if (ens && c.ens_scored) score_args(e, c, &sc);
-    EnsembleQuantileArgs qa;
-    if (ens && c.ens_quant) {
-        quantile_args(c.qspec, c.spec, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, c.quant_out, c.prob_out, &qa);
-        qa.o_T = c.n_keep;
-    }
-    EnsembleExceedArgs xa;
-    if (ens && c.ens_exceed) {
-        exceed_args(c.xspec, c.spec, c.y_true, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, c.table_out, &xa);
-        xa.y_T = xa.o_T = c.n_keep;
-    }
-    EnsembleObsGramArgs oa;
-    LetkfPatchGramArgs pga;
-    if (ens && c.ens_obs && c.ens_local) {           // the patch sums of kept step i land in the region's part[b][i]
-        patch_gram_args(c.spec, c.y_true, c.rinv, c.rinv_bs, c.rinv_ss, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, e->lat_H,
-                        e->lat_W, &pga);
-        pga.part = reinterpret_cast<double*>(base + L.etkf_off + letkf_region(e, c.traj, c.M, c.n_keep).part);
-        pga.y_T = pga.o_T = c.n_keep;
-    } else if (ens && c.ens_obs) {                   // the slice partials of kept step i land in the region's part[b][i]
-        obs_gram_args(c.spec, c.y_true, c.rinv, c.rinv_bs, c.rinv_ss, c.traj, c.M, e->cfg.in_channels, e->cfg.Ly, e->cfg.Lx, &oa);
-        oa.part = reinterpret_cast<double*>(base + L.etkf_off + etkf_region(e, c.traj, c.M, c.n_keep).part);
-        oa.y_T = oa.o_T = c.n_keep;
-    }
+    EnsGroup eg;
+    if (ens) eg.prepare(e, c, L);
     SpectrumArgs sx;
     if (scored && c.spectra) spectrum_args(e, c, &sx);
     FieldStatsArgs fs;
@@ -2690,26 +2705,8 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
                                                    hipMemcpyDeviceToDevice, dstream[d]));
             }
         }
-        if (ens && c.ens_scored) {                   // fb is [kk][traj][M][xper] against y_true[b][i0 .. i0 + kk)
-            sc.frames = fb; sc.kk = kk; sc.y_t = i0;
-            HIPCHK(e, launch_ensemble_score(sc, dstream[d]));
-        }
-        if (ens && c.ens_quant) {                    // fb is [kk][traj][M][xper] -> quantiles / probabilities of kept steps i0 .. i0 + kk - 1
-            qa.frames = fb; qa.kk = kk; qa.o_t = i0;
-            HIPCHK(e, launch_ensemble_quantile(qa, dstream[d]));
-        }
-        if (ens && c.ens_exceed) {                   // fb is [kk][traj][M][xper] against y_true[b][i0 .. i0 + kk) -> counts added into table_out
-            xa.frames = fb; xa.kk = kk; xa.y_t = xa.o_t = i0;
-            HIPCHK(e, launch_ensemble_exceed(xa, dstream[d]));
-        }
-        if (ens && c.ens_obs && c.ens_local) {       // fb is [kk][traj][M][xper] against y_obs[b][i0 .. i0 + kk) -> the patch sums of those steps
-            pga.frames = fb; pga.kk = kk; pga.y_t = pga.o_t = i0;
-            HIPCHK(e, launch_letkf_patch_gram(pga, dstream[d]));
-        } else if (ens && c.ens_obs) {               // fb is [kk][traj][M][xper] against y_obs[b][i0 .. i0 + kk) -> the slice partials of those steps
-            oa.frames = fb; oa.kk = kk; oa.y_t = oa.o_t = i0;
-            HIPCHK(e, launch_ensemble_obs_gram(oa, dstream[d]));
-        }
-        if (ens && c.out) {                          // fb is [kk][traj][M][xper] -> mean / var of out[b][i0 .. i0 + kk)
+        if (ens) HIPCHK(e, eg.launch(fb, kk, i0, dstream[d]));   // the form's kernel first, then the mean / variance
+        if (ens && c.out) {                       // fb is [kk][traj][M][xper] -> mean / var of out[b][i0 .. i0 + kk)
             EnsembleStatsArgs es;
             es.frames = fb; es.mean = c.out + (long)i0 * xper; es.var = c.var_out ? c.var_out + (long)i0 * xper : nullptr;
             es.per = xper; es.out_bs = (long)n_dec * xper; es.B = c.traj; es.M = c.M; es.kk = kk;
@@ -2736,62 +2733,69 @@ static int rollout_loop(lns_engine* e, Runner& r, ExtT zcur, const RolloutCall& 
     return LNS_OK;
 }
 
-// every refusal of a rollout call that needs no plan: nothing here touches the device.  The order is part of the
-// interface (which of two failing checks answers): arguments, batch, eval_max_steps, the model, param.
-static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
-    const bool scored = c.sink == SINK_SCORED, ens = c.sink == SINK_ENSEMBLE, kept = c.sink == SINK_KEPT || ens;
-    const bool ens_scored = ens && c.ens_scored;     // lns_rollout_latent_ensemble_eval: every output but scores_out is optional
-    const bool ens_quant = ens && c.ens_quant;       // lns_rollout_latent_ensemble_quantiles: the mean is optional
-    const bool ens_exceed = ens && c.ens_exceed;     // lns_rollout_latent_ensemble_exceed: likewise
-    const bool ens_obs = ens && c.ens_obs;           // lns_rollout_latent_ensemble_analysis: likewise
-    if (!c.start) return einval(e, c.encode ? "x is null" : "z_in is null");
-    if (ens_obs) {
+// The refusals of a SINK_ENSEMBLE call in two parts, because B / M / T are checked between them (rollout_refusal).  Each check
+// stands once, under the forms that have it; the order within a form is part of the interface.  The forms are not uniform: the
+// scored form's `spec` is mandatory and refused later under its own text; the exceedance form has no per-channel norm check --
+// with more than 8 channels it answers for the thresholds whatever the norm says.
+static int analysis_members_refusal(lns_engine* e, int M) {
+    const char* why = etkf_members_refusal(M);
+    if (why) e->err = std::string("ensemble analysis needs ") + why;
+    return why ? LNS_EINVAL : LNS_OK;
+}
+// part one: the pointers and descriptors of the form
+static int ensemble_args_refusal(lns_engine* e, const RolloutCall& c) {
+    const EnsForm f = c.ens_form;
+    const char* why = nullptr;
+    if (ens_analysis(f)) {
         if (!c.y_true) return einval(e, "y_obs is null");
         if (!c.rinv) return einval(e, "rinv is null");
         if (!c.z_analysis) return einval(e, "z_analysis is null");
         if (c.rinv_bs < 0 || c.rinv_ss < 0) return einval(e, "the strides of rinv must be >= 0 (0: shared)");
-        if (const char* why = etkf_rho_refusal(c.rho)) return einval(e, why);
-        if (c.ens_local) {
-            if (const char* why = letkf_radius_refusal(c.loc_radius)) return einval(e, why);
-            if (const char* why = letkf_bc_refusal(c.bc_y, c.bc_x)) return einval(e, why);
-        }
+        if ((why = etkf_rho_refusal(c.rho))) return einval(e, why);
+        if (f == ENS_ANALYSIS_LOCAL && (why = letkf_radius_refusal(c.loc_radius))) return einval(e, why);
+        if (f == ENS_ANALYSIS_LOCAL && (why = letkf_bc_refusal(c.bc_y, c.bc_x))) return einval(e, why);
     }
-    if ((scored || ens_scored || ens_exceed) && !c.y_true) return einval(e, "y_true is null");
-    if (ens_scored && !c.scores_out) return einval(e, "scores_out is null");
-    if (ens_quant)
-        if (const char* why = quantile_spec_refusal(c.qspec, c.quant_out, c.prob_out)) return einval(e, why);
-    if (ens_exceed)
-        if (const char* why = exceed_spec_refusal(c.xspec, c.table_out)) return einval(e, why);
-    if (!scored && !ens_scored && !ens_quant && !ens_exceed && !ens_obs && !c.out) return einval(e, ens ? "mean_out is null" : "out is null");
+    if ((f == ENS_SCORED || f == ENS_EXCEED) && !c.y_true) return einval(e, "y_true is null");
+    if (f == ENS_SCORED && !c.scores_out) return einval(e, "scores_out is null");
+    if (f == ENS_QUANT && (why = quantile_spec_refusal(c.qspec, c.quant_out, c.prob_out))) return einval(e, why);
+    if (f == ENS_EXCEED && (why = exceed_spec_refusal(c.xspec, c.table_out))) return einval(e, why);
+    if (f == ENS_STATS && !c.out) return einval(e, "mean_out is null");
+    return LNS_OK;
+}
+// part two, behind B / M / T: the member count, then what the form asks of var_out, param and the nullable norm (`spec`)
+static int ensemble_members_refusal(lns_engine* e, const RolloutCall& c) {
+    const EnsForm f = c.ens_form;
+    const bool wide = e->cfg.in_channels > LNS_METRIC_MAX_CH;
+    if (c.var_out && c.M < 2) return einval(e, "var_out needs M >= 2");
+    if (f == ENS_SCORED && (c.M < 2 || c.M > LNS_SCORE_MAX_MEMBERS)) return einval(e, "ensemble scoring needs M in 2 .. 128");
+    if (f == ENS_QUANT && c.M > LNS_SCORE_MAX_MEMBERS) return einval(e, "ensemble quantiles need M in 1 .. 128");
+    if (f == ENS_EXCEED && c.M > LNS_SCORE_MAX_MEMBERS) return einval(e, "ensemble exceedance needs M in 1 .. 128");
+    if (ens_analysis(f))
+        if (int mrc = analysis_members_refusal(e, c.M)) return mrc;
+    if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");         // (ENS_STATS: `out` is not null here)
+    if (ens_analysis(f) && c.param_analysis && !c.param) return einval(e, "param_analysis needs param");
+    if (f == ENS_STATS || f == ENS_SCORED) return LNS_OK;                         // no nullable norm
+    if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
+    if (f != ENS_EXCEED && c.spec && c.spec->per_channel && wide) return einval(e, "norm: the per-channel form needs in_channels <= 8");
+    if ((f == ENS_EXCEED || (f == ENS_QUANT && c.qspec->n_thr > 0)) && wide) return einval(e, "thresholds need in_channels <= 8");
+    if (f == ENS_ANALYSIS_LOCAL && (long)e->lat_H * e->lat_W > LNS_LETKF_MAX_DOMAINS)
+        return einval(e, "local ensemble analysis needs a latent grid of at most 4096 pixels");
+    return LNS_OK;
+}
+
+// every refusal of a rollout call that needs no plan: nothing here touches the device.  The order is part of the
+// interface (which of two failing checks answers): arguments, batch, eval_max_steps, the model, param.
+static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
+    const bool scored = c.sink == SINK_SCORED, ens = c.sink == SINK_ENSEMBLE, kept = c.sink == SINK_KEPT || ens;
+    const bool spec_scored = scored || (ens && c.ens_form == ENS_SCORED);   // `spec` is the mandatory one of the scored calls
+    if (!c.start) return einval(e, c.encode ? "x is null" : "z_in is null");
+    if (int arc = ens ? ensemble_args_refusal(e, c) : LNS_OK) return arc;
+    if (scored && !c.y_true) return einval(e, "y_true is null");
+    if (!scored && !ens && !c.out) return einval(e, "out is null");
     if ((ens ? c.traj : c.B) <= 0) return einval(e, "B must be positive");
     if (ens && c.M <= 0) return einval(e, "M must be positive");
     if (c.T <= 0) return einval(e, "T must be positive");
-    if (ens && c.var_out && c.M < 2) return einval(e, "var_out needs M >= 2");
-    if (ens_scored) {
-        if (c.M < 2 || c.M > LNS_SCORE_MAX_MEMBERS) return einval(e, "ensemble scoring needs M in 2 .. 128");
-        if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
-    }
-    if (ens_quant) {
-        if (c.M > LNS_SCORE_MAX_MEMBERS) return einval(e, "ensemble quantiles need M in 1 .. 128");
-        if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
-        if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
-        if (c.spec && c.spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "norm: the per-channel form needs in_channels <= 8");
-        if (c.qspec->n_thr > 0 && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "thresholds need in_channels <= 8");
-    }
-    if (ens_exceed) {
-        if (c.M > LNS_SCORE_MAX_MEMBERS) return einval(e, "ensemble exceedance needs M in 1 .. 128");
-        if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
-        if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
-        if (e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "thresholds need in_channels <= 8");
-    }
-    if (ens_obs) {
-        if (const char* why = etkf_members_refusal(c.M)) { e->err = std::string("ensemble analysis needs ") + why; return LNS_EINVAL; }
-        if (c.var_out && !c.out) return einval(e, "var_out needs mean_out");
-        if (c.param_analysis && !c.param) return einval(e, "param_analysis needs param");
-        if (c.spec && c.spec->size != sizeof(lns_eval_spec)) return einval(e, "norm: the size field is not sizeof(lns_eval_spec)");
-        if (c.spec && c.spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "norm: the per-channel form needs in_channels <= 8");
-        if (c.ens_local && (long)e->lat_H * e->lat_W > LNS_LETKF_MAX_DOMAINS) return einval(e, "local ensemble analysis needs a latent grid of at most 4096 pixels");
-    }
+    if (int mrc = ens ? ensemble_members_refusal(e, c) : LNS_OK) return mrc;
     if (scored) {
         if (c.t0 < 0 || (long)c.t0 + c.T > c.T_total) {
             e->err = fmt("t0 + T = %d + %d exceeds T_total = %d (or t0 < 0)", c.t0, c.T, c.T_total);
@@ -2799,7 +2803,7 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
         }
         if (!c.frame_out && !c.seq_out) return einval(e, "frame_out and seq_out are both null");
     }
-    if (scored || ens_scored) {
+    if (spec_scored) {
         if (!c.spec || c.spec->size != sizeof(lns_eval_spec)) return einval(e, "spec is null or its size field is not sizeof(lns_eval_spec)");
         if (c.spec->per_channel && e->cfg.in_channels > LNS_METRIC_MAX_CH) return einval(e, "spec: the per-channel form needs in_channels <= 8");
     }
@@ -2867,6 +2871,57 @@ static int rollout_refusal(lns_engine* e, const RolloutCall& c) {
     return LNS_OK;
 }
 
+// whose workspace check_ws finds too small
+static const char* ws_label(SinkKind sink, EnsForm form) {
+    if (sink == SINK_ENSEMBLE) return form == ENS_ANALYSIS_LOCAL ? "local ensemble analysis " : (form == ENS_ANALYSIS ? "ensemble analysis " : "ensemble ");
+    return sink == SINK_SCORED ? "evaluation " : (sink == SINK_KEPT ? "selection " : "");
+}
+
+// What a SINK_ENSEMBLE call enqueues on the caller's stream ahead of rollout_loop.  Exceedance tables: the kernels of every decode
+// stream add into table_out, so it is cleared on the stream they all start behind (the loop's fork event follows this memset).
+static int ensemble_begin(lns_engine* e, const RolloutCall& c, hipStream_t stream) {
+    if (c.ens_form == ENS_EXCEED)
+        HIPCHK(e, hipMemsetAsync(c.table_out, 0, exceed_table_bytes(c.traj, c.n_keep, c.xspec->n_thr, e->cfg.in_channels, c.M), stream));
+    return LNS_OK;
+}
+
+// ... and behind it, on the caller's stream once the decode streams have joined.  Scores: the plane sums in scores_out -> the
+// scores, in place.  The two filters: the sums of every decode stream and the copy of the last latents (c.z_last: the caller's
+// buffer or z_analysis itself) are ordered before them; every buffer has one writer and is read behind it in stream order.
+// Global: slice partials -> S, g, stat; the transform; z_last under X.  Local: patch sums -> the tapered (S, g) per domain and
+// the global ones; the transform per domain, then the global one; latent pixel l under X_loc[l].  Both: a per-member param under X.
+static int ensemble_finish(lns_engine* e, const RolloutCall& c, const WsLayout& L, hipStream_t stream) {
+    const int C = e->cfg.in_channels, HW = e->cfg.Ly * e->cfg.Lx, hw = e->lat_H * e->lat_W;
+    if (c.ens_form == ENS_SCORED) HIPCHK(e, launch_ensemble_score_finish(c.scores_out, c.traj, c.n_keep, C, HW, c.spec->eps, c.seq_out, stream));
+    if (!ens_analysis(c.ens_form)) return LNS_OK;
+    const bool local = c.ens_form == ENS_ANALYSIS_LOCAL;
+    const AnalysisRegion R = analysis_region(e, c.ens_form, c.traj, c.M, c.n_keep);
+    char* rb = static_cast<char*>(c.ws) + L.etkf_off;
+    auto dbl = [&](size_t off, double* given = nullptr) { return given ? given : reinterpret_cast<double*>(rb + off); };   // the caller's buffer, or the region's
+    auto i32 = [&](size_t off, int32_t* given) { return given ? given : reinterpret_cast<int*>(rb + off); };
+    double* stat = dbl(R.stat, c.stat_out);
+    // the global transform: of the Grams of the n_keep steps (the transform sums them), or of the one sum combine has made
+    const EtkfTransformArgs tg = {dbl(R.S), dbl(R.g), dbl(R.X, c.X_out), dbl(R.wbar, c.wbar_out), dbl(R.lam, c.lam_out), i32(R.status, c.status_out),
+                                  c.rho, c.traj, local ? 1 : c.n_keep, c.M};
+    if (local) {
+        const LetkfCombineArgs ca = {dbl(R.part), dbl(R.S_loc), dbl(R.g_loc), dbl(R.S), dbl(R.g), stat, c.loc_radius, c.traj, c.n_keep, c.M,
+                                     e->lat_H, e->lat_W, c.bc_y, c.bc_x};
+        const EtkfTransformArgs tl = {ca.S_loc, ca.g_loc, dbl(R.X_loc, c.X_loc_out), dbl(R.wbar_loc, c.wbar_loc_out), dbl(R.lam_loc, c.lam_loc_out),
+                                      i32(R.status_loc, c.status_loc_out), c.rho, c.traj * hw, 1, c.M};
+        const LetkfUpdateArgs ua = {c.z_last, tl.X, c.z_analysis, c.traj, c.M, e->lat_C, hw};
+        HIPCHK(e, launch_letkf_combine(ca, stream));
+        HIPCHK(e, launch_etkf_transform(tl, stream));
+        HIPCHK(e, launch_etkf_transform(tg, stream));
+        HIPCHK(e, launch_letkf_update(ua, stream));
+    } else {
+        HIPCHK(e, launch_ensemble_obs_gram_finish(dbl(R.part), c.traj * c.n_keep, etkf_slices((long)C * HW), c.M, dbl(R.S), dbl(R.g), stat, stream));
+        HIPCHK(e, launch_etkf_transform(tg, stream));
+        HIPCHK(e, launch_ensemble_transform(c.z_last, tg.X, c.traj, c.M, (long)e->lat_C * hw, c.z_analysis, stream));
+    }
+    if (c.param && c.param_analysis) HIPCHK(e, launch_ensemble_transform(c.param, tg.X, c.traj, c.M, 1, c.param_analysis, stream));
+    return LNS_OK;
+}
+
 // the one call path behind the rollout entry points
 static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if (!e) return LNS_EINVAL;
@@ -2878,21 +2933,9 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     if ((rc = ws_layout(e, c.B, c.sink, &L))) return rc;
     if (scored && c.maps) add_maps_region(e, c.B, &L);
     if (scored && c.attrib) add_attrib_region(e, c.B, &L);
-    const bool ens_obs = c.sink == SINK_ENSEMBLE && c.ens_obs;
-    const bool ens_local = ens_obs && c.ens_local;
-    EtkfRegion R = {};
-    LetkfRegion RL = {};
-    if (ens_local) {
-        RL = letkf_region(e, c.traj, c.M, c.n_keep);
-        L.etkf_off = round_up_sz(L.total, 256);
-        L.total = L.etkf_off + RL.bytes;
-    } else if (ens_obs) {
-        R = etkf_region(e, c.traj, c.M, c.n_keep);
-        L.etkf_off = round_up_sz(L.total, 256);
-        L.total = L.etkf_off + R.bytes;
-    }
-    if ((rc = check_ws(e, L, scored ? "evaluation " : (c.sink == SINK_KEPT ? "selection " : (ens_local ? "local ensemble analysis " : (ens_obs ? "ensemble analysis " : (c.sink == SINK_ENSEMBLE ? "ensemble " : "")))),
-                       c.ws, c.ws_bytes))) return rc;
+    const bool ens = c.sink == SINK_ENSEMBLE;
+    if (ens && ens_analysis(c.ens_form)) add_analysis_region(e, c.ens_form, c.traj, c.M, c.n_keep, &L);
+    if ((rc = check_ws(e, L, ws_label(c.sink, c.ens_form), c.ws, c.ws_bytes))) return rc;
     Plan* pe = nullptr;
     if (c.encode && (rc = get_plan(e, PK_ENC, c.B, 0, 0, &pe))) return rc;
     const lns_config& cfg = e->cfg;
@@ -2912,10 +2955,7 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
     }
     // time maps: the horizon's first call clears the state on the caller's stream, which every stream of the loop starts behind
     if (scored && c.maps && c.t0 == 0) HIPCHK(e, hipMemsetAsync(base + L.maps_off, 0, L.maps_bytes, r.stream));
-    // exceedance tables: the kernels of every decode stream add into table_out, so it is cleared here, on the caller's stream,
-    // which every stream of the loop starts behind (its fork event is recorded after this memset)
-    if (c.sink == SINK_ENSEMBLE && c.ens_exceed)
-        HIPCHK(e, hipMemsetAsync(c.table_out, 0, exceed_table_bytes(c.traj, c.n_keep, c.xspec->n_thr, cfg.in_channels, c.M), r.stream));
+    if (ens && (rc = ensemble_begin(e, c, r.stream))) return rc;   // (ahead of the loop's fork event)
     if ((rc = rollout_loop(e, r, z0, c, L))) return rc;
     // every plane's pair is in place once the decode streams have joined: frame- and sequence-wise ratios, once the
     // horizon is complete (the pairs of the earlier chunks are in the workspace)
@@ -2939,47 +2979,7 @@ static int rollout_call(lns_engine* e, const RolloutCall& c) {
         time_maps_args(e, c, L, &tm);
         HIPCHK(e, launch_time_maps_finish(tm, r.stream));
     }
-    if (c.sink == SINK_ENSEMBLE && c.ens_scored)     // likewise: the plane sums in scores_out -> the scores, in place
-        HIPCHK(e, launch_ensemble_score_finish(c.scores_out, c.traj, c.n_keep, cfg.in_channels, cfg.Ly * cfg.Lx, c.spec->eps,
-                                               c.seq_out, r.stream));
-    if (ens_local) {
-        // The localised filter, on the caller's stream behind the join, as the global one below: the patch sums of every decode
-        // stream and the copy of the last latents are ordered before it.  Every buffer has one writer and is read behind it
-        // in stream order.
-        char* rb = base + L.etkf_off;
-        auto dbl = [&](size_t off) { return reinterpret_cast<double*>(rb + off); };
-        const int hw = e->lat_H * e->lat_W;
-        LetkfCombineArgs ca = {dbl(RL.part), dbl(RL.S_loc), dbl(RL.g_loc), dbl(RL.S), dbl(RL.g), c.stat_out ? c.stat_out : dbl(RL.stat),
-                               c.loc_radius, c.traj, c.n_keep, c.M, e->lat_H, e->lat_W, c.bc_y, c.bc_x};
-        EtkfTransformArgs tl = {ca.S_loc, ca.g_loc, c.X_loc_out ? c.X_loc_out : dbl(RL.X_loc), c.wbar_loc_out ? c.wbar_loc_out : dbl(RL.wbar_loc),
-                                c.lam_loc_out ? c.lam_loc_out : dbl(RL.lam_loc),
-                                c.status_loc_out ? c.status_loc_out : reinterpret_cast<int*>(rb + RL.status_loc), c.rho, c.traj * hw, 1, c.M};
-        EtkfTransformArgs tg = {ca.S_glob, ca.g_glob, c.X_out ? c.X_out : dbl(RL.X), c.wbar_out ? c.wbar_out : dbl(RL.wbar),
-                                c.lam_out ? c.lam_out : dbl(RL.lam), c.status_out ? c.status_out : reinterpret_cast<int*>(rb + RL.status),
-                                c.rho, c.traj, 1, c.M};
-        HIPCHK(e, launch_letkf_combine(ca, r.stream));
-        HIPCHK(e, launch_etkf_transform(tl, r.stream));
-        HIPCHK(e, launch_etkf_transform(tg, r.stream));
-        const LetkfUpdateArgs ua = {c.z_last, tl.X, c.z_analysis, c.traj, c.M, e->lat_C, hw};
-        HIPCHK(e, launch_letkf_update(ua, r.stream));
-        if (c.param && c.param_analysis) HIPCHK(e, launch_ensemble_transform(c.param, tg.X, c.traj, c.M, 1, c.param_analysis, r.stream));
-    } else if (ens_obs) {
-        // The filter, on the caller's stream behind the join: every Gram launch of the decode streams and the copy of the last
-        // latents (c.z_last: the caller's buffer or z_analysis itself) are ordered before it.
-        char* rb = base + L.etkf_off;
-        double* S = reinterpret_cast<double*>(rb + R.S);
-        double* g = reinterpret_cast<double*>(rb + R.g);
-        double* stat = c.stat_out ? c.stat_out : reinterpret_cast<double*>(rb + R.stat);
-        EtkfTransformArgs ta = {S, g, c.X_out ? c.X_out : reinterpret_cast<double*>(rb + R.X),
-                                c.wbar_out ? c.wbar_out : reinterpret_cast<double*>(rb + R.wbar),
-                                c.lam_out ? c.lam_out : reinterpret_cast<double*>(rb + R.lam),
-                                c.status_out ? c.status_out : reinterpret_cast<int*>(rb + R.status), c.rho, c.traj, c.n_keep, c.M};
-        HIPCHK(e, launch_ensemble_obs_gram_finish(reinterpret_cast<const double*>(rb + R.part), c.traj * c.n_keep,
-                                                  etkf_slices((long)cfg.in_channels * cfg.Ly * cfg.Lx), c.M, S, g, stat, r.stream));
-        HIPCHK(e, launch_etkf_transform(ta, r.stream));
-        HIPCHK(e, launch_ensemble_transform(c.z_last, ta.X, c.traj, c.M, zper, c.z_analysis, r.stream));
-        if (c.param && c.param_analysis) HIPCHK(e, launch_ensemble_transform(c.param, ta.X, c.traj, c.M, 1, c.param_analysis, r.stream));
-    }
+    if (ens && (rc = ensemble_finish(e, c, L, r.stream))) return rc;
     return r.finish();
 }
 
@@ -3242,13 +3242,19 @@ int lns_rollout_latent_select(lns_engine* e, const float* z_in, const float* par
 }
 
 // ---- ensemble rollout (include/lns.h) --------------------------------------------------------------------------
+// What the six ensemble entry points share of their RolloutCall; each adds the fields of its form
+static RolloutCall ensemble_call(EnsForm form, const float* z_in, const float* param, int B, int M, int T, const int* keep_steps_host,
+                                 int n_keep, float* mean_out, float* var_out, float* z_last, void* ws, size_t ws_bytes, void* stream) {
+    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
+    c.sink = SINK_ENSEMBLE; c.ens_form = form; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
+    c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
+    return c;
+}
+
 int lns_rollout_latent_ensemble(lns_engine* e, const float* z_in, const float* param, int B, int M, int T,
                                 const int* keep_steps_host, int n_keep, float* mean_out, float* var_out, float* z_last,
                                 void* ws, size_t ws_bytes, void* stream) {
-    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
-    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
-    c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
-    return rollout_call(e, c);
+    return rollout_call(e, ensemble_call(ENS_STATS, z_in, param, B, M, T, keep_steps_host, n_keep, mean_out, var_out, z_last, ws, ws_bytes, stream));
 }
 
 // ---- ensemble validation (include/lns.h) ------------------------------------------------------------------------
@@ -3256,10 +3262,8 @@ int lns_rollout_latent_ensemble_eval(lns_engine* e, const float* z_in, const flo
                                      const int* keep_steps_host, int n_keep, const lns_eval_spec* spec, float* scores_out,
                                      float* seq_out, int32_t* rank_out, float* mean_out, float* var_out, float* z_last,
                                      void* ws, size_t ws_bytes, void* stream) {
-    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
-    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
-    c.ens_scored = true; c.y_true = y_true; c.spec = spec; c.scores_out = scores_out; c.seq_out = seq_out; c.rank_out = rank_out;
-    c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
+    RolloutCall c = ensemble_call(ENS_SCORED, z_in, param, B, M, T, keep_steps_host, n_keep, mean_out, var_out, z_last, ws, ws_bytes, stream);
+    c.y_true = y_true; c.spec = spec; c.scores_out = scores_out; c.seq_out = seq_out; c.rank_out = rank_out;
     return rollout_call(e, c);
 }
 
@@ -3268,10 +3272,8 @@ int lns_rollout_latent_ensemble_quantiles(lns_engine* e, const float* z_in, cons
                                           const int* keep_steps_host, int n_keep, const lns_ensemble_quantile_spec* qspec,
                                           const lns_eval_spec* norm, float* quant_out, float* prob_out, float* mean_out,
                                           float* var_out, float* z_last, void* ws, size_t ws_bytes, void* stream) {
-    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
-    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
-    c.ens_quant = true; c.qspec = qspec; c.spec = norm; c.quant_out = quant_out; c.prob_out = prob_out;
-    c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
+    RolloutCall c = ensemble_call(ENS_QUANT, z_in, param, B, M, T, keep_steps_host, n_keep, mean_out, var_out, z_last, ws, ws_bytes, stream);
+    c.qspec = qspec; c.spec = norm; c.quant_out = quant_out; c.prob_out = prob_out;
     return rollout_call(e, c);
 }
 
@@ -3280,24 +3282,37 @@ int lns_rollout_latent_ensemble_exceed(lns_engine* e, const float* z_in, const f
                                        const int* keep_steps_host, int n_keep, const lns_ensemble_exceed_spec* xspec,
                                        const lns_eval_spec* norm, int32_t* table_out, float* mean_out, float* var_out,
                                        float* z_last, void* ws, size_t ws_bytes, void* stream) {
-    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
-    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
-    c.ens_exceed = true; c.xspec = xspec; c.spec = norm; c.y_true = y_true; c.table_out = table_out;
-    c.out = mean_out; c.var_out = var_out; c.z_last = z_last;
+    RolloutCall c = ensemble_call(ENS_EXCEED, z_in, param, B, M, T, keep_steps_host, n_keep, mean_out, var_out, z_last, ws, ws_bytes, stream);
+    c.xspec = xspec; c.spec = norm; c.y_true = y_true; c.table_out = table_out;
     return rollout_call(e, c);
 }
 
-// ---- ensemble transform Kalman filter (include/lns.h) -----------------------------------------------------------
-int lns_rollout_ensemble_analysis_workspace_bytes(lns_engine* e, int B, int M, int n_keep, size_t* bytes) {
+// ---- ensemble transform Kalman filter, global and localised (include/lns.h) -------------------------------------
+// the size query of either analysis form: the ensemble layout and the form's region behind it
+static int analysis_workspace_bytes(lns_engine* e, EnsForm form, int B, int M, int n_keep, size_t* bytes) {
     if (!e) return LNS_EINVAL;
     if (B <= 0) return einval(e, "B must be positive");
     if (M <= 0) return einval(e, "M must be positive");
-    if (const char* why = etkf_members_refusal(M)) { e->err = std::string("ensemble analysis needs ") + why; return LNS_EINVAL; }
+    if (int mrc = analysis_members_refusal(e, M)) return mrc;
     if (n_keep < 1) return einval(e, "n_keep must be at least 1");
+    if (form == ENS_ANALYSIS_LOCAL && (long)e->lat_H * e->lat_W > LNS_LETKF_MAX_DOMAINS)
+        return einval(e, "local ensemble analysis needs a latent grid of at most 4096 pixels");
     size_t base = 0;
     if (int rc = workspace_bytes(e, ensemble_batch(B, M), SINK_ENSEMBLE, &base)) return rc;
-    if (bytes) *bytes = round_up_sz(base, 256) + etkf_region(e, B, M, n_keep).bytes;
+    if (bytes) *bytes = round_up_sz(base, 256) + analysis_region(e, form, B, M, n_keep).bytes;
     return LNS_OK;
+}
+int lns_rollout_ensemble_analysis_workspace_bytes(lns_engine* e, int B, int M, int n_keep, size_t* bytes) { return analysis_workspace_bytes(e, ENS_ANALYSIS, B, M, n_keep, bytes); }
+int lns_rollout_ensemble_analysis_local_workspace_bytes(lns_engine* e, int B, int M, int n_keep, size_t* bytes) { return analysis_workspace_bytes(e, ENS_ANALYSIS_LOCAL, B, M, n_keep, bytes); }
+
+// what the two analysis entry points add to ensemble_call's RolloutCall alike: the observations and the global filter's outputs
+static void analysis_fields(RolloutCall* c, const float* y_obs, const float* rinv, int64_t rinv_bs, int64_t rinv_ss, const lns_eval_spec* norm,
+                            double rho, float* z_analysis, float* param_analysis, double* X_out, double* wbar_out, double* lam_out,
+                            double* stat_out, int32_t* status_out) {
+    c->y_true = y_obs; c->rinv = rinv; c->rinv_bs = rinv_bs; c->rinv_ss = rinv_ss; c->spec = norm; c->rho = rho;
+    c->z_analysis = z_analysis; c->param_analysis = param_analysis; c->X_out = X_out; c->wbar_out = wbar_out; c->lam_out = lam_out;
+    c->stat_out = stat_out; c->status_out = status_out;
+    c->z_last = c->z_last ? c->z_last : z_analysis;  // the forecast latents of step T - 1: the update reads them (in place without z_last)
 }
 
 int lns_rollout_latent_ensemble_analysis(lns_engine* e, const float* z_in, const float* param, const float* y_obs, const float* rinv,
@@ -3305,28 +3320,9 @@ int lns_rollout_latent_ensemble_analysis(lns_engine* e, const float* z_in, const
                                          const lns_eval_spec* norm, double rho, float* z_analysis, float* param_analysis, double* X_out,
                                          double* wbar_out, double* lam_out, double* stat_out, int32_t* status_out, float* mean_out,
                                          float* var_out, float* z_last, void* ws, size_t ws_bytes, void* stream) {
-    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
-    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
-    c.ens_obs = true; c.y_true = y_obs; c.rinv = rinv; c.rinv_bs = rinv_bs; c.rinv_ss = rinv_ss; c.spec = norm; c.rho = rho;
-    c.z_analysis = z_analysis; c.param_analysis = param_analysis; c.X_out = X_out; c.wbar_out = wbar_out; c.lam_out = lam_out;
-    c.stat_out = stat_out; c.status_out = status_out;
-    c.out = mean_out; c.var_out = var_out;
-    c.z_last = z_last ? z_last : z_analysis;         // the forecast latents of step T - 1: the update reads them (in place without z_last)
+    RolloutCall c = ensemble_call(ENS_ANALYSIS, z_in, param, B, M, T, keep_steps_host, n_keep, mean_out, var_out, z_last, ws, ws_bytes, stream);
+    analysis_fields(&c, y_obs, rinv, rinv_bs, rinv_ss, norm, rho, z_analysis, param_analysis, X_out, wbar_out, lam_out, stat_out, status_out);
     return rollout_call(e, c);
-}
-
-// ---- localised ensemble transform Kalman filter (include/lns.h) --------------------------------------------------
-int lns_rollout_ensemble_analysis_local_workspace_bytes(lns_engine* e, int B, int M, int n_keep, size_t* bytes) {
-    if (!e) return LNS_EINVAL;
-    if (B <= 0) return einval(e, "B must be positive");
-    if (M <= 0) return einval(e, "M must be positive");
-    if (const char* why = etkf_members_refusal(M)) { e->err = std::string("ensemble analysis needs ") + why; return LNS_EINVAL; }
-    if (n_keep < 1) return einval(e, "n_keep must be at least 1");
-    if ((long)e->lat_H * e->lat_W > LNS_LETKF_MAX_DOMAINS) return einval(e, "local ensemble analysis needs a latent grid of at most 4096 pixels");
-    size_t base = 0;
-    if (int rc = workspace_bytes(e, ensemble_batch(B, M), SINK_ENSEMBLE, &base)) return rc;
-    if (bytes) *bytes = round_up_sz(base, 256) + letkf_region(e, B, M, n_keep).bytes;
-    return LNS_OK;
 }
 
 int lns_rollout_latent_ensemble_analysis_local(lns_engine* e, const float* z_in, const float* param, const float* y_obs, const float* rinv,
@@ -3336,15 +3332,10 @@ int lns_rollout_latent_ensemble_analysis_local(lns_engine* e, const float* z_in,
                                                int32_t* status_local, float* param_analysis, double* X_out, double* wbar_out,
                                                double* lam_out, double* stat_out, int32_t* status_out, float* mean_out, float* var_out,
                                                float* z_last, void* ws, size_t ws_bytes, void* stream) {
-    RolloutCall c(z_in, false, param, ensemble_batch(B, M), T, ws, ws_bytes, stream);
-    c.sink = SINK_ENSEMBLE; c.traj = B; c.M = M; c.keep = keep_steps_host; c.n_keep = n_keep;
-    c.ens_obs = true; c.y_true = y_obs; c.rinv = rinv; c.rinv_bs = rinv_bs; c.rinv_ss = rinv_ss; c.spec = norm; c.rho = rho;
-    c.ens_local = true; c.loc_radius = loc_radius; c.bc_y = bc_y; c.bc_x = bc_x;
+    RolloutCall c = ensemble_call(ENS_ANALYSIS_LOCAL, z_in, param, B, M, T, keep_steps_host, n_keep, mean_out, var_out, z_last, ws, ws_bytes, stream);
+    analysis_fields(&c, y_obs, rinv, rinv_bs, rinv_ss, norm, rho, z_analysis, param_analysis, X_out, wbar_out, lam_out, stat_out, status_out);
+    c.loc_radius = loc_radius; c.bc_y = bc_y; c.bc_x = bc_x;
     c.X_loc_out = X_local; c.wbar_loc_out = wbar_local; c.lam_loc_out = lam_local; c.status_loc_out = status_local;
-    c.z_analysis = z_analysis; c.param_analysis = param_analysis; c.X_out = X_out; c.wbar_out = wbar_out; c.lam_out = lam_out;
-    c.stat_out = stat_out; c.status_out = status_out;
-    c.out = mean_out; c.var_out = var_out;
-    c.z_last = z_last ? z_last : z_analysis;         // the forecast latents of step T - 1: the update reads them (in place without z_last)
     return rollout_call(e, c);
 }
 

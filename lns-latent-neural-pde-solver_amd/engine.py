@@ -9,6 +9,7 @@ import contextlib
 import ctypes
 import functools
 import numbers
+import types
 
 import numpy as np
 
@@ -131,6 +132,17 @@ def update_spec(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, max_
     return spec
 
 
+def _op_check(rc, name):
+    """The tail of a call that has no engine handle (lns_op_*, lns_loss_*): the message is the library's create error."""
+    if rc != 0:
+        raise LnsError("%s failed (%d): %s" % (name, rc, _lib.lib().lns_create_error().decode()))
+
+
+def _ref(spec):
+    """A nullable struct argument."""
+    return ctypes.byref(spec) if spec is not None else None
+
+
 def normalize_obs(obs_steps, weights=None):
     """(steps, weights) of an observation table as plain lists: 0-based, strictly ascending steps, 1 .. LNS_OBS_MAX of them;
     weights finite and >= 0 (None: all 1).  The C calls check the same things; this is the early, readable refusal."""
@@ -209,8 +221,7 @@ def obs_loss(z_pred, obs, obs_steps, weights=None, z0=None, z_background=None, b
                                     (ctypes.c_double * len(w))(*w), Engine._ptr(z0), Engine._ptr(z_background), float(background),
                                     Engine._ptr(per), loss.data_ptr(), grad.data_ptr(), Engine._ptr(gbg), scratch.data_ptr(),
                                     scratch.numel(), Engine._stream(z_pred))
-    if rc != 0:
-        raise LnsError("lns_loss_obs_mse failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    _op_check(rc, "lns_loss_obs_mse")
     return loss, per, grad, gbg
 
 
@@ -233,8 +244,7 @@ def orthonormalize(v, r_out=None, logr_acc=None, need_r=False):
                 raise LnsError("%s must be a contiguous float64 %s tensor on v's device" % (name, shape))
         L = _lib.lib()
         rc = L.lns_op_orthonormalize(v.data_ptr(), B, K, n, Engine._ptr(r_out), Engine._ptr(logr_acc), Engine._stream(v))
-    if rc != 0:
-        raise LnsError("lns_op_orthonormalize failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    _op_check(rc, "lns_op_orthonormalize")
     return v, r_out
 
 
@@ -256,8 +266,7 @@ def smooth_l1(pred, target, beta=1.0, need_grad=True, loss_out=None, grad_out=No
         rc = L.lns_loss_smooth_l1(pred.data_ptr(), target.data_ptr(), n, float(beta), loss.data_ptr(),
                                   grad.data_ptr() if grad is not None else None, scratch.data_ptr(), scratch.numel(),
                                   Engine._stream(pred))
-    if rc != 0:
-        raise LnsError("lns_loss_smooth_l1 failed (%d): %s" % (rc, L.lns_create_error().decode()))
+    _op_check(rc, "lns_loss_smooth_l1")
     return loss, grad
 
 
@@ -770,6 +779,66 @@ class Engine:
                            % (p.numel(), B, M))
         return p.reshape(B, M).to(torch.float32).contiguous()
 
+    def _ensemble_setup(self, z, steps, keep_steps, return_mean, return_var, few=None, y=None, y_obs=None):
+        """The checks the six rollout_latent_ensemble* methods share, in the order they are made, and what follows from them:
+        a record of z, B, M, steps, keep, arr (keep as a ctypes array), nk, tail = (C, Ly, Lx) and y, the truth of the kept
+        steps; mean, var, z_last and p are `_ensemble_outputs`'.  The truth comes as y [B, T, ...] (steps None: T; the kept steps
+        are sliced out) or as y_obs [B, n_keep, ...] (taken as it is).  few: the text of the refusal of a variance of fewer than
+        two members, for the forms that refuse it here."""
+        import torch
+        z = self._dev(z)
+        truth = y if y is not None else y_obs
+        if truth is not None:
+            truth = self._dev(truth)
+        C, H, W = self.latent_shape()
+        c = self.cfg
+        tail = (c.in_channels, c.Ly, c.Lx)
+        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
+            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
+        B, M = int(z.shape[0]), int(z.shape[1])
+
+        def flags():
+            if return_var and not return_mean:
+                raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
+            if few and return_var and M < 2:
+                raise LnsError(few % M)
+        if y is not None:
+            if truth.dim() != 5 or truth.shape[0] != B or tuple(truth.shape[2:]) != tail or truth.dtype != torch.float32:
+                raise LnsError("ground truth must be fp32 [B, T, %d, %d, %d] with the latents' batch, got %s" % (tail + (tuple(truth.shape),)))
+            if truth.device != z.device:
+                raise LnsError("ground truth is on %s but the latents are on %s" % (truth.device, z.device))
+        if y_obs is None:
+            flags()
+        steps = int(truth.shape[1]) if steps is None and y is not None else int(steps)
+        if y is not None and steps > truth.shape[1]:
+            raise LnsError("%d steps do not fit the %d steps of the ground truth" % (steps, truth.shape[1]))
+        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
+        nk = len(keep)
+        if y_obs is not None:
+            if tuple(truth.shape) != (B, nk) + tail or truth.device != z.device:
+                raise LnsError("y_obs must be %s on the latents' device, got %s" % ((B, nk) + tail, tuple(truth.shape)))
+            flags()
+        if y is not None:
+            truth = truth[:, keep].contiguous()
+        return types.SimpleNamespace(z=z, B=B, M=M, steps=steps, keep=keep, arr=(ctypes.c_int * nk)(*keep), nk=nk, tail=tail, y=truth,
+                                     mean=None, var=None, z_last=None, p=None)
+
+    def _ensemble_outputs(self, s, param, return_mean, return_var, return_last, out=None):
+        """mean (out: the caller's), var and z_last where asked for and the per-member param into the record -- behind whatever the
+        form makes of its own arguments, so that a bad request is refused before a bad param."""
+        import torch
+        shape = (s.B, s.nk) + s.tail
+        s.mean = self._out(out, shape, s.z.device) if return_mean else None
+        s.var = torch.empty(shape, dtype=torch.float32, device=s.z.device) if return_var else None
+        s.z_last = torch.empty_like(s.z) if return_last else None
+        s.p = self._member_param(param, s.z, s.B, s.M)
+
+    def _ensemble_workspace(self, B, M, device, query="lns_rollout_ensemble_workspace_bytes", *args):
+        """The workspace of batch B * M, at least as large as the ensemble size query `query` asks."""
+        n = ctypes.c_size_t(0)
+        self._check(getattr(self._L, query)(self._h, B, M, *args, ctypes.byref(n)), query)
+        return self._workspace(B * M, device, min_bytes=int(n.value))
+
     def rollout_latent_ensemble(self, z, steps, param=None, keep_steps=None, return_var=True, return_last=False, out=None):
         """z [B, M, c, h, w]: M perturbed members of each of B trajectories (the noise is the caller's, as in training).
         Rolls every member out and returns, per kept step, the mean and the unbiased variance over the members
@@ -778,31 +847,15 @@ class Engine:
         [B] (broadcast over the members) or per member [B, M].  M = 1 has no variance: return_var=False.  out: a
         preallocated mean.  The workspace is the one of batch B * M: `check_finite(B * M)` covers the call."""
         import torch
-        z = self._dev(z)
-        C, H, W = self.latent_shape()
-        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
-            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
-        B, M = int(z.shape[0]), int(z.shape[1])
-        if return_var and M < 2:
-            raise LnsError("the variance needs at least 2 members, got M = %d (return_var=False for the mean alone)" % M)
-        steps = int(steps)
-        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
-        arr = (ctypes.c_int * len(keep))(*keep)
-        c = self.cfg
-        shape = (B, len(keep), c.in_channels, c.Ly, c.Lx)
-        mean = self._out(out, shape, z.device)
-        var = torch.empty(shape, dtype=torch.float32, device=z.device) if return_var else None
-        z_last = torch.empty_like(z) if return_last else None
-        p = self._member_param(param, z, B, M)
-        with torch.cuda.device(z.device):
-            n = ctypes.c_size_t(0)
-            self._check(self._L.lns_rollout_ensemble_workspace_bytes(self._h, B, M, ctypes.byref(n)),
-                        "lns_rollout_ensemble_workspace_bytes")
-            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
-            self._check(self._L.lns_rollout_latent_ensemble(self._h, z.data_ptr(), self._ptr(p), B, M, steps, arr, len(keep),
-                                                            mean.data_ptr(), self._ptr(var), self._ptr(z_last), ws.data_ptr(),
-                                                            ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble")
-        res = (mean,) + ((var,) if return_var else ()) + ((z_last,) if return_last else ())
+        s = self._ensemble_setup(z, steps, keep_steps, True, return_var,
+                                 few="the variance needs at least 2 members, got M = %d (return_var=False for the mean alone)")
+        self._ensemble_outputs(s, param, True, return_var, return_last, out)
+        with torch.cuda.device(s.z.device):
+            ws = self._ensemble_workspace(s.B, s.M, s.z.device)
+            self._check(self._L.lns_rollout_latent_ensemble(self._h, s.z.data_ptr(), self._ptr(s.p), s.B, s.M, s.steps, s.arr, s.nk,
+                                                            s.mean.data_ptr(), self._ptr(s.var), self._ptr(s.z_last), ws.data_ptr(),
+                                                            ws.numel(), self._stream(s.z)), "lns_rollout_latent_ensemble")
+        res = (s.mean,) + ((s.var,) if return_var else ()) + ((s.z_last,) if return_last else ())
         return res[0] if len(res) == 1 else res
 
     def ensemble_stats(self, frames, return_var=True):
@@ -820,8 +873,7 @@ class Engine:
         var = torch.empty(shape, dtype=torch.float32, device=frames.device) if return_var else None
         with torch.cuda.device(frames.device):
             rc = self._L.lns_op_ensemble_stats(frames.data_ptr(), B, M, per, mean.data_ptr(), self._ptr(var), self._stream(frames))
-        if rc != 0:
-            raise LnsError("lns_op_ensemble_stats failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        _op_check(rc, "lns_op_ensemble_stats")
         return (mean, var) if return_var else mean
 
     # -- ensemble validation (include/lns.h "ensemble validation") ---------------------------------------------------
@@ -829,20 +881,26 @@ class Engine:
     def _scores_result(scores, seq, rank, mean=None, var=None, z_last=None):
         return EnsembleScores(scores[..., 0], scores[..., 1], scores[..., 2], scores[..., 3], seq, rank, mean, var, z_last)
 
+    @staticmethod
+    def _frames_and_truth(op, frames, y, yname):
+        """frames [n, B, M, C, H, W] and the truth [B, n, C, H, W] of an op wrapper, checked -> (frames, truth, frames' shape)."""
+        import torch
+        for t in (frames, y):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+                raise LnsError("%s takes fp32 HIP tensors" % op)
+        if frames.dim() != 6 or y.dim() != 5 or y.device != frames.device:
+            raise LnsError("%s takes frames [n, B, M, C, H, W] and %s [B, n, C, H, W] on one device" % (op, yname))
+        n, B, M, C, H, W = shape = tuple(int(v) for v in frames.shape)
+        if tuple(y.shape) != (B, n, C, H, W):
+            raise LnsError("%s must be %s for frames %s, got %s" % (yname, (B, n, C, H, W), shape, tuple(y.shape)))
+        return frames.contiguous(), y.contiguous(), shape
+
     def ensemble_score(self, frames, y, return_rank=True, **norm):
         """The scoring kernels of the ensemble validation on stored member fields (lns_op_ensemble_score): frames
         [n, B, M, C, H, W] (a frame buffer's layout), y [B, n, C, H, W], both normalised; `norm` as in `rollout_eval`.
         Returns EnsembleScores (mean, var, z_last None)."""
         import torch
-        for t in (frames, y):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-                raise LnsError("ensemble_score takes fp32 HIP tensors")
-        if frames.dim() != 6 or y.dim() != 5 or y.device != frames.device:
-            raise LnsError("ensemble_score takes frames [n, B, M, C, H, W] and y [B, n, C, H, W] on one device")
-        n, B, M, C, H, W = (int(v) for v in frames.shape)
-        if tuple(y.shape) != (B, n, C, H, W):
-            raise LnsError("y must be %s for frames %s, got %s" % ((B, n, C, H, W), tuple(frames.shape), tuple(y.shape)))
-        frames, y = frames.contiguous(), y.contiguous()
+        frames, y, (n, B, M, C, H, W) = self._frames_and_truth("ensemble_score", frames, y, "y")
         spec = eval_spec(C, **norm)
         scores = torch.empty((B, n, C, 4), dtype=torch.float32, device=y.device)
         seq = torch.empty((B, C, 4), dtype=torch.float32, device=y.device)
@@ -850,8 +908,7 @@ class Engine:
         with torch.cuda.device(y.device):
             rc = self._L.lns_op_ensemble_score(frames.data_ptr(), y.data_ptr(), n, B, M, C, H, W, ctypes.byref(spec),
                                                scores.data_ptr(), seq.data_ptr(), self._ptr(rank), None, self._stream(y))
-        if rc != 0:
-            raise LnsError("lns_op_ensemble_score failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        _op_check(rc, "lns_op_ensemble_score")
         return self._scores_result(scores, seq, rank)
 
     def rollout_latent_ensemble_eval(self, z, y, steps=None, param=None, keep_steps=None, return_rank=True, return_mean=False,
@@ -864,46 +921,20 @@ class Engine:
         and (return_mean / return_var / return_last) rollout_latent_ensemble's outputs.  The member fields are never stored;
         the workspace is rollout_latent_ensemble's."""
         import torch
-        z = self._dev(z)
-        y = self._dev(y)
-        C, H, W = self.latent_shape()
-        c = self.cfg
-        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
-            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
-        B, M = int(z.shape[0]), int(z.shape[1])
-        if y.dim() != 5 or y.shape[0] != B or tuple(y.shape[2:]) != (c.in_channels, c.Ly, c.Lx) or y.dtype != torch.float32:
-            raise LnsError("ground truth must be fp32 [B, T, %d, %d, %d] with the latents' batch, got %s"
-                           % (c.in_channels, c.Ly, c.Lx, tuple(y.shape)))
-        if y.device != z.device:
-            raise LnsError("ground truth is on %s but the latents are on %s" % (y.device, z.device))
-        if return_var and not return_mean:
-            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
-        steps = int(y.shape[1]) if steps is None else int(steps)
-        if steps > y.shape[1]:
-            raise LnsError("%d steps do not fit the %d steps of the ground truth" % (steps, y.shape[1]))
-        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
-        arr = (ctypes.c_int * len(keep))(*keep)
-        yk = y[:, keep].contiguous()
-        spec = eval_spec(c.in_channels, **norm)
-        nk = len(keep)
-        scores = torch.empty((B, nk, c.in_channels, 4), dtype=torch.float32, device=z.device)
-        seq = torch.empty((B, c.in_channels, 4), dtype=torch.float32, device=z.device)
-        rank = torch.empty((B, nk, c.in_channels, M + 1), dtype=torch.int32, device=z.device) if return_rank else None
-        shape = (B, nk, c.in_channels, c.Ly, c.Lx)
-        mean = torch.empty(shape, dtype=torch.float32, device=z.device) if return_mean else None
-        var = torch.empty(shape, dtype=torch.float32, device=z.device) if return_var else None
-        z_last = torch.empty_like(z) if return_last else None
-        p = self._member_param(param, z, B, M)
-        with torch.cuda.device(z.device):
-            n = ctypes.c_size_t(0)
-            self._check(self._L.lns_rollout_ensemble_workspace_bytes(self._h, B, M, ctypes.byref(n)),
-                        "lns_rollout_ensemble_workspace_bytes")
-            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+        s = self._ensemble_setup(z, steps, keep_steps, return_mean, return_var, y=y)
+        C, dev = self.cfg.in_channels, s.z.device
+        spec = eval_spec(C, **norm)
+        scores = torch.empty((s.B, s.nk, C, 4), dtype=torch.float32, device=dev)
+        seq = torch.empty((s.B, C, 4), dtype=torch.float32, device=dev)
+        rank = torch.empty((s.B, s.nk, C, s.M + 1), dtype=torch.int32, device=dev) if return_rank else None
+        self._ensemble_outputs(s, param, return_mean, return_var, return_last)
+        with torch.cuda.device(dev):
+            ws = self._ensemble_workspace(s.B, s.M, dev)
             self._check(self._L.lns_rollout_latent_ensemble_eval(
-                self._h, z.data_ptr(), self._ptr(p), yk.data_ptr(), B, M, steps, arr, nk, ctypes.byref(spec), scores.data_ptr(),
-                seq.data_ptr(), self._ptr(rank), self._ptr(mean), self._ptr(var), self._ptr(z_last), ws.data_ptr(), ws.numel(),
-                self._stream(z)), "lns_rollout_latent_ensemble_eval")
-        return self._scores_result(scores, seq, rank, mean, var, z_last)
+                self._h, s.z.data_ptr(), self._ptr(s.p), s.y.data_ptr(), s.B, s.M, s.steps, s.arr, s.nk, ctypes.byref(spec),
+                scores.data_ptr(), seq.data_ptr(), self._ptr(rank), self._ptr(s.mean), self._ptr(s.var), self._ptr(s.z_last),
+                ws.data_ptr(), ws.numel(), self._stream(s.z)), "lns_rollout_latent_ensemble_eval")
+        return self._scores_result(scores, seq, rank, s.mean, s.var, s.z_last)
 
     # -- ensemble quantiles (include/lns.h "ensemble quantiles") -------------------------------------------------------
     def ensemble_quantiles(self, frames, quantiles=(), thresholds=(), **norm):
@@ -921,11 +952,9 @@ class Engine:
         quant = torch.empty((B, n, qs.n_q, C, H, W), dtype=torch.float32, device=frames.device) if qs.n_q else None
         prob = torch.empty((B, n, qs.n_thr, C, H, W), dtype=torch.float32, device=frames.device) if qs.n_thr else None
         with torch.cuda.device(frames.device):
-            rc = self._L.lns_op_ensemble_quantiles(frames.data_ptr(), n, B, M, C, H, W, ctypes.byref(qs),
-                                                   ctypes.byref(spec) if spec is not None else None, self._ptr(quant),
-                                                   self._ptr(prob), self._stream(frames))
-        if rc != 0:
-            raise LnsError("lns_op_ensemble_quantiles failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+            rc = self._L.lns_op_ensemble_quantiles(frames.data_ptr(), n, B, M, C, H, W, ctypes.byref(qs), _ref(spec),
+                                                   self._ptr(quant), self._ptr(prob), self._stream(frames))
+        _op_check(rc, "lns_op_ensemble_quantiles")
         return EnsembleQuantiles(quant, prob, None, None, None)
 
     def rollout_latent_ensemble_quantiles(self, z, steps, quantiles=(0.05, 0.5, 0.95), thresholds=(), param=None, keep_steps=None,
@@ -937,39 +966,20 @@ class Engine:
         values are normalised, as the mean is.  Returns EnsembleQuantiles; return_mean / return_var / return_last add
         rollout_latent_ensemble's outputs.  The member fields are never stored; the workspace is rollout_latent_ensemble's."""
         import torch
-        z = self._dev(z)
-        C, H, W = self.latent_shape()
-        c = self.cfg
-        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
-            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
-        B, M = int(z.shape[0]), int(z.shape[1])
-        if return_var and not return_mean:
-            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
-        if return_var and M < 2:
-            raise LnsError("the variance needs at least 2 members, got M = %d" % M)
-        steps = int(steps)
-        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
-        arr = (ctypes.c_int * len(keep))(*keep)
-        nk = len(keep)
-        qs = quantile_spec(c.in_channels, M, quantiles, thresholds)
-        spec = eval_spec(c.in_channels, **norm) if norm else None
-        tail = (c.in_channels, c.Ly, c.Lx)
-        quant = torch.empty((B, nk, qs.n_q) + tail, dtype=torch.float32, device=z.device) if qs.n_q else None
-        prob = torch.empty((B, nk, qs.n_thr) + tail, dtype=torch.float32, device=z.device) if qs.n_thr else None
-        mean = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_mean else None
-        var = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_var else None
-        z_last = torch.empty_like(z) if return_last else None
-        p = self._member_param(param, z, B, M)
-        with torch.cuda.device(z.device):
-            n = ctypes.c_size_t(0)
-            self._check(self._L.lns_rollout_ensemble_workspace_bytes(self._h, B, M, ctypes.byref(n)),
-                        "lns_rollout_ensemble_workspace_bytes")
-            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+        s = self._ensemble_setup(z, steps, keep_steps, return_mean, return_var, few="the variance needs at least 2 members, got M = %d")
+        C, dev = self.cfg.in_channels, s.z.device
+        qs = quantile_spec(C, s.M, quantiles, thresholds)
+        spec = eval_spec(C, **norm) if norm else None
+        quant = torch.empty((s.B, s.nk, qs.n_q) + s.tail, dtype=torch.float32, device=dev) if qs.n_q else None
+        prob = torch.empty((s.B, s.nk, qs.n_thr) + s.tail, dtype=torch.float32, device=dev) if qs.n_thr else None
+        self._ensemble_outputs(s, param, return_mean, return_var, return_last)
+        with torch.cuda.device(dev):
+            ws = self._ensemble_workspace(s.B, s.M, dev)
             self._check(self._L.lns_rollout_latent_ensemble_quantiles(
-                self._h, z.data_ptr(), self._ptr(p), B, M, steps, arr, nk, ctypes.byref(qs),
-                ctypes.byref(spec) if spec is not None else None, self._ptr(quant), self._ptr(prob), self._ptr(mean), self._ptr(var),
-                self._ptr(z_last), ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_quantiles")
-        return EnsembleQuantiles(quant, prob, mean, var, z_last)
+                self._h, s.z.data_ptr(), self._ptr(s.p), s.B, s.M, s.steps, s.arr, s.nk, ctypes.byref(qs), _ref(spec), self._ptr(quant),
+                self._ptr(prob), self._ptr(s.mean), self._ptr(s.var), self._ptr(s.z_last), ws.data_ptr(), ws.numel(), self._stream(s.z)),
+                "lns_rollout_latent_ensemble_quantiles")
+        return EnsembleQuantiles(quant, prob, s.mean, s.var, s.z_last)
 
     # -- ensemble exceedance tables (include/lns.h "ensemble exceedance") ---------------------------------------------
     def ensemble_exceed(self, frames, y, thresholds, **norm):
@@ -978,24 +988,14 @@ class Engine:
         channel) or a per-channel sequence, in the units of the denormalised values; `norm` as in `rollout_eval` (none: the
         values as they are).  Returns the int32 table [B, n, n_thr, C, 2, M + 1]."""
         import torch
-        for t in (frames, y):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-                raise LnsError("ensemble_exceed takes fp32 HIP tensors")
-        if frames.dim() != 6 or y.dim() != 5 or y.device != frames.device:
-            raise LnsError("ensemble_exceed takes frames [n, B, M, C, H, W] and y [B, n, C, H, W] on one device")
-        n, B, M, C, H, W = (int(v) for v in frames.shape)
-        if tuple(y.shape) != (B, n, C, H, W):
-            raise LnsError("y must be %s for frames %s, got %s" % ((B, n, C, H, W), tuple(frames.shape), tuple(y.shape)))
-        frames, y = frames.contiguous(), y.contiguous()
+        frames, y, (n, B, M, C, H, W) = self._frames_and_truth("ensemble_exceed", frames, y, "y")
         xs = exceed_spec(C, thresholds)
         spec = eval_spec(C, **norm) if norm else None
         table = torch.empty((B, n, xs.n_thr, C, 2, M + 1), dtype=torch.int32, device=y.device)
         with torch.cuda.device(y.device):
-            rc = self._L.lns_op_ensemble_exceed(frames.data_ptr(), y.data_ptr(), n, B, M, C, H, W, ctypes.byref(xs),
-                                                ctypes.byref(spec) if spec is not None else None, table.data_ptr(),
-                                                self._stream(y))
-        if rc != 0:
-            raise LnsError("lns_op_ensemble_exceed failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+            rc = self._L.lns_op_ensemble_exceed(frames.data_ptr(), y.data_ptr(), n, B, M, C, H, W, ctypes.byref(xs), _ref(spec),
+                                                table.data_ptr(), self._stream(y))
+        _op_check(rc, "lns_op_ensemble_exceed")
         return table
 
     def rollout_latent_ensemble_exceed(self, z, y, steps, thresholds, param=None, keep_steps=None, return_mean=False,
@@ -1010,47 +1010,19 @@ class Engine:
         the workspace is rollout_latent_ensemble's.  The scores are functions of the table: metrics.brier_scores,
         reliability_curve, roc_curve, contingency_scores."""
         import torch
-        z = self._dev(z)
-        y = self._dev(y)
-        C, H, W = self.latent_shape()
-        c = self.cfg
-        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
-            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
-        B, M = int(z.shape[0]), int(z.shape[1])
-        if y.dim() != 5 or y.shape[0] != B or tuple(y.shape[2:]) != (c.in_channels, c.Ly, c.Lx) or y.dtype != torch.float32:
-            raise LnsError("ground truth must be fp32 [B, T, %d, %d, %d] with the latents' batch, got %s"
-                           % (c.in_channels, c.Ly, c.Lx, tuple(y.shape)))
-        if y.device != z.device:
-            raise LnsError("ground truth is on %s but the latents are on %s" % (y.device, z.device))
-        if return_var and not return_mean:
-            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
-        if return_var and M < 2:
-            raise LnsError("the variance needs at least 2 members, got M = %d" % M)
-        steps = int(y.shape[1]) if steps is None else int(steps)
-        if steps > y.shape[1]:
-            raise LnsError("%d steps do not fit the %d steps of the ground truth" % (steps, y.shape[1]))
-        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
-        arr = (ctypes.c_int * len(keep))(*keep)
-        nk = len(keep)
-        yk = y[:, keep].contiguous()
-        xs = exceed_spec(c.in_channels, thresholds)
-        spec = eval_spec(c.in_channels, **norm) if norm else None
-        table = torch.empty((B, nk, xs.n_thr, c.in_channels, 2, M + 1), dtype=torch.int32, device=z.device)
-        shape = (B, nk, c.in_channels, c.Ly, c.Lx)
-        mean = torch.empty(shape, dtype=torch.float32, device=z.device) if return_mean else None
-        var = torch.empty(shape, dtype=torch.float32, device=z.device) if return_var else None
-        z_last = torch.empty_like(z) if return_last else None
-        p = self._member_param(param, z, B, M)
-        with torch.cuda.device(z.device):
-            n = ctypes.c_size_t(0)
-            self._check(self._L.lns_rollout_ensemble_workspace_bytes(self._h, B, M, ctypes.byref(n)),
-                        "lns_rollout_ensemble_workspace_bytes")
-            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+        s = self._ensemble_setup(z, steps, keep_steps, return_mean, return_var, few="the variance needs at least 2 members, got M = %d", y=y)
+        C, dev = self.cfg.in_channels, s.z.device
+        xs = exceed_spec(C, thresholds)
+        spec = eval_spec(C, **norm) if norm else None
+        table = torch.empty((s.B, s.nk, xs.n_thr, C, 2, s.M + 1), dtype=torch.int32, device=dev)
+        self._ensemble_outputs(s, param, return_mean, return_var, return_last)
+        with torch.cuda.device(dev):
+            ws = self._ensemble_workspace(s.B, s.M, dev)
             self._check(self._L.lns_rollout_latent_ensemble_exceed(
-                self._h, z.data_ptr(), self._ptr(p), yk.data_ptr(), B, M, steps, arr, nk, ctypes.byref(xs),
-                ctypes.byref(spec) if spec is not None else None, table.data_ptr(), self._ptr(mean), self._ptr(var),
-                self._ptr(z_last), ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_exceed")
-        return EnsembleExceedance(table, mean, var, z_last)
+                self._h, s.z.data_ptr(), self._ptr(s.p), s.y.data_ptr(), s.B, s.M, s.steps, s.arr, s.nk, ctypes.byref(xs), _ref(spec),
+                table.data_ptr(), self._ptr(s.mean), self._ptr(s.var), self._ptr(s.z_last), ws.data_ptr(), ws.numel(), self._stream(s.z)),
+                "lns_rollout_latent_ensemble_exceed")
+        return EnsembleExceedance(table, s.mean, s.var, s.z_last)
 
     # -- ensemble transform Kalman filter (include/lns.h "ensemble transform Kalman filter") --------------------------
     @staticmethod
@@ -1076,15 +1048,7 @@ class Engine:
         observation-error variance per value, [C, H, W], [n, C, H, W] or [B, n, C, H, W] (0: not observed); `norm` as in
         `rollout_eval` (none: the values as they are).  Returns (S [B, n, M, M], g [B, n, M], stat [B, n, 3]) in float64."""
         import torch
-        for t in (frames, y_obs):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-                raise LnsError("ensemble_obs_gram takes fp32 HIP tensors")
-        if frames.dim() != 6 or y_obs.dim() != 5 or y_obs.device != frames.device:
-            raise LnsError("ensemble_obs_gram takes frames [n, B, M, C, H, W] and y_obs [B, n, C, H, W] on one device")
-        n, B, M, C, H, W = (int(v) for v in frames.shape)
-        if tuple(y_obs.shape) != (B, n, C, H, W):
-            raise LnsError("y_obs must be %s for frames %s, got %s" % ((B, n, C, H, W), tuple(frames.shape), tuple(y_obs.shape)))
-        frames, y_obs = frames.contiguous(), y_obs.contiguous()
+        frames, y_obs, (n, B, M, C, H, W) = self._frames_and_truth("ensemble_obs_gram", frames, y_obs, "y_obs")
         r, r_bs, r_ss = self._rinv(rinv, B, n, (C, H, W), frames.device)
         spec = eval_spec(C, **norm) if norm else None
         S = torch.empty((B, n, M, M), dtype=torch.float64, device=frames.device)
@@ -1092,10 +1056,8 @@ class Engine:
         stat = torch.empty((B, n, 3), dtype=torch.float64, device=frames.device)
         with torch.cuda.device(frames.device):
             rc = self._L.lns_op_ensemble_obs_gram(frames.data_ptr(), y_obs.data_ptr(), r.data_ptr(), r_bs, r_ss, n, B, M, C, H, W,
-                                                  ctypes.byref(spec) if spec is not None else None, S.data_ptr(), g.data_ptr(),
-                                                  stat.data_ptr(), self._stream(frames))
-        if rc != 0:
-            raise LnsError("lns_op_ensemble_obs_gram failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+                                                  _ref(spec), S.data_ptr(), g.data_ptr(), stat.data_ptr(), self._stream(frames))
+        _op_check(rc, "lns_op_ensemble_obs_gram")
         return S, g, stat
 
     def etkf_transform(self, S, g, rho=1.0):
@@ -1117,8 +1079,7 @@ class Engine:
         with torch.cuda.device(S.device):
             rc = self._L.lns_op_etkf_transform(S.data_ptr(), g.data_ptr(), B, n, M, float(rho), X.data_ptr(), wbar.data_ptr(),
                                                lam.data_ptr(), status.data_ptr(), self._stream(S))
-        if rc != 0:
-            raise LnsError("lns_op_etkf_transform failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        _op_check(rc, "lns_op_etkf_transform")
         return X, wbar, lam, status
 
     def ensemble_transform(self, z, X, out=None):
@@ -1138,9 +1099,18 @@ class Engine:
         n = z[0, 0].numel() if z.dim() > 2 else 1
         with torch.cuda.device(z.device):
             rc = self._L.lns_op_ensemble_transform(z.data_ptr(), X.contiguous().data_ptr(), B, M, n, out.data_ptr(), self._stream(z))
-        if rc != 0:
-            raise LnsError("lns_op_ensemble_transform failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        _op_check(rc, "lns_op_ensemble_transform")
         return out
+
+    def _analysis_outputs(self, s, param):
+        """What both analysis methods return of the global filter: za, pa (the transformed param: given per member only), X, wbar,
+        lam, stat, status."""
+        import torch
+        f64 = dict(dtype=torch.float64, device=s.z.device)
+        per_member = s.p is not None and torch.as_tensor(param).numel() == s.B * s.M and s.M > 1
+        return (torch.empty_like(s.z), torch.empty_like(s.p) if per_member else None, torch.empty((s.B, s.M, s.M), **f64),
+                torch.empty((s.B, s.M), **f64), torch.empty((s.B, s.M), **f64), torch.empty((s.B, s.nk, 3), **f64),
+                torch.empty((s.B,), dtype=torch.int32, device=s.z.device))
 
     def rollout_latent_ensemble_analysis(self, z, y_obs, rinv, steps, param=None, keep_steps=None, rho=1.0, return_mean=False,
                                          return_var=False, return_last=False, **norm):
@@ -1153,47 +1123,20 @@ class Engine:
         or per member -- given per member ([B, M]) it is updated by the same transform.  Returns EnsembleAnalysis.  The
         member fields are never stored and nothing is read back."""
         import torch
-        z = self._dev(z)
-        y_obs = self._dev(y_obs)
-        C, H, W = self.latent_shape()
-        c = self.cfg
-        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
-            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
-        B, M = int(z.shape[0]), int(z.shape[1])
-        steps = int(steps)
-        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
-        nk = len(keep)
-        tail = (c.in_channels, c.Ly, c.Lx)
-        if tuple(y_obs.shape) != (B, nk) + tail or y_obs.device != z.device:
-            raise LnsError("y_obs must be %s on the latents' device, got %s" % ((B, nk) + tail, tuple(y_obs.shape)))
-        if return_var and not return_mean:
-            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
-        arr = (ctypes.c_int * nk)(*keep)
-        y_obs = y_obs.contiguous()
-        r, r_bs, r_ss = self._rinv(rinv, B, nk, tail, z.device)
-        spec = eval_spec(c.in_channels, **norm) if norm else None
-        f64 = dict(dtype=torch.float64, device=z.device)
-        za = torch.empty_like(z)
-        p = self._member_param(param, z, B, M)
-        per_member = p is not None and torch.as_tensor(param).numel() == B * M and M > 1
-        pa = torch.empty_like(p) if per_member else None
-        X, wbar, lam = torch.empty((B, M, M), **f64), torch.empty((B, M), **f64), torch.empty((B, M), **f64)
-        stat = torch.empty((B, nk, 3), **f64)
-        status = torch.empty((B,), dtype=torch.int32, device=z.device)
-        mean = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_mean else None
-        var = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_var else None
-        z_last = torch.empty_like(z) if return_last else None
-        with torch.cuda.device(z.device):
-            n = ctypes.c_size_t(0)
-            self._check(self._L.lns_rollout_ensemble_analysis_workspace_bytes(self._h, B, M, nk, ctypes.byref(n)),
-                        "lns_rollout_ensemble_analysis_workspace_bytes")
-            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+        s = self._ensemble_setup(z, steps, keep_steps, return_mean, return_var, y_obs=y_obs)
+        dev = s.z.device
+        r, r_bs, r_ss = self._rinv(rinv, s.B, s.nk, s.tail, dev)
+        spec = eval_spec(self.cfg.in_channels, **norm) if norm else None
+        self._ensemble_outputs(s, param, return_mean, return_var, return_last)
+        za, pa, X, wbar, lam, stat, status = self._analysis_outputs(s, param)
+        with torch.cuda.device(dev):
+            ws = self._ensemble_workspace(s.B, s.M, dev, "lns_rollout_ensemble_analysis_workspace_bytes", s.nk)
             self._check(self._L.lns_rollout_latent_ensemble_analysis(
-                self._h, z.data_ptr(), self._ptr(p), y_obs.data_ptr(), r.data_ptr(), r_bs, r_ss, B, M, steps, arr, nk,
-                ctypes.byref(spec) if spec is not None else None, float(rho), za.data_ptr(), self._ptr(pa), X.data_ptr(),
-                wbar.data_ptr(), lam.data_ptr(), stat.data_ptr(), status.data_ptr(), self._ptr(mean), self._ptr(var),
-                self._ptr(z_last), ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_analysis")
-        return EnsembleAnalysis(za, pa, X, wbar, lam, stat, status, mean, var, z_last)
+                self._h, s.z.data_ptr(), self._ptr(s.p), s.y.data_ptr(), r.data_ptr(), r_bs, r_ss, s.B, s.M, s.steps, s.arr, s.nk,
+                _ref(spec), float(rho), za.data_ptr(), self._ptr(pa), X.data_ptr(), wbar.data_ptr(), lam.data_ptr(), stat.data_ptr(),
+                status.data_ptr(), self._ptr(s.mean), self._ptr(s.var), self._ptr(s.z_last), ws.data_ptr(), ws.numel(),
+                self._stream(s.z)), "lns_rollout_latent_ensemble_analysis")
+        return EnsembleAnalysis(za, pa, X, wbar, lam, stat, status, s.mean, s.var, s.z_last)
 
     # -- localised ensemble transform Kalman filter (include/lns.h "localised ensemble transform Kalman filter") ------
     def ensemble_patch_gram(self, frames, y_obs, rinv, grid, **norm):
@@ -1201,25 +1144,15 @@ class Engine:
         and `norm` as `ensemble_obs_gram`; grid = (h, w): the latent grid whose patches cut the frame.  Returns part
         [B, n, h*w, M*M + M + 3] float64: per patch the Gram [M, M] (symmetric), g [M] and stat [3]."""
         import torch
-        for t in (frames, y_obs):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-                raise LnsError("ensemble_patch_gram takes fp32 HIP tensors")
-        if frames.dim() != 6 or y_obs.dim() != 5 or y_obs.device != frames.device:
-            raise LnsError("ensemble_patch_gram takes frames [n, B, M, C, H, W] and y_obs [B, n, C, H, W] on one device")
-        n, B, M, C, H, W = (int(v) for v in frames.shape)
-        if tuple(y_obs.shape) != (B, n, C, H, W):
-            raise LnsError("y_obs must be %s for frames %s, got %s" % ((B, n, C, H, W), tuple(frames.shape), tuple(y_obs.shape)))
+        frames, y_obs, (n, B, M, C, H, W) = self._frames_and_truth("ensemble_patch_gram", frames, y_obs, "y_obs")
         h, w = (int(v) for v in grid)
-        frames, y_obs = frames.contiguous(), y_obs.contiguous()
         r, r_bs, r_ss = self._rinv(rinv, B, n, (C, H, W), frames.device)
         spec = eval_spec(C, **norm) if norm else None
         part = torch.empty((B, n, max(h * w, 0), M * M + M + 3), dtype=torch.float64, device=frames.device)
         with torch.cuda.device(frames.device):
             rc = self._L.lns_op_ensemble_patch_gram(frames.data_ptr(), y_obs.data_ptr(), r.data_ptr(), r_bs, r_ss, n, B, M, C, H, W, h, w,
-                                                    ctypes.byref(spec) if spec is not None else None, part.data_ptr(),
-                                                    self._stream(frames))
-        if rc != 0:
-            raise LnsError("lns_op_ensemble_patch_gram failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+                                                    _ref(spec), part.data_ptr(), self._stream(frames))
+        _op_check(rc, "lns_op_ensemble_patch_gram")
         return part
 
     def letkf_combine(self, part, grid, radius, boundary=("periodic", "periodic")):
@@ -1243,8 +1176,7 @@ class Engine:
         with torch.cuda.device(part.device):
             rc = self._L.lns_op_letkf_combine(part.data_ptr(), B, n, M, h, w, float(radius), bc_y, bc_x, S_l.data_ptr(), g_l.data_ptr(),
                                               S_g.data_ptr(), g_g.data_ptr(), stat.data_ptr(), self._stream(part))
-        if rc != 0:
-            raise LnsError("lns_op_letkf_combine failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        _op_check(rc, "lns_op_letkf_combine")
         return S_l, g_l, S_g, g_g, stat
 
     def ensemble_transform_local(self, z, X_local, out=None):
@@ -1264,8 +1196,7 @@ class Engine:
         with torch.cuda.device(z.device):
             rc = self._L.lns_op_ensemble_transform_local(z.data_ptr(), X_local.contiguous().data_ptr(), B, M, c, h, w, out.data_ptr(),
                                                          self._stream(z))
-        if rc != 0:
-            raise LnsError("lns_op_ensemble_transform_local failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        _op_check(rc, "lns_op_ensemble_transform_local")
         return out
 
     def rollout_latent_ensemble_analysis_local(self, z, y_obs, rinv, steps, loc_radius, boundary="auto", param=None, keep_steps=None,
@@ -1276,54 +1207,28 @@ class Engine:
         the workspace.  Everything else as rollout_latent_ensemble_analysis.  Returns LocalEnsembleAnalysis."""
         import torch
         from . import metrics
-        z = self._dev(z)
-        y_obs = self._dev(y_obs)
-        C, H, W = self.latent_shape()
-        c = self.cfg
-        if z.dim() != 5 or tuple(z.shape[2:]) != (C, H, W):
-            raise LnsError("ensemble latents must be [B, M, %d, %d, %d], got %s" % (C, H, W, tuple(z.shape)))
-        B, M = int(z.shape[0]), int(z.shape[1])
-        steps = int(steps)
-        keep = normalize_keep_steps(range(steps) if keep_steps is None else keep_steps, steps)
-        nk = len(keep)
-        tail = (c.in_channels, c.Ly, c.Lx)
-        if tuple(y_obs.shape) != (B, nk) + tail or y_obs.device != z.device:
-            raise LnsError("y_obs must be %s on the latents' device, got %s" % ((B, nk) + tail, tuple(y_obs.shape)))
-        if return_var and not return_mean:
-            raise LnsError("return_var needs return_mean (the variance comes from the kernel that writes the mean)")
-        bc_y, bc_x = metrics.flow_boundary(boundary, c)
-        arr = (ctypes.c_int * nk)(*keep)
-        y_obs = y_obs.contiguous()
-        r, r_bs, r_ss = self._rinv(rinv, B, nk, tail, z.device)
-        spec = eval_spec(c.in_channels, **norm) if norm else None
-        f64 = dict(dtype=torch.float64, device=z.device)
-        za = torch.empty_like(z)
-        p = self._member_param(param, z, B, M)
-        per_member = p is not None and torch.as_tensor(param).numel() == B * M and M > 1
-        pa = torch.empty_like(p) if per_member else None
-        hw = H * W
-        Xl = torch.empty((B, hw, M, M), **f64) if return_X else None
-        wl = torch.empty((B, hw, M), **f64) if return_X else None
-        ll = torch.empty((B, hw, M), **f64)
-        sl = torch.empty((B, hw), dtype=torch.int32, device=z.device)
-        X, wbar, lam = torch.empty((B, M, M), **f64), torch.empty((B, M), **f64), torch.empty((B, M), **f64)
-        stat = torch.empty((B, nk, 3), **f64)
-        status = torch.empty((B,), dtype=torch.int32, device=z.device)
-        mean = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_mean else None
-        var = torch.empty((B, nk) + tail, dtype=torch.float32, device=z.device) if return_var else None
-        z_last = torch.empty_like(z) if return_last else None
-        with torch.cuda.device(z.device):
-            n = ctypes.c_size_t(0)
-            self._check(self._L.lns_rollout_ensemble_analysis_local_workspace_bytes(self._h, B, M, nk, ctypes.byref(n)),
-                        "lns_rollout_ensemble_analysis_local_workspace_bytes")
-            ws = self._workspace(B * M, z.device, min_bytes=int(n.value))
+        s = self._ensemble_setup(z, steps, keep_steps, return_mean, return_var, y_obs=y_obs)
+        dev = s.z.device
+        bc_y, bc_x = metrics.flow_boundary(boundary, self.cfg)
+        r, r_bs, r_ss = self._rinv(rinv, s.B, s.nk, s.tail, dev)
+        spec = eval_spec(self.cfg.in_channels, **norm) if norm else None
+        self._ensemble_outputs(s, param, return_mean, return_var, return_last)
+        za, pa, X, wbar, lam, stat, status = self._analysis_outputs(s, param)
+        f64 = dict(dtype=torch.float64, device=dev)
+        hw = s.z.shape[3] * s.z.shape[4]
+        Xl = torch.empty((s.B, hw, s.M, s.M), **f64) if return_X else None
+        wl = torch.empty((s.B, hw, s.M), **f64) if return_X else None
+        ll = torch.empty((s.B, hw, s.M), **f64)
+        sl = torch.empty((s.B, hw), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            ws = self._ensemble_workspace(s.B, s.M, dev, "lns_rollout_ensemble_analysis_local_workspace_bytes", s.nk)
             self._check(self._L.lns_rollout_latent_ensemble_analysis_local(
-                self._h, z.data_ptr(), self._ptr(p), y_obs.data_ptr(), r.data_ptr(), r_bs, r_ss, B, M, steps, arr, nk,
-                ctypes.byref(spec) if spec is not None else None, float(rho), float(loc_radius), bc_y, bc_x, za.data_ptr(),
-                self._ptr(Xl), self._ptr(wl), ll.data_ptr(), sl.data_ptr(), self._ptr(pa), X.data_ptr(), wbar.data_ptr(),
-                lam.data_ptr(), stat.data_ptr(), status.data_ptr(), self._ptr(mean), self._ptr(var), self._ptr(z_last),
-                ws.data_ptr(), ws.numel(), self._stream(z)), "lns_rollout_latent_ensemble_analysis_local")
-        return LocalEnsembleAnalysis(za, pa, Xl, wl, ll, sl, X, wbar, lam, stat, status, mean, var, z_last)
+                self._h, s.z.data_ptr(), self._ptr(s.p), s.y.data_ptr(), r.data_ptr(), r_bs, r_ss, s.B, s.M, s.steps, s.arr, s.nk,
+                _ref(spec), float(rho), float(loc_radius), bc_y, bc_x, za.data_ptr(), self._ptr(Xl), self._ptr(wl), ll.data_ptr(),
+                sl.data_ptr(), self._ptr(pa), X.data_ptr(), wbar.data_ptr(), lam.data_ptr(), stat.data_ptr(), status.data_ptr(),
+                self._ptr(s.mean), self._ptr(s.var), self._ptr(s.z_last), ws.data_ptr(), ws.numel(), self._stream(s.z)),
+                "lns_rollout_latent_ensemble_analysis_local")
+        return LocalEnsembleAnalysis(za, pa, Xl, wl, ll, sl, X, wbar, lam, stat, status, s.mean, s.var, s.z_last)
 
     # -- streaming validation rollout (include/lns.h "streaming validation rollout") --------------------------------
     def _eval_common(self, first, y, steps, t0, keep_steps, norm):
@@ -1509,7 +1414,7 @@ class Engine:
         """A `select` of _scored_call: the statistics of `stats_steps`, their histograms and (optional) spectra."""
         sel, arr, stats, hs, counts = self._stats_alloc(stats_steps, hist, T, B, device)
         sargs, stail, _ = self._spectrum_select(spectrum_steps, T, B, device, optional=True, basis=basis)
-        hp = ctypes.byref(hs) if hs is not None else None
+        hp = _ref(hs)
         return sargs + (arr, len(sel), hp, stats.data_ptr(), self._ptr(counts)), (stats, counts, sel) + stail, None
 
     def rollout_eval_stats(self, x, y, steps=None, param=None, keep_steps=(), stats_steps=None, hist=None, spectrum_steps=(),
@@ -1910,8 +1815,7 @@ class Engine:
                 rc = self._L.lns_op_conv_wgrad(dy.data_ptr(), x.data_ptr(), B, Cin, Cout, H, W, int(ksize), int(dilation), int(pad_y),
                                                int(pad_x), int(form), int(bool(accumulate)), dw.data_ptr(), scratch.data_ptr(),
                                                int(n.value), self._stream(dy))
-        if rc != 0:
-            raise LnsError("lns_op_conv_wgrad failed (%d): %s" % (rc, self._L.lns_create_error().decode()))
+        _op_check(rc, "lns_op_conv_wgrad")
         return dw
 
     def train_step_workspace_bytes(self, B, h, w, T):
@@ -1951,8 +1855,8 @@ class Engine:
                                                pc.data_ptr() if pc is not None else None, B, h, w, T, float(beta), arr(grads),
                                                arr(exp_avg) if exp_avg is not None else None,
                                                arr(exp_avg_sq) if exp_avg_sq is not None else None,
-                                               ctypes.byref(spec) if spec is not None else None, loss_out.data_ptr(),
-                                               workspace.data_ptr(), workspace.numel(), self._stream(z_in)), "lns_train_step")
+                                               _ref(spec), loss_out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                               self._stream(z_in)), "lns_train_step")
         return loss_out
 
     def train_step_clip_workspace_bytes(self, B, h, w, T):

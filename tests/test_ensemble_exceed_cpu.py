@@ -121,6 +121,7 @@ _REFUSALS = [
     (dict(mean=None), _VM),
     (dict(norm="short"), _NORM),
     (dict(eng="wide"), _CH), (dict(eng="wide", norm=None), _CH),
+    (dict(eng="wide", norm="per_channel"), _CH),                   # (this form has no per-channel norm check of its own)
     (dict(k=_ints(0, 4, 3)), _KEEP_2_3), (dict(k=None), (-1, "keep_steps is null")),
     (dict(nk=0), _N_KEEP_1), (dict(nk=-1), _N_KEEP_1),
     (dict(B=512, M=128), _BATCH),

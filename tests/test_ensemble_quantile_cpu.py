@@ -2,6 +2,7 @@
 exported and bound, refuse bad arguments before any device work in the documented order, the kernel uses no scratch memory
 -- and the fp32 statement the GPU tests hold it to (tests/ensemble_quantile_reference.py) has the properties a quantile /
 exceedance reference must have, agrees with numpy.quantile in float64, and notices the mistakes an implementation can make."""
+import copy
 import ctypes
 import os
 import re
@@ -72,9 +73,12 @@ def test_quantile_symbols_are_declared_exported_and_bound():
 def _engines():
     from lns_amd import _lib, config, engine
     mini = config.preset("ns2d_mini")
+    wide = copy.copy(mini)
+    wide.in_channels = 9
     return {"full": engine.Engine(engine.make_config(mini, ae_prefix="vq_ae.", prop_prefix="propagator.")),
             "cond": engine.Engine(engine.make_config(config.preset("twophase_cond"), ae_prefix="ae.", prop_prefix="propagator.")),
-            "noprop": engine.Engine(engine.make_config(mini, prop_kind=_lib.LNS_PROP_NONE, ae_prefix="vq_ae."))}
+            "noprop": engine.Engine(engine.make_config(mini, prop_kind=_lib.LNS_PROP_NONE, ae_prefix="vq_ae.")),
+            "wide": engine.Engine(engine.make_config(wide, ae_prefix="vq_ae.", prop_prefix="propagator."))}
 
 
 _PASSED = (-3, "lns_finalize_weights must be called first")        # every refusal passed: no weights on this machine
@@ -90,6 +94,8 @@ _QO, _PO = (-1, "quant_out is null but n_q > 0"), (-1, "prob_out is null but n_t
 _MR = (-1, "ensemble quantiles need M in 1 .. 128")
 _VM, _V2 = (-1, "var_out needs mean_out"), (-1, "var_out needs M >= 2")
 _NORM = (-1, "norm: the size field is not sizeof(lns_eval_spec)")
+_NPC = (-1, "norm: the per-channel form needs in_channels <= 8")
+_CH = (-1, "thresholds need in_channels <= 8")
 # (arguments of the call that differ from a valid one, expected (return code, message))
 _REFUSALS = [
     (dict(), _PASSED), (dict(mean=None, var=None), _PASSED), (dict(var=None), _PASSED), (dict(last=_P), _PASSED),
@@ -105,6 +111,10 @@ _REFUSALS = [
     (dict(M=1), _V2), (dict(M=129), _MR), (dict(M=129, mean=None, var=None), _MR),
     (dict(mean=None), _VM),
     (dict(norm="short"), _NORM),
+    # nine channels: the per-channel norm answers before the thresholds; quantiles alone with a scalar norm or none pass
+    (dict(eng="wide", norm="per_channel"), _NPC), (dict(eng="wide", norm="per_channel", qs="only_q", prob=None), _NPC),
+    (dict(eng="wide"), _CH), (dict(eng="wide", norm=None), _CH), (dict(eng="wide", qs="only_thr", quant=None), _CH),
+    (dict(eng="wide", qs="only_q", prob=None), _PASSED), (dict(eng="wide", norm="short"), _NORM),
     (dict(k=_ints(0, 4, 3)), _KEEP_2_3), (dict(k=None), (-1, "keep_steps is null")),
     (dict(nk=0), _N_KEEP_1), (dict(nk=-1), _N_KEEP_1),
     (dict(B=512, M=128), _BATCH),

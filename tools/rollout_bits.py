@@ -5,7 +5,8 @@ rollout_latent, rollout_latent with keep_steps, rollout_eval, rollout_latent_eva
 rollout_latent_ensemble with M = 3 members, rollout_latent_ensemble_eval, rollout_latent_ensemble_quantiles (three quantiles,
 one threshold, mean / var / z_last as well), rollout_latent_ensemble_exceed (the same threshold against y; mean / var / z_last
 as well) and rollout_latent_ensemble_analysis (every 4th pixel of channel 0 of y observed at the kept steps, rho = 1.1; z, X, wbar,
-lam, stat, status, mean / var / z_last) on the same members where the library has them, and
+lam, stat, status, mean / var / z_last) and rollout_latent_ensemble_analysis_local (the same observations, radius 2 latent pixels,
+return_X; every tensor it returns) on the same members where the library has them, and
 the six newer scored calls -- rollout_eval_spectrum / _stats / _maps from x and their rollout_latent_ forms in two chunks, 4 + 3:
 spectra at steps [0, 3, 6], statistics at [1, 2, 6] with an 8-bin histogram, maps from step 1 every 2, the _maps forms with all
 three selections together; every tensor they return is hashed, the chunks' per-step tensors concatenated) under
@@ -53,6 +54,7 @@ CHUNKS = ((0, 4, [1]), (4, 3, [0, 2]))              # (t0, steps, keep_steps of 
 NORM = dict(mean=0.37, std=1.9)
 MEMBERS, NOISE = 3, 0.05                            # rollout_latent_ensemble: z0 + NOISE * filler.normal per member
 QUANTILES, THRESHOLDS = (0.05, 0.5, 0.95), (0.5,)      # rollout_latent_ensemble_quantiles, rollout_latent_ensemble_exceed
+LOC_RADIUS = 2.0                                    # rollout_latent_ensemble_analysis_local
 SPECTRUM_STEPS, STATS_STEPS, HIST, MAP_STEPS = [0, 3, 6], [1, 2, 6], (8, -4.0, 4.0), (1, 2)
 DECODE_GROUPS = (None, 1, 2, 0)                     # None: never set (it comes first); 0: automatic, here one group of all T steps
 
@@ -171,6 +173,11 @@ def entries(eng, x, y, p):
                                                      return_mean=True, return_var=True, return_last=True, **NORM)
             yield "rollout_latent_ensemble_analysis", dict(z=r.z, X=r.X, wbar=r.wbar, lam=r.lam, stat=r.stat, status=r.status,
                                                            mean=r.mean, var=r.var, z_last=r.z_last)
+            if eng._L.lns_build_has(b"ensemble_letkf") == 1:
+                r = eng.rollout_latent_ensemble_analysis_local(ze, y[:, KEEP].contiguous(), rinv, T, LOC_RADIUS, param=p, keep_steps=KEEP,
+                                                               rho=1.1, return_mean=True, return_var=True, return_last=True,
+                                                               return_X=True, **NORM)
+                yield "rollout_latent_ensemble_analysis_local", scored(r)
     for name, sel in (("spectrum", dict(spectrum_steps=SPECTRUM_STEPS)), ("stats", dict(stats_steps=STATS_STEPS, hist=HIST)),
                       ("maps", dict(map_steps=MAP_STEPS, stats_steps=STATS_STEPS, hist=HIST, spectrum_steps=SPECTRUM_STEPS))):
         if eng._L.lns_build_has(b"eval_" + name.encode()) == 1:
