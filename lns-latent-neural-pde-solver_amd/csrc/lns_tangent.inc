@@ -1,6 +1,6 @@
 // ---------------------------------------------------------------------------------------------------------------------
 // Tangent-linear rollout of the latent propagator (include/lns.h "tangent-linear rollout"; included by lns_engine.cpp after
-// lns_train.inc, whose plans, layout and run_tconv it uses).
+// lns_train.inc, whose plans, layout, tape view and run_tconv it uses).
 //
 // lns_train_tangent carries K perturbations of every sample's initial latent forward along the trajectory a preceding
 // lns_train_forward computed: v <- J_t v for t = t0 .. t0 + nsteps - 1, J_t the Jacobian of propagator step t with respect
@@ -96,42 +96,35 @@ int lns_train_tangent(lns_engine* e, const float* const* params, int B, int H, i
         return launch_gn_train_jvp(a, s);
     };
     for (int t = t0; t < t0 + nsteps; ++t) {
-        const float* tp = W + L.tape0 + (size_t)t * L.tape_step;
+        const ConstTapeStep tape(L, W, t);
         float *dx = buf[0], *f1 = buf[1], *f2 = buf[2], *f3 = buf[3];         // dx: tangent of the current block's input
         if ((rc = run_tconv(e, p.in_proj, t == t0 ? v : zt, W + L.pk_in, nullptr, dx, nullptr, s))) return rc;
-        const float* x = tp + L.off_x0;
         for (int i = 0; i < p.nb; ++i) {
             const PropParams::Blk& b = pp.blk[i];
-            const float* tb = tp + L.off_blk + (size_t)i * L.blk_stride;
-            const size_t ts = L.blk_stride / TB_COUNT;
-            const float* st = tp + L.off_stats + (size_t)i * L.st_blk;
-            HIPCHK(e, gn(1, x, st, params[b.g1], dx, nullptr, f1));                                             // d n1
-            if ((rc = run_tconv(e, p.c_d1, f1, W + L.pk_c1[i], nullptr, f2, nullptr, s))) return rc;           // d u1
-            HIPCHK(e, launch_gelu_jvp(f2, tb + TB_U1 * ts, f2, R, K, ns, s));                                   // d a1
+            HIPCHK(e, gn(1, tape.block_in(i), tape.stats(i, 0), params[b.g1], dx, nullptr, f1));                // d n1
+            if ((rc = run_tconv(e, p.c_d1, f1, W + L.pk(i, BC_C1), nullptr, f2, nullptr, s))) return rc;        // d u1
+            HIPCHK(e, launch_gelu_jvp(f2, tape.t(i, TB_U1), f2, R, K, ns, s));                                  // d a1
+            if ((rc = run_tconv(e, p.c_dd, f2, W + L.pk(i, BC_C3), nullptr, f1, nullptr, s))) return rc;        // d u2 / d h (emb: none)
             float* dx1;                                                                                         // tangent of x1
             if (!p.cond) {
-                if ((rc = run_tconv(e, p.c_dd, f2, W + L.pk_c3[i], nullptr, f1, nullptr, s))) return rc;       // d u2
-                HIPCHK(e, launch_gelu_jvp(f1, tb + TB_U2 * ts, f1, R, K, ns, s));                               // d a2
-                if ((rc = run_tconv(e, p.c_d1, f1, W + L.pk_c5[i], nullptr, f2, dx, s))) return rc;            // d x1 = d x + conv.5
+                HIPCHK(e, launch_gelu_jvp(f1, tape.t(i, TB_U2), f1, R, K, ns, s));                              // d a2
+                if ((rc = run_tconv(e, p.c_d1, f1, W + L.pk(i, BC_C5), nullptr, f2, dx, s))) return rc;         // d x1 = d x + conv.5
                 dx1 = f2;
-                HIPCHK(e, gn(1, tb + TB_X1 * ts, st + L.st_blk / 3, params[b.g2], dx1, nullptr, f1));           // d n2
+                HIPCHK(e, gn(1, tape.t(i, TB_X1), tape.stats(i, 1), params[b.g2], dx1, nullptr, f1));           // d n2
             } else {
-                if ((rc = run_tconv(e, p.c_dd, f2, W + L.pk_c3[i], nullptr, f1, nullptr, s))) return rc;       // d h (emb: no tangent)
-                HIPCHK(e, gn(1, tb + TB_U2 * ts, st + 2 * (L.st_blk / 3), params[b.cg], f1, nullptr, f2));      // d GN(h)
-                HIPCHK(e, launch_gelu_jvp(f2, tb + TB_NC * ts, f2, R, K, ns, s));                               // d a2
-                if ((rc = run_tconv(e, p.c_d1, f2, W + L.pk_c5[i], nullptr, f3, dx, s))) return rc;            // d x1
+                HIPCHK(e, gn(1, tape.t(i, TB_U2), tape.stats(i, 2), params[b.cg], f1, nullptr, f2));            // d GN(h)
+                HIPCHK(e, launch_gelu_jvp(f2, tape.t(i, TB_NC), f2, R, K, ns, s));                              // d a2
+                if ((rc = run_tconv(e, p.c_d1, f2, W + L.pk(i, BC_C5), nullptr, f3, dx, s))) return rc;         // d x1
                 dx1 = f3;
-                HIPCHK(e, launch_chan_scale_rows(dx1, vv.blk(L, W, i, TV_M, B, D), f2, R, K, D, HW, s));        // d xm
-                HIPCHK(e, gn(1, tb + TB_XM * ts, st + L.st_blk / 3, params[b.g2], f2, nullptr, f1));            // d n2
+                HIPCHK(e, launch_chan_scale_rows(dx1, vv.blk(i, TV_M), f2, R, K, D, HW, s));                    // d xm
+                HIPCHK(e, gn(1, tape.t(i, TB_XM), tape.stats(i, 1), params[b.g2], f2, nullptr, f1));            // d n2
             }
             float* g = dx1 == f2 ? f3 : f2;                                   // free: neither d x1 nor d n2
-            if ((rc = run_tconv(e, p.c_1, f1, W + L.pk_f1[i], nullptr, g, nullptr, s))) return rc;             // d v
-            HIPCHK(e, launch_gelu_jvp(g, tb + TB_V * ts, g, R, K, ns, s));                                      // d g
-            if ((rc = run_tconv(e, p.c_1, g, W + L.pk_f3[i], nullptr, dx, dx1, s))) return rc;                 // d x2 = d x1 + ffn.3
-            x = tb + TB_X2 * ts;
+            if ((rc = run_tconv(e, p.c_1, f1, W + L.pk(i, BC_F1), nullptr, g, nullptr, s))) return rc;          // d v
+            HIPCHK(e, launch_gelu_jvp(g, tape.t(i, TB_V), g, R, K, ns, s));                                     // d g
+            if ((rc = run_tconv(e, p.c_1, g, W + L.pk(i, BC_F3), nullptr, dx, dx1, s))) return rc;              // d x2 = d x1 + ffn.3
         }
-        const float* stO = tp + L.off_stats + (size_t)p.nb * L.st_blk;
-        HIPCHK(e, gn(32, x, stO, params[pp.out_g], dx, nullptr, f1));
+        HIPCHK(e, gn(32, tape.last_x(), tape.stats_out(), params[pp.out_g], dx, nullptr, f1));
         if ((rc = run_tconv(e, p.out_proj, f1, W + L.pk_out, nullptr, zt, nullptr, s))) return rc;
         if (jv_out)                                  // jv_out is [B][K][nsteps][c][HW]: a row's steps are nsteps*c*HW apart
             HIPCHK(e, launch_add_rows(zt, nz, nullptr, 0, jv_out + (size_t)(t - t0) * nz, (long)nsteps * nz, R, nz, s));

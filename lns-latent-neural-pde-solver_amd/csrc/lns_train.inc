@@ -26,6 +26,9 @@
 
 namespace {
 
+size_t round64(size_t floats) { return (floats + 63) / 64 * 64; }
+size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
 struct TConv {                       // one convolution geometry with its gather maps on the device
     int Cin = 0, Cout = 0, k = 1, dil = 1, kc_log2 = 3, Cin_pad = 0, Cout_pad = 0, variant = 0;
     int wg_S = 1;                    // slices of the batch-parallel weight gradient (wgrad_split_slices of the plan's shape)
@@ -212,11 +215,25 @@ int prop_params(lns_engine* e, const PropParams** out) {
     return LNS_OK;
 }
 
+// The five convolutions of a DilatedResidualBlock (plain or conditional): geometry in the plan, weight and bias (null: none) in
+// PropParams::Blk.  in_proj and out_proj (Cin != Cout: the transposed convolution has a geometry of its own) stay outside.
+enum BlkConv { BC_C1 = 0, BC_C3, BC_C5, BC_F1, BC_F3, BC_COUNT };      // conv.1, conv.3, conv.5 / cond_conv1.2, ffn.1, ffn.3
+struct BlkConvRow { TConv TrainPlan::*geom; int PropParams::Blk::*w; int PropParams::Blk::*b; };
+const BlkConvRow kBlkConv[BC_COUNT] = {
+    {&TrainPlan::c_d1, &PropParams::Blk::c1w, &PropParams::Blk::c1b},
+    {&TrainPlan::c_dd, &PropParams::Blk::c3w, &PropParams::Blk::c3b},
+    {&TrainPlan::c_d1, &PropParams::Blk::c5w, &PropParams::Blk::c5b},
+    {&TrainPlan::c_1, &PropParams::Blk::f1w, nullptr},
+    {&TrainPlan::c_1, &PropParams::Blk::f3w, nullptr},
+};
+
 // workspace layout (floats): weight packs | tape[T] | backward scratch [| partial sums of the batch-parallel weight gradient]
 struct TrainLayout {
+    int nb = 0;
     size_t n = 0, nl = 0;                          // B*D*HW, B*c*HW
     size_t pk_in = 0, pk_inT = 0, pk_out = 0, pk_outT = 0;
-    std::vector<size_t> pk_c1, pk_c3, pk_c5, pk_f1, pk_f3, pk_c1T, pk_c3T, pk_c5T, pk_f1T, pk_f3T;
+    std::vector<size_t> pk_blk;                    // [block][BlkConv][forward | flipped]
+    size_t pk(int i, int conv, bool flipped = false) const { return pk_blk[((size_t)i * BC_COUNT + conv) * 2 + (flipped ? 1 : 0)]; }
     size_t tape0 = 0, tape_step = 0, st_blk = 0;   // per step: x0 | blocks | nO | stats
     size_t scratch = 0, total = 0;
     size_t wg_part = 0, wg_floats = 0;             // option "train_wgrad" = 1: [S][Cout][Cin][k*k] of the plan's largest launch
@@ -230,37 +247,33 @@ enum { TV_EMB = 0, TV_VG, TV_C1, TV_C1G, TV_M, TV_DEMB, TV_DM, TV_COUNT };     /
 
 void train_layout(const TrainPlan& p, int T, TrainLayout& L, int wgrad_form) {
     const size_t HW = (size_t)p.H * p.W;
-    L.n = (size_t)p.B * p.D * HW; L.nl = (size_t)p.B * p.c * HW;
+    L.nb = p.nb; L.n = (size_t)p.B * p.D * HW; L.nl = (size_t)p.B * p.c * HW;
     size_t off = 0;
-    auto take = [&](size_t floats) { const size_t o = off; off += (floats + 63) / 64 * 64; return o; };
+    auto take = [&](size_t floats) { const size_t o = off; off += round64(floats); return o; };
     L.pk_in = take(p.in_proj.pack_floats()); L.pk_inT = take(p.in_proj_T.pack_floats());
     L.pk_out = take(p.out_proj.pack_floats()); L.pk_outT = take(p.out_proj_T.pack_floats());
-    for (int i = 0; i < p.nb; ++i) {
-        L.pk_c1.push_back(take(p.c_d1.pack_floats())); L.pk_c1T.push_back(take(p.c_d1.pack_floats()));
-        L.pk_c3.push_back(take(p.c_dd.pack_floats())); L.pk_c3T.push_back(take(p.c_dd.pack_floats()));
-        L.pk_c5.push_back(take(p.c_d1.pack_floats())); L.pk_c5T.push_back(take(p.c_d1.pack_floats()));
-        L.pk_f1.push_back(take(p.c_1.pack_floats())); L.pk_f1T.push_back(take(p.c_1.pack_floats()));
-        L.pk_f3.push_back(take(p.c_1.pack_floats())); L.pk_f3T.push_back(take(p.c_1.pack_floats()));
-    }
+    for (int i = 0; i < p.nb; ++i)
+        for (const BlkConvRow& r : kBlkConv)
+            for (int flipped = 0; flipped < 2; ++flipped) L.pk_blk.push_back(take((p.*r.geom).pack_floats()));
     // one step of tape
     size_t so = 0;
-    auto stake = [&](size_t floats) { const size_t o = so; so += (floats + 63) / 64 * 64; return o; };
+    auto stake = [&](size_t floats) { const size_t o = so; so += round64(floats); return o; };
     L.off_x0 = stake(L.n);
-    L.off_blk = so; L.blk_stride = TB_COUNT * ((L.n + 63) / 64 * 64);
+    L.off_blk = so; L.blk_stride = TB_COUNT * round64(L.n);
     so += (size_t)p.nb * L.blk_stride;
     L.off_nO = stake(L.n);
-    L.off_stats = so;                                            // per block 2 x [B][1][2], then [B][32][2]
-    L.st_blk = 3 * (((size_t)p.B * 2 + 63) / 64 * 64);
-    so += (size_t)p.nb * L.st_blk + ((size_t)p.B * 32 * 2 + 63) / 64 * 64;
+    L.off_stats = so;                                            // per block 3 x [B][1][2], then [B][32][2]
+    L.st_blk = 3 * round64((size_t)p.B * 2);
+    so += (size_t)p.nb * L.st_blk + round64((size_t)p.B * 32 * 2);
     L.tape_step = so;
     L.tape0 = off; off += (size_t)T * L.tape_step;
     L.scratch = off;
-    off += 4 * ((L.n + 63) / 64 * 64) + 2 * ((L.nl + 63) / 64 * 64) + ((size_t)p.B * p.D * 2 + 63) / 64 * 64;
+    off += 4 * round64(L.n) + 2 * round64(L.nl) + round64((size_t)p.B * p.D * 2);
     if (p.cond) {
-        const size_t vd = ((size_t)p.B * p.D + 63) / 64 * 64, ve = ((size_t)p.B * std::max(p.E, p.D) + 63) / 64 * 64;
+        const size_t vd = round64((size_t)p.B * p.D), ve = round64((size_t)p.B * std::max(p.E, p.D));
         L.vec0 = off; L.vec_blk = TV_COUNT * vd; off += (size_t)p.nb * L.vec_blk;
         L.vec_glob = off; off += 8 * ve;                          // fe, l0, l0g, ce, d_ce, 3 scratch vectors
-        L.vstat = off; off += (size_t)p.nb * (((size_t)p.B * 2 + 63) / 64 * 64);
+        L.vstat = off; off += (size_t)p.nb * round64((size_t)p.B * 2);
     }
     if (wgrad_form == 1) {                                           // appended: everything above keeps its offset
         for (const TConv* t : {&p.in_proj, &p.c_d1, &p.c_dd, &p.c_1, &p.out_proj})
@@ -269,6 +282,24 @@ void train_layout(const TrainPlan& p, int T, TrainLayout& L, int wgrad_form) {
     }
     L.total = off;
 }
+
+// One step of tape by name (the layout's offsets are used here and nowhere else).  F = float: the forward, which writes the
+// tape; const float: the backward and the tangent walk, which read it.
+template <typename F>
+struct TapeStepT {
+    const TrainLayout& L; F* tp;
+    TapeStepT(const TrainLayout& L_, F* W, int t) : L(L_), tp(W + L_.tape0 + (size_t)t * L_.tape_step) {}
+    F* x0() const { return tp + L.off_x0; }                                                  // in_proj's output
+    F* t(int i, int which) const { return tp + L.off_blk + (size_t)i * L.blk_stride + (size_t)which * (L.blk_stride / TB_COUNT); }
+    F* block_in(int i) const { return i == 0 ? x0() : t(i - 1, TB_X2); }
+    // (mean, rstd) of block i's GroupNorms -- slot 0: conv.0 / conv1.0, 1: ffn.0, 2: cond_conv1.0
+    F* stats(int i, int slot) const { return tp + L.off_stats + (size_t)i * L.st_blk + (size_t)slot * (L.st_blk / 3); }
+    F* nO() const { return tp + L.off_nO; }                                                  // out_proj's GroupNorm output
+    F* stats_out() const { return stats(L.nb, 0); }
+    F* last_x() const { return block_in(L.nb); }                                             // the last block's output
+};
+using TapeStep = TapeStepT<float>;
+using ConstTapeStep = TapeStepT<const float>;
 
 int run_tconv(lns_engine* e, const TConv& t, const float* x, const float* wpack, const float* bias, float* y, const float* res,
               hipStream_t s) {
@@ -293,29 +324,22 @@ int run_wgrad(lns_engine* e, const TConv& t, const TrainPlan& p, const float* dy
 
 int pack_all(lns_engine* e, const TrainPlan& p, const TrainLayout& L, const PropParams& pp, const float* const* P, float* ws, bool with_T,
              hipStream_t s) {
-    auto fwd = [&](const TConv& t, int widx, size_t off) -> hipError_t {
-        return launch_pack_conv_w(P[widx], ws + off, t.Cout, t.Cin, t.k, t.Cin_pad, t.Cout_pad, 0, s);
+    // flipped: the pack of the transposed convolution, whose geometry object tT (Cin <-> Cout; a D -> D conv's own) gives the pads
+    auto pack = [&](const TConv& t, const TConv& tT, int widx, size_t off, int flipped) -> hipError_t {
+        const TConv& pads = flipped ? tT : t;
+        return launch_pack_conv_w(P[widx], ws + off, t.Cout, t.Cin, t.k, pads.Cin_pad, pads.Cout_pad, flipped, s);
     };
-    // the transposed convolution's geometry object tT (Cin <-> Cout) gives the pads of the flipped pack
-    auto bwd = [&](const TConv& t, const TConv& tT, int widx, size_t off) -> hipError_t {
-        return launch_pack_conv_w(P[widx], ws + off, t.Cout, t.Cin, t.k, tT.Cin_pad, tT.Cout_pad, 1, s);
-    };
-    HIPCHK(e, fwd(p.in_proj, pp.in_w, L.pk_in));
-    HIPCHK(e, fwd(p.out_proj, pp.out_w, L.pk_out));
-    if (with_T) {
-        HIPCHK(e, bwd(p.in_proj, p.in_proj_T, pp.in_w, L.pk_inT));
-        HIPCHK(e, bwd(p.out_proj, p.out_proj_T, pp.out_w, L.pk_outT));
+    const int sides = with_T ? 2 : 1;                                         // the forward packs, then the flipped ones
+    for (int flipped = 0; flipped < sides; ++flipped) {
+        HIPCHK(e, pack(p.in_proj, p.in_proj_T, pp.in_w, flipped ? L.pk_inT : L.pk_in, flipped));
+        HIPCHK(e, pack(p.out_proj, p.out_proj_T, pp.out_w, flipped ? L.pk_outT : L.pk_out, flipped));
     }
-    for (int i = 0; i < p.nb; ++i) {
-        const PropParams::Blk& b = pp.blk[i];
-        HIPCHK(e, fwd(p.c_d1, b.c1w, L.pk_c1[i])); HIPCHK(e, fwd(p.c_dd, b.c3w, L.pk_c3[i])); HIPCHK(e, fwd(p.c_d1, b.c5w, L.pk_c5[i]));
-        HIPCHK(e, fwd(p.c_1, b.f1w, L.pk_f1[i])); HIPCHK(e, fwd(p.c_1, b.f3w, L.pk_f3[i]));
-        if (with_T) {
-            HIPCHK(e, bwd(p.c_d1, p.c_d1, b.c1w, L.pk_c1T[i])); HIPCHK(e, bwd(p.c_dd, p.c_dd, b.c3w, L.pk_c3T[i]));
-            HIPCHK(e, bwd(p.c_d1, p.c_d1, b.c5w, L.pk_c5T[i])); HIPCHK(e, bwd(p.c_1, p.c_1, b.f1w, L.pk_f1T[i]));
-            HIPCHK(e, bwd(p.c_1, p.c_1, b.f3w, L.pk_f3T[i]));
-        }
-    }
+    for (int i = 0; i < p.nb; ++i)
+        for (int flipped = 0; flipped < sides; ++flipped)
+            for (int c = 0; c < BC_COUNT; ++c) {
+                const TConv& t = p.*kBlkConv[c].geom;
+                HIPCHK(e, pack(t, t, pp.blk[i].*kBlkConv[c].w, L.pk(i, c, flipped), flipped));
+            }
     return LNS_OK;
 }
 
@@ -331,6 +355,15 @@ GnTrainArgs gn_args(const TrainPlan& p, int groups, float eps, const float* x, f
     a.x = x; a.y = y; a.stats = stats; a.gamma = gamma; a.beta = beta;
     a.B = p.B; a.C = p.D; a.HW = p.H * p.W; a.groups = groups; a.eps = eps;
     return a;
+}
+
+// The tail of a size query: the plan itself (device maps) is built now when a device is there -- the caller's current one, as
+// torch sets it (no tensor in such a call) -- so that the first run call does not; the size does not need one.
+int prebuild_train_plan(lns_engine* e, int B, int H, int W) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) { (void)hipGetLastError(); return LNS_OK; }
+    TrainPlan* p;
+    return get_train_plan(e, device, B, H, W, &p);
 }
 
 }  // namespace
@@ -355,26 +388,21 @@ int lns_train_workspace_bytes(lns_engine* e, int B, int H, int W, int T, size_t*
     TrainLayout L;
     train_layout(dims, T, L, e->opt_train_wgrad);
     *bytes = L.total * 4;
-    // the plan itself (device maps) is built here when a device is there -- the caller's current one, as torch sets it (no
-    // tensor in this call) -- so that the first run call does not; the size does not need one
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) { (void)hipGetLastError(); return LNS_OK; }
-    TrainPlan* p;
-    return get_train_plan(e, device, B, H, W, &p);
+    return prebuild_train_plan(e, B, H, W);
 }
 
 // the per-sample vector network of the conditional propagator (step-invariant): ce, and per block emb and m
 struct VecView {
     float *fe, *l0, *l0g, *ce, *dce, *t1, *t2, *t3;
-    float* blk(const TrainLayout& L, float* W, int i, int which, int B, int D) const {
-        (void)B; (void)D;
-        return W + L.vec0 + (size_t)i * L.vec_blk + (size_t)which * (L.vec_blk / TV_COUNT);
-    }
+    float *blk0, *vstat0; size_t vd, vs;           // per-block vectors and GroupNorm statistics: base and slot size
+    float* blk(int i, int which) const { return blk0 + ((size_t)i * TV_COUNT + which) * vd; }       // which: TV_*
+    float* vstat(int i) const { return vstat0 + (size_t)i * vs; }
 };
 VecView vec_view(const TrainPlan& p, const TrainLayout& L, float* W) {
-    const size_t ve = ((size_t)p.B * std::max(p.E, p.D) + 63) / 64 * 64;
+    const size_t ve = round64((size_t)p.B * std::max(p.E, p.D));
     float* g = W + L.vec_glob;
-    return VecView{g, g + ve, g + 2 * ve, g + 3 * ve, g + 4 * ve, g + 5 * ve, g + 6 * ve, g + 7 * ve};
+    return VecView{g, g + ve, g + 2 * ve, g + 3 * ve, g + 4 * ve, g + 5 * ve, g + 6 * ve, g + 7 * ve,
+                   W + L.vec0, W + L.vstat, L.vec_blk / TV_COUNT, round64((size_t)p.B * 2)};
 }
 int cond_vectors_forward(lns_engine* e, const TrainPlan& p, const TrainLayout& L, const PropParams& pp, const float* const* P,
                          const float* param, float* W, hipStream_t s) {
@@ -386,13 +414,12 @@ int cond_vectors_forward(lns_engine* e, const TrainPlan& p, const TrainLayout& L
     HIPCHK(e, launch_vec_linear_fwd(v.l0g, P[pp.m2w], P[pp.m2b], v.ce, B, E, E, s));
     for (int i = 0; i < p.nb; ++i) {
         const PropParams::Blk& b = pp.blk[i];
-        float* emb = v.blk(L, W, i, TV_EMB, B, D);
+        float* emb = v.blk(i, TV_EMB);
         HIPCHK(e, launch_vec_linear_fwd(v.ce, P[b.ce_w], P[b.ce_b], emb, B, E, D, s));
-        float* vst = W + L.vstat + (size_t)i * (((size_t)B * 2 + 63) / 64 * 64);
-        HIPCHK(e, launch_vec_gn(emb, P[b.vg], P[b.vb], v.blk(L, W, i, TV_VG, B, D), vst, nullptr, nullptr, nullptr, nullptr, 0, B, D, 1e-5f, s));
-        HIPCHK(e, launch_vec_linear_fwd(v.blk(L, W, i, TV_VG, B, D), P[b.v1w], P[b.v1b], v.blk(L, W, i, TV_C1, B, D), B, D, D, s));
-        HIPCHK(e, launch_vec_gelu(v.blk(L, W, i, TV_C1, B, D), nullptr, v.blk(L, W, i, TV_C1G, B, D), B * D, s));
-        HIPCHK(e, launch_vec_linear_fwd(v.blk(L, W, i, TV_C1G, B, D), P[b.v3w], P[b.v3b], v.blk(L, W, i, TV_M, B, D), B, D, D, s));
+        HIPCHK(e, launch_vec_gn(emb, P[b.vg], P[b.vb], v.blk(i, TV_VG), v.vstat(i), nullptr, nullptr, nullptr, nullptr, 0, B, D, 1e-5f, s));
+        HIPCHK(e, launch_vec_linear_fwd(v.blk(i, TV_VG), P[b.v1w], P[b.v1b], v.blk(i, TV_C1), B, D, D, s));
+        HIPCHK(e, launch_vec_gelu(v.blk(i, TV_C1), nullptr, v.blk(i, TV_C1G), B * D, s));
+        HIPCHK(e, launch_vec_linear_fwd(v.blk(i, TV_C1G), P[b.v3w], P[b.v3b], v.blk(i, TV_M), B, D, D, s));
     }
     return LNS_OK;
 }
@@ -425,50 +452,45 @@ int lns_train_forward(lns_engine* e, const float* const* params, const float* z_
     const size_t HW = (size_t)p.H * p.W;
     const int BD = p.B * p.D;
     for (int t = 0; t < T; ++t) {
-        float* tp = W + L.tape0 + (size_t)t * L.tape_step;
+        const TapeStep tape(L, W, t);
         const float* zin = t == 0 ? z_in : z_pred + (size_t)(t - 1) * p.c * HW;
         // z_pred is [B][T][c][h][w]: step t reads / writes through a batch stride of T*c*HW
         ConvArgs ain = p.in_proj.base;
         ain.x = zin; ain.x_bs = t == 0 ? (long)p.c * HW : (long)T * p.c * HW;
-        ain.w = W + L.pk_in; ain.bias = params[pp.in_b]; ain.y = tp + L.off_x0;
+        ain.w = W + L.pk_in; ain.bias = params[pp.in_b]; ain.y = tape.x0();
         HIPCHK(e, launch_conv(p.in_proj.variant, ain, s));
-        float* x = tp + L.off_x0;
         for (int i = 0; i < p.nb; ++i) {
             const PropParams::Blk& b = pp.blk[i];
-            float* tb = tp + L.off_blk + (size_t)i * L.blk_stride;
-            const size_t ts = L.blk_stride / TB_COUNT;
-            float* st = tp + L.off_stats + (size_t)i * L.st_blk;
-            HIPCHK(e, launch_gn_train_fwd(gn_args(p, 1, 1e-5f, x, tb + TB_N1 * ts, st, params[b.g1], params[b.b1]), s));
-            if ((rc = run_tconv(e, p.c_d1, tb + TB_N1 * ts, W + L.pk_c1[i], params[b.c1b], tb + TB_U1 * ts, nullptr, s))) return rc;
-            HIPCHK(e, launch_gelu_fwd(tb + TB_U1 * ts, tb + TB_A1 * ts, n, s));
+            const float* x = tape.block_in(i);
+            HIPCHK(e, launch_gn_train_fwd(gn_args(p, 1, 1e-5f, x, tape.t(i, TB_N1), tape.stats(i, 0), params[b.g1], params[b.b1]), s));
+            if ((rc = run_tconv(e, p.c_d1, tape.t(i, TB_N1), W + L.pk(i, BC_C1), params[b.c1b], tape.t(i, TB_U1), nullptr, s))) return rc;
+            HIPCHK(e, launch_gelu_fwd(tape.t(i, TB_U1), tape.t(i, TB_A1), n, s));
             const float* ffn_in;
             if (!p.cond) {
-                if ((rc = run_tconv(e, p.c_dd, tb + TB_A1 * ts, W + L.pk_c3[i], params[b.c3b], tb + TB_U2 * ts, nullptr, s))) return rc;
-                HIPCHK(e, launch_gelu_fwd(tb + TB_U2 * ts, tb + TB_A2 * ts, n, s));
-                if ((rc = run_tconv(e, p.c_d1, tb + TB_A2 * ts, W + L.pk_c5[i], params[b.c5b], tb + TB_X1 * ts, x, s))) return rc;
-                ffn_in = tb + TB_X1 * ts;
+                if ((rc = run_tconv(e, p.c_dd, tape.t(i, TB_A1), W + L.pk(i, BC_C3), params[b.c3b], tape.t(i, TB_U2), nullptr, s))) return rc;
+                HIPCHK(e, launch_gelu_fwd(tape.t(i, TB_U2), tape.t(i, TB_A2), n, s));
+                if ((rc = run_tconv(e, p.c_d1, tape.t(i, TB_A2), W + L.pk(i, BC_C5), params[b.c5b], tape.t(i, TB_X1), x, s))) return rc;
+                ffn_in = tape.t(i, TB_X1);
             } else {
                 // h = conv1.3(a1) + emb (per-sample broadcast add in the conv epilogue) ; x1 = x + cond_conv1.2(GELU(GN(h)))
                 ConvArgs ah = p.c_dd.base;
-                ah.x = tb + TB_A1 * ts; ah.w = W + L.pk_c3[i]; ah.bias = params[b.c3b]; ah.y = tb + TB_U2 * ts;
-                ah.badd = vv.blk(L, W, i, TV_EMB, p.B, p.D);
+                ah.x = tape.t(i, TB_A1); ah.w = W + L.pk(i, BC_C3); ah.bias = params[b.c3b]; ah.y = tape.t(i, TB_U2);
+                ah.badd = vv.blk(i, TV_EMB);
                 HIPCHK(e, launch_conv(p.c_dd.variant, ah, s));
-                HIPCHK(e, launch_gn_train_fwd(gn_args(p, 1, 1e-5f, tb + TB_U2 * ts, tb + TB_NC * ts, st + 2 * (L.st_blk / 3), params[b.cg], params[b.cb]), s));
-                HIPCHK(e, launch_gelu_fwd(tb + TB_NC * ts, tb + TB_A2 * ts, n, s));
-                if ((rc = run_tconv(e, p.c_d1, tb + TB_A2 * ts, W + L.pk_c5[i], params[b.c5b], tb + TB_X1 * ts, x, s))) return rc;
-                HIPCHK(e, launch_chan_scale(tb + TB_X1 * ts, vv.blk(L, W, i, TV_M, p.B, p.D), nullptr, tb + TB_XM * ts, BD, (int)HW, s));
-                ffn_in = tb + TB_XM * ts;
+                HIPCHK(e, launch_gn_train_fwd(gn_args(p, 1, 1e-5f, tape.t(i, TB_U2), tape.t(i, TB_NC), tape.stats(i, 2), params[b.cg], params[b.cb]), s));
+                HIPCHK(e, launch_gelu_fwd(tape.t(i, TB_NC), tape.t(i, TB_A2), n, s));
+                if ((rc = run_tconv(e, p.c_d1, tape.t(i, TB_A2), W + L.pk(i, BC_C5), params[b.c5b], tape.t(i, TB_X1), x, s))) return rc;
+                HIPCHK(e, launch_chan_scale(tape.t(i, TB_X1), vv.blk(i, TV_M), nullptr, tape.t(i, TB_XM), BD, (int)HW, s));
+                ffn_in = tape.t(i, TB_XM);
             }
-            HIPCHK(e, launch_gn_train_fwd(gn_args(p, 1, 1e-5f, ffn_in, tb + TB_N2 * ts, st + L.st_blk / 3, params[b.g2], params[b.b2]), s));
-            if ((rc = run_tconv(e, p.c_1, tb + TB_N2 * ts, W + L.pk_f1[i], nullptr, tb + TB_V * ts, nullptr, s))) return rc;
-            HIPCHK(e, launch_gelu_fwd(tb + TB_V * ts, tb + TB_G * ts, n, s));
-            if ((rc = run_tconv(e, p.c_1, tb + TB_G * ts, W + L.pk_f3[i], nullptr, tb + TB_X2 * ts, tb + TB_X1 * ts, s))) return rc;
-            x = tb + TB_X2 * ts;
+            HIPCHK(e, launch_gn_train_fwd(gn_args(p, 1, 1e-5f, ffn_in, tape.t(i, TB_N2), tape.stats(i, 1), params[b.g2], params[b.b2]), s));
+            if ((rc = run_tconv(e, p.c_1, tape.t(i, TB_N2), W + L.pk(i, BC_F1), nullptr, tape.t(i, TB_V), nullptr, s))) return rc;
+            HIPCHK(e, launch_gelu_fwd(tape.t(i, TB_V), tape.t(i, TB_G), n, s));
+            if ((rc = run_tconv(e, p.c_1, tape.t(i, TB_G), W + L.pk(i, BC_F3), nullptr, tape.t(i, TB_X2), tape.t(i, TB_X1), s))) return rc;
         }
-        float* stO = tp + L.off_stats + (size_t)p.nb * L.st_blk;
-        HIPCHK(e, launch_gn_train_fwd(gn_args(p, 32, 1e-6f, x, tp + L.off_nO, stO, params[pp.out_g], params[pp.out_be]), s));
+        HIPCHK(e, launch_gn_train_fwd(gn_args(p, 32, 1e-6f, tape.last_x(), tape.nO(), tape.stats_out(), params[pp.out_g], params[pp.out_be]), s));
         ConvArgs ao = p.out_proj.base;
-        ao.x = tp + L.off_nO; ao.w = W + L.pk_out; ao.bias = params[pp.out_b];
+        ao.x = tape.nO(); ao.w = W + L.pk_out; ao.bias = params[pp.out_b];
         ao.y = z_pred + (size_t)t * p.c * HW; ao.y_bs = (long)T * p.c * HW;
         HIPCHK(e, launch_conv(p.out_proj.variant, ao, s));
     }
@@ -507,7 +529,7 @@ int lns_train_backward_ex(lns_engine* e, const float* const* params, const float
     if ((rc = pack_all(e, p, L, pp, params, W, true, s))) return rc;
     const VecView vv = p.cond ? vec_view(p, L, W) : VecView{};
     const long n = (long)L.n;
-    const size_t HW = (size_t)p.H * p.W, np = (L.n + 63) / 64 * 64, nlp = (L.nl + 63) / 64 * 64;
+    const size_t HW = (size_t)p.H * p.W, np = round64(L.n), nlp = round64(L.nl);
     float* dA = W + L.scratch; float* dB = dA + np; float* dC = dB + np; float* dD = dC + np;
     float* dz = dD + np;                 // [B][c][HW] gradient w.r.t. the step's output (contiguous)
     float* dz2 = dz + nlp;
@@ -515,104 +537,91 @@ int lns_train_backward_ex(lns_engine* e, const float* const* params, const float
     float* wgp = wgrad_form == 1 ? W + L.wg_part : nullptr;      // batch-parallel weight gradient: its partial sums
     const long nbs = (long)p.D * HW;     // sample stride of the D-channel tensors
     const int Bn = p.B, BD = p.B * p.D;
+    int acc = 0;                         // parameter gradients: written at the first processed step, accumulated after
+    // The walk's two idioms, each holding the state-only condition once.  conv_bwd: d bias (bidx >= 0), d weight from (dy, the
+    // convolution's input x), then d input = the transposed convolution tT on the flipped pack at packT, into dxo.
+    auto conv_bwd = [&](const TConv& t, const TConv& tT, int bidx, int widx, const float* dy, const float* x, long x_bs, size_t packT,
+                        float* dxo) -> int {
+        if (!so) {
+            if (bidx >= 0) HIPCHK(e, launch_bias_grad(dy, Bn, t.Cout, (int)HW, grads[bidx], acc, s));
+            if (int wrc = run_wgrad(e, t, p, dy, x, x_bs, grads[widx], acc, wgp, s)) return wrc;
+        }
+        return run_tconv(e, tT, dy, W + packT, nullptr, dxo, nullptr, s);
+    };
+    auto blk_conv_bwd = [&](int i, BlkConv k, const float* dy, const float* x, float* dxo) -> int {
+        const BlkConvRow& r = kBlkConv[k];
+        const PropParams::Blk& b = pp.blk[i];
+        return conv_bwd(p.*r.geom, p.*r.geom, r.b ? b.*r.b : -1, b.*r.w, dy, x, nbs, L.pk(i, k, true), dxo);
+    };
+    // gn_bwd: dxo = add + GroupNorm backward of dy (x, stats: the forward's input and statistics), then d gamma / d beta
+    auto gn_bwd = [&](int groups, float eps, const float* x, const float* stats, int gidx, int bidx, const float* dy, const float* add,
+                      float* dxo) -> int {
+        GnTrainArgs g = gn_args(p, groups, eps, x, nullptr, const_cast<float*>(stats), params[gidx], params[bidx]);      // (read only)
+        g.dy = dy; g.dx = dxo; g.add = add; g.part = part;
+        HIPCHK(e, launch_gn_train_bwd(g, s));
+        if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[gidx], grads[bidx], acc, s));
+        return LNS_OK;
+    };
     for (int t = T - 1; t >= 0; --t) {
-        const int acc = t == T - 1 ? 0 : 1;          // parameter gradients: written at the first processed step, accumulated after
-        float* tp = W + L.tape0 + (size_t)t * L.tape_step;
+        acc = t == T - 1 ? 0 : 1;
+        const ConstTapeStep tape(L, W, t);
         // gradient w.r.t. z_pred[:, t] = caller's + what flowed back from step t+1 (in dz2), made contiguous in dz
         // (rows of the [B][T][c][HW] tensors are T*c*HW apart)
         HIPCHK(e, launch_add_rows(grad_z_pred + (size_t)t * p.c * HW, (long)T * p.c * HW, t == T - 1 ? nullptr : dz2, (long)p.c * HW, dz,
                                   (long)p.c * HW, Bn, (long)(p.c * HW), s));
         // ---- out_proj: z = conv1(nO) + b ; nO = GN32(xL)
-        float* stO = tp + L.off_stats + (size_t)p.nb * L.st_blk;
-        const float* xL = p.nb ? tp + L.off_blk + (size_t)(p.nb - 1) * L.blk_stride + TB_X2 * (L.blk_stride / TB_COUNT) : tp + L.off_x0;
-        if (!so) HIPCHK(e, launch_bias_grad(dz, Bn, p.c, (int)HW, grads[pp.out_b], acc, s));
-        if (!so && (rc = run_wgrad(e, p.out_proj, p, dz, tp + L.off_nO, nbs, grads[pp.out_w], acc, wgp, s))) return rc;
-        if ((rc = run_tconv(e, p.out_proj_T, dz, W + L.pk_outT, nullptr, dA, nullptr, s))) return rc;        // d nO
-        {
-            GnTrainArgs g = gn_args(p, 32, 1e-6f, xL, nullptr, stO, params[pp.out_g], params[pp.out_be]);
-            g.dy = dA; g.dx = dB; g.add = nullptr; g.part = part;
-            HIPCHK(e, launch_gn_train_bwd(g, s));
-            if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[pp.out_g], grads[pp.out_be], acc, s));
-        }
+        if ((rc = conv_bwd(p.out_proj, p.out_proj_T, pp.out_b, pp.out_w, dz, tape.nO(), nbs, L.pk_outT, dA))) return rc;      // d nO
+        if ((rc = gn_bwd(32, 1e-6f, tape.last_x(), tape.stats_out(), pp.out_g, pp.out_be, dA, nullptr, dB))) return rc;
         float* dx = dB;                    // gradient w.r.t. the current block's output x2
         float* f1 = dA; float* f2 = dC; float* f3 = dD;     // free scratch tensors
         for (int i = p.nb - 1; i >= 0; --i) {
             const PropParams::Blk& b = pp.blk[i];
-            float* tb = tp + L.off_blk + (size_t)i * L.blk_stride;
-            const size_t ts = L.blk_stride / TB_COUNT;
-            float* st = tp + L.off_stats + (size_t)i * L.st_blk;
-            const float* xin = i == 0 ? tp + L.off_x0 : tp + L.off_blk + (size_t)(i - 1) * L.blk_stride + TB_X2 * ts;
             // x2 = x1 + ffn.3(g): d w(f3), d g
-            if (!so && (rc = run_wgrad(e, p.c_1, p, dx, tb + TB_G * ts, nbs, grads[b.f3w], acc, wgp, s))) return rc;
-            if ((rc = run_tconv(e, p.c_1, dx, W + L.pk_f3T[i], nullptr, f1, nullptr, s))) return rc;           // d g
-            HIPCHK(e, launch_gelu_bwd(f1, tb + TB_V * ts, f2, n, s));                                            // d v
-            if (!so && (rc = run_wgrad(e, p.c_1, p, f2, tb + TB_N2 * ts, nbs, grads[b.f1w], acc, wgp, s))) return rc;
-            if ((rc = run_tconv(e, p.c_1, f2, W + L.pk_f1T[i], nullptr, f1, nullptr, s))) return rc;           // d n2
+            if ((rc = blk_conv_bwd(i, BC_F3, dx, tape.t(i, TB_G), f1))) return rc;                               // d g
+            HIPCHK(e, launch_gelu_bwd(f1, tape.t(i, TB_V), f2, n, s));                                           // d v
+            if ((rc = blk_conv_bwd(i, BC_F1, f2, tape.t(i, TB_N2), f1))) return rc;                              // d n2
             float* dx1;                                                                                          // gradient w.r.t. x1
             if (!p.cond) {
-                GnTrainArgs g = gn_args(p, 1, 1e-5f, tb + TB_X1 * ts, nullptr, st + L.st_blk / 3, params[b.g2], params[b.b2]);
-                g.dy = f1; g.dx = f3; g.add = dx; g.part = part;                                                 // d x1 = d x2 + GN path
-                HIPCHK(e, launch_gn_train_bwd(g, s));
-                if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.g2], grads[b.b2], acc, s));
+                if ((rc = gn_bwd(1, 1e-5f, tape.t(i, TB_X1), tape.stats(i, 1), b.g2, b.b2, f1, dx, f3))) return rc;     // d x1 = d x2 + GN path
                 dx1 = f3;
             } else {
                 // ffn input was xm = x1 (1 + m): d xm through the GroupNorm, then d m += <d xm, x1>, d x1 = d x2 + d xm (1 + m)
-                GnTrainArgs g = gn_args(p, 1, 1e-5f, tb + TB_XM * ts, nullptr, st + L.st_blk / 3, params[b.g2], params[b.b2]);
-                g.dy = f1; g.dx = f3; g.add = nullptr; g.part = part;
-                HIPCHK(e, launch_gn_train_bwd(g, s));
-                if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.g2], grads[b.b2], acc, s));
-                HIPCHK(e, launch_chan_dot(f3, tb + TB_X1 * ts, vv.blk(L, W, i, TV_DM, p.B, p.D), BD, (int)HW, acc, s));
-                HIPCHK(e, launch_chan_scale(f3, vv.blk(L, W, i, TV_M, p.B, p.D), dx, f1, BD, (int)HW, s));
+                if ((rc = gn_bwd(1, 1e-5f, tape.t(i, TB_XM), tape.stats(i, 1), b.g2, b.b2, f1, nullptr, f3))) return rc;
+                HIPCHK(e, launch_chan_dot(f3, tape.t(i, TB_X1), vv.blk(i, TV_DM), BD, (int)HW, acc, s));
+                HIPCHK(e, launch_chan_scale(f3, vv.blk(i, TV_M), dx, f1, BD, (int)HW, s));
                 dx1 = f1;
             }
             float* g1 = dx1 == f3 ? f1 : f3;           // two scratch tensors besides dx1 (dx is free from here on)
             float* g2 = f2;
             // x1 = x + conv.5 / cond_conv1.2 (a2)
-            if (!so) HIPCHK(e, launch_bias_grad(dx1, Bn, p.D, (int)HW, grads[b.c5b], acc, s));
-            if (!so && (rc = run_wgrad(e, p.c_d1, p, dx1, tb + TB_A2 * ts, nbs, grads[b.c5w], acc, wgp, s))) return rc;
-            if ((rc = run_tconv(e, p.c_d1, dx1, W + L.pk_c5T[i], nullptr, g1, nullptr, s))) return rc;         // d a2
+            if ((rc = blk_conv_bwd(i, BC_C5, dx1, tape.t(i, TB_A2), g1))) return rc;                             // d a2
             if (!p.cond) {
-                HIPCHK(e, launch_gelu_bwd(g1, tb + TB_U2 * ts, g2, n, s));                                        // d u2
+                HIPCHK(e, launch_gelu_bwd(g1, tape.t(i, TB_U2), g2, n, s));                                      // d u2
             } else {
-                HIPCHK(e, launch_gelu_bwd(g1, tb + TB_NC * ts, g2, n, s));                                        // d GN(h)
-                GnTrainArgs g = gn_args(p, 1, 1e-5f, tb + TB_U2 * ts, nullptr, st + 2 * (L.st_blk / 3), params[b.cg], params[b.cb]);
-                g.dy = g2; g.dx = g1; g.add = nullptr; g.part = part;                                            // d h
-                HIPCHK(e, launch_gn_train_bwd(g, s));
-                if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.cg], grads[b.cb], acc, s));
-                HIPCHK(e, launch_chan_dot(g1, nullptr, vv.blk(L, W, i, TV_DEMB, p.B, p.D), BD, (int)HW, acc, s));   // h = .. + emb
+                HIPCHK(e, launch_gelu_bwd(g1, tape.t(i, TB_NC), g2, n, s));                                      // d GN(h)
+                if ((rc = gn_bwd(1, 1e-5f, tape.t(i, TB_U2), tape.stats(i, 2), b.cg, b.cb, g2, nullptr, g1))) return rc;     // d h
+                HIPCHK(e, launch_chan_dot(g1, nullptr, vv.blk(i, TV_DEMB), BD, (int)HW, acc, s));                // h = .. + emb
                 std::swap(g1, g2);                                                                               // d h is in g2 now
             }
-            if (!so) HIPCHK(e, launch_bias_grad(g2, Bn, p.D, (int)HW, grads[b.c3b], acc, s));
-            if (!so && (rc = run_wgrad(e, p.c_dd, p, g2, tb + TB_A1 * ts, nbs, grads[b.c3w], acc, wgp, s))) return rc;
-            if ((rc = run_tconv(e, p.c_dd, g2, W + L.pk_c3T[i], nullptr, g1, nullptr, s))) return rc;          // d a1
-            HIPCHK(e, launch_gelu_bwd(g1, tb + TB_U1 * ts, g2, n, s));                                            // d u1
-            if (!so) HIPCHK(e, launch_bias_grad(g2, Bn, p.D, (int)HW, grads[b.c1b], acc, s));
-            if (!so && (rc = run_wgrad(e, p.c_d1, p, g2, tb + TB_N1 * ts, nbs, grads[b.c1w], acc, wgp, s))) return rc;
-            if ((rc = run_tconv(e, p.c_d1, g2, W + L.pk_c1T[i], nullptr, g1, nullptr, s))) return rc;          // d n1
-            {
-                GnTrainArgs g = gn_args(p, 1, 1e-5f, xin, nullptr, st, params[b.g1], params[b.b1]);
-                g.dy = g1; g.dx = dx; g.add = dx1; g.part = part;                                                // d x = d x1 + GN path
-                HIPCHK(e, launch_gn_train_bwd(g, s));
-                if (!so) HIPCHK(e, launch_colsum2(part, Bn, p.D, grads[b.g1], grads[b.b1], acc, s));
-            }
+            if ((rc = blk_conv_bwd(i, BC_C3, g2, tape.t(i, TB_A1), g1))) return rc;                              // d a1
+            HIPCHK(e, launch_gelu_bwd(g1, tape.t(i, TB_U1), g2, n, s));                                          // d u1
+            if ((rc = blk_conv_bwd(i, BC_C1, g2, tape.t(i, TB_N1), g1))) return rc;                              // d n1
+            if ((rc = gn_bwd(1, 1e-5f, tape.block_in(i), tape.stats(i, 0), b.g1, b.b1, g1, dx1, dx))) return rc;     // d x = d x1 + GN path
         }
         // ---- in_proj: x0 = conv1(z_in) + b
         const float* zin = t == 0 ? z_in : z_pred + (size_t)(t - 1) * p.c * HW;
+        // the weight-gradient kernel reads x with a plain [B][Cin][HW] layout: step t > 0 reads z_pred through its T-strided batch
+        // axis, so it is copied to a contiguous buffer first (small: B x c x HW; the batch-parallel form takes a batch stride and
+        // reads z_pred in place).  The copy's launch follows the bias gradient's, which is therefore issued here and not by conv_bwd.
         if (!so) HIPCHK(e, launch_bias_grad(dx, Bn, p.D, (int)HW, grads[pp.in_b], acc, s));
-        {
-            // the weight-gradient kernel reads x with a plain [B][Cin][HW] layout: step t > 0 reads z_pred through its
-            // T-strided batch axis, so it is copied to a contiguous buffer first (small: B x c x HW)
-            // (the batch-parallel form takes a batch stride and reads z_pred in place)
-            const float* zc = zin;
-            long zbs = t == 0 ? (long)p.c * HW : (long)T * p.c * HW;
-            if (t > 0 && !wgp && !so) {                          // (state-only: nothing reads the copy)
-                HIPCHK(e, launch_add_rows(zin, (long)T * p.c * HW, nullptr, 0, dz, (long)p.c * HW, Bn, (long)(p.c * HW), s));
-                zc = dz; zbs = (long)p.c * HW;
-            }
-            if (!so && (rc = run_wgrad(e, p.in_proj, p, dx, zc, zbs, grads[pp.in_w], acc, wgp, s))) return rc;
+        const float* zc = zin;
+        long zbs = t == 0 ? (long)p.c * HW : (long)T * p.c * HW;
+        if (t > 0 && !wgp && !so) {                          // (state-only: nothing reads the copy)
+            HIPCHK(e, launch_add_rows(zin, (long)T * p.c * HW, nullptr, 0, dz, (long)p.c * HW, Bn, (long)(p.c * HW), s));
+            zc = dz; zbs = (long)p.c * HW;
         }
         float* dzin = t == 0 ? (grad_z_in ? grad_z_in : dz2) : dz2;
-        if ((rc = run_tconv(e, p.in_proj_T, dx, W + L.pk_inT, nullptr, dzin, nullptr, s))) return rc;            // d z_{t-1}
+        if ((rc = conv_bwd(p.in_proj, p.in_proj_T, -1, pp.in_w, dx, zc, zbs, L.pk_inT, dzin))) return rc;           // d z_{t-1}
     }
     if (p.cond && (!so || grad_param)) {
         // the vector network, once: accumulated d m / d emb of every block -> cond_conv2, cond_emb, cond_emb_proj.
@@ -622,14 +631,13 @@ int lns_train_backward_ex(lns_engine* e, const float* const* params, const float
         const int E = p.E, D = p.D;
         for (int i = 0; i < p.nb; ++i) {
             const PropParams::Blk& b = pp.blk[i];
-            float* vst = W + L.vstat + (size_t)i * (((size_t)Bn * 2 + 63) / 64 * 64); (void)vst;
-            float* dm = vv.blk(L, W, i, TV_DM, Bn, D);
-            float* demb = vv.blk(L, W, i, TV_DEMB, Bn, D);
+            float* dm = vv.blk(i, TV_DM);
+            float* demb = vv.blk(i, TV_DEMB);
             // m = W3 c1g + b3 ; c1g = GELU(c1) ; c1 = W1 vg + b1 ; vg = GN(emb)
-            HIPCHK(e, launch_vec_linear_bwd(dm, vv.blk(L, W, i, TV_C1G, Bn, D), params[b.v3w], vv.t1, 0, G(b.v3w), G(b.v3b), 0, Bn, D, D, s));
-            HIPCHK(e, launch_vec_gelu(vv.blk(L, W, i, TV_C1, Bn, D), vv.t1, vv.t2, Bn * D, s));
-            HIPCHK(e, launch_vec_linear_bwd(vv.t2, vv.blk(L, W, i, TV_VG, Bn, D), params[b.v1w], vv.t1, 0, G(b.v1w), G(b.v1b), 0, Bn, D, D, s));
-            HIPCHK(e, launch_vec_gn(vv.blk(L, W, i, TV_EMB, Bn, D), params[b.vg], params[b.vb], nullptr, nullptr, vv.t1, vv.t2, G(b.vg), G(b.vb), 0, Bn, D, 1e-5f, s));
+            HIPCHK(e, launch_vec_linear_bwd(dm, vv.blk(i, TV_C1G), params[b.v3w], vv.t1, 0, G(b.v3w), G(b.v3b), 0, Bn, D, D, s));
+            HIPCHK(e, launch_vec_gelu(vv.blk(i, TV_C1), vv.t1, vv.t2, Bn * D, s));
+            HIPCHK(e, launch_vec_linear_bwd(vv.t2, vv.blk(i, TV_VG), params[b.v1w], vv.t1, 0, G(b.v1w), G(b.v1b), 0, Bn, D, D, s));
+            HIPCHK(e, launch_vec_gn(vv.blk(i, TV_EMB), params[b.vg], params[b.vb], nullptr, nullptr, vv.t1, vv.t2, G(b.vg), G(b.vb), 0, Bn, D, 1e-5f, s));
             HIPCHK(e, launch_add(vv.t2, demb, vv.t3, (long)Bn * D, s));                                          // d emb, both paths
             // emb = Wce ce + bce : d ce accumulates over the blocks
             HIPCHK(e, launch_vec_linear_bwd(vv.t3, vv.ce, params[b.ce_w], vv.dce, i > 0 ? 1 : 0, G(b.ce_w), G(b.ce_b), 0, Bn, E, D, s));
@@ -656,8 +664,6 @@ int lns_train_backward(lns_engine* e, const float* const* params, const float* z
 // Reference: train_stage2_ns2d.py:210-216.  Every argument check below is host-only and precedes the first HIP call.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-
-size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 
 // lns_adam_spec -> the kernel's scalars; the bias corrections in double from the host-side step count
 int adam_scalars(const lns_adam_spec* sp, AdamScalars& sc, std::string& err) {
@@ -828,9 +834,7 @@ int lns_train_step_workspace_bytes(lns_engine* e, int B, int H, int W, int T, si
     StepLayout S; int rc;
     if ((rc = step_layout(e, B, H, W, T, S))) return rc;
     *bytes = S.total;
-    // build the plan now when a device is there, as lns_train_workspace_bytes does
-    size_t tb = 0;
-    return lns_train_workspace_bytes(e, B, H, W, T, &tb);
+    return prebuild_train_plan(e, B, H, W);
 }
 
 // lns_train_step (adam_spec or neither) and lns_train_step_clip (update_spec): one body, so the two cannot drift apart
@@ -996,7 +1000,7 @@ static int wgrad_op_check(int B, int Cin, int Cout, int H, int W, int ksize, int
 int lns_op_conv_wgrad_scratch_bytes(int B, int Cin, int Cout, int H, int W, int ksize, int form, size_t* bytes) {
     if (!bytes) { g_create_error = "conv_wgrad: bytes is null"; return LNS_EINVAL; }
     if (int rc = wgrad_op_check(B, Cin, Cout, H, W, ksize, form)) return rc;
-    *bytes = form == 1 ? (wgrad_split_scratch_floats(B, H, W, Cin, Cout, ksize) + 63) / 64 * 64 * 4 : 0;
+    *bytes = form == 1 ? round64(wgrad_split_scratch_floats(B, H, W, Cin, Cout, ksize)) * 4 : 0;
     return LNS_OK;
 }
 int lns_op_conv_wgrad(const float* dy, const float* x, int B, int Cin, int Cout, int H, int W, int ksize, int dilation, int pad_y,
@@ -1183,8 +1187,7 @@ int lns_fit_step_workspace_bytes(lns_engine* e, int B, int H, int W, int T, int 
     FitLayout F; int rc;
     if ((rc = fit_layout(e, B, H, W, T, n_obs, F))) return rc;
     *bytes = F.total;
-    size_t tb = 0;                       // build the plan now when a device is there, as lns_train_workspace_bytes does
-    return lns_train_workspace_bytes(e, B, H, W, T, &tb);
+    return prebuild_train_plan(e, B, H, W);
 }
 
 int lns_fit_step(lns_engine* e, const float* const* params, float* z0, float* param, const float* obs, const float* z_background,
