@@ -1245,6 +1245,99 @@ int lns_fit_step(lns_engine* e, const float* const* params, float* z0, float* pa
                  float* exp_avg_z, float* exp_avg_sq_z, float* g_p, float* exp_avg_p, float* exp_avg_sq_p, float* loss,
                  float* per_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- latent fit: Gauss-Newton ("fit_gauss_newton" in lns_build_has) ------------------------------------------------------
+ * The fit of z0 is a nonlinear least-squares problem, and both halves of its Gauss-Newton operator are calls of this
+ * header: lns_train_tangent gives J v, the state-only lns_train_backward_ex gives J^T w.  Per sample b, n = c*h*w,
+ * J_k = d z_pred[t_k] / d z0 at the current z0:
+ *     L(z0)   = sum_k w_k (1/n) |z_pred[t_k] - obs_k|^2 + lambda (1/n) |z0 - z_b|^2          (lns_loss_obs_mse's loss)
+ *     H v     = sum_k (2 w_k / n) J_k^T (J_k v) + (2 lambda / n + mu) v                       (mu >= 0: Levenberg damping, absolute)
+ *     v^T H v = sum_k (2 w_k / n) |J_k v|^2 + (2 lambda / n + mu) |v|^2
+ * An outer iteration solves H delta = -g (g: the gradient lns_fit_step forms in g_z) by n_cg steps of conjugate gradients
+ * from delta = 0 and adds delta to z0.  No reference counterpart.
+ *
+ * lns_train_gn_product follows an lns_train_forward(..., T, ...) from z_in on the SAME workspace with the SAME params, as
+ * lns_train_tangent does, and enqueues: a copy of v [B,c,h,w] into the workspace's latent tangent (v is only read) ->
+ * lns_train_tangent (K = 1, steps 0 .. T - 1, jv_out = the cotangent area) -> the weighting, in place on that area: on the
+ * plane of observed step t_k the double sum of squares of the unscaled values, then jv = (float)(2 w_k / n) * jv (the
+ * coefficient of lns_loss_obs_mse); exact zeros on every other step; and the double sum of v^2 -> the state-only
+ * lns_train_backward_ex with that area as grad_z_pred into hv [B,c,h,w] (not v) -> vhv [B] DOUBLE (nullable):
+ * sum_k (2 w_k / n) |J_k v|^2 in ascending k, then + (2 lambda / n + mu) |v|^2, one thread per sample, all in double
+ * (2 w_k / n and 2 lambda / n + mu formed in double on the host); and, when c_d = (float)(2 lambda / n + mu) != 0,
+ * hv = hv + c_d * v, one fp32 multiplication and one fp32 addition per element, not contracted.  vhv comes from the
+ * tangent side alone: a sum of squares, never negative, whatever rounding the adjoint adds to hv.
+ * Order of the sums: lns_loss_obs_mse's (256-thread block per plane, a thread adds i = tid, tid + 256, ... ascending in
+ * double, the wave as a butterfly with neighbours first, the four waves (w0 + w1) + (w2 + w3)).  No atomics; scalar
+ * accesses; bit-reproducible; the tape and the forward weight packs are left as they were, so further products and
+ * lns_train_tangent calls may follow on the same forward.
+ * T must equal obs_steps[n_obs-1] + 1 (LNS_EINVAL otherwise): the cotangent then has exactly grad_z_pred's layout.
+ * Workspace (lns_train_gn_product_workspace_bytes(e, B, h, w, T, n_obs); needs no GPU; the forward must be given it):
+ * lns_train_tangent_workspace_bytes(e, B, h, w, T, 1)'s layout, no offset moved | the cotangent, 4 * B * T * n bytes | the
+ * double partials, 8 * B * (n_obs + 1) bytes -- each part rounded up to 256 bytes.
+ * Refusals, decided on the host in this order before anything is enqueued: null e / params / z_in / z_pred / v / hv, hv == v
+ * (size query: null bytes, then no propagator, B, T, n_obs, the latent size); no propagator (LNS_ESTATE); B < 1 or beyond the
+ * batch limit; the latent size; B * n >= 2^31; the observation table as in lns_loss_obs_mse (n_obs, steps, weights,
+ * background); T != last step + 1; damping negative or not finite; a null propagator parameter pointer; workspace null or
+ * short (LNS_ENOMEM naming the bytes); then the pointers' device.  A refused call touches nothing.  No host
+ * synchronisation, allocation or host copy inside the call. */
+int lns_train_gn_product_workspace_bytes(lns_engine* e, int B, int h, int w, int T, int n_obs, size_t* bytes);
+int lns_train_gn_product(lns_engine* e, const float* const* params, const float* z_in, const float* z_pred, int B, int h,
+                         int w, int T, int n_obs, const int* obs_steps_host, const double* obs_weight_host_or_null,
+                         double background, double damping, const float* v, float* hv, double* vhv_or_null,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* Conjugate gradients per sample on fp32 vectors [B,n] with every scalar in double on the device (rs, rs0 [B] double).
+ *   lns_op_cg_start:  x = 0, r_i = -g_i, p = r, rs[b] = rs0[b] = sum_i (double)r_i^2.
+ *   lns_op_cg_update: one step with hp = H p.  php [B] double: the caller's <p, H p>; NULL: sum_i (double)p_i (double)hp_i here.
+ *       active = isfinite(rs) && rs > 0 && isfinite(php) && php > 0 && rs > tol^2 rs0
+ *       not active: NOTHING of this sample is written (x, r, p, rs keep their bits, applied[b] is not incremented: a frozen
+ *                   sample never receives a NaN)
+ *       alpha = rs / php;  x_i = (float)((double)x_i + alpha (double)p_i);  r_i = (float)((double)r_i - alpha (double)hp_i)
+ *       rs' = sum_i (double)r_i^2 (the new r);  beta = rs' / rs;  p_i = (float)((double)r_i + beta (double)p_i);  rs = rs'
+ *       applied[b] += 1   (int32 [B], nullable; the caller zeroes it)
+ * Every product and sum in double, each element rounded once, nothing contracted; one 256-thread block per sample, the
+ * sums in lns_op_orthonormalize's order.  Scalar accesses: the bits do not depend on the pointers' alignment.  Refuse null
+ * required pointers, B outside 1 .. 65535, n outside 1 .. 2^31 - 1, tol negative or not finite (LNS_EINVAL; message:
+ * lns_create_error()); never synchronise. */
+int lns_op_cg_start(const float* g, float* x, float* r, float* p, int B, int64_t n, double* rs, double* rs0, void* stream);
+int lns_op_cg_update(float* x, float* r, float* p, const float* hp, const double* php_or_null, int B, int64_t n, double tol,
+                     double* rs, const double* rs0, int32_t* applied_or_null, void* stream);
+
+/* One outer Gauss-Newton iteration on z0 [B,c,h,w] (updated IN PLACE), enqueued on `stream` in this order:
+ *     lns_train_forward over T = obs_steps[n_obs-1] + 1 steps -> lns_loss_obs_mse -> the state-only lns_train_backward_ex ->
+ *     g = grad_z_in + grad_z0_bg (a separate fp32 add, only with z_background) -> lns_op_cg_start ->
+ *     n_cg x ( lns_train_gn_product on the direction p, then lns_op_cg_update with php = the product's vhv ) ->
+ *     z0 = z0 + x (a plain fp32 add)
+ * -- the bits of those calls made one after the other; up to the add that forms g it is lns_fit_step's first half, so for
+ * the same z0 loss [B] (the loss BEFORE the update) and per [B,n_obs] (nullable) have lns_fit_step's bits.  cg_resid [B]
+ * float (nullable): (float)sqrt(rs / rs0) after the last step, 0 where the gradient is 0; applied [B] int32 (nullable): the
+ * steps that were applied to each sample (zeroed here).  `param` [B] is a known input of the conditional propagator --
+ * required there, ignored on the plain one, never fitted: the tangent has no param direction.  z_background / background as
+ * in lns_fit_step.  spec: flags must be 0, 1 <= n_cg <= LNS_GN_CG_MAX, damping (mu) and cg_tol finite and >= 0.
+ * Workspace (lns_fit_gn_step_workspace_bytes(e, B, h, w, T, n_obs); LNS_ENOMEM names the needed size):
+ * lns_train_gn_product_workspace_bytes' layout | z_pred, 4 * B * T * n bytes | grad_z0_bg | g | x | r | p | hp, 4 * B * n
+ * bytes each | rs | rs0 | vhv, 8 * B bytes each -- each part rounded up to 256 bytes.
+ * Refusals, decided on the host in this order before anything is enqueued: null e; no propagator (LNS_ESTATE); spec null or
+ * of another size; flags; n_cg; cg_tol; null params, z0 / obs, param (conditional), loss; background > 0 without
+ * z_background; then lns_train_gn_product's from "B < 1" on (T follows the table); workspace null or short (LNS_ENOMEM);
+ * then the pointers' device.  A refused call touches nothing.  No host synchronisation, allocation or host copy. */
+#define LNS_GN_CG_MAX 64
+typedef struct lns_gn_spec {
+    uint32_t size;                              /* sizeof(lns_gn_spec) */
+    uint32_t flags;                             /* 0 */
+    int32_t n_obs;
+    int32_t n_cg;                               /* 1 .. LNS_GN_CG_MAX */
+    const int* obs_steps;                       /* host, n_obs entries */
+    const double* obs_weight;                   /* host, n_obs entries, or NULL */
+    double background;                          /* lambda */
+    double damping;                             /* mu */
+    double cg_tol;                              /* a sample stops when |r| <= cg_tol |r0| */
+} lns_gn_spec;
+int lns_fit_gn_step_workspace_bytes(lns_engine* e, int B, int h, int w, int T, int n_obs, size_t* bytes);
+int lns_fit_gn_step(lns_engine* e, const float* const* params, float* z0, const float* param_or_null, const float* obs,
+                    const float* z_background_or_null, int B, int h, int w, const lns_gn_spec* spec, float* loss,
+                    float* per_or_null, float* cg_resid_or_null, int32_t* applied_or_null, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ---- tangent-linear rollout: perturbations carried forward along a trajectory -----------------------------------------
  * No reference counterpart: the reference never linearises its propagator.  lns_train_backward_ex with no gradient array
  * carries a cotangent back through the rollout, J^T w; this is the other half of the pair, J v, so that
@@ -1334,7 +1427,8 @@ int lns_timing_mfma_flops(const lns_engine* e, int index, double* mfma_flops);
  * lns_op_fa_reducer, lns_op_fa_lrk, lns_op_ln_pe, lns_op_apply, lns_rotary_table and the two fit predicates are there;
  * "eval_flow" = lns_rollout_eval_flow, lns_rollout_latent_eval_flow, lns_op_flow_stats and lns_op_vorticity are there;
  * "latent_fit" = lns_train_backward_ex, lns_loss_obs_mse, its size query, lns_fit_step and its size query are there;
- * "rollout_tangent" = lns_train_tangent, its size query and lns_op_orthonormalize are there; "ensemble_etkf" =
+ * "rollout_tangent" = lns_train_tangent, its size query and lns_op_orthonormalize are there; "fit_gauss_newton" =
+ * lns_train_gn_product, lns_fit_gn_step, their size queries, lns_op_cg_start and lns_op_cg_update are there; "ensemble_etkf" =
  * lns_rollout_latent_ensemble_analysis, its size query, lns_op_ensemble_obs_gram, lns_op_etkf_transform and
  * lns_op_ensemble_transform are there; "ensemble_letkf" = lns_rollout_latent_ensemble_analysis_local, its size query,
  * lns_op_ensemble_patch_gram, lns_op_letkf_combine and lns_op_ensemble_transform_local are there.

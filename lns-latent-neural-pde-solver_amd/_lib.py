@@ -164,6 +164,7 @@ class LnsUpdateSpec(ctypes.Structure):
 LNS_OBS_MAX = 64
 LNS_FIT_STATE, LNS_FIT_PARAM = 1, 2
 LNS_TANGENT_MAX = 32
+LNS_GN_CG_MAX = 64
 
 
 class LnsFitSpec(ctypes.Structure):
@@ -173,6 +174,16 @@ class LnsFitSpec(ctypes.Structure):
         ("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_obs", ctypes.c_int32), ("reserved", ctypes.c_int32),
         ("obs_steps", ctypes.POINTER(ctypes.c_int)), ("obs_weight", ctypes.POINTER(ctypes.c_double)),
         ("background", ctypes.c_double), ("state", LnsUpdateSpec), ("param", LnsUpdateSpec),
+    ]
+
+
+class LnsGnSpec(ctypes.Structure):
+    """Mirror of `struct lns_gn_spec` (include/lns.h): the observation table (host arrays), the CG step count, the weight
+    of the background term, the Levenberg damping and the relative residual at which a sample's CG stops."""
+    _fields_ = [
+        ("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_obs", ctypes.c_int32), ("n_cg", ctypes.c_int32),
+        ("obs_steps", ctypes.POINTER(ctypes.c_int)), ("obs_weight", ctypes.POINTER(ctypes.c_double)),
+        ("background", ctypes.c_double), ("damping", ctypes.c_double), ("cg_tol", ctypes.c_double),
     ]
 
 
@@ -240,6 +251,8 @@ SYMBOLS = [
     "lns_train_step_clip_workspace_bytes", "lns_train_step_clip",
     "lns_train_backward_ex", "lns_loss_obs_mse_scratch_bytes", "lns_loss_obs_mse", "lns_fit_step_workspace_bytes", "lns_fit_step",
     "lns_train_tangent_workspace_bytes", "lns_train_tangent", "lns_op_orthonormalize",
+    "lns_train_gn_product_workspace_bytes", "lns_train_gn_product", "lns_op_cg_start", "lns_op_cg_update",
+    "lns_fit_gn_step_workspace_bytes", "lns_fit_gn_step",
     "lns_trace_enable", "lns_trace_count", "lns_trace_info", "lns_trace_copy",
     "lns_timing_enable", "lns_timing_count", "lns_timing_info", "lns_timing_mfma_flops", "lns_build_has",
     "lns_op_conv_wgrad_scratch_bytes", "lns_op_conv_wgrad",
@@ -424,6 +437,14 @@ def lib():
         L.lns_train_tangent_workspace_bytes.argtypes = [vp, i, i, i, i, i, c.POINTER(c.c_size_t)]
         L.lns_train_tangent.argtypes = [vp, vp, i, i, i, i, i, i, i, vp, vp, vp, c.c_size_t, vp]
         L.lns_op_orthonormalize.argtypes = [vp, i, i, c.c_int64, vp, vp, vp]
+    if hasattr(L, "lns_fit_gn_step"):
+        ip, dp = c.POINTER(c.c_int), c.POINTER(c.c_double)
+        L.lns_train_gn_product_workspace_bytes.argtypes = [vp, i, i, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_train_gn_product.argtypes = [vp, vp, vp, vp, i, i, i, i, i, ip, dp, c.c_double, c.c_double, vp, vp, vp, vp, c.c_size_t, vp]
+        L.lns_op_cg_start.argtypes = [vp, vp, vp, vp, i, c.c_int64, vp, vp, vp]
+        L.lns_op_cg_update.argtypes = [vp, vp, vp, vp, vp, i, c.c_int64, c.c_double, vp, vp, vp, vp]
+        L.lns_fit_gn_step_workspace_bytes.argtypes = [vp, i, i, i, i, i, c.POINTER(c.c_size_t)]
+        L.lns_fit_gn_step.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, c.POINTER(LnsGnSpec), vp, vp, vp, vp, vp, c.c_size_t, vp]
     L.lns_build_has.argtypes = [c.c_char_p]
     L.lns_trace_enable.argtypes = [vp, i]
     L.lns_trace_count.argtypes = [vp]

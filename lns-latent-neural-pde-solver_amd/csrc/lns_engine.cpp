@@ -3432,6 +3432,7 @@ int lns_build_has(const char* feature) {
     if (!strcmp(feature, "train_ops")) return 1;
     if (!strcmp(feature, "latent_fit")) return 1;
     if (!strcmp(feature, "rollout_tangent")) return 1;
+    if (!strcmp(feature, "fit_gauss_newton")) return 1;
     if (!strcmp(feature, "rollout_select")) return 1;
     if (!strcmp(feature, "rollout_ensemble")) return 1;
     if (!strcmp(feature, "ensemble_score")) return 1;
@@ -3462,3 +3463,4 @@ int lns_build_has(const char* feature) {
 
 #include "lns_train.inc"
 #include "lns_tangent.inc"
+#include "lns_fit_gn.inc"

@@ -80,6 +80,31 @@ struct ObsTable {
 hipError_t launch_obs_mse(const ObsTable& tb, const float* z_pred, const float* obs, const float* z0, const float* zb, int B, int T,
                           long n, float* per, float* loss, float* grad, float* gbg, double* part, hipStream_t s);
 
+// ---- Gauss-Newton latent fit (fit_gn.inc) ---------------------------------------------------------------------------------
+// The observation table of a Gauss-Newton product as a kernel argument: coef[k] = (float)(2 w_k / n) as in ObsTable,
+// cw[k] = 2 w_k / n and cd = 2 lambda / n + mu in double (the sums of v^T H v), c_d = (float)cd (the diagonal term of H v).
+struct GnTable {
+    int n_obs, pad;
+    int steps[OBS_MAX];
+    float coef[OBS_MAX];
+    float c_d, pad2;
+    double cw[OBS_MAX];
+    double cd;
+};
+// jv [B][T][n] in place: part[b][k] = sum_i (double)jv[b,t_k,i]^2 on the unscaled values, then jv = coef[k] jv; exact zeros on
+// the steps that are not observed; part[b][n_obs] = sum_i (double)v[b,i]^2.  part: B * (n_obs + 1) doubles.
+hipError_t launch_gn_weight(const GnTable& tb, float* jv, const float* v, int B, int T, long n, double* part, hipStream_t s);
+// vhv[b] (nullable) = sum_k cw[k] part[b][k] + cd part[b][n_obs] in double; hv[i] = hv[i] + c_d v[i] in fp32 when c_d != 0
+hipError_t launch_gn_finish(const GnTable& tb, const double* part, float* hv, const float* v, int B, long n, double* vhv, hipStream_t s);
+// Conjugate gradients per sample on [B][n] vectors, one block per sample, scalars rs / rs0 [B] in double on the device.
+// start: x = 0, r = p = -g, rs = rs0 = <r, r>.  update: one step with <p, H p> = php[b] (php null: <p, hp> summed here); a
+// sample with rs or php not finite or not positive, or rs <= tol2 rs0, is not written at all.  applied [B] (nullable): += 1.
+hipError_t launch_cg_start(const float* g, float* x, float* r, float* p, int B, long n, double* rs, double* rs0, hipStream_t s);
+hipError_t launch_cg_update(float* x, float* r, float* p, const float* hp, const double* php, int B, long n, double tol2, double* rs,
+                            const double* rs0, int* applied, hipStream_t s);
+// resid[b] = (float)sqrt(rs / rs0), 0 where rs0 is 0
+hipError_t launch_cg_resid(const double* rs, const double* rs0, int B, float* resid, hipStream_t s);
+
 // ---- tangent-linear rollout (tangent.inc) --------------------------------------------------------------------------------
 // Tangent tensors are [B*K][C][HW], row r = b*K + k; what is read from the forward's tape belongs to sample b = r / K.
 struct GnJvpArgs {

@@ -449,5 +449,6 @@ hipError_t launch_vec_gn(const float* x, const float* gamma, const float* beta, 
 #include "lns_optim.inc"
 #include "latent_fit.inc"
 #include "tangent.inc"
+#include "fit_gn.inc"
 
 }  // namespace lns

@@ -457,7 +457,8 @@ class LatentDynamics(_Hosted):
         z_pred, _ = self._engine(z0).rollout_latent(z0, z_out.shape[1], param=param, to_x=False)
         return loss_fn(z_pred, z_out)
 
-    def assimilate(self, x0, y_obs, obs_steps, *rest, iters=40, weights=None, chunk=32, **fit):
+    def assimilate(self, x0, y_obs, obs_steps, *rest, iters=40, weights=None, chunk=32, method="adam", outer=3, cg_iters=8,
+                   damping=0.0, **fit):
         """assimilate(x0, y_obs, obs_steps, iters=...) -- conditional: assimilate(x0, y_obs, obs_steps, param, iters=...):
         which initial latent makes the rollout agree with ALL the observed frames, and (conditional model) which `param`
         explains them.  x0 [B,C,Ly,Lx]: the frame the forecast would start from -- its encoding is the start of the fit and
@@ -466,9 +467,19 @@ class LatentDynamics(_Hosted):
         arguments (lr_state, lr_param, betas, eps, background, fit_state, fit_param).  Returns fit.FitResult (z0, param,
         loss [iters, B], per [B, n_obs]); `model._engine(z0).rollout_latent(z0, steps, param=...)` forecasts from it.
         With a conditional ENCODER fitting `param` is refused: the encoding of the observations would depend on the
-        unknown (LatentFit.run on latents has no such limit)."""
+        unknown (LatentFit.run on latents has no such limit).
+        method="gauss_newton": the state is fitted by LatentFit.run_gauss_newton -- `outer` iterations of `cg_iters`
+        conjugate-gradient steps on the Gauss-Newton operator, Levenberg `damping` -- instead of `iters` Adam steps; loss is
+        then [outer + 1, B].  `param` is a known input there: fit_param=True is refused (the tangent-linear rollout has no
+        param direction)."""
         from . import fit as _fit
         from . import metrics as _metrics
+        if method not in ("adam", "gauss_newton"):
+            raise LnsError("assimilate: method must be 'adam' or 'gauss_newton', got %r" % (method,))
+        if method == "gauss_newton" and fit.get("fit_param"):
+            raise LnsError("assimilate: method='gauss_newton' fits the state only: the tangent-linear rollout has no param "
+                           "direction, so there is no Gauss-Newton product for param; drop fit_param=True (param is then a "
+                           "known input), or use method='adam'")
         param = None
         if self._conditional:
             if not rest:
@@ -479,7 +490,7 @@ class LatentDynamics(_Hosted):
                             else "assimilate() takes (x0, y_obs, obs_steps, ...)")
         fitter = _fit.LatentFit(self, **fit)
         cond_enc = bool(getattr(self.args, "cond_encoder", False))
-        if cond_enc and fitter.fit_param:
+        if cond_enc and fitter.fit_param and method == "adam":
             raise LnsError("assimilate: the encoder is conditional, so the encoding of the observations would depend on the "
                            "param being fitted; pass fit_param=False, or fit latents with lns_amd.fit.LatentFit.run")
         x0 = self._fields(x0)
@@ -493,6 +504,9 @@ class LatentDynamics(_Hosted):
             enc_po = torch.as_tensor(param).reshape(B, 1).expand(B, n_obs).reshape(-1) if cond_enc else None
             z_obs = _metrics.encode_dataset(self._ae, frames, chunk=chunk, out_device=x0.device, param=enc_po)
         z_obs = z_obs.reshape((B, n_obs) + tuple(z_obs.shape[1:]))
+        if method == "gauss_newton":
+            return fitter.run_gauss_newton(z0, z_obs, obs_steps, param=param, weights=weights, outer=outer, cg_iters=cg_iters,
+                                           damping=damping)
         return fitter.run(z0, z_obs, obs_steps, param=param, weights=weights, iters=iters)
 
     @torch.no_grad()

@@ -178,6 +178,76 @@ def fit_spec(obs_steps, weights=None, background=0.0, state=None, param=None):
     return spec
 
 
+def gn_spec(obs_steps, weights=None, background=0.0, n_cg=8, damping=0.0, cg_tol=0.0):
+    """`lns_gn_spec`: the observation table, the CG steps of one outer Gauss-Newton iteration, the weight of the background
+    term, the Levenberg damping mu (absolute, added to the diagonal of H) and the relative residual |r| / |r0| at which a
+    sample's CG stops.  The host arrays are kept alive by the returned object."""
+    steps, w = normalize_obs(obs_steps, weights)
+    spec = _lib.LnsGnSpec()
+    spec.size = ctypes.sizeof(_lib.LnsGnSpec)
+    spec.flags = 0
+    spec.n_obs, spec.n_cg = len(steps), int(n_cg)
+    spec._steps = (ctypes.c_int * len(steps))(*steps)
+    spec._weights = (ctypes.c_double * len(w))(*w)
+    spec.obs_steps = ctypes.cast(spec._steps, ctypes.POINTER(ctypes.c_int))
+    spec.obs_weight = ctypes.cast(spec._weights, ctypes.POINTER(ctypes.c_double))
+    spec.background, spec.damping, spec.cg_tol = float(background), float(damping), float(cg_tol)
+    return spec
+
+
+def _cg_vectors(who, first, others, scalars, applied=None):
+    """The checks cg_start / cg_update share: contiguous fp32 [B,...] HIP tensors of one shape, float64 [B] scalars."""
+    import torch
+    if not isinstance(first, torch.Tensor) or not first.is_cuda or first.dtype != torch.float32 or first.dim() < 2 \
+            or not first.is_contiguous():
+        raise LnsError("%s works on contiguous fp32 [B,...] HIP device tensors (there is no CPU fallback), got %s"
+                       % (who, ("%s %s on %s" % (first.dtype, tuple(first.shape), first.device)) if isinstance(first, torch.Tensor)
+                          else type(first)))
+    B = int(first.shape[0])
+    for t_ in others:
+        if not isinstance(t_, torch.Tensor) or t_.shape != first.shape or t_.dtype != torch.float32 or not t_.is_contiguous() \
+                or t_.device != first.device:
+            raise LnsError("%s: every vector must be a contiguous fp32 tensor of shape %s on one device" % (who, tuple(first.shape)))
+    for t_ in scalars:
+        if t_ is not None and (not isinstance(t_, torch.Tensor) or tuple(t_.shape) != (B,) or t_.dtype != torch.float64
+                               or not t_.is_contiguous() or t_.device != first.device):
+            raise LnsError("%s: rs / rs0 / php must be contiguous float64 [B] tensors on the vectors' device" % who)
+    if applied is not None and (tuple(applied.shape) != (B,) or applied.dtype != torch.int32 or not applied.is_contiguous()
+                                or applied.device != first.device):
+        raise LnsError("%s: applied must be a contiguous int32 [B] tensor on the vectors' device" % who)
+    return B, (first[0].numel() if B else 0)
+
+
+def cg_start(g, x, r, p, rs=None, rs0=None):
+    """The start of conjugate gradients per sample (lns_op_cg_start): x = 0, r = p = -g, rs = rs0 = <r, r> in double in a
+    fixed order.  g, x, r, p: fp32 [B,...]; rs, rs0: float64 [B] (allocated when None).  Returns (rs, rs0).
+    Bit-reproducible; never synchronises.  Module-level because the op needs no engine."""
+    import torch
+    B, n = _cg_vectors("cg_start", g, (x, r, p), (rs, rs0))
+    with torch.cuda.device(g.device):
+        rs = torch.empty(B, dtype=torch.float64, device=g.device) if rs is None else rs
+        rs0 = torch.empty(B, dtype=torch.float64, device=g.device) if rs0 is None else rs0
+        rc = _lib.lib().lns_op_cg_start(g.data_ptr(), x.data_ptr(), r.data_ptr(), p.data_ptr(), B, n, rs.data_ptr(), rs0.data_ptr(),
+                                        Engine._stream(g))
+    _op_check(rc, "lns_op_cg_start")
+    return rs, rs0
+
+
+def cg_update(x, r, p, hp, rs, rs0, php=None, tol=0.0, applied=None):
+    """One step of conjugate gradients per sample (lns_op_cg_update), IN PLACE on x, r, p and rs: hp = H p; php [B] float64:
+    <p, H p> (None: <p, hp> is summed inside); a sample whose rs or php is not finite or not positive, or whose
+    |r| <= tol |r0|, is not written at all; applied [B] int32: += 1 for every sample that was.  Bit-reproducible; never
+    synchronises."""
+    import torch
+    B, n = _cg_vectors("cg_update", x, (r, p, hp), (rs, rs0, php), applied)
+    if rs is None or rs0 is None:
+        raise LnsError("cg_update: rs and rs0 are required")
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().lns_op_cg_update(x.data_ptr(), r.data_ptr(), p.data_ptr(), hp.data_ptr(), Engine._ptr(php), B, n, float(tol),
+                                         rs.data_ptr(), rs0.data_ptr(), Engine._ptr(applied), Engine._stream(x))
+    _op_check(rc, "lns_op_cg_update")
+
+
 def obs_loss(z_pred, obs, obs_steps, weights=None, z0=None, z_background=None, background=0.0, need_per=True, need_bg_grad=None,
              grad_out=None):
     """Observation loss of a latent rollout and its gradient, one loss per trajectory (lns_loss_obs_mse): z_pred
@@ -1777,6 +1847,97 @@ class Engine:
                                              self._ptr(exp_avg_p), self._ptr(exp_avg_sq_p), loss.data_ptr(), per.data_ptr(),
                                              workspace.data_ptr(), workspace.numel(), self._stream(z0)), "lns_fit_step")
         return loss, per
+
+    # -- latent fit: Gauss-Newton (include/lns.h "latent fit: Gauss-Newton") ------------------------------------------
+    cg_start = staticmethod(cg_start)
+    cg_update = staticmethod(cg_update)
+
+    def train_gn_product_workspace_bytes(self, B, h, w, T, n_obs):
+        """Bytes of the workspace train_forward(..., workspace=) and train_gn_product share: train_tangent's for K = 1 plus the
+        cotangent and the double partials.  Needs no GPU."""
+        n = ctypes.c_size_t(0)
+        self._check(self._L.lns_train_gn_product_workspace_bytes(self._h, int(B), int(h), int(w), int(T), int(n_obs), ctypes.byref(n)),
+                    "lns_train_gn_product_workspace_bytes")
+        return int(n.value)
+
+    def train_gn_product(self, params, z_in, z_pred, v, obs_steps, workspace, weights=None, background=0.0, damping=0.0, hv=None,
+                         vhv=None, need_vhv=True):
+        """(H v, v^T H v) of the Gauss-Newton operator of the observation loss at z_in, on the tape of the
+        train_forward(params, z_in, T = obs_steps[-1] + 1, workspace=workspace) that gave z_pred: v [B,c,h,w] is only read;
+        hv like v and vhv [B] float64 are the caller's or allocated (need_vhv False and vhv None: no vhv).  Never
+        synchronises; with hv / vhv given nothing allocates."""
+        import torch
+        z_in, v = self._dev(z_in), self._dev(v)
+        steps, w_ = normalize_obs(obs_steps, weights)
+        B, c, h, w = z_in.shape
+        T = steps[-1] + 1
+        if v.shape != z_in.shape or v.device != z_in.device:
+            raise LnsError("v must be [B,c,h,w] like z_in %s on its device, got %s" % (tuple(z_in.shape), tuple(v.shape)))
+        if tuple(z_pred.shape) != (B, T, c, h, w) or z_pred.dtype != torch.float32 or not z_pred.is_contiguous() or z_pred.device != z_in.device:
+            raise LnsError("z_pred must be the contiguous fp32 [B,%d,c,h,w] of the forward over the last observed step + 1" % T)
+        with torch.cuda.device(z_in.device):
+            if hv is None:
+                hv = torch.empty_like(v)
+            if vhv is None and need_vhv:
+                vhv = torch.empty(B, dtype=torch.float64, device=z_in.device)
+            if hv.shape != v.shape or hv.dtype != torch.float32 or not hv.is_contiguous() or hv.device != v.device:
+                raise LnsError("hv must be a contiguous fp32 tensor like v")
+            if vhv is not None and (tuple(vhv.shape) != (B,) or vhv.dtype != torch.float64 or not vhv.is_contiguous() or vhv.device != v.device):
+                raise LnsError("vhv must be a contiguous float64 [B] tensor on v's device")
+            self._check(self._L.lns_train_gn_product(
+                self._h, self._ptr_array(params) if isinstance(params, dict) else params, z_in.data_ptr(), z_pred.data_ptr(), B, h, w, T,
+                len(steps), (ctypes.c_int * len(steps))(*steps), (ctypes.c_double * len(w_))(*w_), float(background), float(damping),
+                v.data_ptr(), hv.data_ptr(), self._ptr(vhv), workspace.data_ptr(), workspace.numel(), self._stream(z_in)),
+                "lns_train_gn_product")
+        return hv, vhv
+
+    def fit_gn_step_workspace_bytes(self, B, h, w, T, n_obs):
+        """Bytes of the workspace of fit_gn_step for T = last observed step + 1 rollout steps and n_obs observations."""
+        n = ctypes.c_size_t(0)
+        self._check(self._L.lns_fit_gn_step_workspace_bytes(self._h, int(B), int(h), int(w), int(T), int(n_obs), ctypes.byref(n)),
+                    "lns_fit_gn_step_workspace_bytes")
+        return int(n.value)
+
+    def fit_gn_step(self, params, z0, obs, spec, param=None, z_background=None, loss=None, per=None, cg_resid=None, applied=None,
+                    workspace=None):
+        """One outer Gauss-Newton iteration on z0 [B,c,h,w], IN PLACE (lns_fit_gn_step): training forward, observation loss,
+        state-only adjoint, spec.n_cg steps of conjugate gradients on H delta = -g with H v from the tangent and the adjoint,
+        z0 += delta.  spec: gn_spec(...); param [B]: the conditional propagator's known input.  Returns (loss [B] before the
+        update, per [B,n_obs], cg_resid [B] = |r| / |r0|, applied [B] int32); nothing here synchronises, and with the four
+        outputs and the workspace given nothing allocates."""
+        import torch
+        if isinstance(z0, torch.Tensor) and not z0.is_contiguous():
+            raise LnsError("fit_gn_step updates z0 in place: it must be contiguous")
+        z0, obs = self._dev(z0), self._dev(obs)
+        B, c, h, w = z0.shape
+        if obs.dim() != 5 or obs.shape[0] != B or obs.shape[1] != spec.n_obs or tuple(obs.shape[2:]) != (c, h, w) or obs.device != z0.device:
+            raise LnsError("obs must be [B,%d,%d,%d,%d] on z0's device, got %s on %s" % (spec.n_obs, c, h, w, tuple(obs.shape), obs.device))
+        if param is not None:
+            param = self._dev(param)
+            if tuple(param.shape) != (B,) or param.device != z0.device:
+                raise LnsError("param must be [B] on z0's device")
+        if z_background is not None:
+            z_background = self._dev(z_background)
+            if z_background.shape != z0.shape or z_background.device != z0.device:
+                raise LnsError("z_background must match z0")
+        T = int(spec._steps[spec.n_obs - 1]) + 1
+        with torch.cuda.device(z0.device):
+            dev = z0.device
+            if workspace is None:
+                workspace = torch.empty(self.fit_gn_step_workspace_bytes(B, h, w, T, spec.n_obs), dtype=torch.uint8, device=dev)
+            loss = torch.empty(B, dtype=torch.float32, device=dev) if loss is None else loss
+            per = torch.empty((B, spec.n_obs), dtype=torch.float32, device=dev) if per is None else per
+            cg_resid = torch.empty(B, dtype=torch.float32, device=dev) if cg_resid is None else cg_resid
+            applied = torch.empty(B, dtype=torch.int32, device=dev) if applied is None else applied
+            for t_, shape, dt, name in ((loss, (B,), torch.float32, "loss"), (per, (B, spec.n_obs), torch.float32, "per"),
+                                        (cg_resid, (B,), torch.float32, "cg_resid"), (applied, (B,), torch.int32, "applied")):
+                if tuple(t_.shape) != shape or t_.dtype != dt or not t_.is_contiguous() or t_.device != dev:
+                    raise LnsError("%s must be a contiguous %s tensor of shape %s on z0's device" % (name, dt, shape))
+            self._check(self._L.lns_fit_gn_step(self._h, self._ptr_array(params) if isinstance(params, dict) else params, z0.data_ptr(),
+                                                self._ptr(param), obs.data_ptr(), self._ptr(z_background), B, h, w, ctypes.byref(spec),
+                                                loss.data_ptr(), per.data_ptr(), cg_resid.data_ptr(), applied.data_ptr(),
+                                                workspace.data_ptr(), workspace.numel(), self._stream(z0)), "lns_fit_gn_step")
+        return loss, per, cg_resid, applied
 
     # -- device-resident training step (include/lns.h "device-resident training step") -------------------------------
     smooth_l1 = staticmethod(smooth_l1)

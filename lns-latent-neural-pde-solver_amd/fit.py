@@ -48,6 +48,7 @@ class LatentFit:
         self._eng = self._own._eng
         self.fit_state = bool(fit_state)
         self.fit_param = model._conditional if fit_param is None else bool(fit_param)     # None: "the model is conditional"
+        self._param_fit_asked = fit_param is not None and bool(fit_param)                 # run_gauss_newton refuses only this
         if self.fit_param and not model._conditional:
             raise LnsError("fit_param needs the conditional model: a plain propagator has no param")
         if not self.fit_state and not self.fit_param:
@@ -82,6 +83,92 @@ class LatentFit:
                 ws = torch.empty(need, dtype=torch.uint8, device=self._device)
             self._ws[key] = ws
         return ws
+
+    def _gn_workspace(self, B, h, w, T, n_obs):
+        need = self._eng.fit_gn_step_workspace_bytes(B, h, w, T, n_obs)
+        key = ("gn", self._device, B, h, w, T, n_obs, need)
+        ws = self._ws.get(key)
+        if ws is None:
+            with torch.cuda.device(self._device):
+                ws = torch.empty(need, dtype=torch.uint8, device=self._device)
+            self._ws[key] = ws
+        return ws
+
+    def _start(self, z0, param):
+        """What run and the Gauss-Newton calls refuse about (z0, param), and the pointer table."""
+        self._current()
+        if self.model._conditional != (param is not None):
+            raise LnsError("param must be given exactly for the conditional model")
+        if not isinstance(z0, torch.Tensor) or z0.dim() != 4 or z0.device != self._device:
+            raise LnsError("z0 must be [B,c,h,w] on the propagator's device %s" % (self._device,))
+
+    @torch.no_grad()
+    def run_gauss_newton(self, z0, obs, obs_steps, param=None, weights=None, outer=3, cg_iters=8, damping=0.0, cg_tol=0.0,
+                         z_background=None):
+        """The fit of the STATE by Gauss-Newton: `outer` iterations, each ONE call of the C ABI (lns_fit_gn_step) -- forward,
+        observation loss, state-only adjoint, `cg_iters` steps of conjugate gradients on H delta = -g with H v from the
+        tangent-linear rollout and the adjoint, z0 += delta.  damping: Levenberg's mu added to the diagonal of H (absolute);
+        cg_tol: a sample's CG stops at |r| <= cg_tol |r0|.  No line search: the step is taken as it is.  param [B]: the known
+        parameter of the conditional model (the tangent has no param direction, so it is not fitted here: an instance built
+        with fit_param=True is refused).  Arguments otherwise as in `run`.  Returns FitResult(z0, param, loss [outer + 1, B],
+        per [B, n_obs]): row i < outer is the loss before iteration i, the last row the loss of the returned z0 (one more
+        forward and observation loss), per belongs to it.  Works on clones; never synchronises."""
+        if self._param_fit_asked:
+            raise LnsError("run_gauss_newton fits the state only: the tangent-linear rollout has no param direction, so there "
+                           "is no Gauss-Newton product for param; build LatentFit without fit_param=True (param is then a "
+                           "known input), or use run")
+        self._start(z0, param)
+        outer = int(outer)
+        if outer < 1:
+            raise LnsError("outer must be >= 1")
+        steps, w_ = _engine.normalize_obs(obs_steps, weights)
+        with torch.cuda.device(self._device):
+            z = z0.detach().to(torch.float32).clone(memory_format=torch.contiguous_format)
+            B, c, h, w = z.shape
+            p = self._eng._param(param, z).clone() if param is not None else None
+            zb = None
+            if self.background > 0 or z_background is not None:
+                zb = (z0 if z_background is None else z_background).detach().to(torch.float32).clone(memory_format=torch.contiguous_format)
+            dev = self._device
+            T = steps[-1] + 1
+            loss = torch.empty((outer + 1, B), dtype=torch.float32, device=dev)
+            per = torch.empty((B, len(steps)), dtype=torch.float32, device=dev)
+            resid = torch.empty(B, dtype=torch.float32, device=dev)
+            applied = torch.empty(B, dtype=torch.int32, device=dev)
+            ws = self._gn_workspace(B, h, w, T, len(steps))
+            obs = self._eng._dev(obs)
+            spec = _engine.gn_spec(steps, w_, self.background, n_cg=cg_iters, damping=damping, cg_tol=cg_tol)
+            for it in range(outer):
+                self._eng.fit_gn_step(self._arr, z, obs, spec, param=p, z_background=zb, loss=loss[it], per=per, cg_resid=resid,
+                                      applied=applied, workspace=ws)
+            z_pred, _ = self._eng.train_forward(self._arr, z, T, param=p, workspace=ws)
+            bg = dict(z0=z, z_background=zb, background=self.background, need_bg_grad=False) if zb is not None else {}
+            last, per, _, _ = _engine.obs_loss(z_pred, obs, steps, w_, **bg)
+            loss[outer].copy_(last)
+        return FitResult((z, p, loss, per))
+
+    @torch.no_grad()
+    def hessian_product(self, z0, v, obs_steps, param=None, weights=None, damping=0.0):
+        """(H v, v^T H v) of the Gauss-Newton operator of the fit's loss at z0 for every vector of v [B,K,c,h,w]: one training
+        forward, then one lns_train_gn_product per k.  Returns (hv [B,K,c,h,w], vhv [B,K] float64); uses self.background."""
+        self._start(z0, param)
+        steps, w_ = _engine.normalize_obs(obs_steps, weights)
+        if not isinstance(v, torch.Tensor) or v.dim() != 5 or v.shape[0] != z0.shape[0] or v.shape[2:] != z0.shape[1:] or v.device != z0.device:
+            raise LnsError("v must be [B,K,c,h,w] matching z0 %s on its device" % (tuple(z0.shape),))
+        with torch.cuda.device(self._device):
+            z = self._eng._dev(z0.detach())
+            B, c, h, w = z.shape
+            K, T = int(v.shape[1]), steps[-1] + 1
+            p = self._eng._param(param, z) if param is not None else None
+            ws = self._gn_workspace(B, h, w, T, len(steps))
+            z_pred, _ = self._eng.train_forward(self._arr, z, T, param=p, workspace=ws)
+            hv = torch.empty((K, B, c, h, w), dtype=torch.float32, device=self._device)
+            vhv = torch.empty((K, B), dtype=torch.float64, device=self._device)
+            vk = v.detach().to(torch.float32).transpose(0, 1).contiguous()
+            for k in range(K):
+                self._eng.train_gn_product(self._arr, z, z_pred, vk[k], steps, ws, weights=w_, background=self.background,
+                                           damping=damping, hv=hv[k], vhv=vhv[k])
+        return hv.transpose(0, 1).contiguous(), vhv.transpose(0, 1).contiguous()
 
     @torch.no_grad()
     def run(self, z0, obs, obs_steps, param=None, weights=None, iters=40, z_background=None):
