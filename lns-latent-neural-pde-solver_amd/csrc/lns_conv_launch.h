@@ -10,6 +10,7 @@
 
 #include "../../include/lns.h"
 #include "lns_kernels.h"
+#include "lns_knobs.h"
 
 namespace lns {
 
@@ -68,23 +69,23 @@ inline bool conv_geometry(ConvGeom& g, int B, int Cout, int Hv, int Wv, int k, i
     if (force_variant >= 0) cands = {force_variant};
     else if (Cout <= 32) cands = {CV_S32};
     else if (Cout <= 64) cands = need_wgm1 ? std::vector<int>{CV_L64, CV_M64} : std::vector<int>{CV_L64, CV_M64, CV_S64};
-    else if (getenv("LNS_CONV_USE_128")) cands = {CV_L128, CV_M128, CV_S64};   // tuning knob (tile choice only)
+    else if (knobs().conv_use_128) cands = {CV_L128, CV_M128, CV_S64};   // tuning knob (tile choice only)
     else cands = {CV_L64, CV_M64, CV_S64};   // 64-cout tiles at 2 waves/SIMD beat 128-cout tiles at 1 (measured)
     // bf16x3 kernel for every eligible 3x3 conv.  Eligibility is a function of the layer only (never of B):
     // the fp32 variants accumulate in a different order, and a trajectory must not change bitwise with the
     // batch it is computed in.
-    static const bool no_bf16x3 = getenv("LNS_CONV_FP32_MFMA") != nullptr;
+    const bool no_bf16x3 = knobs().conv_fp32_mfma;
     const bool use_b = allow_bf16x3 && !no_bf16x3 && k == 3 && stride == 1 && Cout > 32;
     if (force_variant < 0 && use_b) {   // fp32 variants only if the geometry rules the bf16x3 tiles out
         cands.insert(cands.begin(), f16x2 ? (int)CV_F64 : (int)CV_B64);
     }
-    static const bool no_b1 = getenv("LNS_CONV1_FP32_MFMA") != nullptr;
+    const bool no_b1 = knobs().conv1_fp32_mfma;
     // 1x1: bf16x3 unless the layer is a thin projection (few output channels / a handful of input channels:
     // bandwidth-bound, and a 64-cout MFMA tile would be mostly padding) -- again a per-layer rule
     if (force_variant < 0 && allow_bf16x3 && !no_bf16x3 && !no_b1 && k == 1 && stride == 1 && Cout > 32 && Cin >= 16)
         cands = {(int)CV_B1};
     // <= 4 output channels (the decoder's last conv): streaming VALU kernel, one HBM read of the input
-    static const bool no_thin = getenv("LNS_CONV1_NO_THIN") != nullptr;
+    const bool no_thin = knobs().conv1_no_thin;
     if (force_variant < 0 && allow_thin && !no_thin && k == 1 && stride == 1 && Cout <= 4 && Cin <= 512 && (Hv * Wv) % 4 == 0)
         cands = {(int)CV_THIN};
     g.kc_log2 = conv_pick_kc_log2(k, stride, kc_log2_pack);
@@ -135,13 +136,11 @@ inline bool conv_geometry(ConvGeom& g, int B, int Cout, int Hv, int Wv, int k, i
         g.cout_tiles = (Cout + vi.TM - 1) / vi.TM;
         g.PH = tmp.PH; g.PW = tmp.PW; g.sel_kc_log2 = best_kc;
         found = true;
-        static const long min_blocks = getenv("LNS_CONV_MIN_BLOCKS") ? atol(getenv("LNS_CONV_MIN_BLOCKS")) : 128;
         if (cands[ci] == CV_B64 && Cout >= 64 && !need_wgm1 && force_variant < 0) {
             // 32-cout tiles (same accumulation order, same bits) when 64-cout tiles give fewer blocks than this.
             // Measured on NS2d-128 (16x16 latent layers, 256 -> 512 blocks): no gain (17.9k vs 18.7k
             // trajectory-steps/s), so the default is off; kept as a tuning knob and covered by the kernel tests.
-            static const long want = getenv("LNS_CONVB32_BELOW") ? atol(getenv("LNS_CONVB32_BELOW")) : 0;
-            if (blocks < want) { g.variant = CV_B32; g.cout_tiles = (Cout + 31) / 32; }
+            if (blocks < knobs().convb32_below) { g.variant = CV_B32; g.cout_tiles = (Cout + 31) / 32; }
         }
         if (cands[ci] == CV_F64 && Cout >= 64 && !need_wgm1 && force_variant < 0) {
             // the same for the f16x2 form.  On 256-block launches (the 16x16 latent layers of NS2d at B = 64) it measured
@@ -149,11 +148,10 @@ inline bool conv_geometry(ConvGeom& g, int B, int Cout, int Hv, int Wv, int k, i
             // stages and splits the whole patch), but launches that leave three quarters of the CUs idle gain: the 7 x 15
             // latent layers of the two-phase models at B = 32 (64 blocks) 19.7 -> 15.3 us, dilated 20.5 -> 17.8
             // (tools/conv_time.py lat_tp / lat_tp_d4, variant 13).  Same bits either way, so the batch may decide.
-            static const long wantf = getenv("LNS_CONVF32_BELOW") ? atol(getenv("LNS_CONVF32_BELOW")) : 100;
-            if (blocks < wantf) { g.variant = CV_F32; g.cout_tiles = (Cout + 31) / 32; }
+            if (blocks < knobs().convf32_below) { g.variant = CV_F32; g.cout_tiles = (Cout + 31) / 32; }
         }
         if (cands[ci] >= CV_B64) break;                        // never fall through to another kernel family by launch size
-        if (blocks >= min_blocks) break;
+        if (blocks >= knobs().conv_min_blocks) break;
     }
     return found;
 }
@@ -187,10 +185,9 @@ inline void conv_set_geometry(ConvArgs& a, const ConvGeom& g, int B, int Cin, in
 // "No resize" is Hv == Hin && Wv == Win.  The planner used to write it as `up2 || (!in.vH && !in.vW)`; the two agree:
 // a TRef's virtual size is only ever set as (2H, 2W) or as a target (outH, outW) != (H, W), both components together, so
 // vH != 0 means (Hv, Wv) != (H, W) before the rewrite and vH == 0 means Hv == H && Wv == W; the phase form (up2) rewrites
-// (Hv, Wv) to (H, W) on both sides.  LNS_NO_ARITH_MAPS (A/B knob: table reads everywhere) is read once per process.
+// (Hv, Wv) to (H, W) on both sides.  LNS_NO_ARITH_MAPS (A/B knob): table reads everywhere.
 inline void conv_set_map_arith(ConvArgs& a, int variant, int k, int Hin, int Win, int Hv, int Wv, const int* pad, int my, int mx) {
-    static const bool no_arith = getenv("LNS_NO_ARITH_MAPS") != nullptr;
-    if (no_arith || k != 3 || Hv != Hin || Wv != Win || !cv_is_split_3x3(variant)) return;
+    if (knobs().no_arith_maps || k != 3 || Hv != Hin || Wv != Win || !cv_is_split_3x3(variant)) return;
     if (pad[0] > Hin || pad[1] > Hin || pad[2] > Win || pad[3] > Win) return;
     if ((my != LNS_PAD_ZEROS && my != LNS_PAD_CIRCULAR) || (mx != LNS_PAD_ZEROS && mx != LNS_PAD_CIRCULAR)) return;
     a.map_arith = 1;

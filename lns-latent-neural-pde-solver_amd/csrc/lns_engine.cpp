@@ -80,8 +80,9 @@ struct GnTileRule {
 static bool gn_tile_rule(GnTileRule& r, const ConvArgs& c, int variant, int H, int W, int groups, bool premul, int B, size_t stat_cap) {
     // From 16 x 16 planes up (two 128-pixel tiles): below 1024 pixels the merge launch used to cost what the statistics
     // launch cost, but the merge now happens inside the consumer convolution (no launch at all) whenever it can.
-    static const bool no_fold = getenv("LNS_GN_NO_FOLD") != nullptr;        // A/B knob: round 2's behaviour
-    static const long min_hw = getenv("LNS_GN_FUSE_MIN_HW") ? atol(getenv("LNS_GN_FUSE_MIN_HW")) : (no_fold ? 1024 : 256);
+    const Knobs& kn = knobs();
+    const bool no_fold = kn.gn_no_fold;        // A/B knob: round 2's behaviour
+    const long min_hw = kn.gn_fuse_min_hw;     // (256; 1024 under LNS_GN_NO_FOLD)
     // producers with the statistics epilogue: the split-operand 3x3 kernels and the streaming 1x1 kernel (not its
     // input-stationary form, not with a fused second conv: its statistics would be taken of the wrong tensor... they
     // are taken of what is stored, which is right -- but only the plain form is covered by tests:
@@ -90,11 +91,11 @@ static bool gn_tile_rule(GnTileRule& r, const ConvArgs& c, int variant, int H, i
     // two-pass statistics over the valid pixels (ConvArgs::stat_count) -- the three statistics launches per conditional
     // block were a quarter of config 4's dependency chain.  A per-sample channel multiplier (premul) is applied
     // to the partials by whoever merges them.
-    static const bool no_ragged = getenv("LNS_GN_NO_RAGGED") != nullptr;
+    const bool no_ragged = kn.gn_no_ragged;
     const bool ragged1 = !no_fold && !no_ragged && !c.up2 && c.tiles_x * c.tiles_y == 1 && H * W < GN_TILE_PIXELS;
     // ... and planes whose 128-pixel tiles do not cover them exactly (14 x 30, 28 x 60, 61 x 121 in the two-phase decoder):
     // every block counts its own valid pixels, the finalize kernel merges partials of unequal counts (never folded)
-    static const bool no_ragged_tiles = getenv("LNS_GN_NO_RAGGED_TILES") != nullptr;
+    const bool no_ragged_tiles = kn.gn_no_ragged_tiles;
     const bool raggedN = !no_fold && !no_ragged && !no_ragged_tiles && !c.up2 && !ragged1 && H * W > GN_TILE_PIXELS;
     const bool prod_ok = variant == CV_F64 || variant == CV_F32 || variant == CV_B64 ||
                          (variant == CV_B1 && !no_fold && c.ct_per_block == 0 && !c.w2 &&
@@ -110,7 +111,7 @@ static bool gn_tile_rule(GnTileRule& r, const ConvArgs& c, int variant, int H, i
     if (!(exact || ragged1 || raggedN) || (size_t)B * tiles * c.Cout * 8 > stat_cap) return false;
     // foldable into the consumer's prologue: few tiles, one group or power-of-two groups within a wave
     const int cg = c.Cout / groups;
-    static const int fold_tiles = getenv("LNS_GN_FOLD_TILES") ? atoi(getenv("LNS_GN_FOLD_TILES")) : 2;
+    const int fold_tiles = (int)kn.gn_fold_tiles;
     // (a per-sample channel multiplier is applied by stage_ss_from_partials in its one-group branch only:
     //  with several groups the finalize kernel, which handles premul for any grouping, runs instead)
     r.foldable = !no_fold && (exact || ragged1) && tiles <= fold_tiles && c.Cout <= 512 && (!premul || groups == 1) &&
@@ -288,8 +289,7 @@ struct Planner {
     uint64_t stat_scratch = 0;
     size_t stat_cap = 0;
     void init_stat_scratch() {
-        static const bool off = getenv("LNS_GN_NO_FUSE") != nullptr;
-        if (off) return;
+        if (knobs().gn_no_fuse) return;
         stat_cap = (size_t)B * 128 * e->cfg.Ly * e->cfg.Lx / GN_TILE_PIXELS * 8;   // C * H * W <= 128 * Ly * Lx
         // (a propagator-only engine has no field size: room for what the latent chain folds, <= 4 tiles x 512 channels,
         //  so that it takes the same per-layer decisions -- the same bits -- as the propagator inside a full model)
@@ -426,34 +426,43 @@ struct Planner {
     // fused conv; consumes the pending transforms of `in`
     // fuse_pack >= 0: a following 1x1 conv (64 -> 64) applied in the epilogue of this one
     static bool can_fuse_1x1(const ConvPack& first, const ConvPack& second) {
-        static const bool off = getenv("LNS_NO_FUSE_1X1") != nullptr;
-        return !off && first.cout == 64 && second.k == 1 && second.cin == 64 && second.cout == 64;
+        return !knobs().no_fuse_1x1 && first.cout == 64 && second.k == 1 && second.cin == 64 && second.cout == 64;
     }
-    TRef emit_conv(const TRef& in, int pack_id, int k, int stride, int dil, const int* pad, int my, int mx,
-                   int act_out, const TRef* res, uint64_t badd, const TRef* out_forced, const std::string& name,
-                   int fuse_pack = -1, bool want_amax = true) {
-        const ConvPack& pk = e->packs[pack_id];
-        if (pk.cin != in.C) throw std::runtime_error(fmt("%s: input has %d channels, conv expects %d", name.c_str(), in.C, pk.cin));
-        int Hv = in.vH ? in.vH : in.H, Wv = in.vW ? in.vW : in.W;
+    // (i) the kernel form of a conv launch, from the layer's facts and the process switches alone: the tiling, the form of the
+    // upsampling conv (ConvArgs::up2: 0 none, 1 one block per output phase, 2 resident patch, 3 quad phase, 4 dual phase)
+    // and the input-stationary 1x1's cout tiles per block.  Hv x Wv: the plane the convolution sees (the phase form: the
+    // source).  Every switch read of a conv launch is here; throws before anything is allocated or emitted.
+    struct ConvForm { ConvGeom g; int up2, ct_per_block, Hv, Wv; };
+    static ConvForm conv_form(const ConvPack& pk, const TRef& in, int B, int k, int stride, int dil, const int* pad, int act_out,
+                              bool has_res, bool has_badd, bool fused, bool up2_dual, const std::string& name) {
+        const Knobs& kn = knobs();
+        ConvForm f;
+        f.Hv = in.vH ? in.vH : in.H; f.Wv = in.vW ? in.vW : in.W;
         // 3x3 over an exactly 2x nearest-upsampled tensor: the phase-decomposed four-tap form (conv3_bf16x3_kernel, NTAP = 4)
         // -- tiles, patch and maps are those of a plain pad-1 3x3 convolution of the SOURCE; a per-layer rule
-        static const bool fp32_only = getenv("LNS_CONV_FP32_MFMA") != nullptr;     // (strict-fp32 runs: no split-operand kernels)
+        // (LNS_CONV_FP32_MFMA, strict-fp32 runs: no split-operand kernels)
         const bool up2 = k == 3 && stride == 1 && dil == 1 && in.vH == 2 * in.H && in.vW == 2 * in.W && pk.has_wu && pk.f16 &&
-                         pad[0] == 1 && pad[1] == 1 && pad[2] == 1 && pad[3] == 1 && in.bounded() && pk.cout > 32 && !fp32_only;
-        if (up2) { Hv = in.H; Wv = in.W; }
-        ConvGeom g;
-        const bool thin_ok = !res && !badd && act_out == ACT_NONE && fuse_pack < 0 && !in.vH &&
+                         pad[0] == 1 && pad[1] == 1 && pad[2] == 1 && pad[3] == 1 && in.bounded() && pk.cout > 32 && !kn.conv_fp32_mfma;
+        if (up2) { f.Hv = in.H; f.Wv = in.W; }
+        ConvGeom& g = f.g;
+        const bool thin_ok = !has_res && !has_badd && act_out == ACT_NONE && !fused && !in.vH &&
                              (in.act == ACT_NONE || (in.act == ACT_SWISH && in.ss != 0));
         // split-operand kernels only where the input carries a bound for the dynamic activation scale (tensors
         // handed in by the caller do not: those few convolutions stay on the fp32 matrix instruction)
         auto tiling = [&](ConvGeom& gg, int force_variant, int force_bw_log2 = -1) {
-            return conv_geometry(gg, B, pk.cout, Hv, Wv, k, stride, dil, pad, pk.kc_log2, pk.Cout_pad, force_variant, fuse_pack >= 0,
+            return conv_geometry(gg, B, pk.cout, f.Hv, f.Wv, k, stride, dil, pad, pk.kc_log2, pk.Cout_pad, force_variant, fused,
                                  pk.has_wb && in.bounded(), pk.cin, pk.f16, thin_ok, force_bw_log2);
         };
         if (!tiling(g, -1)) throw std::runtime_error("no conv tiling for " + name);
         if (up2 && g.variant == CV_F32 && !tiling(g, CV_F64))      // (a small launch: the phase form exists for 64-cout tiles only)
             throw std::runtime_error("no conv tiling for " + name);
         if (up2 && g.variant != CV_F64) throw std::runtime_error("phase form needs the f16x2 64-cout tiles: " + name);
+        // what the forms' predicates (convuq_fits, convur_fits, convud_fits) read of a launch
+        ConvArgs probe;
+        memset(&probe, 0, sizeof probe);
+        probe.ks = 3; probe.stride = 1; probe.dil = 1; probe.up2 = 1; probe.wb = &probe; probe.Cin_pad = pk.Cin_pad;
+        probe.Cout = pk.cout; probe.Hout = 2 * in.H; probe.Wout = 2 * in.W;
+        if (has_res) probe.res = reinterpret_cast<const float*>(&probe);
         // Round 4: the quad-phase form of the upsampling conv (conv3_up2q.inc: the patch staged once, four phases per block,
         // two blocks per CU) wants 8 x 16 source tiles -- a 10 x 18 patch of 8 stages is what fits beside its weight ring in
         // 80 KB.  MEASURED (profiles/r04_up2q_time.txt): the plain 64 -> 64 layer at 128^2 213.5 -> 197.6 us, but the layer the
@@ -461,24 +470,80 @@ struct Planner {
         // SIMD) and the 64-channel UpSampleBlock conv 48.5 -> 49.0 us: rollout 34.6k -> 34.3k.  Opt-in (LNS_UP2_QUAD=1) in
         // -DLNS_EXPERIMENTAL builds only; a per-layer rule (Cin_pad in {16, 32, 48, 64}, no residual, the tiling exists).
         bool quad = false;
-        {
-            static const bool no_quad = getenv("LNS_UP2_QUAD") == nullptr || getenv("LNS_UP2_RESIDENT") != nullptr;
-            ConvGeom gq;
-            if (up2 && !no_quad && !res && pk.Cin_pad <= 64 && pk.Cin_pad % 16 == 0 && tiling(gq, CV_F64, 4)) {
-                ConvArgs t;
-                memset(&t, 0, sizeof t);
-                t.ks = 3; t.stride = 1; t.dil = 1; t.up2 = 1; t.wb = &t; t.Cin_pad = pk.Cin_pad; t.PH = gq.PH; t.PW = gq.PW;
-                t.Cout = pk.cout; t.Hout = 2 * in.H; t.Wout = 2 * in.W;
-                if (convuq_fits(t)) { g = gq; quad = true; }
-            }
+        ConvGeom gq;
+        if (up2 && kn.up2_quad && !has_res && pk.Cin_pad <= 64 && pk.Cin_pad % 16 == 0 && tiling(gq, CV_F64, 4)) {
+            probe.PH = gq.PH; probe.PW = gq.PW;
+            if (convuq_fits(probe)) { g = gq; quad = true; }
         }
-        // (thrown before anything is allocated or emitted: a caller may catch it and materialise the activation instead)
-        if (in.act == ACT_GELU && ((g.variant != CV_F64 && g.variant != CV_F32) || up2 || fuse_pack >= 0))
+        if (in.act == ACT_GELU && ((g.variant != CV_F64 && g.variant != CV_F32) || up2 || fused))
             throw NoGeluPrologue("GELU prologue is only built into the f16x2 3x3 kernel: " + name);
-        if (up2) { g.Hout = 2 * in.H; g.Wout = 2 * in.W; }
+        f.up2 = 0;
+        if (up2) {
+            g.Hout = 2 * in.H; g.Wout = 2 * in.W;
+            probe.PH = g.PH; probe.PW = g.PW;
+            f.up2 = 1;
+            // narrow inputs: the split patch of ALL channels can stay in LDS while one block walks the four phases (same
+            // bits, conv3_up2r.inc).  Measured SLOWER (fused 128^2 layer 294 - 299 vs 215 us, rollout 31.9k vs 33.4k): at
+            // 147 KB of LDS a CU holds one block, and nothing overlaps its prologue, four epilogues and weight copies.
+            // Kept as an opt-in variant (LNS_UP2_RESIDENT=1) with its parity tests.
+            if (kn.up2_resident && convur_fits(probe)) f.up2 = 2;
+            if (quad) f.up2 = 3;
+            // the dual-phase form (conv3_up2d.inc: one block per source tile and row phase computes both column phases --
+            // the patch staged once for the two, 8-byte stores of pixel pairs; same bits): a per-layer rule, "up2_dual"
+            // (no fused 1x1)
+            if (f.up2 == 1 && !fused && up2_dual && convud_fits(probe)) f.up2 = 4;
+        }
+        f.ct_per_block = 0;
+        if (g.variant == CV_B1 && pk.Cin_pad <= 64 && g.cout_tiles >= 2 && !fused && !kn.conv1_no_stationary) {
+            // input-stationary form; the number of cout tiles per block only changes the launch shape, never a bit:
+            // as many cout tiles per block as still leave this many blocks (three fit a CU): LNS_CONV1S_MIN_BLOCKS
+            int cpb = g.cout_tiles;
+            while (cpb > 2 && (long)B * g.tiles_x * ((g.cout_tiles + cpb - 1) / cpb) < kn.conv1s_min_blocks) cpb = (cpb + 1) / 2;
+            f.ct_per_block = cpb;
+        }
+        return f;
+    }
+    // (iii) what the launch costs and what it is called: nominal FLOP, bytes, executed matrix-pipe FLOP (every block runs whole
+    // tiles, whole channel stages and whole tap slots), the form label of timing()
+    static void conv_account(Op& op, const ConvForm& f, const ConvPack& pk, const TRef& in, int B, int k, bool has_res, bool fused) {
+        const ConvGeom& g = f.g;
         const ConvVariantInfo vi = conv_variant_info(g.variant);
+        const bool up2 = f.up2 != 0;
+        op.flops = 2.0 * B * g.Hout * g.Wout * (double)pk.cout * pk.cin * k * k + (fused ? 2.0 * B * g.Hout * g.Wout * 64.0 * 64.0 : 0.0);
+        op.bytes = 4.0 * B * ((double)in.C * in.H * in.W + (double)pk.cout * g.Hout * g.Wout * (has_res ? 2 : 1));
+        const double tiles = (double)B * g.tiles_x * g.tiles_y * g.cout_tiles * vi.TM * vi.TN;
+        if (cv_is_f16x2_3x3(g.variant)) {           // 3 products; 10 tap slots for 9 taps, or 4 phases x 4 taps
+            op.mfma_flops = tiles * pk.Cin_pad * (up2 ? 4.0 * 4.0 : 10.0) * 3.0 * 2.0;
+            op.form = up2 ? (fused ? "f16x2 3x3 four-tap phase form + fused 1x1" : "f16x2 3x3 four-tap phase form")
+                          : (fused ? "f16x2 3x3 nine-tap + fused 1x1" : "f16x2 3x3 nine-tap");
+            if (fused) op.mfma_flops += tiles * (up2 ? 4.0 : 1.0) * 64.0 * 3.0 * 2.0;
+        } else if (g.variant == CV_B64 || g.variant == CV_B32) {
+            op.mfma_flops = tiles * pk.Cin_pad * 10.0 * 6.0 * 2.0; op.form = "bf16x3 3x3 nine-tap";
+        } else if (g.variant == CV_B1) {
+            const int cp32 = (pk.Cin_pad + 31) / 32 * 32;
+            op.mfma_flops = tiles * cp32 * (convb1_is_f16() ? 3.0 : 6.0) * 2.0;
+            op.form = f.ct_per_block ? "f16x2 1x1 input-stationary" : (fused ? "f16x2 1x1 + fused 1x1" : "f16x2 1x1 streaming");
+            if (fused) op.mfma_flops += tiles * 64.0 * 3.0 * 2.0;
+        } else if (g.variant == CV_THIN) {
+            op.form = "thin 1x1 projection (VALU)";
+        } else {
+            op.mfma_flops = tiles * pk.Cin_pad * (double)(k * k) * 2.0 + (fused ? tiles * 64.0 * 2.0 : 0.0);
+            op.form = k == 3 ? "fp32 MFMA 3x3" : "fp32 MFMA 1x1";
+        }
+    }
+    TRef emit_conv(const TRef& in, int pack_id, int k, int stride, int dil, const int* pad, int my, int mx,
+                   int act_out, const TRef* res, uint64_t badd, const TRef* out_forced, const std::string& name,
+                   int fuse_pack = -1, bool want_amax = true) {
+        const ConvPack& pk = e->packs[pack_id];
+        if (pk.cin != in.C) throw std::runtime_error(fmt("%s: input has %d channels, conv expects %d", name.c_str(), in.C, pk.cin));
+        // (i) -- thrown before anything is allocated or emitted: a caller may catch NoGeluPrologue and materialise the activation
+        const ConvForm f = conv_form(pk, in, B, k, stride, dil, pad, act_out, res != nullptr, badd != 0, fuse_pack >= 0,
+                                     e->opt_up2_dual != 0, name);
+        const ConvGeom& g = f.g;
+        const bool up2 = f.up2 != 0;
+        // (ii) the launch arguments
         std::vector<int> rm, cm;
-        if (k == 3) conv_tile_maps(rm, cm, g, stride, in.H, in.W, Hv, Wv, up2 ? 0.0f : in.sch, up2 ? 0.0f : in.scw, pad, my, mx);
+        if (k == 3) conv_tile_maps(rm, cm, g, stride, in.H, in.W, f.Hv, f.Wv, up2 ? 0.0f : in.sch, up2 ? 0.0f : in.scw, pad, my, mx);
         else if (in.vH) throw std::runtime_error("1x1 conv of a resized tensor is not supported: " + name);
         TRef out;
         if (out_forced) out = *out_forced;
@@ -497,16 +562,8 @@ struct Planner {
         a.y = as_ptr<float>(out.ptr); a.y_bs = out.bs;
         a.w = as_ptr<const float>(wt(pk.w_off));
         if (g.variant >= CV_B64) a.wb = as_ptr<const void>(wt(up2 ? pk.wu_off : pk.wb_off));   // CV_B32 included
-        a.up2 = up2 ? 1 : 0;
-        if (g.variant == CV_B1 && pk.Cin_pad <= 64 && g.cout_tiles >= 2 && fuse_pack < 0) {
-            // input-stationary form; the number of cout tiles per block only changes the launch shape, never a bit
-            static const bool off = getenv("LNS_CONV1_NO_STATIONARY") != nullptr;
-            // ... as many cout tiles per block as still leave this many blocks (three fit a CU): LNS_CONV1S_MIN_BLOCKS
-            static const long want = getenv("LNS_CONV1S_MIN_BLOCKS") ? atol(getenv("LNS_CONV1S_MIN_BLOCKS")) : 512;
-            int cpb = g.cout_tiles;
-            while (cpb > 2 && (long)B * g.tiles_x * ((g.cout_tiles + cpb - 1) / cpb) < want) cpb = (cpb + 1) / 2;
-            if (!off) a.ct_per_block = cpb;
-        }
+        a.up2 = f.up2;
+        a.ct_per_block = f.ct_per_block;
         a.bias = pk.has_bias ? as_ptr<const float>(wt(pk.b_off)) : nullptr;
         a.ss = as_ptr<const float>(in.ss);
         if (in.gn_lazy >= 0 && !lazy_done[in.gn_lazy]) {
@@ -524,7 +581,7 @@ struct Planner {
         if (k == 3) {
             a.rowmap = as_ptr<const int>(const_ints(rm));
             a.colmap = as_ptr<const int>(const_ints(cm));
-            conv_set_map_arith(a, g.variant, k, in.H, in.W, Hv, Wv, pad, my, mx);
+            conv_set_map_arith(a, g.variant, k, in.H, in.W, f.Hv, f.Wv, pad, my, mx);
         }
         if (res) { a.res = as_ptr<const float>(res->ptr); a.res_bs = res->bs; }
         a.badd = as_ptr<const float>(badd);
@@ -538,42 +595,6 @@ struct Planner {
         // a tensor written to a caller's buffer (the plan's output) is always recorded: nobody scales by it, but
         // lns_check_finite must see a NaN born in the last layer as well
         if ((want_amax && g.variant != CV_THIN) || out_forced) { out.amax = new_amax(name); a.amax_out = as_ptr<unsigned>(out.amax); }
-        if (up2) {
-            // narrow inputs: the split patch of ALL channels can stay in LDS while one block walks the four phases (same
-            // bits, conv3_up2r.inc).  Measured SLOWER (fused 128^2 layer 294 - 299 vs 215 us, rollout 31.9k vs 33.4k): at
-            // 147 KB of LDS a CU holds one block, and nothing overlaps its prologue, four epilogues and weight copies.
-            // Kept as an opt-in variant (LNS_UP2_RESIDENT=1) with its parity tests.
-            static const bool res = getenv("LNS_UP2_RESIDENT") != nullptr;
-            if (res) { a.up2 = 2; if (!convur_fits(a)) a.up2 = 1; }
-            if (quad && convuq_fits(a)) a.up2 = 3;
-            // the dual-phase form (conv3_up2d.inc: one block per source tile and row phase computes both column phases --
-            // the patch staged once for the two, 8-byte stores of pixel pairs; same bits): a per-layer rule, "up2_dual"
-            // (no fused 1x1: ConvArgs::w2 is set below)
-            if (a.up2 == 1 && fuse_pack < 0 && e->opt_up2_dual && convud_fits(a)) a.up2 = 4;
-        }
-        op.flops = 2.0 * B * g.Hout * g.Wout * (double)pk.cout * pk.cin * k * k;
-        op.bytes = 4.0 * B * ((double)in.C * in.H * in.W + (double)pk.cout * g.Hout * g.Wout * (res ? 2 : 1));
-        {   // executed matrix-pipe FLOP of the launch: every block runs whole tiles, whole channel stages and whole tap slots
-            const double tiles = (double)B * g.tiles_x * g.tiles_y * g.cout_tiles * vi.TM * vi.TN;
-            if (cv_is_f16x2_3x3(g.variant)) {           // 3 products; 10 tap slots for 9 taps, or 4 phases x 4 taps
-                op.mfma_flops = tiles * pk.Cin_pad * (up2 ? 4.0 * 4.0 : 10.0) * 3.0 * 2.0;
-                op.form = up2 ? (fuse_pack >= 0 ? "f16x2 3x3 four-tap phase form + fused 1x1" : "f16x2 3x3 four-tap phase form")
-                              : (fuse_pack >= 0 ? "f16x2 3x3 nine-tap + fused 1x1" : "f16x2 3x3 nine-tap");
-                if (fuse_pack >= 0) op.mfma_flops += tiles * (up2 ? 4.0 : 1.0) * 64.0 * 3.0 * 2.0;
-            } else if (g.variant == CV_B64 || g.variant == CV_B32) {
-                op.mfma_flops = tiles * pk.Cin_pad * 10.0 * 6.0 * 2.0; op.form = "bf16x3 3x3 nine-tap";
-            } else if (g.variant == CV_B1) {
-                const int cp32 = (pk.Cin_pad + 31) / 32 * 32;
-                op.mfma_flops = tiles * cp32 * (convb1_is_f16() ? 3.0 : 6.0) * 2.0;
-                op.form = a.ct_per_block ? "f16x2 1x1 input-stationary" : (fuse_pack >= 0 ? "f16x2 1x1 + fused 1x1" : "f16x2 1x1 streaming");
-                if (fuse_pack >= 0) op.mfma_flops += tiles * 64.0 * 3.0 * 2.0;
-            } else if (g.variant == CV_THIN) {
-                op.form = "thin 1x1 projection (VALU)";
-            } else {
-                op.mfma_flops = tiles * pk.Cin_pad * (double)(k * k) * 2.0 + (fuse_pack >= 0 ? tiles * 64.0 * 2.0 : 0.0);
-                op.form = k == 3 ? "fp32 MFMA 3x3" : "fp32 MFMA 1x1";
-            }
-        }
         if (fuse_pack >= 0) {
             const ConvPack& p2 = e->packs[fuse_pack];
             if (!can_fuse_1x1(pk, p2)) throw std::runtime_error("cannot fuse 1x1 into " + name);
@@ -586,8 +607,8 @@ struct Planner {
                     for (float v : e->params[e->pindex.at(key)].host) mx = std::max(mx, fabsf(v));
                 a.w2scale = (mx > 0.0f && std::isfinite(mx)) ? conv_f16_weight_scale(mx) : 1.0f;
             }
-            op.flops += 2.0 * B * g.Hout * g.Wout * 64.0 * 64.0;
         }
+        conv_account(op, f, pk, in, B, k, res != nullptr, fuse_pack >= 0);      // (iii)
         plan->ops.push_back(op);
         return out;
     }
@@ -653,7 +674,7 @@ struct Planner {
             op.at.amax_in = qkv.amax ? as_ptr<const unsigned>(qkv.amax) : nullptr;
             op.flops = 4.0 * B * l.heads * (double)n * n * l.dim_head;
             {
-                const bool f16 = op.at.amax_in != nullptr && getenv("LNS_ATTN_FP32") == nullptr;
+                const bool f16 = attn_is_f16(op.at);
                 const double np_ = (n + 31) / 32 * 32;
                 op.mfma_flops = 4.0 * B * l.heads * np_ * np_ * l.dim_head * (f16 ? 3.0 : 1.0);
                 op.form = f16 ? "f16x2 attention" : "fp32 MFMA attention";
@@ -716,9 +737,9 @@ struct Planner {
         emit_gn(xin, 1, 1e-5f, l.fa_g, l.fa_b, 0, l.name + ".in_norm");
         // in_proj records max |u| per sample: the sandwich's f16x2 form scales its planes by it
         // round 4: in_proj inside the sandwich kernel (fa_fused.inc) -- the plane tensor is only ever the sandwich's OUTPUT
-        static const bool fused_off = getenv("LNS_FA_SANDWICH_FP32") != nullptr || getenv("LNS_CONV_FP32_MFMA") != nullptr ||
-                                      getenv("LNS_CONV1_FP32_MFMA") != nullptr || getenv("LNS_FA_SANDWICH_BF16X3") != nullptr;
-        static const bool no_small = getenv("LNS_FA_FUSED_NO_SMALL") != nullptr;      // A/B knob: only the 64 x 64 block
+        const Knobs& kn = knobs();
+        const bool fused_off = kn.fa_sandwich_fp32 || kn.conv_fp32_mfma || kn.conv1_fp32_mfma || kn.fa_sandwich_bf16x3;
+        const bool no_small = kn.fa_fused_no_small;      // A/B knob: only the 64 x 64 block
         const bool fused_in = e->opt_fa_fused && !fused_off && fa_fused_fits(H, W, C, dh) && !(no_small && H < 64) && !e->packs[l.inproj].has_bias &&
                               e->packs[l.inproj].cout == heads * dh && xin.ss != 0 && xin.gn_bound > 0.0f;
         TRef uphi;
@@ -758,13 +779,12 @@ struct Planner {
         }
         // (chunked: in_proj is re-issued AFTER the pooling / reducer / low-rank ops, so the GroupNorm table it reads must
         //  outlive their allocations)
-        const bool fused_out = getenv("LNS_FA_NO_FUSE_TO_OUT") == nullptr && can_fuse_1x1(e->packs[l.out1], e->packs[l.out3]);
+        const bool fused_out = !kn.fa_no_fuse_to_out && can_fuse_1x1(e->packs[l.out1], e->packs[l.out3]);
         const bool will_chunk = !fused_in && fused_out && fa_chunk_samples((size_t)heads * dh * H * W * 4) > 0;
         if (!will_chunk) free_t(xin);
         // PoolingReducer of both axes in ONE launch, rotary + q k^T of both axes in one more
         // (LNS_FA_NO_MERGE restores one launch per axis)
-        static const bool no_merge = getenv("LNS_FA_NO_MERGE") != nullptr;
-        const bool merge = !no_merge && fa_reducer_fits(C, 2 * C, lat, true);
+        const bool merge = !kn.fa_no_merge && fa_reducer_fits(C, 2 * C, lat, true);
         // no form for this shape: say so here, by name, not at the first launch
         if (!merge && !fa_reducer_fits(C, 2 * C, lat, false))
             throw std::runtime_error(l.name + ": no PoolingReducer kernel for " + fa_axis_limits(C, 2 * C, lat));
@@ -859,8 +879,7 @@ struct Planner {
             op.ff.kx = as_ptr<const float>(tag(SP_WS, kx_off)); op.ff.ky = as_ptr<const float>(tag(SP_WS, ky_off));
             op.ff.B = B; op.ff.heads = heads; op.ff.C = dh; op.ff.Cin = C; op.ff.H = H; op.ff.W = W; op.ff.eps = 1e-5f; op.ff.instnorm = 1;
             op.ff.out = as_ptr<float>(uphi.ptr);
-            static const bool no_rev = getenv("LNS_FA_NO_REVERSE") != nullptr;
-            op.ff.b_rev = no_rev ? 0 : 1;
+            op.ff.b_rev = kn.fa_no_reverse ? 0 : 1;
             op.ff.single_buffer = e->opt_fa_fused == 1 ? 1 : (e->opt_fa_fused == 3 ? 2 : 0);
             // plane groups per block (scheduling only; "fa_fused_gpb" / LNS_FA_FUSED_GPB)
             op.ff.gpb = fa_fused_gpb_rule(e->opt_fa_fused_gpb, dh / 16, B, heads);
@@ -877,15 +896,22 @@ struct Planner {
             op.fs.ky = as_ptr<const float>(tag(SP_WS, ky_off)); op.fs.B = B; op.fs.heads = heads; op.fs.C = dh;
             op.fs.H = H; op.fs.W = W; op.fs.eps = 1e-5f; op.fs.instnorm = 1; op.fs.out = as_ptr<float>(uphi.ptr);
             op.fs.amax_u = uphi.amax ? as_ptr<const unsigned>(uphi.amax) : nullptr;
-            static const bool no_rev = getenv("LNS_FA_NO_REVERSE") != nullptr;
-            op.fs.b_rev = no_rev ? 0 : 1;
+            op.fs.b_rev = kn.fa_no_reverse ? 0 : 1;
             op.flops = 2.0 * B * heads * dh * ((double)H * W * W + (double)H * H * W);
             op.bytes = 8.0 * B * heads * dh * H * W;
-            {   // 32 x 32 tiles; f16x2 form (three products) for planes of <= 96 columns with a recorded max |u|, else fp32 MFMA
+            {   // 32 x 32 tiles; the kernel is the launcher's choice (fa_sandwich_form): products per MFMA tile f16x2 3,
+                // bf16x3 6 (fa_sandwich_b_kernel: hh, hm, mh, mm, hl, lh for U and again for Y), fp32 MFMA 1
                 const double Hp = (H + 31) / 32 * 32, Wp = (W + 31) / 32 * 32;
-                const bool f16 = op.fs.amax_u != nullptr && W <= 96 && getenv("LNS_FA_SANDWICH_FP32") == nullptr;
-                op.mfma_flops = 2.0 * B * heads * dh * (Hp * Wp * Wp + Hp * Hp * Wp) * (f16 ? 3.0 : 1.0);
-                op.form = f16 ? "f16x2 FABlock sandwich" : "fp32 MFMA FABlock sandwich";
+                double products = 1.0;
+                switch (fa_sandwich_form(op.fs)) {
+                    case FA_SAND_F16X2: products = 3.0; op.form = "f16x2 FABlock sandwich"; break;
+                    case FA_SAND_BF16X3: products = 6.0; op.form = "bf16x3 FABlock sandwich"; break;
+                    case FA_SAND_BF16X3_3WAVE: products = 6.0; op.form = "bf16x3 FABlock sandwich (three waves)"; break;
+                    case FA_SAND_FP32: op.form = "fp32 MFMA FABlock sandwich"; break;
+                    default:      // no kernel for this shape: say so here, by name, not at the first launch
+                        throw std::runtime_error(l.name + fmt(": no FABlock sandwich kernel for %d x %d planes (32 x 32 tiles: 1x1, 1x2, 2x1, 2x2, 2x3)", H, W));
+                }
+                op.mfma_flops = 2.0 * B * heads * dh * (Hp * Wp * Wp + Hp * Hp * Wp) * products;
             }
             plan->ops.push_back(op);
         }
@@ -895,8 +921,7 @@ struct Planner {
         // InstanceNorm output (biased variance over H*W values): |y| <= sqrt(H*W - 1)
         uphi.amax = 0; uphi.amax_const = sqrtf((float)(H * W));
         TRef out;
-        static const bool no_fuse_out = getenv("LNS_FA_NO_FUSE_TO_OUT") != nullptr;      // tuning knob (measured: fused wins)
-        if (!no_fuse_out && can_fuse_1x1(e->packs[l.out1], e->packs[l.out3])) {
+        if (fused_out) {      // (LNS_FA_NO_FUSE_TO_OUT: tuning knob; measured: fused wins)
             // to_out.1 (512 -> 64, GELU) and to_out.3 (64 -> 64) + skip in ONE kernel
             out = conv_same1(uphi, l.out1, ACT_GELU, &x, nullptr, l.name + ".to_out.1+3", l.out3, raw_out);
             free_t(uphi);
@@ -1060,7 +1085,7 @@ struct Planner {
         emit_gn(h2, 1, 1e-5f, l.c_g, l.c_b, 0, q + ".cond_conv1.0");
         // GroupNorm -> GELU -> conv: the f16x2 3x3 kernel applies both in its prologue (mode 3); any other kernel gets the
         // materialised tensor (round 2's form, LNS_NO_GELU_PROLOGUE=1)
-        static const bool no_gelu_pro = getenv("LNS_NO_GELU_PROLOGUE") != nullptr || getenv("LNS_CONV_FP32_MFMA") != nullptr;   // (strict-fp32 runs have no split-operand kernels)
+        const bool no_gelu_pro = knobs().no_gelu_prologue || knobs().conv_fp32_mfma;   // (strict-fp32 runs have no split-operand kernels)
         const ConvPack& cpk = e->packs[l.c_conv];
         TRef x1;
         bool fused_gelu = false;
@@ -1243,8 +1268,7 @@ static int finalize_weights(lns_engine* e, int device) {
             p.wb_off = off;
             off += round_up_sz((p.k == 3 ? convb_weight_bytes(p.cout, p.Cin_pad) : convb1_weight_bytes(p.cout, p.Cin_pad)) / 4, 64);
         }
-        static const bool no_up2 = getenv("LNS_NO_UP2_PHASES") != nullptr;       // A/B knob: the nine-tap gather form everywhere
-        p.has_wu = p.up2 && p.has_wb && p.k == 3 && !no_up2;
+        p.has_wu = p.up2 && p.has_wb && p.k == 3 && !knobs().no_up2_phases;       // (A/B knob: the nine-tap gather form everywhere)
         if (p.has_wu) { p.wu_off = off; off += round_up_sz(convu_weight_bytes(p.cout, p.Cin_pad) / 4, 64); }
     }
     for (VecPack& v : e->vecs) { v.off = off; off += round_up_sz(v.count, 64); }
@@ -1265,7 +1289,7 @@ static int finalize_weights(lns_engine* e, int device) {
     }
     // 3x3 convs: two-term fp16 split (f16x2) unless LNS_CONV3_SPLIT=bf16x3; the weight scale is the power of two
     // that brings the largest |w| of the layer just below 2^14
-    static const bool conv3_f16 = !(getenv("LNS_CONV3_SPLIT") && strcmp(getenv("LNS_CONV3_SPLIT"), "bf16x3") == 0);
+    const bool conv3_f16 = knobs().conv3_split == CONV3_SPLIT_F16X2;
     for (ConvPack& p : e->packs) {
         p.f16 = false; p.wscale = 1.0f;
         const bool want = p.has_wb && ((p.k == 3 && conv3_f16) || (p.k == 1 && convb1_is_f16()));
@@ -1574,8 +1598,7 @@ struct Runner {
             }
             {   // LNS_DEBUG_SYNC=1 (diagnosis of a device fault): name every launch on stderr and wait for it, so that the last
                 // line printed names the kernel that faulted
-                static const bool dbg_sync = getenv("LNS_DEBUG_SYNC") != nullptr;
-                if (dbg_sync && op.type != OP_TRACE) {
+                if (knobs().debug_sync && op.type != OP_TRACE) {
                     fprintf(stderr, "[lns] %s (plan B=%d, chunk b0=%d nb=%d)\n", op.name.c_str(), plan.B,
                             op.type == OP_CONV ? op.conv.b0 : (op.type == OP_FASAND ? op.fs.b0 : 0),
                             op.type == OP_CONV ? op.conv.B : (op.type == OP_FASAND ? op.fs.B : plan.B));
@@ -1595,7 +1618,7 @@ struct Runner {
     int finish() {
         if (!e->timing_on || evs.empty()) return LNS_OK;
         HIPCHK(e, hipStreamSynchronize(stream));
-        static const bool by_name = getenv("LNS_TIMING_BY_NAME") != nullptr;   // per-layer breakdown for profiling
+        const bool by_name = knobs().timing_by_name;   // per-layer breakdown for profiling
         if (e->timing.empty() && !by_name) {
             e->timing.resize(CLS_COUNT);
             for (int i = 0; i < CLS_COUNT; ++i) e->timing[i].name = kClsName[i];
@@ -1946,15 +1969,18 @@ int lns_create(const lns_config* cfg, lns_engine** out) {
     if (cfg->abi_version != LNS_ABI_VERSION) { g_create_error = "ABI version mismatch"; return LNS_EINVAL; }
     lns_engine* e = new lns_engine();
     e->cfg = *cfg;
-    if (const char* v = getenv("LNS_DECODE_GROUP")) e->opt_decode_group = atoi(v);
-    if (const char* v = getenv("LNS_DECODE_STREAMS")) e->opt_decode_streams = atoi(v);
-    if (getenv("LNS_NO_OVERLAP")) e->opt_overlap = 0;
-    if (getenv("LNS_PROP_PRIORITY")) e->opt_prop_priority = 1;
-    if (const char* v = getenv("LNS_FA_CHUNK_MB")) e->opt_fa_chunk_mb = atoi(v);
-    if (const char* v = getenv("LNS_FA_FUSED")) e->opt_fa_fused = std::min(3, std::max(0, atoi(v)));
-    if (const char* v = getenv("LNS_FA_FUSED_GPB")) e->opt_fa_fused_gpb = std::max(0, atoi(v));
-    if (getenv("LNS_NO_FOLD_LINEAR")) e->opt_fold_linear = 0;
-    if (const char* v = getenv("LNS_UP2_DUAL")) e->opt_up2_dual = atoi(v) != 0;
+    {   // the options' defaults (lns_knobs.h "option default" rows), read at every create
+        const OptionDefaults d = option_defaults();
+        e->opt_decode_group = (int)d.decode_group;
+        e->opt_decode_streams = (int)d.decode_streams;
+        e->opt_overlap = d.no_overlap ? 0 : 1;
+        e->opt_prop_priority = d.prop_priority ? 1 : 0;
+        e->opt_fa_chunk_mb = (int)d.fa_chunk_mb;
+        e->opt_fa_fused = (int)std::min(3L, std::max(0L, d.fa_fused));
+        e->opt_fa_fused_gpb = (int)std::max(0L, d.fa_fused_gpb);
+        e->opt_fold_linear = d.no_fold_linear ? 0 : 1;
+        e->opt_up2_dual = d.up2_dual != 0;
+    }
     e->cfg.ae_prefix[sizeof(e->cfg.ae_prefix) - 1] = 0;
     e->cfg.prop_prefix[sizeof(e->cfg.prop_prefix) - 1] = 0;
     try {

@@ -224,6 +224,7 @@ struct AttnArgs { const float* qkv; int B, heads, D, n; float scale; float* o;
                   const unsigned* amax_in; };   // [B][LNS_AMAX_SUB] max |qkv| per sample or null: enables the f16x2 form
 template <class F> void for_each_ptr(AttnArgs& a, F&& f) { f(a.qkv); f(a.o); f(a.amax_in); }
 LNS_ARGS_SIZE(AttnArgs, 48);
+bool attn_is_f16(const AttnArgs& a);        // the launch runs the f16x2 kernel (three products), else fp32 MFMA
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 
 // FABlock2D pieces ----------------------------------------------------------
@@ -290,6 +291,9 @@ struct FaSandwichArgs {
 };
 template <class F> void for_each_ptr(FaSandwichArgs& a, F&& f) { f(a.u); f(a.kx); f(a.ky); f(a.out); f(a.amax_u); }
 LNS_ARGS_SIZE(FaSandwichArgs, 80);
+// the kernel a launch runs (planes of 32x32, 32x64, 64x64, 64x96, 64x32 tiles); FA_SAND_NONE: no kernel for the shape
+enum FaSandwichForm { FA_SAND_NONE = 0, FA_SAND_F16X2, FA_SAND_BF16X3, FA_SAND_BF16X3_3WAVE, FA_SAND_FP32 };
+FaSandwichForm fa_sandwich_form(const FaSandwichArgs& a);
 hipError_t launch_fa_sandwich(const FaSandwichArgs& a, hipStream_t s);
 size_t fa_sandwich_lds_bytes(int H, int W);
 

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "lns_kernels.h"
+#include "lns_knobs.h"
 #include "lns_spectrum.h"
 
 namespace lns {
@@ -754,7 +755,7 @@ ConvVariantInfo conv_variant_info(int v) {
 // so a trajectory's result is bit-identical whatever batch (or GPU shard) it is computed in.
 int conv_pick_kc_log2(int ks, int stride, int kc_log2_max) {
     (void)stride;
-    static const bool k4 = getenv("LNS_CONV_KCL4") != nullptr;   // tuning knob
+    const bool k4 = knobs().conv_kcl4;   // tuning knob
     int lg = ks == 3 ? (k4 ? 2 : 3) : 4;     // preferred LDS stage depth; conv_fits() may fall back to 4 for 3x3
     return lg < kc_log2_max ? lg : kc_log2_max;
 }
@@ -2598,7 +2599,7 @@ hipError_t launch_conv_bf16x3(int variant, const ConvArgs& a, hipStream_t s) {
     }
     if (a.up2) return hipErrorInvalidValue;
     if (variant == CV_F64 && !a.w2 && a.w8 >= 0) {        // small launches: the 8-wave form (conv3_w8.inc) -- measured no faster,
-        static const long w8_below = getenv("LNS_CONV_W8_BELOW") ? atol(getenv("LNS_CONV_W8_BELOW")) : 0;      // so opt-in only
+        const long w8_below = knobs().conv_w8_below;      // so opt-in only (default 0)
         const long blocks = (long)a.tiles_x * a.tiles_y * a.cout_tiles * a.B;
         if ((a.w8 == 1 || blocks < w8_below) && convw8_fits(a)) return launch_conv_w8(a, s);
         if (a.w8 == 1) return hipErrorInvalidValue;
@@ -3431,11 +3432,13 @@ __global__ __launch_bounds__(256, 2) void attention_f_kernel(AttnArgs a) {
     }
 }
 
+// f16x2 form where the producer recorded max |qkv| per sample (a per-layer condition); LNS_ATTN_FP32 keeps fp32 MFMA.
+// Asked by launch_attention and by Planner::lower_sa (label, executed FLOP).
+bool attn_is_f16(const AttnArgs& a) { return a.amax_in != nullptr && !knobs().attn_fp32; }
+
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
     dim3 grid((a.n + 127) / 128, a.heads, a.B);
-    // f16x2 form where the producer recorded max |qkv| per sample (a per-layer condition); LNS_ATTN_FP32 keeps fp32 MFMA
-    static const bool fp32_only = getenv("LNS_ATTN_FP32") != nullptr;
-    if (a.amax_in && !fp32_only) {
+    if (attn_is_f16(a)) {
         if (a.D == 64) hipLaunchKernelGGL(attention_f_kernel<64>, grid, dim3(256), 0, s, a);
         else if (a.D == 32) hipLaunchKernelGGL(attention_f_kernel<32>, grid, dim3(256), 0, s, a);
         else return hipErrorInvalidValue;
@@ -3747,7 +3750,7 @@ hipError_t launch_fa_reducer2(const FaReducerArgs& ax, const FaReducerArgs& ay, 
 }
 
 hipError_t launch_fa_reducer(const FaReducerArgs& a, hipStream_t s) {
-    static const bool scalar_only = getenv("LNS_FA_REDUCER_SCALAR") != nullptr;   // A/B knob
+    const bool scalar_only = knobs().fa_reducer_scalar;   // A/B knob
     if (!fa_reducer_fits(a.C, a.Hid, a.Out, false)) return hipErrorInvalidValue;
     if (a.qk && !(fa_reducer_mfma_ok(a) && !scalar_only)) return hipErrorInvalidValue;   // the fused projection needs the MFMA form
     if (!scalar_only && fa_reducer_mfma_ok(a)) {
@@ -4614,81 +4617,83 @@ static size_t fa_sandwich_f_lds_bytes(int HT, int WT) {
 constexpr size_t fa_sandwich_b_lds_const(int HT, int WT, int nwv) {
     return ((size_t)3 * HT * 32 * (HT * 32 + 8) + (size_t)3 * WT * 32 * (WT * 32 + 8) + (size_t)nwv * 3 * 32 * (WT * 32 + 8)) * 2;
 }
-static size_t fa_sandwich_b_lds_bytes(int HT, int WT, int nwv = 4) {
-    const size_t HB = HT * 32, WB = WT * 32;
-    return (3 * HB * (HB + 8) + 3 * WB * (WB + 8) + (size_t)nwv * 3 * 32 * (WB + 8)) * 2;
-}
-
 size_t fa_sandwich_lds_bytes(int H, int W) {
     const int HT = (H + 31) / 32, WT = (W + 31) / 32;
     const size_t HP = HT * 32 + 1, WP = WT * 32 + 1;
     return (HT * 32 * HP + WT * 32 * WP + 4 * 32 * WP) * 4;
 }
 
+// Which kernel a plain sandwich launch runs: a function of the plane (H, W), of whether the producer recorded max |u| and of the
+// process switches -- never of the batch.  Asked by launch_fa_sandwich and by Planner::lower_fa (label, executed FLOP, refusal).
+FaSandwichForm fa_sandwich_form(const FaSandwichArgs& a) {
+    const Knobs& k = knobs();
+    const int HT = (a.H + 31) / 32, WT = (a.W + 31) / 32;
+    // the plane tilings the kernels are instantiated for: 32x32, 32x64, 64x64, 64x96, 64x32
+    if (!((HT == 1 && (WT == 1 || WT == 2)) || (HT == 2 && WT >= 1 && WT <= 3))) return FA_SAND_NONE;
+    if (!k.fa_sandwich_fp32) {
+        // f16x2 form: planes of <= 96 columns whose producer recorded max |u| per sample (a per-layer condition)
+        if (WT <= 3 && !k.fa_sandwich_bf16x3 && a.amax_u != nullptr && fa_sandwich_f_lds_bytes(HT, WT) <= 160 * 1024) return FA_SAND_F16X2;
+        // bf16x3 form whenever its LDS image fits, four waves per block.  Where four private P bands do not fit the LDS (48x96
+        // planes of the SW decoder: 167 KB) the three-wave form exists (NWV = 3, per-tile U) but measured SLOWER than the
+        // fp32-MFMA kernel (SW 96x192x5, B=64: sandwich class 82.0 vs 69.8 ms per rollout -- 46 spilled registers, three waves
+        // per CU), so LNS_FA_SANDWICH_3WAVE opts in and the default for those planes stays fp32 MFMA.
+        const int nwv = fa_sandwich_b_lds_const(HT, WT, 4) <= 160 * 1024 ? 4 : 3;
+        if ((nwv == 4 || k.fa_sandwich_3wave) && fa_sandwich_b_lds_const(HT, WT, nwv) <= 160 * 1024)
+            return nwv == 4 ? FA_SAND_BF16X3 : FA_SAND_BF16X3_3WAVE;
+    }
+    return fa_sandwich_lds_bytes(a.H, a.W) <= 160 * 1024 ? FA_SAND_FP32 : FA_SAND_NONE;
+}
+
 template <int HT, int WT>
-static hipError_t launch_fa_sandwich_t(const FaSandwichArgs& a, hipStream_t s) {
-    // bf16x3 form whenever its LDS image fits (a function of H, W only, so the choice never depends on the batch)
-    static const bool fp32_only = getenv("LNS_FA_SANDWICH_FP32") != nullptr;
-    // Four waves per block.  Where four private P bands do not fit the LDS (48x96 planes of the SW decoder: 167 KB) the
-    // three-wave form of the bf16x3 kernel exists (NWV = 3, per-tile U) but measured SLOWER than the fp32-MFMA kernel
-    // below (SW 96x192x5, B=64: sandwich class 82.0 vs 69.8 ms per rollout -- 46 spilled registers, three waves per CU),
-    // so LNS_FA_SANDWICH_3WAVE opts in and the default for those planes stays fp32 MFMA.
-    static const bool three_wave = getenv("LNS_FA_SANDWICH_3WAVE") != nullptr;
-    constexpr int NWV = fa_sandwich_b_lds_const(HT, WT, 4) <= 160 * 1024 ? 4 : 3;
+static hipError_t launch_fa_sandwich_t(const FaSandwichArgs& a, FaSandwichForm form, hipStream_t s) {
+    constexpr int NWV = fa_sandwich_b_lds_const(HT, WT, 4) <= 160 * 1024 ? 4 : 3;      // (fa_sandwich_form's nwv)
     constexpr bool UL = HT * WT >= 6;
-    // f16x2 form: planes of <= 96 columns whose producer recorded max |u| per sample (a per-layer condition)
-    static const bool no_f16 = getenv("LNS_FA_SANDWICH_BF16X3") != nullptr;
-    if constexpr (WT <= 3) {
-        if (!fp32_only && !no_f16 && a.amax_u != nullptr && fa_sandwich_f_lds_bytes(HT, WT) <= 160 * 1024) {
-            static const int ppb_max = getenv("LNS_FA_PPB") ? atoi(getenv("LNS_FA_PPB")) : 64;
-            int ppb = ppb_max;
-            while (ppb > 4 && (long)a.B * a.heads * ((a.C + ppb - 1) / ppb) < 1024) ppb >>= 1;
-            dim3 grid((a.C + ppb - 1) / ppb, a.heads, a.B);
+    const bool vec = (a.W % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.u) & 15) == 0);
+    // planes per block: the Kx/Ky staging (load + split) is paid once per block, so as many planes as still leave `want` blocks
+    // (>= 2 per CU; fp32: enough blocks to fill the chip, few enough to amortise the staging)
+    auto planes_per_block = [&](int ppb, long want) {
+        while (ppb > 4 && (long)a.B * a.heads * ((a.C + ppb - 1) / ppb) < want) ppb >>= 1;
+        return ppb;
+    };
+    const int ppb = form == FA_SAND_FP32 ? planes_per_block(16, 512) : planes_per_block((int)knobs().fa_ppb, form == FA_SAND_F16X2 ? 1024 : 512);
+    const dim3 grid((a.C + ppb - 1) / ppb, a.heads, a.B);
+    const bool full = vec && HT == WT && a.H == HT * 32 && a.W == WT * 32;       // layer-static: the shape decides, never the batch
+    switch (form) {
+        case FA_SAND_F16X2: {
             const size_t ldsf = fa_sandwich_f_lds_bytes(HT, WT);
-            const bool vec = (a.W % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.u) & 15) == 0);
             constexpr bool ULF = false;
-            if (vec && HT == WT && a.H == HT * 32 && a.W == WT * 32)
-                hipLaunchKernelGGL((fa_sandwich_f_kernel<HT, WT, true, (HT == WT), ULF>), grid, dim3(256), ldsf, s, a, ppb);
+            if (full) hipLaunchKernelGGL((fa_sandwich_f_kernel<HT, WT, true, (HT == WT), ULF>), grid, dim3(256), ldsf, s, a, ppb);
             else if (vec) hipLaunchKernelGGL((fa_sandwich_f_kernel<HT, WT, true, false, ULF>), grid, dim3(256), ldsf, s, a, ppb);
             else hipLaunchKernelGGL((fa_sandwich_f_kernel<HT, WT, false, false, ULF>), grid, dim3(256), ldsf, s, a, ppb);
             return hipGetLastError();
         }
+        case FA_SAND_BF16X3:
+        case FA_SAND_BF16X3_3WAVE: {
+            const size_t ldsb = fa_sandwich_b_lds_const(HT, WT, NWV);
+            if (full) hipLaunchKernelGGL((fa_sandwich_b_kernel<HT, WT, true, (HT == WT), NWV, UL>), grid, dim3(64 * NWV), ldsb, s, a, ppb);
+            else if (vec) hipLaunchKernelGGL((fa_sandwich_b_kernel<HT, WT, true, false, NWV, UL>), grid, dim3(64 * NWV), ldsb, s, a, ppb);
+            else hipLaunchKernelGGL((fa_sandwich_b_kernel<HT, WT, false, false, NWV, UL>), grid, dim3(64 * NWV), ldsb, s, a, ppb);
+            return hipGetLastError();
+        }
+        case FA_SAND_FP32: {
+            const size_t lds = fa_sandwich_lds_bytes(a.H, a.W);
+            if (vec) hipLaunchKernelGGL((fa_sandwich_kernel<HT, WT, true>), grid, dim3(256), lds, s, a, ppb);
+            else hipLaunchKernelGGL((fa_sandwich_kernel<HT, WT, false>), grid, dim3(256), lds, s, a, ppb);
+            return hipGetLastError();
+        }
+        default: return hipErrorInvalidValue;
     }
-    if (!fp32_only && (NWV == 4 || three_wave) && fa_sandwich_b_lds_bytes(HT, WT, NWV) <= 160 * 1024) {
-        // planes per block: the Kx/Ky staging (load + split) is paid once per block, so as many planes as still leave
-        // >= 2 blocks per CU
-        static const int ppb_max = getenv("LNS_FA_PPB") ? atoi(getenv("LNS_FA_PPB")) : 64;
-        int ppb = ppb_max;
-        while (ppb > 4 && (long)a.B * a.heads * ((a.C + ppb - 1) / ppb) < 512) ppb >>= 1;
-        dim3 grid((a.C + ppb - 1) / ppb, a.heads, a.B);
-        const size_t ldsb = fa_sandwich_b_lds_bytes(HT, WT, NWV);
-        const bool vec = (a.W % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.u) & 15) == 0);
-        if (vec && HT == WT && a.H == HT * 32 && a.W == WT * 32)       // layer-static: the shape decides, never the batch
-            hipLaunchKernelGGL((fa_sandwich_b_kernel<HT, WT, true, (HT == WT), NWV, UL>), grid, dim3(64 * NWV), ldsb, s, a, ppb);
-        else if (vec) hipLaunchKernelGGL((fa_sandwich_b_kernel<HT, WT, true, false, NWV, UL>), grid, dim3(64 * NWV), ldsb, s, a, ppb);
-        else hipLaunchKernelGGL((fa_sandwich_b_kernel<HT, WT, false, false, NWV, UL>), grid, dim3(64 * NWV), ldsb, s, a, ppb);
-        return hipGetLastError();
-    }
-    const size_t lds = fa_sandwich_lds_bytes(a.H, a.W);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    // planes per block: enough blocks to fill the chip, few enough to amortise the Kx/Ky staging
-    int ppb = 16;
-    while (ppb > 4 && (long)a.B * a.heads * ((a.C + ppb - 1) / ppb) < 512) ppb >>= 1;
-    dim3 grid((a.C + ppb - 1) / ppb, a.heads, a.B);
-    const bool vec = (a.W % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.u) & 15) == 0);
-    if (vec) hipLaunchKernelGGL((fa_sandwich_kernel<HT, WT, true>), grid, dim3(256), lds, s, a, ppb);
-    else hipLaunchKernelGGL((fa_sandwich_kernel<HT, WT, false>), grid, dim3(256), lds, s, a, ppb);
-    return hipGetLastError();
 }
 
 hipError_t launch_fa_sandwich(const FaSandwichArgs& a, hipStream_t s) {
+    const FaSandwichForm form = fa_sandwich_form(a);
     const int HT = (a.H + 31) / 32, WT = (a.W + 31) / 32;
-    if (HT == 1 && WT == 1) return launch_fa_sandwich_t<1, 1>(a, s);
-    if (HT == 1 && WT == 2) return launch_fa_sandwich_t<1, 2>(a, s);
-    if (HT == 2 && WT == 2) return launch_fa_sandwich_t<2, 2>(a, s);
-    if (HT == 2 && WT == 3) return launch_fa_sandwich_t<2, 3>(a, s);
-    if (HT == 2 && WT == 1) return launch_fa_sandwich_t<2, 1>(a, s);
-    return hipErrorInvalidValue;
+    if (form == FA_SAND_NONE) return hipErrorInvalidValue;
+    if (HT == 1 && WT == 1) return launch_fa_sandwich_t<1, 1>(a, form, s);
+    if (HT == 1 && WT == 2) return launch_fa_sandwich_t<1, 2>(a, form, s);
+    if (HT == 2 && WT == 2) return launch_fa_sandwich_t<2, 2>(a, form, s);
+    if (HT == 2 && WT == 3) return launch_fa_sandwich_t<2, 3>(a, form, s);
+    return launch_fa_sandwich_t<2, 1>(a, form, s);
 }
 
 // ===========================================================================

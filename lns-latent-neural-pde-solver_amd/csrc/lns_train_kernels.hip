@@ -9,6 +9,7 @@
 // Hand-written HIP for gfx950; no CPU fallback.
 #include <cstdlib>
 
+#include "lns_knobs.h"
 #include "lns_train_kernels.h"
 
 namespace lns {

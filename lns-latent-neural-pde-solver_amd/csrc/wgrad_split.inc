@@ -29,26 +29,17 @@ static int wgrad_patch_positions(int H, int W, int k, int dil) {
     return n <= WG_PATCH_MAX ? (int)n : 0;     // 0: tap-on-grid form
 }
 
-// Slices of a launch: a function of the launch shape only.  About WG_TARGET_BLOCKS blocks per launch, at most
-// WG_MAX_SLICES partials per element, every slice the same whole number of chunks (the last one may be shorter).  The
-// constants come from the sweep in profiles/wgrad_split_slices.txt: the step time is flat from one block per CU (256) up
-// to four; two per CU is the middle of the plateau.
-#define WG_TARGET_BLOCKS 512
-#define WG_MAX_SLICES 128
-// LNS_WGRAD_TARGET_BLOCKS / LNS_WGRAD_MAX_SLICES: tuning knobs of tools/wgrad_sweep.py, read ONCE per process (README's
-// environment list), so that within a process S stays a function of the launch shape only
-static long wgrad_env_once(const char* name, long dflt) {
-    const char* t = getenv(name);
-    const long v = t ? atol(t) : dflt;
-    return v >= 1 ? v : dflt;
-}
+// Slices of a launch: a function of the launch shape only.  About `target` blocks per launch, at most `smax` partials per
+// element, every slice the same whole number of chunks (the last one may be shorter).  The two constants (WG_TARGET_BLOCKS,
+// WG_MAX_SLICES in tools/wgrad_sweep.py's records) are the defaults of LNS_WGRAD_TARGET_BLOCKS / LNS_WGRAD_MAX_SLICES in
+// lns_knobs.h, 512 and 128, from the sweep in profiles/wgrad_split_slices.txt: the step time is flat from one block per CU (256)
+// up to four; two per CU is the middle of the plateau.  Read once per process, so that within a process S stays a function of
+// the launch shape only.
 int wgrad_split_slices(int B, int H, int W, int Cin, int Cout, int k) {
     (void)k;
-    static const long env_target = wgrad_env_once("LNS_WGRAD_TARGET_BLOCKS", WG_TARGET_BLOCKS);
-    static const long env_smax = wgrad_env_once("LNS_WGRAD_MAX_SLICES", WG_MAX_SLICES);
     const long nchunk = ((long)H * W + WG_PX - 1) / WG_PX, NC = (long)B * nchunk;
     const long tiles = (long)((Cout + 63) / 64) * ((Cin + 63) / 64);
-    const long target = env_target, smax = env_smax;
+    const long target = knobs().wgrad_target_blocks, smax = knobs().wgrad_max_slices;
     long S = (target + tiles - 1) / tiles;
     if (S > smax) S = smax;
     if (S > NC) S = NC;
